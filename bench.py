@@ -15,8 +15,15 @@ Launch: `python bench.py --gpus N` starts the N ranks itself (fresh child proces
 process touches torch or HIP); under `torch.distributed.run` (RANK set) it runs as the rank it is told.
 
 Prints ONE JSON line (rank 0) with `roofline` (HIP-event-timed hot launch vs the 8 TB/s HBM peak,
-algorithmic bytes 8N(6L+2L(L+1)) per multiply) and, at N=1, `cpu_baseline` (the CPU oracle port on host
-cores: one thread and all cores).
+algorithmic bytes 8N(6L+2L(L+1)) per multiply).  A plain run does only that: set up, warm up, time `--steps`
+steps, write the outputs (`--dump-outputs DIR`), print the line.  `--full` adds the checks and side figures that
+cost time of their own: the oracle spot check of the measured path, the 60-bit-prime and BFV default-ring side
+measurements and, at N=1, `cpu_baseline` (the CPU oracle port on host cores: one thread and all cores).
+
+`--dump-outputs DIR` writes DIR/mul_relin_out.npy: the result ciphertexts of the last timed step (all ranks' pairs,
+gathered on rank 0) for a fixed sample of pairs -- the first, the last and up to 30 others drawn with numpy's
+default_rng(0) -- as float64, shape [pairs][2][L][N] (every residue is below 2^50, so float64 holds it exactly).
+The inputs are seeded, so two builds given the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -47,13 +54,20 @@ def parse(argv=None):
     ap.add_argument("--total-batch", type=int, default=8192,
                     help="strong scaling (default): independent ciphertext pairs per step over ALL ranks")
     ap.add_argument("--batch", type=int, default=0, help="weak scaling: pairs per GPU per step (overrides --total-batch)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="bound of each cpu_baseline leg")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-60bit", action="store_true", help="skip the 60-bit-prime (integer kernel) side measurement")
-    ap.add_argument("--no-bfv", action="store_true", help="skip the BFV default-ring side measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also the oracle spot check, the 60-bit-prime and BFV side measurements and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a seeded sample of the last timed step's results to DIR/mul_relin_out.npy (float64)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: bound of each cpu_baseline leg")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-60bit", action="store_true", help="--full: skip the 60-bit-prime (integer kernel) side measurement")
+    ap.add_argument("--no-bfv", action="store_true", help="--full: skip the BFV default-ring side measurement")
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="rehearse launch + sharding + gather with gloo on the CPU (no device work, no timing claims)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -122,6 +136,22 @@ def measured_traffic(batch):
         return None, None
     except Exception:
         return None, None
+
+
+def dump_outputs(path, results):
+    """Write the sampled pairs of `results` ([pairs][2][L][N] residues on the device) to path/mul_relin_out.npy as
+    float64; returns the pair indices (see the module docstring)."""
+    import numpy as np
+    total = results.shape[0]
+    inner = np.arange(1, total - 1)
+    drawn = np.random.default_rng(0).choice(inner, min(inner.size, 30), replace=False)
+    pairs = sorted({0, total - 1} | {int(i) for i in drawn})
+    sample = results[pairs].cpu().numpy()
+    if sample.min() < 0 or sample.max() >= 2 ** 53:
+        raise SystemExit("bench: a residue does not fit float64 exactly -- outputs not written")
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "mul_relin_out.npy"), sample.astype(np.float64))
+    return pairs
 
 
 def my_share(args, rank, world):
@@ -231,6 +261,10 @@ def run_rank(args):
         gather_ms = (time.perf_counter() - tg) * 1e3
         if rank == 0:
             assert gathered.shape[0] == total
+    dumped_pairs = None
+    if rank == 0 and args.dump_outputs:
+        dumped_pairs = dump_outputs(args.dump_outputs, gathered if world > 1 else out)
+    if world > 1:
         del gathered
 
     if rank == 0:
@@ -257,17 +291,20 @@ def run_rank(args):
         }
         if gather_ms is not None:
             line["gather_ms"] = gather_ms
-        # parity spot check of the measured path against the oracle: first / chunk-boundary / last pairs
-        from oracle import oracle_py as om
-        o = om.Oracle(om.CKKS, N, primes)
-        o.keygen(0xABC00001)
-        checked = sorted({i for i in (0, 255, 256, B - 1) if 0 <= i < B})
-        for i in checked:
-            ha, hb, ho = (t[i].cpu().numpy().view(np.uint64) for t in (a, b, out))
-            if not np.array_equal(o.mul_relin(ha, hb), ho):
-                raise SystemExit("bench: GPU result of pair %d differs from the oracle -- number is invalid" % i)
-        line["checked_pairs_vs_oracle"] = checked
-        if world == 1 and not args.no_60bit:
+        if dumped_pairs is not None:
+            line["dumped_pairs"] = dumped_pairs
+        if args.full:
+            # parity spot check of the measured path against the oracle: first / chunk-boundary / last pairs
+            from oracle import oracle_py as om
+            o = om.Oracle(om.CKKS, N, primes)
+            o.keygen(0xABC00001)
+            checked = sorted({i for i in (0, 255, 256, B - 1) if 0 <= i < B})
+            for i in checked:
+                ha, hb, ho = (t[i].cpu().numpy().view(np.uint64) for t in (a, b, out))
+                if not np.array_equal(o.mul_relin(ha, hb), ho):
+                    raise SystemExit("bench: GPU result of pair %d differs from the oracle -- number is invalid" % i)
+            line["checked_pairs_vs_oracle"] = checked
+        if args.full and world == 1 and not args.no_60bit:
             # the headline chain keeps every key prime below 2^50 (fp64 butterflies); SEAL-typical 60-bit primes run the
             # integer kernels instead -- reported beside it so the precondition of `value` is visible
             del a, b, out
@@ -297,7 +334,7 @@ def run_rank(args):
                                   o6[B60 - 1].cpu().numpy().view(np.uint64)):
                 raise SystemExit("bench: 60-bit chain result differs from the oracle")
             g60.close()
-        if world == 1 and not args.no_bfv:
+        if args.full and world == 1 and not args.no_bfv:
             # the reference itself is BFV on BFVDefault(16384) with Batching(N, 20) (ref:src/runtime/SealCiphertextFactory.cpp:72-100):
             # the same operation on ITS scheme and ring, beside the CKKS headline (BEHZ multiply + relinearise, 8 data limbs)
             gb = capi.Context.bfv_default(16384, device=local_rank)
@@ -336,7 +373,7 @@ def run_rank(args):
                 raise SystemExit("bench: BFV default-ring result differs from the oracle")
             del ab, bb, ob
             gb.close()
-        if not args.no_cpu and world == 1:  # CPU leg on rank 0 at N=1 only
+        if args.full and not args.no_cpu and world == 1:  # CPU leg on rank 0 at N=1 only
             line["cpu_baseline"] = cpu_baseline(primes, args.cpu_seconds)
         print(json.dumps(line), flush=True)
     if world > 1:
