@@ -26,7 +26,8 @@ SYMBOLS = [
     "abc_hip_memcpy_d2d", "abc_hip_keygen", "abc_hip_keygen_secure", "abc_hip_encrypt_secure", "abc_hip_load_secret_key", "abc_hip_load_public_key",
     "abc_hip_load_relin_key", "abc_hip_load_galois_key", "abc_hip_get_secret_key", "abc_hip_get_public_key",
     "abc_hip_get_relin_key", "abc_hip_get_galois_key", "abc_hip_num_galois_keys", "abc_hip_galois_elt_at",
-    "abc_hip_galois_elt_from_step", "abc_hip_batch_encode", "abc_hip_batch_decode", "abc_hip_encrypt", "abc_hip_decrypt",
+    "abc_hip_galois_elt_from_step", "abc_hip_batch_encode", "abc_hip_batch_decode", "abc_hip_ckks_encode", "abc_hip_ckks_decode",
+    "abc_hip_encrypt", "abc_hip_decrypt",
     "abc_hip_add", "abc_hip_sub", "abc_hip_negate", "abc_hip_multiply", "abc_hip_relinearize", "abc_hip_mul_relin",
     "abc_hip_rotate", "abc_hip_apply_galois", "abc_hip_multiply_plain", "abc_hip_add_plain", "abc_hip_sub_plain",
     "abc_hip_rescale", "abc_hip_mod_switch", "abc_hip_ntt_forward", "abc_hip_ntt_inverse", "abc_hip_keyswitch",
@@ -355,6 +356,42 @@ class Context:
         r = self.download(out, p.shape, np.int64)
         pb.free(); out.free()
         return r if np.ndim(plain) == 2 else r[0]
+
+    def ckks_encode(self, values, scale, nl=None):
+        """CKKS slots -> NTT-form plaintext residues on the device: values real or complex, [count][<= N/2] or one row; the
+        slots beyond a row's length are zero.  Returns uint64 [count][nl][N] (or [nl][N] for one row)."""
+        v = np.asarray(values)
+        rows = v.reshape(-1, v.shape[-1]) if v.ndim else v.reshape(1, 1)
+        nl = self.L if nl is None else int(nl)
+        count, vpr = rows.shape
+        re = np.ascontiguousarray(rows.real, dtype=np.float64)
+        im = np.ascontiguousarray(rows.imag, dtype=np.float64) if np.iscomplexobj(rows) else None
+        bufs = [self.upload(re)] + ([self.upload(im)] if im is not None else [])
+        out = self.alloc(count * max(nl, 0) * self.n * 8 or 8)
+        try:
+            self.op("ckks_encode", bufs[0].ptr, bufs[1].ptr if im is not None else None, C.c_size_t(vpr), C.c_double(scale), nl,
+                    out.ptr, C.c_size_t(count))
+            r = self.download(out, (count, nl, self.n))
+        finally:
+            for b in bufs + [out]:
+                b.free()
+        return r if v.ndim == 2 else r[0]
+
+    def ckks_decode(self, plain, scale):
+        """NTT-form plaintext residues [count][nl][N] (or [nl][N]) -> complex slot values [count][N/2] (or [N/2]), divided by scale."""
+        p = np.ascontiguousarray(plain, dtype=np.uint64)
+        p3 = p if p.ndim == 3 else p[None]
+        count, nl = p3.shape[0], p3.shape[1]
+        slots = self.n // 2
+        pb = self.upload(p3)
+        re, im = self.alloc(count * slots * 8), self.alloc(count * slots * 8)
+        try:
+            self.op("ckks_decode", pb.ptr, nl, C.c_double(scale), re.ptr, im.ptr, C.c_size_t(count))
+            r = self.download(re, (count, slots), np.float64) + 1j * self.download(im, (count, slots), np.float64)
+        finally:
+            for b in (pb, re, im):
+                b.free()
+        return r if p.ndim == 3 else r[0]
 
     def encrypt(self, plain, seed=None):
         per = (self.n,) if self.scheme == BFV else (self.L, self.n)

@@ -706,6 +706,7 @@ void abc_hip_ctx_destroy(abc_hip_ctx *c) {
   (void)hipDeviceSynchronize();
   (void)hipFree(c->d_mods); (void)hipFree(c->d_tw); (void)hipFree(c->d_ftw); (void)hipFree(c->d_cst); (void)hipFree(c->d_cstf);
   (void)hipFree(c->d_slot_map);
+  (void)hipFree(c->d_ckks_codec);
   drop_key_twins(c, nullptr);
   (void)hipFree(c->d_sk); (void)hipFree(c->d_pk); (void)hipFree(c->d_relin);
   for (auto &kv : c->d_galois) (void)hipFree(kv.second);
@@ -970,6 +971,17 @@ uint32_t abc_hip_galois_elt_from_step(abc_hip_ctx *c, int step) { return c ? elt
 // ---- encode / encrypt / decrypt ----
 int abc_hip_batch_encode(abc_hip_ctx *c, const int64_t *v, uint64_t *p, size_t count) { CTX_GUARD(c); return batch_encode(c, v, p, count); }
 int abc_hip_batch_decode(abc_hip_ctx *c, const uint64_t *p, int64_t *v, size_t count) { CTX_GUARD(c); return batch_decode(c, p, v, count); }
+int abc_hip_ckks_encode(abc_hip_ctx *c, const double *re, const double *im, size_t values_per_row, double scale, int nl, uint64_t *p,
+                        size_t count) {
+  CTX_GUARD(c);
+  NOT_CAPTURABLE(c, "abc_hip_ckks_encode");
+  return ckks_encode(c, re, im, values_per_row, scale, nl, p, count);
+}
+int abc_hip_ckks_decode(abc_hip_ctx *c, const uint64_t *p, int nl, double scale, double *re, double *im, size_t count) {
+  CTX_GUARD(c);
+  NOT_CAPTURABLE(c, "abc_hip_ckks_decode");
+  return ckks_decode(c, p, nl, scale, re, im, count);
+}
 int abc_hip_encrypt(abc_hip_ctx *c, const uint64_t *p, uint64_t seed, uint64_t *ct, size_t count) { CTX_GUARD(c); NOT_CAPTURABLE(c, "abc_hip_encrypt"); return encrypt(c, p, seed, ct, count); }
 int abc_hip_encrypt_secure(abc_hip_ctx *c, const uint64_t *p, uint64_t *ct, size_t count) { CTX_GUARD(c); NOT_CAPTURABLE(c, "abc_hip_encrypt_secure"); return encrypt_secure(c, p, ct, count); }
 int abc_hip_decrypt(abc_hip_ctx *c, const uint64_t *ct, int size, int nl, uint64_t *p, size_t count) {

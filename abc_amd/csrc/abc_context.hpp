@@ -164,6 +164,7 @@ struct abc_hip_ctx {
   abc::DevConst *d_cst = nullptr;
   abc::DevConstFp *d_cstf = nullptr;
   uint32_t *d_slot_map = nullptr;
+  void *d_ckks_codec = nullptr;  // CKKS slot codec tables (twiddles, twist, slot map, CRT constants), built on first use
   // keys (device)
   uint64_t *d_sk = nullptr, *d_pk = nullptr, *d_relin = nullptr;
   std::map<uint32_t, uint64_t *> d_galois;
@@ -229,6 +230,9 @@ int ckks_multiply_plain(abc_hip_ctx *c, const u64 *ct, const u64 *plain, size_t 
 int ckks_add_plain(abc_hip_ctx *c, const u64 *ct, const u64 *plain, size_t plain_stride, u64 *out, int size, int nl, size_t count, int sub);
 int batch_encode(abc_hip_ctx *c, const int64_t *values, u64 *plain, size_t count);
 int batch_decode(abc_hip_ctx *c, const u64 *plain, int64_t *values, size_t count);
+int ckks_encode(abc_hip_ctx *c, const double *re, const double *im, size_t values_per_row, double scale, int nl, u64 *plain,
+                size_t count);  // abc_kernels_ckks_codec.hip
+int ckks_decode(abc_hip_ctx *c, const u64 *plain, int nl, double scale, double *re, double *im, size_t count);
 int encrypt(abc_hip_ctx *c, const u64 *plain, uint64_t seed, u64 *ct, size_t count);
 int decrypt(abc_hip_ctx *c, const u64 *ct, int size, int nl, u64 *plain, size_t count);
 int keygen(abc_hip_ctx *c, uint64_t seed);

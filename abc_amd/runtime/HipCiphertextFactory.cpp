@@ -17,7 +17,7 @@ HipCiphertextFactory::HipCiphertextFactory(unsigned int numElementsPerCiphertext
 
 HipCiphertextFactory::HipCiphertextFactory(const HipSchemeConfig &cfg)
     : ciphertextSlotSize(cfg.ringDegree), keySeed(cfg.seed), batch(cfg.batch), ckksMode(cfg.ckks), ckksScale(cfg.ckksScale),
-      ckksBits(cfg.ckksBits) {
+      ckksBits(cfg.ckksBits), hostCkksCodec(cfg.hostCkksCodec) {
   if (!batch) throw std::runtime_error("HipCiphertextFactory: batch size must be at least 1");
   if (ckksMode && ckksBits.size() < 2) throw std::runtime_error("HipCiphertextFactory: a CKKS chain needs a data limb and the special prime");
   setupContext(cfg.device);
@@ -169,24 +169,48 @@ std::unique_ptr<AbstractCiphertext> HipCiphertextFactory::createCiphertext(const
   return createCkksCiphertext(data);
 }
 
+uint64_t *HipCiphertextFactory::encodeCkks(const std::vector<double> &rows, size_t count, int level, double scale) const {
+  const size_t N = ciphertextSlotSize, per = (size_t)level * N;
+  void *d_plain = nullptr;
+  abcHipCheck(abc_hip_malloc(ctx, &d_plain, count * per * 8), "plaintext allocation");
+  int rc;
+  if (hostCkksCodec) {  // host encoder (floating point on one thread), forward transform on the device
+    std::vector<uint64_t> coeffs(count * per);
+    const size_t slots = N / 2;
+    for (size_t b = 0; b < count; ++b)
+      ckksEncoder.encode(std::vector<double>(rows.begin() + b * slots, rows.begin() + (b + 1) * slots), scale, level,
+                         coeffs.data() + b * per);
+    rc = abc_hip_memcpy_h2d(ctx, d_plain, coeffs.data(), coeffs.size() * 8);
+    if (!rc) rc = abc_hip_ntt_limbs(ctx, static_cast<uint64_t *>(d_plain), level, count, 0);
+  } else {  // device codec: upload the slot values only
+    void *d_vals = nullptr;
+    rc = abc_hip_malloc(ctx, &d_vals, rows.size() * 8);
+    if (!rc) rc = abc_hip_memcpy_h2d(ctx, d_vals, rows.data(), rows.size() * 8);
+    if (!rc) rc = abc_hip_ckks_encode(ctx, static_cast<const double *>(d_vals), nullptr, N / 2, scale, level,
+                                      static_cast<uint64_t *>(d_plain), count);
+    if (d_vals) abc_hip_free(ctx, d_vals);
+  }
+  if (rc) { abc_hip_free(ctx, d_plain); abcHipCheck(rc, "CKKS encode"); }
+  return static_cast<uint64_t *>(d_plain);
+}
+
 std::unique_ptr<AbstractCiphertext> HipCiphertextFactory::createCkksCiphertext(const std::vector<double> &data) const {
-  // B plaintexts [L][N]: encode on the host (floating point, off the hot path), forward transform + encryption on the device
-  const size_t N = ciphertextSlotSize, per = (size_t)limbs * N;
-  std::vector<uint64_t> coeffs(batch * per);
+  // B rows of N/2 slot values (the queued per-instance vectors, else B copies of `data`), encoded into B plaintexts [L][N]
+  std::vector<double> rows;
+  rows.reserve(batch * ciphertextSlotSize / 2);
   if (!queuedRealInputs.empty()) {
-    for (size_t b = 0; b < batch; ++b) ckksEncoder.encode(expandVector(queuedRealInputs.front()[b]), ckksScale, limbs, coeffs.data() + b * per);
+    for (size_t b = 0; b < batch; ++b) {
+      const auto e = expandVector(queuedRealInputs.front()[b]);
+      rows.insert(rows.end(), e.begin(), e.end());
+    }
     queuedRealInputs.pop_front();
   } else {
-    ckksEncoder.encode(expandVector(data), ckksScale, limbs, coeffs.data());
-    for (size_t b = 1; b < batch; ++b) std::copy(coeffs.begin(), coeffs.begin() + per, coeffs.begin() + b * per);
+    const auto e = expandVector(data);
+    for (size_t b = 0; b < batch; ++b) rows.insert(rows.end(), e.begin(), e.end());
   }
-  void *d_plain = nullptr;
-  abcHipCheck(abc_hip_malloc(ctx, &d_plain, coeffs.size() * 8), "plaintext allocation");
-  int rc = abc_hip_memcpy_h2d(ctx, d_plain, coeffs.data(), coeffs.size() * 8);
-  if (!rc) rc = abc_hip_ntt_limbs(ctx, static_cast<uint64_t *>(d_plain), limbs, batch, 0);
-  if (rc) { abc_hip_free(ctx, d_plain); abcHipCheck(rc, "CKKS encode"); }
+  uint64_t *d_plain = encodeCkks(rows, batch, limbs, ckksScale);
   auto ctxt = std::make_unique<HipCiphertext>(std::cref(*this));  // top level, default scale
-  rc = encryptInto(d_plain, ctxt->devicePtr());
+  const int rc = encryptInto(d_plain, ctxt->devicePtr());
   abc_hip_free(ctx, d_plain);
   abcHipCheck(rc, "encrypt");
   return ctxt;
@@ -199,15 +223,8 @@ const uint64_t *HipCiphertextFactory::cachedCkksPlaintext(const std::vector<doub
     abc_hip_free(ctx, ckksPlainCache.front().d_plain);
     ckksPlainCache.pop_front();
   }
-  const size_t N = ciphertextSlotSize;
-  std::vector<uint64_t> coeffs((size_t)level * N);
-  ckksEncoder.encode(expandVector(value), scale, level, coeffs.data());
-  void *d_plain = nullptr;
-  abcHipCheck(abc_hip_malloc(ctx, &d_plain, coeffs.size() * 8), "plaintext allocation");
-  int rc = abc_hip_memcpy_h2d(ctx, d_plain, coeffs.data(), coeffs.size() * 8);
-  if (!rc) rc = abc_hip_ntt_limbs(ctx, static_cast<uint64_t *>(d_plain), level, 1, 0);
-  if (rc) { abc_hip_free(ctx, d_plain); abcHipCheck(rc, "CKKS encode"); }
-  ckksPlainCache.push_back(CachedCkksPlain{value, level, scale, static_cast<uint64_t *>(d_plain)});
+  uint64_t *d_plain = encodeCkks(expandVector(value), 1, level, scale);
+  ckksPlainCache.push_back(CachedCkksPlain{value, level, scale, d_plain});
   return ckksPlainCache.back().d_plain;
 }
 
@@ -219,13 +236,28 @@ void HipCiphertextFactory::decryptCiphertextRealBatch(AbstractCiphertext &abstra
   void *d_plain = nullptr;
   abcHipCheck(abc_hip_malloc(ctx, &d_plain, bytes), "decrypt allocation");
   int rc = abc_hip_decrypt(ctx, ctxt.devicePtr(), 2, nl, static_cast<uint64_t *>(d_plain), batch);
-  if (!rc) rc = abc_hip_ntt_limbs(ctx, static_cast<uint64_t *>(d_plain), nl, batch, 1);
-  std::vector<uint64_t> coeffs(batch * per);
-  if (!rc) rc = abc_hip_memcpy_d2h(ctx, coeffs.data(), d_plain, bytes);  // synchronises: result observable on return
-  abc_hip_free(ctx, d_plain);
-  abcHipCheck(rc, "decrypt");
   out.assign(batch, {});
-  for (size_t b = 0; b < batch; ++b) ckksEncoder.decode(coeffs.data() + b * per, nl, ctxt.scale(), out[b]);
+  if (hostCkksCodec) {  // download every residue, lift and transform on the host
+    if (!rc) rc = abc_hip_ntt_limbs(ctx, static_cast<uint64_t *>(d_plain), nl, batch, 1);
+    std::vector<uint64_t> coeffs(batch * per);
+    if (!rc) rc = abc_hip_memcpy_d2h(ctx, coeffs.data(), d_plain, bytes);  // synchronises: result observable on return
+    abc_hip_free(ctx, d_plain);
+    abcHipCheck(rc, "decrypt");
+    for (size_t b = 0; b < batch; ++b) ckksEncoder.decode(coeffs.data() + b * per, nl, ctxt.scale(), out[b]);
+    return;
+  }
+  // device codec: only the B x N/2 real parts travel
+  const size_t slots = N / 2;
+  void *d_vals = nullptr;
+  if (!rc) rc = abc_hip_malloc(ctx, &d_vals, batch * slots * 8);
+  if (!rc) rc = abc_hip_ckks_decode(ctx, static_cast<const uint64_t *>(d_plain), nl, ctxt.scale(), static_cast<double *>(d_vals), nullptr,
+                                    batch);
+  std::vector<double> flat(batch * slots);
+  if (!rc) rc = abc_hip_memcpy_d2h(ctx, flat.data(), d_vals, flat.size() * 8);  // synchronises: result observable on return
+  abc_hip_free(ctx, d_plain);
+  if (d_vals) abc_hip_free(ctx, d_vals);
+  abcHipCheck(rc, "decrypt");
+  for (size_t b = 0; b < batch; ++b) out[b].assign(flat.begin() + b * slots, flat.begin() + (b + 1) * slots);
 }
 void HipCiphertextFactory::decryptCiphertextReal(AbstractCiphertext &abstractCiphertext, std::vector<double> &out) const {
   std::vector<std::vector<double>> all;

@@ -29,6 +29,8 @@ struct HipSchemeConfig {
   int device = 0;
   uint64_t seed = 0;  // 0: keys and encryption randomness from the OS-keyed generator; else the reproducible TEST spec
   size_t batch = 1;
+  // CKKS slot codec on the host (CkksEncoder.hpp) instead of the device (abc_hip_ckks_encode / _decode): for A/B runs
+  bool hostCkksCodec = false;
 };
 
 class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapable {
@@ -57,7 +59,8 @@ class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapab
   std::vector<int> ckksBits;
   std::vector<uint64_t> chain;  // the context's primes: data limbs, then the special prime
   uint64_t plainModulus = 0;    // BFV t (0 for CKKS)
-  CkksEncoder ckksEncoder;
+  CkksEncoder ckksEncoder;    // host twin of the device codec (HipSchemeConfig::hostCkksCodec)
+  bool hostCkksCodec = false;
   struct CachedCkksPlain {
     std::vector<double> values;
     int level;
@@ -70,6 +73,8 @@ class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapab
   template <typename T>
   std::vector<T> expandVector(const std::vector<T> &values) const;
   std::unique_ptr<AbstractCiphertext> createCkksCiphertext(const std::vector<double> &data) const;
+  // rows [count][N/2] of slot values -> device plaintexts [count][level][N] (NTT form); caller frees
+  uint64_t *encodeCkks(const std::vector<double> &rows, size_t count, int level, double scale) const;
   int encryptInto(const void *d_plain, uint64_t *d_ct) const;
 
  public:

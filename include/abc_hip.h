@@ -105,6 +105,19 @@ uint32_t abc_hip_galois_elt_from_step(abc_hip_ctx *ctx, int step);
 int abc_hip_batch_encode(abc_hip_ctx *ctx, const int64_t *d_values, uint64_t *d_plain, size_t count);
 /* seal::BatchEncoder::decode (SealCiphertextFactory.cpp:151) */
 int abc_hip_batch_decode(abc_hip_ctx *ctx, const uint64_t *d_plain, int64_t *d_values, size_t count);
+/* CKKS counterpart of seal::BatchEncoder::encode (SealCiphertextFactory.cpp:130; no reference CKKS implementation, see
+ * ABC_HIP_SCHEME_CKKS): d_re / d_im (d_im may be NULL = real slots) [count][values_per_row] doubles, values_per_row <= N/2,
+ * the rest of the N/2 slots zero -> d_plain [count][nl][N], NTT form (ready for abc_hip_encrypt / *_plain), limb j modulo q_j.
+ * Slot i is the evaluation at zeta^(3^i), zeta = exp(i pi / N) (the order of runtime/CkksEncoder.hpp).  Coefficients are rounded to the
+ * nearest integer; one reaching 2^62 in magnitude fails the call (non-zero status).  Reads one word back: not capturable. */
+int abc_hip_ckks_encode(abc_hip_ctx *ctx, const double *d_re, const double *d_im, size_t values_per_row, double scale,
+                        int nl, uint64_t *d_plain, size_t count);
+/* CKKS counterpart of seal::BatchEncoder::decode (SealCiphertextFactory.cpp:151; no reference CKKS implementation):
+ * d_plain [count][nl][N] NTT form (as abc_hip_decrypt writes it; not modified) -> d_re / d_im (d_im may be NULL)
+ * [count][N/2] slot values divided by scale, from the exact centred lift into (-Q/2, Q/2], Q = q_0 ... q_{nl-1}.
+ * Not capturable. */
+int abc_hip_ckks_decode(abc_hip_ctx *ctx, const uint64_t *d_plain, int nl, double scale, double *d_re, double *d_im,
+                        size_t count);
 /* seal::Encryptor::encrypt, public key (SealCiphertextFactory.cpp:12).
  * abc_hip_encrypt_secure: encryption randomness from a freshly OS-keyed ChaCha20 stream per call (never derived from a
  * key seed), wiped afterwards.  abc_hip_encrypt(seed): TEST ONLY, ciphertext i uses the reproducible stream seed+i. */

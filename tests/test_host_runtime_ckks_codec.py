@@ -1,0 +1,29 @@
+"""HipCiphertextFactory's CKKS slot codec on the device against its host twin (tests/cpp/test_hip_ckks_device_codec.cpp)."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RT = os.path.join(ROOT, "abc_amd", "runtime")
+DRIVER = os.path.join(RT, "test_hip_ckks_device_codec")
+
+
+@pytest.fixture(scope="module")
+def built():
+    from abc_amd import capi
+    assert os.path.exists(capi.LIB_PATH), "libabc_hip.so missing: python -m abc_amd.build"
+    subprocess.check_call(["make", "-C", RT, "test_hip_ckks_device_codec"], stdout=subprocess.DEVNULL)
+    return DRIVER
+
+
+def test_device_codec_driver_builds(built):
+    assert os.access(built, os.X_OK)
+
+
+@pytest.mark.gpu
+def test_device_and_host_ckks_codec_behind_the_plugin_surface(built):
+    p = subprocess.run([built], capture_output=True, text=True, timeout=600)
+    print(p.stdout[-3000:])
+    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-2000:]
+    assert " 0 failed" in p.stdout

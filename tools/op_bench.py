@@ -48,6 +48,31 @@ def main():
         print("%-40s %8.3f ms / %d  -> %10.0f op/s" % (k, ms, B, B / ms * 1e3), flush=True)
     del a, b, out
     g.close()
+    # ---- CKKS slot codec (abc_hip_ckks_encode / _decode), batch 256; bytes = the minimum HBM traffic of the sequence ----
+    hbm = 8e12  # MI355X HBM3E peak, bytes/s
+    for n, bits in ((16384, [50, 40, 40, 40, 50]), (65536, [60] + [50] * 7 + [60])):
+        g = capi.Context(capi.CKKS, n, capi.create_primes(n, bits))
+        nl, B, slots = len(bits) - 1, 256, n // 2
+        vals = g.upload(rng.uniform(-1, 1, (B, slots)))
+        plain, re, im = g.alloc(B * nl * n * 8), g.alloc(B * slots * 8), g.alloc(B * slots * 8)
+        cb = C.c_size_t(B)
+        words = nl * n * 8
+        for name, fn, nbytes in (
+            # encode: slot values in, residues out, forward NTT reads and writes them again
+            ("ckks%d_encode_L%d" % (n.bit_length() - 1, nl),
+             lambda: g.op("ckks_encode", vals.ptr, None, C.c_size_t(slots), C.c_double(2.0 ** 40), nl, plain.ptr, cb),
+             slots * 8 + 3 * words),
+            # decode: copy to scratch (read + write), inverse NTT (read + write), lift (read), real + imaginary slots out
+            ("ckks%d_decode_L%d" % (n.bit_length() - 1, nl),
+             lambda: g.op("ckks_decode", plain.ptr, nl, C.c_double(2.0 ** 40), re.ptr, im.ptr, cb),
+             5 * words + 2 * slots * 8)):
+            ms = timeit(g, fn)
+            gbs = B * nbytes / ms * 1e-6
+            res[name] = {"batch": B, "ms": ms, "ops_per_s": B / ms * 1e3, "GB_per_s": gbs, "hbm_fraction": gbs * 1e9 / hbm}
+            print("%-40s %8.3f ms / %d  -> %10.0f op/s  %7.0f GB/s (%.0f %% of HBM)" % (name, ms, B, B / ms * 1e3, gbs, 100 * gbs * 1e9 / hbm),
+                  flush=True)
+        del vals, plain, re, im
+        g.close()
     # ---- BFV N=2^12 (config 2) and BFVDefault(16384) ----
     for n, B in ((4096, 1024), (16384, 256)):
         g = capi.Context.bfv_default(n)

@@ -42,6 +42,9 @@ class Phases:
         return r
 
 
+HOST_CODEC = False  # --host-codec: the numpy encoder / decoder (abc_amd/ckks_encoder.py) instead of the device codec
+
+
 class Ckks:
     """Thin helper: batched CKKS ciphertext handles on one device."""
 
@@ -57,21 +60,33 @@ class Ckks:
         self.L = self.g.L
 
     def encrypt(self, vectors, scale, seed):
-        from abc_amd import ckks_encoder
-        pl = np.stack([ckks_encoder.encode(v, scale, self.n, self.primes[: self.L]) for v in vectors])
-        buf = self.g.upload(pl)
-        self.g.op("ntt_limbs", buf.ptr, self.L, C.c_size_t(len(vectors)), 0)
+        if HOST_CODEC:
+            from abc_amd import ckks_encoder
+            pl = np.stack([ckks_encoder.encode(v, scale, self.n, self.primes[: self.L]) for v in vectors])
+            buf = self.g.upload(pl)
+            self.g.op("ntt_limbs", buf.ptr, self.L, C.c_size_t(len(vectors)), 0)
+        else:  # abc_hip_ckks_encode: only the slot values travel
+            vals = self.g.upload(np.ascontiguousarray(vectors, dtype=np.float64))
+            buf = self.g.alloc(len(vectors) * self.L * self.n * 8)
+            self.g.op("ckks_encode", vals.ptr, None, C.c_size_t(len(vectors[0])), C.c_double(scale), self.L, buf.ptr,
+                      C.c_size_t(len(vectors)))
         ct = self.g.alloc(len(vectors) * 2 * self.L * self.n * 8)
         self.g.op("encrypt", buf.ptr, C.c_uint64(seed), ct.ptr, C.c_size_t(len(vectors)))
         return ct
 
     def decrypt(self, ct, count, nl, scale):
-        from abc_amd import ckks_encoder
         pl = self.g.alloc(count * nl * self.n * 8)
         self.g.op("decrypt", ct.ptr, 2, nl, pl.ptr, C.c_size_t(count))
-        self.g.op("ntt_limbs", pl.ptr, nl, C.c_size_t(count), 1)
-        res = self.g.download(pl, (count, nl, self.n))
-        return [ckks_encoder.decode(r, scale, self.n, self.primes) for r in res]
+        if HOST_CODEC:
+            from abc_amd import ckks_encoder
+            self.g.op("ntt_limbs", pl.ptr, nl, C.c_size_t(count), 1)
+            res = self.g.download(pl, (count, nl, self.n))
+            return [ckks_encoder.decode(r, scale, self.n, self.primes) for r in res]
+        # abc_hip_ckks_decode: only count x N/2 slot values travel back
+        re, im = self.g.alloc(count * self.n // 2 * 8), self.g.alloc(count * self.n // 2 * 8)
+        self.g.op("ckks_decode", pl.ptr, nl, C.c_double(scale), re.ptr, im.ptr, C.c_size_t(count))
+        shp = (count, self.n // 2)
+        return list(self.g.download(re, shp, np.float64) + 1j * self.g.download(im, shp, np.float64))
 
 
 GRAPH = {}  # config -> seconds of one recorded-circuit replay (abc_hip_graph_*: the whole circuit as ONE launch)
@@ -293,7 +308,10 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="independent circuits in total (default: per-config, per GPU)")
     ap.add_argument("--gpus", type=int, default=1, help="start this many ranks (one per GPU) from this script itself")
     ap.add_argument("--dry-run-cpu", action="store_true", help="rehearse launch + sharding + gather with gloo on the CPU")
+    ap.add_argument("--host-codec", action="store_true", help="CKKS configs: encode / decode in numpy instead of on the device")
     args = ap.parse_args()
+    global HOST_CODEC
+    HOST_CODEC = args.host_codec
     if args.gpus > 1 and "RANK" not in os.environ:
         # nothing above this line has imported torch or touched HIP: the ranks are fresh processes (abc_amd/launcher.py)
         from abc_amd.launcher import launch_ranks
