@@ -169,6 +169,10 @@ class Context:
     def reload_env(self):
         _chk(lib().abc_hip_ctx_reload_env(self.h))
 
+    def held_buffers(self):
+        """device buffers (scratch arenas, replaced keys) held back for live recorded circuits; -1 from a library without the count"""
+        return int(lib().abc_hip_ctx_info(self.h, 6))
+
     def set_stream(self, stream_ptr):
         _chk(lib().abc_hip_set_stream(self.h, C.c_void_p(stream_ptr)))
 

@@ -89,18 +89,31 @@ static hipError_t malloc_retry(abc_hip_ctx *c, void **p, size_t bytes) {
   return hipMalloc(p, bytes);
 }
 
+void retire_buffer(abc_hip_ctx *c, void *p, uint64_t born) {
+  if (!p) return;
+  abc_hip_ctx::Held h{p, {}};
+  for (auto &kv : c->live_graphs)
+    if (kv.second > born) h.graphs.push_back(kv.first);  // ended after p was allocated: may have baked it in
+  if (h.graphs.empty()) {
+    (void)hipFree(p);
+    return;
+  }
+  c->held.push_back(std::move(h));
+}
+
 int ensure_workspace(abc_hip_ctx *c, size_t bytes) {
   if (bytes <= c->ws_bytes) return 0;
   if (capturing(c)) { set_error("scratch would grow during graph capture: run the sequence once eagerly first"); return 1; }
   if (c->ws) {
     ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
-    (void)hipFree(c->ws);
+    retire_buffer(c, c->ws, c->ws_born);
     c->ws = nullptr;
     c->ws_bytes = 0;
   }
   size_t want = bytes + bytes / 8;
   ABC_HIP_CHECK(malloc_retry(c, &c->ws, want));
   c->ws_bytes = want;
+  c->ws_born = c->graph_seq;
   return 0;
 }
 
@@ -109,12 +122,13 @@ int ensure_aux(abc_hip_ctx *c, int which, size_t bytes) {
   if (capturing(c)) { set_error("scratch would grow during graph capture: run the sequence once eagerly first"); return 1; }
   if (c->aux[which]) {
     ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
-    (void)hipFree(c->aux[which]);
+    retire_buffer(c, c->aux[which], c->aux_born[which]);
     c->aux[which] = nullptr;
     c->aux_bytes[which] = 0;
   }
   ABC_HIP_CHECK(malloc_retry(c, &c->aux[which], bytes));
   c->aux_bytes[which] = bytes;
+  c->aux_born[which] = c->graph_seq;
   return 0;
 }
 
@@ -712,6 +726,7 @@ void abc_hip_ctx_destroy(abc_hip_ctx *c) {
   for (auto &kv : c->d_galois) (void)hipFree(kv.second);
   (void)hipFree(c->ws);
   for (void *p : c->aux) (void)hipFree(p);
+  for (auto &h : c->held) (void)hipFree(h.p);
   // every block abc_hip_malloc ever handed out and that was not returned to the driver: cached ones and ones the caller
   // still holds (a caller that frees after destroying the context would otherwise leak them)
   for (auto &kv : c->block_size) (void)hipFree(kv.first);
@@ -735,6 +750,7 @@ int abc_hip_ctx_info(const abc_hip_ctx *c, int what) {
     case 3: return c->L;
     case 4: return c->device;
     case 5: return c->nBsk;
+    case 6: return (int)c->held.size();
     default: return -1;
   }
 }
@@ -926,11 +942,17 @@ int abc_hip_keygen_secure(abc_hip_ctx *c) {
     return 1;
   }
 }
+// A key is rewritten in place, and so are its mirrors: a recorded circuit keeps the addresses it baked in and reads the new key on
+// its next replay.  Work already enqueued (a replay among it) finishes on the old words first: the stream is non-blocking, so the
+// synchronous copy below would not wait for it.
 static int load_key(abc_hip_ctx *c, uint64_t **slot, const uint64_t *h, size_t words) {
   NOT_CAPTURABLE(c, "key upload");
-  if (*slot) drop_key_twins(c, *slot);  // the mirror of the words about to be overwritten
-  if (!*slot) ABC_HIP_CHECK(hipMalloc(slot, words * 8));
+  ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
+  const bool fresh = !*slot;
+  if (fresh) ABC_HIP_CHECK(hipMalloc(slot, words * 8));
   ABC_HIP_CHECK(hipMemcpy(*slot, h, words * 8, hipMemcpyHostToDevice));
+  if (!fresh) refresh_key_twins(c, *slot);
+  ABC_HIP_CHECK(hipGetLastError());
   return 0;
 }
 int abc_hip_load_secret_key(abc_hip_ctx *c, const uint64_t *h) { CTX_GUARD(c); return load_key(c, &c->d_sk, h, (size_t)c->K * c->n); }
@@ -1176,6 +1198,7 @@ int abc_hip_graph_end(abc_hip_ctx *c, void **out) {
     return 1;
   }
   settle_capture(c, (void *)exec);
+  c->live_graphs[(void *)exec] = ++c->graph_seq;
   *out = exec;
   return 0;
 }
@@ -1194,6 +1217,20 @@ int abc_hip_graph_destroy(abc_hip_ctx *c, void *exec) {
     for (void *o : kv.second)
       if (o == exec) mine.push_back(kv.first);
   for (void *p : mine) pin_drop(c, p, exec);  // unpin; what the caller had already freed goes back to the cache now
+  // scratch arenas and keys held back for this graph: freed once no live graph may read them (the stream is drained above)
+  c->live_graphs.erase(exec);
+  std::vector<abc_hip_ctx::Held> keep;
+  for (auto &h : c->held) {
+    for (size_t i = 0; i < h.graphs.size(); i++)
+      if (h.graphs[i] == exec) {
+        h.graphs[i] = h.graphs.back();
+        h.graphs.pop_back();
+        break;
+      }
+    if (h.graphs.empty()) (void)hipFree(h.p);
+    else keep.push_back(std::move(h));
+  }
+  c->held.swap(keep);
   return 0;
 }
 

@@ -168,8 +168,8 @@ struct abc_hip_ctx {
   // keys (device)
   uint64_t *d_sk = nullptr, *d_pk = nullptr, *d_relin = nullptr;
   std::map<uint32_t, uint64_t *> d_galois;
-  // fp64 twins of key-switching keys (centred doubles, same layout), built on first use by the fp64 split kernels, dropped when the
-  // key they mirror is rewritten (abc_kernels_fused.hip, key_twin)
+  // fp64 twins of key-switching keys (centred doubles, same layout), built on first use by the fp64 split kernels, rebuilt in place
+  // when the key they mirror is rewritten (abc_kernels_fused.hip, key_twin / refresh_key_twins)
   std::unordered_map<const uint64_t *, double *> key_twins;
   std::unordered_map<const uint64_t *, uint64_t *> key_shoups;  // Shoup quotients of a key (abc_kernels_eval.hip, key_shoup)
   std::vector<uint32_t> galois_order;
@@ -179,6 +179,19 @@ struct abc_hip_ctx {
   size_t ws_bytes = 0;
   void *aux[3] = {nullptr, nullptr, nullptr};
   size_t aux_bytes[3] = {0, 0, 0};
+  // Recorded circuits alive (abc_hip_graph_end .. abc_hip_graph_destroy) and the device buffers held back for them.  A graph
+  // bakes the arenas, keys and key mirrors it used into its kernel arguments; an arena that grows, or a key that goes, while a
+  // graph that may have recorded it is alive is moved to `held` instead of being freed, and freed when the last of those graphs is
+  // destroyed (retire_buffer).  graph_seq numbers the captures; an arena is stamped with the number current when it was
+  // allocated, so only the graphs that ended after that can hold it.
+  uint64_t graph_seq = 0;
+  std::unordered_map<void *, uint64_t> live_graphs;  // exec -> its capture number
+  struct Held {
+    void *p;
+    std::vector<void *> graphs;
+  };
+  std::vector<Held> held;
+  uint64_t ws_born = 0, aux_born[3] = {0, 0, 0};
   size_t limb_words() const { return (size_t)n; }
   size_t key_words() const { return (size_t)L * 2 * K * n; }
 };
@@ -198,6 +211,9 @@ void set_error(const std::string &msg);
 // workspace: grows on demand (never inside a timed region after warm-up)
 int ensure_workspace(abc_hip_ctx *c, size_t bytes);
 int ensure_aux(abc_hip_ctx *c, int which, size_t bytes);
+// free device buffer p (stamped `born`, see abc_hip_ctx::graph_seq), or hold it back while a live graph may reference it; the
+// caller has drained c->stream
+void retire_buffer(abc_hip_ctx *c, void *p, uint64_t born);
 void read_switches(abc_hip_ctx *c);
 
 // ---- launchers implemented in the kernel translation units ----
@@ -274,6 +290,12 @@ int bsplit_back13(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const doubl
 const double *key_twin(abc_hip_ctx *c, const u64 *key);
 const double *key_twin_lookup(const abc_hip_ctx *c, const u64 *key);  // never builds: safe once the lanes have forked
 void drop_key_twins(abc_hip_ctx *c, const u64 *key /* nullptr: all */);
+// rewrite the existing mirrors (fp64 twin, Shoup quotients) of `key` (nullptr: of every key) from its current words, in the same
+// buffers, on c->stream: a recorded circuit keeps their addresses and reads the new key
+void refresh_key_twins(abc_hip_ctx *c, const u64 *key /* nullptr: all */);
+void refresh_key_shoups(abc_hip_ctx *c, const u64 *key /* nullptr: all */);  // abc_kernels_eval.hip
+// a key-switching key that goes (keygen drops a non-default Galois element): the key and its mirrors are retired
+void release_key(abc_hip_ctx *c, u64 *key);
 // internal lanes (streams forked off the context's stream): chunks of one call alternate over them (abc_kernels_fused.hip)
 int fork_lanes(abc_hip_ctx *c, int lanes);
 int join_lanes(abc_hip_ctx *c, int lanes);

@@ -240,7 +240,7 @@ __global__ __launch_bounds__(256) void k_iks_pass0(DevCtx c, const u64 *__restri
 
 // Shoup quotients of a key-switching key, floor(w 2^64 / q) per word, same layout: with them a term of the inner product is one
 // lazy Shoup product of ANY 64-bit transform output (no canonicalisation, no 128-bit product, no Barrett): built on first use,
-// dropped with the key's other mirror (drop_key_twins).
+// rebuilt in place with the key's other mirror when the key is rewritten (refresh_key_twins).
 __global__ __launch_bounds__(256) void k_key_to_shoup(DevCtx c, const u64 *__restrict__ key, u64 *__restrict__ ks, size_t words) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += stride) {
@@ -267,6 +267,12 @@ static const u64 *key_shoup(abc_hip_ctx *c, const u64 *key) {
   hipLaunchKernelGGL(k_key_to_shoup, dim3(grid_for(words, 256)), dim3(256), 0, c->stream, c->dc, key, d, words);
   c->key_shoups[key] = d;
   return d;
+}
+void refresh_key_shoups(abc_hip_ctx *c, const u64 *key) {
+  const size_t words = c->key_words();
+  for (auto &kv : c->key_shoups)
+    if (!key || kv.first == key)
+      hipLaunchKernelGGL(k_key_to_shoup, dim3(grid_for(words, 256)), dim3(256), 0, c->stream, c->dc, kv.first, kv.second, words);
 }
 
 // INV_D: the data limbs' sums go back to coefficients too (BFV); CKKS keeps them in NTT form.  SHOUP: `keys` = the key's Shoup

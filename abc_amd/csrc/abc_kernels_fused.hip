@@ -308,6 +308,24 @@ void drop_key_twins(abc_hip_ctx *c, const u64 *key) {
   drop(c->key_twins);
   drop(c->key_shoups);
 }
+void refresh_key_twins(abc_hip_ctx *c, const u64 *key) {
+  const size_t words = c->key_words();
+  for (auto &kv : c->key_twins)  // whatever the switches say now: a recorded circuit may read the twin
+    if (!key || kv.first == key)
+      hipLaunchKernelGGL(k_key_to_fp, dim3(stream_grid(words, 256)), dim3(256), 0, c->stream, c->dc, kv.first, kv.second, words);
+  refresh_key_shoups(c, key);
+}
+void release_key(abc_hip_ctx *c, u64 *key) {
+  auto take = [&](auto &map) {
+    auto it = map.find(key);
+    if (it == map.end()) return;
+    retire_buffer(c, it->second, 0);
+    map.erase(it);
+  };
+  take(c->key_twins);
+  take(c->key_shoups);
+  retire_buffer(c, key, 0);
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // fp64 twins of the transform kernels above, taken when every key prime is below 2^50 (abc_ntt.hpp, "fp64 residue

@@ -278,16 +278,17 @@ static int keygen_with(abc_hip_ctx *c, P &pub, S &sec) {
   // public key = one symmetric encryption of zero at key level
   if (!c->d_pk) ABC_HIP_CHECK(hipMalloc(&c->d_pk, (size_t)2 * K * N * 8));
   if (make_kskey(c, pub, sec, nullptr, c->d_pk, h_a, h_e, d_a, d_e8, d_e, 1)) return 1;
-  // relinearisation key: switches s^2 -> s
-  drop_key_twins(c, nullptr);  // every key-switching key is about to be regenerated
+  // relinearisation key: switches s^2 -> s.  Every key-switching key is regenerated into the buffer it already has, and its
+  // mirrors are rebuilt in place at the end: a recorded circuit keeps the addresses it baked in (include/abc_hip.h, graphs).
   if (!c->d_relin) ABC_HIP_CHECK(hipMalloc(&c->d_relin, c->key_words() * 8));
   hipLaunchKernelGGL(k_dyadic_mul, dim3(grid_for((size_t)K * N, 256)), dim3(256), 0, c->stream, c->dc, c->d_sk, c->d_sk,
                      (size_t)0, d_newkey, kmap, K, (size_t)1);
   ABC_HIP_CHECK(hipGetLastError());
   if (make_kskey(c, pub, sec, d_newkey, c->d_relin, h_a, h_e, d_a, d_e8, d_e, L)) return 1;
-  // Galois keys for the default element set (GaloisTool::get_elts_all): 2N-1, then 3^(2^i), 3^-(2^i)
-  for (auto &kv : c->d_galois) (void)hipFree(kv.second);
-  c->d_galois.clear();
+  // Galois keys for the default element set (GaloisTool::get_elts_all): 2N-1, then 3^(2^i), 3^-(2^i); an element the caller had
+  // loaded outside that set goes
+  std::map<uint32_t, uint64_t *> old_galois;
+  old_galois.swap(c->d_galois);
   c->galois_order.clear();
   const uint64_t m = 2 * (uint64_t)N;
   std::vector<uint32_t> elts;
@@ -300,7 +301,13 @@ static int keygen_with(abc_hip_ctx *c, P &pub, S &sec) {
   for (uint32_t elt : elts) {
     if (c->d_galois.count(elt)) continue;  // 3^(N/4) = 3^-(N/4) mod 2N is listed twice: first key wins
     u64 *d_key = nullptr;
-    ABC_HIP_CHECK(hipMalloc(&d_key, c->key_words() * 8));
+    auto reuse = old_galois.find(elt);
+    if (reuse != old_galois.end()) {
+      d_key = reuse->second;
+      old_galois.erase(reuse);
+    } else {
+      ABC_HIP_CHECK(hipMalloc(&d_key, c->key_words() * 8));
+    }
     if (launch_galois(c, c->d_sk, d_newkey, K, 1, elt, true)) return 1;
     if (make_kskey(c, pub, sec, d_newkey, d_key, h_a, h_e, d_a, d_e8, d_e, L)) return 1;
     c->d_galois[elt] = d_key;
@@ -311,6 +318,9 @@ static int keygen_with(abc_hip_ctx *c, P &pub, S &sec) {
   (void)hipMemsetAsync(d_e8, 0, (size_t)L * N, c->stream);
   (void)hipMemsetAsync(d_newkey, 0, (size_t)K * N * 8, c->stream);
   ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
+  for (auto &kv : old_galois) release_key(c, kv.second);  // held back while a live graph may read it
+  refresh_key_twins(c, nullptr);
+  ABC_HIP_CHECK(hipGetLastError());
   explicit_bzero(h_e.data(), h_e.size());
   (void)hipFree(d_a); (void)hipFree(d_e); (void)hipFree(d_e8); (void)hipFree(d_newkey);
   return 0;

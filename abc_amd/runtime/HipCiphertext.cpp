@@ -104,13 +104,14 @@ void HipCiphertext::rescaleIfPossible() {
   buf = std::move(t);
   --nl;
 }
-void HipCiphertext::checkScales(double a, double b) {
-  // after a rescale the scale is Delta^2 / q_l, a hair off Delta for a 40-bit prime next to Delta = 2^40 (relative 1e-7 .. 1e-6
-  // for the first NTT primes below a power of two): adding such values is what every CKKS program does (SEAL makes the user
-  // overwrite the scale; here the left operand's scale stands).  Anything coarser is a real mismatch.  Written so that a NaN or
-  // a non-positive scale fails too.
+void HipCiphertext::checkScales(double a, double b) const {
+  // after a rescale the scale is Delta^2 / q_l, a hair off Delta for a 40-bit prime next to Delta = 2^40, and that drift doubles
+  // with every further squaring: adding values from different depths is what every CKKS program does (SEAL makes the user
+  // overwrite the scale; here the left operand's scale stands).  The factory derives the bound from its chain
+  // (HipCiphertextFactory::scaleTolerance); anything coarser is a real mismatch.  Written so that a NaN or a non-positive scale
+  // fails too.
   const double rel = std::fabs(a - b) / std::fmax(std::fabs(a), std::fabs(b));
-  if (!(a > 0.0) || !(b > 0.0) || !(rel <= 1e-5))
+  if (!(a > 0.0) || !(b > 0.0) || !(rel <= getFactory().scaleTolerance()))
     throw std::runtime_error("CKKS: scale mismatch between operands (" + std::to_string(a) + " vs " + std::to_string(b) + ")");
 }
 // a product's scale must leave room under the modulus of its level, or the message wraps around silently (SEAL throws

@@ -1,5 +1,6 @@
 #include "HipCiphertextFactory.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <sstream>
 
@@ -78,6 +79,17 @@ void HipCiphertextFactory::setupContext(int device) {
   chain.assign(primes, primes + count);
   plainModulus = t;
   if (ckksMode) ckksEncoder = CkksEncoder(ciphertextSlotSize, std::vector<uint64_t>(primes, primes + limbs));
+  if (ckksMode) {
+    // A rescale by q_j turns scale s into s^2 / q_j: relative error e -> 2e + eps_j with eps_j = (Delta - q_j) / Delta, so after
+    // d rescales |e| <= (2^d - 1) max_j |eps_j| over the primes a rescale can divide by (q_1 .. q_{L-1}; q_0 never goes).  Two
+    // addends may drift in opposite directions: twice that.  Floor 1e-5 (the fixed bound this check had before), cap 1e-3 (a
+    // chain whose primes sit far from Delta has no meaningful scale tracking); Delta against 2 Delta, or any other real
+    // mismatch, stays far outside either.
+    double eps = 0.0;
+    for (int j = 1; j < limbs; ++j) eps = std::fmax(eps, std::fabs((double)chain[j] - ckksScale) / ckksScale);
+    const double drift = 2.0 * (std::ldexp(1.0, std::max(limbs - 1, 0)) - 1.0) * eps;
+    ckksScaleTol = std::fmin(std::fmax(drift, 1e-5), 1e-3);
+  }
   // fresh keys per factory, like seal::KeyGenerator: OS-keyed ChaCha20 unless a TEST seed asks for the reproducible spec
   if (keySeed) abcHipCheck(abc_hip_keygen(ctx, keySeed), "key generation");
   else abcHipCheck(abc_hip_keygen_secure(ctx), "key generation");

@@ -56,6 +56,7 @@ class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapab
   // CKKS policy (empty / unused for BFV)
   bool ckksMode = false;
   double ckksScale = 0;
+  double ckksScaleTol = 0;  // relative scale difference additions accept (setupContext: from the chain)
   std::vector<int> ckksBits;
   std::vector<uint64_t> chain;  // the context's primes: data limbs, then the special prime
   uint64_t plainModulus = 0;    // BFV t (0 for CKKS)
@@ -93,6 +94,8 @@ class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapab
   [[nodiscard]] size_t ciphertextWords(int level) const { return batch * 2 * (size_t)level * ciphertextSlotSize; }
   [[nodiscard]] bool isCkks() const { return ckksMode; }
   [[nodiscard]] double defaultScale() const { return ckksScale; }
+  // CKKS: largest relative difference between the scales of two addends that is drift, not a mismatch
+  [[nodiscard]] double scaleTolerance() const { return ckksScaleTol; }
   [[nodiscard]] uint64_t prime(int j) const { return chain[j]; }
   // slots a value may fill: N for BFV (two rows of N/2), N/2 for CKKS (one row; rotateRows rotates it cyclically)
   [[nodiscard]] unsigned int usableSlots() const { return ckksMode ? ciphertextSlotSize / 2 : ciphertextSlotSize; }

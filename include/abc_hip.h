@@ -49,7 +49,9 @@ int abc_hip_default_bfv_primes(size_t n, uint64_t *h_out);
 uint64_t abc_hip_plain_modulus_batching(size_t n, int bits);
 /* seal::CoeffModulus::Create(N, bit_sizes) ordering, for CKKS chains */
 int abc_hip_create_primes(size_t n, const int *bit_sizes, int count, uint64_t *h_out);
-int abc_hip_ctx_info(const abc_hip_ctx *ctx, int what); /* 0 scheme, 1 logn, 2 nprimes, 3 L, 4 device */
+/* 0 scheme, 1 logn, 2 nprimes, 3 L, 4 device, 5 BEHZ Bsk size, 6 device buffers held back for live graphs (scratch arenas
+ * and keys that were replaced while a graph that may have recorded them was alive); -1 for an unknown `what` */
+int abc_hip_ctx_info(const abc_hip_ctx *ctx, int what);
 /* Every operation of the context is enqueued on `hip_stream` from now on.  NULL does NOT mean HIP's legacy default
  * stream: it selects the context's own private non-blocking stream again (the state after abc_hip_ctx_create), which is
  * not ordered against anything else -- a caller that produces inputs on another stream (e.g. torch's current stream, whose
@@ -170,7 +172,12 @@ int abc_hip_mod_switch(abc_hip_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, 
  * someone else; a block pinned by several graphs returns to the cache when the last of them is destroyed.  Memory that did not
  * come from abc_hip_malloc is the caller's to keep alive.  A buffer that existed before the capture
  * and is freed inside it is an INPUT of the circuit: it keeps its address and contents are the caller's to refresh before a
- * replay (HipCiphertextFactory::rewriteCiphertext). */
+ * replay (HipCiphertextFactory::rewriteCiphertext).
+ * Context state: scratch arenas, keys and key mirrors (fp64 twins, Shoup quotients) outlive every graph that may have recorded
+ * them.  An eager call after abc_hip_graph_end may grow an arena: the old one is held back until the last graph that may read it
+ * is destroyed (abc_hip_ctx_info 6 counts what is held).  A replay uses the keys that are current when it is LAUNCHED:
+ * abc_hip_load_*_key and abc_hip_keygen wait for enqueued work, then rewrite each key and its mirrors in place; a Galois key
+ * that keygen drops (an element outside the default set) is held back like an arena. */
 int abc_hip_graph_begin(abc_hip_ctx *ctx);
 int abc_hip_graph_end(abc_hip_ctx *ctx, void **graph_exec_out);
 int abc_hip_graph_launch(abc_hip_ctx *ctx, void *graph_exec);

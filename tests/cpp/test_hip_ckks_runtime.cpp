@@ -249,6 +249,67 @@ int main(int argc, char **argv) {
     f.decryptCiphertext(res, ints);
     EXPECT_TRUE(ints[0] == (int64_t)std::llrint(dots[0]));
   });
+  // ---- config 3, recorded: x^8 + x as a squaring tree on the default chain (three rescales: x^8's scale has drifted ~1.6e-5
+  //      from x's, which the addition must accept), B = 2; between compile and replay an eager device decode grows the
+  //      workspace the recording baked in, which must be held back for it ----
+  t.run("config 3: recorded x^8 + x, replayed on new inputs after the device codec grew the scratch", [&] {
+    HipSchemeConfig cfg;
+    cfg.ckks = true;
+    cfg.ringDegree = 16384;
+    cfg.seed = seed;
+    cfg.batch = 2;
+    HipCiphertextFactory f(cfg);
+    const size_t slots = 8192;
+    std::mt19937 rng(17);
+    std::uniform_int_distribution<int> dist(-2, 2);  // x^8 Delta <= 2^48: far below q_0 / 2 at the last level
+    auto draw = [&] {
+      std::vector<std::vector<int64_t>> xs(2, std::vector<int64_t>(slots));
+      for (auto &v : xs)
+        for (auto &x : v) x = dist(rng);
+      return xs;
+    };
+    const auto x1 = draw();
+    f.queueBatchedInput(x1);
+    CircuitRuntime rt(f, "secret int x = {0};");
+    rt.compile("secret int x2 = x *** x;\nsecret int x4 = x2 *** x2;\nsecret int x8 = x4 *** x4;\nsecret int y = x8 +++ x;\n");
+    auto verify = [&](const std::vector<std::vector<int64_t>> &xs, const char *what) {
+      auto out = rt.getOutput("o = y;");
+      auto &res = *dynamic_cast<AbstractCiphertext *>(out[0].second.get());
+      EXPECT_TRUE(hip(res).level() == 1);
+      std::vector<std::vector<double>> dec;
+      f.decryptCiphertextRealBatch(res, dec);  // device codec
+      for (int b = 0; b < 2; ++b)
+        for (size_t i = 0; i < slots; ++i) {
+          const double x = (double)xs[b][i], want = std::pow(x, 8) + x;
+          if (!(std::fabs(dec[b][i] - want) <= 1e-3))
+            throw std::runtime_error(std::string(what) + ": instance " + std::to_string(b) + " slot " + std::to_string(i) + " got " +
+                                     std::to_string(dec[b][i]) + " want " + std::to_string(want));
+        }
+    };
+    verify(x1, "compile run");
+    // an eager decode of 64 plaintexts at the top level asks for 32 MiB of workspace; the recording's is ~14 MiB
+    const size_t count = 64, words = count * 4 * 16384;
+    uint64_t *d_plain = nullptr;
+    double *d_re = nullptr;
+    abcHipCheck(abc_hip_malloc(f.context(), (void **)&d_plain, words * 8), "malloc");
+    abcHipCheck(abc_hip_malloc(f.context(), (void **)&d_re, count * slots * 8), "malloc");
+    std::vector<uint64_t> zeros(words, 0);
+    abcHipCheck(abc_hip_memcpy_h2d(f.context(), d_plain, zeros.data(), words * 8), "upload");
+    abcHipCheck(abc_hip_ckks_decode(f.context(), d_plain, 4, f.defaultScale(), d_re, nullptr, count), "decode");
+    abcHipCheck(abc_hip_sync(f.context()), "sync");
+    abcHipCheck(abc_hip_free(f.context(), d_plain), "free");
+    abcHipCheck(abc_hip_free(f.context(), d_re), "free");
+    // the recording's workspace was held back, not freed: checked before anything replays over it
+    if (!(abc_hip_ctx_info(f.context(), 6) > 0)) throw std::runtime_error("scratch growth freed the recorded workspace");
+    const auto x2 = draw();
+    rt.setInputBatch("x", x2);
+    rt.replay();
+    verify(x2, "replay on new inputs");
+    // a real scale mismatch still throws: Delta against 2 Delta
+    auto a = f.createCiphertext(std::vector<double>{1.0, 2.0});
+    HipCiphertext doubled(std::cref(f), hip(*a).level(), 2 * f.defaultScale());
+    EXPECT_THROWS(a->add(doubled));
+  });
   // ---- config 4: N = 2^15, 8x8 box sum on a 64x64 image (rotations 1,2,4 then 64,128,256, each followed by add) ----
   t.run("config 4: box-sum circuit through CircuitRuntime on a CKKS N = 32768 factory", [&] {
     HipSchemeConfig cfg;

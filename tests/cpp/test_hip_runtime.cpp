@@ -1,6 +1,8 @@
 // HIP backend behind the plugin surface: the reference's SEAL-backed tests re-expressed against
 // HipCiphertextFactory (N = 4096 like test/runtime/SealCiphertextFactoryTest.cpp:14,19 and
 // test/runtime/RuntimeVisitorTest.cpp:16).  Every expected vector below is the reference's own.
+#include <sstream>
+
 #include "CircuitRuntime.hpp"
 #include "HipCiphertext.hpp"
 #include "HipCiphertextFactory.hpp"
@@ -256,6 +258,41 @@ int main() {
     CircuitRuntime bad(f, "secret int a = {1, 2};");
     EXPECT_THROWS(bad.compile("secret int t = {4, 5}; a = a +++ t;"));
     checkPadded(f, *f.createCiphertext(d1)->add(*f.createCiphertext(d2)), {3, 4, 3, 5, 15, 30});
+  });
+  t.run("recorded circuit after loading another factory's keys: the replay uses the keys current at launch", [&] {
+    HipCiphertextFactory fk(N, 0, 0xABC00003ull), other(N, 0, 0xABC00004ull);
+    const std::string program =
+        "secret int r = a *** b;\n"
+        "r = r +++ rotate(r, 1);\n"
+        "r = r +++ rotate(a, 3);\n";  // step 3 has no key of its own: two hops (NAF)
+    CircuitRuntime rt(fk, "secret int a = {3, 3, 1, 4, 5, 9}; secret int b = {0, 1, 2, 1, 10, 21};");
+    rt.compile(program);
+    // every key replaced in place by the other factory's: relinearisation and Galois keys the recording switches with, and the
+    // secret / public key, so that the values below decrypt correctly only if the replay used the new switching keys
+    std::stringstream sk, pk, rk, gk;
+    other.saveSecretKey(sk);
+    other.savePublicKey(pk);
+    other.saveRelinKeys(rk);
+    other.saveGaloisKeys(gk);
+    fk.loadSecretKey(sk);
+    fk.loadPublicKey(pk);
+    fk.loadRelinKeys(rk);
+    fk.loadGaloisKeys(gk);
+    const std::vector<int64_t> a2 = {7, 1, 0, 2, 9, 4}, b2 = {5, 5, 1, 3, 2, 6};
+    rt.setInput("a", a2);  // encrypted under the new public key
+    rt.setInput("b", b2);
+    rt.replay();
+    auto out = rt.getOutput("y = r;");
+    const auto replayed = outputOf(fk, out, "y");
+    CircuitRuntime eager(fk, "secret int a = {7, 1, 0, 2, 9, 4}; secret int b = {5, 5, 1, 3, 2, 6};");
+    eager.executeAst(program);
+    auto out2 = eager.getOutput("y = r;");
+    const auto interpreted = outputOf(fk, out2, "y");
+    EXPECT_TRUE(replayed == interpreted);
+    auto at = [](const std::vector<int64_t> &v, size_t i) { return i < v.size() ? v[i] : v.back(); };
+    std::vector<int64_t> want(8);
+    for (size_t i = 0; i < 8; ++i) want[i] = at(a2, i) * at(b2, i) + at(a2, i + 1) * at(b2, i + 1) + at(a2, i + 3);
+    expectPrefix(replayed, want);
   });
   return t.summary();
 }
