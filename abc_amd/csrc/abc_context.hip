@@ -37,11 +37,7 @@ void read_switches(abc_hip_ctx *c) {
   s.no_pack = env_on("ABC_HIP_NO_PACK");
   s.no_key_twin = env_on("ABC_HIP_NO_KEY_TWIN");
   s.no_bmul = env_on("ABC_HIP_NO_BMUL");
-  s.no_special8x2 = env_on("ABC_HIP_NO_SPECIAL8X2");
-  s.no_bmul_mid = env_on("ABC_HIP_NO_BMUL_MID");
-  s.no_finish_lds = env_on("ABC_HIP_NO_FINISH_LDS");
   s.no_iks = env_on("ABC_HIP_NO_IKS");
-  s.no_bmul_r6 = env_on("ABC_HIP_NO_BMUL_R6");
   s.no_lean_front = env_on("ABC_HIP_NO_LEAN_FRONT");
   s.no_tensor_intt = env_on("ABC_HIP_NO_TENSOR_INTT");
   s.no_galois_fusion = env_on("ABC_HIP_NO_GALOIS_FUSION");
@@ -50,7 +46,6 @@ void read_switches(abc_hip_ctx *c) {
   if (const char *e = std::getenv("ABC_HIP_LEAN_LIMIT")) s.lean_limit = (size_t)std::atol(e);
   if (const char *e = std::getenv("ABC_HIP_PASS0_TARGET_LIMIT")) s.pass0_target_limit = (size_t)std::atol(e);
   if (const char *e = std::getenv("ABC_HIP_BFV_SCRATCH_MB")) s.bfv_scratch_mb = (size_t)std::atol(e);
-  if (const char *e = std::getenv("ABC_HIP_LANE_OFFSET_US")) s.lane_offset_us = (unsigned)std::atoi(e);
   if (const char *e = std::getenv("ABC_HIP_LANES")) {
     s.lanes = std::atoi(e);
     if (s.lanes < 1) s.lanes = 1;
@@ -417,7 +412,6 @@ static int build_context(abc_hip_ctx *c) {
   dc.mods = c->d_mods; dc.tw = c->d_tw; dc.ftw = c->d_ftw; dc.cst = c->d_cst; dc.cstf = c->d_cstf; dc.slot_map = c->d_slot_map;
   dc.logn = logn; dc.n = (int)N; dc.K = K; dc.L = L;
   dc.ps = (int)N;
-  if (const char *e = std::getenv("ABC_HIP_SCRATCH_PAD")) dc.ps = (int)N + (std::atoi(e) / 2) * 2;  // words, kept even (16-byte rows)
   dc.id_bsk = id_bsk; dc.id_t = id_t; dc.id_gamma = id_gamma; dc.id_mtilde = -1;
   return 0;
 }
@@ -682,24 +676,9 @@ int abc_hip_ctx_create(int scheme, int logn, const uint64_t *primes, int nprimes
     set_error("hipEventCreate failed");
     rc = 1;
   }
-  // ABC_HIP_CU_MASK=<m>: lane i may only use the CUs whose index is congruent to i modulo m (experiment: forces two
-  // lanes to run side by side, a memory-bound kernel on one half of every XCD next to an arithmetic-bound one)
-  int mask_mod = 0;
-  if (const char *e = std::getenv("ABC_HIP_CU_MASK")) mask_mod = std::atoi(e);
   for (int i = 0; !rc && i < abc_hip_ctx::kMaxLanes; i++) {
-    hipError_t se;
-    if (mask_mod >= 2) {
-      uint32_t mask[8];
-      for (int w = 0; w < 8; w++) {
-        mask[w] = 0;
-        for (int b = 0; b < 32; b++)
-          if (((w * 32 + b) % mask_mod) == (i % mask_mod)) mask[w] |= 1u << b;
-      }
-      se = hipExtStreamCreateWithCUMask(&c->lane[i], 8, mask);
-    } else {
-      se = hipStreamCreateWithFlags(&c->lane[i], hipStreamNonBlocking);
-    }
-    if (hipEventCreateWithFlags(&c->lane_join[i], hipEventDisableTiming) != hipSuccess || se != hipSuccess) {
+    if (hipStreamCreateWithFlags(&c->lane[i], hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreateWithFlags(&c->lane_join[i], hipEventDisableTiming) != hipSuccess) {
       set_error("lane stream / event creation failed");
       rc = 1;
     }

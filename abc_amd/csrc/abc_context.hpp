@@ -79,7 +79,7 @@ struct DevCtx {
   const DevConstFp *cstf;  // null unless the BEHZ base is fp64-capable
   const u32 *slot_map;  // [N] BatchEncoder index map (BFV)
   int logn, n;
-  int ps;               // scratch limb stride of the split kernels in words: n + pad (HBM channel spread)
+  int ps;               // scratch limb stride of the split kernels in words (always n)
   int K, L;             // key-level primes, data limbs
   int id_bsk, id_t, id_gamma, id_mtilde;  // modulus ids: key primes are 0..K-1
 };
@@ -155,11 +155,10 @@ struct abc_hip_ctx {
   // Path switches (A/B timing and the parity tests of every fallback): the ABC_HIP_* environment variables are read
   // ONCE, when the context is created (abc_hip_ctx_reload_env re-reads them), never on the per-operation path.
   struct Switches {
-    bool no_fused = false, no_split = false, no_split4 = false, no_isplit = false, no_gsplit = false, no_lean_front = false, no_bsplit = false, no_mixed = false, no_pack = false, no_key_twin = false, no_special8x2 = false, no_bmul = false, no_bmul_mid = false, no_finish_lds = false, no_iks = false, no_bmul_r6 = false, no_tensor_intt = false;
+    bool no_fused = false, no_split = false, no_split4 = false, no_isplit = false, no_gsplit = false, no_lean_front = false, no_bsplit = false, no_mixed = false, no_pack = false, no_key_twin = false, no_bmul = false, no_iks = false, no_tensor_intt = false;
     bool no_galois_fusion = false;
     size_t chunk = 0, few_limbs = 48, lean_limit = 96, bfv_scratch_mb = 0, pass0_target_limit = 128;
     int lanes = 2;
-    unsigned lane_offset_us = 0;
   } sw;
   abc::DevConst *d_cst = nullptr;
   abc::DevConstFp *d_cstf = nullptr;
@@ -320,12 +319,69 @@ struct LaneScope {
   }
 };
 
+// One call's chunk / lane loop: `count` ciphertexts in chunks of `chunk`, chunk `turn` on lane `turn % lanes` (fewer than two
+// lanes: the context's stream) with that lane's scratch, `per_ct` words per ciphertext, lane l's starting at l * chunk * per_ct.
+// The workspace grows and the fp64 twin of `twin_key` (nullptr: none needed) is built BEFORE the lanes fork: a capture must not
+// allocate after them.  body(stream, scratch, off, cc) enqueues ciphertexts off .. off + cc - 1 and returns non-zero on error.
+template <class Body>
+int for_each_chunk(abc_hip_ctx *c, size_t count, size_t chunk, int lanes, size_t per_ct, const u64 *twin_key, Body body) {
+  if (ensure_workspace(c, (size_t)lanes * chunk * per_ct * 8)) return 1;
+  if (twin_key) (void)key_twin(c, twin_key);
+  LaneScope scope(c, lanes);
+  if (scope.fork()) return 1;
+  int turn = 0;
+  for (size_t off = 0; off < count; off += chunk, turn++) {
+    const size_t cc = (count - off < chunk) ? count - off : chunk;
+    const int l = (lanes > 1) ? turn % lanes : 0;
+    if (body((lanes > 1) ? c->lane[l] : c->stream, (u64 *)c->ws + (size_t)l * chunk * per_ct, off, cc)) return 1;
+  }
+  return scope.join();
+}
+// single-stream calls: as many ciphertexts per chunk as `budget_bytes` of scratch hold (at least 1, at most count), in even
+// chunks without a runt when there are fewer than 8 of them
+inline size_t even_chunks(size_t budget_bytes, size_t per_ct_words, size_t count) {
+  size_t chunk = budget_bytes / 8 / per_ct_words;
+  if (chunk < 1) chunk = 1;
+  if (chunk > count) chunk = count;
+  else if (count % chunk && count / chunk < 8) chunk = (count + count / chunk) / (count / chunk + 1);
+  return chunk;
+}
+
+// Prime-width predicates (fp_ok: below 2^50, the exact-fp64 kernels; unguarded_ok: 64 q <= 2^64): the name says WHICH primes
+// are inspected, `ok` is the width test.  A sequence must ask about exactly the primes its kernels compute with.
+template <class P>
+inline bool all_key_primes(const abc_hip_ctx *c, P ok) {  // all K: the whole chain's data primes and the special prime
+  for (int j = 0; j < c->K; j++)
+    if (!ok(c->h_mods[j].bits)) return false;
+  return true;
+}
+template <class P>
+inline bool all_data_primes(const abc_hip_ctx *c, int nl, P ok) {  // the first nl data primes, not the special prime
+  for (int j = 0; j < nl; j++)
+    if (!ok(c->h_mods[j].bits)) return false;
+  return true;
+}
+template <class P>
+inline bool all_data_and_special_primes(const abc_hip_ctx *c, int nl, P ok) {  // the first nl data primes and the special prime
+  return all_data_primes(c, nl, ok) && ok(c->h_mods[c->K - 1].bits);
+}
+template <class P>
+inline bool all_mapped_primes(const abc_hip_ctx *c, const LimbMap &map, int nl, P ok) {  // the moduli map.id[0 .. nl-1]
+  for (int j = 0; j < nl; j++)
+    if (!ok(c->h_mods[map.id[j]].bits)) return false;
+  return true;
+}
+template <class P>
+inline u32 data_prime_mask(const abc_hip_ctx *c, int nl, P ok) {  // bit j: data prime j passes (j < nl)
+  u32 mask = 0;
+  for (int j = 0; j < nl; j++)
+    if (ok(c->h_mods[j].bits)) mask |= 1u << j;
+  return mask;
+}
+
 // BFV multiply (+ relinearise) in split form, N = 2^14 (abc_kernels_bmul.hip)
 bool bmul_applies(const abc_hip_ctx *c);           // multiply + relinearise in one sequence
 bool bmul_multiply_applies(const abc_hip_ctx *c);  // the multiply alone (also N = 2^15 / 2^16)
-int launch_ntt_fwd_block_part(abc_hip_ctx *c, u64 *d, const LimbMap &map, int nl, size_t total_limbs);  // abc_kernels_ntt.hip
-int launch_bfv_tensor_inv_block(abc_hip_ctx *c, const u64 *a, const u64 *b, size_t ct_stride, u64 *d, const LimbMap &map, int nlm,
-                                size_t count);  // abc_kernels_bfv.hip
 int bmul_split(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out, size_t count, bool relin);
 // integer twins of the split kernels (abc_kernels_isplit.hip)
 bool isplit_applies(const abc_hip_ctx *c, int nl);

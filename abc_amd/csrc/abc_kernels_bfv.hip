@@ -407,8 +407,7 @@ __global__ __launch_bounds__((1 << LB) / 16) void k_bfv_tensor_inv_block(DevCtx 
 // 0 done, -1 not applicable, 1 error
 static int tensor_inv_big(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *d, const LimbMap &map, int nlm, size_t count) {
   if ((c->logn != 15 && c->logn != 16) || c->sw.no_tensor_intt || big_block_log() != 12) return -1;
-  bool fp = c->use_fp;
-  for (int j = 0; j < nlm; j++) fp = fp && fp_ok(c->h_mods[map.id[j]].bits);
+  const bool fp = c->use_fp && all_mapped_primes(c, map, nlm, fp_ok);
   const int S0 = c->logn - 12;
   const dim3 grid((unsigned)((count * 3 * nlm) << S0)), block((1 << 12) / 16);
   const size_t cts = 2 * (size_t)nlm * c->n;
@@ -419,21 +418,10 @@ static int tensor_inv_big(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *d, co
   ABC_HIP_CHECK(hipGetLastError());
   return launch_ntt_inv_strided_part(c, d, map, nlm, count * 3 * nlm);
 }
-// the fp64 form alone, operands at a caller-given ciphertext stride, no strided pass behind it (abc_kernels_bmul.hip finishes)
-int launch_bfv_tensor_inv_block(abc_hip_ctx *c, const u64 *a, const u64 *b, size_t ct_stride, u64 *d, const LimbMap &map, int nlm,
-                                size_t count) {
-  if ((c->logn != 15 && c->logn != 16) || big_block_log() != 12) { set_error("tensor_inv_block: N = 2^15 / 2^16 only"); return 1; }
-  const int S0 = c->logn - 12;
-  const dim3 grid((unsigned)((count * 3 * nlm) << S0)), block((1 << 12) / 16);
-  hipLaunchKernelGGL((k_bfv_tensor_inv_block<12, true>), grid, block, 0, c->stream, c->dc, a, b, d, map, nlm, S0, ct_stride);
-  ABC_HIP_CHECK(hipGetLastError());
-  return 0;
-}
 
 template <int LB>
 static int launch_tensor_intt(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *d, const LimbMap &map, int nlm, size_t count) {
-  bool fp = c->use_fp;
-  for (int j = 0; j < nlm; j++) fp = fp && fp_ok(c->h_mods[map.id[j]].bits);
+  const bool fp = c->use_fp && all_mapped_primes(c, map, nlm, fp_ok);
   const dim3 grid((unsigned)(count * 3 * nlm)), block((1 << LB) / 16);
   if (fp)
     hipLaunchKernelGGL((k_bfv_tensor_intt<LB, true>), grid, block, 0, c->stream, c->dc, a, b, d, map, nlm);
@@ -490,12 +478,8 @@ int bfv_multiply(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out3, size_t c
   const int L = c->L, nBsk = c->nBsk, nlm = L + nBsk;
   // per ciphertext pair (words): aq,bq 2*2L ; aB,bB 2*2nBsk ; dq 3L ; dB 3nBsk
   const size_t per_ct = (size_t)(4 * L + 4 * nBsk + 3 * L + 3 * nBsk) * N;
-  size_t budget = (size_t)4 << 30;  // scratch capped at 4 GiB (ABC_HIP_BFV_SCRATCH_MB: test knob, forces several chunks)
-  if (c->sw.bfv_scratch_mb) budget = c->sw.bfv_scratch_mb << 20;
-  size_t chunk = (budget / 8) / per_ct;
-  if (chunk < 1) chunk = 1;
-  if (chunk > count) chunk = count;
-  else if (count % chunk && count / chunk < 8) chunk = (count + count / chunk) / (count / chunk + 1);  // even chunks, no runt
+  // scratch capped at 4 GiB (ABC_HIP_BFV_SCRATCH_MB: test knob, forces several chunks)
+  const size_t chunk = even_chunks(c->sw.bfv_scratch_mb ? c->sw.bfv_scratch_mb << 20 : (size_t)4 << 30, per_ct, count);
   if (ensure_workspace(c, chunk * per_ct * 8)) return 1;
   u64 *aq = (u64 *)c->ws;
   u64 *aB = aq + chunk * 4 * L * N;
@@ -618,8 +602,7 @@ int bfv_multiply_plain(abc_hip_ctx *c, const u64 *ct, const u64 *plain, size_t p
   hipLaunchKernelGGL(k_plain_lift, dim3(grid_for(nplain * N, 256)), dim3(256), 0, c->stream, c->dc, plain, lifted, nplain);
   ABC_HIP_CHECK(hipGetLastError());
   if (launch_ntt_fwd(c, lifted, qmap, L, nplain * L)) return 1;
-  bool fp = c->use_fp && c->logn <= 14 && !c->sw.no_fused;
-  for (int j = 0; j < L; j++) fp = fp && fp_ok(c->h_mods[j].bits);
+  const bool fp = c->use_fp && c->logn <= 14 && !c->sw.no_fused && all_data_primes(c, L, fp_ok);
   if (fp && (c->logn < 14 || count * size * L > 48)) {  // single-ciphertext calls keep the spread-out transforms
     const size_t ls = plain_stride ? (size_t)L * N : 0;
     switch (c->logn) {

@@ -18,14 +18,14 @@
 //      fast floor and the conversion back to q (the body of k_behz_floor_fp); components 0, 1 -> the result; component 2 stays in
 //      LDS and every (digit, position) thread runs the key switch's forward cross pass modulo each key prime -> `part`, what
 //      k_fused_operand_pass0_fp<14, false, false> would have produced from a stored c2.                51 read, 16 + 72 written.
-// then k_gsplit_special<14, 8, true> / k_bsplit_tcoef / k_bsplit_finish_big (abc_kernels_gsplit.hip) with the result as addend.
+// then k_bsplit_special8x2<14> / k_bsplit_tcoef / k_bsplit_finish_big (abc_kernels_gsplit.hip) with the result as addend.
 // 502 limb transfers per multiply + relinearise where the LDS-resident sequence (bfv_multiply's six kernels + the key switch's
 // four) moved ~730 (profiles/r02g_bfv16384_traffic_per_kernel.json: 96 MB per pair).  Same arithmetic as those kernels -- exact
 // fp64 residues, every prime (ciphertext and auxiliary) below 2^50 -- bit-identical results (tests/test_gpu_paths.py).
 // Other rings, same three kernels: N = 2^13 with four data limbs (BFVDefault(8192): eight blocks, radix-8 cross passes, the whole
 // multiply + relinearise sequence); N = 2^15 / 2^16 with eight data limbs (the multiply alone; 32 / 64 blocks of 1024 points, the
 // radix-32 / 64 cross passes in two levels through the tile -- a thread holds at most eight values --, rows of 16 / 8 coefficients,
-// nine wavefronts; ABC_HIP_NO_BMUL_R6: 4096-point blocks behind radix-8 / 16 register passes, round 3's first form).
+// nine wavefronts).
 #include <algorithm>
 
 #include "abc_context.hpp"
@@ -100,9 +100,9 @@ __device__ __forceinline__ int m_tix(int l, int blk, int p) {
 }  // namespace
 
 // ---- M1 ----
-// LOGN, R: ring and radix of the cross pass: the 2^R values one cross pass takes are N >> R apart (N = 2^14: R = 4 over 1024-point
-// blocks; N = 2^15 / 2^16: R = 3 / 4 over the 4096-point blocks of the big-ring transforms, abc_kernels_ntt.hip).  A workgroup
-// takes 512 coefficients: 2^R blocks x P = 512 >> R positions.
+// LOGN, R: ring and radix of the cross pass: the 2^R values one cross pass takes are N >> R apart, over 1024-point blocks (N = 2^13
+// / 2^14: R = 3 / 4 in registers; N = 2^15 / 2^16: R = 5 / 6 in two levels through the tile).  A workgroup takes 512 coefficients:
+// 2^R blocks x P = 512 >> R positions.
 template <int LOGN, int R, int LT, int NBT, int NT = 512>
 __global__ __launch_bounds__(NT, 4) void k_bmul_front(DevCtx c, const u64 *__restrict__ a, const u64 *__restrict__ b, double *__restrict__ hA) {
   constexpr int L = LT, nBsk = NBT + 1, NLM = L + nBsk;
@@ -214,11 +214,8 @@ __global__ __launch_bounds__(NT, 4) void k_bmul_front(DevCtx c, const u64 *__res
 }
 
 // ---- M2 ----
-// LB: block size of the tails (10 at N = 2^14: one wavefront per operand polynomial, 256 threads, 35 KiB; 12 at N = 2^15 / 2^16:
-// 256 threads per operand polynomial, 1024 threads, 139 KiB -- one workgroup per CU, but its 187 limb transfers per limb-block
-// shrink to 7: the separate forward-tail kernel wrote and the tensor kernel re-read every operand limb).  Groups of T = 2^LB / 16
-// threads run the block transforms of abc_ntt.hpp side by side; for LB > 10 those contain one workgroup barrier each, which the
-// fourth group -- it has no product component to transform back -- joins without doing the work.
+// LB: block size of the tails (10: one wavefront per operand polynomial, 256 threads, 35 KiB).  Groups of T = 2^LB / 16 threads run
+// the block transforms of abc_ntt.hpp side by side.
 template <int LOGN, int LB>
 __global__ __launch_bounds__(4 * ((1 << LB) / 16)) void k_bmul_mid(DevCtx c, const double *__restrict__ hA, double *__restrict__ hD, int nlm, int L) {
   constexpr int LOGNB = LOGN - LB, T = (1 << LB) / 16, LW = lds_words(LB);
@@ -263,8 +260,6 @@ __global__ __launch_bounds__(4 * ((1 << LB) / 16)) void k_bmul_mid(DevCtx c, con
     double *__restrict__ dst = hD + ((ct * 3 + G) * nlm + l) * N + base;
     ntt_inv_block_a<LB, FpArith>(
         tb, [&](int, int i) { return tb[lds_pad(i)]; }, [&](int, int i, double v) { dst[i] = v; }, t, m, LOGNB, blk, gt);
-  } else if (LB > 10) {
-    block_sync_lds();  // the ONE workgroup barrier inside ntt_inv_block_a<LB > 10> (before its last pass): the fourth group only keeps count
   }
 }
 
@@ -436,7 +431,7 @@ bool bmul_applies(const abc_hip_ctx *c) {
   if (c->logn == 13) return bmul_shape(c, 4) && bsplit_big_applies(c, c->L);  // BFVDefault(8192)
   return c->logn == 14 && bmul_shape(c) && bsplit_applies(c, c->L);
 }
-// the multiply alone (size-3 product): also N = 2^15 / 2^16 over the 4096-point blocks of the big-ring transforms
+// the multiply alone (size-3 product): also N = 2^15 / 2^16
 bool bmul_multiply_applies(const abc_hip_ctx *c) {
   if (c->logn == 14) return bmul_applies(c);
   if (c->logn == 13) return bmul_shape(c, 4);  // BFVDefault(8192): four data limbs, radix-8 cross passes over eight 1024-point blocks
@@ -452,23 +447,16 @@ static size_t bmul_scratch_words(const abc_hip_ctx *c) {
   return X + Y;
 }
 
-// N = 2^15 / 2^16: M1, the block tails of the forward transforms (k_ntt_fwd_fp<12>), the tensor product inside the block tails of
-// the inverse ones (k_bfv_tensor_inv_block<12>), M3 -- where the generic sequence ran extend, two strided + two block forward
-// passes, two tensor / block-inverse launches, two strided inverse passes and the floor (704 limb transfers per pair; here 498)
+// the multiply alone where no key switch follows in the same sequence (N = 2^13, 2^15, 2^16): M1, M2, M3 on the context's stream --
+// where the generic sequence ran extend, two strided + two block forward passes, two tensor / block-inverse launches, two strided
+// inverse passes and the floor
 static int bmul_big(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out3, size_t count) {
   const size_t N = (size_t)c->n;
   const int L = c->L, nlm = c->L + c->nBsk;
   const size_t per_ct = (size_t)7 * nlm * N;
-  size_t chunk = (((size_t)2 << 30) / 8) / per_ct;  // 4 and 8 GiB measured: no difference (config 5: 1 460 circuits/s each)
-  if (c->sw.bfv_scratch_mb) chunk = (c->sw.bfv_scratch_mb << 20) / 8 / per_ct;
-  if (chunk < 1) chunk = 1;
-  if (chunk > count) chunk = count;
-  else if (count % chunk && count / chunk < 8) chunk = (count + count / chunk) / (count / chunk + 1);  // even chunks, no runt
+  // 4 and 8 GiB measured: no difference (config 5: 1 460 circuits/s each)
+  const size_t chunk = even_chunks(c->sw.bfv_scratch_mb ? c->sw.bfv_scratch_mb << 20 : (size_t)2 << 30, per_ct, count);
   if (ensure_workspace(c, chunk * per_ct * 8)) return 1;
-  LimbMap map{};
-  for (int j = 0; j < L; j++) map.id[j] = j;
-  for (int j = 0; j < c->nBsk; j++) map.id[L + j] = c->dc.id_bsk + j;
-  const size_t lds = (size_t)nlm * 512 * 8;
   hipStream_t st = c->stream;
   for (size_t off = 0; off < count; off += chunk) {
     const size_t cc = (count - off < chunk) ? count - off : chunk;
@@ -476,51 +464,24 @@ static int bmul_big(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out3, size_
     const u64 *pa = a + off * 2 * L * N, *pb = b + off * 2 * L * N;
     u64 *po = out3 + off * 3 * L * N;
     if (c->logn == 13) {
+      const size_t lds = (size_t)nlm * 512 * 8;
       hipLaunchKernelGGL((k_bmul_front<13, 3, 4, 4>), dim3((unsigned)(cc * 4 * 16)), dim3(512), lds, st, c->dc, pa, pb, X);
       hipLaunchKernelGGL((k_bmul_mid<13, 10>), dim3((unsigned)(cc * nlm * 8)), dim3(256), (size_t)(4 * lds_words(10)) * 8, st, c->dc,
                          (const double *)X, Y, nlm, L);
       hipLaunchKernelGGL((k_bmul_back<13, 3, 4, 4>), dim3((unsigned)(cc * 3 * 16)), dim3(512), lds, st, c->dc, (const double *)Y, po, X, 1);
-      ABC_HIP_CHECK(hipGetLastError());
-      continue;
-    }
-    if (c->logn == 16 && !c->sw.no_bmul_r6 && !c->sw.no_bmul_mid) {  // 1024-point blocks: M2 as four workgroups per CU, radix-64 cross passes in two levels
+    } else if (c->logn == 16) {  // 1024-point blocks: M2 as four workgroups per CU, radix-64 cross passes in two levels
       const size_t lds = (size_t)nlm * 576 * 8;  // padded tile (m_tix)
       hipLaunchKernelGGL((k_bmul_front<16, 6, 8, 8, 576>), dim3((unsigned)(cc * 4 * 128)), dim3(576), lds, st, c->dc, pa, pb, X);
       hipLaunchKernelGGL((k_bmul_mid<16, 10>), dim3((unsigned)(cc * nlm * 64)), dim3(256), (size_t)(4 * lds_words(10)) * 8, st, c->dc,
                          (const double *)X, Y, nlm, L);
       hipLaunchKernelGGL((k_bmul_back<16, 6, 8, 8, 576>), dim3((unsigned)(cc * 3 * 128)), dim3(576), lds, st, c->dc, (const double *)Y, po, X, 1);
-      ABC_HIP_CHECK(hipGetLastError());
-      continue;
-    }
-    if (c->logn == 15 && !c->sw.no_bmul_r6 && !c->sw.no_bmul_mid) {  // the same at N = 2^15: radix-32 cross passes as 4 x 8, rows of 16 coefficients
+    } else {  // the same at N = 2^15: radix-32 cross passes as 4 x 8, rows of 16 coefficients
       const size_t lds = (size_t)nlm * 576 * 8;
       hipLaunchKernelGGL((k_bmul_front<15, 5, 8, 8, 576>), dim3((unsigned)(cc * 4 * 64)), dim3(576), lds, st, c->dc, pa, pb, X);
       hipLaunchKernelGGL((k_bmul_mid<15, 10>), dim3((unsigned)(cc * nlm * 32)), dim3(256), (size_t)(4 * lds_words(10)) * 8, st, c->dc,
                          (const double *)X, Y, nlm, L);
       hipLaunchKernelGGL((k_bmul_back<15, 5, 8, 8, 576>), dim3((unsigned)(cc * 3 * 64)), dim3(576), lds, st, c->dc, (const double *)Y, po, X, 1);
-      ABC_HIP_CHECK(hipGetLastError());
-      continue;
     }
-    if (c->logn == 16)
-      hipLaunchKernelGGL((k_bmul_front<16, 4, 8, 8>), dim3((unsigned)(cc * 4 * 128)), dim3(512), lds, st, c->dc, pa, pb, X);
-    else
-      hipLaunchKernelGGL((k_bmul_front<15, 3, 8, 8>), dim3((unsigned)(cc * 4 * 64)), dim3(512), lds, st, c->dc, pa, pb, X);
-    ABC_HIP_CHECK(hipGetLastError());
-    if (c->sw.no_bmul_mid) {  // A/B: block tails and tensor product as the separate kernels of the generic sequence
-      if (launch_ntt_fwd_block_part(c, (u64 *)X, map, nlm, cc * 4 * nlm)) return 1;
-      if (launch_bfv_tensor_inv_block(c, (const u64 *)X, (const u64 *)X + 2 * (size_t)nlm * N, 4 * (size_t)nlm * N, (u64 *)Y, map, nlm, cc))
-        return 1;
-    } else if (c->logn == 16) {
-      hipLaunchKernelGGL((k_bmul_mid<16, 12>), dim3((unsigned)(cc * nlm * 16)), dim3(1024), (size_t)(4 * lds_words(12)) * 8, st, c->dc,
-                         (const double *)X, Y, nlm, L);
-    } else {
-      hipLaunchKernelGGL((k_bmul_mid<15, 12>), dim3((unsigned)(cc * nlm * 8)), dim3(1024), (size_t)(4 * lds_words(12)) * 8, st, c->dc,
-                         (const double *)X, Y, nlm, L);
-    }
-    if (c->logn == 16)
-      hipLaunchKernelGGL((k_bmul_back<16, 4, 8, 8>), dim3((unsigned)(cc * 3 * 128)), dim3(512), lds, st, c->dc, (const double *)Y, po, X, 1);
-    else
-      hipLaunchKernelGGL((k_bmul_back<15, 3, 8, 8>), dim3((unsigned)(cc * 3 * 64)), dim3(512), lds, st, c->dc, (const double *)Y, po, X, 1);
     ABC_HIP_CHECK(hipGetLastError());
   }
   return 0;
@@ -543,18 +504,11 @@ int bmul_split(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out, size_t coun
   size_t chunk = c->sw.chunk ? c->sw.chunk : 64;
   if (c->sw.bfv_scratch_mb) chunk = std::max<size_t>(1, (c->sw.bfv_scratch_mb << 20) / 8 / per_ct / (size_t)lanes);
   if (chunk * lanes > count) chunk = (count + lanes - 1) / lanes;
-  if (ensure_workspace(c, (size_t)lanes * chunk * per_ct * 8)) return 1;
   const size_t Xw = std::max((size_t)4 * nlm * N, (size_t)L * (L + 1) * PS);
   const size_t lds = (size_t)nlm * 512 * 8;
-  if (relin) (void)key_twin(c, c->d_relin);  // before the lanes fork (the inner-product kernel reads it)
-  LaneScope scope(c, lanes);
-  if (scope.fork()) return 1;
-  int turn = 0;
-  for (size_t off = 0; off < count; off += chunk, turn++) {
-    const size_t cc = (count - off < chunk) ? count - off : chunk;
-    const int ln = (lanes > 1) ? turn % lanes : 0;
-    hipStream_t st = (lanes > 1) ? c->lane[ln] : c->stream;
-    double *X = (double *)c->ws + (size_t)ln * chunk * per_ct, *Y = X + cc * Xw;
+  // the inner-product kernel of the key switch reads the relinearisation key's fp64 twin
+  return for_each_chunk(c, count, chunk, lanes, per_ct, relin ? c->d_relin : nullptr, [&](hipStream_t st, u64 *scratch, size_t off, size_t cc) {
+    double *X = (double *)scratch, *Y = X + cc * Xw;
     const u64 *pa = a + off * 2 * L * N, *pb = b + off * 2 * L * N;
     u64 *po = out + off * (relin ? 2 : 3) * L * N;
     if (n13) {  // four data limbs, eight blocks (reached with relin only: the plain multiply of this ring is bmul_big's)
@@ -562,16 +516,14 @@ int bmul_split(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out, size_t coun
       hipLaunchKernelGGL((k_bmul_mid<13, 10>), dim3((unsigned)(cc * nlm * 8)), dim3(256), (size_t)(4 * lds_words(10)) * 8, st, c->dc, (const double *)X, Y, nlm, L);
       hipLaunchKernelGGL((k_bmul_back<13, 3, 4, 4>), dim3((unsigned)(cc * 3 * 16)), dim3(512), lds, st, c->dc, (const double *)Y, po, X, 0);
       ABC_HIP_CHECK(hipGetLastError());
-      if (bsplit_back13(c, st, cc, L, (const double *)X, Y, c->d_relin, po, 2 * (size_t)L * N, 1, po)) return 1;
-      continue;
+      return bsplit_back13(c, st, cc, L, (const double *)X, Y, c->d_relin, po, 2 * (size_t)L * N, 1, po);
     }
     hipLaunchKernelGGL((k_bmul_front<14, 4, 8, 8>), dim3((unsigned)(cc * 4 * 32)), dim3(512), lds, st, c->dc, pa, pb, X);
     hipLaunchKernelGGL((k_bmul_mid<14, 10>), dim3((unsigned)(cc * nlm * 16)), dim3(256), (size_t)(4 * lds_words(10)) * 8, st, c->dc, (const double *)X, Y, nlm, L);
     hipLaunchKernelGGL((k_bmul_back<14, 4, 8, 8>), dim3((unsigned)(cc * 3 * 32)), dim3(512), lds, st, c->dc, (const double *)Y, po, X, relin ? 0 : 1);
     ABC_HIP_CHECK(hipGetLastError());
-    if (relin && bsplit_back14(c, st, cc, L, (const double *)X, Y, c->d_relin, po, 2 * (size_t)L * N, 1, po)) return 1;
-  }
-  return scope.join();
+    return relin ? bsplit_back14(c, st, cc, L, (const double *)X, Y, c->d_relin, po, 2 * (size_t)L * N, 1, po) : 0;
+  });
 }
 
 }  // namespace abc

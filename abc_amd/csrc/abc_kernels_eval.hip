@@ -439,9 +439,7 @@ static int iks_finish(abc_hip_ctx *c, const u64 *prodD, const u64 *prodS, const 
 // BFV with the permutation of a rotation folded in (rotate_fused): the integer sequence must be the one that runs
 bool iks_bfv_applies(const abc_hip_ctx *c, int nl) {
   if (c->scheme != 1 || (c->logn != 15 && c->logn != 16) || c->sw.no_iks || big_block_log() != 12 || nl < 1) return false;
-  bool fp = c->use_fp;
-  for (int j = 0; j < nl; j++) fp = fp && fp_ok(c->h_mods[j].bits);
-  fp = fp && fp_ok(c->h_mods[c->K - 1].bits);
+  const bool fp = c->use_fp && all_data_and_special_primes(c, nl, fp_ok);
   return !fp;  // an all-fp64 decomposition takes launch_ks_expand_ntt_fp + the generic kernels
 }
 static int iks_front(abc_hip_ctx *c, const u64 *tc, size_t tcs, const u64 *key, u64 *dec, u64 *prodD, u64 *prodS, int nl, size_t cc, u32 ginv) {
@@ -458,8 +456,7 @@ static int iks_front(abc_hip_ctx *c, const u64 *tc, size_t tcs, const u64 *key, 
   const u64 *keys = key_shoup(c, key);
   const bool ckks = c->scheme == 2;
   // unguarded butterflies where every key prime leaves the room: [0, 4q) out of the strided pass, + 4q per block stage = 52q < 2^64
-  bool guard = false;
-  for (int j = 0; j < c->K; j++) guard = guard || !unguarded_ok(c->h_mods[j].bits);
+  const bool guard = !all_key_primes(c, unguarded_ok);
 #define ABC_IKS(INV_D, SHOUP)                                                                                                        \
   do {                                                                                                                               \
     if (guard)                                                                                                                       \
@@ -484,11 +481,7 @@ int keyswitch_generic(abc_hip_ctx *c, const u64 *target, size_t target_stride, c
   const size_t N = (size_t)c->n;
   // workspace per ciphertext (words): tcoef nl + dec nl(nl+1) + prodD 2nl + prodS 2 + tmod 2nl
   const size_t per_ct = ((size_t)nl + (size_t)nl * (nl + 1) + 2 * nl + 2 + 2 * nl) * N;
-  const size_t budget_words = ((size_t)(c->logn > 14 ? 4 : 1) << 30) / 8;  // <= 1 GiB of scratch per chunk (big rings: 4 GiB)
-  size_t chunk = budget_words / per_ct;
-  if (chunk < 1) chunk = 1;
-  if (chunk > count) chunk = count;
-  else if (count % chunk && count / chunk < 8) chunk = (count + count / chunk) / (count / chunk + 1);  // even chunks, no runt
+  const size_t chunk = even_chunks((size_t)(c->logn > 14 ? 4 : 1) << 30, per_ct, count);  // <= 1 GiB of scratch per chunk (big rings: 4 GiB)
   if (ensure_workspace(c, chunk * per_ct * 8)) return 1;
   u64 *tcoef = (u64 *)c->ws;
   u64 *dec = tcoef + chunk * nl * N;
@@ -739,10 +732,7 @@ static int launch_rescale_mixed(abc_hip_ctx *c, const u64 *in, u64 *out, int nl,
   const size_t N = (size_t)1 << LB;
   if (ensure_workspace(c, polys * N * 8)) return 1;
   u64 *last = (u64 *)c->ws;
-  u32 fpmask = 0;
-  if (c->use_fp && !c->sw.no_mixed)
-    for (int j = 0; j < nl; j++)
-      if (fp_ok(c->h_mods[j].bits)) fpmask |= 1u << j;
+  const u32 fpmask = (c->use_fp && !c->sw.no_mixed) ? data_prime_mask(c, nl, fp_ok) : 0u;
   const dim3 block((1 << LB) / 16);
   hipLaunchKernelGGL(k_rescale_intt_mixed<LB>, dim3((unsigned)polys), block, 0, c->stream, c->dc, in, last, nl, (int)((fpmask >> (nl - 1)) & 1u));
   hipLaunchKernelGGL(k_rescale_ntt_mixed<LB>, dim3((unsigned)(polys * (nl - 1))), block, 0, c->stream, c->dc, in, last, out, nl, (int)polys,
@@ -755,8 +745,7 @@ int launch_rescale(abc_hip_ctx *c, const u64 *in, u64 *out, int size, int nl, si
   if (nl < 2) { set_error("rescale: no limb left to drop"); return 1; }
   const size_t N = (size_t)c->n, polys = count * size;
   if (!polys) return 0;
-  bool fp = c->use_fp && c->logn <= 14 && in != out && !c->sw.no_fused;
-  for (int j = 0; j < nl; j++) fp = fp && fp_ok(c->h_mods[j].bits);
+  const bool fp = c->use_fp && c->logn <= 14 && in != out && !c->sw.no_fused && all_data_primes(c, nl, fp_ok);
   if (!fp && c->logn <= 14 && in != out && !c->sw.no_fused && !c->sw.no_isplit) switch (c->logn) {  // a prime above 2^50 in the chain
       case 10: return launch_rescale_mixed<10>(c, in, out, nl, polys);
       case 11: return launch_rescale_mixed<11>(c, in, out, nl, polys);

@@ -1210,14 +1210,10 @@ static inline int pack_half_done(const abc_hip_ctx *c, int nl) {
   return (!c->sw.no_pack && !c->sw.no_split4 && nl >= 1 && nl <= 5) ? 1 : 0;
 }
 static inline bool all_fp(const abc_hip_ctx *c) {  // fp64 transforms: every key prime below 2^50
-  bool fp = c->use_fp;
-  for (int j = 0; j < c->K; j++) fp = fp && fp_ok(c->h_mods[j].bits);
-  return fp;
+  return c->use_fp && all_key_primes(c, fp_ok);
 }
 static inline bool needs_guard(const abc_hip_ctx *c) {  // unguarded butterflies need (2 logN + 4) q < 2^64 for every key prime
-  bool guard = false;
-  for (int j = 0; j < c->K; j++) guard = guard || !unguarded_ok(c->h_mods[j].bits);
-  return guard;
+  return !all_key_primes(c, unguarded_ok);
 }
 
 // K2a..K3 on one chunk: operand given by (coef, coef_stride) [+ (ntt, ntt_stride) for CKKS], addends by (addend, stride)
@@ -1246,8 +1242,8 @@ static int keyswitch_stage(abc_hip_ctx *c, hipStream_t st, const FusedScratch &s
     ABC_HIP_CHECK(hipGetLastError());
     return 0;
   }
-  bool lazy = !guard;  // 4 products of a (< 64q) operand with a key residue must stay below 2^(k+63): k <= 55
-  for (int j = 0; j < c->K; j++) lazy = lazy && c->h_mods[j].bits <= 55;
+  // 4 products of a (< 64q) operand with a key residue must stay below 2^(k+63): k <= 55
+  const bool lazy = !guard && all_key_primes(c, [](u32 bits) { return bits <= 55; });
   if (guard)
     hipLaunchKernelGGL((k_fused_ks_decomp_ntt<LB, true, false>), dim3(g2a), block, 0, st, c->dc, coef, coef_stride, s.dec, nl,
                        ckks ? 1 : 0);
@@ -1294,19 +1290,10 @@ static ChunkPlan plan_chunks(const abc_hip_ctx *c, int nl, size_t count) {
   return p;
 }
 
-// one wavefront that sleeps for `ticks` of the 100 MHz wall clock (lane phase offset experiment)
-__global__ void k_lane_delay(unsigned ticks) {
-  const unsigned long long t0 = wall_clock64();
-  while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(32);
-}
-
 int fork_lanes(abc_hip_ctx *c, int lanes) {
   if (lanes < 2) return 0;
   ABC_HIP_CHECK(hipEventRecord(c->lane_fork, c->stream));
   for (int l = 0; l < lanes; l++) ABC_HIP_CHECK(hipStreamWaitEvent(c->lane[l], c->lane_fork, 0));
-  // ABC_HIP_LANE_OFFSET_US: lane l starts l x this late, so that the lanes sit in different kernels of the sequence
-  if (const unsigned us = c->sw.lane_offset_us)
-    for (int l = 1; l < lanes; l++) hipLaunchKernelGGL(k_lane_delay, dim3(1), dim3(64), 0, c->lane[l], us * 100u * l);
   return 0;
 }
 int join_lanes(abc_hip_ctx *c, int lanes) {
@@ -1322,73 +1309,41 @@ static int run_isplit(abc_hip_ctx *c, int mode, const u64 *opa, const u64 *opb, 
                       const u64 *key, u64 *out, int nl, size_t count, u32 gelt) {
   const size_t N = (size_t)c->n;
   const ChunkPlan p = plan_chunks(c, nl, count);
-  const size_t per_ct = isplit_scratch_words(c, nl);
-  if (ensure_workspace(c, (size_t)p.lanes * p.chunk * per_ct * 8)) return 1;
-  if (c->logn == 14 && !c->sw.no_mixed) (void)key_twin(c, key);  // the fp64 limbs of a mixed chain go through k_split4_main_fp
-  LaneScope scope(c, p.lanes);
-  if (scope.fork()) return 1;
-  int turn = 0;
-  for (size_t off = 0; off < count; off += p.chunk, turn++) {
-    const size_t cc = (count - off < p.chunk) ? count - off : p.chunk;
-    const int l = (p.lanes > 1) ? turn % p.lanes : 0;
-    hipStream_t st = (p.lanes > 1) ? c->lane[l] : c->stream;
-    u64 *scratch = (u64 *)c->ws + (size_t)l * p.chunk * per_ct;
-    if (isplit_chunk(c, st, scratch, cc, nl, mode, opa + off * opa_stride, opb ? opb + off * opb_stride : nullptr, opa_stride, opb_stride,
-                     add_c1 ? 1 : 0, key, out + off * 2 * (size_t)nl * N, gelt))
-      return 1;
-  }
-  return scope.join();
+  const bool twin = c->logn == 14 && !c->sw.no_mixed;  // the fp64 limbs of a mixed chain go through k_split4_main_fp
+  return for_each_chunk(c, count, p.chunk, p.lanes, isplit_scratch_words(c, nl), twin ? key : nullptr,
+                        [&](hipStream_t st, u64 *scratch, size_t off, size_t cc) {
+                          return isplit_chunk(c, st, scratch, cc, nl, mode, opa + off * opa_stride, opb ? opb + off * opb_stride : nullptr,
+                                              opa_stride, opb_stride, add_c1 ? 1 : 0, key, out + off * 2 * (size_t)nl * N, gelt);
+                        });
 }
 
 // N = 2^15 (abc_kernels_gsplit.hip)
 static int run_gsplit15(abc_hip_ctx *c, int mode, const u64 *opa, const u64 *opb, size_t opa_stride, size_t opb_stride, bool add_c1,
                         const u64 *key, u64 *out, int nl, size_t count, u32 gelt) {
   const size_t N = (size_t)c->n;
-  ChunkPlan p = plan_chunks(c, nl, count);
-  const size_t per_ct = gsplit_scratch_words(c, nl);
-  if (ensure_workspace(c, (size_t)p.lanes * p.chunk * per_ct * 8)) return 1;
-  LaneScope scope(c, p.lanes);
-  if (scope.fork()) return 1;
-  int turn = 0;
-  for (size_t off = 0; off < count; off += p.chunk, turn++) {
-    const size_t cc = (count - off < p.chunk) ? count - off : p.chunk;
-    const int l = (p.lanes > 1) ? turn % p.lanes : 0;
-    hipStream_t st = (p.lanes > 1) ? c->lane[l] : c->stream;
-    u64 *scratch = (u64 *)c->ws + (size_t)l * p.chunk * per_ct;
-    if (gsplit_chunk15(c, st, scratch, cc, nl, mode, opa + off * opa_stride, opb ? opb + off * opb_stride : nullptr, opa_stride,
-                       opb_stride, add_c1 ? 1 : 0, key, out + off * 2 * (size_t)nl * N, gelt))
-      return 1;
-  }
-  return scope.join();
+  const ChunkPlan p = plan_chunks(c, nl, count);
+  return for_each_chunk(c, count, p.chunk, p.lanes, gsplit_scratch_words(c, nl), nullptr,
+                        [&](hipStream_t st, u64 *scratch, size_t off, size_t cc) {
+                          return gsplit_chunk15(c, st, scratch, cc, nl, mode, opa + off * opa_stride, opb ? opb + off * opb_stride : nullptr,
+                                                opa_stride, opb_stride, add_c1 ? 1 : 0, key, out + off * 2 * (size_t)nl * N, gelt);
+                        });
 }
 
 // ---- CKKS multiply + relinearise ----
-// integer split sequence (abc_kernels_isplit.hip): chains with a prime above 2^50
-static int run_isplit(abc_hip_ctx *c, int mode, const u64 *opa, const u64 *opb, size_t opa_stride, size_t opb_stride, bool add_c1,
-                      const u64 *key, u64 *out, int nl, size_t count, u32 gelt);
-
 template <int LB>
 static int run_mul_relin(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out, int nl, size_t count) {
   const size_t N = (size_t)1 << LB;
   if (LB == 14 && !all_fp(c) && isplit_applies(c, nl))
     return run_isplit(c, 0, a, b, 2 * (size_t)nl * N, 2 * (size_t)nl * N, false, c->d_relin, out, nl, count, 0u);
   const ChunkPlan p = plan_chunks(c, nl, count);
-  // the split sequence (N = 2^14, every key prime below 2^50); its scratch limbs are c->dc.ps words apart (N plus an optional
-  // pad, see abc_hip_ctx_create).  Otherwise: the LDS-resident kernels (smaller rings, ABC_HIP_NO_SPLIT, wider primes)
+  // the split sequence (N = 2^14, every key prime below 2^50); its scratch limbs are c->dc.ps words apart.  Otherwise: the
+  // LDS-resident kernels (smaller rings, ABC_HIP_NO_SPLIT, wider primes)
   const bool split = LB == 14 && all_fp(c) && !c->sw.no_split && nl <= 12;
   const size_t SN = split ? (size_t)c->dc.ps : N;
   const size_t per_ct = fused_scratch_limbs(nl) * SN;
-  if (ensure_workspace(c, (size_t)p.lanes * p.chunk * per_ct * 8)) return 1;
-  if (split) (void)key_twin(c, c->d_relin);  // before the lanes fork: they order themselves behind c->stream
-  LaneScope scope(c, p.lanes);
-  if (scope.fork()) return 1;
   const size_t ctw = 2 * (size_t)nl * N;
-  int turn = 0;
-  for (size_t off = 0; off < count; off += p.chunk, turn++) {
-    const size_t cc = (count - off < p.chunk) ? count - off : p.chunk;
-    const int l = (p.lanes > 1) ? turn % p.lanes : 0;
-    hipStream_t st = (p.lanes > 1) ? c->lane[l] : c->stream;
-    const FusedScratch s = carve((u64 *)c->ws + (size_t)l * p.chunk * per_ct, p.chunk, nl, SN);
+  return for_each_chunk(c, count, p.chunk, p.lanes, per_ct, split ? c->d_relin : nullptr, [&](hipStream_t st, u64 *scratch, size_t off, size_t cc) {
+    const FusedScratch s = carve(scratch, p.chunk, nl, SN);
     if constexpr (LB == 14) {
       if (split) {
         // few ciphertexts in flight: the 139 KiB workgroups of the tensor kernel would leave most CUs idle for its whole
@@ -1402,7 +1357,7 @@ static int run_mul_relin(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out, i
                              b + off * ctw, (double *)s.dec, nl, pack);
         launch_split3<0, false>(st, c, s, cc, nl, a + off * ctw, b + off * ctw, 0, 0, 0, c->d_relin, out + off * ctw, 0u, pack);
         ABC_HIP_CHECK(hipGetLastError());
-        continue;
+        return 0;
       }
     }
     if (all_fp(c))  // tensor product, inverse transform and the forward transforms of the decomposition in one LDS-resident kernel
@@ -1411,11 +1366,9 @@ static int run_mul_relin(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out, i
     else
       hipLaunchKernelGGL(k_fused_tensor_intt<LB>, dim3((unsigned)(cc * nl)), dim3((1 << LB) / 16), 0, st, c->dc, a + off * ctw,
                          b + off * ctw, s.c01, s.coef, s.ntt, nl);
-    if (keyswitch_stage<LB>(c, st, s, s.coef, (size_t)nl * N, s.ntt, (size_t)nl * N, c->d_relin, s.c01, ctw, true, out + off * ctw,
-                            nl, cc, all_fp(c) ? 1 : 0))
-      return 1;
-  }
-  return scope.join();
+    return keyswitch_stage<LB>(c, st, s, s.coef, (size_t)nl * N, s.ntt, (size_t)nl * N, c->d_relin, s.c01, ctw, true, out + off * ctw, nl,
+                               cc, all_fp(c) ? 1 : 0);
+  });
 }
 
 // -1: not applicable (ring too large for an LDS-resident limb) -> caller takes the generic path
@@ -1454,7 +1407,8 @@ static int run_keyswitch(abc_hip_ctx *c, const u64 *target, size_t target_stride
     return run_isplit(c, 1, target, addend, target_stride, addend_stride, add_c1, key, out, nl, count, gelt);
   const ChunkPlan p = plan_chunks(c, nl, count);
   // split sequences (N = 2^14, every key prime below 2^50): CKKS as in run_mul_relin; BFV (coefficient-form operand) the
-  // register pass + abc_kernels_gsplit.hip's k_gsplit_special<14, NL, true> / k_bsplit_tcoef / k_bsplit_finish_big
+  // register pass + abc_kernels_gsplit.hip's k_gsplit_special<14, NL, true> (k_bsplit_special8x2 for eight digits) / k_bsplit_tcoef /
+  // k_bsplit_finish_big
   const bool splitc = LB == 14 && ckks && all_fp(c) && !c->sw.no_split && nl <= 12;
   const bool splitb = LB == 14 && !ckks && !c->sw.no_split && bsplit_applies(c, nl);
   // BFV rotation (coefficient form): the kernels gather with elt^-1 mod 2N
@@ -1462,16 +1416,9 @@ static int run_keyswitch(abc_hip_ctx *c, const u64 *target, size_t target_stride
   if (ginv && !splitb) { set_error("run_keyswitch: a BFV permutation is only folded into the split sequence"); return 1; }
   const size_t SN = (splitc || splitb) ? (size_t)c->dc.ps : N;
   const size_t per_ct = fused_scratch_limbs(nl) * SN;
-  if (ensure_workspace(c, (size_t)p.lanes * p.chunk * per_ct * 8)) return 1;
-  if (splitc || splitb) (void)key_twin(c, key);  // before the lanes fork (BFV: the inner-product kernel reads it)
-  LaneScope scope(c, p.lanes);
-  if (scope.fork()) return 1;
-  int turn = 0;
-  for (size_t off = 0; off < count; off += p.chunk, turn++) {
-    const size_t cc = (count - off < p.chunk) ? count - off : p.chunk;
-    const int l = (p.lanes > 1) ? turn % p.lanes : 0;
-    hipStream_t st = (p.lanes > 1) ? c->lane[l] : c->stream;
-    const FusedScratch s = carve((u64 *)c->ws + (size_t)l * p.chunk * per_ct, p.chunk, nl, SN);
+  // the split kernels read the key's fp64 twin (BFV: the inner-product kernel)
+  return for_each_chunk(c, count, p.chunk, p.lanes, per_ct, (splitc || splitb) ? key : nullptr, [&](hipStream_t st, u64 *scratch, size_t off, size_t cc) {
+    const FusedScratch s = carve(scratch, p.chunk, nl, SN);
     const u64 *tg = target + off * target_stride;
     const u64 *ad = addend ? addend + off * addend_stride : nullptr;
     u64 *o = out + off * 2 * nl * N;
@@ -1489,7 +1436,7 @@ static int run_keyswitch(abc_hip_ctx *c, const u64 *target, size_t target_stride
         else
           launch_split3<1, false>(st, c, s, cc, nl, tg, ad, target_stride, addend_stride, add_c1 ? 1 : 0, key, o, 0u, pack);
         ABC_HIP_CHECK(hipGetLastError());
-        continue;
+        return 0;
       }
       if (splitb) {
         // few ciphertexts in flight: one workgroup per (ct, J, target I) instead of per (ct, J)
@@ -1497,8 +1444,7 @@ static int run_keyswitch(abc_hip_ctx *c, const u64 *target, size_t target_stride
         hipLaunchKernelGGL((k_fused_operand_pass0_fp<LB, false, false>), dim3((unsigned)(cc * nl * (per_target ? nl + 1 : 1))),
                            dim3((1 << LB) / 16), 0, st, c->dc, tg, target_stride, (double *)s.dec, nl, per_target ? 1 : 0, ginv, 1);
         // inner product + inverse tails for every key prime, then the register-only finish (a rotation's addend g(c0): gathered there)
-        if (bsplit_back14(c, st, cc, nl, (const double *)s.dec, (double *)s.ksacc, key, ad, addend_stride, add_c1 ? 1 : 0, o, ginv)) return 1;
-        continue;
+        return bsplit_back14(c, st, cc, nl, (const double *)s.dec, (double *)s.ksacc, key, ad, addend_stride, add_c1 ? 1 : 0, o, ginv);
       }
     }
     // LDS-resident kernels (smaller rings, wider primes, ABC_HIP_NO_SPLIT)
@@ -1514,9 +1460,8 @@ static int run_keyswitch(abc_hip_ctx *c, const u64 *target, size_t target_stride
       coef = s.coef;
       coef_stride = (size_t)nl * N;
     }
-    if (keyswitch_stage<LB>(c, st, s, coef, coef_stride, tg, target_stride, key, ad, addend_stride, add_c1, o, nl, cc, 0)) return 1;
-  }
-  return scope.join();
+    return keyswitch_stage<LB>(c, st, s, coef, coef_stride, tg, target_stride, key, ad, addend_stride, add_c1, o, nl, cc, 0);
+  });
 }
 
 // CKKS rotation with the Galois permutation folded into the key switch (N = 2^14, fp64 split path): in [count][2][nl][N]
@@ -1539,7 +1484,7 @@ int rotate_fused(abc_hip_ctx *c, const u64 *in, u32 elt, const u64 *key, u64 *ou
       if (!count) return 0;
       return run_keyswitch<14>(c, in + pwb, 2 * pwb, key, out, nl, count, in, 2 * pwb, false, elt);
     }
-    if ((c->logn == 13 || ((c->logn == 15 || c->logn == 16) && !c->sw.no_finish_lds)) && bsplit_big_applies(c, nl)) {
+    if ((c->logn == 13 || c->logn == 15 || c->logn == 16) && bsplit_big_applies(c, nl)) {
       if (!count) return 0;
       return bsplit_big(c, in + pwb, 2 * pwb, key, out, nl, count, in, 2 * pwb, false, (u32)host::invmod(elt, 2 * (uint64_t)c->n));
     }

@@ -247,7 +247,7 @@ __global__ __launch_bounds__(256) void k_gsplit_cross(DevCtx c, const double *__
 //   (ct, I, block); the inverse-transform tails of BOTH the special limb and the accumulated data limbs; output
 //   [ct][I][comp] limbs -- k_bsplit_tcoef / k_bsplit_finish_big do the rest.
 template <int LOGN, int NL, bool ALL>
-__global__ __launch_bounds__(NL * 64, (ALL && NL == 8) ? 4 : 1) void k_gsplit_special(DevCtx c, const double *__restrict__ part, const u64 *__restrict__ key,
+__global__ __launch_bounds__(NL * 64, 1) void k_gsplit_special(DevCtx c, const double *__restrict__ part, const u64 *__restrict__ key,
                                                             const double *__restrict__ keyf /* the key's fp64 twin, or null */,
                                                             double *__restrict__ tsp_half, int cc) {
   constexpr int LOGNB = LOGN - 10, NB = 1 << LOGNB, nl = NL;
@@ -276,22 +276,9 @@ __global__ __launch_bounds__(NL * 64, (ALL && NL == 8) ? 4 : 1) void k_gsplit_sp
   const Mod m = mod_at(c, ki);
   const FpTable t = fp_table(c, ki);
   const double q = m.qd, qinv = m.qinv;
-  // NL = 8 (512 threads: one coefficient pair per thread): the key words of that pair are requested BEFORE the transform, so their
-  // latency runs under it instead of being exposed after the barrier (the transform's own per-lane twiddle loads queue up behind
-  // them on the in-order vector-memory counter, which costs nothing: all of it is one burst at the start)
-  constexpr bool PREFETCH = ALL && NL == 8;
-  u64x2 pk0[PREFETCH ? NL : 1], pk1[PREFETCH ? NL : 1];
   // key words: 16 raw bytes per (digit, component) either way -- the fp64 twin's words ARE the (centred) doubles (workgroup-uniform)
   const u64 *__restrict__ kw = keyf ? reinterpret_cast<const u64 *>(keyf) : key;
   auto kd = [&](u64 w) { return keyf ? __longlong_as_double((long long)w) : fp_from_u64(w); };
-  if constexpr (PREFETCH) {
-    const int e = 2 * (int)threadIdx.x;
-#pragma unroll
-    for (int Jx = 0; Jx < NL; Jx++) {
-      pk0[Jx] = *reinterpret_cast<const u64x2 *>(kw + (((size_t)Jx * 2 + 0) * c.K + ki) * N + base + e);
-      pk1[Jx] = *reinterpret_cast<const u64x2 *>(kw + (((size_t)Jx * 2 + 1) * c.K + ki) * N + base + e);
-    }
-  }
   {
     double *buf = dyn + J * lds_words(10);
     const double *__restrict__ src = part + ((ct * (nl + 1) + I) * nl + J) * PS + base;
@@ -305,14 +292,8 @@ __global__ __launch_bounds__(NL * 64, (ALL && NL == 8) ? 4 : 1) void k_gsplit_sp
 #pragma unroll
     for (int Jx = 0; Jx < NL; Jx++) {
       const f64x2 v = *reinterpret_cast<const f64x2 *>(dyn + Jx * lds_words(10) + lds_pad(e));
-      u64x2 k0, k1;
-      if constexpr (PREFETCH) {
-        k0 = pk0[Jx];
-        k1 = pk1[Jx];
-      } else {
-        k0 = *reinterpret_cast<const u64x2 *>(kw + (((size_t)Jx * 2 + 0) * c.K + ki) * N + base + e);
-        k1 = *reinterpret_cast<const u64x2 *>(kw + (((size_t)Jx * 2 + 1) * c.K + ki) * N + base + e);
-      }
+      const u64x2 k0 = *reinterpret_cast<const u64x2 *>(kw + (((size_t)Jx * 2 + 0) * c.K + ki) * N + base + e);
+      const u64x2 k1 = *reinterpret_cast<const u64x2 *>(kw + (((size_t)Jx * 2 + 1) * c.K + ki) * N + base + e);
       s0[0] += g_mulmod(v.x, kd(k0.x), q, qinv);
       s0[1] += g_mulmod(v.y, kd(k0.y), q, qinv);
       s1[0] += g_mulmod(v.x, kd(k1.x), q, qinv);
@@ -338,8 +319,8 @@ __global__ __launch_bounds__(NL * 64, (ALL && NL == 8) ? 4 : 1) void k_gsplit_sp
 }
 
 // ---- G2a for eight digits in TWO rounds of four (BFV, ALL key primes): 256 threads, four transform buffers (35 KiB: four workgroups
-// per CU where the 512-thread form above has two), the sums carried in registers across the rounds, two coefficient pairs per thread.
-// Same arithmetic, same buffers as k_gsplit_special<LOGN, 8, true>.
+// per CU where a 512-thread form of the kernel above had two), the sums carried in registers across the rounds, two coefficient pairs
+// per thread.  Same arithmetic, same buffers as k_gsplit_special<LOGN, NL, true>; the only form for eight digits.
 template <int LOGN>
 __global__ __launch_bounds__(256, 4) void k_bsplit_special8x2(DevCtx c, const double *__restrict__ part, const u64 *__restrict__ key,
                                                                const double *__restrict__ keyf /* the key's fp64 twin, or null */,
@@ -855,9 +836,7 @@ size_t gsplit_scratch_words(const abc_hip_ctx *c, int nl) {
 }
 bool gsplit_applies(const abc_hip_ctx *c, int nl) {
   if (c->logn != 15 || c->scheme != 2 || !c->use_fp || c->sw.no_gsplit || nl < 1 || nl > 15) return false;
-  for (int j = 0; j < c->K; j++)
-    if (!fp_ok(c->h_mods[j].bits)) return false;
-  return true;
+  return all_key_primes(c, fp_ok);
 }
 // one chunk at N = 2^15: mode 0 multiply (opa = a, opb = b), mode 1 key switch (opa = operand in NTT form, opb = addend)
 int gsplit_chunk15(abc_hip_ctx *c, hipStream_t st, u64 *scratch, size_t cc, int nl, int mode, const u64 *opa, const u64 *opb,
@@ -886,18 +865,14 @@ __global__ void k_bsplit_finish_big(DevCtx c, const double *__restrict__ half, c
 // half: [cc][nl+1][2] limbs at stride c->dc.ps; part as written by k_fused_operand_pass0_fp<14, false, false> (padded layout)
 bool bsplit_applies(const abc_hip_ctx *c, int nl) {
   if (c->logn != 14 || c->scheme != 1 || !c->use_fp || c->sw.no_bsplit || nl < 1 || nl > 8) return false;
-  for (int j = 0; j < c->K; j++)
-    if (!fp_ok(c->h_mods[j].bits)) return false;
-  return true;
+  return all_key_primes(c, fp_ok);
 }
-int bsplit_back14(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const double *part, double *half, const u64 *key, const u64 *addend,
-                  size_t addend_stride, int add_c1, u64 *out, u32 ginv) {
-  const dim3 g((unsigned)(cc * (nl + 1) * 16));
+// B2 of the BFV sequences: inner product + inverse tails for every key prime, nl digits
+template <int LOGN>
+static void launch_bsplit_special(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const double *part, const u64 *key, double *half) {
+  const dim3 g((unsigned)(cc * (nl + 1) * (1 << (LOGN - 10))));
   const size_t lds = (size_t)((nl < 2 ? 2 : nl) * lds_words(10)) * 8;
-  if (nl == 8 && !c->sw.no_special8x2) {  // two rounds of four digits, four workgroups per CU: +2 % multiply, +5 % rotate
-    hipLaunchKernelGGL((k_bsplit_special8x2<14>), g, dim3(256), 0, st, c->dc, part, key, key_twin_lookup(c, key), half, (int)cc);
-  } else
-#define ABC_BSP(NLV) hipLaunchKernelGGL((k_gsplit_special<14, NLV, true>), g, dim3(64 * NLV), lds, st, c->dc, part, key, key_twin_lookup(c, key), half, (int)cc)
+#define ABC_BSP(NLV) hipLaunchKernelGGL((k_gsplit_special<LOGN, NLV, true>), g, dim3(64 * NLV), lds, st, c->dc, part, key, key_twin_lookup(c, key), half, (int)cc)
   switch (nl) {
     case 1: ABC_BSP(1); break;
     case 2: ABC_BSP(2); break;
@@ -906,9 +881,15 @@ int bsplit_back14(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const doubl
     case 5: ABC_BSP(5); break;
     case 6: ABC_BSP(6); break;
     case 7: ABC_BSP(7); break;
-    default: ABC_BSP(8); break;
+    default:  // eight digits: two rounds of four, four workgroups per CU (+2 % multiply, +5 % rotate over one round of eight)
+      hipLaunchKernelGGL((k_bsplit_special8x2<LOGN>), g, dim3(256), 0, st, c->dc, part, key, key_twin_lookup(c, key), half, (int)cc);
+      break;
   }
 #undef ABC_BSP
+}
+int bsplit_back14(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const double *part, double *half, const u64 *key, const u64 *addend,
+                  size_t addend_stride, int add_c1, u64 *out, u32 ginv) {
+  launch_bsplit_special<14>(c, st, cc, nl, part, key, half);
   // half occupies the ksacc + tsp regions of the caller's scratch (2 nl + 2 limbs per ciphertext), tco the tlast region behind them
   double *tco = half + cc * 2 * (size_t)(nl + 1) * (size_t)c->dc.ps;
   hipLaunchKernelGGL((k_bsplit_tcoef<14>), dim3((unsigned)(cc * 2 * 4)), dim3(256), 0, st, c->dc, half, tco, nl);
@@ -921,20 +902,7 @@ int bsplit_back14(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const doubl
 // the same three launches behind a `part` of eight blocks (N = 2^13: abc_kernels_bmul.hip writes it behind the floor, as at 2^14)
 int bsplit_back13(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const double *part, double *half, const u64 *key, const u64 *addend,
                   size_t addend_stride, int add_c1, u64 *out, u32 ginv) {
-  const dim3 g((unsigned)(cc * (nl + 1) * 8));
-  const size_t lds = (size_t)((nl < 2 ? 2 : nl) * lds_words(10)) * 8;
-#define ABC_BSP(NLV) hipLaunchKernelGGL((k_gsplit_special<13, NLV, true>), g, dim3(64 * NLV), lds, st, c->dc, part, key, key_twin_lookup(c, key), half, (int)cc)
-  switch (nl) {
-    case 1: ABC_BSP(1); break;
-    case 2: ABC_BSP(2); break;
-    case 3: ABC_BSP(3); break;
-    case 4: ABC_BSP(4); break;
-    case 5: ABC_BSP(5); break;
-    case 6: ABC_BSP(6); break;
-    case 7: ABC_BSP(7); break;
-    default: ABC_BSP(8); break;
-  }
-#undef ABC_BSP
+  launch_bsplit_special<13>(c, st, cc, nl, part, key, half);
   double *tco = half + cc * 2 * (size_t)(nl + 1) * (size_t)c->dc.ps;
   hipLaunchKernelGGL((k_bsplit_tcoef<13>), dim3((unsigned)(cc * 2 * 4)), dim3(256), 0, st, c->dc, half, tco, nl);
   hipLaunchKernelGGL((k_bsplit_finish_big<13>), dim3((unsigned)(cc * 2 * nl * 4)), dim3(256), 0, st, c->dc, half, tco, addend,
@@ -945,8 +913,9 @@ int bsplit_back13(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const doubl
 
 // ---- BFV, N = 2^15 / 2^16 (coefficient-form ciphertexts, every key prime below 2^50): the same three steps with NB = 32 / 64 ----
 // B1 k_bsplit_pass0   (ct, J, key prime I, quarter): digit J of the operand, read as it lies (no reduction modulo q_I is needed in
-//                     fp64), forward cross pass modulo q_I -> half-done limb (ct, I, J)
-// B2 k_gsplit_special<LOGN, NL, true>: tails + inner product + inverse tails, every key prime
+//                     fp64), forward cross pass modulo q_I -> half-done limb (ct, I, J).  In registers at N = 2^13; N = 2^15 / 2^16:
+//                     k_bsplit_pass0_lds, as B4 is k_bsplit_finish_lds there
+// B2 k_gsplit_special<LOGN, NL, true> (eight digits: k_bsplit_special8x2): tails + inner product + inverse tails, every key prime
 // B3 k_bsplit_tcoef   : special limb back to canonical coefficients (+ q_sp/2) -- once per (ct, comp), where the N = 2^14 finish
 //                     kernel recomputes it per data prime from registers (16 values; here it would be 64)
 // B4 k_bsplit_finish_big: inverse cross pass of data limb I, N^-1, subtract, q_sp^-1, addend -> coefficient form
@@ -1058,8 +1027,8 @@ __global__ __launch_bounds__(256) void k_bsplit_finish_big(DevCtx c, const doubl
 
 // B1 through LDS for N = 2^15 / 2^16: workgroup (ct, digit J, group of 32 positions) reads the digit ONCE and runs the forward
 // cross pass modulo every key prime I from registers -- stages 0..RB-1 on blocks 2^RA apart, transposition through 16 KiB of LDS,
-// stages RB..R-1 on 2^RA consecutive blocks: at most eight values per thread (k_bsplit_pass0<16>: 64 values, 209 VGPRs, and one
-// read of the digit per key prime: 72 limb reads per ciphertext where 8 do).
+// stages RB..R-1 on 2^RA consecutive blocks: at most eight values per thread (the register-only k_bsplit_pass0<16>, removed: 64
+// values, 209 VGPRs, and one read of the digit per key prime: 72 limb reads per ciphertext where 8 do).
 template <int LOGN>
 __global__ __launch_bounds__(256) void k_bsplit_pass0_lds(DevCtx c, const u64 *__restrict__ src, size_t src_stride, double *__restrict__ part,
                                                           int nl, u32 ginv /* BFV rotation: elt^-1 mod 2N, the permutation folded into the load */) {
@@ -1132,8 +1101,8 @@ __global__ __launch_bounds__(256) void k_bsplit_pass0_lds(DevCtx c, const u64 *_
 }
 
 // B4 through LDS for N = 2^15 / 2^16: the radix-32 / 64 inverse cross pass as TWO register passes of at most eight values with a
-// transposition in 16 KiB of LDS between them, instead of 32 / 64 values per thread (k_bsplit_finish_big<16>: 256 VGPRs, one
-// wavefront per SIMD, 1.6 TB/s on its bytes).  Workgroup ((ct, comp), I, group of 32 positions); stages R-1..RB run on RA
+// transposition in 16 KiB of LDS between them, instead of 32 / 64 values per thread (the register-only k_bsplit_finish_big<16>,
+// removed: 256 VGPRs, one wavefront per SIMD, 1.6 TB/s on its bytes).  Workgroup ((ct, comp), I, group of 32 positions); stages R-1..RB run on RA
 // consecutive block indices (thread = (group of 2^RA blocks, position)), stages RB-1..0 on blocks 2^RA apart (thread = (block
 // index mod 2^RA, position)), which then finishes its 2^RB coefficients: N^-1, subtract the special limb, q_sp^-1, addend.
 template <int LOGN>
@@ -1217,51 +1186,25 @@ __global__ __launch_bounds__(256) void k_bsplit_finish_lds(DevCtx c, const doubl
 // N = 2^13 (BFVDefault(8192): eight 1024-point blocks, radix-8 cross passes in registers) takes the same sequence
 bool bsplit_big_applies(const abc_hip_ctx *c, int nl) {
   if ((c->logn != 13 && c->logn != 15 && c->logn != 16) || c->scheme != 1 || !c->use_fp || c->sw.no_bsplit || c->sw.no_gsplit || nl < 1 || nl > 8) return false;
-  for (int j = 0; j < c->K; j++)
-    if (!fp_ok(c->h_mods[j].bits)) return false;
-  return true;
+  return all_key_primes(c, fp_ok);
 }
 
 template <int LOGN>
 static int bsplit_big_chunk(abc_hip_ctx *c, hipStream_t st, double *scratch, size_t cc, int nl, const u64 *target, size_t target_stride,
                             const u64 *key, const u64 *addend, size_t addend_stride, int add_c1, u64 *out, u32 ginv = 0) {
-  if (ginv && LOGN > 14 && c->sw.no_finish_lds) { set_error("bsplit: the folded BFV permutation needs the LDS cross passes on these rings"); return 1; }
-  constexpr int NB = 1 << (LOGN - 10);
   const size_t PS = (size_t)c->dc.ps;
   double *part = scratch, *half = part + cc * (size_t)nl * (nl + 1) * PS, *tco = half + cc * 2 * (size_t)(nl + 1) * PS;
   constexpr bool REG = LOGN < 15;  // cross passes of at most 16 values stay in registers
   if constexpr (REG)
     hipLaunchKernelGGL((k_bsplit_pass0<LOGN>), dim3((unsigned)(cc * nl * (nl + 1) * 4)), dim3(256), 0, st, c->dc, target, target_stride, part,
                        nl, ginv);
-  else if (c->sw.no_finish_lds)
-    hipLaunchKernelGGL((k_bsplit_pass0<LOGN>), dim3((unsigned)(cc * nl * (nl + 1) * 4)), dim3(256), 0, st, c->dc, target, target_stride, part,
-                       nl, 0u);
   else
     hipLaunchKernelGGL((k_bsplit_pass0_lds<LOGN>), dim3((unsigned)(cc * nl * 32)), dim3(256), 0, st, c->dc, target, target_stride, part, nl, ginv);
-  const dim3 g((unsigned)(cc * (nl + 1) * NB));
-  const size_t lds = (size_t)((nl < 2 ? 2 : nl) * lds_words(10)) * 8;
-  if (nl == 8 && !c->sw.no_special8x2) {
-    hipLaunchKernelGGL((k_bsplit_special8x2<LOGN>), g, dim3(256), 0, st, c->dc, part, key, key_twin_lookup(c, key), half, (int)cc);
-  } else
-#define ABC_BSPB(NLV) hipLaunchKernelGGL((k_gsplit_special<LOGN, NLV, true>), g, dim3(64 * NLV), lds, st, c->dc, part, key, key_twin_lookup(c, key), half, (int)cc)
-  switch (nl) {
-    case 1: ABC_BSPB(1); break;
-    case 2: ABC_BSPB(2); break;
-    case 3: ABC_BSPB(3); break;
-    case 4: ABC_BSPB(4); break;
-    case 5: ABC_BSPB(5); break;
-    case 6: ABC_BSPB(6); break;
-    case 7: ABC_BSPB(7); break;
-    default: ABC_BSPB(8); break;
-  }
-#undef ABC_BSPB
+  launch_bsplit_special<LOGN>(c, st, cc, nl, part, key, half);
   hipLaunchKernelGGL((k_bsplit_tcoef<LOGN>), dim3((unsigned)(cc * 2 * 4)), dim3(256), 0, st, c->dc, half, tco, nl);
   if constexpr (REG)
     hipLaunchKernelGGL((k_bsplit_finish_big<LOGN>), dim3((unsigned)(cc * 2 * nl * 4)), dim3(256), 0, st, c->dc, half, tco, addend,
                        addend_stride, add_c1, out, nl, ginv);
-  else if (c->sw.no_finish_lds)
-    hipLaunchKernelGGL((k_bsplit_finish_big<LOGN>), dim3((unsigned)(cc * 2 * nl * 4)), dim3(256), 0, st, c->dc, half, tco, addend,
-                       addend_stride, add_c1, out, nl, 0u);
   else
     hipLaunchKernelGGL((k_bsplit_finish_lds<LOGN>), dim3((unsigned)(cc * 2 * nl * 32)), dim3(256), 0, st, c->dc, half, tco, addend,
                        addend_stride, add_c1, out, nl, ginv);
@@ -1276,10 +1219,7 @@ int bsplit_big(abc_hip_ctx *c, const u64 *target, size_t target_stride, const u6
   const size_t per_ct = ((size_t)nl * (nl + 1) + 2 * (size_t)(nl + 1) + 2) * PS;  // part | half | tco (words)
   // N = 2^15 / 2^16: 4 GiB of scratch, i.e. 85 ciphertexts per launch group at N = 2^16, L = 8 (1 GiB = 21: config 5 -3.5 % -- a key
   // slice is fetched once per launch group and XCD, k_bsplit_special8x2)
-  size_t chunk = (((size_t)(c->logn > 14 ? 4 : 1) << 30) / 8) / per_ct;
-  if (chunk < 1) chunk = 1;
-  if (chunk > count) chunk = count;
-  else if (count % chunk && count / chunk < 8) chunk = (count + count / chunk) / (count / chunk + 1);  // even chunks, no runt
+  const size_t chunk = even_chunks((size_t)(c->logn > 14 ? 4 : 1) << 30, per_ct, count);
   if (ensure_workspace(c, chunk * per_ct * 8)) return 1;
   (void)key_twin(c, key);  // the inner-product kernels read the key's fp64 twin where it exists
   for (size_t off = 0; off < count; off += chunk) {

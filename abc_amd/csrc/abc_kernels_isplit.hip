@@ -685,9 +685,7 @@ bool isplit_applies(const abc_hip_ctx *c, int nl) {
       nl > (c->logn == 15 ? 15 : 7))
     return false;
   if (c->logn == 15 && c->sw.no_gsplit) return false;  // one switch turns both split sequences of that ring off (A/B, tests)
-  for (int j = 0; j < c->K; j++)
-    if (c->h_mods[j].bits > 60) return false;
-  return true;
+  return all_key_primes(c, [](u32 bits) { return bits <= 60; });
 }
 
 // one chunk of a multiply (mode 0: opa = a, opb = b) or of a key switch (mode 1: opa = operand in NTT form, opb = addend)
@@ -695,13 +693,9 @@ int isplit_chunk(abc_hip_ctx *c, hipStream_t st, u64 *scratch, size_t cc, int nl
                  size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt) {
   const size_t PS = (size_t)c->dc.ps;
   u64 *part = scratch, *tpart = part + cc * (size_t)nl * (nl + 1) * PS, *tsp = tpart + cc * 2 * (size_t)nl * PS;
-  bool guard = false;
-  for (int j = 0; j < c->K; j++) guard = guard || !unguarded_ok(c->h_mods[j].bits);
+  const bool guard = !all_key_primes(c, unguarded_ok);
   // data primes below 2^50 take the fp64 kernels (ABC_HIP_NO_FP64 / ABC_HIP_NO_MIXED: integers throughout)
-  u32 fpmask = 0;
-  if (c->use_fp && !c->sw.no_mixed)
-    for (int j = 0; j < nl; j++)
-      if (fp_ok(c->h_mods[j].bits)) fpmask |= 1u << j;
+  const u32 fpmask = (c->use_fp && !c->sw.no_mixed) ? data_prime_mask(c, nl, fp_ok) : 0u;
   if (c->logn == 15) {
     u64 *hinv = tsp + cc * 2 * PS;
     const dim3 ga((unsigned)(((cc + 3) / 4) * nl * 32)), gb((unsigned)(cc * nl * 4));

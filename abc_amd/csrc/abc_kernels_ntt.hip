@@ -215,9 +215,7 @@ __global__ __launch_bounds__(256) void k_ntt_inv_strided_fp(DevCtx c, u64 *data,
 constexpr int kBigBlockLB = 12;  // LDS block size used under the strided pass for N > 2^14
 
 static bool all_limbs_fp(const abc_hip_ctx *c, const LimbMap &map, int nl) {
-  bool fp = c->use_fp;
-  for (int j = 0; j < nl; j++) fp = fp && fp_ok(c->h_mods[map.id[j]].bits);
-  return fp;
+  return c->use_fp && all_mapped_primes(c, map, nl, fp_ok);
 }
 
 template <int LB>
@@ -228,9 +226,8 @@ static int launch_block(abc_hip_ctx *c, u64 *d, const LimbMap &map, int nl, size
   dim3 grid((unsigned)(total_limbs << S0)), block((1 << LB) / 16);
   // every limb of the launch must allow the unguarded butterflies.  Behind a strided pre-pass (S0 > 0: guarded, values in
   // [0, 4q)) the at most 12 block stages add 4q each: 52q, inside the 64q the unguarded form is sized for
-  bool guard = false;
   const bool fp = all_limbs_fp(c, map, nl);  // with S0 > 0 the strided pass of the same launch makes the same choice
-  for (int j = 0; j < nl; j++) guard = guard || !unguarded_ok(c->h_mods[map.id[j]].bits);
+  const bool guard = !all_mapped_primes(c, map, nl, unguarded_ok);
   if (fp && fwd)
     hipLaunchKernelGGL(k_ntt_fwd_fp<LB>, grid, block, 0, c->stream, c->dc, d, src, src2, split, map, nl, S0);
   else if (fp)
@@ -382,12 +379,6 @@ int launch_ntt_inv_strided_part(abc_hip_ctx *c, u64 *d, const LimbMap &map, int 
                                       : launch_strided<4>(c, d, map, nl, total_limbs, false, nullptr, nullptr, integer_only);
 }
 int big_block_log(void) { return kBigBlockLB; }
-// N > 2^14: only the block stages of the forward transform, in place, on limbs whose strided first stages a fused kernel has done
-// (abc_kernels_bmul.hip, k_bmul_front): raw doubles in, canonical NTT form out
-int launch_ntt_fwd_block_part(abc_hip_ctx *c, u64 *d, const LimbMap &map, int nl, size_t total_limbs) {
-  if (c->logn != 15 && c->logn != 16) { set_error("forward block part: N = 2^15 / 2^16 only"); return 1; }
-  return launch_block<kBigBlockLB>(c, d, map, nl, total_limbs, c->logn - kBigBlockLB, true);
-}
 
 int launch_ntt_fwd(abc_hip_ctx *c, u64 *d, const LimbMap &map, int nl, size_t total_limbs) {
   return launch_ntt(c, d, map, nl, total_limbs, true);
