@@ -27,7 +27,7 @@ SYMBOLS = [
     "abc_hip_load_relin_key", "abc_hip_load_galois_key", "abc_hip_get_secret_key", "abc_hip_get_public_key",
     "abc_hip_get_relin_key", "abc_hip_get_galois_key", "abc_hip_num_galois_keys", "abc_hip_galois_elt_at",
     "abc_hip_galois_elt_from_step", "abc_hip_batch_encode", "abc_hip_batch_decode", "abc_hip_ckks_encode", "abc_hip_ckks_decode",
-    "abc_hip_encrypt", "abc_hip_decrypt",
+    "abc_hip_encrypt", "abc_hip_decrypt", "abc_hip_noise_budget",
     "abc_hip_add", "abc_hip_sub", "abc_hip_negate", "abc_hip_multiply", "abc_hip_relinearize", "abc_hip_mul_relin",
     "abc_hip_rotate", "abc_hip_apply_galois", "abc_hip_multiply_plain", "abc_hip_add_plain", "abc_hip_sub_plain",
     "abc_hip_rescale", "abc_hip_mod_switch", "abc_hip_ntt_forward", "abc_hip_ntt_inverse", "abc_hip_keyswitch",
@@ -420,6 +420,18 @@ class Context:
         r = self.download(out, shp)
         cb.free(); out.free()
         return r if np.ndim(ct) == 4 else r[0]
+
+    def noise_budget(self, ct):
+        """Invariant noise budget in bits of BFV ciphertexts [size][L][N] (-> int) or [count][size][L][N] (-> np.int32 array),
+        computed on the device: only the budgets come back."""
+        a4 = self._batch(ct, 3)
+        cb = self.upload(a4)
+        out = np.zeros(a4.shape[0], dtype=np.int32)
+        try:
+            self.op("noise_budget", cb.ptr, a4.shape[1], a4.shape[2], out.ctypes.data_as(C.POINTER(C.c_int)), C.c_size_t(a4.shape[0]))
+        finally:
+            cb.free()
+        return out if np.ndim(ct) == 4 else int(out[0])
 
     # ---- HIP-graph capture of an op sequence ----
     def graph_begin(self):

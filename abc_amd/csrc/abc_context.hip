@@ -700,6 +700,7 @@ void abc_hip_ctx_destroy(abc_hip_ctx *c) {
   (void)hipFree(c->d_mods); (void)hipFree(c->d_tw); (void)hipFree(c->d_ftw); (void)hipFree(c->d_cst); (void)hipFree(c->d_cstf);
   (void)hipFree(c->d_slot_map);
   (void)hipFree(c->d_ckks_codec);
+  (void)hipFree(c->d_crt);
   drop_key_twins(c, nullptr);
   (void)hipFree(c->d_sk); (void)hipFree(c->d_pk); (void)hipFree(c->d_relin);
   for (auto &kv : c->d_galois) (void)hipFree(kv.second);
@@ -989,6 +990,11 @@ int abc_hip_decrypt(abc_hip_ctx *c, const uint64_t *ct, int size, int nl, uint64
   CTX_GUARD(c);
   if (nl < 1 || nl > c->L) { set_error("decrypt: bad limb count"); return 1; }
   return decrypt(c, ct, size, nl, p, count);
+}
+int abc_hip_noise_budget(abc_hip_ctx *c, const uint64_t *ct, int size, int nl, int *h_budget, size_t count) {
+  CTX_GUARD(c);
+  NOT_CAPTURABLE(c, "abc_hip_noise_budget");
+  return noise_budget(c, ct, size, nl, h_budget, count);
 }
 
 // ---- evaluator ----

@@ -163,7 +163,8 @@ struct abc_hip_ctx {
   abc::DevConst *d_cst = nullptr;
   abc::DevConstFp *d_cstf = nullptr;
   uint32_t *d_slot_map = nullptr;
-  void *d_ckks_codec = nullptr;  // CKKS slot codec tables (twiddles, twist, slot map, CRT constants), built on first use
+  void *d_ckks_codec = nullptr;  // CKKS slot codec tables (twiddles, twist, slot map), built on first use
+  void *d_crt = nullptr;         // CRT constants of the exact centred lift (abc_crt_lift.hpp), either scheme, built on first use
   // keys (device)
   uint64_t *d_sk = nullptr, *d_pk = nullptr, *d_relin = nullptr;
   std::map<uint32_t, uint64_t *> d_galois;
@@ -250,6 +251,7 @@ int ckks_encode(abc_hip_ctx *c, const double *re, const double *im, size_t value
 int ckks_decode(abc_hip_ctx *c, const u64 *plain, int nl, double scale, double *re, double *im, size_t count);
 int encrypt(abc_hip_ctx *c, const u64 *plain, uint64_t seed, u64 *ct, size_t count);
 int decrypt(abc_hip_ctx *c, const u64 *ct, int size, int nl, u64 *plain, size_t count);
+int noise_budget(abc_hip_ctx *c, const u64 *ct, int size, int nl, int *h_budget, size_t count);  // abc_keys.hip
 int keygen(abc_hip_ctx *c, uint64_t seed);
 int keygen_secure(abc_hip_ctx *c);
 int encrypt_secure(abc_hip_ctx *c, const u64 *plain, u64 *ct, size_t count);

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "abc_context.hpp"
+#include "abc_crt_lift.hpp"
 #include "abc_host_math.hpp"
 
 namespace abc {
@@ -47,37 +48,26 @@ struct alignas(16) cplx {
 __device__ __forceinline__ cplx cmul(cplx a, cplx b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
 __device__ __forceinline__ cplx cmul_conj(cplx a, cplx b) { return {a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y}; }  // a conj(b)
 
-constexpr int kWords = kMaxLimbs;  // Q = q_0 ... q_{nl-1} < 2^(61 nl) fits nl words
-
-// CRT constants of the decoder (uploaded once per context)
-struct CodecConst {
-  u64 rad[kMaxLimbs][kMaxLimbs];  // [j][i] = q_0 ... q_{i-1} mod q_j   (i < j)
-  u64 inv_rad[kMaxLimbs];         // (q_0 ... q_{j-1})^-1 mod q_j
-  u64 Q[kMaxLimbs][kWords];       // [nl-1]: q_0 ... q_{nl-1}, little-endian words
-  u64 Qh[kMaxLimbs][kWords];      // [nl-1]: floor(Q / 2)
-};
-
-// per-context table block: omega[M], zeta[M], p2s[M], CodecConst
+// per-context table block: omega[M], zeta[M], p2s[M]; the CRT constants of the lift are the context's (abc_crt_lift.hpp)
 struct CodecTables {
   const cplx *omega, *zeta;
   const u32 *p2s;
   const CodecConst *k;
 };
-size_t tables_bytes(size_t M) { return M * 16 * 2 + M * 4 + sizeof(CodecConst); }
+size_t tables_bytes(size_t M) { return M * 16 * 2 + M * 4; }
 CodecTables tables_at(const abc_hip_ctx *c) {
   const size_t M = (size_t)c->n / 2;
   char *b = (char *)c->d_ckks_codec;
-  return {(const cplx *)b, (const cplx *)(b + M * 16), (const u32 *)(b + M * 32), (const CodecConst *)(b + M * 36)};
+  return {(const cplx *)b, (const cplx *)(b + M * 16), (const u32 *)(b + M * 32), (const CodecConst *)c->d_crt};
 }
 
 int ensure_tables(abc_hip_ctx *c) {
+  if (ensure_crt_const(c)) return 1;
   if (c->d_ckks_codec) return 0;
-  using namespace host;
   const size_t N = (size_t)c->n, M = N / 2;
   std::vector<char> blk(tables_bytes(M), 0);
   cplx *omega = (cplx *)blk.data(), *zeta = (cplx *)(blk.data() + M * 16);
   u32 *p2s = (u32 *)(blk.data() + M * 32);
-  CodecConst *k = (CodecConst *)(blk.data() + M * 36);
   const long double pi = 3.141592653589793238462643383279502884L;
   for (size_t j = 0; j < M; ++j) {
     const long double a = 2 * pi * (long double)j / (long double)M, z = pi * (long double)j / (long double)N;
@@ -90,26 +80,6 @@ int ensure_tables(abc_hip_ctx *c) {
     if (j & 1) p2s[(N - 1 - j) >> 1] = (u32)i | 0x80000000u;
     else p2s[j >> 1] = (u32)i;
     g = (g * 3) & (2 * N - 1);
-  }
-  uint64_t Q[kWords] = {1};
-  for (int j = 0; j < c->L; ++j) {
-    const uint64_t qj = c->primes[j];
-    uint64_t rad = 1;
-    for (int i = 0; i < j; ++i) {
-      k->rad[j][i] = rad;
-      rad = mulmod(rad, c->primes[i] % qj, qj);
-    }
-    k->inv_rad[j] = invmod(rad, qj);
-    u128 carry = 0;
-    for (int w = 0; w < kWords; ++w) {
-      const u128 p = (u128)Q[w] * qj + carry;
-      Q[w] = (uint64_t)p;
-      carry = p >> 64;
-    }
-    for (int w = 0; w < kWords; ++w) {
-      k->Q[j][w] = Q[w];
-      k->Qh[j][w] = (Q[w] >> 1) | (w + 1 < kWords ? Q[w + 1] << 63 : 0);
-    }
   }
   void *d = nullptr;
   ABC_HIP_CHECK(hipMalloc(&d, blk.size()));
@@ -253,60 +223,9 @@ struct SrcLift {
   const cplx *zeta;
   const CodecConst *k;
   __device__ double lift(const u64 *p) const {  // p: limb 0 of the coefficient; limbs are N words apart
-    // vector loads of the Garner and modulus constants (pointers moved to VGPRs): through the scalar unit the compiler hoists
-    // all of them out of the element loop and spills SGPRs
-    const CodecConst *kp = k;
-    const Mod *mods = c.mods;
-    asm volatile("" : "+v"(kp), "+v"(mods));
-    const CodecConst &kc = *kp;
-    u64 d[NLW];
-#pragma unroll
-    for (int j = 0; j < NLW; ++j) {  // Garner digits: value = d_0 + q_0 (d_1 + q_1 (d_2 + ...))
-      d[j] = 0;
-      if (j < nl) {
-        const Mod m = mods[j];
-        u64 acc = 0;
-#pragma unroll
-        for (int i = 0; i < j; ++i) acc = add_mod(acc, mul_mod(d[i], kc.rad[j][i], m), m.q);  // d_i < 2^61: one Barrett
-        d[j] = mul_mod(sub_mod(p[(size_t)j * c.n], acc, m.q), kc.inv_rad[j], m);
-      }
-    }
+    const size_t n = (size_t)c.n;
     u64 x[NLW];
-#pragma unroll
-    for (int w = 0; w < NLW; ++w) x[w] = 0;
-#pragma unroll
-    for (int j = NLW - 1; j >= 0; --j) {  // Horner from the top digit: x < q_j ... q_{nl-1} fits nl - j words
-      if (j < nl) {
-        const u64 q = mods[j].q;
-        u64 carry = d[j];
-#pragma unroll
-        for (int w = 0; w < NLW - j; ++w) {
-          const u64 lo = x[w] * q, hi = mulhi64(x[w], q), s = lo + carry;
-          carry = hi + (s < lo ? 1ull : 0ull);
-          x[w] = s;
-        }
-      }
-    }
-    const u64 *Q = kc.Q[nl - 1], *Qh = kc.Qh[nl - 1];
-    bool gt = false, decided = false;
-#pragma unroll
-    for (int w = NLW - 1; w >= 0; --w) {
-      const u64 h = Qh[w];
-      if (!decided && x[w] != h) {
-        gt = x[w] > h;
-        decided = true;
-      }
-    }
-    if (gt) {  // x > Q/2: the value is x - Q; take Q - x and negate
-      u64 borrow = 0;
-#pragma unroll
-      for (int w = 0; w < NLW; ++w) {
-        const u64 a = Q[w], t = a - x[w];
-        const u64 nb = (a < x[w] || t < borrow) ? 1ull : 0ull;
-        x[w] = t - borrow;
-        borrow = nb;
-      }
-    }
+    const bool gt = crt_lift_centred<NLW>(c.mods, k, nl, [p, n](int j, const Mod &) { return p[(size_t)j * n]; }, x);
     double v = 0.0;
 #pragma unroll
     for (int w = NLW - 1; w >= 0; --w) v = v * 0x1p64 + (double)x[w];

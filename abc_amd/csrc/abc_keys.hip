@@ -5,6 +5,7 @@
 //           elements), create_relin_keys                                       -> keygen
 //   :12     seal::Encryptor::encrypt (public key, then modulus switch to the data level) -> encrypt
 //   :150    seal::Decryptor::decrypt                                           -> decrypt
+// and src/runtime/SealCiphertext.cpp:80-83 seal::Decryptor::invariant_noise_budget -> noise_budget
 // Randomness is sampled on the host with this repo's sampling spec (DESIGN.md "Sampling spec":
 // splitmix64-seeded xoshiro256**, ternary secrets, 21-vs-21-bit centred binomial errors, rejection
 // sampled uniform residues) -- SEAL's own PRNG stream is not reproducible by design -- and only the
@@ -18,6 +19,7 @@
 #include <vector>
 
 #include "abc_context.hpp"
+#include "abc_crt_lift.hpp"
 #include "abc_host_math.hpp"
 
 namespace abc {
@@ -453,15 +455,14 @@ __global__ __launch_bounds__(256) void k_phase_mul(DevCtx c, const u64 *cn, cons
   }
 }
 
-int decrypt(abc_hip_ctx *c, const u64 *ct, int size, int nl, u64 *plain, size_t count) {
-  if (!c->d_sk) { set_error("decrypt: no secret key"); return 1; }
-  if (size < 2 || size > 3) { set_error("decrypt: ciphertext size must be 2 or 3"); return 1; }
-  if (!count) return 0;
+// c1 s (+ c2 s^2) of `count` ciphertexts into the workspace, coefficient form for BFV (forward NTT of c1.., product with the
+// powers of s, inverse NTT), NTT form for CKKS; the caller adds c0.  `extra` bytes of workspace behind the accumulator are the
+// caller's (*extra_out).
+static int phase_without_c0(abc_hip_ctx *c, const u64 *ct, int size, int nl, size_t count, size_t extra, u64 **acc_out, void **extra_out) {
   const size_t N = (size_t)c->n;
   const bool ckks = (c->scheme == 2);
-  if (!ckks && nl != c->L) { set_error("decrypt: BFV ciphertexts live at the top level"); return 1; }
   const size_t pw = (size_t)nl * N;
-  if (ensure_workspace(c, (count * (size - 1) * pw + count * pw) * 8)) return 1;
+  if (ensure_workspace(c, (count * (size - 1) * pw + count * pw) * 8 + extra)) return 1;
   u64 *cn = (u64 *)c->ws, *acc = cn + count * (size - 1) * pw;
   const LimbMap dmap = key_limb_map(c, nl);
   // copy c1.. (strided inside each ciphertext)
@@ -472,6 +473,22 @@ int decrypt(abc_hip_ctx *c, const u64 *ct, int size, int nl, u64 *plain, size_t 
                      count);
   ABC_HIP_CHECK(hipGetLastError());
   if (!ckks && launch_ntt_inv(c, acc, dmap, nl, count * nl)) return 1;
+  *acc_out = acc;
+  if (extra_out) *extra_out = acc + count * pw;
+  return 0;
+}
+
+int decrypt(abc_hip_ctx *c, const u64 *ct, int size, int nl, u64 *plain, size_t count) {
+  if (!c->d_sk) { set_error("decrypt: no secret key"); return 1; }
+  if (size < 2 || size > 3) { set_error("decrypt: ciphertext size must be 2 or 3"); return 1; }
+  if (!count) return 0;
+  const size_t N = (size_t)c->n;
+  const bool ckks = (c->scheme == 2);
+  if (!ckks && nl != c->L) { set_error("decrypt: BFV ciphertexts live at the top level"); return 1; }
+  const size_t pw = (size_t)nl * N;
+  u64 *acc = nullptr;
+  if (phase_without_c0(c, ct, size, nl, count, 0, &acc, nullptr)) return 1;
+  const LimbMap dmap = key_limb_map(c, nl);
   // + c0
   u64 *dst = ckks ? plain : acc;
   if (ckks) ABC_HIP_CHECK(hipMemcpyAsync(plain, acc, count * pw * 8, hipMemcpyDeviceToDevice, c->stream));
@@ -480,6 +497,71 @@ int decrypt(abc_hip_ctx *c, const u64 *ct, int size, int nl, u64 *plain, size_t 
   ABC_HIP_CHECK(hipGetLastError());
   if (ckks) return 0;
   return launch_bfv_decrypt_round(c, acc, plain, count);
+}
+
+// ---------------- invariant noise budget (BFV) ----------------
+// One thread per (ciphertext, coefficient): v = t (c0 + c1 s + c2 s^2) per limb (acc: the inverse-transformed c1 s + c2 s^2), the
+// exact centred lift of v (abc_crt_lift.hpp), the bit length of its magnitude; the maximum over the wavefront by cross-lane
+// shuffles, over the block's waves through LDS, then one atomicMax per block into bits[ciphertext] (zeroed before the launch).
+// An integer maximum does not depend on the order of arrival.  N is a multiple of the block size (logn >= 10): no tail.
+constexpr int kNoiseThreads = 256;
+
+template <int NLW>
+__global__ __launch_bounds__(kNoiseThreads) void k_noise_bits(DevCtx c, const u64 *__restrict__ acc, const u64 *__restrict__ ct,
+                                                              size_t ct_stride, const CodecConst *__restrict__ k, int nl,
+                                                              int *__restrict__ bits) {
+  __shared__ int wave_max[kNoiseThreads / 64];
+  const size_t N = (size_t)c.n;
+  const size_t b = blockIdx.x >> (c.logn - 8);  // N / 256 blocks per ciphertext
+  const size_t n = ((size_t)(blockIdx.x & ((1u << (c.logn - 8)) - 1u)) << 8) + threadIdx.x;
+  const u64 *pa = acc + b * nl * N + n, *p0 = ct + b * ct_stride + n;
+  const DevConst *cst = c.cst;
+  asm volatile("" : "+v"(cst));  // as the lift's constants: vector loads, no SGPR pressure
+  u64 x[NLW];
+  crt_lift_centred<NLW>(
+      c.mods, k, nl, [=](int j, const Mod &m) { return mul_mod(add_mod(pa[(size_t)j * N], p0[(size_t)j * N], m.q), cst->t_mod_q[j], m); }, x);
+  int v = 0;
+#pragma unroll
+  for (int w = 0; w < NLW; ++w)
+    if (x[w]) v = 64 * w + 64 - __clzll((long long)x[w]);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = max(v, __shfl_xor(v, off, 64));
+  if ((threadIdx.x & 63) == 0) wave_max[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 1; w < kNoiseThreads / 64; ++w) v = max(v, wave_max[w]);
+    atomicMax(bits + b, v);
+  }
+}
+
+int noise_budget(abc_hip_ctx *c, const u64 *ct, int size, int nl, int *h_budget, size_t count) {
+  if (c->scheme != 1) { set_error("noise_budget: the invariant noise budget is defined for BFV only (this is a CKKS context)"); return 1; }
+  if (!c->d_sk) { set_error("noise_budget: no secret key"); return 1; }
+  if (size < 2 || size > 3) { set_error("noise_budget: ciphertext size must be 2 or 3"); return 1; }
+  if (nl != c->L) { set_error("noise_budget: BFV ciphertexts live at the top level (nl = L)"); return 1; }
+  if (!count) return 0;
+  if (!ct || !h_budget) { set_error("noise_budget: null pointer"); return 1; }
+  const size_t blocks_per_ct = (size_t)c->n / kNoiseThreads;
+  if (count > 0x7fffffffu / blocks_per_ct) { set_error("noise_budget: batch too large for one call"); return 1; }
+  if (ensure_crt_const(c)) return 1;
+  const size_t pw = (size_t)nl * c->n;
+  u64 *acc = nullptr;
+  void *extra = nullptr;
+  if (phase_without_c0(c, ct, size, nl, count, count * sizeof(int), &acc, &extra)) return 1;
+  int *d_bits = (int *)extra;
+  ABC_HIP_CHECK(hipMemsetAsync(d_bits, 0, count * sizeof(int), c->stream));
+  const dim3 grid((unsigned)(count * blocks_per_ct)), block(kNoiseThreads);
+  const CodecConst *k = (const CodecConst *)c->d_crt;
+  if (nl <= 4) hipLaunchKernelGGL(k_noise_bits<4>, grid, block, 0, c->stream, c->dc, acc, ct, (size_t)size * pw, k, nl, d_bits);
+  else if (nl <= 8) hipLaunchKernelGGL(k_noise_bits<8>, grid, block, 0, c->stream, c->dc, acc, ct, (size_t)size * pw, k, nl, d_bits);
+  else hipLaunchKernelGGL(k_noise_bits<16>, grid, block, 0, c->stream, c->dc, acc, ct, (size_t)size * pw, k, nl, d_bits);
+  ABC_HIP_CHECK(hipGetLastError());
+  ABC_HIP_CHECK(hipMemcpyAsync(h_budget, d_bits, count * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
+  const int qbits = host::prod_bitlen(std::vector<uint64_t>(c->primes.begin(), c->primes.begin() + c->L));
+  for (size_t i = 0; i < count; ++i) h_budget[i] = std::max(0, qbits - h_budget[i] - 1);
+  return 0;
 }
 
 }  // namespace abc

@@ -1,5 +1,6 @@
 #include "HipCiphertext.hpp"
 
+#include <algorithm>
 #include <cmath>
 
 #include "../../include/abc_hip.h"
@@ -156,8 +157,16 @@ std::unique_ptr<HipCiphertext> HipCiphertext::fresh(int level) const {
 std::unique_ptr<HipCiphertext> HipCiphertext::clone_impl() const { return std::make_unique<HipCiphertext>(*this); }
 std::unique_ptr<AbstractCiphertext> HipCiphertext::clone() const { return clone_impl(); }
 
+std::vector<int> HipCiphertext::noiseBitsBatch() const {
+  const auto &f = getFactory();
+  if (f.isCkks()) throw std::runtime_error("noiseBits: the invariant noise budget is defined for BFV only; this factory runs CKKS.");
+  std::vector<int> bits(f.batchSize());
+  abcHipCheck(abc_hip_noise_budget(f.context(), in(), 2, nl, bits.data(), bits.size()), "noise_budget");
+  return bits;
+}
 int HipCiphertext::noiseBits() const {
-  throw std::runtime_error("noiseBits: invariant noise budget is a host-side diagnostic not provided by the HIP backend.");
+  const std::vector<int> bits = noiseBitsBatch();
+  return *std::min_element(bits.begin(), bits.end());
 }
 
 // ---- ctxt-ctxt ----

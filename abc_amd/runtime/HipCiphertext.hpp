@@ -7,6 +7,7 @@
 #pragma once
 
 #include <memory>
+#include <vector>
 
 #include "plugin_api.hpp"
 
@@ -64,7 +65,11 @@ class HipCiphertext : public AbstractCiphertext {
   [[nodiscard]] double scale() const { return sc; }
   [[nodiscard]] uint64_t *devicePtr();  // for writing: un-shares first
   [[nodiscard]] const HipCiphertextFactory &getFactory() const override;
-  [[nodiscard]] int noiseBits() const;  // SealCiphertext::noiseBits, SealCiphertext.cpp:80-83 (host-side diagnostic)
+  // SealCiphertext::noiseBits, SealCiphertext.cpp:80-83: the invariant noise budget in bits, computed on the device
+  // (abc_hip_noise_budget).  Batch mode: the minimum over the B instances (the one that fails first); noiseBitsBatch gives all B.
+  // Both throw std::runtime_error on a CKKS factory.
+  [[nodiscard]] int noiseBits() const;
+  [[nodiscard]] std::vector<int> noiseBitsBatch() const;
 
   std::unique_ptr<AbstractCiphertext> multiply(const AbstractCiphertext &operand) const override;
   void multiplyInplace(const AbstractCiphertext &operand) override;

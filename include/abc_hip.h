@@ -127,6 +127,14 @@ int abc_hip_encrypt_secure(abc_hip_ctx *ctx, const uint64_t *d_plain, uint64_t *
 int abc_hip_encrypt(abc_hip_ctx *ctx, const uint64_t *d_plain, uint64_t seed, uint64_t *d_ct, size_t count);
 /* seal::Decryptor::decrypt (SealCiphertextFactory.cpp:150); size = 2 or 3 polynomials */
 int abc_hip_decrypt(abc_hip_ctx *ctx, const uint64_t *d_ct, int size, int nl, uint64_t *d_plain, size_t count);
+/* Decryptor::invariant_noise_budget (SealCiphertext.cpp:80-83): BFV only, secret key required, size = 2 or 3, nl = L.
+ * d_ct [count][size][nl][N] coefficient form -> h_budget [count] HOST ints, one per ciphertext:
+ *   v = t (c0 + c1 s + c2 s^2) mod Q, Q = q_0 ... q_{L-1}, lifted coefficient-wise into (-Q/2, Q/2] (exact, integers only);
+ *   m = the largest |coefficient|; budget = max(0, bitlen(Q) - bitlen(m) - 1), bitlen(0) = 0.
+ * A positive budget means the ciphertext still decrypts.  Everything runs on the device; the only transfer is the read-back of
+ * `count` ints (one stream synchronisation): not capturable.  A CKKS context, a missing secret key, another size or another
+ * level fail the call (non-zero status); count = 0 succeeds. */
+int abc_hip_noise_budget(abc_hip_ctx *ctx, const uint64_t *d_ct, int size, int nl, int *h_budget, size_t count);
 
 /* ---- evaluator: replaces the seal::Evaluator calls in src/runtime/SealCiphertext.cpp ---- */
 /* Evaluator::add / add_inplace (:92,:114) */

@@ -89,6 +89,11 @@ def main():
             "bfv%d_add" % n: lambda: g.op("add", a.ptr, b.ptr, out.ptr, 2, L, cb),
             "bfv%d_multiply_plain" % n: lambda: g.op("multiply_plain", a.ptr, plain.ptr, C.c_size_t(0), out.ptr, 2, L, cb),
         }
+        # decrypt and the invariant noise budget of the same batch: the budget runs decrypt's transforms, then the exact lift and
+        # the maximum in place of the rounding, and reads B ints back (its one synchronisation is inside the timed call)
+        dec, budgets = g.alloc(B * n * 8), (C.c_int * B)()
+        ops["bfv%d_decrypt" % n] = lambda: g.op("decrypt", a.ptr, 2, L, dec.ptr, cb)
+        ops["bfv%d_noise_budget" % n] = lambda: g.op("noise_budget", a.ptr, 2, L, budgets, cb)
         for k, fn in ops.items():
             ms = timeit(g, fn)
             res[k] = {"batch": B, "ms": ms, "ops_per_s": B / ms * 1e3}
@@ -108,7 +113,7 @@ def main():
         g.graph_destroy(ge)
         res["bfv%d_mul_relin_graph_latency_ms" % n] = ms
         print("%-40s %8.3f ms (batch 1, HIP graph replay)" % ("bfv%d_mul_relin latency" % n, ms), flush=True)
-        del a, b, out
+        del a, b, out, dec
         g.close()
     os.makedirs("gpurun_out", exist_ok=True)
     json.dump(res, open("gpurun_out/op_bench.json", "w"), indent=1)
