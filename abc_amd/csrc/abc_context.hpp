@@ -7,6 +7,8 @@
 #include <mutex>
 #include <unordered_map>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "abc_modarith.hpp"
@@ -269,15 +271,45 @@ int gsplit_chunk15(abc_hip_ctx *c, hipStream_t st, u64 *scratch, size_t cc, int 
                    size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt);
 void gsplit_front14(hipStream_t st, abc_hip_ctx *c, size_t cc, int nl, int mode, const u64 *opa, const u64 *opb, size_t opa_stride,
                     double *hinv, double *part, u32 gelt, int pack = 0);
-bool split4_main_subset(hipStream_t st, abc_hip_ctx *c, size_t cc, int nl, int mode, const double *part, const double *tpart, const u64 *opa,
-                        const u64 *opb, size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt, u32 imap,
-                        int ni);
-bool gsplit_main_subset15(hipStream_t st, abc_hip_ctx *c, size_t cc, int nl, int mode, const double *part, const double *tpart, const u64 *opa,
-                          const u64 *opb, size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt, u32 imap,
-                          int ni);
-void gsplit_main_deep_subset15(hipStream_t st, abc_hip_ctx *c, size_t cc, int nl, int mode, const double *part, const double *tpart,
-                               const u64 *opa, const u64 *opb, size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out,
-                               u32 gelt, u64 imap, int ni);
+// ---- the main step of the split key switch (k_split4_main_fp, k_gsplit_main[_deep], k_isplit_main[_deep]): host side ----
+// its arguments, as the launchers pass them along (the kernels' own argument lists are spelled once, at the launch)
+struct MainArgs {
+  hipStream_t st;
+  size_t cc;  // ciphertexts in the chunk
+  int nl;
+  const void *part, *tpart;  // half-done decomposition / mod-down limbs (doubles or u64: the arithmetic of the kernel)
+  const u64 *opa, *opb;      // mode 0: a, b; mode 1: operand in NTT form, addend (or null)
+  size_t opa_stride, opb_stride;
+  int add_c1;
+  const u64 *key;
+  u64 *out;
+  u32 gelt;
+  u64 imap;  // nibble s = data prime of grid slot s (kAllSlots with ni = nl: all of them; the 512-thread kernels read eight nibbles)
+  int ni;    // slots
+  int pack;  // the half-done limbs are packed (abc_ntt.hpp; k_split4_main_fp only)
+};
+constexpr u64 kAllSlots = 0xfedcba9876543210ull;
+constexpr size_t main_lds_bytes(int nl) { return (size_t)((nl + 1) * lds_words(10)) * 8 + 1024 * 16; }  // nl + 1 buffers + twiddle table
+// (mode, gelt) -> f(MODE, GAL) as integral constants: multiply / key switch with the Galois gather folded in / plain key switch
+template <class Fn>
+inline void dispatch_mode(int mode, u32 gelt, Fn f) {
+  if (mode == 0) f(std::integral_constant<int, 0>{}, std::false_type{});
+  else if (gelt) f(std::integral_constant<int, 1>{}, std::true_type{});
+  else f(std::integral_constant<int, 1>{}, std::false_type{});
+}
+// nl -> f(NL) as an integral constant, NL = nl clamped to [LO, HI]
+template <int LO, class Fn, int... Is>
+inline void dispatch_nl_seq(int nl, Fn &f, std::integer_sequence<int, Is...>) {
+  (void)(((nl == LO + Is) && (f(std::integral_constant<int, LO + Is>{}), true)) || ...);
+}
+template <int LO, int HI, class Fn>
+inline void dispatch_nl(int nl, Fn f) {
+  dispatch_nl_seq<LO>(nl < LO ? LO : nl > HI ? HI : nl, f, std::make_integer_sequence<int, HI - LO + 1>{});
+}
+// over the slots of a.imap: all data primes, or the fp64-capable ones of a mixed chain (abc_kernels_isplit.hip).
+// split4_main (N = 2^14): false = not applicable (more than seven limbs); gsplit_main15: any nl <= 15 (above seven: the deep kernel)
+bool split4_main(abc_hip_ctx *c, int mode, const MainArgs &a);
+void gsplit_main15(abc_hip_ctx *c, int mode, const MainArgs &a);
 bool bsplit_applies(const abc_hip_ctx *c, int nl);
 bool bsplit_big_applies(const abc_hip_ctx *c, int nl);
 bool iks_bfv_applies(const abc_hip_ctx *c, int nl);  // abc_kernels_eval.hip

@@ -332,13 +332,6 @@ void release_key(abc_hip_ctx *c, u64 *key) {
 // arithmetic").  Same buffers, same u64 memory format, bit-identical results; only the arithmetic between the HBM
 // load and the HBM store differs.
 // ---------------------------------------------------------------------------------------------------------------
-// x*y mod q for two residues |x|, |y| <= q: |result| < q  (|x y / q| 2^-52 <= 1/4, plus the rounding 1/2)
-__device__ __forceinline__ double fp_mulmod(double x, double y, double q, double qinv) {
-  const double h = x * y;
-  const double l = __builtin_fma(x, y, -h);
-  const double c = __builtin_rint(h * qinv);
-  return __builtin_fma(-c, q, h) + l;
-}
 // four consecutive words as two adjacent 16-byte stores
 __device__ __forceinline__ void store_run4(u64 *p, const u64 (&v)[4]) {
   reinterpret_cast<u64x2 *>(p)[0] = u64x2{v[0], v[1]};
@@ -957,13 +950,13 @@ __global__ __launch_bounds__(NL ? (NL + 1) * 64 : 832) void k_split3_main_fp(Dev
 }
 
 template <int MODE, bool GAL>
-static void launch_split3_main(hipStream_t st, abc_hip_ctx *c, size_t cc, int nl, const double *part, const double *tpart, const u64 *opa,
-                               const u64 *opb, size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt) {
-  const dim3 grid((unsigned)(cc * nl * 16)), block(64 * (nl + 1));
+static void launch_split3_main(abc_hip_ctx *c, const MainArgs &a) {
+  const int nl = a.nl;
+  const dim3 grid((unsigned)(a.cc * nl * 16)), block(64 * (nl + 1));
   const size_t lds = (size_t)((nl + 1) * lds_words(10)) * 8;
-#define ABC_TM3(NLV)                                                                                                                 \
-  hipLaunchKernelGGL((k_split3_main_fp<MODE, GAL, NLV>), grid, block, lds, st, c->dc, part, tpart, opa, opb, opa_stride, opb_stride, \
-                     add_c1, key, out, nl, gelt)
+#define ABC_TM3(NLV)                                                                                                             \
+  hipLaunchKernelGGL((k_split3_main_fp<MODE, GAL, NLV>), grid, block, lds, a.st, c->dc, (const double *)a.part, (const double *)a.tpart, \
+                     a.opa, a.opb, a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, nl, a.gelt)
   switch (nl) {
     case 1: ABC_TM3(1); break;
     case 2: ABC_TM3(2); break;
@@ -1154,55 +1147,34 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_split4_main_fp(DevCtx 
   else compute_pair(2 * (int)threadIdx.x, ops, std::false_type{});
 }
 
-template <int MODE, bool GAL>
-static bool launch_split4_main(hipStream_t st, abc_hip_ctx *c, size_t cc, int nl, const double *part, const double *tpart, const u64 *opa,
-                               const u64 *opb, size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt,
-                               u32 imap = 0x76543210u, int ni = -1, int pack = 0) {
-  if (nl < 1 || nl > 7) return false;  // nl + 1 transform buffers of 8.5 KiB + the table: two workgroups per CU up to nl = 6, one at 7
-  if (ni < 0) ni = nl;
-  if (ni == 0) return true;
-  const dim3 grid((unsigned)(cc * ni * 16)), block(512);
-  const size_t lds = (size_t)((nl + 1) * lds_words(10)) * 8 + 1024 * 16;
-#define ABC_TM4(NLV)                                                                                                                 \
-  hipLaunchKernelGGL((k_split4_main_fp<MODE, GAL, NLV>), grid, block, lds, st, c->dc, part, tpart, opa, opb, opa_stride, opb_stride, \
-                     add_c1, key, out, gelt, imap, ni, pack, keyf)
-  const double *keyf = key_twin_lookup(c, key);
-  switch (nl) {
-    case 1: ABC_TM4(1); break;
-    case 2: ABC_TM4(2); break;
-    case 3: ABC_TM4(3); break;
-    case 4: ABC_TM4(4); break;
-    case 5: ABC_TM4(5); break;
-    case 6: ABC_TM4(6); break;
-    default: ABC_TM4(7); break;
-  }
-#undef ABC_TM4
+// over the slots of a.imap; mode 0 multiply, mode 1 key switch
+bool split4_main(abc_hip_ctx *c, int mode, const MainArgs &a) {
+  if (a.nl < 1 || a.nl > 7) return false;  // nl + 1 transform buffers of 8.5 KiB + the table: two workgroups per CU up to nl = 6, one at 7
+  if (a.ni == 0) return true;
+  const dim3 grid((unsigned)(a.cc * a.ni * 16)), block(512);
+  const double *keyf = key_twin_lookup(c, a.key);
+  // a.part / a.tpart: raw or packed doubles here (a mixed chain's fp64 limbs: written as doubles by the integer sequence's first steps)
+  dispatch_mode(mode, a.gelt, [&](auto M, auto G) {
+    dispatch_nl<1, 7>(a.nl, [&](auto NL) {
+      hipLaunchKernelGGL((k_split4_main_fp<decltype(M)::value, decltype(G)::value, decltype(NL)::value>), grid, block, main_lds_bytes(a.nl),
+                         a.st, c->dc, (const double *)a.part, (const double *)a.tpart, a.opa, a.opb, a.opa_stride, a.opb_stride, a.add_c1,
+                         a.key, a.out, a.gelt, (u32)a.imap, a.ni, a.pack, keyf);
+    });
+  });
   return true;
 }
-// the same launch over a subset of the data primes (mixed chains, abc_kernels_isplit.hip): mode 0 multiply, mode 1 key switch
-bool split4_main_subset(hipStream_t st, abc_hip_ctx *c, size_t cc, int nl, int mode, const double *part, const double *tpart, const u64 *opa,
-                        const u64 *opb, size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt, u32 imap,
-                        int ni) {
-  if (mode == 0) return launch_split4_main<0, false>(st, c, cc, nl, part, tpart, opa, opb, opa_stride, opb_stride, add_c1, key, out, gelt, imap, ni);
-  if (gelt) return launch_split4_main<1, true>(st, c, cc, nl, part, tpart, opa, opb, opa_stride, opb_stride, add_c1, key, out, gelt, imap, ni);
-  return launch_split4_main<1, false>(st, c, cc, nl, part, tpart, opa, opb, opa_stride, opb_stride, add_c1, key, out, gelt, imap, ni);
-}
 
-
-// K2a..K2c on one chunk (the half-done decomposition limbs are in s.dec)
-template <int MODE, bool GAL>
-static void launch_split3(hipStream_t st, abc_hip_ctx *c, const FusedScratch &s, size_t cc, int nl, const u64 *opa, const u64 *opb,
-                          size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt, int pack) {
-  launch_split_special(st, c, cc, nl, (const double *)s.dec, key, (double *)s.tsp);
-  hipLaunchKernelGGL(k_split3_pass_fp<14>, dim3((unsigned)(cc * 2 * 4)), dim3(256), 0, st, c->dc, (const double *)s.tsp, (double *)s.ksacc,
-                     nl, pack);
+// K2a..K2c on one chunk (the half-done decomposition limbs are in s.dec; a.part / a.tpart are filled in here)
+static void launch_split3(abc_hip_ctx *c, const FusedScratch &s, int mode, MainArgs a) {
+  a.part = s.dec;
+  a.tpart = s.ksacc;
+  launch_split_special(a.st, c, a.cc, a.nl, (const double *)s.dec, a.key, (double *)s.tsp);
+  hipLaunchKernelGGL(k_split3_pass_fp<14>, dim3((unsigned)(a.cc * 2 * 4)), dim3(256), 0, a.st, c->dc, (const double *)s.tsp,
+                     (double *)s.ksacc, a.nl, a.pack);
   // (measured at nl = 5 / 6 / 7, every prime below 2^50: +9.5 / -5 / -14 % against k_split3_main_fp: above five limbs the prefetched
   // key words push the kernel past 128 VGPRs and to one workgroup per CU)
-  if (!c->sw.no_split4 && nl <= 5 && launch_split4_main<MODE, GAL>(st, c, cc, nl, (const double *)s.dec, (const double *)s.ksacc, opa, opb,
-                                                        opa_stride, opb_stride, add_c1, key, out, gelt, 0x76543210u, -1, pack))
-    return;
-  launch_split3_main<MODE, GAL>(st, c, cc, nl, (const double *)s.dec, (const double *)s.ksacc, opa, opb, opa_stride, opb_stride, add_c1,
-                                key, out, gelt);
+  if (!c->sw.no_split4 && a.nl <= 5 && split4_main(c, mode, a)) return;
+  dispatch_mode(mode, a.gelt, [&](auto M, auto G) { launch_split3_main<decltype(M)::value, decltype(G)::value>(c, a); });
 }
 
 // packed half-done limbs (abc_ntt.hpp): only the sequence whose consumer is k_split4_main_fp reads them
@@ -1355,7 +1327,8 @@ static int run_mul_relin(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out, i
         else
           hipLaunchKernelGGL(k_split2_tensor_pass0_fp<LB>, dim3((unsigned)(cc * nl)), dim3((1 << LB) / 16), 0, st, c->dc, a + off * ctw,
                              b + off * ctw, (double *)s.dec, nl, pack);
-        launch_split3<0, false>(st, c, s, cc, nl, a + off * ctw, b + off * ctw, 0, 0, 0, c->d_relin, out + off * ctw, 0u, pack);
+        launch_split3(c, s, 0, MainArgs{st, cc, nl, nullptr, nullptr, a + off * ctw, b + off * ctw, 0, 0, 0, c->d_relin, out + off * ctw, 0u,
+                                        kAllSlots, nl, pack});
         ABC_HIP_CHECK(hipGetLastError());
         return 0;
       }
@@ -1431,10 +1404,8 @@ static int run_keyswitch(abc_hip_ctx *c, const u64 *target, size_t target_stride
           hipLaunchKernelGGL((gelt ? k_fused_operand_pass0_fp<LB, true, true> : k_fused_operand_pass0_fp<LB, true, false>),
                              dim3((unsigned)(cc * nl)), dim3((1 << LB) / 16), 0, st, c->dc, tg, target_stride, (double *)s.dec, nl, 0,
                              gelt, 1 | (pack ? 2 : 0));
-        if (gelt)
-          launch_split3<1, true>(st, c, s, cc, nl, tg, ad, target_stride, addend_stride, add_c1 ? 1 : 0, key, o, gelt, pack);
-        else
-          launch_split3<1, false>(st, c, s, cc, nl, tg, ad, target_stride, addend_stride, add_c1 ? 1 : 0, key, o, 0u, pack);
+        launch_split3(c, s, 1, MainArgs{st, cc, nl, nullptr, nullptr, tg, ad, target_stride, addend_stride, add_c1 ? 1 : 0, key, o, gelt,
+                                        kAllSlots, nl, pack});
         ABC_HIP_CHECK(hipGetLastError());
         return 0;
       }

@@ -19,13 +19,6 @@
 
 namespace abc {
 
-__device__ __forceinline__ double g_mulmod(double x, double y, double q, double qinv) {
-  const double h = x * y;
-  const double l = __builtin_fma(x, y, -h);
-  const double c = __builtin_rint(h * qinv);
-  return __builtin_fma(-c, q, h) + l;
-}
-
 // ---- G1a ----
 // MODE 0: multiply (a, b: [ct][2][nl][N], operand = a1 b1).  MODE 1: operand in NTT form at a + ct * a_stride (Galois gather).
 template <int LOGN, int MODE, bool GAL>
@@ -54,10 +47,10 @@ __global__ __launch_bounds__(256) void k_gsplit_inv_tails(DevCtx c, const u64 *_
         const u64 *pa = a1 + 4 * (lane + 64 * g), *pb = b1 + 4 * (lane + 64 * g);
         const u64x2 a0v = reinterpret_cast<const u64x2 *>(pa)[0], a1v = reinterpret_cast<const u64x2 *>(pa)[1];
         const u64x2 b0v = reinterpret_cast<const u64x2 *>(pb)[0], b1v = reinterpret_cast<const u64x2 *>(pb)[1];
-        x[4 * g + 0] = g_mulmod(fp_from_u64(a0v.x), fp_from_u64(b0v.x), m.qd, m.qinv);
-        x[4 * g + 1] = g_mulmod(fp_from_u64(a0v.y), fp_from_u64(b0v.y), m.qd, m.qinv);
-        x[4 * g + 2] = g_mulmod(fp_from_u64(a1v.x), fp_from_u64(b1v.x), m.qd, m.qinv);
-        x[4 * g + 3] = g_mulmod(fp_from_u64(a1v.y), fp_from_u64(b1v.y), m.qd, m.qinv);
+        x[4 * g + 0] = fp_mulmod(fp_from_u64(a0v.x), fp_from_u64(b0v.x), m.qd, m.qinv);
+        x[4 * g + 1] = fp_mulmod(fp_from_u64(a0v.y), fp_from_u64(b0v.y), m.qd, m.qinv);
+        x[4 * g + 2] = fp_mulmod(fp_from_u64(a1v.x), fp_from_u64(b1v.x), m.qd, m.qinv);
+        x[4 * g + 3] = fp_mulmod(fp_from_u64(a1v.y), fp_from_u64(b1v.y), m.qd, m.qinv);
       }
     } else {
       const u64 *__restrict__ sp = a + ct * a_stride + (size_t)j * N;
@@ -294,10 +287,10 @@ __global__ __launch_bounds__(NL * 64, 1) void k_gsplit_special(DevCtx c, const d
       const f64x2 v = *reinterpret_cast<const f64x2 *>(dyn + Jx * lds_words(10) + lds_pad(e));
       const u64x2 k0 = *reinterpret_cast<const u64x2 *>(kw + (((size_t)Jx * 2 + 0) * c.K + ki) * N + base + e);
       const u64x2 k1 = *reinterpret_cast<const u64x2 *>(kw + (((size_t)Jx * 2 + 1) * c.K + ki) * N + base + e);
-      s0[0] += g_mulmod(v.x, kd(k0.x), q, qinv);
-      s0[1] += g_mulmod(v.y, kd(k0.y), q, qinv);
-      s1[0] += g_mulmod(v.x, kd(k1.x), q, qinv);
-      s1[1] += g_mulmod(v.y, kd(k1.y), q, qinv);
+      s0[0] += fp_mulmod(v.x, kd(k0.x), q, qinv);
+      s0[1] += fp_mulmod(v.y, kd(k0.y), q, qinv);
+      s1[0] += fp_mulmod(v.x, kd(k1.x), q, qinv);
+      s1[1] += fp_mulmod(v.y, kd(k1.y), q, qinv);
       if (NL > 8 && (Jx & 7) == 7) {  // eight products of magnitude < q stay below 2^53; re-centre before adding more
         s0[0] = fp_centre(s0[0], q, qinv); s0[1] = fp_centre(s0[1], q, qinv);
         s1[0] = fp_centre(s1[0], q, qinv); s1[1] = fp_centre(s1[1], q, qinv);
@@ -369,10 +362,10 @@ __global__ __launch_bounds__(256, 4) void k_bsplit_special8x2(DevCtx c, const do
           y0.x = fp_from_u64(k0.x); y0.y = fp_from_u64(k0.y);
           y1.x = fp_from_u64(k1.x); y1.y = fp_from_u64(k1.y);
         }
-        s0[pp][0] += g_mulmod(v.x, y0.x, q, qinv);
-        s0[pp][1] += g_mulmod(v.y, y0.y, q, qinv);
-        s1[pp][0] += g_mulmod(v.x, y1.x, q, qinv);
-        s1[pp][1] += g_mulmod(v.y, y1.y, q, qinv);
+        s0[pp][0] += fp_mulmod(v.x, y0.x, q, qinv);
+        s0[pp][1] += fp_mulmod(v.y, y0.y, q, qinv);
+        s1[pp][0] += fp_mulmod(v.x, y1.x, q, qinv);
+        s1[pp][1] += fp_mulmod(v.y, y1.y, q, qinv);
       }
     }
   }
@@ -559,9 +552,9 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_gsplit_main(DevCtx c, 
         const double y0[2] = {fp_from_u64(o.b0.x), fp_from_u64(o.b0.y)}, y1[2] = {fp_from_u64(o.b1.x), fp_from_u64(o.b1.y)};
 #pragma unroll
         for (int k = 0; k < 2; k++) {
-          x[k] = g_mulmod(x1[k], y1[k], q, qinv);
-          d0[k] = g_mulmod(x0[k], y0[k], q, qinv);
-          d1[k] = g_mulmod(x0[k], y1[k], q, qinv) + g_mulmod(x1[k], y0[k], q, qinv);
+          x[k] = fp_mulmod(x1[k], y1[k], q, qinv);
+          d0[k] = fp_mulmod(x0[k], y0[k], q, qinv);
+          d1[k] = fp_mulmod(x0[k], y1[k], q, qinv) + fp_mulmod(x1[k], y0[k], q, qinv);
         }
       } else {
 #pragma unroll
@@ -577,10 +570,10 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_gsplit_main(DevCtx c, 
       x[0] = v.x;
       x[1] = v.y;
     }
-    s0[0] += g_mulmod(x[0], fp_from_u64(o.k0[Jx].x), q, qinv);
-    s0[1] += g_mulmod(x[1], fp_from_u64(o.k0[Jx].y), q, qinv);
-    s1[0] += g_mulmod(x[0], fp_from_u64(o.k1[Jx].x), q, qinv);
-    s1[1] += g_mulmod(x[1], fp_from_u64(o.k1[Jx].y), q, qinv);
+    s0[0] += fp_mulmod(x[0], fp_from_u64(o.k0[Jx].x), q, qinv);
+    s0[1] += fp_mulmod(x[1], fp_from_u64(o.k0[Jx].y), q, qinv);
+    s1[0] += fp_mulmod(x[0], fp_from_u64(o.k1[Jx].x), q, qinv);
+    s1[1] += fp_mulmod(x[1], fp_from_u64(o.k1[Jx].y), q, qinv);
   }
   const f64x2 u0 = *reinterpret_cast<const f64x2 *>(tt0 + lds_pad(e)), u1 = *reinterpret_cast<const f64x2 *>(tt1 + lds_pad(e));
   u64x2 r;
@@ -657,9 +650,9 @@ __global__ __launch_bounds__(1024) void k_gsplit_main_deep(DevCtx c, const doubl
         const double y0[2] = {fp_from_u64(b0.x), fp_from_u64(b0.y)}, y1[2] = {fp_from_u64(b1.x), fp_from_u64(b1.y)};
 #pragma unroll
         for (int k = 0; k < 2; k++) {
-          x[k] = g_mulmod(x1[k], y1[k], q, qinv);
-          d0[k] = g_mulmod(x0[k], y0[k], q, qinv);
-          d1[k] = g_mulmod(x0[k], y1[k], q, qinv) + g_mulmod(x1[k], y0[k], q, qinv);
+          x[k] = fp_mulmod(x1[k], y1[k], q, qinv);
+          d0[k] = fp_mulmod(x0[k], y0[k], q, qinv);
+          d1[k] = fp_mulmod(x0[k], y1[k], q, qinv) + fp_mulmod(x1[k], y0[k], q, qinv);
         }
       } else {
         const u64 *xl = opa + ct * opa_stride + (size_t)I * N;
@@ -682,10 +675,10 @@ __global__ __launch_bounds__(1024) void k_gsplit_main_deep(DevCtx c, const doubl
     }
     const u64x2 k0 = *reinterpret_cast<const u64x2 *>(key + (((size_t)Jx * 2 + 0) * c.K + I) * N + base + e);
     const u64x2 k1 = *reinterpret_cast<const u64x2 *>(key + (((size_t)Jx * 2 + 1) * c.K + I) * N + base + e);
-    s0[0] += g_mulmod(x[0], fp_from_u64(k0.x), q, qinv);
-    s0[1] += g_mulmod(x[1], fp_from_u64(k0.y), q, qinv);
-    s1[0] += g_mulmod(x[0], fp_from_u64(k1.x), q, qinv);
-    s1[1] += g_mulmod(x[1], fp_from_u64(k1.y), q, qinv);
+    s0[0] += fp_mulmod(x[0], fp_from_u64(k0.x), q, qinv);
+    s0[1] += fp_mulmod(x[1], fp_from_u64(k0.y), q, qinv);
+    s1[0] += fp_mulmod(x[0], fp_from_u64(k1.x), q, qinv);
+    s1[1] += fp_mulmod(x[1], fp_from_u64(k1.y), q, qinv);
     if ((Jx & 7) == 7) {
 #pragma unroll
       for (int k = 0; k < 2; k++) {
@@ -712,12 +705,11 @@ static void launch_gsplit_front(hipStream_t st, abc_hip_ctx *c, size_t cc, int n
   constexpr int NB = 1 << (LOGN - 10);
   const dim3 g1((unsigned)(((cc + 3) / 4) * nl * NB)), g2((unsigned)(cc * nl * (LOGN > 14 ? 32 : 4)));
   const size_t lds = (size_t)(4 * lds_words(10)) * 8 + 1024 * 16;
-  if (mode == 0)
-    hipLaunchKernelGGL((k_gsplit_inv_tails<LOGN, 0, false>), g1, dim3(256), lds, st, c->dc, opa, opb, 0, hinv, nl, (int)cc, 0u);
-  else if (gelt)
-    hipLaunchKernelGGL((k_gsplit_inv_tails<LOGN, 1, true>), g1, dim3(256), lds, st, c->dc, opa, nullptr, opa_stride, hinv, nl, (int)cc, gelt);
-  else
-    hipLaunchKernelGGL((k_gsplit_inv_tails<LOGN, 1, false>), g1, dim3(256), lds, st, c->dc, opa, nullptr, opa_stride, hinv, nl, (int)cc, 0u);
+  dispatch_mode(mode, gelt, [&](auto M, auto G) {
+    constexpr int MODE = decltype(M)::value;
+    hipLaunchKernelGGL((k_gsplit_inv_tails<LOGN, MODE, decltype(G)::value>), g1, dim3(256), lds, st, c->dc, opa, MODE ? nullptr : opb,
+                       MODE ? opa_stride : 0, hinv, nl, (int)cc, gelt);
+  });
   hipLaunchKernelGGL((k_gsplit_cross<LOGN>), g2, dim3(256), 0, st, c->dc, hinv, part, nl, pack);
 }
 void gsplit_front14(hipStream_t st, abc_hip_ctx *c, size_t cc, int nl, int mode, const u64 *opa, const u64 *opb, size_t opa_stride,
@@ -725,109 +717,41 @@ void gsplit_front14(hipStream_t st, abc_hip_ctx *c, size_t cc, int nl, int mode,
   launch_gsplit_front<14>(st, c, cc, nl, mode, opa, opb, opa_stride, hinv, part, gelt, pack);
 }
 
+// G2c over the slots of a.imap: up to seven limbs k_gsplit_main, deep chains (one wavefront per limb still, up to sixteen of
+// them) k_gsplit_main_deep
 template <int LOGN>
-static void launch_gsplit_back(hipStream_t st, abc_hip_ctx *c, size_t cc, int nl, int mode, const u64 *opa, const u64 *opb,
-                               size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, double *part, double *tpart,
-                               double *tsp, u64 *out, u32 gelt) {
-  constexpr int NB = 1 << (LOGN - 10);
-  const size_t lds_sp = (size_t)((nl < 2 ? 2 : nl) * lds_words(10)) * 8;
-  const size_t lds_main = (size_t)((nl + 1) * lds_words(10)) * 8 + 1024 * 16;
-  const dim3 gsp((unsigned)(cc * NB)), gmain((unsigned)(cc * nl * NB));
-  if (nl > 7) {  // deep chains: one wavefront per limb still, but up to sixteen of them
-#define ABC_GSPD(NLV) hipLaunchKernelGGL((k_gsplit_special<LOGN, NLV, false>), gsp, dim3(64 * NLV), lds_sp, st, c->dc, part, key, key_twin_lookup(c, key), tsp, (int)cc)
-    switch (nl) {
-      case 8: ABC_GSPD(8); break;
-      case 9: ABC_GSPD(9); break;
-      case 10: ABC_GSPD(10); break;
-      case 11: ABC_GSPD(11); break;
-      case 12: ABC_GSPD(12); break;
-      case 13: ABC_GSPD(13); break;
-      case 14: ABC_GSPD(14); break;
-      default: ABC_GSPD(15); break;
-    }
-#undef ABC_GSPD
-    hipLaunchKernelGGL((k_gsplit_pass<LOGN>), dim3((unsigned)(cc * 2 * (LOGN > 14 ? 32 : 4))), dim3(256), 0, st, c->dc, tsp, tpart, nl);
-    if (mode == 0)
-      hipLaunchKernelGGL((k_gsplit_main_deep<LOGN, 0, false>), gmain, dim3(1024), lds_main, st, c->dc, part, tpart, opa, opb, opa_stride,
-                         opb_stride, add_c1, key, out, gelt, nl, 0xfedcba9876543210ull, nl);
-    else if (gelt)
-      hipLaunchKernelGGL((k_gsplit_main_deep<LOGN, 1, true>), gmain, dim3(1024), lds_main, st, c->dc, part, tpart, opa, opb, opa_stride,
-                         opb_stride, add_c1, key, out, gelt, nl, 0xfedcba9876543210ull, nl);
+static void launch_gsplit_main(abc_hip_ctx *c, int mode, const MainArgs &a) {
+  if (a.ni < 1) return;
+  const dim3 gmain((unsigned)(a.cc * a.ni * (1 << (LOGN - 10))));
+  const double *part = (const double *)a.part, *tpart = (const double *)a.tpart;  // the limbs of the slots in a.imap are doubles
+  dispatch_mode(mode, a.gelt, [&](auto M, auto G) {
+    constexpr int MODE = decltype(M)::value;
+    constexpr bool GAL = decltype(G)::value;
+    if (a.nl > 7)
+      hipLaunchKernelGGL((k_gsplit_main_deep<LOGN, MODE, GAL>), gmain, dim3(1024), main_lds_bytes(a.nl), a.st, c->dc, part, tpart, a.opa, a.opb,
+                         a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, a.nl, a.imap, a.ni);
     else
-      hipLaunchKernelGGL((k_gsplit_main_deep<LOGN, 1, false>), gmain, dim3(1024), lds_main, st, c->dc, part, tpart, opa, opb, opa_stride,
-                         opb_stride, add_c1, key, out, gelt, nl, 0xfedcba9876543210ull, nl);
-    return;
-  }
-#define ABC_GSP(NLV)                                                                                                                    \
-  hipLaunchKernelGGL((k_gsplit_special<LOGN, NLV, false>), gsp, dim3(64 * NLV), lds_sp, st, c->dc, part, key, key_twin_lookup(c, key), tsp, (int)cc);                            \
-  hipLaunchKernelGGL((k_gsplit_pass<LOGN>), dim3((unsigned)(cc * 2 * (LOGN > 14 ? 32 : 4))), dim3(256), 0, st, c->dc, tsp, tpart, nl);  \
-  if (mode == 0)                                                                                                                        \
-    hipLaunchKernelGGL((k_gsplit_main<LOGN, 0, false, NLV>), gmain, dim3(512), lds_main, st, c->dc, part, tpart, opa, opb, opa_stride,  \
-                       opb_stride, add_c1, key, out, gelt, 0x76543210u, nl);                                                                             \
-  else if (gelt)                                                                                                                        \
-    hipLaunchKernelGGL((k_gsplit_main<LOGN, 1, true, NLV>), gmain, dim3(512), lds_main, st, c->dc, part, tpart, opa, opb, opa_stride,   \
-                       opb_stride, add_c1, key, out, gelt, 0x76543210u, nl);                                                                             \
-  else                                                                                                                                  \
-    hipLaunchKernelGGL((k_gsplit_main<LOGN, 1, false, NLV>), gmain, dim3(512), lds_main, st, c->dc, part, tpart, opa, opb, opa_stride,  \
-                       opb_stride, add_c1, key, out, gelt, 0x76543210u, nl)
-  switch (nl) {
-    case 1: ABC_GSP(1); break;
-    case 2: ABC_GSP(2); break;
-    case 3: ABC_GSP(3); break;
-    case 4: ABC_GSP(4); break;
-    case 5: ABC_GSP(5); break;
-    case 6: ABC_GSP(6); break;
-    default: ABC_GSP(7); break;
-  }
-#undef ABC_GSP
+      dispatch_nl<1, 7>(a.nl, [&](auto NL) {
+        hipLaunchKernelGGL((k_gsplit_main<LOGN, MODE, GAL, decltype(NL)::value>), gmain, dim3(512), main_lds_bytes(a.nl), a.st, c->dc, part,
+                           tpart, a.opa, a.opb, a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, (u32)a.imap, a.ni);
+      });
+  });
 }
+void gsplit_main15(abc_hip_ctx *c, int mode, const MainArgs &a) { launch_gsplit_main<15>(c, mode, a); }
 
-// the deep-chain main step of N = 2^15 over a subset of the data primes (mixed chains of 8 to 15 limbs, abc_kernels_isplit.hip)
-void gsplit_main_deep_subset15(hipStream_t st, abc_hip_ctx *c, size_t cc, int nl, int mode, const double *part, const double *tpart,
-                               const u64 *opa, const u64 *opb, size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out,
-                               u32 gelt, u64 imap, int ni) {
-  if (ni < 1) return;
-  const size_t lds_main = (size_t)((nl + 1) * lds_words(10)) * 8 + 1024 * 16;
-  const dim3 gmain((unsigned)(cc * ni * 32));
-  if (mode == 0)
-    hipLaunchKernelGGL((k_gsplit_main_deep<15, 0, false>), gmain, dim3(1024), lds_main, st, c->dc, part, tpart, opa, opb, opa_stride, opb_stride,
-                       add_c1, key, out, gelt, nl, imap, ni);
-  else if (gelt)
-    hipLaunchKernelGGL((k_gsplit_main_deep<15, 1, true>), gmain, dim3(1024), lds_main, st, c->dc, part, tpart, opa, opb, opa_stride, opb_stride,
-                       add_c1, key, out, gelt, nl, imap, ni);
-  else
-    hipLaunchKernelGGL((k_gsplit_main_deep<15, 1, false>), gmain, dim3(1024), lds_main, st, c->dc, part, tpart, opa, opb, opa_stride, opb_stride,
-                       add_c1, key, out, gelt, nl, imap, ni);
-}
-
-// the main step of N = 2^15 over a subset of the data primes (mixed chains, abc_kernels_isplit.hip): mode 0 multiply, mode 1 key switch
-bool gsplit_main_subset15(hipStream_t st, abc_hip_ctx *c, size_t cc, int nl, int mode, const double *part, const double *tpart, const u64 *opa,
-                          const u64 *opb, size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt, u32 imap,
-                          int ni) {
-  if (nl < 1 || nl > 7 || ni < 1) return ni == 0;
-  const size_t lds_main = (size_t)((nl + 1) * lds_words(10)) * 8 + 1024 * 16;
-  const dim3 gmain((unsigned)(cc * ni * 32));
-#define ABC_GSUB(NLV)                                                                                                                  \
-  if (mode == 0)                                                                                                                       \
-    hipLaunchKernelGGL((k_gsplit_main<15, 0, false, NLV>), gmain, dim3(512), lds_main, st, c->dc, part, tpart, opa, opb, opa_stride,   \
-                       opb_stride, add_c1, key, out, gelt, imap, ni);                                                                  \
-  else if (gelt)                                                                                                                       \
-    hipLaunchKernelGGL((k_gsplit_main<15, 1, true, NLV>), gmain, dim3(512), lds_main, st, c->dc, part, tpart, opa, opb, opa_stride,    \
-                       opb_stride, add_c1, key, out, gelt, imap, ni);                                                                  \
-  else                                                                                                                                 \
-    hipLaunchKernelGGL((k_gsplit_main<15, 1, false, NLV>), gmain, dim3(512), lds_main, st, c->dc, part, tpart, opa, opb, opa_stride,   \
-                       opb_stride, add_c1, key, out, gelt, imap, ni)
-  switch (nl) {
-    case 1: ABC_GSUB(1); break;
-    case 2: ABC_GSUB(2); break;
-    case 3: ABC_GSUB(3); break;
-    case 4: ABC_GSUB(4); break;
-    case 5: ABC_GSUB(5); break;
-    case 6: ABC_GSUB(6); break;
-    default: ABC_GSUB(7); break;
-  }
-#undef ABC_GSUB
-  return true;
+// G2a..G2c; a.part, a.tpart: the chunk's scratch
+template <int LOGN>
+static void launch_gsplit_back(abc_hip_ctx *c, int mode, const MainArgs &a, double *tsp) {
+  constexpr int NB = 1 << (LOGN - 10);
+  const int nl = a.nl;
+  const size_t lds_sp = (size_t)((nl < 2 ? 2 : nl) * lds_words(10)) * 8;
+  dispatch_nl<1, 15>(nl, [&](auto NL) {
+    hipLaunchKernelGGL((k_gsplit_special<LOGN, decltype(NL)::value, false>), dim3((unsigned)(a.cc * NB)), dim3(64 * decltype(NL)::value), lds_sp,
+                       a.st, c->dc, (const double *)a.part, a.key, key_twin_lookup(c, a.key), tsp, (int)a.cc);
+  });
+  hipLaunchKernelGGL((k_gsplit_pass<LOGN>), dim3((unsigned)(a.cc * 2 * (LOGN > 14 ? 32 : 4))), dim3(256), 0, a.st, c->dc, tsp,
+                     (double *)a.tpart, nl);
+  launch_gsplit_main<LOGN>(c, mode, a);
 }
 
 // scratch (words, limb stride c->dc.ps): hinv nl | part nl(nl+1) | tpart 2 nl | tsp_half 2
@@ -845,7 +769,8 @@ int gsplit_chunk15(abc_hip_ctx *c, hipStream_t st, u64 *scratch, size_t cc, int 
   double *hinv = (double *)scratch, *part = hinv + cc * (size_t)nl * PS, *tpart = part + cc * (size_t)nl * (nl + 1) * PS,
          *tsp = tpart + cc * 2 * (size_t)nl * PS;
   launch_gsplit_front<15>(st, c, cc, nl, mode, opa, opb, opa_stride, hinv, part, gelt);
-  launch_gsplit_back<15>(st, c, cc, nl, mode, opa, opb, opa_stride, opb_stride, add_c1, key, part, tpart, tsp, out, gelt);
+  launch_gsplit_back<15>(c, mode, MainArgs{st, cc, nl, part, tpart, opa, opb, opa_stride, opb_stride, add_c1, key, out, gelt, kAllSlots, nl, 0},
+                         tsp);
   ABC_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -872,20 +797,13 @@ template <int LOGN>
 static void launch_bsplit_special(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const double *part, const u64 *key, double *half) {
   const dim3 g((unsigned)(cc * (nl + 1) * (1 << (LOGN - 10))));
   const size_t lds = (size_t)((nl < 2 ? 2 : nl) * lds_words(10)) * 8;
-#define ABC_BSP(NLV) hipLaunchKernelGGL((k_gsplit_special<LOGN, NLV, true>), g, dim3(64 * NLV), lds, st, c->dc, part, key, key_twin_lookup(c, key), half, (int)cc)
-  switch (nl) {
-    case 1: ABC_BSP(1); break;
-    case 2: ABC_BSP(2); break;
-    case 3: ABC_BSP(3); break;
-    case 4: ABC_BSP(4); break;
-    case 5: ABC_BSP(5); break;
-    case 6: ABC_BSP(6); break;
-    case 7: ABC_BSP(7); break;
-    default:  // eight digits: two rounds of four, four workgroups per CU (+2 % multiply, +5 % rotate over one round of eight)
-      hipLaunchKernelGGL((k_bsplit_special8x2<LOGN>), g, dim3(256), 0, st, c->dc, part, key, key_twin_lookup(c, key), half, (int)cc);
-      break;
-  }
-#undef ABC_BSP
+  if (nl > 7)  // eight digits: two rounds of four, four workgroups per CU (+2 % multiply, +5 % rotate over one round of eight)
+    hipLaunchKernelGGL((k_bsplit_special8x2<LOGN>), g, dim3(256), 0, st, c->dc, part, key, key_twin_lookup(c, key), half, (int)cc);
+  else
+    dispatch_nl<1, 7>(nl, [&](auto NL) {
+      hipLaunchKernelGGL((k_gsplit_special<LOGN, decltype(NL)::value, true>), g, dim3(64 * decltype(NL)::value), lds, st, c->dc, part, key,
+                         key_twin_lookup(c, key), half, (int)cc);
+    });
 }
 int bsplit_back14(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const double *part, double *half, const u64 *key, const u64 *addend,
                   size_t addend_stride, int add_c1, u64 *out, u32 ginv) {

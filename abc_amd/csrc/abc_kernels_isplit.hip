@@ -17,14 +17,6 @@
 
 namespace abc {
 
-// x*y mod q for two residues |x|, |y| <= q in exact fp64 (as fp_mulmod of abc_kernels_fused.hip)
-__device__ __forceinline__ double i_fp_mulmod(double x, double y, double q, double qinv) {
-  const double h = x * y;
-  const double l = __builtin_fma(x, y, -h);
-  const double c = __builtin_rint(h * qinv);
-  return __builtin_fma(-c, q, h) + l;
-}
-
 // radix-2^R pass over the 2^R values one thread holds, one from each 1024-point block (array index = block index): the first R
 // stages of a forward transform / the last R of an inverse one, in the arithmetic A of the prime (integer or fp64)
 template <int R, class A>
@@ -54,18 +46,6 @@ __device__ __forceinline__ void x_inv_cross(typename A::E (&x)[1 << R], const ty
   }
 }
 
-template <int LB, class TW, int PER>
-__device__ __forceinline__ void block_twiddles_fetch_g(const TW *tw, int S0, int b, int tid, int nthreads, TW (&v)[PER]) {
-#pragma unroll
-  for (int r = 0; r < PER; r++) {
-    int mm = tid + r * nthreads;
-    if (mm < 1) mm = 1;
-    if (mm > (1 << LB) - 1) mm = (1 << LB) - 1;
-    const int sl = 31 - __builtin_clz(mm);
-    v[r] = tw[(((1 << S0) + b) << sl) + (mm - (1 << sl))];
-  }
-}
-
 // K1 (multiply): c2_j = a1 b1, inverse transform in LDS, first radix-16 pass of the forward transforms modulo the other primes
 // K1 (key switch, KS = true): the operand limb itself (NTT form, Galois gather folded into the load) instead of a1 b1
 template <int LB, bool GUARD, bool KS, bool GAL>
@@ -89,7 +69,7 @@ __global__ __launch_bounds__((1 << LB) / 16) void k_isplit_pass0(DevCtx c, const
       ntt_inv_block_a<LB, FpArith>(ldsd, [&](int, int i) { return fp_from_u64(sp[galois_ntt_src<GAL>((u32)i, gelt, LB)]); }, canon, tf, mf, 0, 0);
     } else {
       const u64 *__restrict__ a1 = a + ct * 2 * pw + pw + (size_t)j * N, *__restrict__ b1 = b + ct * 2 * pw + pw + (size_t)j * N;
-      ntt_inv_block_a<LB, FpArith>(ldsd, [&](int, int i) { return i_fp_mulmod(fp_from_u64(a1[i]), fp_from_u64(b1[i]), q, qinv); }, canon, tf,
+      ntt_inv_block_a<LB, FpArith>(ldsd, [&](int, int i) { return fp_mulmod(fp_from_u64(a1[i]), fp_from_u64(b1[i]), q, qinv); }, canon, tf,
                                    mf, 0, 0);
     }
   } else {
@@ -162,7 +142,7 @@ __global__ __launch_bounds__(256) void k_igsplit_inv_tails(DevCtx c, const u64 *
   const NttTable t = ntt_table(c, j);
   u64x2 *litw = reinterpret_cast<u64x2 *>(dynu + 4 * lds_words(10));
   u64x2 twv[4];
-  block_twiddles_fetch_g<10, u64x2, 4>(t.itw, LOGNB, blk, (int)threadIdx.x, 256, twv);
+  block_twiddles_fetch<10, u64x2, 4>(t.itw, LOGNB, blk, (int)threadIdx.x, 256, twv);
   block_twiddles_store<10, u64x2, 4>(litw, (int)threadIdx.x, 256, twv);
   __syncthreads();
   if (ct >= (size_t)cc) return;  // wavefront-uniform, after the only workgroup barrier
@@ -371,7 +351,7 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_isplit_main(DevCtx c, 
   const u64 inv = cst->inv_special[I], inv_s = cst->inv_special_s[I];
 
   u64x2 twv[PER];
-  block_twiddles_fetch_g<10, u64x2, PER>(t.tw, LOGNB, blk, (int)threadIdx.x, NT, twv);
+  block_twiddles_fetch<10, u64x2, PER>(t.tw, LOGNB, blk, (int)threadIdx.x, NT, twv);
   const bool has_limb = W <= nl;
   const int Wc = has_limb ? W : 0;
   const u64 *__restrict__ src = (Wc < nl - 1) ? part + ((ct * (nl + 1) + I) * nl + (Wc < I ? Wc : Wc + 1)) * PS + base
@@ -496,7 +476,7 @@ __global__ __launch_bounds__(1024) void k_isplit_main_deep(DevCtx c, const u64 *
   const u64 sp = cst->special_mod_q[I], sp_s = cst->special_mod_q_s[I];
   const u64 inv = cst->inv_special[I], inv_s = cst->inv_special_s[I];
   u64x2 twv[1];
-  block_twiddles_fetch_g<10, u64x2, 1>(t.tw, LOGNB, blk, (int)threadIdx.x, NT, twv);
+  block_twiddles_fetch<10, u64x2, 1>(t.tw, LOGNB, blk, (int)threadIdx.x, NT, twv);
   const bool has_limb = W <= nl;
   const int Wc = has_limb ? W : 0;
   const u64 *__restrict__ src = (Wc < nl - 1) ? part + ((ct * (nl + 1) + I) * nl + (Wc < I ? Wc : Wc + 1)) * PS + base
@@ -583,95 +563,51 @@ __global__ __launch_bounds__(1024) void k_isplit_main_deep(DevCtx c, const u64 *
   *reinterpret_cast<u64x2 *>(out + ((ct * 2 + 1) * nl + I) * N + base + e) = u64x2{r1[0], r1[1]};
 }
 
-// steps 2-4 of a deep chain at N = 2^15: special prime (integer), register pass, then the last step per arithmetic class
-template <bool GUARD>
-static void launch_isplit_tail_deep15(hipStream_t st, abc_hip_ctx *c, size_t cc, int nl, u64 *part, u64 *tpart, u64 *tsp_half, int mode,
-                                      const u64 *opa, const u64 *opb, size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key,
-                                      u64 *out, u32 gelt, u32 fpmask) {
-  const size_t lds_sp = (size_t)(nl * lds_words(10)) * 8;
-  const size_t lds_main = (size_t)((nl + 1) * lds_words(10)) * 8 + 1024 * 16;
-  u64 imap_int = 0, imap_fp = 0;
-  int ni_int = 0, ni_fp = 0;
-  for (int I = 0; I < nl; I++) {
-    if ((fpmask >> I) & 1u) imap_fp |= (u64)I << (4 * ni_fp++);
-    else imap_int |= (u64)I << (4 * ni_int++);
-  }
-  const dim3 gsp((unsigned)(cc * 32));
-#define ABC_ISPD(NLV) hipLaunchKernelGGL((k_isplit_special<GUARD, NLV, 15>), gsp, dim3(64 * NLV), lds_sp, st, c->dc, part, key, tsp_half)
-  switch (nl) {
-    case 8: ABC_ISPD(8); break;
-    case 9: ABC_ISPD(9); break;
-    case 10: ABC_ISPD(10); break;
-    case 11: ABC_ISPD(11); break;
-    case 12: ABC_ISPD(12); break;
-    case 13: ABC_ISPD(13); break;
-    case 14: ABC_ISPD(14); break;
-    default: ABC_ISPD(15); break;
-  }
-#undef ABC_ISPD
-  hipLaunchKernelGGL((k_isplit_pass<15, GUARD>), dim3((unsigned)(cc * 2 * 4)), dim3(256), 0, st, c->dc, tsp_half, tpart, nl, fpmask);
-  if (ni_int) {
-    const dim3 gmain((unsigned)(cc * ni_int * 32));
-    if (mode == 0)
-      hipLaunchKernelGGL((k_isplit_main_deep<0, false, GUARD, 15>), gmain, dim3(1024), lds_main, st, c->dc, part, tpart, opa, opb, opa_stride,
-                         opb_stride, add_c1, key, out, gelt, nl, imap_int, ni_int);
-    else if (gelt)
-      hipLaunchKernelGGL((k_isplit_main_deep<1, true, GUARD, 15>), gmain, dim3(1024), lds_main, st, c->dc, part, tpart, opa, opb, opa_stride,
-                         opb_stride, add_c1, key, out, gelt, nl, imap_int, ni_int);
-    else
-      hipLaunchKernelGGL((k_isplit_main_deep<1, false, GUARD, 15>), gmain, dim3(1024), lds_main, st, c->dc, part, tpart, opa, opb, opa_stride,
-                         opb_stride, add_c1, key, out, gelt, nl, imap_int, ni_int);
-  }
-  if (ni_fp)
-    gsplit_main_deep_subset15(st, c, cc, nl, mode, (const double *)part, (const double *)tpart, opa, opb, opa_stride, opb_stride, add_c1, key,
-                              out, gelt, imap_fp, ni_fp);
-}
-
 // ---- launch sequence on one chunk ----
+// steps 2-4: special prime (integer), register pass, then the main step once per arithmetic class -- the integer kernels over the
+// wide data primes (up to seven limbs k_isplit_main, deep chains of N = 2^15 k_isplit_main_deep), the fp64 kernels of
+// abc_kernels_fused.hip / abc_kernels_gsplit.hip over the others
 template <bool GUARD, int LOGN>
-static void launch_isplit_tail(hipStream_t st, abc_hip_ctx *c, size_t cc, int nl, u64 *part, u64 *tpart, u64 *tsp_half, int mode,
-                               const u64 *opa, const u64 *opb, size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out,
-                               u32 gelt, u32 fpmask) {
-  const size_t lds_sp = (size_t)((nl < 2 ? 2 : nl) * lds_words(10)) * 8;
-  const size_t lds_main = (size_t)((nl + 1) * lds_words(10)) * 8 + 1024 * 16;
-  // data primes of the integer main kernel / of the fp64 main kernel, one nibble each
-  u32 imap_int = 0, imap_fp = 0;
-  int ni_int = 0, ni_fp = 0;
-  for (int I = 0; I < nl; I++) {
-    if ((fpmask >> I) & 1u) imap_fp |= (u32)I << (4 * ni_fp++);
-    else imap_int |= (u32)I << (4 * ni_int++);
-  }
+static void launch_isplit_tail(abc_hip_ctx *c, int mode, const MainArgs &a, u64 *tsp_half, u32 fpmask) {
   constexpr int NB = 1 << (LOGN - 10);
-  const dim3 gsp((unsigned)(cc * NB)), gmain((unsigned)(cc * ni_int * NB));
-#define ABC_ISP(NLV)                                                                                                                  \
-  hipLaunchKernelGGL((k_isplit_special<GUARD, NLV, LOGN>), gsp, dim3(64 * NLV), lds_sp, st, c->dc, part, key, tsp_half);              \
-  hipLaunchKernelGGL((k_isplit_pass<LOGN, GUARD>), dim3((unsigned)(cc * 2 * 4)), dim3(256), 0, st, c->dc, tsp_half, tpart, nl, fpmask); \
-  if (ni_int == 0) {                                                                                                                  \
-  } else if (mode == 0)                                                                                                               \
-    hipLaunchKernelGGL((k_isplit_main<0, false, NLV, GUARD, LOGN>), gmain, dim3(512), lds_main, st, c->dc, part, tpart, opa, opb, opa_stride, \
-                       opb_stride, add_c1, key, out, gelt, imap_int, ni_int);                                                         \
-  else if (gelt)                                                                                                                      \
-    hipLaunchKernelGGL((k_isplit_main<1, true, NLV, GUARD, LOGN>), gmain, dim3(512), lds_main, st, c->dc, part, tpart, opa, opb, opa_stride, \
-                       opb_stride, add_c1, key, out, gelt, imap_int, ni_int);                                                         \
-  else                                                                                                                                \
-    hipLaunchKernelGGL((k_isplit_main<1, false, NLV, GUARD, LOGN>), gmain, dim3(512), lds_main, st, c->dc, part, tpart, opa, opb, opa_stride, \
-                       opb_stride, add_c1, key, out, gelt, imap_int, ni_int)
-  switch (nl) {
-    case 1: ABC_ISP(1); break;
-    case 2: ABC_ISP(2); break;
-    case 3: ABC_ISP(3); break;
-    case 4: ABC_ISP(4); break;
-    case 5: ABC_ISP(5); break;
-    case 6: ABC_ISP(6); break;
-    default: ABC_ISP(7); break;
+  const int nl = a.nl;
+  const size_t lds_sp = (size_t)((nl < 2 ? 2 : nl) * lds_words(10)) * 8;
+  // data primes of the integer main kernel / of the fp64 main kernel, one nibble each
+  MainArgs ai = a, af = a;
+  ai.imap = af.imap = 0;
+  ai.ni = af.ni = 0;
+  for (int I = 0; I < nl; I++) {
+    if ((fpmask >> I) & 1u) af.imap |= (u64)I << (4 * af.ni++);
+    else ai.imap |= (u64)I << (4 * ai.ni++);
   }
-#undef ABC_ISP
-  if (ni_fp && LOGN == 14)
-    split4_main_subset(st, c, cc, nl, mode, (const double *)part, (const double *)tpart, opa, opb, opa_stride, opb_stride, add_c1, key, out,
-                       gelt, imap_fp, ni_fp);
-  else if (ni_fp)
-    gsplit_main_subset15(st, c, cc, nl, mode, (const double *)part, (const double *)tpart, opa, opb, opa_stride, opb_stride, add_c1, key, out,
-                         gelt, imap_fp, ni_fp);
+  // one scratch, two arithmetic classes: limbs modulo the primes of fpmask hold doubles (af), the others u64 (ai)
+  const u64 *part = (const u64 *)a.part, *tpart = (const u64 *)a.tpart;
+  dispatch_nl<1, (LOGN == 15 ? 15 : 7)>(nl, [&](auto NL) {
+    hipLaunchKernelGGL((k_isplit_special<GUARD, decltype(NL)::value, LOGN>), dim3((unsigned)(a.cc * NB)), dim3(64 * decltype(NL)::value), lds_sp,
+                       a.st, c->dc, part, a.key, tsp_half);
+  });
+  hipLaunchKernelGGL((k_isplit_pass<LOGN, GUARD>), dim3((unsigned)(a.cc * 2 * 4)), dim3(256), 0, a.st, c->dc, tsp_half, (u64 *)a.tpart, nl,
+                     fpmask);
+  if (ai.ni) {
+    const dim3 gmain((unsigned)(a.cc * ai.ni * NB));
+    dispatch_mode(mode, a.gelt, [&](auto M, auto G) {
+      constexpr int MODE = decltype(M)::value;
+      constexpr bool GAL = decltype(G)::value;
+      if constexpr (LOGN == 15) {
+        if (nl > 7) {
+          hipLaunchKernelGGL((k_isplit_main_deep<MODE, GAL, GUARD, LOGN>), gmain, dim3(1024), main_lds_bytes(nl), a.st, c->dc, part, tpart,
+                             a.opa, a.opb, a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, nl, ai.imap, ai.ni);
+          return;
+        }
+      }
+      dispatch_nl<1, 7>(nl, [&](auto NL) {
+        hipLaunchKernelGGL((k_isplit_main<MODE, GAL, decltype(NL)::value, GUARD, LOGN>), gmain, dim3(512), main_lds_bytes(nl), a.st, c->dc,
+                           part, tpart, a.opa, a.opb, a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, (u32)ai.imap, ai.ni);
+      });
+    });
+  }
+  if (af.ni && LOGN == 14) split4_main(c, mode, af);
+  else if (af.ni) gsplit_main15(c, mode, af);
 }
 
 // scratch (words, limb stride c->dc.ps): part nl(nl+1) | tpart 2 nl | tsp_half 2
@@ -696,49 +632,31 @@ int isplit_chunk(abc_hip_ctx *c, hipStream_t st, u64 *scratch, size_t cc, int nl
   const bool guard = !all_key_primes(c, unguarded_ok);
   // data primes below 2^50 take the fp64 kernels (ABC_HIP_NO_FP64 / ABC_HIP_NO_MIXED: integers throughout)
   const u32 fpmask = (c->use_fp && !c->sw.no_mixed) ? data_prime_mask(c, nl, fp_ok) : 0u;
-  if (c->logn == 15) {
-    u64 *hinv = tsp + cc * 2 * PS;
-    const dim3 ga((unsigned)(((cc + 3) / 4) * nl * 32)), gb((unsigned)(cc * nl * 4));
-    const size_t lds = (size_t)(4 * lds_words(10)) * 8 + 1024 * 16;
-    if (mode == 0)
-      hipLaunchKernelGGL((k_igsplit_inv_tails<15, 0, false>), ga, dim3(256), lds, st, c->dc, opa, opb, 0, hinv, nl, (int)cc, 0u);
-    else if (gelt)
-      hipLaunchKernelGGL((k_igsplit_inv_tails<15, 1, true>), ga, dim3(256), lds, st, c->dc, opa, nullptr, opa_stride, hinv, nl, (int)cc, gelt);
-    else
-      hipLaunchKernelGGL((k_igsplit_inv_tails<15, 1, false>), ga, dim3(256), lds, st, c->dc, opa, nullptr, opa_stride, hinv, nl, (int)cc, 0u);
-    if (nl > 7) {
-      if (guard) {
-        hipLaunchKernelGGL((k_igsplit_cross<15, true>), gb, dim3(256), 0, st, c->dc, hinv, part, nl, fpmask);
-        launch_isplit_tail_deep15<true>(st, c, cc, nl, part, tpart, tsp, mode, opa, opb, opa_stride, opb_stride, add_c1, key, out, gelt, fpmask);
-      } else {
-        hipLaunchKernelGGL((k_igsplit_cross<15, false>), gb, dim3(256), 0, st, c->dc, hinv, part, nl, fpmask);
-        launch_isplit_tail_deep15<false>(st, c, cc, nl, part, tpart, tsp, mode, opa, opb, opa_stride, opb_stride, add_c1, key, out, gelt, fpmask);
-      }
-      ABC_HIP_CHECK(hipGetLastError());
-      return 0;
+  const MainArgs a{st, cc, nl, part, tpart, opa, opb, opa_stride, opb_stride, add_c1, key, out, gelt, kAllSlots, nl, 0};
+  auto with_guard = [&](auto GD) {
+    constexpr bool GUARD = decltype(GD)::value;
+    if (c->logn == 15) {
+      u64 *hinv = tsp + cc * 2 * PS;
+      const dim3 ga((unsigned)(((cc + 3) / 4) * nl * 32)), gb((unsigned)(cc * nl * 4));
+      const size_t lds = (size_t)(4 * lds_words(10)) * 8 + 1024 * 16;
+      dispatch_mode(mode, gelt, [&](auto M, auto G) {
+        constexpr int MODE = decltype(M)::value;
+        hipLaunchKernelGGL((k_igsplit_inv_tails<15, MODE, decltype(G)::value>), ga, dim3(256), lds, st, c->dc, opa, MODE ? nullptr : opb,
+                           MODE ? opa_stride : 0, hinv, nl, (int)cc, gelt);
+      });
+      hipLaunchKernelGGL((k_igsplit_cross<15, GUARD>), gb, dim3(256), 0, st, c->dc, hinv, part, nl, fpmask);
+      launch_isplit_tail<GUARD, 15>(c, mode, a, tsp, fpmask);
+      return;
     }
-    if (guard) {
-      hipLaunchKernelGGL((k_igsplit_cross<15, true>), gb, dim3(256), 0, st, c->dc, hinv, part, nl, fpmask);
-      launch_isplit_tail<true, 15>(st, c, cc, nl, part, tpart, tsp, mode, opa, opb, opa_stride, opb_stride, add_c1, key, out, gelt, fpmask);
-    } else {
-      hipLaunchKernelGGL((k_igsplit_cross<15, false>), gb, dim3(256), 0, st, c->dc, hinv, part, nl, fpmask);
-      launch_isplit_tail<false, 15>(st, c, cc, nl, part, tpart, tsp, mode, opa, opb, opa_stride, opb_stride, add_c1, key, out, gelt, fpmask);
-    }
-    ABC_HIP_CHECK(hipGetLastError());
-    return 0;
-  }
-  const dim3 g1((unsigned)(cc * nl)), b1((1 << 14) / 16);
-  if (guard) {
-    if (mode == 0) hipLaunchKernelGGL((k_isplit_pass0<14, true, false, false>), g1, b1, 0, st, c->dc, opa, opb, 0, part, nl, 0u, fpmask);
-    else if (gelt) hipLaunchKernelGGL((k_isplit_pass0<14, true, true, true>), g1, b1, 0, st, c->dc, opa, nullptr, opa_stride, part, nl, gelt, fpmask);
-    else hipLaunchKernelGGL((k_isplit_pass0<14, true, true, false>), g1, b1, 0, st, c->dc, opa, nullptr, opa_stride, part, nl, 0u, fpmask);
-    launch_isplit_tail<true, 14>(st, c, cc, nl, part, tpart, tsp, mode, opa, opb, opa_stride, opb_stride, add_c1, key, out, gelt, fpmask);
-  } else {
-    if (mode == 0) hipLaunchKernelGGL((k_isplit_pass0<14, false, false, false>), g1, b1, 0, st, c->dc, opa, opb, 0, part, nl, 0u, fpmask);
-    else if (gelt) hipLaunchKernelGGL((k_isplit_pass0<14, false, true, true>), g1, b1, 0, st, c->dc, opa, nullptr, opa_stride, part, nl, gelt, fpmask);
-    else hipLaunchKernelGGL((k_isplit_pass0<14, false, true, false>), g1, b1, 0, st, c->dc, opa, nullptr, opa_stride, part, nl, 0u, fpmask);
-    launch_isplit_tail<false, 14>(st, c, cc, nl, part, tpart, tsp, mode, opa, opb, opa_stride, opb_stride, add_c1, key, out, gelt, fpmask);
-  }
+    dispatch_mode(mode, gelt, [&](auto M, auto G) {
+      constexpr bool KS = decltype(M)::value != 0;
+      hipLaunchKernelGGL((k_isplit_pass0<14, GUARD, KS, decltype(G)::value>), dim3((unsigned)(cc * nl)), dim3((1 << 14) / 16), 0, st, c->dc, opa,
+                         KS ? nullptr : opb, KS ? opa_stride : 0, part, nl, gelt, fpmask);
+    });
+    launch_isplit_tail<GUARD, 14>(c, mode, a, tsp, fpmask);
+  };
+  if (guard) with_guard(std::true_type{});
+  else with_guard(std::false_type{});
   ABC_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -75,6 +75,13 @@ __device__ __forceinline__ double fp_mul_lazy(double y, double w, double wq, dou
   const double c = __builtin_rint(y * wq);
   return __builtin_fma(-c, q, h) + l;
 }
+// x*y mod q for two residues |x|, |y| <= q: |result| < q  (|x y / q| 2^-52 <= 1/4, plus the rounding 1/2)
+__device__ __forceinline__ double fp_mulmod(double x, double y, double q, double qinv) {
+  const double h = x * y;
+  const double l = __builtin_fma(x, y, -h);
+  const double c = __builtin_rint(h * qinv);
+  return __builtin_fma(-c, q, h) + l;
+}
 // centred representative: |result| <= q/2 (+ |x| q 2^-105, nothing)
 __device__ __forceinline__ double fp_centre(double x, double q, double qinv) {
   return __builtin_fma(-__builtin_rint(x * qinv), q, x);
@@ -267,7 +274,9 @@ __device__ __forceinline__ void fwd_pass_lds(typename A::E (&x)[16], const int (
   }
 }
 // workgroup-cooperative fill of that table for the 2^LB-point block b behind S0 strided stages: values first (vector loads,
-// issue early), then the LDS writes (call after whatever else should be requested first)
+// issue early), then the LDS writes (call after whatever else should be requested first).  Two overloads, one per address space
+// the tables are kept in (FpTable: constant, read field by field through tw_load; NttTable: a plain pointer, read as one
+// 16-byte struct): merged into one template over the pointer type, the integer callers compiled to different code.
 template <int LB, class TW, int PER>
 __device__ __forceinline__ void block_twiddles_fetch(const ABC_CONST_AS TW *tw, int S0, int b, int tid, int nthreads, TW (&v)[PER]) {
 #pragma unroll
@@ -277,6 +286,17 @@ __device__ __forceinline__ void block_twiddles_fetch(const ABC_CONST_AS TW *tw, 
     if (mm > (1 << LB) - 1) mm = (1 << LB) - 1;
     const int sl = 31 - __builtin_clz(mm);
     v[r] = tw_load(tw + (((1 << S0) + b) << sl) + (mm - (1 << sl)));
+  }
+}
+template <int LB, class TW, int PER>
+__device__ __forceinline__ void block_twiddles_fetch(const TW *tw, int S0, int b, int tid, int nthreads, TW (&v)[PER]) {
+#pragma unroll
+  for (int r = 0; r < PER; r++) {
+    int mm = tid + r * nthreads;
+    if (mm < 1) mm = 1;
+    if (mm > (1 << LB) - 1) mm = (1 << LB) - 1;
+    const int sl = 31 - __builtin_clz(mm);
+    v[r] = tw[(((1 << S0) + b) << sl) + (mm - (1 << sl))];
   }
 }
 template <int LB, class TW, int PER>

@@ -9,7 +9,7 @@ for f in bfv bmul ckks_codec eval fused gsplit isplit ntt; do
     awk -v F=$f '/Function Name:/ {n=$NF} / VGPRs:/ {v=$NF} /ScratchSize/ {s=$NF} /Occupancy/ {o=$NF} /LDS Size/ {print F" | "n" | "v" | "s" | "o" | "$NF}' |
     while IFS= read -r line; do
       sym=$(echo "$line" | cut -d'|' -f2 | tr -d ' ')
-      dem=$(echo "$sym" | c++filt | sed 's/(.*//; s/^void //')
+      dem=$(echo "$sym" | c++filt | sed 's/(anonymous namespace):://g; s/(.*//; s/^void //')
       echo "$line" | awk -F'|' -v D="$dem" '{print $1"| "D" |"$3"|"$4"|"$5"|"$6}'
     done
 done
