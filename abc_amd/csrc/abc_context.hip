@@ -54,79 +54,6 @@ void read_switches(abc_hip_ctx *c) {
   c->sw = s;
 }
 
-static bool capturing(abc_hip_ctx *c) {
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(c->stream, &st) != hipSuccess) return false;
-  return st != hipStreamCaptureStatusNone;
-}
-
-// Give every cached (free-listed) block back to the driver.  The stream is drained first: a cached block may still be
-// read by work that was enqueued before it was freed.
-static int trim_cache(abc_hip_ctx *c) {
-  std::lock_guard<std::mutex> lock(c->alloc_mu);
-  if (c->free_blocks.empty()) return 0;
-  ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
-  for (auto &kv : c->free_blocks)
-    for (void *p : kv.second) {
-      c->block_size.erase(p);
-      (void)hipFree(p);
-    }
-  c->free_blocks.clear();
-  c->cached_bytes = 0;
-  return 0;
-}
-// hipMalloc; on failure flush this context's cache once and try again (the cache never shrinks by itself)
-static hipError_t malloc_retry(abc_hip_ctx *c, void **p, size_t bytes) {
-  hipError_t e = hipMalloc(p, bytes);
-  if (e == hipSuccess) return e;
-  (void)hipGetLastError();
-  if (trim_cache(c)) return e;
-  return hipMalloc(p, bytes);
-}
-
-void retire_buffer(abc_hip_ctx *c, void *p, uint64_t born) {
-  if (!p) return;
-  abc_hip_ctx::Held h{p, {}};
-  for (auto &kv : c->live_graphs)
-    if (kv.second > born) h.graphs.push_back(kv.first);  // ended after p was allocated: may have baked it in
-  if (h.graphs.empty()) {
-    (void)hipFree(p);
-    return;
-  }
-  c->held.push_back(std::move(h));
-}
-
-int ensure_workspace(abc_hip_ctx *c, size_t bytes) {
-  if (bytes <= c->ws_bytes) return 0;
-  if (capturing(c)) { set_error("scratch would grow during graph capture: run the sequence once eagerly first"); return 1; }
-  if (c->ws) {
-    ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
-    retire_buffer(c, c->ws, c->ws_born);
-    c->ws = nullptr;
-    c->ws_bytes = 0;
-  }
-  size_t want = bytes + bytes / 8;
-  ABC_HIP_CHECK(malloc_retry(c, &c->ws, want));
-  c->ws_bytes = want;
-  c->ws_born = c->graph_seq;
-  return 0;
-}
-
-int ensure_aux(abc_hip_ctx *c, int which, size_t bytes) {
-  if (bytes <= c->aux_bytes[which]) return 0;
-  if (capturing(c)) { set_error("scratch would grow during graph capture: run the sequence once eagerly first"); return 1; }
-  if (c->aux[which]) {
-    ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
-    retire_buffer(c, c->aux[which], c->aux_born[which]);
-    c->aux[which] = nullptr;
-    c->aux_bytes[which] = 0;
-  }
-  ABC_HIP_CHECK(malloc_retry(c, &c->aux[which], bytes));
-  c->aux_bytes[which] = bytes;
-  c->aux_born[which] = c->graph_seq;
-  return 0;
-}
-
 static Mod make_mod(uint64_t q, int logn, bool ntt) {
   using namespace host;
   Mod m{};
@@ -556,13 +483,6 @@ struct OpRange {
     if (hipSetDevice((c)->device) != hipSuccess) { set_error("hipSetDevice failed"); return 1; } \
   } while (0)
 
-// Host-synchronising entry points cannot be recorded, and letting HIP find that out invalidates the capture for good on this
-// runtime (the stream keeps returning hipErrorStreamCaptureInvalidated even after hipStreamEndCapture): refuse up front.
-#define NOT_CAPTURABLE(c, what)                                                                                   \
-  do {                                                                                                            \
-    if ((c)->capture_active) { set_error(what ": not capturable (host transfer / synchronisation inside abc_hip_graph_begin..end)"); return 1; } \
-  } while (0)
-
 extern "C" {
 
 const char *abc_hip_last_error(void) { return g_err.c_str(); }
@@ -686,7 +606,7 @@ int abc_hip_ctx_create(int scheme, int logn, const uint64_t *primes, int nprimes
   if (!rc && !env_on("ABC_HIP_SYNC_ALLOC")) {
     c->cache_alloc = true;
     size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) c->cache_cap = total_b / 4;  // at most a quarter of the device
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) c->buffers.cache_cap = total_b / 4;  // at most a quarter of the device
   }
   if (rc) { abc_hip_ctx_destroy(c); return 1; }
   *out = c;
@@ -701,15 +621,10 @@ void abc_hip_ctx_destroy(abc_hip_ctx *c) {
   (void)hipFree(c->d_slot_map);
   (void)hipFree(c->d_ckks_codec);
   (void)hipFree(c->d_crt);
-  drop_key_twins(c, nullptr);
-  (void)hipFree(c->d_sk); (void)hipFree(c->d_pk); (void)hipFree(c->d_relin);
-  for (auto &kv : c->d_galois) (void)hipFree(kv.second);
-  (void)hipFree(c->ws);
-  for (void *p : c->aux) (void)hipFree(p);
-  for (auto &h : c->held) (void)hipFree(h.p);
-  // every block abc_hip_malloc ever handed out and that was not returned to the driver: cached ones and ones the caller
-  // still holds (a caller that frees after destroying the context would otherwise leak them)
-  for (auto &kv : c->block_size) (void)hipFree(kv.first);
+  // workspace, arenas, keys, key mirrors, what is held back for a graph never destroyed, and every block abc_hip_malloc
+  // handed out and that was not returned to the driver: cached ones and ones the caller still holds (a caller that frees after
+  // destroying the context would otherwise leak them)
+  free_buffers(c);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -730,7 +645,7 @@ int abc_hip_ctx_info(const abc_hip_ctx *c, int what) {
     case 3: return c->L;
     case 4: return c->device;
     case 5: return c->nBsk;
-    case 6: return (int)c->held.size();
+    case 6: return held_buffers(c);
     default: return -1;
   }
 }
@@ -749,131 +664,15 @@ int abc_hip_sync(abc_hip_ctx *c) {
   return 0;
 }
 
-// Caching allocator: a freed buffer goes to a per-context free list (exact-size buckets) instead of back to the
-// driver, and the next request of that size takes it -- no hipMalloc, no hipFree, no device synchronisation.  That is
-// safe because every use of a context's buffers is ordered on the context's stream (the internal lanes fork from and
-// join it inside each call, also on error paths: LaneScope in abc_kernels_fused.hip): whatever still runs on a recycled
-// buffer was issued before its new owner's first use.  A buffer handed to ANOTHER context or stream is the caller's to
-// order (header).  It matters to the plugin classes, where the interpreter clones / drops a ciphertext on every
-// variable read.  The maps are guarded by a mutex (two host threads may share a context for allocation); the cache is
-// flushed by abc_hip_trim, when the cap is reached, and whenever a hipMalloc of this context fails.
-// (hipMallocAsync / hipFreeAsync were tried first and returned wrong results on some boxes of this pool when two
-// contexts alternated -- analysis in DESIGN.md section 4b; ABC_HIP_SYNC_ALLOC=1 turns the cache off.)
-static void *const kCapturing = (void *)(uintptr_t)1;
-// pin bookkeeping (callers hold alloc_mu)
-static void pin_add(abc_hip_ctx *c, void *p, void *owner) {
-  auto &v = c->pin[p];
-  for (void *o : v)
-    if (o == owner) return;
-  v.push_back(owner);
-}
-// drop `owner` from block p; a block nobody owns any more and that its user has already freed returns to the cache
-static void pin_drop(abc_hip_ctx *c, void *p, void *owner) {
-  auto it = c->pin.find(p);
-  if (it == c->pin.end()) return;
-  auto &v = it->second;
-  for (size_t i = 0; i < v.size(); i++)
-    if (v[i] == owner) {
-      v[i] = v.back();
-      v.pop_back();
-      break;
-    }
-  if (!v.empty()) return;
-  c->pin.erase(it);
-  if (c->parked.erase(p)) {
-    const size_t sz = c->block_size[p];
-    c->free_blocks[sz].push_back(p);
-    c->cached_bytes += sz;
-  }
-}
-
-int abc_hip_malloc(abc_hip_ctx *c, void **d_ptr, size_t bytes) {
-  CTX_GUARD(c);
-  if (!bytes) bytes = 8;
-  if (c->cache_alloc) {
-    std::lock_guard<std::mutex> lock(c->alloc_mu);
-    if (c->capture_active) {
-      // inside a capture: a block born and freed in this capture first (safe: stream order inside the graph), then the
-      // cache; never the driver (hipMalloc is not capturable) -- the sequence must have run once eagerly before
-      auto cf = c->cap_free.find(bytes);
-      if (cf != c->cap_free.end() && !cf->second.empty()) {
-        *d_ptr = cf->second.back();
-        cf->second.pop_back();
-        return 0;
-      }
-    }
-    auto it = c->free_blocks.find(bytes);
-    if (it != c->free_blocks.end() && !it->second.empty()) {
-      *d_ptr = it->second.back();
-      it->second.pop_back();
-      c->cached_bytes -= bytes;
-      if (c->capture_active) {
-        pin_add(c, *d_ptr, kCapturing);
-        c->cap_born[*d_ptr] = true;
-      }
-      return 0;
-    }
-    if (c->capture_active) {
-      set_error("allocation during graph capture found no cached buffer: run the sequence once eagerly first");
-      return 1;
-    }
-  }
-  ABC_HIP_CHECK(malloc_retry(c, d_ptr, bytes));
-  if (c->cache_alloc) {
-    std::lock_guard<std::mutex> lock(c->alloc_mu);
-    c->block_size[*d_ptr] = bytes;
-  }
-  return 0;
-}
-int abc_hip_free(abc_hip_ctx *c, void *d_ptr) {
-  CTX_GUARD(c);
-  if (!d_ptr) return 0;
-  if (c->cache_alloc) {
-    bool over_cap = false;
-    {
-      std::lock_guard<std::mutex> lock(c->alloc_mu);
-      auto it = c->block_size.find(d_ptr);
-      if (it != c->block_size.end()) {
-        if (c->capture_active) {
-          if (c->cap_born.count(d_ptr)) {  // an intermediate of the circuit being recorded
-            c->cap_free[it->second].push_back(d_ptr);
-          } else {  // existed before: the graph reads it as an input on every replay -- pinned, never reused
-            pin_add(c, d_ptr, kCapturing);
-            c->parked[d_ptr] = true;
-          }
-          return 0;
-        }
-        if (c->pin.count(d_ptr)) {  // baked into a live graph: parked until abc_hip_graph_destroy
-          c->parked[d_ptr] = true;
-          return 0;
-        }
-        if (c->cached_bytes + it->second <= c->cache_cap) {
-          c->free_blocks[it->second].push_back(d_ptr);
-          c->cached_bytes += it->second;
-          return 0;
-        }
-        c->block_size.erase(it);
-        over_cap = true;
-      }
-    }
-    // cap reached: exact-size buckets strand blocks when sizes vary, so give the whole cache back, not just this block
-    if (over_cap && trim_cache(c)) return 1;
-  }
-  NOT_CAPTURABLE(c, "abc_hip_free of an uncached buffer");
-  ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
-  ABC_HIP_CHECK(hipFree(d_ptr));
-  return 0;
-}
+// allocator and graph lifetime: abc_buffers.hip
+int abc_hip_malloc(abc_hip_ctx *c, void **d_ptr, size_t bytes) { CTX_GUARD(c); return buffer_malloc(c, d_ptr, bytes); }
+int abc_hip_free(abc_hip_ctx *c, void *d_ptr) { CTX_GUARD(c); return buffer_free(c, d_ptr); }
 int abc_hip_trim(abc_hip_ctx *c) {
   CTX_GUARD(c);
   NOT_CAPTURABLE(c, "abc_hip_trim");
   return trim_cache(c);
 }
-size_t abc_hip_cached_bytes(abc_hip_ctx *c) {
-  if (!c) return 0;
-  std::lock_guard<std::mutex> lock(c->alloc_mu);
-  return c->cached_bytes;
-}
+size_t abc_hip_cached_bytes(abc_hip_ctx *c) { return c ? cached_bytes(c) : 0; }
 int abc_hip_ctx_reload_env(abc_hip_ctx *c) {
   CTX_GUARD(c);
   NOT_CAPTURABLE(c, "abc_hip_ctx_reload_env");
@@ -929,9 +728,9 @@ static int load_key(abc_hip_ctx *c, uint64_t **slot, const uint64_t *h, size_t w
   NOT_CAPTURABLE(c, "key upload");
   ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
   const bool fresh = !*slot;
-  if (fresh) ABC_HIP_CHECK(hipMalloc(slot, words * 8));
+  if (fresh) ABC_HIP_CHECK(alloc_context_buffer(c, (void **)slot, words * 8, false));
   ABC_HIP_CHECK(hipMemcpy(*slot, h, words * 8, hipMemcpyHostToDevice));
-  if (!fresh) refresh_key_twins(c, *slot);
+  if (!fresh) refresh_key_mirrors(c, *slot);
   ABC_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -1134,90 +933,14 @@ int abc_hip_keyswitch(abc_hip_ctx *c, const uint64_t *target, uint32_t key_kind,
 }
 
 // ---- graph capture ----
-int abc_hip_graph_begin(abc_hip_ctx *c) {
-  CTX_GUARD(c);
-  ABC_HIP_CHECK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-  std::lock_guard<std::mutex> lock(c->alloc_mu);
-  c->capture_active = true;
-  return 0;
-}
-// hand every block the finished capture may have baked into the graph to `owner`; owner = nullptr (abandoned capture) releases
-// what the capture had pinned
-static void settle_capture(abc_hip_ctx *c, void *owner) {
-  std::lock_guard<std::mutex> lock(c->alloc_mu);
-  c->capture_active = false;
-  for (auto &kv : c->cap_free)
-    for (void *p : kv.second) c->parked[p] = true;  // born and freed inside the capture: nobody holds them any more
-  c->cap_free.clear();
-  c->cap_born.clear();
-  std::vector<void *> mine;
-  for (auto &kv : c->pin)
-    for (void *o : kv.second)
-      if (o == kCapturing) mine.push_back(kv.first);
-  for (void *p : mine) {
-    if (owner) pin_add(c, p, owner);
-    pin_drop(c, p, kCapturing);
-  }
-  if (!owner) return;
-  // every block still out with the caller: the recorded kernels may read it (an operand that existed before the capture and is
-  // freed only later never passed through abc_hip_malloc / abc_hip_free while capture_active was set)
-  std::unordered_map<void *, bool> cached;
-  for (auto &kv : c->free_blocks)
-    for (void *p : kv.second) cached[p] = true;
-  for (auto &kv : c->block_size)
-    if (!cached.count(kv.first)) pin_add(c, kv.first, owner);
-}
-int abc_hip_graph_end(abc_hip_ctx *c, void **out) {
-  CTX_GUARD(c);
-  hipGraph_t graph = nullptr;
-  hipError_t e = hipStreamEndCapture(c->stream, &graph);
-  hipGraphExec_t exec = nullptr;
-  if (e == hipSuccess) {
-    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-  }
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    settle_capture(c, nullptr);
-    set_error(std::string("graph capture failed: ") + hipGetErrorString(e));
-    return 1;
-  }
-  settle_capture(c, (void *)exec);
-  c->live_graphs[(void *)exec] = ++c->graph_seq;
-  *out = exec;
-  return 0;
-}
+int abc_hip_graph_begin(abc_hip_ctx *c) { CTX_GUARD(c); return graph_begin(c); }
+int abc_hip_graph_end(abc_hip_ctx *c, void **out) { CTX_GUARD(c); return graph_end(c, out); }
 int abc_hip_graph_launch(abc_hip_ctx *c, void *exec) {
   CTX_GUARD(c);
   ABC_HIP_CHECK(hipGraphLaunch((hipGraphExec_t)exec, c->stream));
   return 0;
 }
-int abc_hip_graph_destroy(abc_hip_ctx *c, void *exec) {
-  CTX_GUARD(c);
-  ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
-  ABC_HIP_CHECK(hipGraphExecDestroy((hipGraphExec_t)exec));
-  std::lock_guard<std::mutex> lock(c->alloc_mu);
-  std::vector<void *> mine;
-  for (auto &kv : c->pin)
-    for (void *o : kv.second)
-      if (o == exec) mine.push_back(kv.first);
-  for (void *p : mine) pin_drop(c, p, exec);  // unpin; what the caller had already freed goes back to the cache now
-  // scratch arenas and keys held back for this graph: freed once no live graph may read them (the stream is drained above)
-  c->live_graphs.erase(exec);
-  std::vector<abc_hip_ctx::Held> keep;
-  for (auto &h : c->held) {
-    for (size_t i = 0; i < h.graphs.size(); i++)
-      if (h.graphs[i] == exec) {
-        h.graphs[i] = h.graphs.back();
-        h.graphs.pop_back();
-        break;
-      }
-    if (h.graphs.empty()) (void)hipFree(h.p);
-    else keep.push_back(std::move(h));
-  }
-  c->held.swap(keep);
-  return 0;
-}
+int abc_hip_graph_destroy(abc_hip_ctx *c, void *exec) { CTX_GUARD(c); return graph_destroy(c, exec); }
 
 int abc_hip_microbench(abc_hip_ctx *c, int which, int iters, double *ms) { CTX_GUARD(c); return microbench(c, which, iters, ms); }
 

@@ -11,6 +11,7 @@
 #include <utility>
 #include <vector>
 
+#include "abc_buffers.hpp"
 #include "abc_modarith.hpp"
 #include "abc_ntt.hpp"
 
@@ -134,24 +135,12 @@ struct abc_hip_ctx {
   abc::Mod *d_mods = nullptr;
   uint64_t *d_tw = nullptr;
   double *d_ftw = nullptr;
-  // caching allocator behind abc_hip_malloc / abc_hip_free (abc_context.hip)
+  // Every device buffer a recorded circuit (abc_hip_graph_*) may have baked into its kernel arguments -- abc_hip_malloc blocks,
+  // workspace, arenas, keys, key mirrors -- and the graphs that own it: one table, one rule (abc_buffers.hpp), driven by
+  // abc_buffers.hip.  cache_alloc: abc_hip_free recycles blocks through the table's cache (off: ABC_HIP_SYNC_ALLOC=1).
   bool cache_alloc = false;
-  std::mutex alloc_mu;  // guards the three members below
-  size_t cached_bytes = 0, cache_cap = (size_t)8 << 30;
-  std::unordered_map<size_t, std::vector<void *>> free_blocks;  // size -> cached blocks
-  std::unordered_map<void *, size_t> block_size;                 // every live block handed out by abc_hip_malloc
-  // Blocks a recorded circuit (abc_hip_graph_*) may have baked into its kernel arguments are PINNED to it: while the graph exists
-  // they never go back to the free list, whoever frees them.  Pinned = every block this context had handed out and not yet got
-  // back when abc_hip_graph_end ran (a superset of what the sequence read: operands that existed before the capture -- cached
-  // plaintexts, inputs -- are covered without tracing every pointer argument) plus every block the capture itself took from the
-  // cache.  pin: block -> graphs that own it (kCapturing stands for the capture in progress); parked: pinned blocks the caller
-  // has already freed (released to the cache when their last graph is destroyed); cap_free: blocks allocated AND freed during the
-  // running capture, reusable inside it (stream order inside the graph).
-  bool capture_active = false;
-  std::unordered_map<void *, std::vector<void *>> pin;
-  std::unordered_map<void *, bool> parked;
-  std::unordered_map<size_t, std::vector<void *>> cap_free;
-  std::unordered_map<void *, bool> cap_born;  // allocated during the running capture
+  mutable std::mutex alloc_mu;  // guards `buffers`
+  abc::BufferTable buffers;
   bool behz_fp = false;  // BFV: 50-bit BEHZ auxiliary base and fp64 base-conversion kernels
   bool use_fp = true;  // fp64 transforms for primes < 2^50 (ABC_HIP_NO_FP64=1 forces the integer path)
   // Path switches (A/B timing and the parity tests of every fallback): the ABC_HIP_* environment variables are read
@@ -170,30 +159,21 @@ struct abc_hip_ctx {
   // keys (device)
   uint64_t *d_sk = nullptr, *d_pk = nullptr, *d_relin = nullptr;
   std::map<uint32_t, uint64_t *> d_galois;
-  // fp64 twins of key-switching keys (centred doubles, same layout), built on first use by the fp64 split kernels, rebuilt in place
-  // when the key they mirror is rewritten (abc_kernels_fused.hip, key_twin / refresh_key_twins)
-  std::unordered_map<const uint64_t *, double *> key_twins;
-  std::unordered_map<const uint64_t *, uint64_t *> key_shoups;  // Shoup quotients of a key (abc_kernels_eval.hip, key_shoup)
+  // mirrors of key-switching keys (fp64 twin: centred doubles; Shoup quotients; same layout), built on first use, rebuilt in place
+  // when the key they mirror is rewritten (abc_buffers.hip)
+  struct KeyMirror {
+    double *twin = nullptr;
+    uint64_t *shoup = nullptr;
+  };
+  std::unordered_map<const uint64_t *, KeyMirror> key_mirrors;
   std::vector<uint32_t> galois_order;
   // workspace (kernel-sequence scratch) and three caller-level arenas (products, rotation ping-pong buffers);
-  // all grow on demand and are reused, so steady-state calls perform no hipMalloc / hipFree
+  // all grow on demand and are reused, so steady-state calls perform no hipMalloc / hipFree; one that grows while a graph owns
+  // it is held back, not freed (ensure_arena in abc_buffers.hip)
   void *ws = nullptr;
   size_t ws_bytes = 0;
   void *aux[3] = {nullptr, nullptr, nullptr};
   size_t aux_bytes[3] = {0, 0, 0};
-  // Recorded circuits alive (abc_hip_graph_end .. abc_hip_graph_destroy) and the device buffers held back for them.  A graph
-  // bakes the arenas, keys and key mirrors it used into its kernel arguments; an arena that grows, or a key that goes, while a
-  // graph that may have recorded it is alive is moved to `held` instead of being freed, and freed when the last of those graphs is
-  // destroyed (retire_buffer).  graph_seq numbers the captures; an arena is stamped with the number current when it was
-  // allocated, so only the graphs that ended after that can hold it.
-  uint64_t graph_seq = 0;
-  std::unordered_map<void *, uint64_t> live_graphs;  // exec -> its capture number
-  struct Held {
-    void *p;
-    std::vector<void *> graphs;
-  };
-  std::vector<Held> held;
-  uint64_t ws_born = 0, aux_born[3] = {0, 0, 0};
   size_t limb_words() const { return (size_t)n; }
   size_t key_words() const { return (size_t)L * 2 * K * n; }
 };
@@ -210,12 +190,36 @@ void set_error(const std::string &msg);
     }                                                                                               \
   } while (0)
 
-// workspace: grows on demand (never inside a timed region after warm-up)
+// grid of a grid-stride kernel over `items`: enough workgroups to fill 256 CUs several times, the stride loop beyond
+inline unsigned grid_for(size_t items, int block) {
+  size_t g = (items + block - 1) / block;
+  const size_t cap = 256 * 8 * 4;
+  return (unsigned)(g < cap ? (g ? g : 1) : cap);
+}
+// Host-synchronising entry points cannot be recorded, and letting HIP find that out invalidates the capture for good on this
+// runtime (the stream keeps returning hipErrorStreamCaptureInvalidated even after hipStreamEndCapture): refuse up front.
+#define NOT_CAPTURABLE(c, what)                                                                                   \
+  do {                                                                                                            \
+    if ((c)->buffers.capturing) { abc::set_error(what ": not capturable (host transfer / synchronisation inside abc_hip_graph_begin..end)"); return 1; } \
+  } while (0)
+
+// ---- abc_buffers.hip: every allocation a recorded circuit may read, and the bodies of the C entry points of that name ----
+int buffer_malloc(abc_hip_ctx *c, void **d_ptr, size_t bytes);
+int buffer_free(abc_hip_ctx *c, void *d_ptr);
+int trim_cache(abc_hip_ctx *c);
+size_t cached_bytes(abc_hip_ctx *c);
+int graph_begin(abc_hip_ctx *c);
+int graph_end(abc_hip_ctx *c, void **out);
+int graph_destroy(abc_hip_ctx *c, void *exec);
+int held_buffers(const abc_hip_ctx *c);  // context buffers retired while a live graph owns them
+void free_buffers(abc_hip_ctx *c);       // abc_hip_ctx_destroy: everything the table still tracks
+// workspace / arena `which`: grow on demand (never inside a timed region after warm-up, never inside a capture)
 int ensure_workspace(abc_hip_ctx *c, size_t bytes);
 int ensure_aux(abc_hip_ctx *c, int which, size_t bytes);
-// free device buffer p (stamped `born`, see abc_hip_ctx::graph_seq), or hold it back while a live graph may reference it; the
-// caller has drained c->stream
-void retire_buffer(abc_hip_ctx *c, void *p, uint64_t born);
+// hipMalloc of a context buffer (a key, a mirror, an arena), entered into the table; retry: flush the cache once on failure
+hipError_t alloc_context_buffer(abc_hip_ctx *c, void **p, size_t bytes, bool retry);
+// free context buffer p, or hold it back while a live graph owns it; the caller has drained c->stream
+void retire_buffer(abc_hip_ctx *c, void *p);
 void read_switches(abc_hip_ctx *c);
 
 // ---- launchers implemented in the kernel translation units ----
@@ -319,14 +323,13 @@ int bsplit_back14(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const doubl
                   size_t addend_stride, int add_c1, u64 *out, u32 ginv = 0);
 int bsplit_back13(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const double *part, double *half, const u64 *key, const u64 *addend,
                   size_t addend_stride, int add_c1, u64 *out, u32 ginv = 0);
-// the fp64 twin of a key-switching key (nullptr: not available -- capture in progress and not built yet, or allocation failed)
+// the mirrors of a key-switching key (nullptr: not available -- capture in progress and not built yet, or allocation failed)
 const double *key_twin(abc_hip_ctx *c, const u64 *key);
 const double *key_twin_lookup(const abc_hip_ctx *c, const u64 *key);  // never builds: safe once the lanes have forked
-void drop_key_twins(abc_hip_ctx *c, const u64 *key /* nullptr: all */);
-// rewrite the existing mirrors (fp64 twin, Shoup quotients) of `key` (nullptr: of every key) from its current words, in the same
-// buffers, on c->stream: a recorded circuit keeps their addresses and reads the new key
-void refresh_key_twins(abc_hip_ctx *c, const u64 *key /* nullptr: all */);
-void refresh_key_shoups(abc_hip_ctx *c, const u64 *key /* nullptr: all */);  // abc_kernels_eval.hip
+const u64 *key_shoup(abc_hip_ctx *c, const u64 *key);
+// rewrite the existing mirrors of `key` (nullptr: of every key) from its current words, in the same buffers, on c->stream: a
+// recorded circuit keeps their addresses and reads the new key
+void refresh_key_mirrors(abc_hip_ctx *c, const u64 *key /* nullptr: all */);
 // a key-switching key that goes (keygen drops a non-default Galois element): the key and its mirrors are retired
 void release_key(abc_hip_ctx *c, u64 *key);
 // internal lanes (streams forked off the context's stream): chunks of one call alternate over them (abc_kernels_fused.hip)

@@ -18,12 +18,6 @@
 
 namespace abc {
 
-static inline unsigned grid_for(size_t items, int block) {
-  size_t g = (items + block - 1) / block;
-  const size_t cap = 256 * 8 * 4;
-  return (unsigned)(g < cap ? (g ? g : 1) : cap);
-}
-
 // sum_i a[i]*b[i] mod m with a[i] < 2^61, b[i] < m.q: flush the 128-bit accumulator every 4 terms
 // (barrett_reduce precondition x < 2^(k+63)).
 template <class FA, class FB>

@@ -20,12 +20,6 @@ LimbMap key_limb_map(const abc_hip_ctx *c, int nl) {
   return m;
 }
 
-static inline unsigned grid_for(size_t items, int block) {
-  size_t g = (items + block - 1) / block;
-  const size_t cap = 256 * 8 * 4;  // enough workgroups to fill 256 CUs several times, grid-stride beyond
-  return (unsigned)(g < cap ? (g ? g : 1) : cap);
-}
-
 // ---- limb-wise add / sub / negate:  data viewed as [polys][nl][N] ----
 __global__ __launch_bounds__(256) void k_addsub(DevCtx c, const u64 *a, const u64 *b, u64 *out, int nl, size_t words, int op) {
   const size_t stride = (size_t)gridDim.x * blockDim.x * 2;
@@ -236,43 +230,6 @@ __global__ __launch_bounds__(256) void k_iks_pass0(DevCtx c, const u64 *__restri
   u64 *__restrict__ dst = dec + limb * (size_t)c.n + p;
 #pragma unroll
   for (int k = 0; k < (1 << R); k++) dst[(size_t)k * G] = x[k];  // lazy [0, 4q): the block stages are guarded
-}
-
-// Shoup quotients of a key-switching key, floor(w 2^64 / q) per word, same layout: with them a term of the inner product is one
-// lazy Shoup product of ANY 64-bit transform output (no canonicalisation, no 128-bit product, no Barrett): built on first use,
-// rebuilt in place with the key's other mirror when the key is rewritten (refresh_key_twins).
-__global__ __launch_bounds__(256) void k_key_to_shoup(DevCtx c, const u64 *__restrict__ key, u64 *__restrict__ ks, size_t words) {
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += stride) {
-    const int kp = (int)((i >> c.logn) % (size_t)c.K);
-    const u64 q = c.mods[kp].q;
-    u64 r = key[i], quo = 0;  // r < q < 2^61: schoolbook division of r 2^64 by q, one quotient bit per step
-    for (int bit = 0; bit < 64; bit++) {
-      r <<= 1;
-      const bool ge = r >= q;
-      r -= ge ? q : 0;
-      quo = (quo << 1) | (ge ? 1u : 0u);
-    }
-    ks[i] = quo;
-  }
-}
-static const u64 *key_shoup(abc_hip_ctx *c, const u64 *key) {
-  if (c->sw.no_key_twin || !key) return nullptr;
-  auto it = c->key_shoups.find(key);
-  if (it != c->key_shoups.end()) return it->second;
-  if (c->capture_active) return nullptr;  // built by the eager pass that precedes every recording
-  u64 *d = nullptr;
-  const size_t words = c->key_words();
-  if (hipMalloc(&d, words * 8) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  hipLaunchKernelGGL(k_key_to_shoup, dim3(grid_for(words, 256)), dim3(256), 0, c->stream, c->dc, key, d, words);
-  c->key_shoups[key] = d;
-  return d;
-}
-void refresh_key_shoups(abc_hip_ctx *c, const u64 *key) {
-  const size_t words = c->key_words();
-  for (auto &kv : c->key_shoups)
-    if (!key || kv.first == key)
-      hipLaunchKernelGGL(k_key_to_shoup, dim3(grid_for(words, 256)), dim3(256), 0, c->stream, c->dc, kv.first, kv.second, words);
 }
 
 // INV_D: the data limbs' sums go back to coefficients too (BFV); CKKS keeps them in NTT form.  SHOUP: `keys` = the key's Shoup

@@ -35,12 +35,6 @@
 
 namespace abc {
 
-static inline unsigned stream_grid(size_t items, int block) {
-  size_t g = (items + block - 1) / block;
-  const size_t cap = 256 * 8 * 4;
-  return (unsigned)(g < cap ? (g ? g : 1) : cap);
-}
-
 // ---------------------------------------------------------------------------------------------------------------
 // K1 (CKKS multiply front end)
 // ---------------------------------------------------------------------------------------------------------------
@@ -257,74 +251,6 @@ __global__ __launch_bounds__((1 << LB) / 16) void k_fused_ks_moddown_bfv(DevCtx 
         },
         t, m, 0, 0);
   }
-}
-
-// ---- fp64 twins of key-switching keys -----------------------------------------------------------------------------------
-// The split kernels multiply every key word into an fp64 residue: as u64 it costs a conversion per use (two instructions, sixteen
-// words per thread of the last step); as a centred double, converted once when the key is first used, nothing.  Same layout
-// [digit][2][K][N]; words modulo primes above 2^52 convert inexactly and are never read (the fp64 kernels touch fp64-capable
-// primes only).
-__global__ __launch_bounds__(256) void k_key_to_fp(DevCtx c, const u64 *__restrict__ key, double *__restrict__ keyf, size_t words) {
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += stride) {
-    const int kp = (int)((i >> c.logn) % (size_t)c.K);
-    const u64 q = c.mods[kp].q, v = key[i];
-    keyf[i] = v > (q >> 1) ? -(double)(q - v) : (double)v;
-  }
-}
-const double *key_twin_lookup(const abc_hip_ctx *c, const u64 *key) {  // no building: safe after the lanes have forked
-  if (c->sw.no_key_twin) return nullptr;
-  auto it = c->key_twins.find(key);
-  return it == c->key_twins.end() ? nullptr : it->second;
-}
-// call BEFORE fork_lanes: the conversion runs on c->stream and the lanes wait for an event recorded behind it
-const double *key_twin(abc_hip_ctx *c, const u64 *key) {
-  if (c->sw.no_key_twin || !key) return nullptr;
-  auto it = c->key_twins.find(key);
-  if (it != c->key_twins.end()) return it->second;
-  if (c->capture_active) return nullptr;  // built by the eager pass that precedes every recording
-  double *d = nullptr;
-  const size_t words = c->key_words();
-  if (hipMalloc(&d, words * 8) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  hipLaunchKernelGGL(k_key_to_fp, dim3(stream_grid(words, 256)), dim3(256), 0, c->stream, c->dc, key, d, words);
-  c->key_twins[key] = d;
-  return d;
-}
-void drop_key_twins(abc_hip_ctx *c, const u64 *key) {
-  if (c->key_twins.empty() && c->key_shoups.empty()) return;
-  (void)hipStreamSynchronize(c->stream);
-  auto drop = [&](auto &map) {
-    if (!key) {
-      for (auto &kv : map) (void)hipFree(kv.second);
-      map.clear();
-      return;
-    }
-    auto it = map.find(key);
-    if (it != map.end()) {
-      (void)hipFree(it->second);
-      map.erase(it);
-    }
-  };
-  drop(c->key_twins);
-  drop(c->key_shoups);
-}
-void refresh_key_twins(abc_hip_ctx *c, const u64 *key) {
-  const size_t words = c->key_words();
-  for (auto &kv : c->key_twins)  // whatever the switches say now: a recorded circuit may read the twin
-    if (!key || kv.first == key)
-      hipLaunchKernelGGL(k_key_to_fp, dim3(stream_grid(words, 256)), dim3(256), 0, c->stream, c->dc, kv.first, kv.second, words);
-  refresh_key_shoups(c, key);
-}
-void release_key(abc_hip_ctx *c, u64 *key) {
-  auto take = [&](auto &map) {
-    auto it = map.find(key);
-    if (it == map.end()) return;
-    retire_buffer(c, it->second, 0);
-    map.erase(it);
-  };
-  take(c->key_twins);
-  take(c->key_shoups);
-  retire_buffer(c, key, 0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1202,7 +1128,7 @@ static int keyswitch_stage(abc_hip_ctx *c, hipStream_t st, const FusedScratch &s
   if (all_fp(c)) {
     if (!dec_ready)
       hipLaunchKernelGGL(k_fused_ks_decomp_ntt_fp<LB>, dim3(g2a), block, 0, st, c->dc, coef, coef_stride, s.dec, nl, ckks ? 1 : 0);
-    hipLaunchKernelGGL(k_fused_ks_mac, dim3(stream_grid(cc * (nl + 1) * (N / 2), 256)), dim3(256), 0, st, c->dc, s.dec,
+    hipLaunchKernelGGL(k_fused_ks_mac, dim3(grid_for(cc * (nl + 1) * (N / 2), 256)), dim3(256), 0, st, c->dc, s.dec,
                        ckks ? ntt : (const u64 *)nullptr, ntt_stride, key, s.ksacc, s.tsp, nl, cc);
     hipLaunchKernelGGL(k_fused_ks_special_intt_fp<LB>, dim3((unsigned)(cc * 2)), block, 0, st, c->dc, s.tsp, s.tlast);
     if (ckks)
@@ -1225,7 +1151,7 @@ static int keyswitch_stage(abc_hip_ctx *c, hipStream_t st, const FusedScratch &s
   else
     hipLaunchKernelGGL((k_fused_ks_decomp_ntt<LB, false, false>), dim3(g2a), block, 0, st, c->dc, coef, coef_stride, s.dec, nl,
                        ckks ? 1 : 0);
-  hipLaunchKernelGGL(k_fused_ks_mac, dim3(stream_grid(cc * (nl + 1) * (N / 2), 256)), dim3(256), 0, st, c->dc, s.dec,
+  hipLaunchKernelGGL(k_fused_ks_mac, dim3(grid_for(cc * (nl + 1) * (N / 2), 256)), dim3(256), 0, st, c->dc, s.dec,
                      ckks ? ntt : (const u64 *)nullptr, ntt_stride, key, s.ksacc, s.tsp, nl, cc);
   hipLaunchKernelGGL(k_fused_ks_special_intt<LB>, dim3((unsigned)(cc * 2)), block, 0, st, c->dc, s.tsp, s.tlast);
   if (!ckks)

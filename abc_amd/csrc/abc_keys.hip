@@ -26,12 +26,6 @@ namespace abc {
 
 int launch_bfv_decrypt_round(abc_hip_ctx *c, const u64 *phase, u64 *plain, size_t count);
 
-static inline unsigned grid_for(size_t items, int block) {
-  size_t g = (items + block - 1) / block;
-  const size_t cap = 256 * 8 * 4;
-  return (unsigned)(g < cap ? (g ? g : 1) : cap);
-}
-
 // ---------------- host samplers ----------------
 // Two generators behind one interface.  Rng (splitmix64-seeded xoshiro256**) is this repo's SAMPLING SPEC for parity tests:
 // the oracle implements the same stream, so keys and ciphertexts are bit-comparable -- it is NOT a cryptographic generator
@@ -271,18 +265,18 @@ static int keygen_with(abc_hip_ctx *c, P &pub, S &sec) {
   // secret key
   for (size_t x = 0; x < N; x++) h_e[x] = sec.ternary();
   ABC_HIP_CHECK(hipMemcpyAsync(d_e8, h_e.data(), N, hipMemcpyHostToDevice, c->stream));
-  if (!c->d_sk) ABC_HIP_CHECK(hipMalloc(&c->d_sk, (size_t)K * N * 8));
+  if (!c->d_sk) ABC_HIP_CHECK(alloc_context_buffer(c, (void **)&c->d_sk, (size_t)K * N * 8, false));
   hipLaunchKernelGGL(k_small_to_rns, dim3(grid_for((size_t)K * N, 256)), dim3(256), 0, c->stream, c->dc, d_e8, (size_t)1, N, (size_t)0,
                      c->d_sk, kmap, K, (size_t)1);
   ABC_HIP_CHECK(hipGetLastError());
   if (launch_ntt_fwd(c, c->d_sk, kmap, K, K)) return 1;
   ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
   // public key = one symmetric encryption of zero at key level
-  if (!c->d_pk) ABC_HIP_CHECK(hipMalloc(&c->d_pk, (size_t)2 * K * N * 8));
+  if (!c->d_pk) ABC_HIP_CHECK(alloc_context_buffer(c, (void **)&c->d_pk, (size_t)2 * K * N * 8, false));
   if (make_kskey(c, pub, sec, nullptr, c->d_pk, h_a, h_e, d_a, d_e8, d_e, 1)) return 1;
   // relinearisation key: switches s^2 -> s.  Every key-switching key is regenerated into the buffer it already has, and its
   // mirrors are rebuilt in place at the end: a recorded circuit keeps the addresses it baked in (include/abc_hip.h, graphs).
-  if (!c->d_relin) ABC_HIP_CHECK(hipMalloc(&c->d_relin, c->key_words() * 8));
+  if (!c->d_relin) ABC_HIP_CHECK(alloc_context_buffer(c, (void **)&c->d_relin, c->key_words() * 8, false));
   hipLaunchKernelGGL(k_dyadic_mul, dim3(grid_for((size_t)K * N, 256)), dim3(256), 0, c->stream, c->dc, c->d_sk, c->d_sk,
                      (size_t)0, d_newkey, kmap, K, (size_t)1);
   ABC_HIP_CHECK(hipGetLastError());
@@ -308,7 +302,7 @@ static int keygen_with(abc_hip_ctx *c, P &pub, S &sec) {
       d_key = reuse->second;
       old_galois.erase(reuse);
     } else {
-      ABC_HIP_CHECK(hipMalloc(&d_key, c->key_words() * 8));
+      ABC_HIP_CHECK(alloc_context_buffer(c, (void **)&d_key, c->key_words() * 8, false));
     }
     if (launch_galois(c, c->d_sk, d_newkey, K, 1, elt, true)) return 1;
     if (make_kskey(c, pub, sec, d_newkey, d_key, h_a, h_e, d_a, d_e8, d_e, L)) return 1;
@@ -321,7 +315,7 @@ static int keygen_with(abc_hip_ctx *c, P &pub, S &sec) {
   (void)hipMemsetAsync(d_newkey, 0, (size_t)K * N * 8, c->stream);
   ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
   for (auto &kv : old_galois) release_key(c, kv.second);  // held back while a live graph may read it
-  refresh_key_twins(c, nullptr);
+  refresh_key_mirrors(c, nullptr);
   ABC_HIP_CHECK(hipGetLastError());
   explicit_bzero(h_e.data(), h_e.size());
   (void)hipFree(d_a); (void)hipFree(d_e); (void)hipFree(d_e8); (void)hipFree(d_newkey);

@@ -49,8 +49,9 @@ int abc_hip_default_bfv_primes(size_t n, uint64_t *h_out);
 uint64_t abc_hip_plain_modulus_batching(size_t n, int bits);
 /* seal::CoeffModulus::Create(N, bit_sizes) ordering, for CKKS chains */
 int abc_hip_create_primes(size_t n, const int *bit_sizes, int count, uint64_t *h_out);
-/* 0 scheme, 1 logn, 2 nprimes, 3 L, 4 device, 5 BEHZ Bsk size, 6 device buffers held back for live graphs (scratch arenas
- * and keys that were replaced while a graph that may have recorded them was alive); -1 for an unknown `what` */
+/* 0 scheme, 1 logn, 2 nprimes, 3 L, 4 device, 5 BEHZ Bsk size, 6 device buffers held back for live graphs (scratch arenas,
+ * keys and key mirrors that were replaced or dropped while a graph that owns them is alive; parked abc_hip_malloc blocks are not
+ * counted); -1 for an unknown `what` */
 int abc_hip_ctx_info(const abc_hip_ctx *ctx, int what);
 /* Every operation of the context is enqueued on `hip_stream` from now on.  NULL does NOT mean HIP's legacy default
  * stream: it selects the context's own private non-blocking stream again (the state after abc_hip_ctx_create), which is

@@ -3,9 +3,11 @@
 cd "$(dirname "$0")/.."
 echo "# hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage (static LDS only: dynamic LDS is set at launch)"
 echo "file | kernel | VGPRs | scratch B/lane | waves/SIMD | static LDS B"
-for f in bfv bmul ckks_codec eval fused gsplit isplit ntt; do
+for f in bfv bmul ckks_codec eval fused gsplit isplit ntt buffers; do
+  src=abc_amd/csrc/abc_kernels_$f.hip
+  [ $f = buffers ] && src=abc_amd/csrc/abc_buffers.hip  # the two key-mirror kernels
   /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -Wno-pass-failed -I include -c --cuda-device-only \
-    -Rpass-analysis=kernel-resource-usage -o /dev/null abc_amd/csrc/abc_kernels_$f.hip 2>&1 | sed 's/ \[-Rpass-analysis=kernel-resource-usage\]//' |
+    -Rpass-analysis=kernel-resource-usage -o /dev/null $src 2>&1 | sed 's/ \[-Rpass-analysis=kernel-resource-usage\]//' |
     awk -v F=$f '/Function Name:/ {n=$NF} / VGPRs:/ {v=$NF} /ScratchSize/ {s=$NF} /Occupancy/ {o=$NF} /LDS Size/ {print F" | "n" | "v" | "s" | "o" | "$NF}' |
     while IFS= read -r line; do
       sym=$(echo "$line" | cut -d'|' -f2 | tr -d ' ')
