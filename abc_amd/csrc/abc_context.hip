@@ -99,14 +99,11 @@ static void fill_twiddles(uint64_t q, int logn, uint64_t *dst /*[2][N][2]*/) {
   }
 }
 
-// fp64 twin of one modulus' twiddle table: {w centred into (-q/2, q/2], w / q} (both exact-operand roundings)
-static void fill_fp_twiddles(uint64_t q, size_t n, const uint64_t *src /*[2][N][2]*/, double *dst) {
-  const double qd = (double)q;
+// fp64 twin of one modulus' twiddle table: w centred into (-q/2, q/2], one double per twiddle (exact: |w| < 2^49)
+static void fill_fp_twiddles(uint64_t q, size_t n, const uint64_t *src /*[2][N][2]*/, double *dst /*[2][N]*/) {
   for (size_t i = 0; i < 2 * n; i++) {
     const uint64_t w = src[2 * i];
-    const double wc = w > q / 2 ? -(double)(q - w) : (double)w;
-    dst[2 * i] = wc;
-    dst[2 * i + 1] = wc / qd;
+    dst[i] = w > q / 2 ? -(double)(q - w) : (double)w;
   }
 }
 
@@ -165,13 +162,13 @@ static int build_context(abc_hip_ctx *c) {
   const int id_bsk = K, id_gamma = K + c->nBsk, id_t = K + c->nBsk + 1;
   c->h_mods.clear();
   std::vector<uint64_t> h_tw((size_t)nmods * 4 * N, 0);
-  std::vector<double> h_ftw((size_t)nmods * 4 * N, 0.0);
+  std::vector<double> h_ftw((size_t)nmods * 2 * N, 0.0);
   for (int i = 0; i < nmods; i++) {
     const bool ntt = !(bfv && i == id_gamma);
     c->h_mods.push_back(make_mod(c->mod_values[i], logn, ntt));
     if (ntt) fill_twiddles(c->mod_values[i], logn, h_tw.data() + (size_t)i * 4 * N);
     if (ntt && fp_ok(c->h_mods.back().bits))
-      fill_fp_twiddles(c->mod_values[i], N, h_tw.data() + (size_t)i * 4 * N, h_ftw.data() + (size_t)i * 4 * N);
+      fill_fp_twiddles(c->mod_values[i], N, h_tw.data() + (size_t)i * 4 * N, h_ftw.data() + (size_t)i * 2 * N);
   }
 
   // ---- key / modulus switching constants ----

@@ -77,7 +77,7 @@ struct DevConstFp {
 struct DevCtx {
   const Mod *mods;      // [nmods]
   const u64 *tw;        // [nmods][2][N][2]: forward {w, Shoup} pairs, then inverse pairs
-  const double *ftw;    // same shape, fp64 twin {w centred, w / q}; filled for primes < 2^50 only
+  const double *ftw;    // [nmods][2][N]: fp64 twin, w centred (one double per twiddle), forward then inverse; primes < 2^50 only
   const DevConst *cst;  //
   const DevConstFp *cstf;  // null unless the BEHZ base is fp64-capable
   const u32 *slot_map;  // [N] BatchEncoder index map (BFV)
@@ -105,10 +105,10 @@ __device__ __forceinline__ Mod mod_at(const DevCtx &c, int id) {
   return m;
 }
 __device__ __forceinline__ FpTable fp_table(const DevCtx &c, int mid) {
-  const double *b = c.ftw + (size_t)mid * 4 * c.n;
+  const double *b = c.ftw + (size_t)mid * 2 * c.n;
   FpTable t;
-  t.tw = (const ABC_CONST_AS f64x2 *)(b);
-  t.itw = (const ABC_CONST_AS f64x2 *)(b + 2 * (size_t)c.n);
+  t.tw = (const ABC_CONST_AS double *)(b);
+  t.itw = (const ABC_CONST_AS double *)(b + (size_t)c.n);
   return t;
 }
 
@@ -293,7 +293,8 @@ struct MainArgs {
   int pack;  // the half-done limbs are packed (abc_ntt.hpp; k_split4_main_fp only)
 };
 constexpr u64 kAllSlots = 0xfedcba9876543210ull;
-constexpr size_t main_lds_bytes(int nl) { return (size_t)((nl + 1) * lds_words(10)) * 8 + 1024 * 16; }  // nl + 1 buffers + twiddle table
+// nl + 1 transform buffers + the block's twiddle table, 1024 entries of tw_bytes = sizeof(A::TW): 8 (fp64) or 16 (integer)
+constexpr size_t main_lds_bytes(int nl, int tw_bytes) { return (size_t)((nl + 1) * lds_words(10)) * 8 + 1024 * (size_t)tw_bytes; }
 // (mode, gelt) -> f(MODE, GAL) as integral constants: multiply / key switch with the Galois gather folded in / plain key switch
 template <class Fn>
 inline void dispatch_mode(int mode, u32 gelt, Fn f) {

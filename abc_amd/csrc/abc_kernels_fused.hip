@@ -896,7 +896,7 @@ static void launch_split3_main(abc_hip_ctx *c, const MainArgs &a) {
 
 // ---- "split4": K2c with every vector-memory request issued up front ----------------------------------------------------------
 // Same arithmetic and the same buffers as k_split3_main_fp.  What changes is the order of memory requests inside a wavefront:
-// the per-lane twiddles of the tail transform come from an LDS table of the block's own twiddles (16 KiB per workgroup, filled
+// the per-lane twiddles of the tail transform come from an LDS table of the block's own twiddles (8 KiB per workgroup, filled
 // cooperatively) instead of vector loads, so nothing in the transform touches the in-order vector-memory counter any more and
 // the operands of the phase AFTER the transform (key slices, a and b) can be requested before it: one exposed memory latency per
 // workgroup instead of two, and the transform runs under the second one.
@@ -916,11 +916,18 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_split4_main_fp(DevCtx 
   // grid (ct, slot, block), slot < ni; the data prime of a slot is nibble `slot` of imap (all of them: 0x76543210, ni = nl; a subset
   // when a chain mixes fp64-capable and wider primes: abc_kernels_isplit.hip)
   // pack: the half-done limbs of `part` / `tpart` modulo primes of at most 48 bits arrive packed (abc_ntt.hpp)
-  extern __shared__ double dyn[];  // nl + 1 transform buffers, then the block's twiddle table (1024 {w, w/q} pairs)
+  extern __shared__ double dyn[];  // nl + 1 transform buffers, then the block's twiddle table (1024 doubles)
   // 512 threads whatever nl: one coefficient pair per thread afterwards, so every operand of that phase is requested up front;
   // wavefronts nl + 1 .. 7 have no limb to transform and only take part in the table fill and the inner product
   static_assert(NL + 1 <= 8, "one wavefront per limb, eight wavefronts");
   constexpr int nl = NL, NT = 512, PER = 2;
+  // LATE: digits whose key words are requested AFTER the transform.  The multiply at four limbs holds 48 VGPRs of prefetched
+  // operands across the transform and sits on the 128-VGPR ceiling of two workgroups per CU; the butterfly's quotient now hangs
+  // on its own product (one multiply more in the chain, abc_ntt.hpp), which cost five more live registers and, with everything
+  // prefetched, 20 bytes of scratch per lane -- scratch reloads go through the same in-order vmcnt as the prefetch.  The last
+  // digit's eight registers are therefore loaded late: its words come out of L2 and are used last, behind the other digits'
+  // products (123 VGPRs, no scratch).
+  constexpr int LATE = (MODE == 0 && NL == 4) ? 1 : 0;
   const int W = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = threadIdx.x & 63;
   const int blk = blockIdx.x & 15;
@@ -930,15 +937,15 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_split4_main_fp(DevCtx 
   const Mod m = mod_at(c, I);
   const FpTable t = fp_table(c, I);
   const double q = m.qd, qinv = m.qinv;
-  f64x2 *ltw = reinterpret_cast<f64x2 *>(dyn + (nl + 1) * lds_words(10));
+  double *ltw = dyn + (nl + 1) * lds_words(10);
   const size_t pw = (size_t)nl * N;
   // scalar loads (constant address space): a vector load of these after the transform would expose one more memory latency
   const ABC_CONST_AS DevConst *cst = (const ABC_CONST_AS DevConst *)c.cst;
   const double inv = cst->inv_special_c[I], inv_q = cst->inv_special_cq[I];
 
   // (1) twiddle table, (2) this wavefront's half-done limb, (3) the operands of this thread's first coefficient pair
-  f64x2 twv[PER];
-  block_twiddles_fetch<10, f64x2, PER>(t.tw, 4, blk, (int)threadIdx.x, NT, twv);
+  double twv[PER];
+  block_twiddles_fetch<10, double, PER>(t.tw, 4, blk, (int)threadIdx.x, NT, twv);
   const bool has_limb = W <= nl;  // wavefront-uniform
   const int Wc = has_limb ? W : 0;
   const double *__restrict__ src = (Wc < nl - 1) ? part + ((ct * (nl + 1) + I) * nl + (Wc < I ? Wc : Wc + 1)) * (size_t)c.ps + base
@@ -957,15 +964,19 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_split4_main_fp(DevCtx 
       for (int k = 0; k < 8; k++) raw[k] = pack_load_pair<2>(src - base, N, base + (k << 7) + 2 * lane);
     }
   }
-  auto load_pair = [&](int e, PairOps<MODE, NL> &o) {
-    // key words: 16 raw bytes per (digit, component) either way -- the key's fp64 twin where it exists (keyf, workgroup-uniform:
-    // the words ARE the doubles), the u64 key otherwise (converted when used, after the transform)
+  // key words: 16 raw bytes per (digit, component) either way -- the key's fp64 twin where it exists (keyf, workgroup-uniform:
+  // the words ARE the doubles), the u64 key otherwise (converted when used, after the transform)
+  auto load_key = [&](int e, PairOps<MODE, NL> &o, int j0, int j1) {
     const u64 *kw = keyf ? reinterpret_cast<const u64 *>(keyf) : key;
 #pragma unroll
     for (int Jx = 0; Jx < NL; Jx++) {
+      if (Jx < j0 || Jx >= j1) continue;
       o.k0[Jx] = *reinterpret_cast<const u64x2 *>(kw + (((size_t)Jx * 2 + 0) * c.K + I) * N + base + e);
       o.k1[Jx] = *reinterpret_cast<const u64x2 *>(kw + (((size_t)Jx * 2 + 1) * c.K + I) * N + base + e);
     }
+  };
+  auto load_pair = [&](int e, PairOps<MODE, NL> &o) {
+    load_key(e, o, 0, NL - LATE);
     if (MODE == 0) {
       const u64 *pa = opa + ct * 2 * pw + (size_t)I * N + base + e, *pb = opb + ct * 2 * pw + (size_t)I * N + base + e;
       o.a0 = *reinterpret_cast<const u64x2 *>(pa); o.a1 = *reinterpret_cast<const u64x2 *>(pa + pw);
@@ -988,7 +999,7 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_split4_main_fp(DevCtx 
   PairOps<MODE, NL> ops;
   load_pair(2 * (int)threadIdx.x, ops);
 
-  block_twiddles_store<10, f64x2, PER>(ltw, (int)threadIdx.x, NT, twv);
+  block_twiddles_store<10, double, PER>(ltw, (int)threadIdx.x, NT, twv);
   __syncthreads();
   if (has_limb) {
     double *buf = dyn + W * lds_words(10);
@@ -1006,7 +1017,7 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_split4_main_fp(DevCtx 
 #pragma unroll
       for (int k = 0; k < 8; k++) pack_decode_pair<2>(raw[k], xin[k], xin[8 + k]);
     }
-    // raw half-done limbs arrive below 4.1 q (four lazy stages from a canonical value): primes of 49 / 50 bits re-centre before
+    // raw half-done limbs arrive below 4.7 q (four lazy stages from a canonical value): primes of 49 / 50 bits re-centre before
     // the remaining ten stages, smaller ones have the headroom for all fourteen (abc_ntt.hpp, FpK::red); packed ones arrive
     // centred -- wavefront-uniform branch
     if (m.bits >= 49) {
@@ -1015,6 +1026,7 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_split4_main_fp(DevCtx 
     }
     ntt_fwd_tail1024_pairs<FpTail>(buf, xin, [&](int, int i, double v) { buf[lds_pad(i)] = v; }, t, m, 4, blk, lane, ltw);
   }
+  if (LATE) load_key(2 * (int)threadIdx.x, ops, NL - LATE, NL);
   __syncthreads();
   const double *tt0 = dyn + (nl - 1) * lds_words(10), *tt1 = dyn + nl * lds_words(10);
   auto compute_pair = [&](int e, const PairOps<MODE, NL> &o, auto twin) {
@@ -1075,14 +1087,14 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_split4_main_fp(DevCtx 
 
 // over the slots of a.imap; mode 0 multiply, mode 1 key switch
 bool split4_main(abc_hip_ctx *c, int mode, const MainArgs &a) {
-  if (a.nl < 1 || a.nl > 7) return false;  // nl + 1 transform buffers of 8.5 KiB + the table: two workgroups per CU up to nl = 6, one at 7
+  if (a.nl < 1 || a.nl > 7) return false;  // nl + 1 transform buffers of 8.5 KiB + the 8 KiB table: LDS allows two workgroups per CU up to nl = 7
   if (a.ni == 0) return true;
   const dim3 grid((unsigned)(a.cc * a.ni * 16)), block(512);
   const double *keyf = key_twin_lookup(c, a.key);
   // a.part / a.tpart: raw or packed doubles here (a mixed chain's fp64 limbs: written as doubles by the integer sequence's first steps)
   dispatch_mode(mode, a.gelt, [&](auto M, auto G) {
     dispatch_nl<1, 7>(a.nl, [&](auto NL) {
-      hipLaunchKernelGGL((k_split4_main_fp<decltype(M)::value, decltype(G)::value, decltype(NL)::value>), grid, block, main_lds_bytes(a.nl),
+      hipLaunchKernelGGL((k_split4_main_fp<decltype(M)::value, decltype(G)::value, decltype(NL)::value>), grid, block, main_lds_bytes(a.nl, sizeof(double)),
                          a.st, c->dc, (const double *)a.part, (const double *)a.tpart, a.opa, a.opb, a.opa_stride, a.opb_stride, a.add_c1,
                          a.key, a.out, a.gelt, (u32)a.imap, a.ni, a.pack, keyf);
     });

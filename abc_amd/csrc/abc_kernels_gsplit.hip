@@ -34,9 +34,9 @@ __global__ __launch_bounds__(256) void k_gsplit_inv_tails(DevCtx c, const u64 *_
   const size_t N = (size_t)1 << LOGN, base = (size_t)blk << 10, PS = (size_t)c.ps, pw = (size_t)nl * N;
   const Mod m = mod_at(c, j);
   const FpTable t = fp_table(c, j);
-  f64x2 *litw = reinterpret_cast<f64x2 *>(dyn + 4 * lds_words(10));
-  f64x2 twv[4];
-  block_twiddles_fetch<10, f64x2, 4>(t.itw, LOGNB, blk, (int)threadIdx.x, 256, twv);
+  double *litw = dyn + 4 * lds_words(10);
+  double twv[4];
+  block_twiddles_fetch<10, double, 4>(t.itw, LOGNB, blk, (int)threadIdx.x, 256, twv);
   const bool live = ct < (size_t)cc;  // wavefront-uniform
   double x[16];
   if (live) {  // PassIdx<10, 8, 2>: slot 4g + k = element 4 (lane + 64 g) + k
@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void k_gsplit_inv_tails(DevCtx c, const u64 *_
           x[4 * g + k] = fp_from_u64(sp[galois_ntt_src<GAL>((u32)(base + 4 * (lane + 64 * g) + k), gelt, LOGN)]);
     }
   }
-  block_twiddles_store<10, f64x2, 4>(litw, (int)threadIdx.x, 256, twv);
+  block_twiddles_store<10, double, 4>(litw, (int)threadIdx.x, 256, twv);
   __syncthreads();
   if (live) {
     double *buf = dyn + W * lds_words(10);
@@ -122,6 +122,12 @@ struct CrossLds {
     double y[1 << RB];
 #pragma unroll
     for (int h = 0; h < (1 << RB); h++) y[h] = x[h] + add;
+    // R = 5 / 6 lazy stages from a canonical residue (|y| < 2^50) reach 5.99 / 7.62 * 2^50 for a 50-bit prime; from a sum of two
+    // residues (add != 0) they would pass 8 * 2^50, so that sum is re-centred first (workgroup-uniform branch)
+    if (kk.red && add != 0.0) {
+#pragma unroll
+      for (int h = 0; h < (1 << RB); h++) y[h] = fp_centre(y[h], kk.q, kk.qinv);
+    }
 #pragma unroll
     for (int u = 0; u < RB; u++) {
       const int hf = 1 << (RB - 1 - u);
@@ -340,7 +346,7 @@ __global__ __launch_bounds__(256, 4) void k_bsplit_special8x2(DevCtx c, const do
     const double *__restrict__ src = part + ((ct * (nl + 1) + I) * nl + J) * PS + base;
     double xin[16];
 #pragma unroll
-    for (int k = 0; k < 16; k++) xin[k] = src[(k << 6) + lane];
+    for (int k = 0; k < 16; k++) xin[k] = src[((k & 7) << 7) + ((k >> 3) << 6) + lane];  // slot g*8 + k = element k*128 + g*64 + lane (TailSched<10>, pass 0)
     if (r) __syncthreads();  // round 0's buffers have been consumed
     ntt_fwd_block_a<10, FpTail>(
         buf, [&](int s, int) { return fp_centre(xin[s], q, qinv); }, [&](int, int i, double v) { buf[lds_pad(i)] = v; }, t, m, LOGNB, blk,
@@ -487,13 +493,13 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_gsplit_main(DevCtx c, 
   const Mod m = mod_at(c, I);
   const FpTable t = fp_table(c, I);
   const double q = m.qd, qinv = m.qinv;
-  f64x2 *ltw = reinterpret_cast<f64x2 *>(dyn + (nl + 1) * lds_words(10));
+  double *ltw = dyn + (nl + 1) * lds_words(10);
   const size_t pw = (size_t)nl * N;
   const ABC_CONST_AS DevConst *cst = (const ABC_CONST_AS DevConst *)c.cst;
   const double inv = cst->inv_special_c[I], inv_q = cst->inv_special_cq[I];
 
-  f64x2 twv[PER];
-  block_twiddles_fetch<10, f64x2, PER>(t.tw, LOGNB, blk, (int)threadIdx.x, NT, twv);
+  double twv[PER];
+  block_twiddles_fetch<10, double, PER>(t.tw, LOGNB, blk, (int)threadIdx.x, NT, twv);
   const bool has_limb = W <= nl;
   const int Wc = has_limb ? W : 0;
   const double *__restrict__ src = (Wc < nl - 1) ? part + ((ct * (nl + 1) + I) * nl + (Wc < I ? Wc : Wc + 1)) * PS + base
@@ -532,7 +538,7 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_gsplit_main(DevCtx c, 
       }
     }
   }
-  block_twiddles_store<10, f64x2, PER>(ltw, (int)threadIdx.x, NT, twv);
+  block_twiddles_store<10, double, PER>(ltw, (int)threadIdx.x, NT, twv);
   __syncthreads();
   if (has_limb) {
     double *buf = dyn + W * lds_words(10);
@@ -605,12 +611,12 @@ __global__ __launch_bounds__(1024) void k_gsplit_main_deep(DevCtx c, const doubl
   const Mod m = mod_at(c, I);
   const FpTable t = fp_table(c, I);
   const double q = m.qd, qinv = m.qinv;
-  f64x2 *ltw = reinterpret_cast<f64x2 *>(dyn + (nl + 1) * lds_words(10));
+  double *ltw = dyn + (nl + 1) * lds_words(10);
   const size_t pw = (size_t)nl * N;
   const ABC_CONST_AS DevConst *cst = (const ABC_CONST_AS DevConst *)c.cst;
   const double inv = cst->inv_special_c[I], inv_q = cst->inv_special_cq[I];
-  f64x2 twv[1];
-  block_twiddles_fetch<10, f64x2, 1>(t.tw, LOGNB, blk, (int)threadIdx.x, NT, twv);
+  double twv[1];
+  block_twiddles_fetch<10, double, 1>(t.tw, LOGNB, blk, (int)threadIdx.x, NT, twv);
   const bool has_limb = W <= nl;
   const int Wc = has_limb ? W : 0;
   const double *__restrict__ src = (Wc < nl - 1) ? part + ((ct * (nl + 1) + I) * nl + (Wc < I ? Wc : Wc + 1)) * PS + base
@@ -624,7 +630,7 @@ __global__ __launch_bounds__(1024) void k_gsplit_main_deep(DevCtx c, const doubl
       xin[8 + k] = v.y;
     }
   }
-  block_twiddles_store<10, f64x2, 1>(ltw, (int)threadIdx.x, NT, twv);
+  block_twiddles_store<10, double, 1>(ltw, (int)threadIdx.x, NT, twv);
   __syncthreads();
   if (has_limb) {
     double *buf = dyn + W * lds_words(10);
@@ -704,7 +710,7 @@ static void launch_gsplit_front(hipStream_t st, abc_hip_ctx *c, size_t cc, int n
                                 size_t opa_stride, double *hinv, double *part, u32 gelt, int pack = 0) {
   constexpr int NB = 1 << (LOGN - 10);
   const dim3 g1((unsigned)(((cc + 3) / 4) * nl * NB)), g2((unsigned)(cc * nl * (LOGN > 14 ? 32 : 4)));
-  const size_t lds = (size_t)(4 * lds_words(10)) * 8 + 1024 * 16;
+  const size_t lds = (size_t)(4 * lds_words(10)) * 8 + 1024 * sizeof(double);
   dispatch_mode(mode, gelt, [&](auto M, auto G) {
     constexpr int MODE = decltype(M)::value;
     hipLaunchKernelGGL((k_gsplit_inv_tails<LOGN, MODE, decltype(G)::value>), g1, dim3(256), lds, st, c->dc, opa, MODE ? nullptr : opb,
@@ -728,11 +734,11 @@ static void launch_gsplit_main(abc_hip_ctx *c, int mode, const MainArgs &a) {
     constexpr int MODE = decltype(M)::value;
     constexpr bool GAL = decltype(G)::value;
     if (a.nl > 7)
-      hipLaunchKernelGGL((k_gsplit_main_deep<LOGN, MODE, GAL>), gmain, dim3(1024), main_lds_bytes(a.nl), a.st, c->dc, part, tpart, a.opa, a.opb,
+      hipLaunchKernelGGL((k_gsplit_main_deep<LOGN, MODE, GAL>), gmain, dim3(1024), main_lds_bytes(a.nl, sizeof(double)), a.st, c->dc, part, tpart, a.opa, a.opb,
                          a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, a.nl, a.imap, a.ni);
     else
       dispatch_nl<1, 7>(a.nl, [&](auto NL) {
-        hipLaunchKernelGGL((k_gsplit_main<LOGN, MODE, GAL, decltype(NL)::value>), gmain, dim3(512), main_lds_bytes(a.nl), a.st, c->dc, part,
+        hipLaunchKernelGGL((k_gsplit_main<LOGN, MODE, GAL, decltype(NL)::value>), gmain, dim3(512), main_lds_bytes(a.nl, sizeof(double)), a.st, c->dc, part,
                            tpart, a.opa, a.opb, a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, (u32)a.imap, a.ni);
       });
   });

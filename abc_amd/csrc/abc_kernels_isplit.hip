@@ -595,13 +595,13 @@ static void launch_isplit_tail(abc_hip_ctx *c, int mode, const MainArgs &a, u64 
       constexpr bool GAL = decltype(G)::value;
       if constexpr (LOGN == 15) {
         if (nl > 7) {
-          hipLaunchKernelGGL((k_isplit_main_deep<MODE, GAL, GUARD, LOGN>), gmain, dim3(1024), main_lds_bytes(nl), a.st, c->dc, part, tpart,
+          hipLaunchKernelGGL((k_isplit_main_deep<MODE, GAL, GUARD, LOGN>), gmain, dim3(1024), main_lds_bytes(nl, sizeof(u64x2)), a.st, c->dc, part, tpart,
                              a.opa, a.opb, a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, nl, ai.imap, ai.ni);
           return;
         }
       }
       dispatch_nl<1, 7>(nl, [&](auto NL) {
-        hipLaunchKernelGGL((k_isplit_main<MODE, GAL, decltype(NL)::value, GUARD, LOGN>), gmain, dim3(512), main_lds_bytes(nl), a.st, c->dc,
+        hipLaunchKernelGGL((k_isplit_main<MODE, GAL, decltype(NL)::value, GUARD, LOGN>), gmain, dim3(512), main_lds_bytes(nl, sizeof(u64x2)), a.st, c->dc,
                            part, tpart, a.opa, a.opb, a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, (u32)ai.imap, ai.ni);
       });
     });

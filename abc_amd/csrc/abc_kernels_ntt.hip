@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void k_ntt_inv_strided(DevCtx c, u64 *data, Li
 }
 
 // fp64 twins of the two strided passes (every prime of the launch below 2^50).  Forward: u64 in, raw doubles out
-// (R <= 4 stages from a canonical input stay below 4.1 q even for 50-bit primes).  Inverse: raw doubles in, re-centred,
+// (R <= 4 stages from a canonical input stay below 4.7 q even for 50-bit primes).  Inverse: raw doubles in, re-centred,
 // R stages, N^-1, canonical u64 out.
 template <int R>
 __global__ __launch_bounds__(256) void k_ntt_fwd_strided_fp(DevCtx c, u64 *data, const u64 *src, const u64 *src2, size_t split, LimbMap map,
@@ -173,8 +173,8 @@ __global__ __launch_bounds__(256) void k_ntt_fwd_strided_fp(DevCtx c, u64 *data,
 #pragma unroll
     for (int k = 0; k < (1 << R); k++) {
       if (k & half) continue;
-      const f64x2 tp = tw_load(t.tw + (1 << u) + (k >> (R - u)));
-      const double a = x[k], v = fp_mul_lazy(x[k | half], tp.x, tp.y, m.qd);
+      const double w = tw_load(t.tw + (1 << u) + (k >> (R - u)));
+      const double a = x[k], v = fp_mul_tw(x[k | half], w, m.qd, m.qinv);
       x[k] = a + v;
       x[k | half] = a - v;
     }
@@ -201,10 +201,10 @@ __global__ __launch_bounds__(256) void k_ntt_inv_strided_fp(DevCtx c, u64 *data,
 #pragma unroll
     for (int k = 0; k < (1 << R); k++) {
       if (k & half) continue;
-      const f64x2 tp = tw_load(t.itw + (1 << u) + (k >> (R - u)));
+      const double w = tw_load(t.itw + (1 << u) + (k >> (R - u)));
       const double a = x[k], b2 = x[k | half];
       x[k] = a + b2;  // at most 2^R * q/2 = 8 q after R = 4 stages
-      x[k | half] = fp_mul_lazy(a - b2, tp.x, tp.y, m.qd);
+      x[k | half] = fp_mul_tw(a - b2, w, m.qd, m.qinv);
     }
   }
 #pragma unroll
@@ -347,8 +347,8 @@ __global__ __launch_bounds__(256) void k_ks_expand_strided_fp(DevCtx c, const u6
 #pragma unroll
     for (int k = 0; k < (1 << R); k++) {
       if (k & half) continue;
-      const f64x2 tp = tw_load(t.tw + (1 << u) + (k >> (R - u)));
-      const double a = x[k], v = fp_mul_lazy(x[k | half], tp.x, tp.y, m.qd);
+      const double w = tw_load(t.tw + (1 << u) + (k >> (R - u)));
+      const double a = x[k], v = fp_mul_tw(x[k | half], w, m.qd, m.qinv);
       x[k] = a + v;
       x[k | half] = a - v;
     }

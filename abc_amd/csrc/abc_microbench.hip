@@ -243,17 +243,17 @@ __global__ __launch_bounds__(256) void k_mb_bfly_asm(const Mod *mods, u64 *sink,
   sink[(size_t)blockIdx.x * blockDim.x + threadIdx.x] = r;
 }
 
-// fp64 butterfly for primes below 2^50: v = y*w - rint(y*w/q)*q through two error-free FMA steps (no corrections,
+// fp64 butterfly for primes below 2^50: v = y*w - rint(fl(y*w) * (1/q))*q through two error-free FMA steps (no corrections,
 // signed lazy residues), then X = a + v, Y = a - v.  8 DP instructions.
-__global__ __launch_bounds__(256) void k_mb_bfly_fp(const Mod *mods, u64 *sink, int iters, double w, double wq) {
-  const double q = mods[1].qd;
+__global__ __launch_bounds__(256) void k_mb_bfly_fp(const Mod *mods, u64 *sink, int iters, double w) {
+  const double q = mods[1].qd, qinv = mods[1].qinv;
   double x[4], y[4];
   for (int k = 0; k < 4; k++) { x[k] = threadIdx.x + 17 * k + 1; y[k] = blockIdx.x + 31 * k + 5; }
   for (int i = 0; i < iters; i++) {
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       const double a = x[k];
-      const double v = fp_mul_lazy(y[k], w, wq, q);
+      const double v = fp_mul_tw(y[k], w, q, qinv);
       x[k] = a + v;
       y[k] = a - v;
     }
@@ -280,8 +280,7 @@ int microbench_bfly(abc_hip_ctx *c, int which, int iters, double *ms) {
       hipLaunchKernelGGL(k_mb_bfly_cpp, dim3(blocks), dim3(threads), 0, c->stream, c->d_mods, sink, iters, w, ws);
     else if (which == 2) {
       const u64 q1 = c->h_mods[1].q, w1 = q1 / 3 + 12345;
-      hipLaunchKernelGGL(k_mb_bfly_fp, dim3(blocks), dim3(threads), 0, c->stream, c->d_mods, sink, iters, (double)w1,
-                         (double)w1 / (double)q1);
+      hipLaunchKernelGGL(k_mb_bfly_fp, dim3(blocks), dim3(threads), 0, c->stream, c->d_mods, sink, iters, (double)w1);
     } else
       hipLaunchKernelGGL(k_mb_bfly_asm, dim3(blocks), dim3(threads), 0, c->stream, c->d_mods, sink, iters, w, ws);
     ABC_HIP_CHECK(hipGetLastError());
@@ -395,15 +394,15 @@ __global__ __launch_bounds__(512) void k_mb_ntt_split(DevCtx c, const u64 *src, 
   const size_t limb = (size_t)(blockIdx.x / (2 * pair_stride)) * pair_stride + (blockIdx.x % pair_stride);
   const u64 *base = src + limb * c.n;
   u64 *out = dst + limb * c.n + ((size_t)h << 13);
-  const f64x2 w0 = tw_load(t.tw + 1);
-  const double q = m.qd;
+  const double w0 = tw_load(t.tw + 1);
+  const double q = m.qd, qinv = m.qinv;
   if (h == 0)
     ntt_fwd_block_a<13, FpArith>(
-        lds, [&](int, int i) { return fp_from_u64(base[i]) + fp_mul_lazy(fp_from_u64(base[i + 8192]), w0.x, w0.y, q); },
+        lds, [&](int, int i) { return fp_from_u64(base[i]) + fp_mul_tw(fp_from_u64(base[i + 8192]), w0, q, qinv); },
         [&](int, int i, double v) { out[i] = fp_to_canon(v, m.qd, m.qinv); }, t, m, 1, 0);
   else
     ntt_fwd_block_a<13, FpArith>(
-        lds, [&](int, int i) { return fp_from_u64(base[i]) - fp_mul_lazy(fp_from_u64(base[i + 8192]), w0.x, w0.y, q); },
+        lds, [&](int, int i) { return fp_from_u64(base[i]) - fp_mul_tw(fp_from_u64(base[i + 8192]), w0, q, qinv); },
         [&](int, int i, double v) { out[i] = fp_to_canon(v, m.qd, m.qinv); }, t, m, 1, 1);
 }
 

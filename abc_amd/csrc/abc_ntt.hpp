@@ -31,10 +31,13 @@ struct NttTable {
   const u64x2 *tw;   // [N] forward twiddles {w, Shoup quotient}, bit-reversed order: tw[m+i].x = psi^bitrev(m+i)
   const u64x2 *itw;  // [N] inverse twiddles (itw[m+i].x = tw[m+i].x^-1)
 };
-// fp64 twin of the table for primes below 2^50: {w centred into (-q/2, q/2], w / q}
+// a pair of doubles moved as one 16-byte word (two adjacent coefficients, two key words)
 struct alignas(16) f64x2 {
   double x, y;
 };
+// fp64 twin of the table for primes below 2^50: ONE double per twiddle, w centred into (-q/2, q/2].  The butterfly estimates
+// its quotient from the product it has computed anyway (fp_mul_tw), so no w / q twin is kept: half the table, half the bytes
+// of every twiddle load, and an LDS table of a block's twiddles is 8 KiB.
 // The tables are read through the constant address space: they never change while a kernel runs, and saying so lets
 // the compiler keep wave-uniform twiddles on the scalar unit (s_load, lgkmcnt) even in kernels that store to HBM
 // between two transforms.  On gfx950 loads and stores share one in-order vmcnt, so a twiddle fetched with a vector
@@ -42,26 +45,25 @@ struct alignas(16) f64x2 {
 // stores of one transform are to drain under the first passes of the next.
 #define ABC_CONST_AS __attribute__((address_space(4)))
 struct FpTable {
-  const ABC_CONST_AS f64x2 *tw, *itw;
+  const ABC_CONST_AS double *tw, *itw;
 };
-__device__ __forceinline__ f64x2 tw_load(const ABC_CONST_AS f64x2 *p) {
-  f64x2 r;
-  r.x = p->x;
-  r.y = p->y;
-  return r;
-}
+__device__ __forceinline__ double tw_load(const ABC_CONST_AS double *p) { return *p; }
 __device__ __forceinline__ u64x2 tw_load(const u64x2 *p) { return *p; }
 
 // ---- fp64 residue arithmetic (primes < 2^50) ------------------------------------------------------------
 // Residues are integer-valued doubles, signed and lazily reduced.  Every operation below is exact as long as
 // the magnitudes stay below 2^53, so results are the same integers mod q that the 64-bit path produces; only the
 // quotient estimate c is approximate, which changes WHICH representative comes out, never its residue class.
-//   v = y*w - c*q,  c = rint(y * (w/q)):  h = fl(y*w), l = y*w - h (FMA, exact), d = h - c*q (FMA, exact because
+//   v = y*w - c*q,  c = rint(fl(h * qinv)):  h = fl(y*w), l = y*w - h (FMA, exact), d = h - c*q (FMA, exact because
 //   |d| < 2^53 and d is a multiple of ulp(h) or an integer), v = d + l.
-//   |c - y*w/q| <= 1/2 + |y| * |w/q| * 2^-52  and |w| <= q/2, so  |v| <= q/2 + |y| * q * 2^-53:
-//   one stage grows a bound Y on |value| to at most Y (1 + q 2^-53) + q/2.
-// Primes of 49 and 50 bits (q 2^-53 >= 1/16) are re-centred at the start of every register pass (FpK::red),
-// smaller ones need no reduction inside a forward transform (2^50 (1 + 2^-5)^14 + 7.7 q < 2^52).
+//   h, qinv = fl(1/q) and their product are each rounded once, so |c - y*w/q| <= 1/2 + 3 |y w / q| 2^-53, and |w| <= q/2:
+//   |v| <= q/2 + 1.5 |y| q 2^-53 -- one stage grows a bound Y on |value| to at most Y (1 + 1.5 q 2^-53) + q/2.
+//   (A stored w/q twin gave Y (1 + q 2^-53) + q/2 for the same six instructions; it cost a second word per twiddle.)
+// Primes of 49 and 50 bits (1.5 q 2^-53 >= 3/32) are re-centred at the start of every register pass (FpK::red): four stages
+// from a canonical value then reach 4.63 q, from 2 q (a sum of two residues) 6.61 q, of the 8 q that 2^53 allows a 50-bit
+// prime.  Smaller primes need no reduction inside a forward transform: q 2^-53 <= 2^-5, sixteen stages (N = 2^16) from a
+// canonical value stay below 14 q < 2^52, fourteen from a residue of ANOTHER prime (|y| < 2^50: a half-done decomposition
+// limb) below 1.9 * 2^50 + 11.5 q < 2^53.
 // 8 DP instructions per butterfly instead of 16 integer ones, no carry chains (no VCC hazards), measured
 // 3.2 T butterflies/s against 2.2 T/s in isolation (tools/microbench.py probes 200/202).
 struct FpK {
@@ -69,10 +71,18 @@ struct FpK {
   bool red;  // 49- and 50-bit primes
 };
 #pragma clang fp contract(off)
+// y * w for a scalar constant that carries its own w/q twin (N^-1, q_special^-1, the BEHZ constants): quotient from y * wq
 __device__ __forceinline__ double fp_mul_lazy(double y, double w, double wq, double q) {
   const double h = y * w;
   const double l = __builtin_fma(y, w, -h);
   const double c = __builtin_rint(y * wq);
+  return __builtin_fma(-c, q, h) + l;
+}
+// y * w for a twiddle, |w| <= q/2: quotient from the product itself (the arithmetic of fp_mulmod below)
+__device__ __forceinline__ double fp_mul_tw(double y, double w, double q, double qinv) {
+  const double h = y * w;
+  const double l = __builtin_fma(y, w, -h);
+  const double c = __builtin_rint(h * qinv);
   return __builtin_fma(-c, q, h) + l;
 }
 // x*y mod q for two residues |x|, |y| <= q: |result| < q  (|x y / q| 2^-52 <= 1/4, plus the rounding 1/2)
@@ -144,6 +154,18 @@ __device__ __forceinline__ void pack_decode_pair(const u64x2 &r, double &v0, dou
   v1 = __longlong_as_double((long long)b1) - kPackMagic;
 }
 
+// Pass schedules of a block transform (sum = LB, last forward pass has R = 2 so each lane ends with 32-byte contiguous runs).
+// An arithmetic policy names the schedule of its FORWARD transform (A::sched<LB>); inverse transforms all use Sched.
+template <int LB> struct Sched;
+template <> struct Sched<10> { static constexpr int R0 = 4, R1 = 4, R2 = 2, R3 = 0; };
+template <> struct Sched<11> { static constexpr int R0 = 4, R1 = 3, R2 = 2, R3 = 2; };
+template <> struct Sched<12> { static constexpr int R0 = 4, R1 = 4, R2 = 2, R3 = 2; };
+template <> struct Sched<13> { static constexpr int R0 = 4, R1 = 4, R2 = 3, R3 = 2; };
+template <> struct Sched<14> { static constexpr int R0 = 4, R1 = 4, R2 = 4, R3 = 2; };
+// 1024-point forward tails from a centred input (FpTail): seven stages before the one re-centring, three after
+template <int LB> struct TailSched;
+template <> struct TailSched<10> { static constexpr int R0 = 3, R1 = 4, R2 = 3, R3 = 0; };
+
 // ---- arithmetic policies of the register passes ---------------------------------------------------------
 // Integer (Harvey lazy) butterflies.
 // GUARD = false: no per-stage correction of X and the cheaper quotient estimate (mul_shoup_lazy4, product in
@@ -156,6 +178,7 @@ struct IntArith {
   using E = u64;
   using TW = u64x2;
   using Table = NttTable;
+  template <int LB> using sched = Sched<LB>;
   struct K {
     u64 q, two_q;
   };
@@ -184,23 +207,26 @@ struct IntArith {
 
 // fp64 butterflies.  Forward: X = a + v, Y = a - v.  Inverse: X = a + b (doubles every stage: 16x per pass, so
 // every pass after the first starts by re-centring; the first one too for 49/50-bit primes, whose (a - b) may not
-// exceed 8q), Y = (a - b) w.
+// exceed 8q), Y = (a - b) w.  With B the bound on |a|, |b|:  |Y| <= q/2 + 1.5 (2 B) q 2^-53 <= q/2 + 3 B / 8 < 2 B for every
+// B >= q/2, so the doubling of X is the bound of a stage whatever the quotient estimate: four stages from centred values
+// reach 16 (q/2 + 2) = 8 q + 32 < 2^53 for a prime q = 1 (mod 2N) below 2^50, exactly as with a stored w/q.
 struct FpArith {
   using E = double;
-  using TW = f64x2;
+  using TW = double;
   using Table = FpTable;
   using K = FpK;
+  template <int LB> using sched = Sched<LB>;
   __device__ __forceinline__ static K consts(const Mod &m) { return K{m.qd, m.qinv, m.bits >= 49}; }
-  __device__ __forceinline__ static void fwd(E &X, E &Y, const TW tp, const K &k) {
+  __device__ __forceinline__ static void fwd(E &X, E &Y, const TW w, const K &k) {
     const double a = X;
-    const double v = fp_mul_lazy(Y, tp.x, tp.y, k.q);
+    const double v = fp_mul_tw(Y, w, k.q, k.qinv);
     X = a + v;
     Y = a - v;
   }
-  __device__ __forceinline__ static void inv(E &X, E &Y, const TW tp, const K &k) {
+  __device__ __forceinline__ static void inv(E &X, E &Y, const TW w, const K &k) {
     const double a = X, c = Y;
     X = a + c;
-    Y = fp_mul_lazy(a - c, tp.x, tp.y, k.q);
+    Y = fp_mul_tw(a - c, w, k.q, k.qinv);
   }
   __device__ __forceinline__ static void centre16(E (&x)[16], const K &k) {
 #pragma unroll
@@ -214,13 +240,17 @@ struct FpArith {
   }
 };
 
-// Forward BLOCK TAILS (at most 12 stages) that start from a CENTRED input, |x| <= q/2: the per-stage bound Y -> Y (1 + q 2^-53) + q/2
-// gives, from 0.5 q,  1.06, 1.70, 2.41, 3.21, 4.11, 5.12, 6.26, 7.55 q after eight stages of a 50-bit prime (2^53 = 8 q * 2^50 / q:
-// the ninth would pass it) and 7.6 q after ten, 9.6 q after twelve stages of a 49-bit one (limit 16 q).  So a tail needs ONE
-// re-centring for 50-bit primes -- before pass 2, which every schedule reaches after at most eight stages (4+4, 3+4) -- and none for
-// 49-bit ones, where FpArith re-centres before every pass (it serves whole 14-stage transforms from canonical inputs too).
-// tests/test_fp64_exactness.py replays both schedules with Python integers.
+// Forward 1024-point BLOCK TAILS that start from a CENTRED input, |x| <= q/2: the per-stage bound Y -> Y (1 + 1.5 q 2^-53) + q/2
+// gives, from 0.5 q,  1.09, 1.80, 2.64, 3.63, 4.81, 6.21, 7.88 q after SEVEN stages of a 50-bit prime and 9.86 q after eight
+// (2^53 = 8 q * 2^50 / q), and 8.96 q after ten stages of a 49-bit one (limit 16 q).  So a tail needs ONE re-centring for 50-bit
+// primes -- before pass 2, which must come after at most seven stages: the schedule is 3 + 4 + 3 (TailSched, and
+// ntt_fwd_tail1024_pairs below), not the 4 + 4 + 2 of a whole transform, which the bound allowed while the quotient came from a
+// stored w/q (7.55 q after eight stages).  3 + 4 + 3 costs the same eighty butterflies per lane and two more per-lane twiddle
+// loads in the last pass; a second re-centring in 4 + 4 + 2 would have cost 48 DP instructions per lane.  The output of a tail
+// is below 2.64 q.  No re-centring for 49-bit primes, where FpArith re-centres before every pass (it serves whole 14-stage
+// transforms from canonical inputs too).  tests/test_fp64_exactness_single_twiddle.py replays every schedule with Python integers.
 struct FpTail : FpArith {
+  template <int LB> using sched = TailSched<LB>;
   template <int PASS> __device__ __forceinline__ static void fwd_begin(E (&x)[16], const K &k) {
     if (PASS == 2 && k.red && k.q >= 562949953421312.0) centre16(x, k);  // q >= 2^49: a 50-bit prime (workgroup-uniform)
   }
@@ -444,14 +474,6 @@ __device__ __forceinline__ void block_sync_lds() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
-// Pass schedules (sum = LB, last forward pass has R = 2 so each lane ends with 32-byte contiguous runs).
-template <int LB> struct Sched;
-template <> struct Sched<10> { static constexpr int R0 = 4, R1 = 4, R2 = 2, R3 = 0; };
-template <> struct Sched<11> { static constexpr int R0 = 4, R1 = 3, R2 = 2, R3 = 2; };
-template <> struct Sched<12> { static constexpr int R0 = 4, R1 = 4, R2 = 2, R3 = 2; };
-template <> struct Sched<13> { static constexpr int R0 = 4, R1 = 4, R2 = 3, R3 = 2; };
-template <> struct Sched<14> { static constexpr int R0 = 4, R1 = 4, R2 = 4, R3 = 2; };
-
 // ---- forward block transform -----------------------------------------------------------------------
 // load(r, i)  -> u64 in [0,4q)  coefficient i (block-local natural index) for register slot r
 // store(r, i, v)               v in [0,4q) lazily reduced value of output slot i (block-local,
@@ -462,7 +484,7 @@ template <int LB, class A, class Load, class Store, bool LTW = false>
 __device__ __forceinline__ void ntt_fwd_block_a(typename A::E *lds, Load load, Store store, const typename A::Table &t,
                                                 const Mod &m, int S0, int b, int tid_in = -1,
                                                 const typename A::TW *ltw = nullptr /* LTW: block twiddle table in LDS */) {
-  using SC = Sched<LB>;
+  using SC = typename A::template sched<LB>;
   // a 1024-point block is one wavefront: callers may run several of them side by side in one workgroup (tid_in =
   // the lane id), so nothing in it may be a workgroup barrier
   const int tid = tid_in < 0 ? (int)threadIdx.x : tid_in;
