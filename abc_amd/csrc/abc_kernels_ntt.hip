@@ -78,7 +78,8 @@ __global__ __launch_bounds__((1 << LB) / 16) void k_ntt_inv_fp(DevCtx c, u64 *da
     ntt_inv_block_a<LB, FpArith>(
         lds, ld, [&](int, int i, double v) { base[i] = fp_to_canon(fp_mul_lazy(v, m.inv_n_c, m.inv_n_cq, m.qd), m.qd, m.qinv); }, t, m,
         0, 0);
-  else  // the strided pass finishes the transform: hand over raw doubles (|x| <= 16 q after the last block pass)
+  else  // the strided pass finishes the transform: hand over raw doubles (|x| <= 8 q + 32 after the last block pass: four
+        // stages from re-centred values, inv_begin; the strided pass re-centres them on the way in)
     ntt_inv_block_a<LB, FpArith>(lds, ld, [&](int, int i, double v) { reinterpret_cast<double *>(base)[i] = v; }, t, m, S0, b);
 }
 

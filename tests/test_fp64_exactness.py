@@ -1,15 +1,20 @@
-"""CPU model of the fp64 residue arithmetic of abc_amd/csrc/abc_ntt.hpp ("fp64 residue arithmetic", FpArith).
+"""CPU model of fp_mul_lazy (abc_amd/csrc/abc_ntt.hpp): the fp64 product y * w whose quotient comes from a STORED twin fl(w / q).
 
-The HIP path claims: every step of the fp64 butterfly is EXACT as long as magnitudes stay below 2^53, so the
-transform returns the same residues as the integer algorithm; 49/50-bit primes must re-centre at every register pass,
-smaller primes never inside a forward transform.  This test replays the device algorithm with Python integers for the
-exact parts and IEEE doubles for the two inexact ones (the stored w/q and the quotient estimate), on adversarial inputs
-(all q-1, alternating 0 / q-1, (q +- 1)/2), and checks
+Twiddles no longer carry that twin (fp_mul_tw estimates the quotient from the product itself; its schedules and bounds are
+replayed in tests/test_fp64_exactness_single_twiddle.py).  The pair arithmetic lives on in fp_mul_lazy, for the scalar constants
+that keep a w / q next to them: N^-1 at the end of every inverse transform, the inverse of the special prime in the key switch,
+the BEHZ base-conversion constants.  Its claim is the same as before: every step is EXACT as long as magnitudes stay below 2^53;
+only the quotient estimate c = rint(fl(y * fl(w/q))) is approximate, which changes which representative comes out, never its
+residue class, and one product grows a bound Y on |y| to at most Y (1 + q 2^-53) + q/2.
+
+This file stresses that arithmetic far beyond its call sites (one product of a value of at most 8 q + 32): whole transforms are
+chained out of it, with Python integers for the exact parts and IEEE doubles for the two inexact ones (the stored w/q and the
+quotient estimate), on adversarial inputs (all q-1, alternating 0 / q-1, (q +- 1)/2), and checks
   * the FMA steps really are exact (h - c q and the low product part fit a double without rounding),
-  * no magnitude reaches 2^53 under the pass schedule the kernels use (4,4,4,2 at N = 2^14),
+  * no magnitude reaches 2^53 when the chain is re-centred as the growth above demands (every four products for 49/50-bit primes),
   * the canonicalised output equals the oracle's NTT (tests/test_oracle_golden.py pins the oracle),
-  * and that the re-centring the schedule prescribes is NECESSARY: without it a 50-bit prime does leave the exact range.
-No GPU, no HIP library: this is the host-side proof obligation of the device code.
+  * and that this re-centring is NECESSARY: without it a 50-bit prime does leave the exact range;
+plus the encoding of packed half-done limbs.  No GPU, no HIP library: this is the host-side proof obligation of the device code.
 """
 import numpy as np
 import pytest
@@ -90,9 +95,8 @@ class Model:
 
 
 def _fp_forward(x, q, tables, schedule, recentre):
-    """Cooley-Tukey, natural in -> bit-reversed out, stages grouped into register passes like ntt_fwd_block_a.
-    recentre: True (before every pass but the first: FpArith for 49/50-bit primes), False, or the set of passes that start with
-    a re-centring (FpTail: {2} for 50-bit primes, nothing for smaller ones)"""
+    """Cooley-Tukey, natural in -> bit-reversed out, every product an fp_mul_lazy with the twiddle's stored fl(w/q); stages grouped
+    into passes.  recentre: True (before every pass but the first), False, or the set of passes that start with a re-centring"""
     n = len(x)
     m = Model(q)
     x = list(x)
@@ -120,7 +124,9 @@ CASES = [(50, True), (40, False)]
 
 
 @pytest.mark.parametrize("bits,red", CASES)
-def test_fp64_forward_transform_is_exact_and_matches_oracle(bits, red):
+def test_fp_mul_lazy_chained_as_a_whole_transform_is_exact_and_matches_oracle(bits, red):
+    """a 12-stage forward transform built from fp_mul_lazy products, each twiddle with its stored fl(w/q), in passes of 4 + 4 + 2 + 2
+    products with a re-centring between passes for the 50-bit prime"""
     from oracle import oracle_py as om
     n, logn = 4096, 12  # the per-stage growth argument does not depend on N; 2^12 keeps pure Python in seconds
     primes = om.create_primes(n, [bits, 40 if bits == 50 else 41])
@@ -147,9 +153,10 @@ def test_fp64_forward_transform_is_exact_and_matches_oracle(bits, red):
     (50, (4, 4, 2, 2), {2}), (49, (4, 4, 2, 2), set()),
 ])
 def test_fp64_block_tail_policy_from_centred_inputs(bits, schedule, recentre):
-    """FpTail (abc_ntt.hpp): a forward block tail of ten (1024 points) or twelve (4096 points) stages that starts from CENTRED
-    values re-centres once for a 50-bit prime (before pass 2) and never for a 49-bit one -- every step exact, every magnitude
-    below 2^53, residues equal to the oracle's transform."""
+    """Chains of ten or twelve fp_mul_lazy products per value that start from CENTRED values: under the growth of a stored w/q,
+    Y (1 + q 2^-53) + q/2, one re-centring (before the third group of products) is enough for a 50-bit prime and none is needed for
+    a 49-bit one -- every step exact, every magnitude below 2^53, residues equal to the oracle's transform.  (The twiddle
+    butterflies themselves grow faster now, fp_mul_tw: FpTail's 3 + 4 + 3 is proved in test_fp64_exactness_single_twiddle.py.)"""
     from oracle import oracle_py as om
     n = 1 << sum(schedule)
     primes = om.create_primes(n, [bits, 40])

@@ -6,7 +6,12 @@ Y (1 + q 2^-53) + q/2 with a stored w/q).  The estimate only chooses WHICH repre
 as long as magnitudes stay below 2^53.  This file replays, with Python integers for the exact parts and IEEE doubles for the
 estimate, every stage schedule the kernels are compiled with:
 
-  * whole 14-stage forward and inverse transforms (ntt_fwd_block_a<14> / ntt_inv_block_a<14>, FpArith);
+  * whole forward and inverse block transforms of 10 .. 14 stages (ntt_fwd_block_a<LB> / ntt_inv_block_a<LB>, FpArith, Sched<LB>);
+  * the stand-alone launches of abc_kernels_ntt.hip that are not one block: the few-limb N = 2^14 form (k_ntt_fwd_strided_fp<4>: four
+    raw stages from a canonical input, then k_ntt_fwd_fp<10> with a re-centred load; inverse k_ntt_inv_fp<10>, then
+    k_ntt_inv_strided_fp<4> with a re-centred load) and the N = 2^15 / 2^16 forms (three / four strided stages around 4096-point
+    blocks), each to its very end: fp_to_canon in the forward store; fp_mul_lazy by N^-1 with its stored fl(w/q), then fp_to_canon,
+    in the inverse one;
   * the N = 2^14 split forms: a radix-16 register pass from a canonical residue, from a residue of ANOTHER (50-bit) prime or
     from a sum of two residues (k_split3_pass_fp: t + fix), then the ten-stage tail from re-centred values -- FpTail's 3 + 4 + 3
     (k_split4_main_fp through ntt_fwd_tail1024_pairs; k_split_special_fp, k_bmul_mid, k_gsplit_special through TailSched<10>),
@@ -21,10 +26,19 @@ bits, and asserts for each: both FMA steps are exact, every intermediate stays b
 transform.  Concrete inputs do not reach the worst case of every rounding at once, so the proof obligation itself -- the bound
 recurrence over each schedule -- is asserted next to the replay, and as a check on that bookkeeping the schedule FpTail had
 before (4 + 4 stages before its one re-centring) is shown to pass 2^53 for a 50-bit prime under the new growth while it did
-not under the old one.  No GPU, no HIP library.
+not under the old one.  The plans are written from the tables SCHED / TAIL_SCHED below, and test_plans_follow_the_header parses
+the Sched<> / TailSched<> specialisations out of abc_ntt.hpp and compares: a header edit without a model edit fails there, so the
+proof stays about the schedule that is compiled.  No GPU, no HIP library.
 """
+import os
+import re
+
 import numpy as np
 import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "abc_amd", "csrc", "abc_ntt.hpp")
+NTT_KERNELS = os.path.join(ROOT, "abc_amd", "csrc", "abc_kernels_ntt.hip")
 
 LIMIT = 1 << 53
 BITS = [40, 48, 49, 50]
@@ -86,6 +100,21 @@ class Model:
         assert abs(v) < LIMIT
         return v
 
+    def mul_lazy(self, y, w, wq):
+        """fp_mul_lazy: y * w for a constant that carries wq = fl(w / q); the quotient comes from fl(y * wq)"""
+        q = self.q
+        prod = y * w
+        h = float(prod)
+        hi = int(h)
+        l = prod - hi
+        assert float(l) == l, "low product part is not a double"
+        c = round(float(y) * wq)        # |y| < 2^53 is an integer-valued double already
+        d = hi - c * q
+        assert abs(d) < LIMIT, "h - c q left the exact range"
+        v = d + l
+        assert abs(v) < LIMIT
+        return v
+
     def centre(self, x):
         r = x - round(float(x) * self.qinv) * self.q
         assert abs(r) <= self.q // 2 + 1
@@ -98,7 +127,32 @@ class Model:
         assert p < LIMIT, "a value left the exact range"
 
 
-def _run_forward(x, q, tw, plan):
+def _to_canon(x, q):
+    """fp_to_canon on integer-valued doubles, its bit manipulation replayed with numpy: centre, add q where the sign bit of the high
+    dword is set (a mask, no comparison), add 2^52 and strip the exponent.  fma(-c, q, x) is exact whenever its result fits 53 bits
+    (asserted), so integers give it; a result that cancels to zero is +0 in round-to-nearest (c and x are never both -0: -0 in gives
+    c = -0, so the product -c q is +0), which is what the array built from integers holds."""
+    x = np.asarray(x, dtype=np.float64)
+    qd = np.float64(q)
+    qinv = np.float64(1.0) / qd
+    c = np.rint(x * qinv)
+    r_int = [int(a) - int(b) * q for a, b in zip(x, c)]
+    assert all(abs(v) < LIMIT for v in r_int)
+    r = np.array(r_int, dtype=np.float64)
+    neg = ((r.view(np.uint64) >> np.uint64(32)).astype(np.uint32).view(np.int32) >> 31).view(np.uint32).astype(np.uint64)
+    qb = np.array([qd]).view(np.uint64)[0]
+    add = (((qb >> np.uint64(32)) & neg) << np.uint64(32)) | ((qb & np.uint64(0xffffffff)) & neg)
+    r = r + add.view(np.float64)
+    return (r + np.float64(4503599627370496.0)).view(np.uint64) & np.uint64(0x000fffffffffffff)
+
+
+def _from_u64(v):
+    """fp_from_u64: the word below 2^52 dropped into the mantissa of 2^52, minus 2^52"""
+    v = np.asarray(v, dtype=np.uint64)
+    return (v | np.uint64(0x4330000000000000)).view(np.float64) - np.float64(4503599627370496.0)
+
+
+def _run_forward(x, q, tw, plan, canon=False):
     """Cooley-Tukey, natural in -> bit-reversed out; plan = stage counts and re-centrings in the order the kernels apply them"""
     n = len(x)
     m = Model(q)
@@ -121,10 +175,12 @@ def _run_forward(x, q, tw, plan):
             m.see(x)
             stage += 1
     assert 1 << stage == n
+    if canon:  # the stand-alone kernels' store functor
+        return [int(v) for v in _to_canon([float(v) for v in x], q)], m.peak
     return [v % q for v in x], m.peak
 
 
-def _run_inverse(x, q, itw, plan):
+def _run_inverse(x, q, itw, plan, finish=False):
     """Gentleman-Sande, bit-reversed in -> natural out (before N^-1): X = a + b, Y = (a - b) w"""
     n = len(x)
     m = Model(q)
@@ -149,6 +205,12 @@ def _run_inverse(x, q, itw, plan):
             m.see(x)
     assert stage == 0
     inv_n = _pow(n, q - 2, q)
+    if finish:  # the stand-alone kernels' end: fp_mul_lazy by the centred N^-1 and its fl(w / q) (make_mod), then fp_to_canon
+        w = inv_n - q if inv_n > q // 2 else inv_n
+        wq = float(w) / float(q)
+        x = [m.mul_lazy(v, w, wq) for v in x]
+        m.see(x)
+        return [int(v) for v in _to_canon([float(v) for v in x], q)], m.peak
     return [v * inv_n % q for v in x], m.peak
 
 
@@ -194,14 +256,38 @@ def _c50(bits):
     return [C] if bits == 50 else []   # FpTail: one re-centring, 50-bit primes only
 
 
-def _tail(bits):                       # FpTail, 3 + 4 + 3 from centred values
-    return [3, 4] + _c50(bits) + [3]
+# The pass schedules the plans are written from: Sched<LB> / TailSched<LB> of abc_ntt.hpp (test_plans_follow_the_header compares)
+SCHED = {10: (4, 4, 2, 0), 11: (4, 3, 2, 2), 12: (4, 4, 2, 2), 13: (4, 4, 3, 2), 14: (4, 4, 4, 2)}
+TAIL_SCHED = {10: (3, 4, 3, 0)}
+BIG_BLOCK_LB = 12                      # kBigBlockLB of abc_kernels_ntt.hip: the block under the strided pass for N > 2^14
+
+
+def _tail(bits):                       # FpTail, 3 + 4 + 3 from centred values: its one re-centring comes before pass 2
+    r0, r1, r2, _ = TAIL_SCHED[10]
+    return [r0, r1] + _c50(bits) + [r2]
+
+
+def _fwd_block(lb, bits):
+    """ntt_fwd_block_a<LB, FpArith>: FpArith::fwd_begin<PASS> re-centres before every pass but the first, 49/50-bit primes only"""
+    plan = []
+    for i, r in enumerate(r for r in SCHED[lb] if r):
+        plan += (_red(bits) if i else []) + [r]
+    return plan
+
+
+def _inv_block(lb, bits):
+    """ntt_inv_block_a<LB, FpArith>: the passes of Sched<LB> backwards; FpArith::inv_begin<PASS> re-centres before every pass but the
+    first, and before that one too for 49/50-bit primes"""
+    plan = []
+    for i, r in enumerate(r for r in reversed(SCHED[lb]) if r):
+        plan += ([C] if i else _red(bits)) + [r]
+    return plan
 
 
 # forward plans: name -> (logn, plan(bits), kind of input, applicable(bits))
 FORWARD = {
     # ntt_fwd_block_a<14, FpArith>: 4 + 4 + 4 + 2 from a canonical input
-    "whole14": (14, lambda b: [4] + _red(b) + [4] + _red(b) + [4] + _red(b) + [2], "canonical", lambda b: True),
+    "whole14": (14, lambda b: _fwd_block(14, b), "canonical", lambda b: True),
     # register pass (k_split2_tensor_pass0_fp: residue of another prime; k_split3_pass_fp: t + fix), re-centred load
     # (packed limbs, 49/50-bit primes, the special prime), FpTail
     "split14_tail": (14, lambda b: [4, C] + _tail(b), "foreign", lambda b: True),
@@ -209,23 +295,46 @@ FORWARD = {
     # the same without any re-centring: raw half-done limbs of primes of at most 48 bits
     "split14_raw": (14, lambda b: [4, 3, 4, 3], "foreign", lambda b: b <= 48),
     # k_split3_main_fp: ntt_fwd_block_a<10, FpArith>, 4 + 4 + 2 behind the register pass
-    "split14_fparith": (14, lambda b: [4, C, 4] + _red(b) + [4] + _red(b) + [2], "sum", lambda b: True),
+    "split14_fparith": (14, lambda b: [4, C] + _fwd_block(10, b), "sum", lambda b: True),
     # N = 2^15: CrossLds::forward (2 + 3 stages; a sum is re-centred first for 49/50-bit primes), then k_gsplit_main's FpTail
     "cross15_tail": (15, lambda b: [5, C] + _tail(b), "foreign", lambda b: True),
     "cross15_tail_sum": (15, lambda b: _red(b) + [5, C] + _tail(b), "sum", lambda b: True),
     # k_gsplit_main_deep: FpArith through ntt_fwd_tail1024_pairs, the load re-centred for 49/50-bit primes only
     "cross15_deep": (15, lambda b: _red(b) + [5] + _red(b) + [3] + _red(b) + [4] + _red(b) + [3], "sum", lambda b: True),
 }
+# k_ntt_fwd_fp<LB>, S0 = 0 (launch_ntt, N = 2^10 .. 2^13): one whole block from a canonical input (fp_from_u64)
+for _lb in (10, 11, 12, 13):
+    FORWARD["whole%d" % _lb] = (_lb, lambda b, lb=_lb: _fwd_block(lb, b), "canonical", lambda b: True)
+# launch_ntt, N = 2^14 with few limbs in flight: k_ntt_fwd_strided_fp<4> (four stages, nothing re-centred, raw doubles out), then
+# k_ntt_fwd_fp<10> with S0 = 4: the load re-centres (fp_centre, every width), then Sched<10> under FpArith
+FORWARD["few14"] = (14, lambda b: [4, C] + _fwd_block(10, b), "canonical", lambda b: True)
+# N = 2^15 / 2^16: k_ntt_fwd_strided_fp<logN - 12>, then k_ntt_fwd_fp<12> with S0 = logN - 12 in the same way
+for _logn in (15, 16):
+    FORWARD["big%d" % _logn] = (_logn, lambda b, s0=_logn - BIG_BLOCK_LB: [s0, C] + _fwd_block(BIG_BLOCK_LB, b), "canonical",
+                                lambda b: True)
+# the plans of the stand-alone kernels (abc_kernels_ntt.hip) are replayed to their last instruction: the forward store is
+# fp_to_canon, the inverse one fp_mul_lazy by N^-1, then fp_to_canon
+STANDALONE = {"whole10", "whole11", "whole12", "whole13", "whole14", "few14", "big15", "big16"}
+FULL_INPUTS = {"whole10", "whole11", "whole12", "whole13", "whole14", "few14"}  # the others: the "few" set (pure Python at N >= 2^15)
 # what a plan may start from (the bound) -- "foreign": a canonical residue of another prime, |y| < 2^50 whatever q
 START = {"canonical": lambda bits: _qmax(bits), "sum": lambda bits: 2.0 * _qmax(bits), "foreign": lambda bits: 2.0 ** 50}
 
 # inverse plans: ntt_inv_block_a re-centres before every pass but the first, and before that one too for 49/50-bit primes
 INVERSE = {
     # ntt_inv_block_a<14>: 2 + 4 + 4 + 4; also k_split_special_fp's block tail (2 + 4 + 4) followed by k_split3_pass_fp (centre16 + 4)
-    "whole14": (14, lambda b: _red(b) + [2, C, 4, C, 4, C, 4]),
+    "whole14": (14, lambda b: _inv_block(14, b)),
     # N = 2^15: block tails 2 + 4 + 4, then CrossLds::inverse (re-centred load, 3 stages, re-centring, 2 stages)
     "tails15_cross": (15, lambda b: _red(b) + [2, C, 4, C, 4, C, 3, C, 2]),
 }
+# k_ntt_inv_fp<LB>, S0 = 0: one whole block
+for _lb in (10, 11, 12, 13):
+    INVERSE["whole%d" % _lb] = (_lb, lambda b, lb=_lb: _inv_block(lb, b))
+# few limbs at N = 2^14: k_ntt_inv_fp<10> with S0 = 4 hands raw doubles (at most 8 q + 32: four stages from re-centred values) to
+# k_ntt_inv_strided_fp<4>, whose load re-centres whatever the width
+INVERSE["few14"] = (14, lambda b: _inv_block(10, b) + [C, 4])
+# N = 2^15 / 2^16: k_ntt_inv_fp<12>, then k_ntt_inv_strided_fp<3> / <4>
+for _logn in (15, 16):
+    INVERSE["big%d" % _logn] = (_logn, lambda b, s0=_logn - BIG_BLOCK_LB: _inv_block(BIG_BLOCK_LB, b) + [C, s0])
 
 
 def _inputs(n, q, kind, rng, few):
@@ -260,8 +369,8 @@ def test_forward_schedules_are_exact_and_match_the_oracle(name, bits):
     q, o = _prime(n, bits)
     tw, _ = _tables(n, q)
     rng = np.random.default_rng(11)
-    for label, x in _inputs(n, q, kind, rng, few=(name != "whole14")).items():
-        got, peak = _run_forward(x, q, tw, plan)
+    for label, x in _inputs(n, q, kind, rng, few=(name not in FULL_INPUTS)).items():
+        got, peak = _run_forward(x, q, tw, plan, canon=(name in STANDALONE))
         want = o.ntt(0, np.array([v % q for v in x], dtype=np.uint64))
         assert got == [int(v) for v in want], (name, bits, label)
         assert peak < LIMIT, (name, bits, label, peak / q)
@@ -273,19 +382,98 @@ def test_inverse_schedules_are_exact_and_match_the_oracle(name, bits):
     logn, plan_of = INVERSE[name]
     plan, n = plan_of(bits), 1 << logn
     # inputs: canonical residues, or products of two of them (fp_mulmod: |x| < q)
-    assert _inverse_bound(plan, _qmax(bits), bits) < 2.0 ** 53, (name, bits)
+    bound = _inverse_bound(plan, _qmax(bits), bits)
+    assert bound < 2.0 ** 53, (name, bits)
+    if name in STANDALONE:
+        # what fp_mul_lazy is handed is at most 8 q + 32 (four stages from re-centred values), behind a strided pass as behind a block;
+        # its quotient c = rint(fl(y fl(w/q))) is off by at most 1/2 + |y w / q| 2^-52, so |y w - c q| <= q/2 + |y| q 2^-53 <= 1.5 q + 4,
+        # and h - c q, which differs from that by the low product part (at most half an ulp of |y w| < 2^102), is exact
+        qm = _qmax(bits)
+        assert bound <= 8.0 * qm + 32.0
+        assert qm / 2 + bound * qm * 2.0 ** -53 + 2.0 ** 49 < 2.0 ** 53
     q, o = _prime(n, bits)
     _, itw = _tables(n, q)
     rng = np.random.default_rng(13)
-    for label, x in _inputs(n, q, "canonical", rng, few=(name != "whole14")).items():
-        got, peak = _run_inverse(x, q, itw, plan)
+    finish = name in STANDALONE
+    for label, x in _inputs(n, q, "canonical", rng, few=(name not in FULL_INPUTS)).items():
+        got, peak = _run_inverse(x, q, itw, plan, finish)
         want = o.intt(0, np.array(x, dtype=np.uint64))
         assert got == [int(v) for v in want], (name, bits, label)
         assert peak < LIMIT, (name, bits, label, peak / q)
     # signed inputs too: what fp_mulmod hands the inverse transform of a product, |x| < q
     x = [int(v) - (q - 1) for v in rng.integers(0, 2 * q - 1, size=n, dtype=np.uint64)]
-    got, _ = _run_inverse(x, q, itw, plan)
+    got, _ = _run_inverse(x, q, itw, plan, finish)
     assert got == [int(v) for v in o.intt(0, np.array([v % q for v in x], dtype=np.uint64))], (name, bits, "signed")
+
+
+@pytest.mark.parametrize("bits", BITS)
+def test_conversions_at_the_ends_of_the_range(bits):
+    """fp_to_canon (the store of every stand-alone transform) on 0, -0, +-1, +-(q-1)/2, +-(q+1)/2, +-q, +-8 q, 8 q + 32 and random
+    lazy values up to the 8 q + 32 an inverse pass may leave; fp_from_u64 (their load) on 0, q - 1 and the largest words"""
+    from oracle import oracle_py as om
+    rng = np.random.default_rng(bits)
+    for n in (1024, 65536):
+        q = om.create_primes(n, [bits, 40 if bits != 40 else 41])[0]
+        edge = [0, 1, -1, (q - 1) // 2, -((q - 1) // 2), (q + 1) // 2, -((q + 1) // 2), q - 1, 1 - q, q, -q, q + 1, -q - 1,
+                8 * q, -8 * q, 8 * q + 32, -8 * q - 32]
+        assert 8 * q + 32 < LIMIT  # q = 1 (mod 2N) keeps even a 50-bit prime far enough below 2^50
+        vals = edge + [int(v) - (8 * q + 32) for v in rng.integers(0, 16 * q + 65, size=20000, dtype=np.uint64)]
+        x = np.array([float(v) for v in vals] + [-0.0], dtype=np.float64)
+        want = [v % q for v in vals] + [0]
+        assert [int(v) for v in _to_canon(x, q)] == want, (bits, n)
+        words = [0, 1, q - 1, (1 << 50) - 1, (1 << 52) - 1] + [int(v) for v in rng.integers(0, 1 << 52, size=1000, dtype=np.uint64)]
+        back = _from_u64(words)
+        assert [int(v) for v in back] == words and all(float(w) == b for w, b in zip(words, back)), (bits, n)
+
+
+def _header_schedules(header=HEADER, kernels=NTT_KERNELS):
+    """the Sched<LB> / TailSched<LB> specialisations of abc_ntt.hpp and kBigBlockLB of abc_kernels_ntt.hip, as compiled"""
+    pat = re.compile(r"template\s*<>\s*struct\s+(Sched|TailSched)\s*<\s*(\d+)\s*>\s*\{\s*static\s+constexpr\s+int\s+"
+                     r"R0\s*=\s*(\d+)\s*,\s*R1\s*=\s*(\d+)\s*,\s*R2\s*=\s*(\d+)\s*,\s*R3\s*=\s*(\d+)\s*;\s*\}\s*;")
+    found = {"Sched": {}, "TailSched": {}}
+    with open(header) as f:
+        text = f.read()
+    for kind, lb, r0, r1, r2, r3 in pat.findall(text):
+        assert int(lb) not in found[kind], "two specialisations of %s<%s>" % (kind, lb)
+        found[kind][int(lb)] = (int(r0), int(r1), int(r2), int(r3))
+    # every specialisation must have been understood: count the declarations independently of the pattern above
+    assert len(re.findall(r"struct\s+Sched\s*<\s*\d+\s*>", text)) == len(found["Sched"])
+    assert len(re.findall(r"struct\s+TailSched\s*<\s*\d+\s*>", text)) == len(found["TailSched"])
+    with open(kernels) as f:
+        big = re.findall(r"constexpr\s+int\s+kBigBlockLB\s*=\s*(\d+)\s*;", f.read())
+    assert len(big) == 1
+    return found, int(big[0])
+
+
+def _stages(plan):
+    return [s for s in plan if s != C]
+
+
+def _check_plans_against(found, big):
+    assert found["Sched"] == SCHED, "abc_ntt.hpp's Sched<> changed: the plans of this file describe another schedule"
+    assert found["TailSched"] == TAIL_SCHED, "abc_ntt.hpp's TailSched<> changed: the plans of this file describe another schedule"
+    assert big == BIG_BLOCK_LB
+    for bits in BITS:
+        for lb, sc in found["Sched"].items():
+            assert sum(sc) == lb
+            passes = [r for r in sc if r]
+            assert _stages(FORWARD["whole%d" % lb][1](bits)) == passes
+            assert _stages(INVERSE["whole%d" % lb][1](bits)) == passes[::-1]
+        s10, sbig = [r for r in found["Sched"][10] if r], [r for r in found["Sched"][big] if r]
+        t10 = [r for r in found["TailSched"][10] if r]
+        assert _stages(FORWARD["few14"][1](bits)) == [4] + s10 and _stages(INVERSE["few14"][1](bits)) == s10[::-1] + [4]
+        assert _stages(FORWARD["split14_fparith"][1](bits)) == [4] + s10
+        for logn in (15, 16):
+            assert _stages(FORWARD["big%d" % logn][1](bits)) == [logn - big] + sbig
+            assert _stages(INVERSE["big%d" % logn][1](bits)) == sbig[::-1] + [logn - big]
+        assert _stages(FORWARD["split14_tail"][1](bits)) == [4] + t10 and _stages(FORWARD["cross15_tail"][1](bits)) == [5] + t10
+        # FpTail's one re-centring sits before its pass 2 (fwd_begin<2>), 50-bit primes only
+        assert _tail(bits) == t10[:2] + ([C] if bits == 50 else []) + t10[2:]
+
+
+def test_plans_follow_the_header():
+    """the stage counts of the plans above are the constants the kernels are compiled with"""
+    _check_plans_against(*_header_schedules())
 
 
 def test_four_plus_four_tail_breaks_the_bound_for_50_bit_primes():

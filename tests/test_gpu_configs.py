@@ -23,6 +23,20 @@ def _eq(name, got, want):
         raise AssertionError("%s: %d/%d words differ, first at %s" % (name, len(bad), got.size, tuple(bad[0])))
 
 
+def _extreme_ct(primes, nl, n, rng):
+    """a 2-component 'ciphertext' with residues from {0, 1, (q-1)/2, (q+1)/2, q-2, q-1} and random values, and a long run of q-1
+    (as tests/test_gpu_paths.py builds them)"""
+    ct = np.empty((2, nl, n), dtype=np.uint64)
+    for j in range(nl):
+        q = primes[j]
+        pool = np.array([0, 1, (q - 1) // 2, (q + 1) // 2, q - 2, q - 1], dtype=np.uint64)
+        pick = rng.integers(0, 8, size=(2, n))
+        rnd = rng.integers(0, q, size=(2, n), dtype=np.uint64)
+        ct[:, j, :] = np.where(pick < 6, pool[np.minimum(pick, 5)], rnd)
+    ct[0, :, : n // 4] = np.array(primes[:nl], dtype=np.uint64)[:, None] - 1
+    return ct
+
+
 def _pair(oracle_mod, capi, scheme, n, primes, t=0, seed=0xABC00001):
     o = oracle_mod.Oracle(scheme, n, primes, t)
     o.keygen(seed)
@@ -147,7 +161,8 @@ def test_big_ring_bfv_on_an_fp64_chain(n, bits, generic, oracle_mod, capi, monke
     kernels with a radix-32 / radix-64 cross pass (abc_kernels_gsplit.hip, k_bsplit_*); with ABC_HIP_NO_BSPLIT the generic
     sequence.  Eight data limbs (the BFVDefault shape): the multiply takes abc_kernels_bmul.hip's fused extension / floor kernels
     around the block tails (1024-point blocks behind two-level radix-32 / 64 cross passes);
-    ABC_HIP_NO_BMUL selects the separate kernels.  All must give the oracle's residues."""
+    ABC_HIP_NO_BMUL selects the separate kernels.  All must give the oracle's residues -- on ordinary encryptions and on end-of-range
+    residues (the forward cross pass re-centres "a sum of two residues" for these primes: the sums are then at their largest)."""
     if generic is True:
         monkeypatch.setenv("ABC_HIP_NO_BSPLIT", "1")
     if generic == "unfused_multiply":
@@ -168,6 +183,16 @@ def test_big_ring_bfv_on_an_fp64_chain(n, bits, generic, oracle_mod, capi, monke
     got = g.mul_relin(batch_a, batch_b)
     _eq("N=%d fp64-chain batch rows 0-1" % n, got[:2], want)
     assert np.array_equal(got[2], g.mul_relin(r, a))
+    # end-of-range residues through the same kernels: rotation, multiply + relinearise (alone and as one row of a batch), multiply
+    ex = _extreme_ct(primes, len(bits) - 1, n, np.random.default_rng(n + len(bits)))
+    _eq("N=%d fp64-chain rotate, extreme residues" % n, g.rotate(ex, 5), o.rotate(ex, 5))
+    want_ex = o.mul_relin(ex, a)
+    _eq("N=%d fp64-chain mul_relin, extreme residues" % n, g.mul_relin(ex, a), want_ex)
+    got = g.mul_relin(np.stack([a, ex, b]), np.stack([b, a, r]))
+    _eq("N=%d fp64-chain batch with an extreme row [0]" % n, got[0], want[0])
+    _eq("N=%d fp64-chain batch with an extreme row [1]" % n, got[1], want_ex)
+    _eq("N=%d fp64-chain batch with an extreme row [2]" % n, got[2], want[1])
+    _eq("N=%d fp64-chain multiply (3 components), extreme residues" % n, g.multiply(ex, ex), o.multiply(ex, ex))
 
 
 def test_bfv_default_8192_and_16384(oracle_mod, capi):
