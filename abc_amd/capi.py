@@ -21,7 +21,7 @@ _lib = None
 SYMBOLS = [
     "abc_hip_last_error", "abc_hip_device_count", "abc_hip_ctx_create", "abc_hip_ctx_destroy",
     "abc_hip_default_bfv_primes", "abc_hip_plain_modulus_batching", "abc_hip_create_primes", "abc_hip_ctx_info",
-    "abc_hip_set_stream", "abc_hip_sync", "abc_hip_ctx_reload_env", "abc_hip_malloc", "abc_hip_free", "abc_hip_trim",
+    "abc_hip_set_stream", "abc_hip_sync", "abc_hip_ctx_reload_env", "abc_hip_route", "abc_hip_malloc", "abc_hip_free", "abc_hip_trim",
     "abc_hip_cached_bytes", "abc_hip_memcpy_h2d", "abc_hip_memcpy_d2h",
     "abc_hip_memcpy_d2d", "abc_hip_keygen", "abc_hip_keygen_secure", "abc_hip_encrypt_secure", "abc_hip_load_secret_key", "abc_hip_load_public_key",
     "abc_hip_load_relin_key", "abc_hip_load_galois_key", "abc_hip_get_secret_key", "abc_hip_get_public_key",
@@ -59,6 +59,7 @@ def lib():
         L.abc_hip_cached_bytes.restype = C.c_size_t
         L.abc_hip_cached_bytes.argtypes = [C.c_void_p]
         L.abc_hip_galois_elt_from_step.restype = C.c_uint32
+        L.abc_hip_route.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_char_p, C.c_size_t]
         _lib = L
     return _lib
 
@@ -168,6 +169,14 @@ class Context:
 
     def reload_env(self):
         _chk(lib().abc_hip_ctx_reload_env(self.h))
+
+    ROUTE_OPS = {"mul_relin": 0, "keyswitch": 1, "relinearize": 1, "rotate": 2, "rescale": 3, "multiply": 4}
+
+    def route(self, op, nl, count=1, in_place=False):
+        """the kernel sequence such a call takes, as the string of abc_route.hpp's formatter"""
+        buf = C.create_string_buffer(128)
+        _chk(lib().abc_hip_route(self.h, self.ROUTE_OPS.get(op, op), nl, count, int(in_place), buf, len(buf)))
+        return buf.value.decode()
 
     def held_buffers(self):
         """device buffers (scratch arenas, replaced keys) held back for live recorded circuits; -1 from a library without the count"""

@@ -52,6 +52,15 @@ void read_switches(abc_hip_ctx *c) {
     if (s.lanes > abc_hip_ctx::kMaxLanes) s.lanes = abc_hip_ctx::kMaxLanes;
   }
   c->sw = s;
+  // the facts the routes are a function of (abc_route.hpp): the primes are fixed by now, so this is the only walk over them
+  RouteFacts &f = c->facts;
+  f = RouteFacts{};
+  f.scheme = c->scheme; f.logn = c->logn; f.K = c->K; f.L = c->L; f.nB = c->nB;
+  f.use_fp = c->use_fp; f.behz_fp = c->behz_fp;
+  f.big_block_log = big_block_log();
+  for (int j = 0; j < c->K; j++) f.bits[j] = (unsigned char)c->h_mods[j].bits;
+  f.sw = s;
+  f.finish();
 }
 
 static Mod make_mod(uint64_t q, int logn, bool ntt) {
@@ -291,7 +300,7 @@ static int build_context(abc_hip_ctx *c) {
   ABC_HIP_CHECK(hipMalloc(&c->d_ftw, h_ftw.size() * 8));
   ABC_HIP_CHECK(hipMemcpy(c->d_ftw, h_ftw.data(), h_ftw.size() * 8, hipMemcpyHostToDevice));
   c->use_fp = !env_on("ABC_HIP_NO_FP64");
-  read_switches(c);
+  read_switches(c);  // after the moduli: the route facts hold their widths
   ABC_HIP_CHECK(hipMalloc(&c->d_cst, sizeof(DevConst)));
   ABC_HIP_CHECK(hipMemcpy(c->d_cst, &k, sizeof(DevConst), hipMemcpyHostToDevice));
   if (bfv && c->behz_fp) {
@@ -366,12 +375,9 @@ static std::vector<int> naf(int value) {
   return out;
 }
 
-// key switch dispatcher: LDS-resident kernels when the ring fits, generic kernels otherwise
 static int keyswitch(abc_hip_ctx *c, const u64 *target, size_t target_stride, const u64 *key, u64 *out2, int nl, size_t count,
                      const u64 *addend, size_t addend_stride, bool add_c1) {
-  const int rc = keyswitch_fused(c, target, target_stride, key, out2, nl, count, addend, addend_stride, add_c1);
-  if (rc >= 0) return rc;
-  return keyswitch_generic(c, target, target_stride, key, out2, nl, count, addend, addend_stride, add_c1);
+  return launch_keyswitch(c, route_keyswitch(c->facts, nl), target, target_stride, key, out2, nl, count, addend, addend_stride, add_c1);
 }
 
 static int apply_galois(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, uint32_t elt, size_t count) {
@@ -380,16 +386,15 @@ static int apply_galois(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, uint32_
   if (!count) return 0;
   const size_t N = (size_t)c->n, pw = (size_t)nl * N;
   const bool ntt_form = (c->scheme == ABC_HIP_SCHEME_CKKS);
-  {  // N = 2^14 CKKS: the permutation is a block-local gather, done inside the key-switch kernels
-    const int rc = rotate_fused(c, in, elt, it->second, out, nl, count);
-    if (rc >= 0) return rc;
-  }
+  // out = (g(c0) + ks0, ks1) with ks = KeySwitch(g(c1))
+  const RotRoute r = route_rotate(c->facts, nl, in == out);
+  if (r.fold)  // the permutation is a gather inside the key-switch kernels
+    return launch_keyswitch(c, r.ks, in + pw, 2 * pw, it->second, out, nl, count, in, 2 * pw, false, elt);
   // g(c0), g(c1) live in arena 0 (keyswitch_generic uses c->ws)
   if (ensure_aux(c, 0, count * 2 * pw * 8)) return 1;
   u64 *g = (u64 *)c->aux[0];
   if (launch_galois(c, in, g, nl, count * 2, elt, ntt_form)) return 1;
-  // out = (g(c0) + ks0, ks1) with ks = KeySwitch(g(c1))
-  return keyswitch(c, g + pw, 2 * pw, it->second, out, nl, count, g, 2 * pw, false);
+  return launch_keyswitch(c, r.ks, g + pw, 2 * pw, it->second, out, nl, count, g, 2 * pw, false);
 }
 
 static int rotate(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, int steps, size_t count) {
@@ -799,6 +804,15 @@ static int check_level(abc_hip_ctx *c, int nl) {
   if (c->scheme == ABC_HIP_SCHEME_BFV && nl != c->L) { set_error("BFV ciphertexts live at the top level (nl = L)"); return 1; }
   return 0;
 }
+int abc_hip_route(abc_hip_ctx *c, int op, int nl, size_t count, int in_place, char *buf, size_t cap) {
+  CTX_GUARD(c);
+  if (check_level(c, nl)) return 1;  // nl as the operation itself takes it (BFV: L, also for multiply)
+  if (op == kRouteRescale && (nl < 2 || c->scheme != ABC_HIP_SCHEME_CKKS)) { set_error("route: rescale needs CKKS and nl >= 2"); return 1; }
+  const int n = buf ? format_op(buf, cap, c->facts, op, nl, count, in_place != 0) : -1;
+  if (n == -2) { set_error("route: unknown operation"); return 1; }
+  if (n < 0) { set_error("route: buffer too small"); return 1; }
+  return 0;
+}
 int abc_hip_add(abc_hip_ctx *c, const uint64_t *a, const uint64_t *b, uint64_t *out, int size, int nl, size_t count) {
   CTX_GUARD(c);
   if (check_level(c, nl)) return 1;
@@ -818,7 +832,7 @@ int abc_hip_multiply(abc_hip_ctx *c, const uint64_t *a, const uint64_t *b, uint6
   CTX_GUARD(c);
   if (check_level(c, nl)) return 1;
   if (c->scheme == ABC_HIP_SCHEME_CKKS) return launch_ckks_tensor(c, a, b, out3, nl, count);
-  return bfv_multiply(c, a, b, out3, count);
+  return bfv_multiply(c, route_bfv_multiply(c->facts), a, b, out3, count);
 }
 int abc_hip_relinearize(abc_hip_ctx *c, const uint64_t *ct3, uint64_t *out2, int nl, size_t count) {
   CTX_GUARD(c);
@@ -829,17 +843,16 @@ int abc_hip_mul_relin(abc_hip_ctx *c, const uint64_t *a, const uint64_t *b, uint
   CTX_GUARD(c);
   if (check_level(c, nl)) return 1;
   if (!c->d_relin) { set_error("mul_relin: no relinearisation key"); return 1; }
-  if (c->scheme == ABC_HIP_SCHEME_CKKS) {
-    const int rc = ckks_mul_relin_fused(c, a, b, out, nl, count);
-    if (rc >= 0) return rc;
-  }
-  if (c->scheme == ABC_HIP_SCHEME_BFV && bmul_applies(c)) return bmul_split(c, a, b, out, count, true);
+  const MulRoute r = route_mul_relin(c->facts, nl);
+  if (r.seq == Seq::bmul) return bmul_split(c, a, b, out, count, true);
+  if (r.seq != Seq::generic) return launch_mul_relin(c, r.seq, a, b, out, nl, count);
   // generic path: size-3 product in arena 1, then key switch
   const size_t bytes = count * 3 * nl * (size_t)c->n * 8;
   if (ensure_aux(c, 1, bytes ? bytes : 8)) return 1;
   u64 *t3 = (u64 *)c->aux[1];
-  int rc = (c->scheme == ABC_HIP_SCHEME_CKKS) ? launch_ckks_tensor(c, a, b, t3, nl, count) : bfv_multiply(c, a, b, t3, count);
-  if (!rc) rc = relinearize(c, t3, out, nl, count);
+  int rc = (c->scheme == ABC_HIP_SCHEME_CKKS) ? launch_ckks_tensor(c, a, b, t3, nl, count) : bfv_multiply(c, r.mul, a, b, t3, count);
+  const size_t pw = (size_t)nl * c->n;  // target = c2, addend = (c0, c1), as in relinearize
+  if (!rc) rc = launch_keyswitch(c, r.ks, t3 + 2 * pw, 3 * pw, c->d_relin, out, nl, count, t3, 3 * pw, true);
   return rc;
 }
 int abc_hip_rotate(abc_hip_ctx *c, const uint64_t *in, uint64_t *out, int nl, int steps, size_t count) {

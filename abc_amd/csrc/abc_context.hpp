@@ -14,6 +14,7 @@
 #include "abc_buffers.hpp"
 #include "abc_modarith.hpp"
 #include "abc_ntt.hpp"
+#include "abc_route.hpp"
 
 namespace abc {
 
@@ -143,14 +144,11 @@ struct abc_hip_ctx {
   abc::BufferTable buffers;
   bool behz_fp = false;  // BFV: 50-bit BEHZ auxiliary base and fp64 base-conversion kernels
   bool use_fp = true;  // fp64 transforms for primes < 2^50 (ABC_HIP_NO_FP64=1 forces the integer path)
-  // Path switches (A/B timing and the parity tests of every fallback): the ABC_HIP_* environment variables are read
-  // ONCE, when the context is created (abc_hip_ctx_reload_env re-reads them), never on the per-operation path.
-  struct Switches {
-    bool no_fused = false, no_split = false, no_split4 = false, no_isplit = false, no_gsplit = false, no_lean_front = false, no_bsplit = false, no_mixed = false, no_pack = false, no_key_twin = false, no_bmul = false, no_iks = false, no_tensor_intt = false;
-    bool no_galois_fusion = false;
-    size_t chunk = 0, few_limbs = 48, lean_limit = 96, bfv_scratch_mb = 0, pass0_target_limit = 128;
-    int lanes = 2;
-  } sw;
+  // Path switches and everything else a kernel sequence is chosen by (abc_route.hpp): filled ONCE, when the context is created
+  // (abc_hip_ctx_reload_env fills them again), never on the per-operation path.
+  using Switches = abc::Switches;
+  Switches sw;
+  abc::RouteFacts facts;
   abc::DevConst *d_cst = nullptr;
   abc::DevConstFp *d_cstf = nullptr;
   uint32_t *d_slot_map = nullptr;
@@ -220,14 +218,14 @@ int ensure_aux(abc_hip_ctx *c, int which, size_t bytes);
 hipError_t alloc_context_buffer(abc_hip_ctx *c, void **p, size_t bytes, bool retry);
 // free context buffer p, or hold it back while a live graph owns it; the caller has drained c->stream
 void retire_buffer(abc_hip_ctx *c, void *p);
-void read_switches(abc_hip_ctx *c);
+void read_switches(abc_hip_ctx *c);  // the environment into c->sw, then c->facts
 
 // ---- launchers implemented in the kernel translation units ----
 LimbMap key_limb_map(const abc_hip_ctx *c, int nl);  // 0..nl-1 -> data primes, nl -> special prime
 // in-place forward / inverse NTT over `limbs` consecutive limbs laid out [groups][nl][N]; limb j of each
 // group uses modulus map.id[j % nl]
 int launch_ntt_fwd(abc_hip_ctx *c, u64 *d, const LimbMap &map, int nl, size_t total_limbs);
-int launch_ks_expand_ntt_fp(abc_hip_ctx *c, const u64 *tcoef, size_t tstride, u64 *dec, const LimbMap &map, int nl, size_t count);
+int launch_ks_expand_ntt_fp(abc_hip_ctx *c, const u64 *tcoef, size_t tstride, u64 *dec, const LimbMap &map, int nl, size_t count);  // KsFront::fp
 int launch_ntt_fwd_from2(abc_hip_ctx *c, const u64 *src, const u64 *src2, u64 *d, const LimbMap &map, int nl, size_t total_limbs);
 int launch_ntt_fwd_from(abc_hip_ctx *c, const u64 *src, u64 *d, const LimbMap &map, int nl, size_t total_limbs);  // out of place
 int launch_ntt_inv(abc_hip_ctx *c, u64 *d, const LimbMap &map, int nl, size_t total_limbs);
@@ -236,7 +234,7 @@ int big_block_log(void);
 
 int launch_addsub(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out, int nl, size_t polys, int op);  // 0 add 1 sub 2 neg
 int launch_ckks_tensor(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out3, int nl, size_t count);
-int keyswitch_generic(abc_hip_ctx *c, const u64 *target, size_t target_stride, const u64 *key, u64 *out2, int nl,
+int keyswitch_generic(abc_hip_ctx *c, KsFront front, const u64 *target, size_t target_stride, const u64 *key, u64 *out2, int nl,
                       size_t count, const u64 *addend, size_t addend_stride, bool add_c1, u32 ginv = 0);
 int launch_ks_tmod(abc_hip_ctx *c, const u64 *prodS, u64 *tmod, int nl, size_t polys);
 int launch_ks_finish(abc_hip_ctx *c, const u64 *prodD, const u64 *tmod, u64 *out, const u64 *addend, size_t addend_stride,
@@ -245,7 +243,7 @@ int launch_galois(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, size_t polys,
 int launch_rescale(abc_hip_ctx *c, const u64 *in, u64 *out, int size, int nl, size_t count);
 int launch_drop_last(abc_hip_ctx *c, const u64 *in, u64 *out, int size, int nl, size_t count);
 
-int bfv_multiply(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out3, size_t count);
+int bfv_multiply(abc_hip_ctx *c, BfvMul m, const u64 *a, const u64 *b, u64 *out3, size_t count);
 int bfv_multiply_plain(abc_hip_ctx *c, const u64 *ct, const u64 *plain, size_t plain_stride, u64 *out, int size, size_t count);
 int bfv_addsub_plain(abc_hip_ctx *c, const u64 *ct, const u64 *plain, size_t plain_stride, u64 *out, int size, size_t count, int sub);
 int ckks_multiply_plain(abc_hip_ctx *c, const u64 *ct, const u64 *plain, size_t plain_stride, u64 *out, int size, int nl, size_t count);
@@ -263,13 +261,13 @@ int keygen_secure(abc_hip_ctx *c);
 int encrypt_secure(abc_hip_ctx *c, const u64 *plain, u64 *ct, size_t count);
 int microbench(abc_hip_ctx *c, int which, int iters, double *ms);
 
-// LDS-resident fast paths (N <= 2^14); return -1 if not applicable (caller falls back to the generic kernels)
-int rotate_fused(abc_hip_ctx *c, const u64 *in, u32 elt, const u64 *key, u64 *out, int nl, size_t count);
-int keyswitch_fused(abc_hip_ctx *c, const u64 *target, size_t target_stride, const u64 *key, u64 *out2, int nl, size_t count,
-                    const u64 *addend, size_t addend_stride, bool add_c1);
-int ckks_mul_relin_fused(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out, int nl, size_t count);
+// the key switch of route r (abc_kernels_fused.hip; any sequence); gelt: the Galois element of a rotation folded into it
+// (RotRoute::fold), with target = c1, addend = c0 of the ciphertext
+int launch_keyswitch(abc_hip_ctx *c, const KsRoute &r, const u64 *target, size_t target_stride, const u64 *key, u64 *out2, int nl, size_t count,
+                     const u64 *addend, size_t addend_stride, bool add_c1, u32 gelt = 0);
+// CKKS multiply + relinearise in one sequence (every Seq but bmul and generic)
+int launch_mul_relin(abc_hip_ctx *c, Seq seq, const u64 *a, const u64 *b, u64 *out, int nl, size_t count);
 // split key switch without LDS-resident limbs (abc_kernels_gsplit.hip): N = 2^15, and the first step at N = 2^14 for small batches
-bool gsplit_applies(const abc_hip_ctx *c, int nl);
 size_t gsplit_scratch_words(const abc_hip_ctx *c, int nl);
 int gsplit_chunk15(abc_hip_ctx *c, hipStream_t st, u64 *scratch, size_t cc, int nl, int mode, const u64 *opa, const u64 *opb,
                    size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt);
@@ -302,6 +300,17 @@ inline void dispatch_mode(int mode, u32 gelt, Fn f) {
   else if (gelt) f(std::integral_constant<int, 1>{}, std::true_type{});
   else f(std::integral_constant<int, 1>{}, std::false_type{});
 }
+// logn -> f(LB) as an integral constant and its result; a ring outside [LO, HI] is an error (the routes keep it from happening)
+template <int LO, int HI, class Fn>
+inline int dispatch_logn(int logn, Fn f) {
+  if constexpr (LO <= HI) {
+    if (logn == LO) return f(std::integral_constant<int, LO>{});
+    return dispatch_logn<LO + 1, HI>(logn, f);
+  } else {
+    set_error("no kernel of this sequence for the ring degree");
+    return 1;
+  }
+}
 // nl -> f(NL) as an integral constant, NL = nl clamped to [LO, HI]
 template <int LO, class Fn, int... Is>
 inline void dispatch_nl_seq(int nl, Fn &f, std::integer_sequence<int, Is...>) {
@@ -315,9 +324,6 @@ inline void dispatch_nl(int nl, Fn f) {
 // split4_main (N = 2^14): false = not applicable (more than seven limbs); gsplit_main15: any nl <= 15 (above seven: the deep kernel)
 bool split4_main(abc_hip_ctx *c, int mode, const MainArgs &a);
 void gsplit_main15(abc_hip_ctx *c, int mode, const MainArgs &a);
-bool bsplit_applies(const abc_hip_ctx *c, int nl);
-bool bsplit_big_applies(const abc_hip_ctx *c, int nl);
-bool iks_bfv_applies(const abc_hip_ctx *c, int nl);  // abc_kernels_eval.hip
 int bsplit_big(abc_hip_ctx *c, const u64 *target, size_t target_stride, const u64 *key, u64 *out, int nl, size_t count, const u64 *addend,
                size_t addend_stride, bool add_c1, u32 ginv = 0);
 int bsplit_back14(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const double *part, double *half, const u64 *key, const u64 *addend,
@@ -385,14 +391,8 @@ inline size_t even_chunks(size_t budget_bytes, size_t per_ct_words, size_t count
   return chunk;
 }
 
-// Prime-width predicates (fp_ok: below 2^50, the exact-fp64 kernels; unguarded_ok: 64 q <= 2^64): the name says WHICH primes
-// are inspected, `ok` is the width test.  A sequence must ask about exactly the primes its kernels compute with.
-template <class P>
-inline bool all_key_primes(const abc_hip_ctx *c, P ok) {  // all K: the whole chain's data primes and the special prime
-  for (int j = 0; j < c->K; j++)
-    if (!ok(c->h_mods[j].bits)) return false;
-  return true;
-}
+// Prime-width predicates for the per-launch arithmetic choices (launch_ntt, the BFV tensor kernels, multiply_plain); which
+// SEQUENCE runs is abc_route.hpp's business.  The name says WHICH primes are inspected, `ok` is the width test.
 template <class P>
 inline bool all_data_primes(const abc_hip_ctx *c, int nl, P ok) {  // the first nl data primes, not the special prime
   for (int j = 0; j < nl; j++)
@@ -400,31 +400,18 @@ inline bool all_data_primes(const abc_hip_ctx *c, int nl, P ok) {  // the first 
   return true;
 }
 template <class P>
-inline bool all_data_and_special_primes(const abc_hip_ctx *c, int nl, P ok) {  // the first nl data primes and the special prime
-  return all_data_primes(c, nl, ok) && ok(c->h_mods[c->K - 1].bits);
-}
-template <class P>
 inline bool all_mapped_primes(const abc_hip_ctx *c, const LimbMap &map, int nl, P ok) {  // the moduli map.id[0 .. nl-1]
   for (int j = 0; j < nl; j++)
     if (!ok(c->h_mods[map.id[j]].bits)) return false;
   return true;
 }
-template <class P>
-inline u32 data_prime_mask(const abc_hip_ctx *c, int nl, P ok) {  // bit j: data prime j passes (j < nl)
-  u32 mask = 0;
-  for (int j = 0; j < nl; j++)
-    if (ok(c->h_mods[j].bits)) mask |= 1u << j;
-  return mask;
-}
 
 // BFV multiply (+ relinearise) in split form, N = 2^14 (abc_kernels_bmul.hip)
-bool bmul_applies(const abc_hip_ctx *c);           // multiply + relinearise in one sequence
-bool bmul_multiply_applies(const abc_hip_ctx *c);  // the multiply alone (also N = 2^15 / 2^16)
-int bmul_split(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out, size_t count, bool relin);
+int bmul_split(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out, size_t count, bool relin);  // Seq::bmul / BfvMul::split
+int bmul_big(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out3, size_t count);                 // BfvMul::big
 // integer twins of the split kernels (abc_kernels_isplit.hip)
-bool isplit_applies(const abc_hip_ctx *c, int nl);
 size_t isplit_scratch_words(const abc_hip_ctx *c, int nl);
 int isplit_chunk(abc_hip_ctx *c, hipStream_t st, u64 *scratch, size_t cc, int nl, int mode, const u64 *opa, const u64 *opb,
-                 size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt);
+                 size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt, const ChunkRoute &k);
 
 }  // namespace abc

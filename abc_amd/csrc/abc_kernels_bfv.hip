@@ -429,14 +429,8 @@ static int tensor_intt(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *d, const
   if (c->sw.no_tensor_intt) return -1;
   // single-ciphertext calls: the separate kernels spread a transform over many workgroups (launch_ntt, "few limbs")
   if (c->logn == 14 && count * 3 * (size_t)nlm <= 48) return -1;
-  switch (c->logn) {
-    case 10: return launch_tensor_intt<10>(c, a, b, d, map, nlm, count);
-    case 11: return launch_tensor_intt<11>(c, a, b, d, map, nlm, count);
-    case 12: return launch_tensor_intt<12>(c, a, b, d, map, nlm, count);
-    case 13: return launch_tensor_intt<13>(c, a, b, d, map, nlm, count);
-    case 14: return launch_tensor_intt<14>(c, a, b, d, map, nlm, count);
-    default: return -1;
-  }
+  if (c->logn > 14 || c->logn < 10) return -1;
+  return dispatch_logn<10, 14>(c->logn, [&](auto LB) { return launch_tensor_intt<decltype(LB)::value>(c, a, b, d, map, nlm, count); });
 }
 
 // shapes of BFVDefault(4096 / 8192 / 16384) and of config 5 get fully unrolled kernels (the L = 8, nB = 9 shape was tried:
@@ -464,10 +458,11 @@ static void launch_behz_floor(abc_hip_ctx *c, const u64 *dq, const u64 *dB, u64 
   ABC_BEHZ_DISPATCH(k_behz_floor, dim3(grid_for(polys * c->n, 256)), c->dc, dq, dB, out, polys);
 }
 
-int bfv_multiply(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out3, size_t count) {
+int bfv_multiply(abc_hip_ctx *c, BfvMul m, const u64 *a, const u64 *b, u64 *out3, size_t count) {
   if (c->scheme != 1) { set_error("bfv_multiply on a non-BFV context"); return 1; }
   if (!count) return 0;
-  if (bmul_multiply_applies(c)) return bmul_split(c, a, b, out3, count, false);  // BFVDefault shape on fp64 primes: abc_kernels_bmul.hip
+  if (m == BfvMul::split) return bmul_split(c, a, b, out3, count, false);  // BFVDefault shapes on fp64 primes: abc_kernels_bmul.hip
+  if (m == BfvMul::big) return bmul_big(c, a, b, out3, count);
   const size_t N = (size_t)c->n;
   const int L = c->L, nBsk = c->nBsk, nlm = L + nBsk;
   // per ciphertext pair (words): aq,bq 2*2L ; aB,bB 2*2nBsk ; dq 3L ; dB 3nBsk
@@ -597,16 +592,9 @@ int bfv_multiply_plain(abc_hip_ctx *c, const u64 *ct, const u64 *plain, size_t p
   ABC_HIP_CHECK(hipGetLastError());
   if (launch_ntt_fwd(c, lifted, qmap, L, nplain * L)) return 1;
   const bool fp = c->use_fp && c->logn <= 14 && !c->sw.no_fused && all_data_primes(c, L, fp_ok);
-  if (fp && (c->logn < 14 || count * size * L > 48)) {  // single-ciphertext calls keep the spread-out transforms
+  if (fp && c->logn >= 10 && (c->logn < 14 || count * size * L > 48)) {  // single-ciphertext calls keep the spread-out transforms
     const size_t ls = plain_stride ? (size_t)L * N : 0;
-    switch (c->logn) {
-      case 10: return launch_mul_plain_fused<10>(c, ct, lifted, ls, out, size, count);
-      case 11: return launch_mul_plain_fused<11>(c, ct, lifted, ls, out, size, count);
-      case 12: return launch_mul_plain_fused<12>(c, ct, lifted, ls, out, size, count);
-      case 13: return launch_mul_plain_fused<13>(c, ct, lifted, ls, out, size, count);
-      case 14: return launch_mul_plain_fused<14>(c, ct, lifted, ls, out, size, count);
-      default: break;
-    }
+    return dispatch_logn<10, 14>(c->logn, [&](auto LB) { return launch_mul_plain_fused<decltype(LB)::value>(c, ct, lifted, ls, out, size, count); });
   }
   if (out != ct) ABC_HIP_CHECK(hipMemcpyAsync(out, ct, count * size * L * N * 8, hipMemcpyDeviceToDevice, c->stream));
   if (launch_ntt_fwd(c, out, qmap, L, count * size * L)) return 1;

@@ -422,22 +422,7 @@ __global__ __launch_bounds__(NT, 4) void k_bmul_back(DevCtx c, const double *__r
 }
 
 // ---- host side ----
-static bool bmul_shape(const abc_hip_ctx *c, int limbs = 8) {
-  return c->scheme == 1 && c->use_fp && c->behz_fp && !c->sw.no_bmul && !c->sw.no_split && !c->sw.no_fused && c->L == limbs &&
-         c->nB == limbs && c->K == c->L + 1;
-}
-// multiply + relinearise in one sequence (N = 2^14)
-bool bmul_applies(const abc_hip_ctx *c) {
-  if (c->logn == 13) return bmul_shape(c, 4) && bsplit_big_applies(c, c->L);  // BFVDefault(8192)
-  return c->logn == 14 && bmul_shape(c) && bsplit_applies(c, c->L);
-}
-// the multiply alone (size-3 product): also N = 2^15 / 2^16
-bool bmul_multiply_applies(const abc_hip_ctx *c) {
-  if (c->logn == 14) return bmul_applies(c);
-  if (c->logn == 13) return bmul_shape(c, 4);  // BFVDefault(8192): four data limbs, radix-8 cross passes over eight 1024-point blocks
-  return (c->logn == 15 || c->logn == 16) && bmul_shape(c) && !c->sw.no_gsplit && big_block_log() == 12;
-}
-
+// (when these sequences apply: Seq::bmul and BfvMul::split / big, abc_route.hpp)
 // scratch per ciphertext pair (words): X = max(hA, part) | Y = max(hD, half + tco)
 static size_t bmul_scratch_words(const abc_hip_ctx *c) {
   const size_t N = (size_t)c->n, PS = (size_t)c->dc.ps;
@@ -450,7 +435,7 @@ static size_t bmul_scratch_words(const abc_hip_ctx *c) {
 // the multiply alone where no key switch follows in the same sequence (N = 2^13, 2^15, 2^16): M1, M2, M3 on the context's stream --
 // where the generic sequence ran extend, two strided + two block forward passes, two tensor / block-inverse launches, two strided
 // inverse passes and the floor
-static int bmul_big(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out3, size_t count) {
+int bmul_big(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out3, size_t count) {
   const size_t N = (size_t)c->n;
   const int L = c->L, nlm = c->L + c->nBsk;
   const size_t per_ct = (size_t)7 * nlm * N;
@@ -490,10 +475,6 @@ static int bmul_big(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out3, size_
 // relin = true: out [count][2][L][N] = relinearised product; false: out [count][3][L][N] = the size-3 product
 int bmul_split(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out, size_t count, bool relin) {
   if (!count) return 0;
-  if (c->logn > 14 || (c->logn == 13 && !relin)) {
-    if (relin) { set_error("bmul_split: multiply + relinearise in one sequence is an N = 2^13 / 2^14 path"); return 1; }
-    return bmul_big(c, a, b, out, count);
-  }
   const bool n13 = c->logn == 13;
   const size_t N = (size_t)c->n, PS = (size_t)c->dc.ps;
   const int L = c->L, nlm = c->L + c->nBsk;

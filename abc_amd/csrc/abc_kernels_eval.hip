@@ -391,18 +391,12 @@ static int iks_finish(abc_hip_ctx *c, const u64 *prodD, const u64 *prodS, const 
   return 0;
 }
 
-// 1: error; -1: not applicable (the caller takes the generic kernels); 0: prodS holds the special limb's sums half-way back to
+// KsFront::iks (N = 2^15 / 2^16, 4096-point blocks).  On return prodS holds the special limb's sums half-way back to
 // coefficients (strided stages left), prodD the data limbs' -- likewise for BFV, in NTT form for CKKS
-// BFV with the permutation of a rotation folded in (rotate_fused): the integer sequence must be the one that runs
-bool iks_bfv_applies(const abc_hip_ctx *c, int nl) {
-  if (c->scheme != 1 || (c->logn != 15 && c->logn != 16) || c->sw.no_iks || big_block_log() != 12 || nl < 1) return false;
-  const bool fp = c->use_fp && all_data_and_special_primes(c, nl, fp_ok);
-  return !fp;  // an all-fp64 decomposition takes launch_ks_expand_ntt_fp + the generic kernels
-}
-static int iks_front(abc_hip_ctx *c, const u64 *tc, size_t tcs, const u64 *key, u64 *dec, u64 *prodD, u64 *prodS, int nl, size_t cc, u32 ginv) {
-  if ((c->logn != 15 && c->logn != 16) || c->sw.no_iks) return -1;
+static int iks_front(abc_hip_ctx *c, const u64 *tc, size_t tcs, const u64 *key, u64 *dec, u64 *prodD, u64 *prodS, int nl, size_t cc, u32 ginv,
+                     bool guard) {
   const int S0 = c->logn - big_block_log();
-  if (big_block_log() != 12) return -1;
+  if (S0 != 3 && S0 != 4) { set_error("iks_front: N = 2^15 / 2^16 with 4096-point blocks only"); return 1; }
   const size_t limbs = cc * nl * (nl + 1);
   const int G = c->n >> S0;
   const dim3 g0((unsigned)(limbs * (G / 256)));
@@ -412,8 +406,7 @@ static int iks_front(abc_hip_ctx *c, const u64 *tc, size_t tcs, const u64 *key, 
   const dim3 g1((unsigned)((cc * (nl + 1)) << S0));
   const u64 *keys = key_shoup(c, key);
   const bool ckks = c->scheme == 2;
-  // unguarded butterflies where every key prime leaves the room: [0, 4q) out of the strided pass, + 4q per block stage = 52q < 2^64
-  const bool guard = !all_key_primes(c, unguarded_ok);
+  // unguarded butterflies (!guard) where every key prime leaves the room: [0, 4q) out of the strided pass, + 4q per block stage = 52q < 2^64
 #define ABC_IKS(INV_D, SHOUP)                                                                                                        \
   do {                                                                                                                               \
     if (guard)                                                                                                                       \
@@ -430,11 +423,11 @@ static int iks_front(abc_hip_ctx *c, const u64 *tc, size_t tcs, const u64 *key, 
   return 0;
 }
 
-int keyswitch_generic(abc_hip_ctx *c, const u64 *target, size_t target_stride, const u64 *key, u64 *out2, int nl, size_t count,
+int keyswitch_generic(abc_hip_ctx *c, KsFront front, const u64 *target, size_t target_stride, const u64 *key, u64 *out2, int nl, size_t count,
                       const u64 *addend, size_t addend_stride, bool add_c1, u32 ginv) {
   if (!count) return 0;
-  if (ginv && !iks_bfv_applies(c, nl)) { set_error("keyswitch_generic: a folded permutation needs the fused integer sequence"); return 1; }
   const bool ckks = (c->scheme == 2);
+  if (ginv && (front != KsFront::iks || ckks)) { set_error("keyswitch_generic: a folded permutation needs the fused integer sequence"); return 1; }
   const size_t N = (size_t)c->n;
   // workspace per ciphertext (words): tcoef nl + dec nl(nl+1) + prodD 2nl + prodS 2 + tmod 2nl
   const size_t per_ct = ((size_t)nl + (size_t)nl * (nl + 1) + 2 * nl + 2 + 2 * nl) * N;
@@ -460,21 +453,20 @@ int keyswitch_generic(abc_hip_ctx *c, const u64 *target, size_t target_stride, c
       tc = tcoef;
       tcs = nl * N;
     }
-    const int fused_expand = launch_ks_expand_ntt_fp(c, tc, tcs, dec, dmap, nl, cc);
-    if (fused_expand > 0) return 1;
-    const int iks = fused_expand < 0 ? iks_front(c, tc, tcs, key, dec, prodD, prodS, nl, cc, ginv) : -1;
-    if (iks > 0) return 1;
-    if (iks == 0 && !ckks) {  // inner products done, block stages of the inverse transforms too: one kernel does the rest
+    if (front == KsFront::fp && launch_ks_expand_ntt_fp(c, tc, tcs, dec, dmap, nl, cc)) return 1;
+    const bool iks = front == KsFront::iks;
+    if (iks && iks_front(c, tc, tcs, key, dec, prodD, prodS, nl, cc, ginv, c->facts.guard)) return 1;
+    if (iks && !ckks) {  // inner products done, block stages of the inverse transforms too: one kernel does the rest
       if (iks_finish(c, prodD, prodS, addend ? addend + off * addend_stride : nullptr, addend_stride, add_c1, out2 + off * 2 * nl * N, nl, cc, ginv))
         return 1;
       continue;
     }
-    if (iks == 0) {  // CKKS: the special limb's strided stages (integers, like its block stages: k_iks_special), then as ever
+    if (iks) {  // CKKS: the special limb's strided stages (integers, like its block stages: k_iks_special), then as ever
       if (launch_ntt_inv_strided_part(c, prodS, smap, 1, cc * 2, true)) return 1;
       if (launch_ks_tmod(c, prodS, tmod, nl, cc * 2)) return 1;
       if (launch_ntt_fwd(c, tmod, dmap, nl, cc * 2 * nl)) return 1;
     } else {
-      if (fused_expand < 0) {
+      if (front == KsFront::plain) {
         hipLaunchKernelGGL(k_ks_expand, dim3(grid_for(cc * nl * N, 256)), dim3(256), 0, c->stream, c->dc, tc, tcs, dec, nl, cc);
         ABC_HIP_CHECK(hipGetLastError());
         if (launch_ntt_fwd(c, dec, dmap, nl + 1, cc * nl * (nl + 1))) return 1;
@@ -685,11 +677,10 @@ __global__ __launch_bounds__((1 << LB) / 16) void k_rescale_ntt_mixed(DevCtx c, 
   }
 }
 template <int LB>
-static int launch_rescale_mixed(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, size_t polys) {
+static int launch_rescale_mixed(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, size_t polys, u32 fpmask) {
   const size_t N = (size_t)1 << LB;
   if (ensure_workspace(c, polys * N * 8)) return 1;
   u64 *last = (u64 *)c->ws;
-  const u32 fpmask = (c->use_fp && !c->sw.no_mixed) ? data_prime_mask(c, nl, fp_ok) : 0u;
   const dim3 block((1 << LB) / 16);
   hipLaunchKernelGGL(k_rescale_intt_mixed<LB>, dim3((unsigned)polys), block, 0, c->stream, c->dc, in, last, nl, (int)((fpmask >> (nl - 1)) & 1u));
   hipLaunchKernelGGL(k_rescale_ntt_mixed<LB>, dim3((unsigned)(polys * (nl - 1))), block, 0, c->stream, c->dc, in, last, out, nl, (int)polys,
@@ -702,23 +693,11 @@ int launch_rescale(abc_hip_ctx *c, const u64 *in, u64 *out, int size, int nl, si
   if (nl < 2) { set_error("rescale: no limb left to drop"); return 1; }
   const size_t N = (size_t)c->n, polys = count * size;
   if (!polys) return 0;
-  const bool fp = c->use_fp && c->logn <= 14 && in != out && !c->sw.no_fused && all_data_primes(c, nl, fp_ok);
-  if (!fp && c->logn <= 14 && in != out && !c->sw.no_fused && !c->sw.no_isplit) switch (c->logn) {  // a prime above 2^50 in the chain
-      case 10: return launch_rescale_mixed<10>(c, in, out, nl, polys);
-      case 11: return launch_rescale_mixed<11>(c, in, out, nl, polys);
-      case 12: return launch_rescale_mixed<12>(c, in, out, nl, polys);
-      case 13: return launch_rescale_mixed<13>(c, in, out, nl, polys);
-      case 14: return launch_rescale_mixed<14>(c, in, out, nl, polys);
-      default: break;
-    }
-  if (fp) switch (c->logn) {
-      case 10: return launch_rescale_fp<10>(c, in, out, nl, polys);
-      case 11: return launch_rescale_fp<11>(c, in, out, nl, polys);
-      case 12: return launch_rescale_fp<12>(c, in, out, nl, polys);
-      case 13: return launch_rescale_fp<13>(c, in, out, nl, polys);
-      case 14: return launch_rescale_fp<14>(c, in, out, nl, polys);
-      default: break;
-    }
+  const RescaleRoute r = route_rescale(c->facts, nl, in == out);
+  if (r.kind == Rescale::mixed)  // a prime above 2^50 in the chain
+    return dispatch_logn<10, 14>(c->logn, [&](auto LB) { return launch_rescale_mixed<decltype(LB)::value>(c, in, out, nl, polys, r.fpmask); });
+  if (r.kind == Rescale::fp)
+    return dispatch_logn<10, 14>(c->logn, [&](auto LB) { return launch_rescale_fp<decltype(LB)::value>(c, in, out, nl, polys); });
   if (ensure_workspace(c, (polys * N + polys * (nl - 1) * N) * 8)) return 1;
   u64 *last = (u64 *)c->ws, *tmod = last + polys * N;
   hipLaunchKernelGGL(k_gather_last, dim3(grid_for(polys * N, 256)), dim3(256), 0, c->stream, c->dc, in, last, nl, polys);

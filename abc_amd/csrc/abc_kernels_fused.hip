@@ -4,29 +4,11 @@
 //
 // Replaces, for rings that fit LDS:
 //   SealCiphertext::multiply / multiplyInplace = Evaluator::multiply + relinearize_inplace
-//       (src/runtime/SealCiphertext.cpp:102-107,121-124)                     -> ckks_mul_relin_fused, keyswitch_fused
-//   SealCiphertext::rotateRows / rotateRowsInplace = Evaluator::rotate_rows    (:52-61) -> keyswitch_fused
-// Three launch sequences live here; the dispatcher (run_mul_relin / run_keyswitch / keyswitch_stage) takes the first one the
-// context's primes and ring size allow, and tests/test_gpu_paths.py holds all of them bit-identical to the oracle:
-//   split fp64  (N = 2^14, every key prime < 2^50; the headline configuration; sequence described above k_split2_tensor_pass0_fp)
-//       K1  k_split2_tensor_pass0_fp / k_fused_operand_pass0_fp : tensor product or operand, inverse transform of limb j in LDS,
-//                                          first radix-16 register pass of the forward transforms modulo the other key primes;
-//                                          half-done limbs to scratch, packed (abc_ntt.hpp) or as raw doubles
-//       K2a k_split_special_fp, K2b k_split3_pass_fp, K2c k_split4_main_fp (k_split3_main_fp for six and seven limbs)
-//   LDS-resident fp64 (N < 2^14, or ABC_HIP_NO_SPLIT; every key prime < 2^50)
-//       K1 tensor_decomp_fp (operand_intt_fp + decomp_ntt_fp for a key switch), K2b mac, K2c special_intt_fp, K3 moddown_fp / _bfv_fp
-//   LDS-resident integer (any prime up to 61 bits)
-//       K1  tensor_intt : c0 = a0b0, c1 = a0b1 + a1b0 to scratch (so `out` may alias an operand); c2 = a1b1 kept in
-//                         NTT form and, through an in-LDS inverse transform, in coefficient form
-//       K2a decomp_ntt  : workgroup (ct, key prime I, limb J) reduces operand limb J modulo key prime I and
-//                         transforms it in LDS
-//       K2b mac         : streaming inner product with key[J][.][I] (128-bit lazy accumulation)
-//       K2c special     : the special-prime limb goes back to coefficients, plus the q_sp/2 rounding offset
-//       K3  moddown     : workgroup (ct, comp, j): CKKS: reduce the special-prime polynomial modulo q_j, transform
-//                         it, subtract, scale by q_sp^-1, add c0 / c1.  BFV: inverse-transform the accumulated limb,
-//                         then the same subtract / scale / add in coefficient form
-// (chains that mix wide and fp64-capable primes: abc_kernels_isplit.hip; N = 2^15: abc_kernels_gsplit.hip; BFV multiply:
-// abc_kernels_bmul.hip)
+//       (src/runtime/SealCiphertext.cpp:102-107,121-124)                     -> launch_mul_relin, launch_keyswitch
+//   SealCiphertext::rotateRows / rotateRowsInplace = Evaluator::rotate_rows    (:52-61) -> launch_keyswitch
+// Which sequence a call takes -- the split fp64 kernels at N = 2^14, the LDS-resident fp64 or integer kernels, or one of the
+// other translation units' -- is decided in abc_route.hpp and tabulated in DESIGN.md section 3b; the launch functions at the end
+// of this file switch over that route.  tests/test_gpu_paths.py holds every route bit-identical to the oracle.
 // Algorithmic HBM bytes per multiply: 8N(6L + 2L(L+1)); measured: DESIGN.md section 4.
 #include <type_traits>
 
@@ -717,9 +699,7 @@ static void launch_split_special(hipStream_t st, abc_hip_ctx *c, size_t cc, int 
 #undef ABC_SP
 }
 
-// scratch limbs per ciphertext: coef L, ntt L, dec L(L+1), ksacc 2L, tsp 2, tlast 2, c01 2L
-static inline size_t fused_scratch_limbs(int nl) { return (size_t)nl * (nl + 1) + 6 * (size_t)nl + 4; }
-
+// fused_scratch_limbs(L) (abc_route.hpp) per ciphertext: coef L, ntt L, dec L(L+1), ksacc 2L, tsp 2, tlast 2, c01 2L
 struct FusedScratch {
   u64 *coef, *ntt, *dec, *ksacc, *tsp, *tlast, *c01;
 };
@@ -1103,41 +1083,29 @@ bool split4_main(abc_hip_ctx *c, int mode, const MainArgs &a) {
 }
 
 // K2a..K2c on one chunk (the half-done decomposition limbs are in s.dec; a.part / a.tpart are filled in here)
-static void launch_split3(abc_hip_ctx *c, const FusedScratch &s, int mode, MainArgs a) {
+static void launch_split3(abc_hip_ctx *c, const FusedScratch &s, int mode, MainArgs a, bool main4) {
   a.part = s.dec;
   a.tpart = s.ksacc;
   launch_split_special(a.st, c, a.cc, a.nl, (const double *)s.dec, a.key, (double *)s.tsp);
   hipLaunchKernelGGL(k_split3_pass_fp<14>, dim3((unsigned)(a.cc * 2 * 4)), dim3(256), 0, a.st, c->dc, (const double *)s.tsp,
                      (double *)s.ksacc, a.nl, a.pack);
-  // (measured at nl = 5 / 6 / 7, every prime below 2^50: +9.5 / -5 / -14 % against k_split3_main_fp: above five limbs the prefetched
-  // key words push the kernel past 128 VGPRs and to one workgroup per CU)
-  if (!c->sw.no_split4 && a.nl <= 5 && split4_main(c, mode, a)) return;
+  if (main4 && split4_main(c, mode, a)) return;
   dispatch_mode(mode, a.gelt, [&](auto M, auto G) { launch_split3_main<decltype(M)::value, decltype(G)::value>(c, a); });
-}
-
-// packed half-done limbs (abc_ntt.hpp): only the sequence whose consumer is k_split4_main_fp reads them
-static inline int pack_half_done(const abc_hip_ctx *c, int nl) {
-  return (!c->sw.no_pack && !c->sw.no_split4 && nl >= 1 && nl <= 5) ? 1 : 0;
-}
-static inline bool all_fp(const abc_hip_ctx *c) {  // fp64 transforms: every key prime below 2^50
-  return c->use_fp && all_key_primes(c, fp_ok);
-}
-static inline bool needs_guard(const abc_hip_ctx *c) {  // unguarded butterflies need (2 logN + 4) q < 2^64 for every key prime
-  return !all_key_primes(c, unguarded_ok);
 }
 
 // K2a..K3 on one chunk: operand given by (coef, coef_stride) [+ (ntt, ntt_stride) for CKKS], addends by (addend, stride)
 template <int LB>
 static int keyswitch_stage(abc_hip_ctx *c, hipStream_t st, const FusedScratch &s, const u64 *coef, size_t coef_stride, const u64 *ntt,
                            size_t ntt_stride, const u64 *key, const u64 *addend, size_t addend_stride, bool add_c1, u64 *out, int nl,
-                           size_t cc, int dec_ready = 0 /* 1: dec already holds the transformed decomposition limbs */) {
+                           size_t cc, bool fp /* Seq::lds_fp, else lds_int with k's guard / lazy */, const ChunkRoute &k,
+                           int dec_ready = 0 /* 1: dec already holds the transformed decomposition limbs */) {
   const size_t N = (size_t)1 << LB;
   const dim3 block((1 << LB) / 16);
   const bool ckks = (c->scheme == 2);
-  const bool guard = needs_guard(c);
+  const bool guard = k.guard, lazy = k.lazy;
   const unsigned g2a = (unsigned)(cc * (nl + 1) * nl);
   const unsigned g3 = (unsigned)(cc * 2 * nl);
-  if (all_fp(c)) {
+  if (fp) {
     if (!dec_ready)
       hipLaunchKernelGGL(k_fused_ks_decomp_ntt_fp<LB>, dim3(g2a), block, 0, st, c->dc, coef, coef_stride, s.dec, nl, ckks ? 1 : 0);
     hipLaunchKernelGGL(k_fused_ks_mac, dim3(grid_for(cc * (nl + 1) * (N / 2), 256)), dim3(256), 0, st, c->dc, s.dec,
@@ -1152,8 +1120,6 @@ static int keyswitch_stage(abc_hip_ctx *c, hipStream_t st, const FusedScratch &s
     ABC_HIP_CHECK(hipGetLastError());
     return 0;
   }
-  // 4 products of a (< 64q) operand with a key residue must stay below 2^(k+63): k <= 55
-  const bool lazy = !guard && all_key_primes(c, [](u32 bits) { return bits <= 55; });
   if (guard)
     hipLaunchKernelGGL((k_fused_ks_decomp_ntt<LB, true, false>), dim3(g2a), block, 0, st, c->dc, coef, coef_stride, s.dec, nl,
                        ckks ? 1 : 0);
@@ -1179,27 +1145,6 @@ static int keyswitch_stage(abc_hip_ctx *c, hipStream_t st, const FusedScratch &s
   return 0;
 }
 
-struct ChunkPlan {
-  size_t chunk;
-  int lanes;
-};
-// Chunks alternate between two internal streams so that the HBM-streaming kernels of one chunk overlap the ALU-bound
-// transforms of the other; measured on MI355X: 256-pair chunks on two lanes beat one 512-pair chunk per lane.
-static ChunkPlan plan_chunks(const abc_hip_ctx *c, int nl, size_t count) {
-  ChunkPlan p{c->sw.chunk, c->sw.lanes};
-  if (count <= 8) p.lanes = 1;
-  if (!p.chunk) {
-    const size_t per_ct_bytes = fused_scratch_limbs(nl) * c->n * 8;
-    const size_t cap = ((size_t)4 << 30) / per_ct_bytes / (size_t)p.lanes;  // scratch capped at 4 GiB
-    p.chunk = (count + p.lanes - 1) / p.lanes;
-    if (p.chunk > 128) p.chunk = 128;  // measured this round: 128 > 256 > 64 > 512 (+2 / 0 / -0.5 / -1.5 %)
-    if (p.chunk > cap) p.chunk = cap;
-    if (p.chunk < 1) p.chunk = 1;
-  }
-  if (p.chunk > count) p.chunk = count;
-  return p;
-}
-
 int fork_lanes(abc_hip_ctx *c, int lanes) {
   if (lanes < 2) return 0;
   ABC_HIP_CHECK(hipEventRecord(c->lane_fork, c->stream));
@@ -1218,12 +1163,12 @@ int join_lanes(abc_hip_ctx *c, int lanes) {
 static int run_isplit(abc_hip_ctx *c, int mode, const u64 *opa, const u64 *opb, size_t opa_stride, size_t opb_stride, bool add_c1,
                       const u64 *key, u64 *out, int nl, size_t count, u32 gelt) {
   const size_t N = (size_t)c->n;
-  const ChunkPlan p = plan_chunks(c, nl, count);
-  const bool twin = c->logn == 14 && !c->sw.no_mixed;  // the fp64 limbs of a mixed chain go through k_split4_main_fp
-  return for_each_chunk(c, count, p.chunk, p.lanes, isplit_scratch_words(c, nl), twin ? key : nullptr,
+  const ChunkPlan p = plan_chunks(c->facts, nl, count);
+  const ChunkRoute k = route_chunk(c->facts, Seq::isplit, nl, p.chunk);  // nothing in it depends on the chunk
+  return for_each_chunk(c, count, p.chunk, p.lanes, isplit_scratch_words(c, nl), k.fp_twin ? key : nullptr,
                         [&](hipStream_t st, u64 *scratch, size_t off, size_t cc) {
                           return isplit_chunk(c, st, scratch, cc, nl, mode, opa + off * opa_stride, opb ? opb + off * opb_stride : nullptr,
-                                              opa_stride, opb_stride, add_c1 ? 1 : 0, key, out + off * 2 * (size_t)nl * N, gelt);
+                                              opa_stride, opb_stride, add_c1 ? 1 : 0, key, out + off * 2 * (size_t)nl * N, gelt, k);
                         });
 }
 
@@ -1231,7 +1176,7 @@ static int run_isplit(abc_hip_ctx *c, int mode, const u64 *opa, const u64 *opb, 
 static int run_gsplit15(abc_hip_ctx *c, int mode, const u64 *opa, const u64 *opb, size_t opa_stride, size_t opb_stride, bool add_c1,
                         const u64 *key, u64 *out, int nl, size_t count, u32 gelt) {
   const size_t N = (size_t)c->n;
-  const ChunkPlan p = plan_chunks(c, nl, count);
+  const ChunkPlan p = plan_chunks(c->facts, nl, count);
   return for_each_chunk(c, count, p.chunk, p.lanes, gsplit_scratch_words(c, nl), nullptr,
                         [&](hipStream_t st, u64 *scratch, size_t off, size_t cc) {
                           return gsplit_chunk15(c, st, scratch, cc, nl, mode, opa + off * opa_stride, opb ? opb + off * opb_stride : nullptr,
@@ -1239,89 +1184,69 @@ static int run_gsplit15(abc_hip_ctx *c, int mode, const u64 *opa, const u64 *opb
                         });
 }
 
-// ---- CKKS multiply + relinearise ----
+// ---- CKKS multiply + relinearise: Seq::split14 (its scratch limbs are c->dc.ps words apart), lds_fp, lds_int ----
 template <int LB>
-static int run_mul_relin(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out, int nl, size_t count) {
+static int run_mul_relin(abc_hip_ctx *c, Seq seq, const u64 *a, const u64 *b, u64 *out, int nl, size_t count) {
   const size_t N = (size_t)1 << LB;
-  if (LB == 14 && !all_fp(c) && isplit_applies(c, nl))
-    return run_isplit(c, 0, a, b, 2 * (size_t)nl * N, 2 * (size_t)nl * N, false, c->d_relin, out, nl, count, 0u);
-  const ChunkPlan p = plan_chunks(c, nl, count);
-  // the split sequence (N = 2^14, every key prime below 2^50); its scratch limbs are c->dc.ps words apart.  Otherwise: the
-  // LDS-resident kernels (smaller rings, ABC_HIP_NO_SPLIT, wider primes)
-  const bool split = LB == 14 && all_fp(c) && !c->sw.no_split && nl <= 12;
+  const ChunkPlan p = plan_chunks(c->facts, nl, count);
+  const bool split = seq == Seq::split14, fp = seq != Seq::lds_int;
   const size_t SN = split ? (size_t)c->dc.ps : N;
   const size_t per_ct = fused_scratch_limbs(nl) * SN;
   const size_t ctw = 2 * (size_t)nl * N;
   return for_each_chunk(c, count, p.chunk, p.lanes, per_ct, split ? c->d_relin : nullptr, [&](hipStream_t st, u64 *scratch, size_t off, size_t cc) {
     const FusedScratch s = carve(scratch, p.chunk, nl, SN);
+    const ChunkRoute k = route_chunk(c->facts, seq, nl, cc);
     if constexpr (LB == 14) {
       if (split) {
-        // few ciphertexts in flight: the 139 KiB workgroups of the tensor kernel would leave most CUs idle for its whole
-        // duration; the block-wise inverse tails + register cross pass of abc_kernels_gsplit.hip spread over the chip instead
-        const bool lean = !c->sw.no_lean_front && cc * nl <= c->sw.lean_limit;  // measured at nl = 4: +5 % at 16 pairs, even at 32, -5 % at 48
-        const int pack = pack_half_done(c, nl);
-        if (lean)
-          gsplit_front14(st, c, cc, nl, 0, a + off * ctw, b + off * ctw, 0, (double *)s.coef, (double *)s.dec, 0u, pack);
+        // lean: the block-wise inverse tails + register cross pass of abc_kernels_gsplit.hip spread over the chip
+        if (k.lean)
+          gsplit_front14(st, c, cc, nl, 0, a + off * ctw, b + off * ctw, 0, (double *)s.coef, (double *)s.dec, 0u, k.pack);
         else
           hipLaunchKernelGGL(k_split2_tensor_pass0_fp<LB>, dim3((unsigned)(cc * nl)), dim3((1 << LB) / 16), 0, st, c->dc, a + off * ctw,
-                             b + off * ctw, (double *)s.dec, nl, pack);
+                             b + off * ctw, (double *)s.dec, nl, (int)k.pack);
         launch_split3(c, s, 0, MainArgs{st, cc, nl, nullptr, nullptr, a + off * ctw, b + off * ctw, 0, 0, 0, c->d_relin, out + off * ctw, 0u,
-                                        kAllSlots, nl, pack});
+                                        kAllSlots, nl, k.pack},
+                      k.main4);
         ABC_HIP_CHECK(hipGetLastError());
         return 0;
       }
     }
-    if (all_fp(c))  // tensor product, inverse transform and the forward transforms of the decomposition in one LDS-resident kernel
+    if (fp)  // tensor product, inverse transform and the forward transforms of the decomposition in one LDS-resident kernel
       hipLaunchKernelGGL(k_fused_tensor_decomp_fp<LB>, dim3((unsigned)(cc * nl)), dim3((1 << LB) / 16), 0, st, c->dc, a + off * ctw,
                          b + off * ctw, s.c01, s.ntt, s.dec, nl);
     else
       hipLaunchKernelGGL(k_fused_tensor_intt<LB>, dim3((unsigned)(cc * nl)), dim3((1 << LB) / 16), 0, st, c->dc, a + off * ctw,
                          b + off * ctw, s.c01, s.coef, s.ntt, nl);
     return keyswitch_stage<LB>(c, st, s, s.coef, (size_t)nl * N, s.ntt, (size_t)nl * N, c->d_relin, s.c01, ctw, true, out + off * ctw, nl,
-                               cc, all_fp(c) ? 1 : 0);
+                               cc, fp, k, fp ? 1 : 0);
   });
 }
 
-// -1: not applicable (ring too large for an LDS-resident limb) -> caller takes the generic path
-int ckks_mul_relin_fused(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out, int nl, size_t count) {
-  if (c->logn == 15 && gsplit_applies(c, nl)) {
-    if (!count) return 0;
-    const size_t ctw = 2 * (size_t)nl * c->n;
-    return run_gsplit15(c, 0, a, b, ctw, ctw, false, c->d_relin, out, nl, count, 0u);
-  }
-  if (c->logn == 15 && !all_fp(c) && isplit_applies(c, nl)) {  // a prime above 2^50: the integer split sequence with 32 blocks
-    if (!count) return 0;
-    const size_t ctw = 2 * (size_t)nl * c->n;
-    return run_isplit(c, 0, a, b, ctw, ctw, false, c->d_relin, out, nl, count, 0u);
-  }
-  if (c->logn > 14) return -1;
-  if (c->sw.no_fused) return -1;
+int launch_mul_relin(abc_hip_ctx *c, Seq seq, const u64 *a, const u64 *b, u64 *out, int nl, size_t count) {
   if (!count) return 0;
-  switch (c->logn) {
-    case 10: return run_mul_relin<10>(c, a, b, out, nl, count);
-    case 11: return run_mul_relin<11>(c, a, b, out, nl, count);
-    case 12: return run_mul_relin<12>(c, a, b, out, nl, count);
-    case 13: return run_mul_relin<13>(c, a, b, out, nl, count);
-    case 14: return run_mul_relin<14>(c, a, b, out, nl, count);
-    default: return -1;
+  const size_t ctw = 2 * (size_t)nl * c->n;
+  switch (seq) {
+    case Seq::gsplit15: return run_gsplit15(c, 0, a, b, ctw, ctw, false, c->d_relin, out, nl, count, 0u);
+    case Seq::isplit: return run_isplit(c, 0, a, b, ctw, ctw, false, c->d_relin, out, nl, count, 0u);
+    case Seq::split14:
+    case Seq::lds_fp:
+    case Seq::lds_int: return dispatch_logn<10, 14>(c->logn, [&](auto LB) { return run_mul_relin<decltype(LB)::value>(c, seq, a, b, out, nl, count); });
+    default: set_error("launch_mul_relin: not a multiply + relinearise sequence of this file"); return 1;
   }
 }
 
-// ---- general key switch: out[ct] = KeySwitch(target[ct]) (+ addend) ----
+// ---- general key switch: out[ct] = KeySwitch(target[ct]) (+ addend): Seq::split14, bsplit14, lds_fp, lds_int ----
 // target: [nl][N] per ciphertext at target + ct*target_stride, in the ciphertext's own form (BFV coefficient, CKKS NTT)
 template <int LB>
-static int run_keyswitch(abc_hip_ctx *c, const u64 *target, size_t target_stride, const u64 *key, u64 *out, int nl, size_t count,
-                         const u64 *addend, size_t addend_stride, bool add_c1, u32 gelt = 0) {
+static int run_keyswitch(abc_hip_ctx *c, Seq seq, const u64 *target, size_t target_stride, const u64 *key, u64 *out, int nl, size_t count,
+                         const u64 *addend, size_t addend_stride, bool add_c1, u32 gelt) {
   const size_t N = (size_t)1 << LB;
   const bool ckks = (c->scheme == 2);
-  if (LB == 14 && ckks && !all_fp(c) && isplit_applies(c, nl))
-    return run_isplit(c, 1, target, addend, target_stride, addend_stride, add_c1, key, out, nl, count, gelt);
-  const ChunkPlan p = plan_chunks(c, nl, count);
+  const ChunkPlan p = plan_chunks(c->facts, nl, count);
   // split sequences (N = 2^14, every key prime below 2^50): CKKS as in run_mul_relin; BFV (coefficient-form operand) the
   // register pass + abc_kernels_gsplit.hip's k_gsplit_special<14, NL, true> (k_bsplit_special8x2 for eight digits) / k_bsplit_tcoef /
   // k_bsplit_finish_big
-  const bool splitc = LB == 14 && ckks && all_fp(c) && !c->sw.no_split && nl <= 12;
-  const bool splitb = LB == 14 && !ckks && !c->sw.no_split && bsplit_applies(c, nl);
+  const bool splitc = seq == Seq::split14, splitb = seq == Seq::bsplit14, fp = seq != Seq::lds_int;
   // BFV rotation (coefficient form): the kernels gather with elt^-1 mod 2N
   const u32 ginv = (!ckks && gelt) ? (u32)host::invmod(gelt, 2 * (uint64_t)N) : 0u;
   if (ginv && !splitb) { set_error("run_keyswitch: a BFV permutation is only folded into the split sequence"); return 1; }
@@ -1330,28 +1255,28 @@ static int run_keyswitch(abc_hip_ctx *c, const u64 *target, size_t target_stride
   // the split kernels read the key's fp64 twin (BFV: the inner-product kernel)
   return for_each_chunk(c, count, p.chunk, p.lanes, per_ct, (splitc || splitb) ? key : nullptr, [&](hipStream_t st, u64 *scratch, size_t off, size_t cc) {
     const FusedScratch s = carve(scratch, p.chunk, nl, SN);
+    const ChunkRoute k = route_chunk(c->facts, seq, nl, cc);
     const u64 *tg = target + off * target_stride;
     const u64 *ad = addend ? addend + off * addend_stride : nullptr;
     u64 *o = out + off * 2 * nl * N;
     if constexpr (LB == 14) {
       if (splitc) {
-        const int pack = pack_half_done(c, nl);
-        if (!c->sw.no_lean_front && cc * nl <= c->sw.lean_limit)
-          gsplit_front14(st, c, cc, nl, 1, tg, nullptr, target_stride, (double *)s.coef, (double *)s.dec, gelt, pack);
+        if (k.lean)
+          gsplit_front14(st, c, cc, nl, 1, tg, nullptr, target_stride, (double *)s.coef, (double *)s.dec, gelt, k.pack);
         else
           hipLaunchKernelGGL((gelt ? k_fused_operand_pass0_fp<LB, true, true> : k_fused_operand_pass0_fp<LB, true, false>),
                              dim3((unsigned)(cc * nl)), dim3((1 << LB) / 16), 0, st, c->dc, tg, target_stride, (double *)s.dec, nl, 0,
-                             gelt, 1 | (pack ? 2 : 0));
+                             gelt, 1 | (k.pack ? 2 : 0));
         launch_split3(c, s, 1, MainArgs{st, cc, nl, nullptr, nullptr, tg, ad, target_stride, addend_stride, add_c1 ? 1 : 0, key, o, gelt,
-                                        kAllSlots, nl, pack});
+                                        kAllSlots, nl, k.pack},
+                      k.main4);
         ABC_HIP_CHECK(hipGetLastError());
         return 0;
       }
       if (splitb) {
-        // few ciphertexts in flight: one workgroup per (ct, J, target I) instead of per (ct, J)
-        const bool per_target = cc * nl < c->sw.pass0_target_limit;
-        hipLaunchKernelGGL((k_fused_operand_pass0_fp<LB, false, false>), dim3((unsigned)(cc * nl * (per_target ? nl + 1 : 1))),
-                           dim3((1 << LB) / 16), 0, st, c->dc, tg, target_stride, (double *)s.dec, nl, per_target ? 1 : 0, ginv, 1);
+        // few ciphertexts in flight (k.per_target): one workgroup per (ct, J, target I) instead of per (ct, J)
+        hipLaunchKernelGGL((k_fused_operand_pass0_fp<LB, false, false>), dim3((unsigned)(cc * nl * (k.per_target ? nl + 1 : 1))),
+                           dim3((1 << LB) / 16), 0, st, c->dc, tg, target_stride, (double *)s.dec, nl, k.per_target ? 1 : 0, ginv, 1);
         // inner product + inverse tails for every key prime, then the register-only finish (a rotation's addend g(c0): gathered there)
         return bsplit_back14(c, st, cc, nl, (const double *)s.dec, (double *)s.ksacc, key, ad, addend_stride, add_c1 ? 1 : 0, o, ginv);
       }
@@ -1360,7 +1285,7 @@ static int run_keyswitch(abc_hip_ctx *c, const u64 *target, size_t target_stride
     const u64 *coef = tg;
     size_t coef_stride = target_stride;
     if (ckks) {  // operand arrives in NTT form: coefficient form via one in-LDS inverse transform per limb
-      if (all_fp(c))
+      if (fp)
         hipLaunchKernelGGL(k_fused_operand_intt_fp<LB>, dim3((unsigned)(cc * nl)), dim3((1 << LB) / 16), 0, st, c->dc, tg,
                            target_stride, s.coef, nl);
       else
@@ -1369,72 +1294,30 @@ static int run_keyswitch(abc_hip_ctx *c, const u64 *target, size_t target_stride
       coef = s.coef;
       coef_stride = (size_t)nl * N;
     }
-    return keyswitch_stage<LB>(c, st, s, coef, coef_stride, tg, target_stride, key, ad, addend_stride, add_c1, o, nl, cc, 0);
+    return keyswitch_stage<LB>(c, st, s, coef, coef_stride, tg, target_stride, key, ad, addend_stride, add_c1, o, nl, cc, fp, k, 0);
   });
 }
 
-// CKKS rotation with the Galois permutation folded into the key switch (N = 2^14, fp64 split path): in [count][2][nl][N]
-// NTT form; out = (g(c0) + ks0, ks1), ks = KeySwitch(g(c1)).  -1: not applicable, caller permutes first.
-int rotate_fused(abc_hip_ctx *c, const u64 *in, u32 elt, const u64 *key, u64 *out, int nl, size_t count) {
-  if (c->logn == 15 && in != out && gsplit_applies(c, nl) && !c->sw.no_galois_fusion) {
-    if (!count) return 0;
-    const size_t pw15 = (size_t)nl * c->n;
-    return run_gsplit15(c, 1, in + pw15, in, 2 * pw15, 2 * pw15, false, key, out, nl, count, elt);
-  }
-  if (c->logn == 15 && c->scheme == 2 && in != out && !all_fp(c) && isplit_applies(c, nl) && !c->sw.no_galois_fusion) {
-    if (!count) return 0;
-    const size_t pw15 = (size_t)nl * c->n;
-    return run_isplit(c, 1, in + pw15, in, 2 * pw15, 2 * pw15, false, key, out, nl, count, elt);
-  }
-  if (c->scheme == 1 && in != out && !c->sw.no_galois_fusion && !c->sw.no_split && !c->sw.no_fused) {
-    // BFV, coefficient form: the signed permutation folded into the first step's load and the last step's addend (fp64 chains)
-    const size_t pwb = (size_t)nl * c->n;
-    if (c->logn == 14 && bsplit_applies(c, nl)) {
-      if (!count) return 0;
-      return run_keyswitch<14>(c, in + pwb, 2 * pwb, key, out, nl, count, in, 2 * pwb, false, elt);
-    }
-    if ((c->logn == 13 || c->logn == 15 || c->logn == 16) && bsplit_big_applies(c, nl)) {
-      if (!count) return 0;
-      return bsplit_big(c, in + pwb, 2 * pwb, key, out, nl, count, in, 2 * pwb, false, (u32)host::invmod(elt, 2 * (uint64_t)c->n));
-    }
-  }
-  if (c->scheme == 1 && in != out && !c->sw.no_galois_fusion && iks_bfv_applies(c, nl) && !bsplit_big_applies(c, nl)) {
-    if (!count) return 0;  // BFV on a big ring with a prime above 2^50: k_iks_pass0 / k_iks_finish gather
-    const size_t pwb = (size_t)nl * c->n;
-    return keyswitch_generic(c, in + pwb, 2 * pwb, key, out, nl, count, in, 2 * pwb, false, (u32)host::invmod(elt, 2 * (uint64_t)c->n));
-  }
-  if (c->logn != 14 || c->scheme != 2 || in == out) return -1;
-  if (!all_fp(c) && !isplit_applies(c, nl)) return -1;
-  if (c->sw.no_split || c->sw.no_fused || c->sw.no_galois_fusion) return -1;
+int launch_keyswitch(abc_hip_ctx *c, const KsRoute &r, const u64 *target, size_t target_stride, const u64 *key, u64 *out, int nl, size_t count,
+                     const u64 *addend, size_t addend_stride, bool add_c1, u32 gelt) {
   if (!count) return 0;
-  const size_t N = (size_t)c->n, pw = (size_t)nl * N;
-  return run_keyswitch<14>(c, in + pw, 2 * pw, key, out, nl, count, in, 2 * pw, false, elt);
-}
-
-int keyswitch_fused(abc_hip_ctx *c, const u64 *target, size_t target_stride, const u64 *key, u64 *out, int nl, size_t count,
-                    const u64 *addend, size_t addend_stride, bool add_c1) {
-  if (c->logn == 15 && gsplit_applies(c, nl)) {
-    if (!count) return 0;
-    return run_gsplit15(c, 1, target, addend, target_stride, addend_stride, add_c1, key, out, nl, count, 0u);
-  }
-  if (c->logn == 15 && c->scheme == 2 && !all_fp(c) && isplit_applies(c, nl)) {
-    if (!count) return 0;
-    return run_isplit(c, 1, target, addend, target_stride, addend_stride, add_c1, key, out, nl, count, 0u);
-  }
-  if (bsplit_big_applies(c, nl)) {  // BFV, N = 2^15 / 2^16, fp64-capable chain
-    if (!count) return 0;
-    return bsplit_big(c, target, target_stride, key, out, nl, count, addend, addend_stride, add_c1);
-  }
-  if (c->logn > 14) return -1;
-  if (c->sw.no_fused) return -1;
-  if (!count) return 0;
-  switch (c->logn) {
-    case 10: return run_keyswitch<10>(c, target, target_stride, key, out, nl, count, addend, addend_stride, add_c1);
-    case 11: return run_keyswitch<11>(c, target, target_stride, key, out, nl, count, addend, addend_stride, add_c1);
-    case 12: return run_keyswitch<12>(c, target, target_stride, key, out, nl, count, addend, addend_stride, add_c1);
-    case 13: return run_keyswitch<13>(c, target, target_stride, key, out, nl, count, addend, addend_stride, add_c1);
-    case 14: return run_keyswitch<14>(c, target, target_stride, key, out, nl, count, addend, addend_stride, add_c1);
-    default: return -1;
+  switch (r.seq) {
+    case Seq::gsplit15: return run_gsplit15(c, 1, target, addend, target_stride, addend_stride, add_c1, key, out, nl, count, gelt);
+    case Seq::isplit: return run_isplit(c, 1, target, addend, target_stride, addend_stride, add_c1, key, out, nl, count, gelt);
+    case Seq::bsplit_big:  // BFV, coefficient form: the signed permutation folded into the first step's load and the last step's addend
+      return bsplit_big(c, target, target_stride, key, out, nl, count, addend, addend_stride, add_c1,
+                        gelt ? (u32)host::invmod(gelt, 2 * (uint64_t)c->n) : 0u);
+    case Seq::generic:
+      return keyswitch_generic(c, r.front, target, target_stride, key, out, nl, count, addend, addend_stride, add_c1,
+                               gelt ? (u32)host::invmod(gelt, 2 * (uint64_t)c->n) : 0u);
+    case Seq::split14:
+    case Seq::bsplit14:
+    case Seq::lds_fp:
+    case Seq::lds_int:
+      return dispatch_logn<10, 14>(c->logn, [&](auto LB) {
+        return run_keyswitch<decltype(LB)::value>(c, r.seq, target, target_stride, key, out, nl, count, addend, addend_stride, add_c1, gelt);
+      });
+    default: set_error("launch_keyswitch: not a key-switch sequence"); return 1;
   }
 }
 

@@ -764,10 +764,6 @@ static void launch_gsplit_back(abc_hip_ctx *c, int mode, const MainArgs &a, doub
 size_t gsplit_scratch_words(const abc_hip_ctx *c, int nl) {
   return ((size_t)nl + (size_t)nl * (nl + 1) + 2 * (size_t)nl + 2) * (size_t)c->dc.ps;
 }
-bool gsplit_applies(const abc_hip_ctx *c, int nl) {
-  if (c->logn != 15 || c->scheme != 2 || !c->use_fp || c->sw.no_gsplit || nl < 1 || nl > 15) return false;
-  return all_key_primes(c, fp_ok);
-}
 // one chunk at N = 2^15: mode 0 multiply (opa = a, opb = b), mode 1 key switch (opa = operand in NTT form, opb = addend)
 int gsplit_chunk15(abc_hip_ctx *c, hipStream_t st, u64 *scratch, size_t cc, int nl, int mode, const u64 *opa, const u64 *opb,
                    size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt) {
@@ -794,10 +790,6 @@ __global__ void k_bsplit_finish_big(DevCtx c, const double *__restrict__ half, c
                                     size_t addend_stride, int add_c1, u64 *__restrict__ out, int nl, u32 ginv);
 
 // half: [cc][nl+1][2] limbs at stride c->dc.ps; part as written by k_fused_operand_pass0_fp<14, false, false> (padded layout)
-bool bsplit_applies(const abc_hip_ctx *c, int nl) {
-  if (c->logn != 14 || c->scheme != 1 || !c->use_fp || c->sw.no_bsplit || nl < 1 || nl > 8) return false;
-  return all_key_primes(c, fp_ok);
-}
 // B2 of the BFV sequences: inner product + inverse tails for every key prime, nl digits
 template <int LOGN>
 static void launch_bsplit_special(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const double *part, const u64 *key, double *half) {
@@ -1108,11 +1100,6 @@ __global__ __launch_bounds__(256) void k_bsplit_finish_lds(DevCtx c, const doubl
 }
 
 // N = 2^13 (BFVDefault(8192): eight 1024-point blocks, radix-8 cross passes in registers) takes the same sequence
-bool bsplit_big_applies(const abc_hip_ctx *c, int nl) {
-  if ((c->logn != 13 && c->logn != 15 && c->logn != 16) || c->scheme != 1 || !c->use_fp || c->sw.no_bsplit || c->sw.no_gsplit || nl < 1 || nl > 8) return false;
-  return all_key_primes(c, fp_ok);
-}
-
 template <int LOGN>
 static int bsplit_big_chunk(abc_hip_ctx *c, hipStream_t st, double *scratch, size_t cc, int nl, const u64 *target, size_t target_stride,
                             const u64 *key, const u64 *addend, size_t addend_stride, int add_c1, u64 *out, u32 ginv = 0) {

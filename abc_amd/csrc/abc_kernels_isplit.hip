@@ -616,22 +616,13 @@ size_t isplit_scratch_words(const abc_hip_ctx *c, int nl) {
   return ((size_t)nl * (nl + 1) + 2 * (size_t)nl + 2 + (c->logn == 15 ? (size_t)nl : 0)) * (size_t)c->dc.ps;
 }
 
-bool isplit_applies(const abc_hip_ctx *c, int nl) {
-  if ((c->logn != 14 && c->logn != 15) || c->scheme != 2 || c->sw.no_fused || c->sw.no_split || c->sw.no_isplit || nl < 1 ||
-      nl > (c->logn == 15 ? 15 : 7))
-    return false;
-  if (c->logn == 15 && c->sw.no_gsplit) return false;  // one switch turns both split sequences of that ring off (A/B, tests)
-  return all_key_primes(c, [](u32 bits) { return bits <= 60; });
-}
-
 // one chunk of a multiply (mode 0: opa = a, opb = b) or of a key switch (mode 1: opa = operand in NTT form, opb = addend)
 int isplit_chunk(abc_hip_ctx *c, hipStream_t st, u64 *scratch, size_t cc, int nl, int mode, const u64 *opa, const u64 *opb,
-                 size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt) {
+                 size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt, const ChunkRoute &k) {
   const size_t PS = (size_t)c->dc.ps;
   u64 *part = scratch, *tpart = part + cc * (size_t)nl * (nl + 1) * PS, *tsp = tpart + cc * 2 * (size_t)nl * PS;
-  const bool guard = !all_key_primes(c, unguarded_ok);
-  // data primes below 2^50 take the fp64 kernels (ABC_HIP_NO_FP64 / ABC_HIP_NO_MIXED: integers throughout)
-  const u32 fpmask = (c->use_fp && !c->sw.no_mixed) ? data_prime_mask(c, nl, fp_ok) : 0u;
+  const bool guard = k.guard;
+  const u32 fpmask = k.fpmask;  // data primes below 2^50 take the fp64 kernels (ABC_HIP_NO_FP64 / ABC_HIP_NO_MIXED: integers throughout)
   const MainArgs a{st, cc, nl, part, tpart, opa, opb, opa_stride, opb_stride, add_c1, key, out, gelt, kAllSlots, nl, 0};
   auto with_guard = [&](auto GD) {
     constexpr bool GUARD = decltype(GD)::value;

@@ -322,7 +322,7 @@ static int launch_ntt(abc_hip_ctx *c, u64 *d, const LimbMap &map, int nl, size_t
 // Key-switch decomposition for N > 2^14, fp64 primes: the strided pass reads operand limb J once per target prime I
 // straight from the operand (no reduction modulo q_I is needed in fp64) and writes the half-done limb (ct, J, I), the
 // block kernel finishes it -- the separate expand kernel and its round trip disappear.
-// dec[ct][J][I] for I <= nl (I = nl: the special prime).  -1: not applicable.
+// dec[ct][J][I] for I <= nl (I = nl: the special prime).  KsFront::fp (abc_route.hpp).
 template <int R>
 __global__ __launch_bounds__(256) void k_ks_expand_strided_fp(DevCtx c, const u64 *__restrict__ tcoef, size_t tstride,
                                                               u64 *__restrict__ dec, LimbMap map, int nl) {
@@ -358,7 +358,7 @@ __global__ __launch_bounds__(256) void k_ks_expand_strided_fp(DevCtx c, const u6
   for (int k = 0; k < (1 << R); k++) dst[(size_t)k * G] = x[k];
 }
 int launch_ks_expand_ntt_fp(abc_hip_ctx *c, const u64 *tcoef, size_t tstride, u64 *dec, const LimbMap &map, int nl, size_t count) {
-  if (c->logn <= 14 || !all_limbs_fp(c, map, nl + 1)) return -1;
+  if (c->logn <= 14 || !all_limbs_fp(c, map, nl + 1)) { set_error("fp64 key-switch expansion: N > 2^14 and fp64-capable primes only"); return 1; }
   const int S0 = c->logn - kBigBlockLB;
   const size_t limbs = count * nl * (nl + 1);
   const int G = c->n >> S0;

@@ -1,0 +1,310 @@
+// abc_route.hpp -- which kernel sequence a call takes.  Plain C++17: no HIP header, no pointer to device memory, so the whole
+// table runs in a host test (tests/cpp/test_route.cpp) and behind abc_hip_route.
+//
+// One pure function per operation maps (context facts, switches, nl, aliasing) to a named route; one more maps (route, nl,
+// ciphertexts in the chunk) to the per-chunk choices.  The dispatchers (abc_context.hip, abc_kernels_fused.hip,
+// abc_kernels_eval.hip, abc_kernels_bfv.hip) switch over the result and decide nothing themselves.  DESIGN.md section 3b holds
+// the same table in prose, with the strings format() writes.
+//
+// Not part of a route: whether a key's fp64 twin or Shoup mirror exists.  That is a property of a buffer (ABC_HIP_NO_KEY_TWIN and
+// allocation success, key_twin_lookup in abc_buffers.hip), looked up at the launch; the kernels take either form.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+
+namespace abc {
+
+// Path switches (A/B timing and the parity tests of every fallback): the ABC_HIP_* environment variables are read ONCE, when
+// the context is created (abc_hip_ctx_reload_env re-reads them), never on the per-operation path.
+struct Switches {
+  bool no_fused = false, no_split = false, no_split4 = false, no_isplit = false, no_gsplit = false, no_lean_front = false, no_bsplit = false, no_mixed = false, no_pack = false, no_key_twin = false, no_bmul = false, no_iks = false, no_tensor_intt = false;
+  bool no_galois_fusion = false;
+  size_t chunk = 0, few_limbs = 48, lean_limit = 96, bfv_scratch_mb = 0, pass0_target_limit = 128;
+  int lanes = 2;
+};
+
+// prime widths the kernels are exact for (abc_ntt.hpp: fp_ok, unguarded_ok)
+constexpr unsigned kFpBits = 50;         // fp64 transforms
+constexpr unsigned kLazyBits = 55;       // 4 products of a (< 64q) operand with a key residue stay below 2^(k+63)
+constexpr unsigned kUnguardedBits = 57;  // unguarded butterflies: 64 q <= 2^64
+constexpr unsigned kIsplitBits = 60;     // the integer split kernels
+
+// scratch limbs per ciphertext of the LDS-resident and N = 2^14 split sequences (carve, abc_kernels_fused.hip)
+constexpr size_t fused_scratch_limbs(int nl) { return (size_t)nl * (nl + 1) + 6 * (size_t)nl + 4; }
+
+// Everything a route depends on besides the call's own arguments.  Filled when the context is created and by
+// abc_hip_ctx_reload_env (primes never change afterwards); finish() derives what the routes ask per call.
+struct RouteFacts {
+  int scheme = 0, logn = 0, K = 0, L = 0, nB = 0;  // scheme 1 BFV, 2 CKKS; K key primes (bits[K-1]: the special prime), L data limbs
+  bool use_fp = true, behz_fp = false;
+  int big_block_log = 12;
+  unsigned char bits[17] = {};  // width of key prime j
+  Switches sw;
+  // derived
+  unsigned widest = 0;   // widest key prime
+  uint32_t fp_mask = 0;  // bit j: key prime j is fp64-capable (whatever use_fp says)
+  bool all_fp = false;   // fp64 transforms throughout: use_fp and every key prime below 2^50
+  bool guard = false;    // some key prime needs the guarded butterflies
+  bool lazy = false;     // unguarded, and the inner product may accumulate lazily
+  void finish() {
+    widest = 0;
+    fp_mask = 0;
+    for (int j = 0; j < K; j++) {
+      if (bits[j] > widest) widest = bits[j];
+      if (bits[j] <= kFpBits) fp_mask |= 1u << j;
+    }
+    all_fp = use_fp && widest <= kFpBits;
+    guard = widest > kUnguardedBits;
+    lazy = widest <= kLazyBits;
+  }
+  uint32_t fp_data_mask(int nl) const { return fp_mask & ((1u << nl) - 1u); }  // the first nl data primes
+  bool data_fp(int nl) const { return fp_data_mask(nl) == (1u << nl) - 1u; }
+  bool special_fp() const { return K > 0 && ((fp_mask >> (K - 1)) & 1u); }
+};
+
+// ---- the sequences ----
+enum class Seq {
+  split14,     // CKKS, N = 2^14, fp64: tensor / operand pass 0 (lean or fat), special, pass, main (split4 or split3)
+  gsplit15,    // CKKS, N = 2^15, fp64 (abc_kernels_gsplit.hip)
+  isplit,      // CKKS, N = 2^14 / 2^15, a prime above 2^50: integer split kernels, fp64 for the limbs in fpmask (abc_kernels_isplit.hip)
+  bsplit14,    // BFV, N = 2^14, fp64: operand pass 0 + bsplit_back14
+  bsplit_big,  // BFV, N = 2^13 / 2^15 / 2^16, fp64 (bsplit_big)
+  lds_fp,      // LDS-resident limbs, fp64
+  lds_int,     // LDS-resident limbs, integers (guard / lazy)
+  bmul,        // BFV multiply + relinearise in one split sequence (abc_kernels_bmul.hip)
+  generic      // the one-kernel-per-step sequences (abc_kernels_eval.hip, abc_kernels_bfv.hip)
+};
+enum class KsFront { plain, fp, iks };     // generic key switch: k_ks_expand + transforms / fp64 strided expand / k_iks_pass0 + k_iks_special
+enum class BfvMul { behz, split, big };    // BFV multiply alone: generic BEHZ kernels / bmul_split on lanes (2^14) / bmul_big
+enum class Rescale { generic, fp, mixed };
+
+struct KsRoute {
+  Seq seq;
+  KsFront front;  // seq == generic only
+};
+struct MulRoute {
+  Seq seq;
+  BfvMul mul;  // seq == generic on BFV: how the size-3 product is formed (CKKS: launch_ckks_tensor)
+  KsRoute ks;  // seq == generic: the key switch that follows
+};
+struct RotRoute {
+  bool fold;  // the permutation is folded into the key switch `ks`; otherwise k_galois first, then `ks`
+  KsRoute ks;
+};
+struct RescaleRoute {
+  Rescale kind;
+  uint32_t fpmask;  // mixed: limbs that take the fp64 butterflies
+};
+
+namespace route_detail {
+inline bool gsplit_ok(const RouteFacts &f, int nl) {
+  return f.logn == 15 && f.scheme == 2 && f.use_fp && !f.sw.no_gsplit && nl >= 1 && nl <= 15 && f.widest <= kFpBits;
+}
+inline bool bsplit_ok(const RouteFacts &f, int nl) {
+  return f.logn == 14 && f.scheme == 1 && f.use_fp && !f.sw.no_bsplit && nl >= 1 && nl <= 8 && f.widest <= kFpBits;
+}
+inline bool bsplit_big_ok(const RouteFacts &f, int nl) {
+  return (f.logn == 13 || f.logn == 15 || f.logn == 16) && f.scheme == 1 && f.use_fp && !f.sw.no_bsplit && !f.sw.no_gsplit && nl >= 1 &&
+         nl <= 8 && f.widest <= kFpBits;
+}
+inline bool isplit_ok(const RouteFacts &f, int nl) {
+  if ((f.logn != 14 && f.logn != 15) || f.scheme != 2 || f.sw.no_fused || f.sw.no_split || f.sw.no_isplit || nl < 1 ||
+      nl > (f.logn == 15 ? 15 : 7))
+    return false;
+  if (f.logn == 15 && f.sw.no_gsplit) return false;  // one switch turns both split sequences of that ring off (A/B, tests)
+  return f.widest <= kIsplitBits;
+}
+inline bool bmul_shape(const RouteFacts &f, int limbs) {
+  return f.scheme == 1 && f.use_fp && f.behz_fp && !f.sw.no_bmul && !f.sw.no_split && !f.sw.no_fused && f.L == limbs && f.nB == limbs &&
+         f.K == f.L + 1;
+}
+inline bool bmul_relin_ok(const RouteFacts &f) {
+  if (f.logn == 13) return bmul_shape(f, 4) && bsplit_big_ok(f, f.L);  // BFVDefault(8192)
+  return f.logn == 14 && bmul_shape(f, 8) && bsplit_ok(f, f.L);
+}
+// the choice among the sequences with LDS-resident or N = 2^14 split limbs (rings 2^10 .. 2^14)
+inline Seq lds_seq(const RouteFacts &f, int nl, bool mul) {
+  const bool ckks = f.scheme == 2;
+  if (f.logn == 14 && ckks && !f.all_fp && isplit_ok(f, nl)) return Seq::isplit;
+  if (f.logn == 14 && ckks && f.all_fp && !f.sw.no_split && nl <= 12) return Seq::split14;
+  if (!mul && f.logn == 14 && !ckks && !f.sw.no_split && bsplit_ok(f, nl)) return Seq::bsplit14;
+  return f.all_fp ? Seq::lds_fp : Seq::lds_int;
+}
+}  // namespace route_detail
+
+// the front of the generic key switch at level nl
+inline KsFront route_ks_front(const RouteFacts &f, int nl) {
+  if (f.logn > 14 && f.use_fp && f.data_fp(nl) && f.special_fp()) return KsFront::fp;
+  if ((f.logn == 15 || f.logn == 16) && !f.sw.no_iks && f.big_block_log == 12) return KsFront::iks;
+  return KsFront::plain;
+}
+
+// relinearise and plain key switch
+inline KsRoute route_keyswitch(const RouteFacts &f, int nl) {
+  using namespace route_detail;
+  const KsRoute generic{Seq::generic, route_ks_front(f, nl)};
+  if (f.logn == 15 && gsplit_ok(f, nl)) return {Seq::gsplit15, KsFront::plain};
+  if (f.logn == 15 && f.scheme == 2 && !f.all_fp && isplit_ok(f, nl)) return {Seq::isplit, KsFront::plain};
+  if (bsplit_big_ok(f, nl)) return {Seq::bsplit_big, KsFront::plain};
+  if (f.logn > 14 || f.logn < 10 || f.sw.no_fused) return generic;
+  return {lds_seq(f, nl, false), KsFront::plain};
+}
+
+inline BfvMul route_bfv_multiply(const RouteFacts &f) {
+  using namespace route_detail;
+  if (f.logn == 14) return bmul_relin_ok(f) ? BfvMul::split : BfvMul::behz;
+  if (f.logn == 13) return bmul_shape(f, 4) ? BfvMul::big : BfvMul::behz;
+  return ((f.logn == 15 || f.logn == 16) && bmul_shape(f, 8) && !f.sw.no_gsplit && f.big_block_log == 12) ? BfvMul::big : BfvMul::behz;
+}
+
+inline MulRoute route_mul_relin(const RouteFacts &f, int nl) {
+  using namespace route_detail;
+  const KsRoute none{Seq::generic, KsFront::plain};
+  if (f.scheme == 2) {
+    if (f.logn == 15 && gsplit_ok(f, nl)) return {Seq::gsplit15, BfvMul::behz, none};
+    if (f.logn == 15 && !f.all_fp && isplit_ok(f, nl)) return {Seq::isplit, BfvMul::behz, none};
+    if (f.logn <= 14 && f.logn >= 10 && !f.sw.no_fused) return {lds_seq(f, nl, true), BfvMul::behz, none};
+    return {Seq::generic, BfvMul::behz, route_keyswitch(f, nl)};
+  }
+  if (bmul_relin_ok(f)) return {Seq::bmul, BfvMul::split, none};
+  return {Seq::generic, route_bfv_multiply(f), route_keyswitch(f, nl)};
+}
+
+// one Galois element at level nl
+inline RotRoute route_rotate(const RouteFacts &f, int nl, bool in_place) {
+  using namespace route_detail;
+  const bool may_fold = !in_place && !f.sw.no_galois_fusion;
+  if (may_fold && f.logn == 15 && gsplit_ok(f, nl)) return {true, {Seq::gsplit15, KsFront::plain}};
+  if (may_fold && f.logn == 15 && f.scheme == 2 && !f.all_fp && isplit_ok(f, nl)) return {true, {Seq::isplit, KsFront::plain}};
+  if (may_fold && f.scheme == 1) {
+    if (!f.sw.no_split && !f.sw.no_fused) {
+      if (f.logn == 14 && bsplit_ok(f, nl)) return {true, {Seq::bsplit14, KsFront::plain}};
+      if (bsplit_big_ok(f, nl)) return {true, {Seq::bsplit_big, KsFront::plain}};
+    }
+    // a big ring with a prime above 2^50: k_iks_pass0 / k_iks_finish gather
+    if ((f.logn == 15 || f.logn == 16) && route_ks_front(f, nl) == KsFront::iks && !bsplit_big_ok(f, nl)) return {true, {Seq::generic, KsFront::iks}};
+  }
+  if (may_fold && f.logn == 14 && f.scheme == 2 && (f.all_fp || isplit_ok(f, nl)) && !f.sw.no_split && !f.sw.no_fused)
+    return {true, {lds_seq(f, nl, false), KsFront::plain}};
+  return {false, route_keyswitch(f, nl)};
+}
+
+inline RescaleRoute route_rescale(const RouteFacts &f, int nl, bool in_place) {
+  if (f.logn > 14 || f.logn < 10 || in_place || f.sw.no_fused) return {Rescale::generic, 0u};
+  if (f.use_fp && f.data_fp(nl)) return {Rescale::fp, 0u};
+  if (f.sw.no_isplit) return {Rescale::generic, 0u};
+  return {Rescale::mixed, (f.use_fp && !f.sw.no_mixed) ? f.fp_data_mask(nl) : 0u};  // a prime above 2^50 in the chain
+}
+
+// ---- per chunk ----
+struct ChunkPlan {
+  size_t chunk;
+  int lanes;
+};
+// Chunks alternate between two internal streams so that the HBM-streaming kernels of one chunk overlap the ALU-bound
+// transforms of the other; measured on MI355X: 256-pair chunks on two lanes beat one 512-pair chunk per lane.
+inline ChunkPlan plan_chunks(const RouteFacts &f, int nl, size_t count) {
+  ChunkPlan p{f.sw.chunk, f.sw.lanes};
+  if (count <= 8) p.lanes = 1;
+  if (!p.chunk) {
+    const size_t per_ct_bytes = fused_scratch_limbs(nl) * ((size_t)1 << f.logn) * 8;
+    const size_t cap = ((size_t)4 << 30) / per_ct_bytes / (size_t)p.lanes;  // scratch capped at 4 GiB
+    p.chunk = (count + p.lanes - 1) / p.lanes;
+    if (p.chunk > 128) p.chunk = 128;  // measured: 128 > 256 > 64 > 512 (+2 / 0 / -0.5 / -1.5 %)
+    if (p.chunk > cap) p.chunk = cap;
+    if (p.chunk < 1) p.chunk = 1;
+  }
+  if (p.chunk > count) p.chunk = count;
+  return p;
+}
+// the choices that depend on the cc ciphertexts of one chunk (a ragged last chunk may differ from the others); fields a
+// sequence does not read stay false / 0
+struct ChunkRoute {
+  bool lean = false;        // split14: block-wise front (gsplit_front14) instead of the 139 KiB tensor / operand kernel
+  bool pack = false;        // split14: packed half-done limbs (abc_ntt.hpp); only k_split4_main_fp reads them
+  bool main4 = false;       // split14: k_split4_main_fp, else k_split3_main_fp
+  bool per_target = false;  // bsplit14: one workgroup per (ct, J, target I) in pass 0
+  bool guard = false, lazy = false;  // lds_int, isplit
+  bool fp_twin = false;     // isplit: the fp64 limbs' main step is k_split4_main_fp, which wants the key's fp64 twin built
+  uint32_t fpmask = 0;      // isplit: data limbs on the fp64 kernels
+};
+inline ChunkRoute route_chunk(const RouteFacts &f, Seq seq, int nl, size_t cc) {
+  ChunkRoute k;
+  switch (seq) {
+    case Seq::split14:
+      // few ciphertexts in flight: the 139 KiB workgroups of the tensor kernel would leave most CUs idle for its whole
+      // duration (measured at nl = 4: +5 % at 16 pairs, even at 32, -5 % at 48)
+      k.lean = !f.sw.no_lean_front && cc * nl <= f.sw.lean_limit;
+      // (measured at nl = 5 / 6 / 7, every prime below 2^50: +9.5 / -5 / -14 % against k_split3_main_fp: above five limbs the
+      // prefetched key words push the kernel past 128 VGPRs and to one workgroup per CU)
+      k.main4 = !f.sw.no_split4 && nl >= 1 && nl <= 5;
+      k.pack = k.main4 && !f.sw.no_pack;
+      break;
+    case Seq::bsplit14: k.per_target = cc * nl < f.sw.pass0_target_limit; break;
+    case Seq::lds_int:
+      k.guard = f.guard;
+      k.lazy = f.lazy;
+      break;
+    case Seq::isplit:
+      k.guard = f.guard;
+      k.fp_twin = f.logn == 14 && !f.sw.no_mixed;
+      k.fpmask = (f.use_fp && !f.sw.no_mixed) ? f.fp_data_mask(nl) : 0u;
+      break;
+    default: break;
+  }
+  return k;
+}
+
+// ---- names, and a route as a short string, e.g. "split14 front=lean pack=1 main=split4" (tests and DESIGN.md quote these) ----
+inline const char *name(Seq s) {
+  constexpr const char *names[] = {"split14", "gsplit15", "isplit", "bsplit14", "bsplit_big", "lds_fp", "lds_int", "bmul", "generic"};
+  return names[(int)s];
+}
+inline const char *name(KsFront k) { return k == KsFront::fp ? "fp" : k == KsFront::iks ? "iks" : "plain"; }
+inline const char *name(BfvMul m) { return m == BfvMul::split ? "bmul" : m == BfvMul::big ? "bmul_big" : "behz"; }
+inline const char *name(Rescale r) { return r == Rescale::fp ? "fp" : r == Rescale::mixed ? "mixed" : "generic"; }
+
+// the key switch r of a call of `count` ciphertexts (per-chunk fields: its first chunk) into buf
+inline void format_ks(char *buf, size_t cap, const RouteFacts &f, const KsRoute &r, int nl, size_t count) {
+  const ChunkRoute k = route_chunk(f, r.seq, nl, plan_chunks(f, nl, count).chunk);
+  switch (r.seq) {
+    case Seq::split14: snprintf(buf, cap, "split14 front=%s pack=%d main=%s", k.lean ? "lean" : "fat", (int)k.pack, k.main4 ? "split4" : "split3"); break;
+    case Seq::isplit: snprintf(buf, cap, "isplit%d guard=%d fpmask=0x%x", f.logn, (int)k.guard, (unsigned)k.fpmask); break;
+    case Seq::bsplit14: snprintf(buf, cap, "bsplit14 pass0=%s", k.per_target ? "per_target" : "per_limb"); break;
+    case Seq::lds_int: snprintf(buf, cap, "lds_int guard=%d lazy=%d", (int)k.guard, (int)k.lazy); break;
+    case Seq::generic:
+      if (r.front == KsFront::iks) snprintf(buf, cap, "generic front=iks guard=%d", (int)f.guard);
+      else snprintf(buf, cap, "generic front=%s", name(r.front));
+      break;
+    default: snprintf(buf, cap, "%s", name(r.seq)); break;
+  }
+}
+// The route of one call into buf: what abc_hip_route returns.  op: include/abc_hip.h, ABC_HIP_ROUTE_*.  Returns the length,
+// -1 if cap is too small, -2 for an unknown op.
+enum RouteOp { kRouteMulRelin = 0, kRouteKeyswitch = 1, kRouteRotate = 2, kRouteRescale = 3, kRouteMultiply = 4 };
+inline int format_op(char *buf, size_t cap, const RouteFacts &f, int op, int nl, size_t count, bool in_place) {
+  char ks[80];
+  int n = -2;
+  if (op == kRouteMulRelin) {
+    const MulRoute r = route_mul_relin(f, nl);
+    format_ks(ks, sizeof ks, f, r.seq == Seq::generic ? r.ks : KsRoute{r.seq, KsFront::plain}, nl, count);
+    n = r.seq == Seq::generic ? snprintf(buf, cap, "generic mul=%s ks=%s", f.scheme == 2 ? "tensor" : name(r.mul), ks) : snprintf(buf, cap, "%s", ks);
+  } else if (op == kRouteKeyswitch) {
+    format_ks(ks, sizeof ks, f, route_keyswitch(f, nl), nl, count);
+    n = snprintf(buf, cap, "%s", ks);
+  } else if (op == kRouteRotate) {
+    const RotRoute r = route_rotate(f, nl, in_place);
+    format_ks(ks, sizeof ks, f, r.ks, nl, count);
+    n = snprintf(buf, cap, "%s %s", r.fold ? "fold" : "permute", ks);
+  } else if (op == kRouteRescale) {
+    const RescaleRoute r = route_rescale(f, nl, in_place);
+    n = r.kind == Rescale::mixed ? snprintf(buf, cap, "mixed fpmask=0x%x", (unsigned)r.fpmask) : snprintf(buf, cap, "%s", name(r.kind));
+  } else if (op == kRouteMultiply) {
+    n = snprintf(buf, cap, "%s", f.scheme == 1 ? name(route_bfv_multiply(f)) : "tensor");
+  }
+  return n < 0 ? n : (size_t)n < cap ? n : -1;
+}
+
+}  // namespace abc

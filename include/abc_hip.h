@@ -63,6 +63,17 @@ int abc_hip_sync(abc_hip_ctx *ctx);
 /* The ABC_HIP_* path switches (README) are read when the context is created, not per operation; this re-reads them
  * (drains the stream first).  For A/B timing and the parity tests of the fallback paths. */
 int abc_hip_ctx_reload_env(abc_hip_ctx *ctx);
+/* Which kernel sequence a call of `count` ciphertexts at level nl takes (the route table: DESIGN.md section 3b), written
+ * to buf as a short string such as "split14 front=lean pack=1 main=split4"; per-chunk fields are those of the first
+ * chunk.  in_place: d_out aliases d_in (rotate, rescale).  Read-only: allocates nothing, launches nothing, touches no
+ * stream (legal inside abc_hip_graph_begin..end).  nl is checked as the operation itself checks it (BFV: nl = L for every
+ * op, multiply included; rescale: CKKS and nl >= 2).  Non-zero on a bad op / nl or a buffer too small (80 bytes hold any). */
+#define ABC_HIP_ROUTE_MUL_RELIN 0
+#define ABC_HIP_ROUTE_KEYSWITCH 1 /* relinearize, keyswitch */
+#define ABC_HIP_ROUTE_ROTATE 2    /* one Galois element */
+#define ABC_HIP_ROUTE_RESCALE 3
+#define ABC_HIP_ROUTE_MULTIPLY 4
+int abc_hip_route(abc_hip_ctx *ctx, int op, int nl, size_t count, int in_place, char *buf, size_t cap);
 
 /* ---- device memory (so that FFI callers need no HIP runtime binding) ----
  * Freed buffers are cached per context and recycled by size, so a buffer may be freed right after the last operation

@@ -26,6 +26,69 @@ VARIANTS = {
 }
 
 
+# What each variant must make the dispatcher choose (the strings of abc_route.hpp / DESIGN.md section 3b): without this a switch
+# that stopped selecting its path would leave every parity test green.  CKKS, N = 2^14, chain [50, 40, 40, 40, 50]: (mul_relin,
+# rotate, rescale); the same at every level 1 .. 4 and for the batches used here (at most 24 (ciphertext, limb) pairs per chunk).
+_SPLIT = "split14 front=%s pack=%d main=%s"
+EXPECTED_ROUTE = {
+    "default": (_SPLIT % ("lean", 1, "split4"), "fold " + _SPLIT % ("lean", 1, "split4"), "fp"),
+    "integer_transforms": ("isplit14 guard=0 fpmask=0x0", "fold isplit14 guard=0 fpmask=0x0", "mixed fpmask=0x0"),
+    "integer_v1": ("lds_int guard=0 lazy=1", "permute lds_int guard=0 lazy=1", "generic"),
+    "fp64_unsplit": ("lds_fp", "permute lds_fp", "fp"),
+    "fp64_fat_front": (_SPLIT % ("fat", 1, "split4"), "fold " + _SPLIT % ("fat", 1, "split4"), "fp"),
+    "fp64_unpacked": (_SPLIT % ("lean", 0, "split4"), "fold " + _SPLIT % ("lean", 0, "split4"), "fp"),
+    "fp64_unpacked_fat_front": (_SPLIT % ("fat", 0, "split4"), "fold " + _SPLIT % ("fat", 0, "split4"), "fp"),
+    "fp64_u64_keys": (_SPLIT % ("lean", 1, "split4"), "fold " + _SPLIT % ("lean", 1, "split4"), "fp"),  # differs in the key mirror, not the route
+    "fp64_split3_main": (_SPLIT % ("lean", 0, "split3"), "fold " + _SPLIT % ("lean", 0, "split3"), "fp"),
+    "generic": ("generic mul=tensor ks=generic front=plain", "permute generic front=plain", "generic"),
+    "no_galois_fusion_sync_alloc": (_SPLIT % ("lean", 1, "split4"), "permute " + _SPLIT % ("lean", 1, "split4"), "fp"),
+}
+# BFVDefault(16384), one ciphertext (8 limbs: below the per-target limit of pass 0): (mul_relin, rotate, multiply)
+_B14 = "bsplit14 pass0=per_target"
+EXPECTED_ROUTE_BFV14 = {
+    "default": ("bmul", "fold " + _B14, "bmul"),
+    "bfv_unsplit_multiply": ("generic mul=behz ks=" + _B14, "fold " + _B14, "behz"),
+    "bfv_v1_keyswitch": ("generic mul=behz ks=lds_fp", "permute lds_fp", "behz"),
+    "bfv_separate_permutation": ("bmul", "permute " + _B14, "bmul"),
+    "bfv_seal_aux_base": ("generic mul=behz ks=" + _B14, "fold " + _B14, "behz"),  # the split multiply needs the 50-bit auxiliary base
+    "bfv_int_behz_kernels": ("generic mul=behz ks=" + _B14, "fold " + _B14, "behz"),  # ... and its fp64 base-conversion kernels
+    "integer_transforms": ("generic mul=behz ks=lds_int guard=0 lazy=1", "permute lds_int guard=0 lazy=1", "behz"),
+    "fp64_unsplit": ("generic mul=behz ks=lds_fp", "permute lds_fp", "behz"),  # on BFV the same sequences as bfv_v1_keyswitch
+}
+# BFVDefault(8192): (mul_relin, rotate, multiply, relinearize)
+EXPECTED_ROUTE_BFV13 = {
+    "default": ("bmul", "fold bsplit_big", "bmul_big", "bsplit_big"),
+    "bfv_unsplit_multiply": ("generic mul=behz ks=bsplit_big", "fold bsplit_big", "behz", "bsplit_big"),
+    "bfv_v1_keyswitch": ("generic mul=bmul_big ks=lds_fp", "permute lds_fp", "bmul_big", "lds_fp"),
+    "bfv_separate_permutation": ("bmul", "permute bsplit_big", "bmul_big", "bsplit_big"),
+    "bfv_seal_aux_base": ("generic mul=behz ks=bsplit_big", "fold bsplit_big", "behz", "bsplit_big"),
+    "integer_transforms": ("generic mul=behz ks=lds_int guard=0 lazy=1", "permute lds_int guard=0 lazy=1", "behz", "lds_int guard=0 lazy=1"),
+}
+
+
+def test_variants_meant_to_differ_have_different_routes():
+    """no GPU work: the tables above.  fp64_u64_keys (key mirror) and the SYNC_ALLOC half of no_galois_fusion_sync_alloc differ
+    outside the route; on BFV, NO_SPLIT and NO_BSPLIT select the same sequences, and leaving the fp64 BEHZ base (either way) selects
+    what NO_BMUL selects -- the generic multiply, whose own kernels then differ by base, a per-launch choice outside the route."""
+    same_on_purpose = [{"default", "fp64_u64_keys"}, {"bfv_v1_keyswitch", "fp64_unsplit"},
+                       {"bfv_unsplit_multiply", "bfv_seal_aux_base", "bfv_int_behz_kernels"}]
+    for table in (EXPECTED_ROUTE, EXPECTED_ROUTE_BFV14, EXPECTED_ROUTE_BFV13):
+        names = list(table)
+        for i, a in enumerate(names):
+            for b in names[i + 1:]:
+                if not any({a, b} <= group for group in same_on_purpose):
+                    assert table[a] != table[b], (a, b)
+    assert EXPECTED_ROUTE["no_galois_fusion_sync_alloc"][0] == EXPECTED_ROUTE["default"][0]  # only the rotation differs
+
+
+def _check_routes(g, variant, nl, count=1, rescale=False):
+    mul, rot, resc = EXPECTED_ROUTE[variant]
+    assert g.route("mul_relin", nl, count) == mul, (variant, nl, count)
+    assert g.route("rotate", nl, count) == rot, (variant, nl, count)
+    if rescale:
+        assert g.route("rescale", nl, count) == resc, (variant, nl)
+
+
 def _same(name, got, want):
     got, want = np.asarray(got), np.asarray(want)
     assert got.shape == want.shape, name
@@ -77,6 +140,9 @@ def test_ckks14_paths_bit_exact(variant, oracle14, capi, monkeypatch):
     g = capi.Context(capi.CKKS, o.n, primes)  # ABC_HIP_NO_FP64 is read when the context is built
     g.load_keys(sk=o.secret_key(), pk=o.public_key(), relin=o.relin_key(),
                 galois={e: o.galois_key(e) for e in o.galois_elts()})
+    _check_routes(g, variant, 4)
+    _check_routes(g, variant, 3)
+    _check_routes(g, variant, 4, count=5)
     _same(variant + " mul_relin", g.mul_relin(ins["cx"], ins["cy"]), want["mul"])
     _same(variant + " mul_relin extreme residues", g.mul_relin(ins["ex"], ins["ey"]), want["mul_extreme"])
     _same(variant + " rotate", g.rotate(ins["cx"], -7), want["rot"])
@@ -105,6 +171,8 @@ def test_ckks14_every_level_bit_exact(variant, oracle14, capi, monkeypatch):
     x, y = ins["cx"], ins["cy"]
     for level in (4, 3, 2, 1):
         assert x.shape[1] == level
+        _check_routes(g, variant, level, rescale=level > 1)
+        _check_routes(g, variant, level, count=3, rescale=level > 1)
         _same("%s mul_relin at level %d" % (variant, level), g.mul_relin(x, y), o.mul_relin(x, y))
         _same("%s rotate at level %d" % (variant, level), g.rotate(x, 5), o.rotate(x, 5))
         if level > 1:
@@ -135,6 +203,10 @@ def test_bfv14_keyswitch_paths_bit_exact(variant, oracle_mod, capi, monkeypatch)
                 galois={e: o.galois_key(e) for e in o.galois_elts()})
     rng = np.random.default_rng(5)
     nl = len(o.primes) - 1
+    mul, rot, mult = EXPECTED_ROUTE_BFV14[variant]
+    assert (g.route("mul_relin", nl), g.route("rotate", nl), g.route("multiply", nl)) == (mul, rot, mult)
+    # 40 ciphertexts: 20 per chunk on two lanes, 160 (ciphertext, limb) pairs: pass 0 of the split key switch per limb
+    assert g.route("mul_relin", nl, 40) == mul.replace("per_target", "per_limb") and g.route("rotate", nl, 40) == rot.replace("per_target", "per_limb")
     ex = _extreme_ct(o.primes, nl, o.n, rng)
     _same(variant + " bfv rotate extreme", g.rotate(ex, 1), o.rotate(ex, 1))
     ct = o.encrypt(o.encode(oracle_mod.expand_vector([3, 1, 4, 1, 5], o.n)), 9)
@@ -173,6 +245,9 @@ def test_bfv13_split_paths_bit_exact(variant, oracle_mod, capi, monkeypatch):
                 galois={e: o.galois_key(e) for e in o.galois_elts()})
     rng = np.random.default_rng(13)
     nl = len(o.primes) - 1
+    for count in (1, 37):
+        assert (g.route("mul_relin", nl, count), g.route("rotate", nl, count), g.route("multiply", nl, count),
+                g.route("relinearize", nl, count)) == EXPECTED_ROUTE_BFV13[variant]
     ex = _extreme_ct(o.primes, nl, o.n, rng)
     ct = o.encrypt(o.encode(oracle_mod.expand_vector([3, 1, 4, 1, 5], o.n)), 9)
     _same(variant + " bfv13 multiply (size 3)", g.multiply(ct, ex), o.multiply(ct, ex))
@@ -206,6 +281,9 @@ def test_fp64_and_integer_paths_agree_on_random_residues(oracle14, capi, monkeyp
     g_int = capi.Context(capi.CKKS, o.n, primes)
     g_int.load_keys(**keys)
     monkeypatch.delenv("ABC_HIP_NO_FP64")
+    for nl in (1, 2, 3, 4):  # 200 pairs: chunks of 100, the fat front
+        assert g_fp.route("mul_relin", nl, 200) == _SPLIT % ("fat", 1, "split4") and g_int.route("mul_relin", nl, 200) == "isplit14 guard=0 fpmask=0x0"
+        assert g_fp.route("rotate", nl, 200) == "fold " + _SPLIT % ("fat", 1, "split4") and g_int.route("rotate", nl, 200) == "fold isplit14 guard=0 fpmask=0x0"
     rng = np.random.default_rng(99)
     B = 200
     for rnd in range(10):
@@ -243,6 +321,19 @@ WIDE_CHAINS = {
 }
 
 
+def _wide_route(bits, nl, isplit):
+    """(mul_relin / key-switch route, rescale route) of a chain of these prime widths at N = 2^14, nl <= 7, small batches"""
+    key = bits[:-1] + bits[-1:]  # every key prime counts for the sequence, whatever the level
+    fp = sum(1 << j for j in range(nl) if bits[j] <= 50)
+    resc = "fp" if fp == (1 << nl) - 1 else "generic" if isplit == "round1" else "mixed fpmask=0x%x" % (0 if isplit == "integer_only" else fp)
+    if max(key) <= 50:
+        return _SPLIT % ("lean", 1 if nl <= 5 else 0, "split4" if nl <= 5 else "split3"), True, resc
+    guard = int(max(key) > 57)
+    if isplit == "round1":
+        return "lds_int guard=%d lazy=%d" % (guard, int(max(key) <= 55)), False, resc
+    return "isplit14 guard=%d fpmask=0x%x" % (guard, 0 if isplit == "integer_only" else fp), True, resc
+
+
 @pytest.mark.parametrize("isplit", ["mixed", "integer_only", "round1"])
 @pytest.mark.parametrize("chain", list(WIDE_CHAINS))
 def test_ckks14_wide_prime_chains_every_level(chain, isplit, oracle_mod, capi, monkeypatch):
@@ -265,6 +356,10 @@ def test_ckks14_wide_prime_chains_every_level(chain, isplit, oracle_mod, capi, m
     y = _extreme_ct(primes, L, n, rng)
     for level in range(L, 0, -1):
         assert x.shape[1] == level
+        seq, fold, resc = _wide_route(WIDE_CHAINS[chain], level, isplit)
+        for count in (1, 3):
+            assert g.route("mul_relin", level, count) == seq and g.route("rotate", level, count) == ("fold " if fold else "permute ") + seq
+        assert level == 1 or g.route("rescale", level) == resc
         _same("%s mul_relin level %d" % (chain, level), g.mul_relin(x, y), o.mul_relin(x, y))
         _same("%s rotate level %d" % (chain, level), g.rotate(y, 3), o.rotate(y, 3))
         _same("%s rotate (NAF) level %d" % (chain, level), g.rotate(x, 7), o.rotate(x, 7))
@@ -304,6 +399,9 @@ def test_ckks14_packed_half_done_limbs(chain, front, oracle_mod, capi, monkeypat
     x = np.stack([rng.integers(0, q, size=(2, n), dtype=np.uint64) for q in primes[:L]], axis=1)
     y = _extreme_ct(primes, L, n, rng)
     for level in range(L, 0, -1):
+        for count in (1, 5):
+            assert g.route("mul_relin", level, count) == _SPLIT % (front, 1, "split4")
+            assert g.route("rotate", level, count) == "fold " + _SPLIT % (front, 1, "split4")
         _same("%s mul_relin level %d" % (chain, level), g.mul_relin(x, y), o.mul_relin(x, y))
         _same("%s mul_relin extreme level %d" % (chain, level), g.mul_relin(y, y), o.mul_relin(y, y))
         _same("%s rotate level %d" % (chain, level), g.rotate(y, 3), o.rotate(y, 3))
@@ -335,6 +433,7 @@ def test_multi_chunk_batches_every_pair(variant, oracle14, capi, monkeypatch):
                 galois={e: o.galois_key(e) for e in o.galois_elts()})
     rng = np.random.default_rng(11)
     B = 11  # chunks of 3, 3, 3, 2 over two lanes: two chunks per lane, a ragged tail
+    _check_routes(g, variant, 4, count=B)
     pool = [ins["cx"], ins["cy"], ins["ex"], ins["ey"]]
     a = np.stack([pool[int(i)] for i in rng.integers(0, 4, B)])
     b = np.stack([pool[int(i)] for i in rng.integers(0, 4, B)])
