@@ -1250,6 +1250,7 @@ static int run_keyswitch(abc_hip_ctx *c, Seq seq, const u64 *target, size_t targ
   // BFV rotation (coefficient form): the kernels gather with elt^-1 mod 2N
   const u32 ginv = (!ckks && gelt) ? (u32)host::invmod(gelt, 2 * (uint64_t)N) : 0u;
   if (ginv && !splitb) { set_error("run_keyswitch: a BFV permutation is only folded into the split sequence"); return 1; }
+  if (ckks && gelt && !splitc) { set_error("run_keyswitch: a CKKS permutation is only folded into the split sequence"); return 1; }
   const size_t SN = (splitc || splitb) ? (size_t)c->dc.ps : N;
   const size_t per_ct = fused_scratch_limbs(nl) * SN;
   // the split kernels read the key's fp64 twin (BFV: the inner-product kernel)

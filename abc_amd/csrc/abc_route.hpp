@@ -186,8 +186,11 @@ inline RotRoute route_rotate(const RouteFacts &f, int nl, bool in_place) {
     // a big ring with a prime above 2^50: k_iks_pass0 / k_iks_finish gather
     if ((f.logn == 15 || f.logn == 16) && route_ks_front(f, nl) == KsFront::iks && !bsplit_big_ok(f, nl)) return {true, {Seq::generic, KsFront::iks}};
   }
-  if (may_fold && f.logn == 14 && f.scheme == 2 && (f.all_fp || isplit_ok(f, nl)) && !f.sw.no_split && !f.sw.no_fused)
-    return {true, {lds_seq(f, nl, false), KsFront::plain}};
+  if (may_fold && f.logn == 14 && f.scheme == 2 && !f.sw.no_split && !f.sw.no_fused) {
+    // only the split sequences gather; the LDS-resident kernels (all-fp chains above twelve limbs) take the permuted ciphertext
+    const Seq s = lds_seq(f, nl, false);
+    if (s == Seq::split14 || s == Seq::isplit) return {true, {s, KsFront::plain}};
+  }
   return {false, route_keyswitch(f, nl)};
 }
 

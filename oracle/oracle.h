@@ -49,7 +49,9 @@ void orc_ntt_forward_plain(const orc_ctx *c, uint64_t *a);
 void orc_ntt_inverse_plain(const orc_ctx *c, uint64_t *a);
 
 /* keys */
-int orc_keygen(orc_ctx *c, uint64_t seed);
+int orc_keygen(orc_ctx *c, uint64_t seed);                 /* every default Galois element */
+/* the same secret / public / relin key; Galois keys only for elts[0 .. count), in that order, duplicates skipped */
+int orc_keygen_elts(orc_ctx *c, uint64_t seed, const uint32_t *elts, int count);
 int orc_get_secret_key(const orc_ctx *c, uint64_t *out);   /* [L+1][N] NTT form */
 int orc_get_public_key(const orc_ctx *c, uint64_t *out);   /* [2][L+1][N] */
 int orc_get_relin_key(const orc_ctx *c, uint64_t *out);    /* [L][2][L+1][N] */

@@ -57,6 +57,7 @@ def lib():
         L.orc_galois_elt_from_step.argtypes = [C.c_void_p, C.c_int]
         L.orc_galois_elt_at.restype = C.c_uint32
         L.orc_galois_elt_at.argtypes = [C.c_void_p, C.c_int]
+        L.orc_keygen_elts.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.c_int]
         L.orc_time_mul_relin.restype = C.c_double
         _lib = L
     return _lib
@@ -114,8 +115,13 @@ class Oracle:
         return cls(BFV, n, default_bfv_primes(n), plain_modulus_batching(n, 20))
 
     # ---- keys ----
-    def keygen(self, seed):
-        assert lib().orc_keygen(self.h, C.c_uint64(seed)) == 0
+    def keygen(self, seed, elts=None):
+        """elts: Galois keys for these elements only (in this order); None: the default list.  The other keys do not depend on it."""
+        if elts is None:
+            assert lib().orc_keygen(self.h, C.c_uint64(seed)) == 0
+        else:
+            arr = (C.c_uint32 * max(len(elts), 1))(*elts)
+            assert lib().orc_keygen_elts(self.h, C.c_uint64(seed), arr, len(elts)) == 0
 
     def secret_key(self):
         out = np.zeros((self.K, self.n), dtype=np.uint64)

@@ -122,9 +122,22 @@ int orc_naf(int value, int *out) {
   return cnt;
 }
 
-int orc_keygen(orc_ctx *c, uint64_t seed) {
+/* Secret, public and relin key in orc_keygen's sampling order, then one Galois key per element of elts, in the order given
+ * (an element named twice gets one key, as in SEAL). */
+int orc_keygen_elts(orc_ctx *c, uint64_t seed, const uint32_t *elts, int count) {
   size_t n = c->n;
   int K = c->nkey, L = c->L;
+  if (count < 0 || (count > 0 && !elts)) return -1;
+  {
+    int distinct = 0; /* refuse before anything is sampled: the key table holds ORC_MAX_GALOIS entries */
+    for (int e = 0; e < count; e++) {
+      int dup = 0;
+      for (int d = 0; d < e; d++) dup |= (elts[d] == elts[e]);
+      distinct += !dup;
+      if (!(elts[e] & 1u) || elts[e] >= 2 * n) return -1; /* an element of (Z/2N)^* */
+    }
+    if (distinct > ORC_MAX_GALOIS) return -1;
+  }
   orc_rng rng;
   orc_rng_seed(&rng, seed);
   free(c->sk_ntt); free(c->pk); free(c->relin);
@@ -149,18 +162,8 @@ int orc_keygen(orc_ctx *c, uint64_t seed) {
   size_t key_words = (size_t)L * 2 * K * n;
   c->relin = (uint64_t *)malloc(key_words * 8);
   make_kswitch_key(c, &rng, s2, c->relin);
-  /* Galois keys for all default elements [SEAL-recall: GaloisTool::get_elts_all] */
-  uint64_t m = 2ull * n;
-  uint32_t elts[ORC_MAX_GALOIS];
-  int ne = 0;
-  elts[ne++] = (uint32_t)(m - 1);
-  uint64_t pos = 3, neg = orc_inv_mod(3, m);
-  for (int i = 0; i < c->logn - 1; i++) {
-    elts[ne++] = (uint32_t)pos; pos = (pos * pos) & (m - 1);
-    elts[ne++] = (uint32_t)neg; neg = (neg * neg) & (m - 1);
-  }
   int nk = 0;
-  for (int e = 0; e < ne; e++) {
+  for (int e = 0; e < count; e++) {
     /* [SEAL-recall: KeyGenerator::create_galois_keys] "do we already have the key?" -> skip
      * (3^(N/4) == 3^-(N/4) mod 2N, so the default list names that element twice) */
     int dup = 0;
@@ -175,6 +178,20 @@ int orc_keygen(orc_ctx *c, uint64_t seed) {
   c->ngal = nk;
   free(s2);
   return 0;
+}
+
+int orc_keygen(orc_ctx *c, uint64_t seed) {
+  /* Galois keys for all default elements [SEAL-recall: GaloisTool::get_elts_all] */
+  uint64_t m = 2ull * c->n;
+  uint32_t elts[ORC_MAX_GALOIS];
+  int ne = 0;
+  elts[ne++] = (uint32_t)(m - 1);
+  uint64_t pos = 3, neg = orc_inv_mod(3, m);
+  for (int i = 0; i < c->logn - 1; i++) {
+    elts[ne++] = (uint32_t)pos; pos = (pos * pos) & (m - 1);
+    elts[ne++] = (uint32_t)neg; neg = (neg * neg) & (m - 1);
+  }
+  return orc_keygen_elts(c, seed, elts, ne);
 }
 
 int orc_get_secret_key(const orc_ctx *c, uint64_t *out) {

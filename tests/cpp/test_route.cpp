@@ -212,9 +212,23 @@ int main() {
     EQ(mul(fp, 13), "lds_fp");
     EQ(ks(fp, 13), "lds_fp");
     EQ(rot(fp, 12), "fold split14 front=lean pack=0 main=split3");
-    // KNOWN DEFECT, pinned because this change keeps every decision: the LDS-resident kernels have no gather, so this rotation drops
-    // its permutation (rotation (d)).  The fix makes this "permute lds_fp"; flipping the line then is no regression.
-    EQ(rot(fp, 13), "fold lds_fp");
+    EQ(rot(fp, 12, 1, true), "permute split14 front=lean pack=0 main=split3");
+    EQ(rot(fp, 13), "permute lds_fp");  // the LDS-resident kernels have no gather: k_galois first
+    EQ(rot(fp, 13, 1, true), "permute lds_fp");
+    const RouteFacts fp15 = facts(CKKS, 14, chain(50, 40, 14, 50));  // the deepest chain a context accepts
+    EQ(rot(fp15, 12), "fold split14 front=lean pack=0 main=split3");
+    EQ(rot(fp15, 15), "permute lds_fp");
+    EQ(rot(fp15, 15, 3), "permute lds_fp");
+    EQ(rot(fp15, 15, 1, true), "permute lds_fp");
+    for (int nl = 1; nl <= 15; nl++) {  // a fold names a sequence that gathers, at every level and for every switch
+      for (auto set : {+SW(no_split), +SW(no_fused), +SW(no_isplit), +SW(no_split4), +SW(no_lean_front), +SW(no_mixed), +SW(no_gsplit)})
+        for (bool int_only : {false, true}) {
+          RouteFacts g = with(fp15, set);
+          if (int_only) g = with(g, NO_FP64);
+          const RotRoute r = route_rotate(g, nl, false);
+          EXPECT_TRUE(!r.fold || r.ks.seq == Seq::split14 || r.ks.seq == Seq::isplit);
+        }
+    }
     const RouteFacts wide = facts(CKKS, 14, chain(60, 40, 8, 60));
     EQ(mul(wide, 7), "isplit14 guard=1 fpmask=0x7e");
     EQ(mul(wide, 8), "lds_int guard=1 lazy=0");

@@ -10,6 +10,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 CHAINS = {"50-40": [50, 40, 40, 40, 50], "60-40": [60, 40, 40, 40, 60]}
+DEEP = [50] + [40] * 14 + [50]
 SCALE = 2.0 ** 40
 
 
@@ -22,10 +23,8 @@ def contexts(oracle_mod, capi):
         if key not in cache:
             primes = oracle_mod.create_primes(n, bits)
             assert capi.create_primes(n, bits) == primes
-            o = oracle_mod.Oracle(oracle_mod.CKKS, n, primes)
-            o.keygen(0xC0DEC)
+            o = oracle_mod.Oracle(oracle_mod.CKKS, n, primes)  # the codec needs no keys
             g = capi.Context(capi.CKKS, n, primes)
-            g.keygen(0xC0DEC)
             cache[key] = (o, g)
         return cache[key]
     yield get
@@ -38,6 +37,12 @@ def _grid():
         for name, bits in CHAINS.items():
             yield pytest.param(1 << logn, bits, id="N%d-%s" % (1 << logn, name))
     yield pytest.param(1 << 16, [60, 50, 50, 50, 50, 50, 50, 50, 60], id="N65536-8limbs")
+    yield pytest.param(1 << 14, DEEP, id="N16384-15limbs")
+
+
+def _levels(o):
+    """the deep chain: both sides of the decoder's 8-word / 16-word lift (SrcLift<8> up to eight limbs, SrcLift<16> above)"""
+    return [1, 8, 9, 12, 15] if o.L == 15 else sorted({1, o.L})
 
 
 def _values(rng, n, count, cplx):
@@ -68,7 +73,7 @@ def _assert_close_coeffs(o, got, want, what):
 def test_encode_matches_oracle(contexts, n, bits):
     o, g = contexts(n, bits)
     rng = np.random.default_rng(n + len(bits))
-    for nl in sorted({1, o.L}):
+    for nl in _levels(o):
         for cplx in (False, True):
             for count in (n // 2, n // 2 - 37):
                 v = _values(rng, n, count, cplx)
@@ -87,7 +92,7 @@ def test_encode_matches_oracle(contexts, n, bits):
 def test_decode_matches_oracle(contexts, n, bits):
     o, g = contexts(n, bits)
     rng = np.random.default_rng(2 * n + len(bits))
-    for nl in sorted({1, o.L}):
+    for nl in _levels(o):
         enc = o.ckks_encode(_values(rng, n, n // 2, True), SCALE, nl)
         # uniformly random residues: the full-width centred lift, both halves of (-Q/2, Q/2]
         rnd = np.stack([rng.integers(0, o.primes[j], n, dtype=np.uint64) for j in range(nl)])
@@ -103,11 +108,33 @@ def test_decode_matches_oracle(contexts, n, bits):
 def test_round_trip(contexts, n, bits):
     o, g = contexts(n, bits)
     rng = np.random.default_rng(3 * n)
-    for nl in range(1, o.L + 1):
+    for nl in (_levels(o) if o.L == 15 else range(1, o.L + 1)):
         v = _values(rng, n, n // 2, True)
         got = g.ckks_decode(g.ckks_encode(v, SCALE, nl), SCALE)
         err = np.abs(got - v) / np.maximum(1.0, np.abs(v))
         assert err.max() <= 1e-7, "N=%d nl=%d: round trip %g off" % (n, nl, err.max())
+
+
+@pytest.mark.parametrize("nl", [1, 8, 9, 12, 15])
+def test_decode_lift_exact_on_a_constant(contexts, nl):
+    """The lift alone, without the oracle's long double: the constant polynomial V = Q // 3 (Q: the product of the first nl primes)
+    and its negative Q - V.  In NTT form every word of limb j is V mod q_j, and every slot of a constant is the constant, so each
+    must decode to +-float(V) / scale.  Bound 1e-12 relative: at most 16 roundings in the word Horner plus an 8192-point
+    transform of a constant come to a few 1e-15."""
+    n = 1 << 14
+    o, g = contexts(n, DEEP)
+    Q = 1
+    for q in o.primes[:nl]:
+        Q *= q
+    V = Q // 3
+    for sign, value in ((1.0, V), (-1.0, Q - V)):
+        plain = np.stack([np.full(n, value % q, dtype=np.uint64) for q in o.primes[:nl]])
+        got = g.ckks_decode(plain, SCALE)
+        want = sign * float(V) / SCALE
+        assert np.abs(got.real - want).max() <= 1e-12 * abs(want), "nl=%d sign %+d: real part %g off (relative)" % (
+            nl, sign, np.abs(got.real - want).max() / abs(want))
+        assert np.abs(got.imag).max() <= 1e-12 * abs(want), "nl=%d sign %+d: imaginary part %g (relative)" % (
+            nl, sign, np.abs(got.imag).max() / abs(want))
 
 
 def test_pipeline_without_host_codec(contexts):
@@ -115,6 +142,7 @@ def test_pipeline_without_host_codec(contexts):
     n = 16384
     o, g = contexts(n, CHAINS["50-40"])
     rng = np.random.default_rng(7)
+    g.keygen(0xC0DEC)
     x, y = rng.uniform(-1, 1, n // 2), rng.uniform(-1, 1, n // 2)
     cx, cy = g.encrypt(g.ckks_encode(x, SCALE), seed=11), g.encrypt(g.ckks_encode(y, SCALE), seed=12)
     plain = g.decrypt(g.rescale(g.mul_relin(cx, cy)))

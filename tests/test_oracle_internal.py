@@ -132,3 +132,41 @@ def test_timed_mul_relin_bfv_default_ring_runs_in_its_arena(oracle_mod):
     b = o.encrypt(o.encode(oracle_mod.expand_vector([0, 1, 2, 1, 10, 21], o.n)), 2)
     assert o.time_mul_relin(a, b, 1) > 0.0
     assert list(o.decode(o.decrypt(o.mul_relin(a, b)))[:6]) == [0, 3, 2, 4, 50, 189]
+
+
+def test_keygen_for_chosen_galois_elements(oracle_mod):
+    """Oracle.keygen(seed, elts): the default list gives orc_keygen's keys bit for bit; a sub-list changes no other key, and its first
+    key is the default run's first key (both are sampled right after the relin key)."""
+    n = 4096
+    primes = oracle_mod.create_primes(n, [40, 40, 41])
+    full, same, part = (oracle_mod.Oracle(oracle_mod.CKKS, n, primes) for _ in range(3))
+    full.keygen(21)
+    elts = full.galois_elts()
+    assert len(elts) == 2 * (full.logn - 1) and elts[0] == 2 * n - 1  # 3^(N/4) is named twice in the default list: one key
+    default_list = [2 * n - 1]
+    pos, neg = 3, pow(3, -1, 2 * n)
+    for _ in range(full.logn - 1):
+        default_list += [pos, neg]
+        pos, neg = pos * pos % (2 * n), neg * neg % (2 * n)
+    same.keygen(21, elts=default_list)
+    assert same.galois_elts() == elts
+    sub = [elts[0], full.elt_from_step(8), elts[0], full.elt_from_step(1)]  # a duplicate is skipped
+    part.keygen(21, elts=sub)
+    assert part.galois_elts() == [sub[0], sub[1], sub[3]]
+    for other in (same, part):
+        assert np.array_equal(other.secret_key(), full.secret_key())
+        assert np.array_equal(other.public_key(), full.public_key())
+        assert np.array_equal(other.relin_key(), full.relin_key())
+    for e in elts:
+        assert np.array_equal(same.galois_key(e), full.galois_key(e)), e
+    assert np.array_equal(part.galois_key(sub[0]), full.galois_key(elts[0]))
+    # later keys follow other draws of the stream, but they are keys for their element: a rotation decrypts to the rotated slots
+    bfv = oracle_mod.Oracle.bfv_default(n)
+    bfv.keygen(5, elts=[bfv.elt_from_step(1)])
+    ct = bfv.encrypt(bfv.encode(oracle_mod.expand_vector([1, 2, 3, 4], n)), 3)
+    assert list(bfv.decode(bfv.decrypt(bfv.rotate(ct, 1)))[:3]) == [2, 3, 4]
+    with pytest.raises(RuntimeError):
+        bfv.rotate(ct, 2)  # no key for that step
+    none = oracle_mod.Oracle(oracle_mod.CKKS, n, primes)
+    none.keygen(21, elts=[])
+    assert none.galois_elts() == [] and np.array_equal(none.relin_key(), full.relin_key())
