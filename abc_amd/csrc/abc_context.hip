@@ -804,6 +804,14 @@ static int check_level(abc_hip_ctx *c, int nl) {
   if (c->scheme == ABC_HIP_SCHEME_BFV && nl != c->L) { set_error("BFV ciphertexts live at the top level (nl = L)"); return 1; }
   return 0;
 }
+// one plaintext for the batch (0) or one per ciphertext; any other stride would read past a row or overlap two (abc_hip.h)
+static int check_plain_stride(abc_hip_ctx *c, const char *op, size_t plain_stride, int nl) {
+  if (!plain_stride) return 0;
+  const bool ckks = c->scheme == ABC_HIP_SCHEME_CKKS;
+  if (ckks ? plain_stride >= (size_t)nl * c->n : plain_stride == (size_t)c->n) return 0;
+  set_error(std::string(op) + (ckks ? ": plain_stride must be 0 or at least nl * N" : ": plain_stride must be 0 or N"));
+  return 1;
+}
 int abc_hip_route(abc_hip_ctx *c, int op, int nl, size_t count, int in_place, char *buf, size_t cap) {
   CTX_GUARD(c);
   if (check_level(c, nl)) return 1;  // nl as the operation itself takes it (BFV: L, also for multiply)
@@ -869,21 +877,21 @@ int abc_hip_apply_galois(abc_hip_ctx *c, const uint64_t *in, uint64_t *out, int 
 int abc_hip_multiply_plain(abc_hip_ctx *c, const uint64_t *ct, const uint64_t *plain, size_t plain_stride, uint64_t *out, int size,
                            int nl, size_t count) {
   CTX_GUARD(c);
-  if (check_level(c, nl)) return 1;
+  if (check_level(c, nl) || check_plain_stride(c, "multiply_plain", plain_stride, nl)) return 1;
   if (c->scheme == ABC_HIP_SCHEME_CKKS) return ckks_multiply_plain(c, ct, plain, plain_stride, out, size, nl, count);
   return bfv_multiply_plain(c, ct, plain, plain_stride, out, size, count);
 }
 int abc_hip_add_plain(abc_hip_ctx *c, const uint64_t *ct, const uint64_t *plain, size_t plain_stride, uint64_t *out, int size, int nl,
                       size_t count) {
   CTX_GUARD(c);
-  if (check_level(c, nl)) return 1;
+  if (check_level(c, nl) || check_plain_stride(c, "add_plain", plain_stride, nl)) return 1;
   if (c->scheme == ABC_HIP_SCHEME_CKKS) return ckks_add_plain(c, ct, plain, plain_stride, out, size, nl, count, 0);
   return bfv_addsub_plain(c, ct, plain, plain_stride, out, size, count, 0);
 }
 int abc_hip_sub_plain(abc_hip_ctx *c, const uint64_t *ct, const uint64_t *plain, size_t plain_stride, uint64_t *out, int size, int nl,
                       size_t count) {
   CTX_GUARD(c);
-  if (check_level(c, nl)) return 1;
+  if (check_level(c, nl) || check_plain_stride(c, "sub_plain", plain_stride, nl)) return 1;
   if (c->scheme == ABC_HIP_SCHEME_CKKS) return ckks_add_plain(c, ct, plain, plain_stride, out, size, nl, count, 1);
   return bfv_addsub_plain(c, ct, plain, plain_stride, out, size, count, 1);
 }

@@ -583,11 +583,11 @@ int bfv_multiply_plain(abc_hip_ctx *c, const u64 *ct, const u64 *plain, size_t p
   if (!count) return 0;
   const size_t N = (size_t)c->n;
   const int L = c->L;
+  if (plain_stride && plain_stride != N) { set_error("multiply_plain: plain_stride must be 0 or N"); return 1; }
   const size_t nplain = plain_stride ? count : 1;
   if (ensure_workspace(c, nplain * L * N * 8)) return 1;
   u64 *lifted = (u64 *)c->ws;
   const LimbMap qmap = key_limb_map(c, L);
-  if (plain_stride && plain_stride != N) { set_error("multiply_plain: plain_stride must be 0 or N"); return 1; }
   hipLaunchKernelGGL(k_plain_lift, dim3(grid_for(nplain * N, 256)), dim3(256), 0, c->stream, c->dc, plain, lifted, nplain);
   ABC_HIP_CHECK(hipGetLastError());
   if (launch_ntt_fwd(c, lifted, qmap, L, nplain * L)) return 1;

@@ -165,7 +165,15 @@ int abc_hip_mul_relin(abc_hip_ctx *ctx, const uint64_t *d_a, const uint64_t *d_b
 int abc_hip_rotate(abc_hip_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, int nl, int steps, size_t count);
 /* Evaluator::apply_galois for one element */
 int abc_hip_apply_galois(abc_hip_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, int nl, uint32_t galois_elt, size_t count);
-/* Evaluator::multiply_plain(_inplace) (:159,:196); plain_stride = 0 broadcasts one plaintext to the batch */
+/* The three plaintext operations.  d_out may be d_ct (the reference's *_inplace call sites); size = 2 or 3.
+ * plain_stride, in words, is the distance from ciphertext i's plaintext to ciphertext i + 1's:
+ *   0            one plaintext, broadcast to the batch (d_plain holds N words for BFV, nl * N for CKKS);
+ *   BFV:  N      one plaintext per ciphertext, d_plain [count][N];
+ *   CKKS: >= nl * N  one plaintext per ciphertext; row i starts at d_plain + i * plain_stride and its first nl limbs are read.
+ *                A stride above nl * N is how plaintexts laid out for a higher level ([count][L][N], stride L * N) are
+ *                applied to ciphertexts at nl < L: limb j is modulo q_j at every level.
+ * Any other stride would read past a row or let rows overlap: the call fails (non-zero status) and enqueues nothing. */
+/* Evaluator::multiply_plain(_inplace) (:159,:196) */
 int abc_hip_multiply_plain(abc_hip_ctx *ctx, const uint64_t *d_ct, const uint64_t *d_plain, size_t plain_stride,
                            uint64_t *d_out, int size, int nl, size_t count);
 /* Evaluator::add_plain(_inplace) (:134,:175) */

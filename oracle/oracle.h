@@ -88,6 +88,7 @@ int orc_ckks_rescale(const orc_ctx *c, const uint64_t *ct, int size, int nl, uin
 int orc_ckks_mod_switch(const orc_ctx *c, const uint64_t *ct, int size, int nl, uint64_t *out);
 int orc_ckks_multiply_plain(const orc_ctx *c, const uint64_t *ct, int size, int nl, const uint64_t *plain, uint64_t *out);
 int orc_ckks_add_plain(const orc_ctx *c, const uint64_t *ct, int size, int nl, const uint64_t *plain, uint64_t *out);
+int orc_ckks_sub_plain(const orc_ctx *c, const uint64_t *ct, int size, int nl, const uint64_t *plain, uint64_t *out);
 int orc_ckks_encode(const orc_ctx *c, const double *re, const double *im, size_t count, double scale, int nl,
                     uint64_t *plain);
 int orc_ckks_decode(const orc_ctx *c, const uint64_t *plain, int nl, double scale, double *re, double *im);

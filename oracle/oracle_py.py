@@ -275,7 +275,10 @@ class Oracle:
     def sub_plain(self, ct, plain):
         ct = np.ascontiguousarray(ct)
         out = np.zeros_like(ct)
-        assert lib().orc_bfv_sub_plain(self.h, _p(ct), ct.shape[0], _p(plain), _p(out)) == 0
+        if self.scheme == BFV:
+            assert lib().orc_bfv_sub_plain(self.h, _p(ct), ct.shape[0], _p(plain), _p(out)) == 0
+        else:
+            assert lib().orc_ckks_sub_plain(self.h, _p(ct), ct.shape[0], ct.shape[1], _p(plain), _p(out)) == 0
         return out
 
     # ---- CKKS ----

@@ -468,6 +468,16 @@ int orc_ckks_add_plain(const orc_ctx *c, const uint64_t *ct, int size, int nl, c
     }
   return 0;
 }
+int orc_ckks_sub_plain(const orc_ctx *c, const uint64_t *ct, int size, int nl, const uint64_t *plain, uint64_t *out) {
+  size_t n = c->n;
+  memmove(out, ct, (size_t)size * nl * n * 8);
+  for (int j = 0; j < nl; j++)
+    for (size_t k = 0; k < n; k++) {
+      size_t o = (size_t)j * n + k;
+      out[o] = orc_sub_mod(out[o], plain[o], c->qmod[j].q);
+    }
+  return 0;
+}
 
 /* ---------- CPU baseline timing ---------- */
 double orc_time_mul_relin(const orc_ctx *c, const uint64_t *a, const uint64_t *b, int nl, int iters, uint64_t *out2) {

@@ -170,3 +170,36 @@ def test_keygen_for_chosen_galois_elements(oracle_mod):
     none = oracle_mod.Oracle(oracle_mod.CKKS, n, primes)
     none.keygen(21, elts=[])
     assert none.galois_elts() == [] and np.array_equal(none.relin_key(), full.relin_key())
+
+
+@pytest.mark.parametrize("size", [2, 3])
+def test_ckks_plain_ops_are_componentwise_integer_arithmetic(size, oracle_mod):
+    """orc_ckks_multiply_plain / _add_plain / _sub_plain against Python integers, below the top level (nl = 2 of L = 3, one prime of
+    60 bits): every component times p; only component 0 plus or minus p, the others unchanged"""
+    n, nl = 1024, 2
+    primes = oracle_mod.create_primes(n, [60, 40, 50, 60])
+    o = oracle_mod.Oracle(oracle_mod.CKKS, n, primes)
+    assert nl < o.L
+    rng = np.random.default_rng(size)
+    ct = np.stack([rng.integers(0, q, size=(size, n), dtype=np.uint64) for q in primes[:nl]], axis=1)
+    pl = np.stack([rng.integers(0, q, size=n, dtype=np.uint64) for q in primes[:nl]])
+    for j, q in enumerate(primes[:nl]):  # ends of the range, and a - a / a + (q - a)
+        ct[:, j, :4] = [0, 1, q - 1, (q - 1) // 2]
+        pl[j, :8] = [0, 1, q - 1, (q - 1) // 2, q - 1, 0, 1, q - 2]
+        pl[j, 8] = ct[0, j, 8]
+        pl[j, 9] = (q - int(ct[0, j, 9])) % q
+    got = {"mul": o.multiply_plain(ct, pl), "add": o.add_plain(ct, pl), "sub": o.sub_plain(ct, pl)}
+    for j, q in enumerate(primes[:nl]):
+        p = [int(v) for v in pl[j]]
+        for c in range(size):
+            x = [int(v) for v in ct[c, j]]
+            assert [int(v) for v in got["mul"][c, j]] == [a * b % q for a, b in zip(x, p)], (c, j)
+            assert [int(v) for v in got["add"][c, j]] == ([(a + b) % q for a, b in zip(x, p)] if c == 0 else x), (c, j)
+            assert [int(v) for v in got["sub"][c, j]] == ([(a - b) % q for a, b in zip(x, p)] if c == 0 else x), (c, j)
+    assert got["sub"][0, 0, 8] == 0 and got["add"][0, 0, 9] == 0
+    # BFV keeps its own function
+    b = oracle_mod.Oracle.bfv_default(4096)
+    cb = np.stack([rng.integers(0, q, size=(2, 4096), dtype=np.uint64) for q in b.primes[:b.L]], axis=1)
+    pb = rng.integers(0, b.t, size=4096, dtype=np.uint64)
+    back = b.add_plain(b.sub_plain(cb, pb), pb)
+    assert np.array_equal(back, cb) and not np.array_equal(b.sub_plain(cb, pb), cb)
