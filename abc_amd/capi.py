@@ -34,6 +34,7 @@ SYMBOLS = [
     "abc_hip_microbench", "abc_hip_timer_start", "abc_hip_timer_stop",
     "abc_hip_ntt_limbs",
     "abc_hip_graph_begin", "abc_hip_graph_end", "abc_hip_graph_launch", "abc_hip_graph_destroy",
+    "abc_hip_encrypt_keyed", "abc_hip_keygen_keyed", "abc_hip_keyed_small", "abc_hip_keyed_uniform", "abc_hip_keyed_small_host",
 ]
 
 
@@ -60,6 +61,11 @@ def lib():
         L.abc_hip_cached_bytes.argtypes = [C.c_void_p]
         L.abc_hip_galois_elt_from_step.restype = C.c_uint32
         L.abc_hip_route.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_char_p, C.c_size_t]
+        L.abc_hip_encrypt_keyed.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_size_t]
+        L.abc_hip_keygen_keyed.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+        L.abc_hip_keyed_small.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_size_t]
+        L.abc_hip_keyed_uniform.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_void_p]
+        L.abc_hip_keyed_small_host.argtypes = [C.c_char_p, C.c_uint64, C.c_size_t, C.c_size_t, C.c_void_p]
         _lib = L
     return _lib
 
@@ -89,6 +95,20 @@ def create_primes(n, bit_sizes):
     bs = (C.c_int * len(bit_sizes))(*bit_sizes)
     _chk(lib().abc_hip_create_primes(n, bs, len(bit_sizes), out))
     return [int(x) for x in out]
+
+
+def _key32(key):
+    key = bytes(key)
+    if len(key) != 32:
+        raise ValueError("a sampling key is 32 bytes")
+    return key
+
+
+def keyed_small_host(key, nonce, n, count):
+    """Host twin of Context.keyed_small (the keyed sampling spec): no context, no GPU.  int8 [count][3][n]."""
+    out = np.zeros((count, 3, n), dtype=np.int8)
+    _chk(lib().abc_hip_keyed_small_host(_key32(key), nonce % 2 ** 64, n, count, out.ctypes.data_as(C.c_void_p)))
+    return out
 
 
 class DeviceBuffer:
@@ -192,6 +212,28 @@ class Context:
             _chk(lib().abc_hip_keygen_secure(self.h))
         else:
             _chk(lib().abc_hip_keygen(self.h, C.c_uint64(seed)))
+
+    def keygen_keyed(self, key_sec, key_pub):
+        """the keyed sampling spec: key_sec (32 bytes) draws the secret key and the errors, key_pub the published polynomials"""
+        _chk(lib().abc_hip_keygen_keyed(self.h, _key32(key_sec), _key32(key_pub)))
+
+    def keyed_small(self, key, nonce, count):
+        """the raw draws of encrypt_keyed: int8 [count][3][N] (u | e0 | e1), ciphertext i from stream nonce + i"""
+        out = self.alloc(count * 3 * self.n)
+        try:
+            _chk(lib().abc_hip_keyed_small(self.h, _key32(key), nonce % 2 ** 64, out.ptr, count))
+            return self.download(out, (count, 3, self.n), np.int8)
+        finally:
+            out.free()
+
+    def keyed_uniform(self, key, stream, nkeys):
+        """the uniform polynomials of a key: uint64 [nkeys][K][N], limb j modulo q_j, from stream `stream` of `key`"""
+        out = self.alloc(nkeys * self.K * self.n * 8)
+        try:
+            _chk(lib().abc_hip_keyed_uniform(self.h, _key32(key), stream % 2 ** 64, nkeys, out.ptr))
+            return self.download(out, (nkeys, self.K, self.n))
+        finally:
+            out.free()
 
     def load_keys(self, sk=None, pk=None, relin=None, galois=None):
         def p(a):
@@ -418,6 +460,20 @@ class Context:
             self.op("encrypt", pb.ptr, C.c_uint64(seed), out.ptr, C.c_size_t(p.shape[0]))
         r = self.download(out, shp)
         pb.free(); out.free()
+        return r if np.ndim(plain) == len(per) + 1 else r[0]
+
+    def encrypt_keyed(self, plain, key, nonce=0):
+        """the keyed sampling spec: ciphertext i of the batch draws from stream nonce + i of `key` (32 bytes); never reuse a pair"""
+        per = (self.n,) if self.scheme == BFV else (self.L, self.n)
+        p = np.ascontiguousarray(plain, dtype=np.uint64).reshape((-1,) + per)
+        pb = self.upload(p)
+        shp = (p.shape[0], 2, self.L, self.n)
+        out = self.alloc(int(np.prod(shp)) * 8)
+        try:
+            _chk(lib().abc_hip_encrypt_keyed(self.h, pb.ptr, _key32(key), nonce % 2 ** 64, out.ptr, p.shape[0]))
+            r = self.download(out, shp)
+        finally:
+            pb.free(); out.free()
         return r if np.ndim(plain) == len(per) + 1 else r[0]
 
     def decrypt(self, ct):

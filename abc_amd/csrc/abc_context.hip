@@ -15,6 +15,7 @@
 
 #include "abc_context.hpp"
 #include "abc_host_math.hpp"
+#include "abc_sample.hpp"
 
 namespace abc {
 
@@ -41,6 +42,7 @@ void read_switches(abc_hip_ctx *c) {
   s.no_lean_front = env_on("ABC_HIP_NO_LEAN_FRONT");
   s.no_tensor_intt = env_on("ABC_HIP_NO_TENSOR_INTT");
   s.no_galois_fusion = env_on("ABC_HIP_NO_GALOIS_FUSION");
+  s.host_sampling = env_on("ABC_HIP_HOST_SAMPLING");
   if (const char *e = std::getenv("ABC_HIP_CHUNK")) s.chunk = (size_t)std::atol(e);
   if (const char *e = std::getenv("ABC_HIP_FEW_LIMBS")) s.few_limbs = (size_t)std::atol(e);
   if (const char *e = std::getenv("ABC_HIP_LEAN_LIMIT")) s.lean_limit = (size_t)std::atol(e);
@@ -723,6 +725,16 @@ int abc_hip_keygen_secure(abc_hip_ctx *c) {
     return 1;
   }
 }
+int abc_hip_keygen_keyed(abc_hip_ctx *c, const uint8_t key_sec[32], const uint8_t key_pub[32]) {
+  CTX_GUARD(c);
+  NOT_CAPTURABLE(c, "abc_hip_keygen_keyed");
+  try {
+    return keygen_keyed(c, key_sec, key_pub);
+  } catch (const std::exception &e) {
+    set_error(e.what());
+    return 1;
+  }
+}
 // A key is rewritten in place, and so are its mirrors: a recorded circuit keeps the addresses it baked in and reads the new key on
 // its next replay.  Work already enqueued (a replay among it) finishes on the old words first: the stream is non-blocking, so the
 // synchronous copy below would not wait for it.
@@ -787,6 +799,27 @@ int abc_hip_ckks_decode(abc_hip_ctx *c, const uint64_t *p, int nl, double scale,
 }
 int abc_hip_encrypt(abc_hip_ctx *c, const uint64_t *p, uint64_t seed, uint64_t *ct, size_t count) { CTX_GUARD(c); NOT_CAPTURABLE(c, "abc_hip_encrypt"); return encrypt(c, p, seed, ct, count); }
 int abc_hip_encrypt_secure(abc_hip_ctx *c, const uint64_t *p, uint64_t *ct, size_t count) { CTX_GUARD(c); NOT_CAPTURABLE(c, "abc_hip_encrypt_secure"); return encrypt_secure(c, p, ct, count); }
+int abc_hip_encrypt_keyed(abc_hip_ctx *c, const uint64_t *p, const uint8_t key[32], uint64_t nonce, uint64_t *ct, size_t count) {
+  CTX_GUARD(c);
+  NOT_CAPTURABLE(c, "abc_hip_encrypt_keyed");
+  return encrypt_keyed(c, p, key, nonce, ct, count);
+}
+int abc_hip_keyed_small(abc_hip_ctx *c, const uint8_t key[32], uint64_t nonce, int8_t *d_small, size_t count) {
+  CTX_GUARD(c);
+  NOT_CAPTURABLE(c, "abc_hip_keyed_small");
+  return keyed_small(c, key, nonce, d_small, count);
+}
+int abc_hip_keyed_uniform(abc_hip_ctx *c, const uint8_t key[32], uint64_t stream, int nkeys, uint64_t *d_a) {
+  CTX_GUARD(c);
+  NOT_CAPTURABLE(c, "abc_hip_keyed_uniform");
+  return keyed_uniform(c, key, stream, nkeys, d_a);
+}
+int abc_hip_keyed_small_host(const uint8_t key[32], uint64_t nonce, size_t n, size_t count, int8_t *h_small) {
+  if (!key || (!h_small && count)) { set_error("keyed_small_host: null pointer"); return 1; }
+  if (!n || n % 8) { set_error("keyed_small_host: n must be a positive multiple of 8"); return 1; }
+  keyed::encrypt_small_host(key, nonce, n, count, h_small);
+  return 0;
+}
 int abc_hip_decrypt(abc_hip_ctx *c, const uint64_t *ct, int size, int nl, uint64_t *p, size_t count) {
   CTX_GUARD(c);
   if (nl < 1 || nl > c->L) { set_error("decrypt: bad limb count"); return 1; }

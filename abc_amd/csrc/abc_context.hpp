@@ -260,6 +260,16 @@ int keygen(abc_hip_ctx *c, uint64_t seed);
 int keygen_secure(abc_hip_ctx *c);
 int encrypt_secure(abc_hip_ctx *c, const u64 *plain, u64 *ct, size_t count);
 int microbench(abc_hip_ctx *c, int which, int iters, double *ms);
+// ---- the keyed sampling spec (abc_sample.hpp): kernels in abc_kernels_sample.hip, entry points in abc_keys.hip ----
+constexpr size_t kSampleKeyBytes = 64;  // device key buffer: 8 key words, the 64-bit nonce, padding
+int upload_sample_key(abc_hip_ctx *c, void *d_kb, const uint8_t key[32], uint64_t nonce);
+int launch_sample_small(abc_hip_ctx *c, const void *d_kb, uint64_t stream_off, size_t streams, size_t polys, size_t ternaries,
+                        int8_t *d_out);
+int launch_sample_uniform(abc_hip_ctx *c, const void *d_kb, uint64_t stream_off, int nkeys, u64 *d_a);
+int encrypt_keyed(abc_hip_ctx *c, const u64 *plain, const uint8_t key[32], uint64_t nonce, u64 *ct, size_t count);
+int keygen_keyed(abc_hip_ctx *c, const uint8_t key_sec[32], const uint8_t key_pub[32]);
+int keyed_small(abc_hip_ctx *c, const uint8_t key[32], uint64_t nonce, int8_t *d_small, size_t count);
+int keyed_uniform(abc_hip_ctx *c, const uint8_t key[32], uint64_t stream, int nkeys, u64 *d_a);
 
 // the key switch of route r (abc_kernels_fused.hip; any sequence); gelt: the Galois element of a rotation folded into it
 // (RotRoute::fold), with target = c1, addend = c0 of the ciphertext

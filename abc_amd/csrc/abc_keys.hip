@@ -6,11 +6,12 @@
 //   :12     seal::Encryptor::encrypt (public key, then modulus switch to the data level) -> encrypt
 //   :150    seal::Decryptor::decrypt                                           -> decrypt
 // and src/runtime/SealCiphertext.cpp:80-83 seal::Decryptor::invariant_noise_budget -> noise_budget
-// Randomness is sampled on the host with this repo's sampling spec (DESIGN.md "Sampling spec":
-// splitmix64-seeded xoshiro256**, ternary secrets, 21-vs-21-bit centred binomial errors, rejection
-// sampled uniform residues) -- SEAL's own PRNG stream is not reproducible by design -- and only the
-// small polynomials travel to the device; all ring arithmetic (NTTs, products, modulus switching)
-// runs in HIP kernels.
+// Randomness follows this repo's two sampling specs (SEAL's own PRNG stream is not reproducible by
+// design).  The seeded spec (splitmix64-seeded xoshiro256**, ternary secrets, 21-vs-21-bit centred binomial errors,
+// rejection sampled uniform residues) is sequential: it is drawn on the host and only the small polynomials travel to the
+// device.  The keyed spec (abc_sample.hpp: counter-based ChaCha20, no rejection) is drawn on the device by
+// abc_kernels_sample.hip; it serves the keyed entry points and, keyed from getrandom(2), the OS-keyed ones.  All ring
+// arithmetic (NTTs, products, modulus switching) runs in HIP kernels either way.
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -21,6 +22,7 @@
 #include "abc_context.hpp"
 #include "abc_crt_lift.hpp"
 #include "abc_host_math.hpp"
+#include "abc_sample.hpp"
 
 namespace abc {
 
@@ -30,9 +32,9 @@ int launch_bfv_decrypt_round(abc_hip_ctx *c, const u64 *phase, u64 *plain, size_
 // Two generators behind one interface.  Rng (splitmix64-seeded xoshiro256**) is this repo's SAMPLING SPEC for parity tests:
 // the oracle implements the same stream, so keys and ciphertexts are bit-comparable -- it is NOT a cryptographic generator
 // (64-bit seed, linear state) and is only reached through the explicitly seeded entry points.  ChaCha (ChaCha20 keyed with
-// 256 bits from getrandom(2)) serves abc_hip_keygen_secure / abc_hip_encrypt_secure, which is what the plugin classes use
-// when no test seed is given: secret material (secret key, errors, encryption randomness) and public material (the uniform
-// `a` polynomials that are published inside the keys) come from independently keyed streams.
+// 256 bits from getrandom(2)) serves abc_hip_keygen_secure / abc_hip_encrypt_secure under ABC_HIP_HOST_SAMPLING=1 (by default
+// they draw on the device: the keyed spec, abc_sample.hpp): secret material (secret key, errors, encryption randomness) and
+// public material (the uniform `a` polynomials that are published inside the keys) come from independently keyed streams.
 struct Sampler {
   virtual uint64_t next() = 0;
   virtual ~Sampler() {}
@@ -208,21 +210,111 @@ __global__ __launch_bounds__(256) void k_enc_mul_pk(DevCtx c, const u64 *u, cons
 }
 
 // ---------------- key generation ----------------
-// pub draws the uniform `a` polynomials (published in the key), sec the errors; the seeded spec passes one generator as both
-// (P, S: the generators' concrete -- final -- types, so the 156 M draws of a key set at N = 2^16 inline and the rejection limit of
-// `uniform` is computed once per prime instead of once per draw)
+// Where the draws of a key set come from: one policy per sampling path, all with the same four members.
+//   begin(c, d_kb)   once the staging buffers exist; d_kb: 2 * kSampleKeyBytes of device memory behind the int8 staging
+//   secret(c, d_e8)  the ternary secret key, N int8 on the device
+//   key(c, stream, nkeys, d_a, d_e8)  the uniform a [nkeys][K][N] (published) and the errors [nkeys][N] (secret) of one key
+//   staged(c)        after the kernels that read d_a / d_e8 are enqueued (a host policy waits: its staging is reused)
+// Sequential generators (the seeded spec, host ChaCha20): pub draws the uniform `a` polynomials, sec the errors; the seeded spec
+// passes one generator as both (P, S: the generators' concrete -- final -- types, so the 156 M draws of a key set at N = 2^16
+// inline and the rejection limit of `uniform` is computed once per prime instead of once per draw)
 template <class P, class S>
-static int make_kskey(abc_hip_ctx *c, P &pub, S &sec, const u64 *d_new_key, u64 *d_key, std::vector<uint64_t> &h_a,
-                      std::vector<int8_t> &h_e, u64 *d_a, int8_t *d_e8, u64 *d_e, int nkeys) {
+struct SequentialDraws {
+  P &pub;
+  S &sec;
+  std::vector<uint64_t> h_a;
+  std::vector<int8_t> h_e;
+  SequentialDraws(P &p, S &s) : pub(p), sec(s) {}
+  ~SequentialDraws() {
+    if (!h_e.empty()) explicit_bzero(h_e.data(), h_e.size());
+  }
+  int begin(abc_hip_ctx *c, void *) {
+    h_a.resize((size_t)c->L * c->K * c->n);
+    h_e.resize((size_t)c->L * c->n);
+    return 0;
+  }
+  int secret(abc_hip_ctx *c, int8_t *d_e8) {
+    const size_t N = (size_t)c->n;
+    for (size_t x = 0; x < N; x++) h_e[x] = sec.ternary();
+    ABC_HIP_CHECK(hipMemcpyAsync(d_e8, h_e.data(), N, hipMemcpyHostToDevice, c->stream));
+    return 0;
+  }
+  int key(abc_hip_ctx *c, uint64_t, int nkeys, u64 *d_a, int8_t *d_e8) {
+    const size_t N = (size_t)c->n;
+    const int K = c->K;
+    for (int i = 0; i < nkeys; i++) {
+      for (int j = 0; j < K; j++)
+        for (size_t x = 0; x < N; x++) h_a[((size_t)i * K + j) * N + x] = pub.uniform(c->primes[j]);
+      for (size_t x = 0; x < N; x++) h_e[(size_t)i * N + x] = sec.cbd();
+    }
+    ABC_HIP_CHECK(hipMemcpyAsync(d_a, h_a.data(), (size_t)nkeys * K * N * 8, hipMemcpyHostToDevice, c->stream));
+    ABC_HIP_CHECK(hipMemcpyAsync(d_e8, h_e.data(), (size_t)nkeys * N, hipMemcpyHostToDevice, c->stream));
+    return 0;
+  }
+  int staged(abc_hip_ctx *c) {
+    ABC_HIP_CHECK(hipStreamSynchronize(c->stream));  // host staging buffers are reused by the next key
+    return 0;
+  }
+};
+// the keyed spec on the device: nothing is staged on the host, and no key costs an upload or a synchronisation
+struct KeyedDraws {
+  const uint8_t *key_sec, *key_pub;
+  const void *d_sec = nullptr, *d_pub = nullptr;
+  int begin(abc_hip_ctx *c, void *d_kb) {
+    d_sec = d_kb;
+    d_pub = (const char *)d_kb + kSampleKeyBytes;
+    return upload_sample_key(c, (void *)d_sec, key_sec, 0) || upload_sample_key(c, (void *)d_pub, key_pub, 0);
+  }
+  int secret(abc_hip_ctx *c, int8_t *d_e8) { return launch_sample_small(c, d_sec, keyed::kStreamSecret, 1, 1, 1, d_e8); }
+  int key(abc_hip_ctx *c, uint64_t stream, int nkeys, u64 *d_a, int8_t *d_e8) {
+    return launch_sample_uniform(c, d_pub, stream, nkeys, d_a) || launch_sample_small(c, d_sec, stream, 1, (size_t)nkeys, 0, d_e8);
+  }
+  int staged(abc_hip_ctx *) { return 0; }
+};
+// the keyed spec on the host (ABC_HIP_HOST_SAMPLING=1): the same words from the host twin, uploaded
+struct KeyedHostDraws {
+  uint32_t sec[8], pub[8];
+  std::vector<uint64_t> h_a;
+  std::vector<int8_t> h_e;
+  KeyedHostDraws(const uint8_t *key_sec, const uint8_t *key_pub) {
+    keyed::load_key(key_sec, sec);
+    keyed::load_key(key_pub, pub);
+  }
+  ~KeyedHostDraws() {
+    explicit_bzero(sec, sizeof(sec));
+    explicit_bzero(pub, sizeof(pub));
+    if (!h_e.empty()) explicit_bzero(h_e.data(), h_e.size());
+  }
+  int begin(abc_hip_ctx *c, void *) {
+    h_a.resize((size_t)c->L * c->K * c->n);
+    h_e.resize((size_t)c->L * c->n);
+    return 0;
+  }
+  int secret(abc_hip_ctx *c, int8_t *d_e8) {
+    keyed::small_host(sec, keyed::kStreamSecret, (size_t)c->n, 1, 1, h_e.data());
+    ABC_HIP_CHECK(hipMemcpyAsync(d_e8, h_e.data(), (size_t)c->n, hipMemcpyHostToDevice, c->stream));
+    return 0;
+  }
+  int key(abc_hip_ctx *c, uint64_t stream, int nkeys, u64 *d_a, int8_t *d_e8) {
+    const size_t N = (size_t)c->n;
+    keyed::uniform_host(pub, stream, N, c->K, c->primes.data(), nkeys, h_a.data());
+    keyed::small_host(sec, stream, N, (size_t)nkeys, 0, h_e.data());
+    ABC_HIP_CHECK(hipMemcpyAsync(d_a, h_a.data(), (size_t)nkeys * c->K * N * 8, hipMemcpyHostToDevice, c->stream));
+    ABC_HIP_CHECK(hipMemcpyAsync(d_e8, h_e.data(), (size_t)nkeys * N, hipMemcpyHostToDevice, c->stream));
+    return 0;
+  }
+  int staged(abc_hip_ctx *c) {
+    ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return 0;
+  }
+};
+
+template <class D>
+static int make_kskey(abc_hip_ctx *c, D &draws, uint64_t stream, const u64 *d_new_key, u64 *d_key, u64 *d_a, int8_t *d_e8, u64 *d_e,
+                      int nkeys) {
   const size_t N = (size_t)c->n;
   const int K = c->K;
-  for (int i = 0; i < nkeys; i++) {
-    for (int j = 0; j < K; j++)
-      for (size_t x = 0; x < N; x++) h_a[((size_t)i * K + j) * N + x] = pub.uniform(c->primes[j]);
-    for (size_t x = 0; x < N; x++) h_e[(size_t)i * N + x] = sec.cbd();
-  }
-  ABC_HIP_CHECK(hipMemcpyAsync(d_a, h_a.data(), (size_t)nkeys * K * N * 8, hipMemcpyHostToDevice, c->stream));
-  ABC_HIP_CHECK(hipMemcpyAsync(d_e8, h_e.data(), (size_t)nkeys * N, hipMemcpyHostToDevice, c->stream));
+  if (draws.key(c, stream, nkeys, d_a, d_e8)) return 1;
   LimbMap kmap{};
   for (int j = 0; j < K; j++) kmap.id[j] = j;
   hipLaunchKernelGGL(k_small_to_rns, dim3(grid_for((size_t)nkeys * K * N, 256)), dim3(256), 0, c->stream, c->dc, d_e8, (size_t)1, N,
@@ -232,39 +324,66 @@ static int make_kskey(abc_hip_ctx *c, P &pub, S &sec, const u64 *d_new_key, u64 
   hipLaunchKernelGGL(k_make_kskey, dim3(grid_for((size_t)nkeys * K * N, 256)), dim3(256), 0, c->stream, c->dc, d_a, d_e, c->d_sk,
                      d_new_key, d_key, nkeys);
   ABC_HIP_CHECK(hipGetLastError());
-  ABC_HIP_CHECK(hipStreamSynchronize(c->stream));  // host staging buffers are reused by the next key
+  return draws.staged(c);
+}
+
+static int getrandom_fill(uint8_t *p, size_t bytes) {
+  size_t got = 0;
+  while (got < bytes) {
+    const ssize_t r = getrandom(p + got, bytes - got, 0);
+    if (r <= 0) return 1;
+    got += (size_t)r;
+  }
   return 0;
 }
 
-template <class P, class S>
-static int keygen_with(abc_hip_ctx *c, P &pub, S &sec);
+template <class D>
+static int keygen_with(abc_hip_ctx *c, D &draws);
 int keygen(abc_hip_ctx *c, uint64_t seed) {
   Rng rng(seed);
-  return keygen_with(c, rng, rng);
+  SequentialDraws<Rng, Rng> draws(rng, rng);
+  return keygen_with(c, draws);
+}
+int keygen_keyed(abc_hip_ctx *c, const uint8_t key_sec[32], const uint8_t key_pub[32]) {
+  if (!key_sec || !key_pub) { set_error("keygen_keyed: null key"); return 1; }
+  if (c->sw.host_sampling) {
+    KeyedHostDraws draws(key_sec, key_pub);
+    return keygen_with(c, draws);
+  }
+  KeyedDraws draws{key_sec, key_pub};
+  return keygen_with(c, draws);
 }
 int keygen_secure(abc_hip_ctx *c) {
-  ChaCha sec(1), pub(2);  // independently keyed: nothing derived from the secret stream is ever published
-  if (!sec.ok || !pub.ok) { set_error("keygen: getrandom failed"); return 1; }
-  return keygen_with(c, pub, sec);
+  if (c->sw.host_sampling) {
+    ChaCha sec(1), pub(2);  // independently keyed: nothing derived from the secret stream is ever published
+    if (!sec.ok || !pub.ok) { set_error("keygen: getrandom failed"); return 1; }
+    SequentialDraws<ChaCha, ChaCha> draws(pub, sec);
+    return keygen_with(c, draws);
+  }
+  uint8_t keys[2][32];  // two independent keys from the operating system: [0] secret material, [1] published material
+  int rc = getrandom_fill(&keys[0][0], sizeof(keys));
+  if (rc) set_error("keygen: getrandom failed");
+  else rc = keygen_keyed(c, keys[0], keys[1]);
+  explicit_bzero(keys, sizeof(keys));
+  return rc;
 }
-template <class P, class S>
-static int keygen_with(abc_hip_ctx *c, P &pub, S &sec) {
+template <class D>
+static int keygen_with(abc_hip_ctx *c, D &draws) {
   const size_t N = (size_t)c->n;
   const int K = c->K, L = c->L;
   LimbMap kmap{};
   for (int j = 0; j < K; j++) kmap.id[j] = j;
-  // staging
-  std::vector<uint64_t> h_a((size_t)L * K * N);
-  std::vector<int8_t> h_e((size_t)L * N);
+  // staging; the sampling keys of the keyed spec sit behind the int8 polynomials and are wiped with them
+  const size_t e8_bytes = (size_t)L * N + 2 * kSampleKeyBytes;
   u64 *d_a = nullptr, *d_e = nullptr, *d_newkey = nullptr;
   int8_t *d_e8 = nullptr;
   ABC_HIP_CHECK(hipMalloc(&d_a, (size_t)L * K * N * 8));
   ABC_HIP_CHECK(hipMalloc(&d_e, (size_t)L * K * N * 8));
-  ABC_HIP_CHECK(hipMalloc(&d_e8, (size_t)L * N));
+  ABC_HIP_CHECK(hipMalloc(&d_e8, e8_bytes));
   ABC_HIP_CHECK(hipMalloc(&d_newkey, (size_t)K * N * 8));
+  if (draws.begin(c, d_e8 + (size_t)L * N)) return 1;
   // secret key
-  for (size_t x = 0; x < N; x++) h_e[x] = sec.ternary();
-  ABC_HIP_CHECK(hipMemcpyAsync(d_e8, h_e.data(), N, hipMemcpyHostToDevice, c->stream));
+  if (draws.secret(c, d_e8)) return 1;
   if (!c->d_sk) ABC_HIP_CHECK(alloc_context_buffer(c, (void **)&c->d_sk, (size_t)K * N * 8, false));
   hipLaunchKernelGGL(k_small_to_rns, dim3(grid_for((size_t)K * N, 256)), dim3(256), 0, c->stream, c->dc, d_e8, (size_t)1, N, (size_t)0,
                      c->d_sk, kmap, K, (size_t)1);
@@ -273,14 +392,14 @@ static int keygen_with(abc_hip_ctx *c, P &pub, S &sec) {
   ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
   // public key = one symmetric encryption of zero at key level
   if (!c->d_pk) ABC_HIP_CHECK(alloc_context_buffer(c, (void **)&c->d_pk, (size_t)2 * K * N * 8, false));
-  if (make_kskey(c, pub, sec, nullptr, c->d_pk, h_a, h_e, d_a, d_e8, d_e, 1)) return 1;
+  if (make_kskey(c, draws, keyed::kStreamPublic, nullptr, c->d_pk, d_a, d_e8, d_e, 1)) return 1;
   // relinearisation key: switches s^2 -> s.  Every key-switching key is regenerated into the buffer it already has, and its
   // mirrors are rebuilt in place at the end: a recorded circuit keeps the addresses it baked in (include/abc_hip.h, graphs).
   if (!c->d_relin) ABC_HIP_CHECK(alloc_context_buffer(c, (void **)&c->d_relin, c->key_words() * 8, false));
   hipLaunchKernelGGL(k_dyadic_mul, dim3(grid_for((size_t)K * N, 256)), dim3(256), 0, c->stream, c->dc, c->d_sk, c->d_sk,
                      (size_t)0, d_newkey, kmap, K, (size_t)1);
   ABC_HIP_CHECK(hipGetLastError());
-  if (make_kskey(c, pub, sec, d_newkey, c->d_relin, h_a, h_e, d_a, d_e8, d_e, L)) return 1;
+  if (make_kskey(c, draws, keyed::kStreamRelin, d_newkey, c->d_relin, d_a, d_e8, d_e, L)) return 1;
   // Galois keys for the default element set (GaloisTool::get_elts_all): 2N-1, then 3^(2^i), 3^-(2^i); an element the caller had
   // loaded outside that set goes
   std::map<uint32_t, uint64_t *> old_galois;
@@ -305,39 +424,142 @@ static int keygen_with(abc_hip_ctx *c, P &pub, S &sec) {
       ABC_HIP_CHECK(alloc_context_buffer(c, (void **)&d_key, c->key_words() * 8, false));
     }
     if (launch_galois(c, c->d_sk, d_newkey, K, 1, elt, true)) return 1;
-    if (make_kskey(c, pub, sec, d_newkey, d_key, h_a, h_e, d_a, d_e8, d_e, L)) return 1;
+    if (make_kskey(c, draws, keyed::galois_stream(elt), d_newkey, d_key, d_a, d_e8, d_e, L)) return 1;
     c->d_galois[elt] = d_key;
     c->galois_order.push_back(elt);
   }
-  // the staging buffers held the secret key, s^2 / g(s) and the errors: wipe before release
+  // the staging buffers held the secret key, s^2 / g(s), the errors and the sampling keys: wipe before release
   (void)hipMemsetAsync(d_e, 0, (size_t)L * K * N * 8, c->stream);
-  (void)hipMemsetAsync(d_e8, 0, (size_t)L * N, c->stream);
+  (void)hipMemsetAsync(d_e8, 0, e8_bytes, c->stream);
   (void)hipMemsetAsync(d_newkey, 0, (size_t)K * N * 8, c->stream);
   ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
   for (auto &kv : old_galois) release_key(c, kv.second);  // held back while a live graph may read it
   refresh_key_mirrors(c, nullptr);
   ABC_HIP_CHECK(hipGetLastError());
-  explicit_bzero(h_e.data(), h_e.size());
   (void)hipFree(d_a); (void)hipFree(d_e); (void)hipFree(d_e8); (void)hipFree(d_newkey);
   return 0;
 }
 
 // ---------------- encryption ----------------
+// workspace of one call: key 64 bytes | small [count][3][N] int8 | u [K][N] | cfull [2][K][N] | err [2][K][N] | prodD [2][L][N] |
+// prodS [2][N] | tmod [2][L][N] (u and everything behind it per ciphertext).  The sampling key of the keyed spec, the draws and
+// everything derived from them before the modulus switch are the first wipe_bytes.
+struct EncryptWs {
+  void *d_kb;
+  int8_t *d_small;
+  u64 *u, *cfull, *err, *prodD, *prodS, *tmod;
+  size_t wipe_bytes;
+};
+static int encrypt_workspace(abc_hip_ctx *c, size_t count, EncryptWs &w) {
+  const size_t N = (size_t)c->n;
+  const size_t K = (size_t)c->K, L = (size_t)c->L;
+  const size_t per_ct_words = (K + 2 * K + 2 * K + 2 * L + 2 + 2 * L) * N;
+  const size_t small_bytes = (count * 3 * N + 7) / 8 * 8;
+  if (ensure_workspace(c, kSampleKeyBytes + small_bytes + count * per_ct_words * 8)) return 1;
+  w.d_kb = c->ws;
+  w.d_small = (int8_t *)c->ws + kSampleKeyBytes;
+  w.u = (u64 *)(w.d_small + small_bytes);
+  w.cfull = w.u + count * K * N;
+  w.err = w.cfull + count * 2 * K * N;
+  w.prodD = w.err + count * 2 * K * N;
+  w.prodS = w.prodD + count * 2 * L * N;
+  w.tmod = w.prodS + count * 2 * N;
+  w.wipe_bytes = kSampleKeyBytes + small_bytes + count * 5 * K * N * 8;
+  return 0;
+}
+// host draws [count][3][N] into the workspace; the host copy is wiped once the upload has completed
+static int upload_small(abc_hip_ctx *c, std::vector<int8_t> &h_small, const EncryptWs &w) {
+  const hipError_t e = hipMemcpyAsync(w.d_small, h_small.data(), h_small.size(), hipMemcpyHostToDevice, c->stream);
+  const hipError_t s = hipStreamSynchronize(c->stream);  // h_small is the caller's local
+  explicit_bzero(h_small.data(), h_small.size());
+  ABC_HIP_CHECK(e);
+  ABC_HIP_CHECK(s);
+  return 0;
+}
+static int encrypt_from_small(abc_hip_ctx *c, const u64 *plain, u64 *ct, size_t count, const EncryptWs &w, bool wipe);
 static int encrypt_with(abc_hip_ctx *c, const u64 *plain, uint64_t seed, Sampler *secure, u64 *ct, size_t count);
+static int no_public_key(const abc_hip_ctx *c) {
+  if (c->d_pk) return 0;
+  set_error("encrypt: no public key (call abc_hip_keygen or abc_hip_load_public_key)");
+  return 1;
+}
 int encrypt(abc_hip_ctx *c, const u64 *plain, uint64_t seed, u64 *ct, size_t count) {
   return encrypt_with(c, plain, seed, nullptr, ct, count);
 }
-int encrypt_secure(abc_hip_ctx *c, const u64 *plain, u64 *ct, size_t count) {
-  ChaCha sec(3);  // a fresh 256-bit key from the operating system per call: nothing is derived from the key seed
-  if (!sec.ok) { set_error("encrypt: getrandom failed"); return 1; }
-  return encrypt_with(c, plain, 0, &sec, ct, count);
+// the keyed spec: ciphertext i takes stream nonce + i; u from words 0 .. N-1 (ternary), e0 and e1 from the 2N words behind (cbd)
+int encrypt_keyed(abc_hip_ctx *c, const u64 *plain, const uint8_t key[32], uint64_t nonce, u64 *ct, size_t count) {
+  if (!key) { set_error("encrypt_keyed: null key"); return 1; }
+  if (no_public_key(c)) return 1;
+  if (!count) return 0;
+  EncryptWs w;
+  if (encrypt_workspace(c, count, w)) return 1;
+  if (c->sw.host_sampling) {
+    const size_t N = (size_t)c->n;
+    std::vector<int8_t> h_small(count * 3 * N);
+    keyed::encrypt_small_host(key, nonce, N, count, h_small.data());
+    if (upload_small(c, h_small, w)) return 1;
+  } else {
+    if (upload_sample_key(c, w.d_kb, key, nonce)) return 1;
+    if (launch_sample_small(c, w.d_kb, 0, count, 3, 1, w.d_small)) return 1;
+  }
+  return encrypt_from_small(c, plain, ct, count, w, true);
 }
-static int encrypt_with(abc_hip_ctx *c, const u64 *plain, uint64_t seed, Sampler *secure, u64 *ct, size_t count) {
-  if (!c->d_pk) { set_error("encrypt: no public key (call abc_hip_keygen or abc_hip_load_public_key)"); return 1; }
+int encrypt_secure(abc_hip_ctx *c, const u64 *plain, u64 *ct, size_t count) {
+  if (c->sw.host_sampling) {
+    ChaCha sec(3);  // a fresh 256-bit key from the operating system per call: nothing is derived from the key seed
+    if (!sec.ok) { set_error("encrypt: getrandom failed"); return 1; }
+    return encrypt_with(c, plain, 0, &sec, ct, count);
+  }
+  uint8_t key[32];  // fresh per call, so every (key, nonce + i) pair is used once
+  int rc = getrandom_fill(key, sizeof(key));
+  if (rc) set_error("encrypt: getrandom failed");
+  else rc = encrypt_keyed(c, plain, key, 0, ct, count);
+  explicit_bzero(key, sizeof(key));
+  return rc;
+}
+// the raw draws of the keyed spec, as encrypt_keyed takes them
+int keyed_small(abc_hip_ctx *c, const uint8_t key[32], uint64_t nonce, int8_t *d_small, size_t count) {
+  if (!key || (!d_small && count)) { set_error("keyed_small: null pointer"); return 1; }
+  if ((uintptr_t)d_small & 7) { set_error("keyed_small: d_small must be 8-byte aligned"); return 1; }
   if (!count) return 0;
   const size_t N = (size_t)c->n;
-  const int K = c->K, L = c->L;
-  const bool ckks = (c->scheme == 2);
+  if (c->sw.host_sampling) {
+    std::vector<int8_t> h_small(count * 3 * N);
+    keyed::encrypt_small_host(key, nonce, N, count, h_small.data());
+    ABC_HIP_CHECK(hipMemcpyAsync(d_small, h_small.data(), h_small.size(), hipMemcpyHostToDevice, c->stream));
+    ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return 0;
+  }
+  if (ensure_workspace(c, kSampleKeyBytes)) return 1;
+  if (upload_sample_key(c, c->ws, key, nonce)) return 1;
+  if (launch_sample_small(c, c->ws, 0, count, 3, 1, d_small)) return 1;
+  ABC_HIP_CHECK(hipMemsetAsync(c->ws, 0, kSampleKeyBytes, c->stream));
+  return 0;
+}
+int keyed_uniform(abc_hip_ctx *c, const uint8_t key[32], uint64_t stream, int nkeys, u64 *d_a) {
+  if (!key || !d_a) { set_error("keyed_uniform: null pointer"); return 1; }
+  if (nkeys < 1 || nkeys > c->L) { set_error("keyed_uniform: nkeys must be between 1 and L"); return 1; }
+  if ((uintptr_t)d_a & 15) { set_error("keyed_uniform: d_a must be 16-byte aligned"); return 1; }
+  if (c->sw.host_sampling) {
+    std::vector<uint64_t> h_a((size_t)nkeys * c->K * c->n);
+    uint32_t k[8];
+    keyed::load_key(key, k);
+    keyed::uniform_host(k, stream, (size_t)c->n, c->K, c->primes.data(), nkeys, h_a.data());
+    explicit_bzero(k, sizeof(k));
+    ABC_HIP_CHECK(hipMemcpyAsync(d_a, h_a.data(), h_a.size() * 8, hipMemcpyHostToDevice, c->stream));
+    ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return 0;
+  }
+  if (ensure_workspace(c, kSampleKeyBytes)) return 1;
+  if (upload_sample_key(c, c->ws, key, 0)) return 1;
+  if (launch_sample_uniform(c, c->ws, stream, nkeys, d_a)) return 1;
+  ABC_HIP_CHECK(hipMemsetAsync(c->ws, 0, kSampleKeyBytes, c->stream));
+  return 0;
+}
+static int encrypt_with(abc_hip_ctx *c, const u64 *plain, uint64_t seed, Sampler *secure, u64 *ct, size_t count) {
+  if (no_public_key(c)) return 1;
+  if (!count) return 0;
+  const size_t N = (size_t)c->n;
   // host sampling: per ciphertext i the stream seed+i yields u, e0, e1 -- independent streams, so a batch is drawn by up to 16
   // host threads (the seeded spec gives the same bytes whatever the thread count; the secure path keys one ChaCha20 instance per
   // worker from the operating system).  Config 5 encrypts 1 125 ciphertexts of 2^16 slots: 221 M draws, 530 ms on one thread.
@@ -381,17 +603,18 @@ static int encrypt_with(abc_hip_ctx *c, const u64 *plain, uint64_t seed, Sampler
     }
     if (failed) { explicit_bzero(h_small.data(), h_small.size()); set_error("encrypt: getrandom failed"); return 1; }
   }
-  // workspace: small 3N bytes | u [K][N] | cfull [2][K][N] | err [2][K][N] | prodD [2][L][N] | prodS [2][N] | tmod [2][L][N]
-  const size_t per_ct_words = (size_t)(K + 2 * K + 2 * K + 2 * L + 2 + 2 * L) * N;
-  const size_t small_bytes = (count * 3 * N + 7) / 8 * 8;
-  if (ensure_workspace(c, small_bytes + count * per_ct_words * 8)) return 1;
-  int8_t *d_small = (int8_t *)c->ws;
-  u64 *u = (u64 *)((char *)c->ws + small_bytes);
-  u64 *cfull = u + count * K * N, *err = cfull + count * 2 * K * N;
-  u64 *prodD = err + count * 2 * K * N, *prodS = prodD + count * 2 * L * N, *tmod = prodS + count * 2 * N;
-  ABC_HIP_CHECK(hipMemcpyAsync(d_small, h_small.data(), count * 3 * N, hipMemcpyHostToDevice, c->stream));
-  ABC_HIP_CHECK(hipStreamSynchronize(c->stream));  // h_small is a local
-  explicit_bzero(h_small.data(), h_small.size());
+  EncryptWs w;
+  if (encrypt_workspace(c, count, w)) return 1;
+  if (upload_small(c, h_small, w)) return 1;
+  return encrypt_from_small(c, plain, ct, count, w, secure != nullptr);
+}
+// ciphertexts from the draws in w.d_small (u | e0 | e1 per ciphertext): everything downstream of the sampling
+static int encrypt_from_small(abc_hip_ctx *c, const u64 *plain, u64 *ct, size_t count, const EncryptWs &w, bool wipe) {
+  const size_t N = (size_t)c->n;
+  const int K = c->K, L = c->L;
+  const bool ckks = (c->scheme == 2);
+  const int8_t *d_small = w.d_small;
+  u64 *u = w.u, *cfull = w.cfull, *err = w.err, *prodD = w.prodD, *prodS = w.prodS, *tmod = w.tmod;
   LimbMap kmap{};
   for (int j = 0; j < K; j++) kmap.id[j] = j;
   // u (poly 0 of each [3][N] triple) -> residues at key level -> NTT
@@ -422,8 +645,9 @@ static int encrypt_with(abc_hip_ctx *c, const u64 *plain, uint64_t seed, Sampler
   const LimbMap dmap = key_limb_map(c, L);
   if (ckks && launch_ntt_fwd(c, tmod, dmap, L, count * 2 * L)) return 1;
   if (launch_ks_finish(c, prodD, tmod, ct, nullptr, 0, false, L, count)) return 1;
-  // the encryption randomness (u, e0, e1 and everything derived before the modulus switch) lives in the workspace: wipe it
-  if (secure) ABC_HIP_CHECK(hipMemsetAsync(c->ws, 0, small_bytes + count * (size_t)(5 * K) * N * 8, c->stream));
+  // the encryption randomness (the sampling key, u, e0, e1 and everything derived before the modulus switch) lives in the
+  // workspace: wipe it
+  if (wipe) ABC_HIP_CHECK(hipMemsetAsync(c->ws, 0, w.wipe_bytes, c->stream));
   // add the message
   if (ckks) return ckks_add_plain(c, ct, plain, (size_t)L * N, ct, 2, L, count, 0);
   return bfv_addsub_plain(c, ct, plain, N, ct, 2, count, 0);

@@ -93,13 +93,20 @@ int abc_hip_memcpy_d2d(abc_hip_ctx *ctx, void *d_dst, const void *d_src, size_t 
 /* ---- keys: replaces seal::KeyGenerator use at SealCiphertextFactory.cpp:89-93 ---- */
 /* generate sk, pk, relin key and all default Galois keys on the device.
  * abc_hip_keygen_secure: what a deployment uses (and HipCiphertextFactory's default): secret key and errors from ChaCha20
- * keyed with 256 bits of getrandom(2), the published uniform polynomials from an independently keyed stream, secret
- * temporaries wiped before release.
+ * keyed with 256 bits of getrandom(2), the published uniform polynomials from an independently keyed stream, drawn on the
+ * device (abc_hip_keygen_keyed below), secret temporaries wiped before release.
  * abc_hip_keygen(seed): TEST ONLY -- the repo's reproducible sampling spec (splitmix64-seeded xoshiro256**),
  * which the CPU oracle implements too so that keys are bit-comparable; a 64-bit seed and a linear generator are not
  * cryptographic strength. */
 int abc_hip_keygen_secure(abc_hip_ctx *ctx);
 int abc_hip_keygen(abc_hip_ctx *ctx, uint64_t seed);
+/* The keyed sampling spec ("Keyed sampling spec"): counter-based ChaCha20, every draw a pure function of
+ * (key, stream id, word number), drawn by HIP kernels.  key_sec serves the secret key and the errors, key_pub the published
+ * uniform polynomials; stream 0 the secret key, 1 the public key, 2 the relinearisation key, 2 + galois_elt a Galois key.
+ * Deterministic given the two keys.  abc_hip_keygen_secure is this call with two fresh 32-byte keys from getrandom(2).
+ * ABC_HIP_HOST_SAMPLING=1 draws the same words on the host (bit-identical keys); for abc_hip_keygen_secure /
+ * abc_hip_encrypt_secure that switch selects the sequential host ChaCha20 sampler instead.  Keys are rewritten in place (graphs). */
+int abc_hip_keygen_keyed(abc_hip_ctx *ctx, const uint8_t key_sec[32], const uint8_t key_pub[32]);
 /* or load externally generated keys (host pointers) */
 int abc_hip_load_secret_key(abc_hip_ctx *ctx, const uint64_t *h_sk /*[L+1][N] NTT*/);
 int abc_hip_load_public_key(abc_hip_ctx *ctx, const uint64_t *h_pk /*[2][L+1][N]*/);
@@ -137,6 +144,17 @@ int abc_hip_ckks_decode(abc_hip_ctx *ctx, const uint64_t *d_plain, int nl, doubl
  * key seed), wiped afterwards.  abc_hip_encrypt(seed): TEST ONLY, ciphertext i uses the reproducible stream seed+i. */
 int abc_hip_encrypt_secure(abc_hip_ctx *ctx, const uint64_t *d_plain, uint64_t *d_ct, size_t count);
 int abc_hip_encrypt(abc_hip_ctx *ctx, const uint64_t *d_plain, uint64_t seed, uint64_t *d_ct, size_t count);
+/* Keyed sampling spec: ciphertext i draws u, e0, e1 from ChaCha20 stream nonce + i (mod 2^64) of `key`, on the device; the key
+ * and the draws are wiped afterwards.  abc_hip_encrypt_secure is this call with a fresh key from getrandom(2) and nonce 0.
+ * Deterministic given (key, nonce): the caller must never reuse a (key, nonce + i) pair. */
+int abc_hip_encrypt_keyed(abc_hip_ctx *ctx, const uint64_t *d_plain, const uint8_t key[32], uint64_t nonce, uint64_t *d_ct,
+                          size_t count);
+/* the raw draws, for parity tests: d_small int8 [count][3][N] (u | e0 | e1), 8-byte aligned */
+int abc_hip_keyed_small(abc_hip_ctx *ctx, const uint8_t key[32], uint64_t nonce, int8_t *d_small, size_t count);
+/* d_a u64 [nkeys][K][N], stream id as in the spec, 1 <= nkeys <= L, 16-byte aligned */
+int abc_hip_keyed_uniform(abc_hip_ctx *ctx, const uint8_t key[32], uint64_t stream, int nkeys, uint64_t *d_a);
+/* host twin of abc_hip_keyed_small, no context and no GPU: h_small int8 [count][3][n], n a multiple of 8 */
+int abc_hip_keyed_small_host(const uint8_t key[32], uint64_t nonce, size_t n, size_t count, int8_t *h_small);
 /* seal::Decryptor::decrypt (SealCiphertextFactory.cpp:150); size = 2 or 3 polynomials */
 int abc_hip_decrypt(abc_hip_ctx *ctx, const uint64_t *d_ct, int size, int nl, uint64_t *d_plain, size_t count);
 /* Decryptor::invariant_noise_budget (SealCiphertext.cpp:80-83): BFV only, secret key required, size = 2 or 3, nl = L.
@@ -191,7 +209,7 @@ int abc_hip_mod_switch(abc_hip_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, 
  * eager per-call dispatch of SpecialRuntimeVisitor, src/runtime/RuntimeVisitor.cpp:40-159).
  * Everything enqueued on the context between begin and end is recorded instead of executed; the sequence must have
  * run once eagerly before (so that no scratch allocation happens while capturing) and may only use device pointers
- * that stay valid for every launch.  abc_hip_encrypt / abc_hip_keygen / *_h2d / *_d2h are not capturable.
+ * that stay valid for every launch.  abc_hip_encrypt* / abc_hip_keygen* / abc_hip_keyed_* / *_h2d / *_d2h are not capturable.
  * Buffers: abc_hip_malloc inside a capture is served from the cache only (never the driver).  Every buffer the recorded
  * sequence can have touched is pinned to the graph until abc_hip_graph_destroy: the blocks the capture itself allocated or
  * freed, and EVERY abc_hip_malloc block of this context that is still out with the caller when abc_hip_graph_end runs (so an

@@ -25,6 +25,8 @@ def rand_ct(g, rng, batch, size, nl):
 
 
 def main():
+    # --only SUBSTRING: the entries whose name contains it (the contexts are still created)
+    only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else ""
     res = {}
     rng = np.random.default_rng(0)
     # ---- CKKS N=2^14, 4 limbs ----
@@ -43,6 +45,8 @@ def main():
         "ckks14_rescale": lambda: g.op("rescale", a.ptr, out.ptr, 2, 4, cb),
     }
     for k, fn in ops.items():
+        if only not in k:
+            continue
         ms = timeit(g, fn)
         res[k] = {"batch": B, "ms": ms, "ops_per_s": B / ms * 1e3}
         print("%-40s %8.3f ms / %d  -> %10.0f op/s" % (k, ms, B, B / ms * 1e3), flush=True)
@@ -66,6 +70,8 @@ def main():
             ("ckks%d_decode_L%d" % (n.bit_length() - 1, nl),
              lambda: g.op("ckks_decode", plain.ptr, nl, C.c_double(2.0 ** 40), re.ptr, im.ptr, cb),
              5 * words + 2 * slots * 8)):
+            if only not in name:
+                continue
             ms = timeit(g, fn)
             gbs = B * nbytes / ms * 1e-6
             res[name] = {"batch": B, "ms": ms, "ops_per_s": B / ms * 1e3, "GB_per_s": gbs, "hbm_fraction": gbs * 1e9 / hbm}
@@ -94,10 +100,28 @@ def main():
         dec, budgets = g.alloc(B * n * 8), (C.c_int * B)()
         ops["bfv%d_decrypt" % n] = lambda: g.op("decrypt", a.ptr, 2, L, dec.ptr, cb)
         ops["bfv%d_noise_budget" % n] = lambda: g.op("noise_budget", a.ptr, 2, L, budgets, cb)
+        # OS-keyed encryption of the batch (abc_hip_encrypt_secure: getrandom + ChaCha20 sampling on the device, or on the host
+        # under ABC_HIP_HOST_SAMPLING=1) and, on the reference's default ring, a whole key set (abc_hip_keygen_secure: batch 1)
+        plains = g.upload(rng.integers(0, g.t, size=(B, n), dtype=np.uint64))
+        ops["bfv%d_encrypt_secure" % n] = lambda: g.op("encrypt_secure", plains.ptr, out.ptr, cb)
+        # the sampling alone, key upload included: the draws of that batch, and the uniform polynomials of one key-switching key
+        key = bytes(range(32))
+        ops["bfv%d_keyed_small(draws of encrypt_secure)" % n] = lambda: g.op("keyed_small", key, C.c_uint64(0), out.ptr, cb)
+        ops["bfv%d_keyed_uniform(one key: L x K limbs)" % n] = lambda: g.op("keyed_uniform", key, C.c_uint64(2), L, out.ptr)
         for k, fn in ops.items():
+            if only not in k:
+                continue
             ms = timeit(g, fn)
             res[k] = {"batch": B, "ms": ms, "ops_per_s": B / ms * 1e3}
             print("%-40s %8.3f ms / %d  -> %10.0f op/s" % (k, ms, B, B / ms * 1e3), flush=True)
+        if n == 16384 and only in "bfv16384_keygen_secure":
+            ms = timeit(g, lambda: g.keygen(None), reps=3)
+            res["bfv16384_keygen_secure"] = {"batch": 1, "ms": ms, "ops_per_s": 1e3 / ms}
+            print("%-40s %8.3f ms (sk, pk, relin, %d Galois keys)" % ("bfv16384_keygen_secure", ms, len(g.galois_elts())), flush=True)
+        if only:
+            del a, b, out, dec, plains
+            g.close()
+            continue
         # single-ciphertext latency (what the C++ plugin shim sees)
         one = C.c_size_t(1)
         ms = timeit(g, lambda: g.op("mul_relin", a.ptr, b.ptr, out.ptr, L, one), reps=20)
@@ -113,7 +137,7 @@ def main():
         g.graph_destroy(ge)
         res["bfv%d_mul_relin_graph_latency_ms" % n] = ms
         print("%-40s %8.3f ms (batch 1, HIP graph replay)" % ("bfv%d_mul_relin latency" % n, ms), flush=True)
-        del a, b, out, dec
+        del a, b, out, dec, plains
         g.close()
     os.makedirs("gpurun_out", exist_ok=True)
     json.dump(res, open("gpurun_out/op_bench.json", "w"), indent=1)

@@ -43,6 +43,19 @@ class Phases:
 
 
 HOST_CODEC = False  # --host-codec: the numpy encoder / decoder (abc_amd/ckks_encoder.py) instead of the device codec
+OS_KEYED = False  # --os-keyed: abc_hip_keygen_secure / abc_hip_encrypt_secure (what the plugin uses) instead of the seeded test spec
+
+
+def keygen(g, seed):
+    """every config verifies against the cleartext computation, none against the oracle's keys: all of them may be OS-keyed"""
+    g.keygen(None if OS_KEYED else seed)
+
+
+def encrypt(g, plain, seed, ct, count):
+    if OS_KEYED:
+        g.op("encrypt_secure", plain.ptr, ct.ptr, count)
+    else:
+        g.op("encrypt", plain.ptr, C.c_uint64(seed), ct.ptr, count)
 
 
 class Ckks:
@@ -53,7 +66,7 @@ class Ckks:
         t0 = time.perf_counter()
         self.n, self.primes = n, capi.create_primes(n, bits)
         self.g = capi.Context(capi.CKKS, n, self.primes, device=device)
-        self.g.keygen(seed)
+        keygen(self.g, seed)
         self.g.sync()
         if ph is not None:
             ph.ms["t_keygen"] += (time.perf_counter() - t0) * 1e3
@@ -71,7 +84,7 @@ class Ckks:
             self.g.op("ckks_encode", vals.ptr, None, C.c_size_t(len(vectors[0])), C.c_double(scale), self.L, buf.ptr,
                       C.c_size_t(len(vectors)))
         ct = self.g.alloc(len(vectors) * 2 * self.L * self.n * 8)
-        self.g.op("encrypt", buf.ptr, C.c_uint64(seed), ct.ptr, C.c_size_t(len(vectors)))
+        encrypt(self.g, buf, seed, ct, C.c_size_t(len(vectors)))
         return ct
 
     def decrypt(self, ct, count, nl, scale):
@@ -113,7 +126,7 @@ def config2(dev, rank, world, batch, ph):
 
     def setup():
         g_ = capi.Context.bfv_default(n, device=dev)
-        g_.keygen(0xABC00001)
+        keygen(g_, 0xABC00001)
         return g_
 
     g = ph.run("t_keygen", None, setup)
@@ -127,7 +140,7 @@ def config2(dev, rank, world, batch, ph):
     def enc(v, seed):
         vb, pl, ct = g.upload(v.astype(np.int64)), g.alloc(cnt * n * 8), g.alloc(cnt * 2 * g.L * n * 8)
         g.op("batch_encode", vb.ptr, pl.ptr, cb)
-        g.op("encrypt", pl.ptr, C.c_uint64(seed), ct.ptr, cb)
+        encrypt(g, pl, seed, ct, cb)
         return ct
 
     cx, cy = ph.run("t_input_encryption", g, lambda: (enc(x, 100 + a0), enc(y, 5000 + a0)))
@@ -236,7 +249,7 @@ def config5(dev, rank, world, batch, ph, bits=None):
     def setup():
         primes = capi.create_primes(n, [bits] * 8 + [bits + 1])
         g_ = capi.Context(capi.BFV, n, primes, t, device=dev)
-        g_.keygen(0xABC00001)
+        keygen(g_, 0xABC00001)
         return g_
 
     g = ph.run("t_keygen", None, setup)
@@ -251,7 +264,7 @@ def config5(dev, rank, world, batch, ph, bits=None):
         for j in range(9):
             vb, pl, ct = g.upload(vals[j].astype(np.int64)), g.alloc(cnt * n * 8), g.alloc(cnt * 2 * g.L * n * 8)
             g.op("batch_encode", vb.ptr, pl.ptr, cb)
-            g.op("encrypt", pl.ptr, C.c_uint64(1000 * j + a0), ct.ptr, cb)
+            encrypt(g, pl, 1000 * j + a0, ct, cb)
             cts_.append(ct)
         return cts_
 
@@ -309,9 +322,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1, help="start this many ranks (one per GPU) from this script itself")
     ap.add_argument("--dry-run-cpu", action="store_true", help="rehearse launch + sharding + gather with gloo on the CPU")
     ap.add_argument("--host-codec", action="store_true", help="CKKS configs: encode / decode in numpy instead of on the device")
+    ap.add_argument("--os-keyed", action="store_true",
+                    help="keys and encryption randomness from the OS-keyed entry points (abc_hip_keygen_secure / abc_hip_encrypt_secure) "
+                         "instead of the seeded test spec; ABC_HIP_HOST_SAMPLING=1 then selects the host sampler for the A/B")
     args = ap.parse_args()
-    global HOST_CODEC
-    HOST_CODEC = args.host_codec
+    global HOST_CODEC, OS_KEYED
+    HOST_CODEC, OS_KEYED = args.host_codec, args.os_keyed
     if args.gpus > 1 and "RANK" not in os.environ:
         # nothing above this line has imported torch or touched HIP: the ranks are fresh processes (abc_amd/launcher.py)
         from abc_amd.launcher import launch_ranks
@@ -332,6 +348,8 @@ def main():
         ph = Phases()
         ok, cnt, dt, digest = fn(dev, rank, world, batch, ph)
         line = {"config": cfg, "rank": rank, "circuits": cnt, "verified": ok, "seconds": dt, "circuits_per_s": cnt / dt}
+        if OS_KEYED:
+            line["os_keyed"] = "host sampling" if os.environ.get("ABC_HIP_HOST_SAMPLING", "0") != "0" else "device sampling"
         line.update({k: round(v, 3) for k, v in ph.ms.items()})  # ms, the reference's CSV columns (ref:examples/main.cpp:41)
         if cfg in GRAPH:  # the same circuit recorded once and replayed as one graph launch (verified: the decrypted result is the replay's)
             line["recorded_replay_circuits_per_s"] = cnt / GRAPH[cfg] if isinstance(GRAPH[cfg], float) else GRAPH[cfg]
