@@ -487,6 +487,17 @@ struct OpRange {
     if (hipSetDevice((c)->device) != hipSuccess) { set_error("hipSetDevice failed"); return 1; } \
   } while (0)
 
+// no exception crosses the C boundary: what() becomes the error text of a failed call
+template <class F>
+static int guarded(F &&body) {
+  try {
+    return body();
+  } catch (const std::exception &e) {
+    set_error(e.what());
+    return 1;
+  }
+}
+
 extern "C" {
 
 const char *abc_hip_last_error(void) { return g_err.c_str(); }
@@ -534,7 +545,7 @@ uint64_t abc_hip_plain_modulus_batching(size_t n, int bits) {
 }
 
 int abc_hip_create_primes(size_t n, const int *bit_sizes, int count, uint64_t *out) {
-  try {
+  return guarded([&] {
     std::map<int, std::vector<uint64_t>> table;
     for (int i = 0; i < count; i++) table[bit_sizes[i]];
     for (auto &kv : table) {
@@ -548,10 +559,7 @@ int abc_hip_create_primes(size_t n, const int *bit_sizes, int count, uint64_t *o
       v.pop_back();
     }
     return 0;
-  } catch (const std::exception &e) {
-    set_error(e.what());
-    return 1;
-  }
+  });
 }
 
 int abc_hip_ctx_create(int scheme, int logn, const uint64_t *primes, int nprimes, uint64_t plain_modulus, int device,
@@ -708,32 +716,17 @@ int abc_hip_memcpy_d2d(abc_hip_ctx *c, void *dst, const void *src, size_t bytes)
 int abc_hip_keygen(abc_hip_ctx *c, uint64_t seed) {
   CTX_GUARD(c);
   NOT_CAPTURABLE(c, "abc_hip_keygen");
-  try {
-    return keygen(c, seed);
-  } catch (const std::exception &e) {
-    set_error(e.what());
-    return 1;
-  }
+  return guarded([&] { return keygen(c, seed); });
 }
 int abc_hip_keygen_secure(abc_hip_ctx *c) {
   CTX_GUARD(c);
   NOT_CAPTURABLE(c, "abc_hip_keygen_secure");
-  try {
-    return keygen_secure(c);
-  } catch (const std::exception &e) {
-    set_error(e.what());
-    return 1;
-  }
+  return guarded([&] { return keygen_secure(c); });
 }
 int abc_hip_keygen_keyed(abc_hip_ctx *c, const uint8_t key_sec[32], const uint8_t key_pub[32]) {
   CTX_GUARD(c);
   NOT_CAPTURABLE(c, "abc_hip_keygen_keyed");
-  try {
-    return keygen_keyed(c, key_sec, key_pub);
-  } catch (const std::exception &e) {
-    set_error(e.what());
-    return 1;
-  }
+  return guarded([&] { return keygen_keyed(c, key_sec, key_pub); });
 }
 // A key is rewritten in place, and so are its mirrors: a recorded circuit keeps the addresses it baked in and reads the new key on
 // its next replay.  Work already enqueued (a replay among it) finishes on the old words first: the stream is non-blocking, so the
@@ -797,22 +790,22 @@ int abc_hip_ckks_decode(abc_hip_ctx *c, const uint64_t *p, int nl, double scale,
   NOT_CAPTURABLE(c, "abc_hip_ckks_decode");
   return ckks_decode(c, p, nl, scale, re, im, count);
 }
-int abc_hip_encrypt(abc_hip_ctx *c, const uint64_t *p, uint64_t seed, uint64_t *ct, size_t count) { CTX_GUARD(c); NOT_CAPTURABLE(c, "abc_hip_encrypt"); return encrypt(c, p, seed, ct, count); }
-int abc_hip_encrypt_secure(abc_hip_ctx *c, const uint64_t *p, uint64_t *ct, size_t count) { CTX_GUARD(c); NOT_CAPTURABLE(c, "abc_hip_encrypt_secure"); return encrypt_secure(c, p, ct, count); }
+int abc_hip_encrypt(abc_hip_ctx *c, const uint64_t *p, uint64_t seed, uint64_t *ct, size_t count) { CTX_GUARD(c); NOT_CAPTURABLE(c, "abc_hip_encrypt"); return guarded([&] { return encrypt(c, p, seed, ct, count); }); }
+int abc_hip_encrypt_secure(abc_hip_ctx *c, const uint64_t *p, uint64_t *ct, size_t count) { CTX_GUARD(c); NOT_CAPTURABLE(c, "abc_hip_encrypt_secure"); return guarded([&] { return encrypt_secure(c, p, ct, count); }); }
 int abc_hip_encrypt_keyed(abc_hip_ctx *c, const uint64_t *p, const uint8_t key[32], uint64_t nonce, uint64_t *ct, size_t count) {
   CTX_GUARD(c);
   NOT_CAPTURABLE(c, "abc_hip_encrypt_keyed");
-  return encrypt_keyed(c, p, key, nonce, ct, count);
+  return guarded([&] { return encrypt_keyed(c, p, key, nonce, ct, count); });
 }
 int abc_hip_keyed_small(abc_hip_ctx *c, const uint8_t key[32], uint64_t nonce, int8_t *d_small, size_t count) {
   CTX_GUARD(c);
   NOT_CAPTURABLE(c, "abc_hip_keyed_small");
-  return keyed_small(c, key, nonce, d_small, count);
+  return guarded([&] { return keyed_small(c, key, nonce, d_small, count); });
 }
 int abc_hip_keyed_uniform(abc_hip_ctx *c, const uint8_t key[32], uint64_t stream, int nkeys, uint64_t *d_a) {
   CTX_GUARD(c);
   NOT_CAPTURABLE(c, "abc_hip_keyed_uniform");
-  return keyed_uniform(c, key, stream, nkeys, d_a);
+  return guarded([&] { return keyed_uniform(c, key, stream, nkeys, d_a); });
 }
 int abc_hip_keyed_small_host(const uint8_t key[32], uint64_t nonce, size_t n, size_t count, int8_t *h_small) {
   if (!key || (!h_small && count)) { set_error("keyed_small_host: null pointer"); return 1; }

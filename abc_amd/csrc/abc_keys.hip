@@ -7,13 +7,13 @@
 //   :150    seal::Decryptor::decrypt                                           -> decrypt
 // and src/runtime/SealCiphertext.cpp:80-83 seal::Decryptor::invariant_noise_budget -> noise_budget
 // Randomness follows this repo's two sampling specs (SEAL's own PRNG stream is not reproducible by
-// design).  The seeded spec (splitmix64-seeded xoshiro256**, ternary secrets, 21-vs-21-bit centred binomial errors,
+// design).  The seeded spec (Rng below: splitmix64-seeded xoshiro256**, ternary secrets, 21-vs-21-bit centred binomial errors,
 // rejection sampled uniform residues) is sequential: it is drawn on the host and only the small polynomials travel to the
-// device.  The keyed spec (abc_sample.hpp: counter-based ChaCha20, no rejection) is drawn on the device by
-// abc_kernels_sample.hip; it serves the keyed entry points and, keyed from getrandom(2), the OS-keyed ones.  All ring
-// arithmetic (NTTs, products, modulus switching) runs in HIP kernels either way.
+// device.  The keyed spec (abc_sample.hpp: counter-based ChaCha20, no rejection, the library's only cipher) is drawn on the
+// device by abc_kernels_sample.hip, or word for word by its host twin under ABC_HIP_HOST_SAMPLING=1; it serves the keyed entry
+// points, and the OS-keyed ones are the keyed ones under keys from getrandom(2).  All ring arithmetic (NTTs, products, modulus
+// switching) runs in HIP kernels either way.
 #include <algorithm>
-#include <atomic>
 #include <cstring>
 #include <sys/random.h>
 #include <thread>
@@ -29,33 +29,11 @@ namespace abc {
 int launch_bfv_decrypt_round(abc_hip_ctx *c, const u64 *phase, u64 *plain, size_t count);
 
 // ---------------- host samplers ----------------
-// Two generators behind one interface.  Rng (splitmix64-seeded xoshiro256**) is this repo's SAMPLING SPEC for parity tests:
-// the oracle implements the same stream, so keys and ciphertexts are bit-comparable -- it is NOT a cryptographic generator
-// (64-bit seed, linear state) and is only reached through the explicitly seeded entry points.  ChaCha (ChaCha20 keyed with
-// 256 bits from getrandom(2)) serves abc_hip_keygen_secure / abc_hip_encrypt_secure under ABC_HIP_HOST_SAMPLING=1 (by default
-// they draw on the device: the keyed spec, abc_sample.hpp): secret material (secret key, errors, encryption randomness) and
-// public material (the uniform `a` polynomials that are published inside the keys) come from independently keyed streams.
-struct Sampler {
-  virtual uint64_t next() = 0;
-  virtual ~Sampler() {}
-  int8_t ternary() {
-    for (;;) {
-      const uint64_t x = next();
-      if (x != ~0ull) return (int8_t)((int)(x % 3) - 1);
-    }
-  }
-  int8_t cbd() {
-    const uint64_t x = next();
-    return (int8_t)(__builtin_popcountll(x & 0x1FFFFF) - __builtin_popcountll((x >> 21) & 0x1FFFFF));
-  }
-  uint64_t uniform(uint64_t q) {
-    const uint64_t lim = ~0ull - (~0ull % q) - 1;
-    uint64_t x;
-    do x = next(); while (x >= lim);
-    return x % q;
-  }
-};
-struct Rng final : Sampler {
+// Rng (splitmix64-seeded xoshiro256**) is this repo's SAMPLING SPEC for parity tests: the oracle implements the same stream, so
+// keys and ciphertexts are bit-comparable -- it is NOT a cryptographic generator (64-bit seed, linear state) and is only reached
+// through the explicitly seeded entry points.  A plain struct: every draw inlines into its loop.  Everything else (the keyed and
+// the OS-keyed entry points) draws the keyed spec of abc_sample.hpp, whose host twin needs no generator state.
+struct Rng {
   uint64_t s[4];
   explicit Rng(uint64_t seed) {
     uint64_t x = seed;
@@ -67,64 +45,50 @@ struct Rng final : Sampler {
     }
   }
   static uint64_t rotl(uint64_t v, int k) { return (v << k) | (v >> (64 - k)); }
-  uint64_t next() override {
+  uint64_t next() {
     const uint64_t r = rotl(s[1] * 5, 7) * 9, t = s[1] << 17;
     s[2] ^= s[0]; s[3] ^= s[1]; s[1] ^= s[2]; s[0] ^= s[3];
     s[2] ^= t;
     s[3] = rotl(s[3], 45);
     return r;
   }
-};
-// ChaCha20 (RFC 8439 block function) as a deterministic random bit generator: 256-bit key from the operating system,
-// 64-bit block counter, 64-bit stream id
-struct ChaCha final : Sampler {
-  uint32_t key[8], buf[16];
-  uint64_t counter = 0, stream;
-  int pos = 16;
-  bool ok = false;
-  explicit ChaCha(uint64_t stream_id) : stream(stream_id) {
-    size_t got = 0;
-    unsigned char *k = reinterpret_cast<unsigned char *>(key);
-    while (got < sizeof(key)) {
-      const ssize_t r = getrandom(k + got, sizeof(key) - got, 0);
-      if (r <= 0) return;
-      got += (size_t)r;
+  int8_t ternary() {
+    for (;;) {
+      const uint64_t x = next();
+      if (x != ~0ull) return (int8_t)((int)(x % 3) - 1);
     }
-    ok = true;
   }
-  ~ChaCha() override {
-    explicit_bzero(key, sizeof(key));
-    explicit_bzero(buf, sizeof(buf));
+  int8_t cbd() {
+    const uint64_t x = next();
+    return (int8_t)(__builtin_popcountll(x & 0x1FFFFF) - __builtin_popcountll((x >> 21) & 0x1FFFFF));
   }
-  static uint32_t rotl32(uint32_t v, int k) { return (v << k) | (v >> (32 - k)); }
-  static void qr(uint32_t &a, uint32_t &b, uint32_t &c, uint32_t &d) {
-    a += b; d ^= a; d = rotl32(d, 16);
-    c += d; b ^= c; b = rotl32(b, 12);
-    a += b; d ^= a; d = rotl32(d, 8);
-    c += d; b ^= c; b = rotl32(b, 7);
-  }
-  void refill() {
-    uint32_t st[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u};
-    for (int i = 0; i < 8; i++) st[4 + i] = key[i];
-    st[12] = (uint32_t)counter; st[13] = (uint32_t)(counter >> 32);
-    st[14] = (uint32_t)stream; st[15] = (uint32_t)(stream >> 32);
-    uint32_t x[16];
-    for (int i = 0; i < 16; i++) x[i] = st[i];
-    for (int r = 0; r < 10; r++) {
-      qr(x[0], x[4], x[8], x[12]); qr(x[1], x[5], x[9], x[13]); qr(x[2], x[6], x[10], x[14]); qr(x[3], x[7], x[11], x[15]);
-      qr(x[0], x[5], x[10], x[15]); qr(x[1], x[6], x[11], x[12]); qr(x[2], x[7], x[8], x[13]); qr(x[3], x[4], x[9], x[14]);
-    }
-    for (int i = 0; i < 16; i++) buf[i] = x[i] + st[i];
-    counter++;
-    pos = 0;
-  }
-  uint64_t next() override {
-    if (pos >= 16) refill();
-    const uint64_t v = (uint64_t)buf[pos] | ((uint64_t)buf[pos + 1] << 32);
-    pos += 2;
-    return v;
+  // uniform residue modulo q by rejection; lim = reject_limit(q), which a caller computes once per prime, not once per draw
+  static uint64_t reject_limit(uint64_t q) { return ~0ull - (~0ull % q) - 1; }
+  uint64_t uniform(uint64_t q, uint64_t lim) {
+    uint64_t x;
+    do x = next(); while (x >= lim);
+    return x % q;
   }
 };
+
+static int getrandom_fill(uint8_t *p, size_t bytes) {
+  size_t got = 0;
+  while (got < bytes) {
+    const ssize_t r = getrandom(p + got, bytes - got, 0);
+    if (r <= 0) return 1;
+    got += (size_t)r;
+  }
+  return 0;
+}
+// host draws to the device; the host copy is wiped once the upload has completed
+static int upload_wiped(abc_hip_ctx *c, void *dst, void *h, size_t bytes) {
+  const hipError_t e = hipMemcpyAsync(dst, h, bytes, hipMemcpyHostToDevice, c->stream);
+  const hipError_t s = hipStreamSynchronize(c->stream);  // h is the caller's local
+  explicit_bzero(h, bytes);
+  ABC_HIP_CHECK(e);
+  ABC_HIP_CHECK(s);
+  return 0;
+}
 
 // ---------------- kernels ----------------
 // small signed polynomial [polys][N] (int8) -> residues [polys][nlm][N] for the mapped moduli
@@ -210,22 +174,23 @@ __global__ __launch_bounds__(256) void k_enc_mul_pk(DevCtx c, const u64 *u, cons
 }
 
 // ---------------- key generation ----------------
-// Where the draws of a key set come from: one policy per sampling path, all with the same four members.
+// Where the draws of a key set come from: one policy per sampling path (seeded host, keyed host, keyed device), all with the
+// same four members.
 //   begin(c, d_kb)   once the staging buffers exist; d_kb: 2 * kSampleKeyBytes of device memory behind the int8 staging
 //   secret(c, d_e8)  the ternary secret key, N int8 on the device
 //   key(c, stream, nkeys, d_a, d_e8)  the uniform a [nkeys][K][N] (published) and the errors [nkeys][N] (secret) of one key
 //   staged(c)        after the kernels that read d_a / d_e8 are enqueued (a host policy waits: its staging is reused)
-// Sequential generators (the seeded spec, host ChaCha20): pub draws the uniform `a` polynomials, sec the errors; the seeded spec
-// passes one generator as both (P, S: the generators' concrete -- final -- types, so the 156 M draws of a key set at N = 2^16
-// inline and the rejection limit of `uniform` is computed once per prime instead of once per draw)
-template <class P, class S>
-struct SequentialDraws {
-  P &pub;
-  S &sec;
+// The two host policies are HostDraws over a Fill: the staging, the uploads and the wipes are one body, and a Fill (plain data:
+// it is wiped byte-wise) only says how the words come about -- secret(c, e) and key(c, stream, nkeys, a, e) into host memory.
+template <class Fill>
+struct HostDraws {
+  Fill fill;
   std::vector<uint64_t> h_a;
   std::vector<int8_t> h_e;
-  SequentialDraws(P &p, S &s) : pub(p), sec(s) {}
-  ~SequentialDraws() {
+  template <class... A>
+  explicit HostDraws(A &&...a) : fill(a...) {}  // in place: no second copy of a key to wipe
+  ~HostDraws() {
+    explicit_bzero(&fill, sizeof(fill));  // generator state or sampling keys
     if (!h_e.empty()) explicit_bzero(h_e.data(), h_e.size());
   }
   int begin(abc_hip_ctx *c, void *) {
@@ -234,26 +199,57 @@ struct SequentialDraws {
     return 0;
   }
   int secret(abc_hip_ctx *c, int8_t *d_e8) {
-    const size_t N = (size_t)c->n;
-    for (size_t x = 0; x < N; x++) h_e[x] = sec.ternary();
-    ABC_HIP_CHECK(hipMemcpyAsync(d_e8, h_e.data(), N, hipMemcpyHostToDevice, c->stream));
+    fill.secret(c, h_e.data());
+    ABC_HIP_CHECK(hipMemcpyAsync(d_e8, h_e.data(), (size_t)c->n, hipMemcpyHostToDevice, c->stream));
     return 0;
   }
-  int key(abc_hip_ctx *c, uint64_t, int nkeys, u64 *d_a, int8_t *d_e8) {
+  int key(abc_hip_ctx *c, uint64_t stream, int nkeys, u64 *d_a, int8_t *d_e8) {
     const size_t N = (size_t)c->n;
-    const int K = c->K;
-    for (int i = 0; i < nkeys; i++) {
-      for (int j = 0; j < K; j++)
-        for (size_t x = 0; x < N; x++) h_a[((size_t)i * K + j) * N + x] = pub.uniform(c->primes[j]);
-      for (size_t x = 0; x < N; x++) h_e[(size_t)i * N + x] = sec.cbd();
-    }
-    ABC_HIP_CHECK(hipMemcpyAsync(d_a, h_a.data(), (size_t)nkeys * K * N * 8, hipMemcpyHostToDevice, c->stream));
+    fill.key(c, stream, nkeys, h_a.data(), h_e.data());
+    ABC_HIP_CHECK(hipMemcpyAsync(d_a, h_a.data(), (size_t)nkeys * c->K * N * 8, hipMemcpyHostToDevice, c->stream));
     ABC_HIP_CHECK(hipMemcpyAsync(d_e8, h_e.data(), (size_t)nkeys * N, hipMemcpyHostToDevice, c->stream));
     return 0;
   }
   int staged(abc_hip_ctx *c) {
     ABC_HIP_CHECK(hipStreamSynchronize(c->stream));  // host staging buffers are reused by the next key
     return 0;
+  }
+};
+// the seeded spec: one sequential stream, in the order secret key, then per key a_i (limb by limb), e_i
+struct SeededFill {
+  Rng rng;
+  explicit SeededFill(uint64_t seed) : rng(seed) {}
+  void secret(const abc_hip_ctx *c, int8_t *e) {
+    for (size_t x = 0; x < (size_t)c->n; x++) e[x] = rng.ternary();
+  }
+  void key(const abc_hip_ctx *c, uint64_t, int nkeys, uint64_t *a, int8_t *e) {
+    const size_t N = (size_t)c->n;
+    const int K = c->K;
+    for (int i = 0; i < nkeys; i++) {
+      for (int j = 0; j < K; j++) {  // 156 M draws for a key set at N = 2^16: the rejection limit once per prime
+        const uint64_t q = c->primes[j], lim = Rng::reject_limit(q);
+        uint64_t *row = a + ((size_t)i * K + j) * N;
+        for (size_t x = 0; x < N; x++) row[x] = rng.uniform(q, lim);
+      }
+      for (size_t x = 0; x < N; x++) e[(size_t)i * N + x] = rng.cbd();
+    }
+  }
+};
+// host twin of launch_sample_uniform: a [nkeys][K][N] of (key words, stream)
+static void sample_uniform_host(const abc_hip_ctx *c, const uint32_t k[8], uint64_t stream, int nkeys, uint64_t *a) {
+  keyed::uniform_host(k, stream, (size_t)c->n, c->K, c->primes.data(), nkeys, a);
+}
+// the keyed spec on the host (ABC_HIP_HOST_SAMPLING=1): the same words as KeyedDraws from the host twin
+struct KeyedHostFill {
+  uint32_t sec[8], pub[8];
+  KeyedHostFill(const uint8_t key_sec[32], const uint8_t key_pub[32]) {
+    keyed::load_key(key_sec, sec);
+    keyed::load_key(key_pub, pub);
+  }
+  void secret(const abc_hip_ctx *c, int8_t *e) { keyed::small_host(sec, keyed::kStreamSecret, (size_t)c->n, 1, 1, e); }
+  void key(const abc_hip_ctx *c, uint64_t stream, int nkeys, uint64_t *a, int8_t *e) {
+    sample_uniform_host(c, pub, stream, nkeys, a);
+    keyed::small_host(sec, stream, (size_t)c->n, (size_t)nkeys, 0, e);
   }
 };
 // the keyed spec on the device: nothing is staged on the host, and no key costs an upload or a synchronisation
@@ -271,135 +267,87 @@ struct KeyedDraws {
   }
   int staged(abc_hip_ctx *) { return 0; }
 };
-// the keyed spec on the host (ABC_HIP_HOST_SAMPLING=1): the same words from the host twin, uploaded
-struct KeyedHostDraws {
-  uint32_t sec[8], pub[8];
-  std::vector<uint64_t> h_a;
-  std::vector<int8_t> h_e;
-  KeyedHostDraws(const uint8_t *key_sec, const uint8_t *key_pub) {
-    keyed::load_key(key_sec, sec);
-    keyed::load_key(key_pub, pub);
-  }
-  ~KeyedHostDraws() {
-    explicit_bzero(sec, sizeof(sec));
-    explicit_bzero(pub, sizeof(pub));
-    if (!h_e.empty()) explicit_bzero(h_e.data(), h_e.size());
-  }
-  int begin(abc_hip_ctx *c, void *) {
-    h_a.resize((size_t)c->L * c->K * c->n);
-    h_e.resize((size_t)c->L * c->n);
+
+// The device staging of one key generation: a [L][K][N] | e in residues [L][K][N] | e as int8 [L][N], the two sampling keys of the
+// keyed spec behind it | new key [K][N].  All but a hold secret material (the secret key, s^2 / g(s), the errors, the sampling
+// keys): however keygen_with ends, they are zeroed on the stream before they are freed.  Reports nothing: a failure on this way
+// out cannot be acted on.
+struct KeygenStaging {
+  abc_hip_ctx *c;
+  const size_t ae_bytes, e8_bytes, newkey_bytes;
+  u64 *d_a = nullptr, *d_e = nullptr, *d_newkey = nullptr;
+  int8_t *d_e8 = nullptr;
+  bool wiped = false;
+  explicit KeygenStaging(abc_hip_ctx *ctx)
+      : c(ctx), ae_bytes((size_t)c->L * c->K * c->n * 8), e8_bytes((size_t)c->L * c->n + 2 * kSampleKeyBytes),
+        newkey_bytes((size_t)c->K * c->n * 8) {}
+  KeygenStaging(const KeygenStaging &) = delete;
+  KeygenStaging &operator=(const KeygenStaging &) = delete;
+  int alloc() {
+    ABC_HIP_CHECK(hipMalloc(&d_a, ae_bytes));
+    ABC_HIP_CHECK(hipMalloc(&d_e, ae_bytes));
+    ABC_HIP_CHECK(hipMalloc(&d_e8, e8_bytes));
+    ABC_HIP_CHECK(hipMalloc(&d_newkey, newkey_bytes));
     return 0;
   }
-  int secret(abc_hip_ctx *c, int8_t *d_e8) {
-    keyed::small_host(sec, keyed::kStreamSecret, (size_t)c->n, 1, 1, h_e.data());
-    ABC_HIP_CHECK(hipMemcpyAsync(d_e8, h_e.data(), (size_t)c->n, hipMemcpyHostToDevice, c->stream));
-    return 0;
+  void *sample_keys() const { return d_e8 + (e8_bytes - 2 * kSampleKeyBytes); }
+  hipError_t wipe() {
+    wiped = true;
+    if (d_e) (void)hipMemsetAsync(d_e, 0, ae_bytes, c->stream);
+    if (d_e8) (void)hipMemsetAsync(d_e8, 0, e8_bytes, c->stream);
+    if (d_newkey) (void)hipMemsetAsync(d_newkey, 0, newkey_bytes, c->stream);
+    return hipStreamSynchronize(c->stream);
   }
-  int key(abc_hip_ctx *c, uint64_t stream, int nkeys, u64 *d_a, int8_t *d_e8) {
-    const size_t N = (size_t)c->n;
-    keyed::uniform_host(pub, stream, N, c->K, c->primes.data(), nkeys, h_a.data());
-    keyed::small_host(sec, stream, N, (size_t)nkeys, 0, h_e.data());
-    ABC_HIP_CHECK(hipMemcpyAsync(d_a, h_a.data(), (size_t)nkeys * c->K * N * 8, hipMemcpyHostToDevice, c->stream));
-    ABC_HIP_CHECK(hipMemcpyAsync(d_e8, h_e.data(), (size_t)nkeys * N, hipMemcpyHostToDevice, c->stream));
-    return 0;
-  }
-  int staged(abc_hip_ctx *c) {
-    ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return 0;
+  ~KeygenStaging() {
+    if (!wiped) (void)wipe();
+    (void)hipFree(d_a); (void)hipFree(d_e); (void)hipFree(d_e8); (void)hipFree(d_newkey);
   }
 };
 
 template <class D>
-static int make_kskey(abc_hip_ctx *c, D &draws, uint64_t stream, const u64 *d_new_key, u64 *d_key, u64 *d_a, int8_t *d_e8, u64 *d_e,
+static int make_kskey(abc_hip_ctx *c, D &draws, uint64_t stream, const u64 *d_new_key, u64 *d_key, const KeygenStaging &st,
                       int nkeys) {
   const size_t N = (size_t)c->n;
   const int K = c->K;
-  if (draws.key(c, stream, nkeys, d_a, d_e8)) return 1;
-  LimbMap kmap{};
-  for (int j = 0; j < K; j++) kmap.id[j] = j;
-  hipLaunchKernelGGL(k_small_to_rns, dim3(grid_for((size_t)nkeys * K * N, 256)), dim3(256), 0, c->stream, c->dc, d_e8, (size_t)1, N,
-                     (size_t)0, d_e, kmap, K, (size_t)nkeys);
+  if (draws.key(c, stream, nkeys, st.d_a, st.d_e8)) return 1;
+  const LimbMap kmap = key_limb_map(c, c->L);  // the identity over the K key limbs
+  hipLaunchKernelGGL(k_small_to_rns, dim3(grid_for((size_t)nkeys * K * N, 256)), dim3(256), 0, c->stream, c->dc, st.d_e8, (size_t)1,
+                     N, (size_t)0, st.d_e, kmap, K, (size_t)nkeys);
   ABC_HIP_CHECK(hipGetLastError());
-  if (launch_ntt_fwd(c, d_e, kmap, K, (size_t)nkeys * K)) return 1;
-  hipLaunchKernelGGL(k_make_kskey, dim3(grid_for((size_t)nkeys * K * N, 256)), dim3(256), 0, c->stream, c->dc, d_a, d_e, c->d_sk,
-                     d_new_key, d_key, nkeys);
+  if (launch_ntt_fwd(c, st.d_e, kmap, K, (size_t)nkeys * K)) return 1;
+  hipLaunchKernelGGL(k_make_kskey, dim3(grid_for((size_t)nkeys * K * N, 256)), dim3(256), 0, c->stream, c->dc, st.d_a, st.d_e,
+                     c->d_sk, d_new_key, d_key, nkeys);
   ABC_HIP_CHECK(hipGetLastError());
   return draws.staged(c);
 }
 
-static int getrandom_fill(uint8_t *p, size_t bytes) {
-  size_t got = 0;
-  while (got < bytes) {
-    const ssize_t r = getrandom(p + got, bytes - got, 0);
-    if (r <= 0) return 1;
-    got += (size_t)r;
-  }
-  return 0;
-}
-
-template <class D>
-static int keygen_with(abc_hip_ctx *c, D &draws);
-int keygen(abc_hip_ctx *c, uint64_t seed) {
-  Rng rng(seed);
-  SequentialDraws<Rng, Rng> draws(rng, rng);
-  return keygen_with(c, draws);
-}
-int keygen_keyed(abc_hip_ctx *c, const uint8_t key_sec[32], const uint8_t key_pub[32]) {
-  if (!key_sec || !key_pub) { set_error("keygen_keyed: null key"); return 1; }
-  if (c->sw.host_sampling) {
-    KeyedHostDraws draws(key_sec, key_pub);
-    return keygen_with(c, draws);
-  }
-  KeyedDraws draws{key_sec, key_pub};
-  return keygen_with(c, draws);
-}
-int keygen_secure(abc_hip_ctx *c) {
-  if (c->sw.host_sampling) {
-    ChaCha sec(1), pub(2);  // independently keyed: nothing derived from the secret stream is ever published
-    if (!sec.ok || !pub.ok) { set_error("keygen: getrandom failed"); return 1; }
-    SequentialDraws<ChaCha, ChaCha> draws(pub, sec);
-    return keygen_with(c, draws);
-  }
-  uint8_t keys[2][32];  // two independent keys from the operating system: [0] secret material, [1] published material
-  int rc = getrandom_fill(&keys[0][0], sizeof(keys));
-  if (rc) set_error("keygen: getrandom failed");
-  else rc = keygen_keyed(c, keys[0], keys[1]);
-  explicit_bzero(keys, sizeof(keys));
-  return rc;
-}
 template <class D>
 static int keygen_with(abc_hip_ctx *c, D &draws) {
   const size_t N = (size_t)c->n;
   const int K = c->K, L = c->L;
-  LimbMap kmap{};
-  for (int j = 0; j < K; j++) kmap.id[j] = j;
-  // staging; the sampling keys of the keyed spec sit behind the int8 polynomials and are wiped with them
-  const size_t e8_bytes = (size_t)L * N + 2 * kSampleKeyBytes;
-  u64 *d_a = nullptr, *d_e = nullptr, *d_newkey = nullptr;
-  int8_t *d_e8 = nullptr;
-  ABC_HIP_CHECK(hipMalloc(&d_a, (size_t)L * K * N * 8));
-  ABC_HIP_CHECK(hipMalloc(&d_e, (size_t)L * K * N * 8));
-  ABC_HIP_CHECK(hipMalloc(&d_e8, e8_bytes));
-  ABC_HIP_CHECK(hipMalloc(&d_newkey, (size_t)K * N * 8));
-  if (draws.begin(c, d_e8 + (size_t)L * N)) return 1;
+  const LimbMap kmap = key_limb_map(c, L);
+  KeygenStaging st(c);
+  if (st.alloc()) return 1;
+  u64 *const d_newkey = st.d_newkey;
+  if (draws.begin(c, st.sample_keys())) return 1;
   // secret key
-  if (draws.secret(c, d_e8)) return 1;
+  if (draws.secret(c, st.d_e8)) return 1;
   if (!c->d_sk) ABC_HIP_CHECK(alloc_context_buffer(c, (void **)&c->d_sk, (size_t)K * N * 8, false));
-  hipLaunchKernelGGL(k_small_to_rns, dim3(grid_for((size_t)K * N, 256)), dim3(256), 0, c->stream, c->dc, d_e8, (size_t)1, N, (size_t)0,
-                     c->d_sk, kmap, K, (size_t)1);
+  hipLaunchKernelGGL(k_small_to_rns, dim3(grid_for((size_t)K * N, 256)), dim3(256), 0, c->stream, c->dc, st.d_e8, (size_t)1, N,
+                     (size_t)0, c->d_sk, kmap, K, (size_t)1);
   ABC_HIP_CHECK(hipGetLastError());
   if (launch_ntt_fwd(c, c->d_sk, kmap, K, K)) return 1;
   ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
   // public key = one symmetric encryption of zero at key level
   if (!c->d_pk) ABC_HIP_CHECK(alloc_context_buffer(c, (void **)&c->d_pk, (size_t)2 * K * N * 8, false));
-  if (make_kskey(c, draws, keyed::kStreamPublic, nullptr, c->d_pk, d_a, d_e8, d_e, 1)) return 1;
+  if (make_kskey(c, draws, keyed::kStreamPublic, nullptr, c->d_pk, st, 1)) return 1;
   // relinearisation key: switches s^2 -> s.  Every key-switching key is regenerated into the buffer it already has, and its
   // mirrors are rebuilt in place at the end: a recorded circuit keeps the addresses it baked in (include/abc_hip.h, graphs).
   if (!c->d_relin) ABC_HIP_CHECK(alloc_context_buffer(c, (void **)&c->d_relin, c->key_words() * 8, false));
   hipLaunchKernelGGL(k_dyadic_mul, dim3(grid_for((size_t)K * N, 256)), dim3(256), 0, c->stream, c->dc, c->d_sk, c->d_sk,
                      (size_t)0, d_newkey, kmap, K, (size_t)1);
   ABC_HIP_CHECK(hipGetLastError());
-  if (make_kskey(c, draws, keyed::kStreamRelin, d_newkey, c->d_relin, d_a, d_e8, d_e, L)) return 1;
+  if (make_kskey(c, draws, keyed::kStreamRelin, d_newkey, c->d_relin, st, L)) return 1;
   // Galois keys for the default element set (GaloisTool::get_elts_all): 2N-1, then 3^(2^i), 3^-(2^i); an element the caller had
   // loaded outside that set goes
   std::map<uint32_t, uint64_t *> old_galois;
@@ -424,20 +372,36 @@ static int keygen_with(abc_hip_ctx *c, D &draws) {
       ABC_HIP_CHECK(alloc_context_buffer(c, (void **)&d_key, c->key_words() * 8, false));
     }
     if (launch_galois(c, c->d_sk, d_newkey, K, 1, elt, true)) return 1;
-    if (make_kskey(c, draws, keyed::galois_stream(elt), d_newkey, d_key, d_a, d_e8, d_e, L)) return 1;
+    if (make_kskey(c, draws, keyed::galois_stream(elt), d_newkey, d_key, st, L)) return 1;
     c->d_galois[elt] = d_key;
     c->galois_order.push_back(elt);
   }
-  // the staging buffers held the secret key, s^2 / g(s), the errors and the sampling keys: wipe before release
-  (void)hipMemsetAsync(d_e, 0, (size_t)L * K * N * 8, c->stream);
-  (void)hipMemsetAsync(d_e8, 0, e8_bytes, c->stream);
-  (void)hipMemsetAsync(d_newkey, 0, (size_t)K * N * 8, c->stream);
-  ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
+  ABC_HIP_CHECK(st.wipe());  // before anything is released
   for (auto &kv : old_galois) release_key(c, kv.second);  // held back while a live graph may read it
   refresh_key_mirrors(c, nullptr);
   ABC_HIP_CHECK(hipGetLastError());
-  (void)hipFree(d_a); (void)hipFree(d_e); (void)hipFree(d_e8); (void)hipFree(d_newkey);
   return 0;
+}
+int keygen(abc_hip_ctx *c, uint64_t seed) {
+  HostDraws<SeededFill> draws(seed);
+  return keygen_with(c, draws);
+}
+int keygen_keyed(abc_hip_ctx *c, const uint8_t key_sec[32], const uint8_t key_pub[32]) {
+  if (!key_sec || !key_pub) { set_error("keygen_keyed: null key"); return 1; }
+  if (c->sw.host_sampling) {
+    HostDraws<KeyedHostFill> draws(key_sec, key_pub);
+    return keygen_with(c, draws);
+  }
+  KeyedDraws draws{key_sec, key_pub};
+  return keygen_with(c, draws);
+}
+int keygen_secure(abc_hip_ctx *c) {
+  uint8_t keys[2][32];  // two independent keys from the operating system: [0] secret material, [1] published material
+  int rc = getrandom_fill(&keys[0][0], sizeof(keys));
+  if (rc) set_error("keygen: getrandom failed");
+  else rc = keygen_keyed(c, keys[0], keys[1]);
+  explicit_bzero(keys, sizeof(keys));
+  return rc;
 }
 
 // ---------------- encryption ----------------
@@ -466,147 +430,6 @@ static int encrypt_workspace(abc_hip_ctx *c, size_t count, EncryptWs &w) {
   w.tmod = w.prodS + count * 2 * N;
   w.wipe_bytes = kSampleKeyBytes + small_bytes + count * 5 * K * N * 8;
   return 0;
-}
-// host draws [count][3][N] into the workspace; the host copy is wiped once the upload has completed
-static int upload_small(abc_hip_ctx *c, std::vector<int8_t> &h_small, const EncryptWs &w) {
-  const hipError_t e = hipMemcpyAsync(w.d_small, h_small.data(), h_small.size(), hipMemcpyHostToDevice, c->stream);
-  const hipError_t s = hipStreamSynchronize(c->stream);  // h_small is the caller's local
-  explicit_bzero(h_small.data(), h_small.size());
-  ABC_HIP_CHECK(e);
-  ABC_HIP_CHECK(s);
-  return 0;
-}
-static int encrypt_from_small(abc_hip_ctx *c, const u64 *plain, u64 *ct, size_t count, const EncryptWs &w, bool wipe);
-static int encrypt_with(abc_hip_ctx *c, const u64 *plain, uint64_t seed, Sampler *secure, u64 *ct, size_t count);
-static int no_public_key(const abc_hip_ctx *c) {
-  if (c->d_pk) return 0;
-  set_error("encrypt: no public key (call abc_hip_keygen or abc_hip_load_public_key)");
-  return 1;
-}
-int encrypt(abc_hip_ctx *c, const u64 *plain, uint64_t seed, u64 *ct, size_t count) {
-  return encrypt_with(c, plain, seed, nullptr, ct, count);
-}
-// the keyed spec: ciphertext i takes stream nonce + i; u from words 0 .. N-1 (ternary), e0 and e1 from the 2N words behind (cbd)
-int encrypt_keyed(abc_hip_ctx *c, const u64 *plain, const uint8_t key[32], uint64_t nonce, u64 *ct, size_t count) {
-  if (!key) { set_error("encrypt_keyed: null key"); return 1; }
-  if (no_public_key(c)) return 1;
-  if (!count) return 0;
-  EncryptWs w;
-  if (encrypt_workspace(c, count, w)) return 1;
-  if (c->sw.host_sampling) {
-    const size_t N = (size_t)c->n;
-    std::vector<int8_t> h_small(count * 3 * N);
-    keyed::encrypt_small_host(key, nonce, N, count, h_small.data());
-    if (upload_small(c, h_small, w)) return 1;
-  } else {
-    if (upload_sample_key(c, w.d_kb, key, nonce)) return 1;
-    if (launch_sample_small(c, w.d_kb, 0, count, 3, 1, w.d_small)) return 1;
-  }
-  return encrypt_from_small(c, plain, ct, count, w, true);
-}
-int encrypt_secure(abc_hip_ctx *c, const u64 *plain, u64 *ct, size_t count) {
-  if (c->sw.host_sampling) {
-    ChaCha sec(3);  // a fresh 256-bit key from the operating system per call: nothing is derived from the key seed
-    if (!sec.ok) { set_error("encrypt: getrandom failed"); return 1; }
-    return encrypt_with(c, plain, 0, &sec, ct, count);
-  }
-  uint8_t key[32];  // fresh per call, so every (key, nonce + i) pair is used once
-  int rc = getrandom_fill(key, sizeof(key));
-  if (rc) set_error("encrypt: getrandom failed");
-  else rc = encrypt_keyed(c, plain, key, 0, ct, count);
-  explicit_bzero(key, sizeof(key));
-  return rc;
-}
-// the raw draws of the keyed spec, as encrypt_keyed takes them
-int keyed_small(abc_hip_ctx *c, const uint8_t key[32], uint64_t nonce, int8_t *d_small, size_t count) {
-  if (!key || (!d_small && count)) { set_error("keyed_small: null pointer"); return 1; }
-  if ((uintptr_t)d_small & 7) { set_error("keyed_small: d_small must be 8-byte aligned"); return 1; }
-  if (!count) return 0;
-  const size_t N = (size_t)c->n;
-  if (c->sw.host_sampling) {
-    std::vector<int8_t> h_small(count * 3 * N);
-    keyed::encrypt_small_host(key, nonce, N, count, h_small.data());
-    ABC_HIP_CHECK(hipMemcpyAsync(d_small, h_small.data(), h_small.size(), hipMemcpyHostToDevice, c->stream));
-    ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return 0;
-  }
-  if (ensure_workspace(c, kSampleKeyBytes)) return 1;
-  if (upload_sample_key(c, c->ws, key, nonce)) return 1;
-  if (launch_sample_small(c, c->ws, 0, count, 3, 1, d_small)) return 1;
-  ABC_HIP_CHECK(hipMemsetAsync(c->ws, 0, kSampleKeyBytes, c->stream));
-  return 0;
-}
-int keyed_uniform(abc_hip_ctx *c, const uint8_t key[32], uint64_t stream, int nkeys, u64 *d_a) {
-  if (!key || !d_a) { set_error("keyed_uniform: null pointer"); return 1; }
-  if (nkeys < 1 || nkeys > c->L) { set_error("keyed_uniform: nkeys must be between 1 and L"); return 1; }
-  if ((uintptr_t)d_a & 15) { set_error("keyed_uniform: d_a must be 16-byte aligned"); return 1; }
-  if (c->sw.host_sampling) {
-    std::vector<uint64_t> h_a((size_t)nkeys * c->K * c->n);
-    uint32_t k[8];
-    keyed::load_key(key, k);
-    keyed::uniform_host(k, stream, (size_t)c->n, c->K, c->primes.data(), nkeys, h_a.data());
-    explicit_bzero(k, sizeof(k));
-    ABC_HIP_CHECK(hipMemcpyAsync(d_a, h_a.data(), h_a.size() * 8, hipMemcpyHostToDevice, c->stream));
-    ABC_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return 0;
-  }
-  if (ensure_workspace(c, kSampleKeyBytes)) return 1;
-  if (upload_sample_key(c, c->ws, key, 0)) return 1;
-  if (launch_sample_uniform(c, c->ws, stream, nkeys, d_a)) return 1;
-  ABC_HIP_CHECK(hipMemsetAsync(c->ws, 0, kSampleKeyBytes, c->stream));
-  return 0;
-}
-static int encrypt_with(abc_hip_ctx *c, const u64 *plain, uint64_t seed, Sampler *secure, u64 *ct, size_t count) {
-  if (no_public_key(c)) return 1;
-  if (!count) return 0;
-  const size_t N = (size_t)c->n;
-  // host sampling: per ciphertext i the stream seed+i yields u, e0, e1 -- independent streams, so a batch is drawn by up to 16
-  // host threads (the seeded spec gives the same bytes whatever the thread count; the secure path keys one ChaCha20 instance per
-  // worker from the operating system).  Config 5 encrypts 1 125 ciphertexts of 2^16 slots: 221 M draws, 530 ms on one thread.
-  std::vector<int8_t> h_small(count * 3 * N);
-  {
-    auto fill = [N](auto &rng, int8_t *p) {  // concrete (final) generator type: the draws inline
-      for (size_t x = 0; x < N; x++) p[x] = rng.ternary();
-      for (size_t x = 0; x < 2 * N; x++) p[N + x] = rng.cbd();
-    };
-    const size_t hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    const size_t workers = count >= 4 ? std::min(hw, count) : 1;
-    std::atomic<int> failed{0};
-    auto work = [&](size_t w) {
-      const size_t i0 = count * w / workers, i1 = count * (w + 1) / workers;
-      if (secure) {
-        if (w == 0) {  // the caller's generator serves the first share
-          for (size_t i = i0; i < i1; i++) {
-            int8_t *p = h_small.data() + i * 3 * N;
-            for (size_t x = 0; x < N; x++) p[x] = secure->ternary();
-            for (size_t x = 0; x < 2 * N; x++) p[N + x] = secure->cbd();
-          }
-          return;
-        }
-        ChaCha own(0x100 + w);
-        if (!own.ok) { failed = 1; return; }
-        for (size_t i = i0; i < i1; i++) fill(own, h_small.data() + i * 3 * N);
-        return;
-      }
-      for (size_t i = i0; i < i1; i++) {
-        Rng seeded(seed + i);
-        fill(seeded, h_small.data() + i * 3 * N);
-      }
-    };
-    if (workers == 1) {
-      work(0);
-    } else {
-      std::vector<std::thread> pool;
-      for (size_t w = 1; w < workers; w++) pool.emplace_back(work, w);
-      work(0);
-      for (auto &t : pool) t.join();
-    }
-    if (failed) { explicit_bzero(h_small.data(), h_small.size()); set_error("encrypt: getrandom failed"); return 1; }
-  }
-  EncryptWs w;
-  if (encrypt_workspace(c, count, w)) return 1;
-  if (upload_small(c, h_small, w)) return 1;
-  return encrypt_from_small(c, plain, ct, count, w, secure != nullptr);
 }
 // ciphertexts from the draws in w.d_small (u | e0 | e1 per ciphertext): everything downstream of the sampling
 static int encrypt_from_small(abc_hip_ctx *c, const u64 *plain, u64 *ct, size_t count, const EncryptWs &w, bool wipe) {
@@ -651,6 +474,93 @@ static int encrypt_from_small(abc_hip_ctx *c, const u64 *plain, u64 *ct, size_t 
   // add the message
   if (ckks) return ckks_add_plain(c, ct, plain, (size_t)L * N, ct, 2, L, count, 0);
   return bfv_addsub_plain(c, ct, plain, N, ct, 2, count, 0);
+}
+static int no_public_key(const abc_hip_ctx *c) {
+  if (c->d_pk) return 0;
+  set_error("encrypt: no public key (call abc_hip_keygen or abc_hip_load_public_key)");
+  return 1;
+}
+// The seeded spec: ciphertext i draws u, e0, e1 from Rng(seed + i) -- independent streams, so a batch is drawn by up to 16 host
+// threads and the bytes do not depend on the thread count.  Config 5 encrypts 1 125 ciphertexts of 2^16 slots: 221 M draws,
+// 530 ms on one thread.
+int encrypt(abc_hip_ctx *c, const u64 *plain, uint64_t seed, u64 *ct, size_t count) {
+  if (no_public_key(c)) return 1;
+  if (!count) return 0;
+  const size_t N = (size_t)c->n;
+  std::vector<int8_t> h_small(count * 3 * N);
+  const size_t hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+  const size_t workers = count >= 4 ? std::min(hw, count) : 1;
+  auto work = [&](size_t w) {
+    for (size_t i = count * w / workers; i < count * (w + 1) / workers; i++) {
+      Rng rng(seed + i);
+      int8_t *p = h_small.data() + i * 3 * N;
+      for (size_t x = 0; x < N; x++) p[x] = rng.ternary();
+      for (size_t x = 0; x < 2 * N; x++) p[N + x] = rng.cbd();
+    }
+  };
+  std::vector<std::thread> pool;
+  for (size_t w = 1; w < workers; w++) pool.emplace_back(work, w);
+  work(0);
+  for (auto &t : pool) t.join();
+  EncryptWs w;
+  if (encrypt_workspace(c, count, w)) return 1;
+  if (upload_wiped(c, w.d_small, h_small.data(), h_small.size())) return 1;
+  return encrypt_from_small(c, plain, ct, count, w, false);
+}
+// The keyed spec: ciphertext i takes stream nonce + i; u from words 0 .. N-1 (ternary), e0 and e1 from the 2N words behind (cbd).
+// The draws [count][3][N] of (key, nonce) into d_small: by the device sampler, which reads the key from d_kb (kSampleKeyBytes of
+// device memory that the caller wipes), or under ABC_HIP_HOST_SAMPLING=1 by the host twin and an upload.
+static int keyed_small_draws(abc_hip_ctx *c, const uint8_t key[32], uint64_t nonce, size_t count, void *d_kb, int8_t *d_small) {
+  if (c->sw.host_sampling) {
+    std::vector<int8_t> h_small(count * 3 * (size_t)c->n);
+    keyed::encrypt_small_host(key, nonce, (size_t)c->n, count, h_small.data());
+    return upload_wiped(c, d_small, h_small.data(), h_small.size());
+  }
+  return upload_sample_key(c, d_kb, key, nonce) || launch_sample_small(c, d_kb, 0, count, 3, 1, d_small);
+}
+int encrypt_keyed(abc_hip_ctx *c, const u64 *plain, const uint8_t key[32], uint64_t nonce, u64 *ct, size_t count) {
+  if (!key) { set_error("encrypt_keyed: null key"); return 1; }
+  if (no_public_key(c)) return 1;
+  if (!count) return 0;
+  EncryptWs w;
+  if (encrypt_workspace(c, count, w)) return 1;
+  if (keyed_small_draws(c, key, nonce, count, w.d_kb, w.d_small)) return 1;
+  return encrypt_from_small(c, plain, ct, count, w, true);
+}
+int encrypt_secure(abc_hip_ctx *c, const u64 *plain, u64 *ct, size_t count) {
+  uint8_t key[32];  // fresh per call, so every (key, nonce + i) pair is used once
+  int rc = getrandom_fill(key, sizeof(key));
+  if (rc) set_error("encrypt: getrandom failed");
+  else rc = encrypt_keyed(c, plain, key, 0, ct, count);
+  explicit_bzero(key, sizeof(key));
+  return rc;
+}
+// the raw draws of the keyed spec, as encrypt_keyed takes them
+int keyed_small(abc_hip_ctx *c, const uint8_t key[32], uint64_t nonce, int8_t *d_small, size_t count) {
+  if (!key || (!d_small && count)) { set_error("keyed_small: null pointer"); return 1; }
+  if ((uintptr_t)d_small & 7) { set_error("keyed_small: d_small must be 8-byte aligned"); return 1; }
+  if (!count) return 0;
+  if (ensure_workspace(c, kSampleKeyBytes)) return 1;
+  const int rc = keyed_small_draws(c, key, nonce, count, c->ws, d_small);
+  ABC_HIP_CHECK(hipMemsetAsync(c->ws, 0, kSampleKeyBytes, c->stream));
+  return rc;
+}
+int keyed_uniform(abc_hip_ctx *c, const uint8_t key[32], uint64_t stream, int nkeys, u64 *d_a) {
+  if (!key || !d_a) { set_error("keyed_uniform: null pointer"); return 1; }
+  if (nkeys < 1 || nkeys > c->L) { set_error("keyed_uniform: nkeys must be between 1 and L"); return 1; }
+  if ((uintptr_t)d_a & 15) { set_error("keyed_uniform: d_a must be 16-byte aligned"); return 1; }
+  if (c->sw.host_sampling) {
+    std::vector<uint64_t> h_a((size_t)nkeys * c->K * c->n);
+    uint32_t k[8];
+    keyed::load_key(key, k);
+    sample_uniform_host(c, k, stream, nkeys, h_a.data());
+    explicit_bzero(k, sizeof(k));
+    return upload_wiped(c, d_a, h_a.data(), h_a.size() * 8);
+  }
+  if (ensure_workspace(c, kSampleKeyBytes)) return 1;
+  const int rc = upload_sample_key(c, c->ws, key, 0) || launch_sample_uniform(c, c->ws, stream, nkeys, d_a);
+  ABC_HIP_CHECK(hipMemsetAsync(c->ws, 0, kSampleKeyBytes, c->stream));
+  return rc;
 }
 
 // ---------------- decryption ----------------

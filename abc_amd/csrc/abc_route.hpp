@@ -21,7 +21,7 @@ namespace abc {
 struct Switches {
   bool no_fused = false, no_split = false, no_split4 = false, no_isplit = false, no_gsplit = false, no_lean_front = false, no_bsplit = false, no_mixed = false, no_pack = false, no_key_twin = false, no_bmul = false, no_iks = false, no_tensor_intt = false;
   bool no_galois_fusion = false;
-  bool host_sampling = false;  // ABC_HIP_HOST_SAMPLING: the OS-keyed and keyed entry points draw on the host (no route depends on it)
+  bool host_sampling = false;  // ABC_HIP_HOST_SAMPLING: the keyed entries (the OS-keyed ones call them) draw with the host twin of the keyed spec (no route depends on it)
   size_t chunk = 0, few_limbs = 48, lean_limit = 96, bfv_scratch_mb = 0, pass0_target_limit = 128;
   int lanes = 2;
 };

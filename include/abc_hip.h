@@ -104,8 +104,9 @@ int abc_hip_keygen(abc_hip_ctx *ctx, uint64_t seed);
  * (key, stream id, word number), drawn by HIP kernels.  key_sec serves the secret key and the errors, key_pub the published
  * uniform polynomials; stream 0 the secret key, 1 the public key, 2 the relinearisation key, 2 + galois_elt a Galois key.
  * Deterministic given the two keys.  abc_hip_keygen_secure is this call with two fresh 32-byte keys from getrandom(2).
- * ABC_HIP_HOST_SAMPLING=1 draws the same words on the host (bit-identical keys); for abc_hip_keygen_secure /
- * abc_hip_encrypt_secure that switch selects the sequential host ChaCha20 sampler instead.  Keys are rewritten in place (graphs). */
+ * ABC_HIP_HOST_SAMPLING=1 draws the same words on the host (bit-identical keys); abc_hip_keygen_secure and
+ * abc_hip_encrypt_secure are the keyed entries under keys from getrandom(2) and follow that switch with them.  Keys are rewritten
+ * in place (graphs). */
 int abc_hip_keygen_keyed(abc_hip_ctx *ctx, const uint8_t key_sec[32], const uint8_t key_pub[32]);
 /* or load externally generated keys (host pointers) */
 int abc_hip_load_secret_key(abc_hip_ctx *ctx, const uint64_t *h_sk /*[L+1][N] NTT*/);

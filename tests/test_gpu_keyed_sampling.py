@@ -166,12 +166,30 @@ def test_encrypt_secure_is_fresh_and_decrypts(rings):
         for i in range(5):
             _same("oracle decrypt %d" % i, o.decrypt(cts[i]), pls[i])
     with HostSampling(g):
-        c = g.encrypt(pls, None)  # the sequential host sampler, as before
+        c, d = g.encrypt(pls, None), g.encrypt(pls, None)  # the host twin under a fresh OS key per call
     assert not np.array_equal(a, c)
+    assert not np.array_equal(c, d)
     _same("host-sampled secure encryption decrypts", g.decrypt(c), pls)
 
 
 # ---- key generation ----
+def test_secure_entries_under_host_sampling(oracle_mod, capi):
+    """OS-keyed key generation and encryption through the host twin: fresh keys per call, regenerated in place, and the keys
+    serve the device sampler afterwards"""
+    o = _oracle(oracle_mod, "bfv4096")
+    g = _context(capi, o)
+    _, pls = _plains(o, 2, 9)
+    with HostSampling(g):
+        g.keygen(None)
+        first = g.get_key("sk")
+        g.keygen(None)
+        assert not np.array_equal(g.get_key("sk"), first)
+        assert g.held_buffers() == 0  # every key regenerated into the buffer it had
+        _same("host-sampled keys and encryption", g.decrypt(g.encrypt(pls, None)), pls)
+    _same("host-sampled keys, device-sampled encryption", g.decrypt(g.encrypt(pls, None)), pls)
+    g.close()
+
+
 def _all_keys(g, elts):
     return [("sk", g.get_key("sk")), ("pk", g.get_key("pk")), ("relin", g.get_key("relin"))] + \
         [("galois %d" % e, g.get_key("galois", e)) for e in elts]

@@ -100,8 +100,8 @@ def main():
         dec, budgets = g.alloc(B * n * 8), (C.c_int * B)()
         ops["bfv%d_decrypt" % n] = lambda: g.op("decrypt", a.ptr, 2, L, dec.ptr, cb)
         ops["bfv%d_noise_budget" % n] = lambda: g.op("noise_budget", a.ptr, 2, L, budgets, cb)
-        # OS-keyed encryption of the batch (abc_hip_encrypt_secure: getrandom + ChaCha20 sampling on the device, or on the host
-        # under ABC_HIP_HOST_SAMPLING=1) and, on the reference's default ring, a whole key set (abc_hip_keygen_secure: batch 1)
+        # OS-keyed encryption of the batch (abc_hip_encrypt_secure: getrandom + ChaCha20 sampling on the device, or by the keyed
+        # spec's single-threaded host twin under ABC_HIP_HOST_SAMPLING=1) and, on the reference's default ring, a whole key set (abc_hip_keygen_secure: batch 1)
         plains = g.upload(rng.integers(0, g.t, size=(B, n), dtype=np.uint64))
         ops["bfv%d_encrypt_secure" % n] = lambda: g.op("encrypt_secure", plains.ptr, out.ptr, cb)
         # the sampling alone, key upload included: the draws of that batch, and the uniform polynomials of one key-switching key

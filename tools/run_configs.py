@@ -324,7 +324,7 @@ def main():
     ap.add_argument("--host-codec", action="store_true", help="CKKS configs: encode / decode in numpy instead of on the device")
     ap.add_argument("--os-keyed", action="store_true",
                     help="keys and encryption randomness from the OS-keyed entry points (abc_hip_keygen_secure / abc_hip_encrypt_secure) "
-                         "instead of the seeded test spec; ABC_HIP_HOST_SAMPLING=1 then selects the host sampler for the A/B")
+                         "instead of the seeded test spec; ABC_HIP_HOST_SAMPLING=1 then draws the same spec with its host twin")
     args = ap.parse_args()
     global HOST_CODEC, OS_KEYED
     HOST_CODEC, OS_KEYED = args.host_codec, args.os_keyed
