@@ -880,15 +880,20 @@ static void launch_split3_main(abc_hip_ctx *c, const MainArgs &a) {
 // cooperatively) instead of vector loads, so nothing in the transform touches the in-order vector-memory counter any more and
 // the operands of the phase AFTER the transform (key slices, a and b) can be requested before it: one exposed memory latency per
 // workgroup instead of two, and the transform runs under the second one.
-template <int MODE, int NL>
+// HALVES (nl <= 4): the pair phase one output component at a time.  The key words of one component share one register set, the
+// non-diagonal digits are read from LDS once per half, and every operand of the pair phase is requested after this wavefront's
+// transform instead of before it: 70 VGPRs, so that three workgroups fit a CU by registers as well as by LDS (3 x 50.5 KiB).
+// Without it the pair phase is in one piece with its operands prefetched across the transform (nl = 5..7, where LDS allows two
+// workgroups per CU anyway, and ABC_HIP_MAIN_TWO_PER_CU=1).  The sums, their order and every rounding are the same: same bits.
+template <int MODE, int NL, bool HALVES>
 struct PairOps {
-  u64x2 k0[NL], k1[NL];
-  u64x2 a0, a1, b0, b1;      // MODE 0
-  u64 xs[2], d0s[2], d1s[2];  // MODE 1
+  u64x2 k[HALVES ? NL : 2 * NL];  // HALVES: digit Jx of the component in hand; otherwise [2 Jx + component]
+  u64x2 a0, a1, b0, b1;           // MODE 0
+  u64 xs[2], d0s[2], d1s[2];      // MODE 1
 };
 
-template <int MODE, bool GAL, int NL>
-__global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_split4_main_fp(DevCtx c, const double *__restrict__ part,
+template <int MODE, bool GAL, int NL, bool HALVES>
+__global__ __launch_bounds__(512, HALVES ? 6 : NL <= 4 ? 4 : 2) void k_split4_main_fp(DevCtx c, const double *__restrict__ part,
                                                                    const double *__restrict__ tpart, const u64 *__restrict__ opa,
                                                                    const u64 *__restrict__ opb, size_t opa_stride, size_t opb_stride,
                                                                    int add_c1, const u64 *__restrict__ key, u64 *__restrict__ out, u32 gelt,
@@ -900,14 +905,16 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_split4_main_fp(DevCtx 
   // 512 threads whatever nl: one coefficient pair per thread afterwards, so every operand of that phase is requested up front;
   // wavefronts nl + 1 .. 7 have no limb to transform and only take part in the table fill and the inner product
   static_assert(NL + 1 <= 8, "one wavefront per limb, eight wavefronts");
+  static_assert(!HALVES || NL <= 4, "three workgroups per CU: four transform buffers at the most");
   constexpr int nl = NL, NT = 512, PER = 2;
   // LATE: digits whose key words are requested AFTER the transform.  The multiply at four limbs holds 48 VGPRs of prefetched
   // operands across the transform and sits on the 128-VGPR ceiling of two workgroups per CU; the butterfly's quotient now hangs
   // on its own product (one multiply more in the chain, abc_ntt.hpp), which cost five more live registers and, with everything
   // prefetched, 20 bytes of scratch per lane -- scratch reloads go through the same in-order vmcnt as the prefetch.  The last
   // digit's eight registers are therefore loaded late: its words come out of L2 and are used last, behind the other digits'
-  // products (123 VGPRs, no scratch).
-  constexpr int LATE = (MODE == 0 && NL == 4) ? 1 : 0;
+  // products (123 VGPRs, no scratch).  HALVES requests everything late.
+  constexpr int LATE = (!HALVES && MODE == 0 && NL == 4) ? 1 : 0;
+  using Ops = PairOps<MODE, NL, HALVES>;
   const int W = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = threadIdx.x & 63;
   const int blk = blockIdx.x & 15;
@@ -946,17 +953,21 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_split4_main_fp(DevCtx 
   }
   // key words: 16 raw bytes per (digit, component) either way -- the key's fp64 twin where it exists (keyf, workgroup-uniform:
   // the words ARE the doubles), the u64 key otherwise (converted when used, after the transform)
-  auto load_key = [&](int e, PairOps<MODE, NL> &o, int j0, int j1) {
+  // digits j0 .. j1 - 1; HALVES: of component comp
+  auto load_key = [&](int e, Ops &o, int j0, int j1, int comp) {
     const u64 *kw = keyf ? reinterpret_cast<const u64 *>(keyf) : key;
 #pragma unroll
     for (int Jx = 0; Jx < NL; Jx++) {
       if (Jx < j0 || Jx >= j1) continue;
-      o.k0[Jx] = *reinterpret_cast<const u64x2 *>(kw + (((size_t)Jx * 2 + 0) * c.K + I) * N + base + e);
-      o.k1[Jx] = *reinterpret_cast<const u64x2 *>(kw + (((size_t)Jx * 2 + 1) * c.K + I) * N + base + e);
+      if constexpr (HALVES) {
+        o.k[Jx] = *reinterpret_cast<const u64x2 *>(kw + (((size_t)Jx * 2 + comp) * c.K + I) * N + base + e);
+      } else {
+        o.k[2 * Jx + 0] = *reinterpret_cast<const u64x2 *>(kw + (((size_t)Jx * 2 + 0) * c.K + I) * N + base + e);
+        o.k[2 * Jx + 1] = *reinterpret_cast<const u64x2 *>(kw + (((size_t)Jx * 2 + 1) * c.K + I) * N + base + e);
+      }
     }
   };
-  auto load_pair = [&](int e, PairOps<MODE, NL> &o) {
-    load_key(e, o, 0, NL - LATE);
+  auto load_operands = [&](int e, Ops &o) {
     if (MODE == 0) {
       const u64 *pa = opa + ct * 2 * pw + (size_t)I * N + base + e, *pb = opb + ct * 2 * pw + (size_t)I * N + base + e;
       o.a0 = *reinterpret_cast<const u64x2 *>(pa); o.a1 = *reinterpret_cast<const u64x2 *>(pa + pw);
@@ -976,8 +987,12 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_split4_main_fp(DevCtx 
       }
     }
   };
-  PairOps<MODE, NL> ops;
-  load_pair(2 * (int)threadIdx.x, ops);
+  Ops ops;
+  const int e0 = 2 * (int)threadIdx.x;
+  if (!HALVES) {
+    load_key(e0, ops, 0, NL - LATE, 0);
+    load_operands(e0, ops);
+  }
 
   block_twiddles_store<10, double, PER>(ltw, (int)threadIdx.x, NT, twv);
   __syncthreads();
@@ -1006,63 +1021,101 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_split4_main_fp(DevCtx 
     }
     ntt_fwd_tail1024_pairs<FpTail>(buf, xin, [&](int, int i, double v) { buf[lds_pad(i)] = v; }, t, m, 4, blk, lane, ltw);
   }
-  if (LATE) load_key(2 * (int)threadIdx.x, ops, NL - LATE, NL);
+  // HALVES: a wavefront without a limb arrives here straight from the first barrier, so its requests are in flight across the
+  // others' transform at no cost in registers; the transforming wavefronts wait for theirs behind the second barrier
+  if (HALVES) {
+    load_key(e0, ops, 0, NL, 0);
+    load_operands(e0, ops);
+  }
+  if (LATE) load_key(e0, ops, NL - LATE, NL, 0);
   __syncthreads();
-  const double *tt0 = dyn + (nl - 1) * lds_words(10), *tt1 = dyn + nl * lds_words(10);
-  auto compute_pair = [&](int e, const PairOps<MODE, NL> &o, auto twin) {
+  auto compute_pair = [&](int e, Ops &o, auto twin) {
     constexpr bool TW = decltype(twin)::value;
     auto kd = [](u64 w) { return TW ? __longlong_as_double((long long)w) : fp_from_u64(w); };
-    double s0[2] = {0.0, 0.0}, s1[2] = {0.0, 0.0}, d0[2] = {0.0, 0.0}, d1[2] = {0.0, 0.0};
-#pragma unroll
-    for (int Jx = 0; Jx < NL; Jx++) {
-      double x[2];
-      if (Jx == I) {
-        if (MODE == 0) {
-          const double x0[2] = {fp_from_u64(o.a0.x), fp_from_u64(o.a0.y)}, x1[2] = {fp_from_u64(o.a1.x), fp_from_u64(o.a1.y)};
-          const double y0[2] = {fp_from_u64(o.b0.x), fp_from_u64(o.b0.y)}, y1[2] = {fp_from_u64(o.b1.x), fp_from_u64(o.b1.y)};
-#pragma unroll
-          for (int k = 0; k < 2; k++) {
-            x[k] = fp_mulmod(x1[k], y1[k], q, qinv);
-            d0[k] = fp_mulmod(x0[k], y0[k], q, qinv);
-            d1[k] = fp_mulmod(x0[k], y1[k], q, qinv) + fp_mulmod(x1[k], y0[k], q, qinv);
-          }
-        } else {
-#pragma unroll
-          for (int k = 0; k < 2; k++) {
-            x[k] = fp_from_u64(o.xs[k]);
-            d0[k] = fp_from_u64(o.d0s[k]);
-            d1[k] = fp_from_u64(o.d1s[k]);
-          }
-        }
-      } else {
-        const int w = Jx < I ? Jx : Jx - 1;
-        const f64x2 v = *reinterpret_cast<const f64x2 *>(dyn + w * lds_words(10) + lds_pad(e));
-        x[0] = v.x;
-        x[1] = v.y;
-      }
-      s0[0] += fp_mulmod(x[0], kd(o.k0[Jx].x), q, qinv);
-      s0[1] += fp_mulmod(x[1], kd(o.k0[Jx].y), q, qinv);
-      s1[0] += fp_mulmod(x[0], kd(o.k1[Jx].x), q, qinv);
-      s1[1] += fp_mulmod(x[1], kd(o.k1[Jx].y), q, qinv);
-      if (Jx == 7) {
+    double xd[2], d0[2] = {0.0, 0.0}, d1[2] = {0.0, 0.0};
+    auto diagonal = [&]() {  // the digit modulo q_I itself and the terms folded in as q_sp c: everything that depends on a and b
+      if (MODE == 0) {
+        const double x0[2] = {fp_from_u64(o.a0.x), fp_from_u64(o.a0.y)}, x1[2] = {fp_from_u64(o.a1.x), fp_from_u64(o.a1.y)};
+        const double y0[2] = {fp_from_u64(o.b0.x), fp_from_u64(o.b0.y)}, y1[2] = {fp_from_u64(o.b1.x), fp_from_u64(o.b1.y)};
 #pragma unroll
         for (int k = 0; k < 2; k++) {
-          s0[k] = fp_centre(s0[k], q, qinv);
-          s1[k] = fp_centre(s1[k], q, qinv);
+          xd[k] = fp_mulmod(x1[k], y1[k], q, qinv);
+          d0[k] = fp_mulmod(x0[k], y0[k], q, qinv);
+          d1[k] = fp_mulmod(x0[k], y1[k], q, qinv) + fp_mulmod(x1[k], y0[k], q, qinv);
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+          xd[k] = fp_from_u64(o.xs[k]);
+          d0[k] = fp_from_u64(o.d0s[k]);
+          d1[k] = fp_from_u64(o.d1s[k]);
         }
       }
+    };
+    auto digit = [&](int Jx, double *x) {  // Jx != I: finished by wavefront Jx (Jx - 1 past the diagonal)
+      const int w = Jx < I ? Jx : Jx - 1;
+      const f64x2 v = *reinterpret_cast<const f64x2 *>(dyn + w * lds_words(10) + lds_pad(e));
+      x[0] = v.x;
+      x[1] = v.y;
+    };
+    auto finish = [&](int comp, const double *s, const double *d) {  // (sum + q_sp c - NTT(t)) q_sp^-1
+      const f64x2 u = *reinterpret_cast<const f64x2 *>(dyn + (nl - 1 + comp) * lds_words(10) + lds_pad(e));
+      u64x2 r;
+      r.x = fp_to_canon(fp_mul_lazy(s[0] - u.x, inv, inv_q, q) + d[0], q, qinv);
+      r.y = fp_to_canon(fp_mul_lazy(s[1] - u.y, inv, inv_q, q) + d[1], q, qinv);
+      *reinterpret_cast<u64x2 *>(out + ((ct * 2 + comp) * nl + I) * N + base + e) = r;
+    };
+    if constexpr (HALVES) {
+      diagonal();  // before the first store: `out` may alias a or b
+      // pinned here: left alone the compiler sinks d1's products into the second half and keeps all of a and b alive for them
+      // (16 VGPRs instead of 4, and scratch at four limbs)
+#pragma unroll
+      for (int k = 0; k < 2; k++) asm volatile("" : "+v"(xd[k]), "+v"(d0[k]), "+v"(d1[k]));
+      auto half = [&](auto comp, const double *d) {
+        double s[2] = {0.0, 0.0};
+#pragma unroll
+        for (int Jx = 0; Jx < NL; Jx++) {  // at most four products: below the re-centring at Jx == 7
+          double x[2] = {xd[0], xd[1]};
+          if (Jx != I) digit(Jx, x);
+          s[0] += fp_mulmod(x[0], kd(o.k[Jx].x), q, qinv);
+          s[1] += fp_mulmod(x[1], kd(o.k[Jx].y), q, qinv);
+        }
+        finish(decltype(comp)::value, s, d);
+      };
+      half(std::integral_constant<int, 0>{}, d0);
+      __builtin_amdgcn_sched_barrier(0);  // the second half's requests stay behind the first half's store (78 -> 70 VGPRs at four limbs)
+      load_key(e, o, 0, NL, 1);
+      half(std::integral_constant<int, 1>{}, d1);
+    } else {
+      double s0[2] = {0.0, 0.0}, s1[2] = {0.0, 0.0};
+#pragma unroll
+      for (int Jx = 0; Jx < NL; Jx++) {
+        double x[2];
+        if (Jx == I) {
+          diagonal();
+          x[0] = xd[0];
+          x[1] = xd[1];
+        } else {
+          digit(Jx, x);
+        }
+        s0[0] += fp_mulmod(x[0], kd(o.k[2 * Jx + 0].x), q, qinv);
+        s0[1] += fp_mulmod(x[1], kd(o.k[2 * Jx + 0].y), q, qinv);
+        s1[0] += fp_mulmod(x[0], kd(o.k[2 * Jx + 1].x), q, qinv);
+        s1[1] += fp_mulmod(x[1], kd(o.k[2 * Jx + 1].y), q, qinv);
+        if (Jx == 7) {
+#pragma unroll
+          for (int k = 0; k < 2; k++) {
+            s0[k] = fp_centre(s0[k], q, qinv);
+            s1[k] = fp_centre(s1[k], q, qinv);
+          }
+        }
+      }
+      finish(0, s0, d0);
+      finish(1, s1, d1);
     }
-    const f64x2 u0 = *reinterpret_cast<const f64x2 *>(tt0 + lds_pad(e)), u1 = *reinterpret_cast<const f64x2 *>(tt1 + lds_pad(e));
-    u64x2 r;
-    r.x = fp_to_canon(fp_mul_lazy(s0[0] - u0.x, inv, inv_q, q) + d0[0], q, qinv);
-    r.y = fp_to_canon(fp_mul_lazy(s0[1] - u0.y, inv, inv_q, q) + d0[1], q, qinv);
-    *reinterpret_cast<u64x2 *>(out + ((ct * 2 + 0) * nl + I) * N + base + e) = r;
-    r.x = fp_to_canon(fp_mul_lazy(s1[0] - u1.x, inv, inv_q, q) + d1[0], q, qinv);
-    r.y = fp_to_canon(fp_mul_lazy(s1[1] - u1.y, inv, inv_q, q) + d1[1], q, qinv);
-    *reinterpret_cast<u64x2 *>(out + ((ct * 2 + 1) * nl + I) * N + base + e) = r;
   };
-  if (keyf) compute_pair(2 * (int)threadIdx.x, ops, std::true_type{});  // workgroup-uniform
-  else compute_pair(2 * (int)threadIdx.x, ops, std::false_type{});
+  if (keyf) compute_pair(e0, ops, std::true_type{});  // workgroup-uniform
+  else compute_pair(e0, ops, std::false_type{});
 }
 
 // over the slots of a.imap; mode 0 multiply, mode 1 key switch
@@ -1074,9 +1127,16 @@ bool split4_main(abc_hip_ctx *c, int mode, const MainArgs &a) {
   // a.part / a.tpart: raw or packed doubles here (a mixed chain's fp64 limbs: written as doubles by the integer sequence's first steps)
   dispatch_mode(mode, a.gelt, [&](auto M, auto G) {
     dispatch_nl<1, 7>(a.nl, [&](auto NL) {
-      hipLaunchKernelGGL((k_split4_main_fp<decltype(M)::value, decltype(G)::value, decltype(NL)::value>), grid, block, main_lds_bytes(a.nl, sizeof(double)),
-                         a.st, c->dc, (const double *)a.part, (const double *)a.tpart, a.opa, a.opb, a.opa_stride, a.opb_stride, a.add_c1,
-                         a.key, a.out, a.gelt, (u32)a.imap, a.ni, a.pack, keyf);
+      auto launch = [&](auto H) {
+        hipLaunchKernelGGL((k_split4_main_fp<decltype(M)::value, decltype(G)::value, decltype(NL)::value, decltype(H)::value>), grid, block,
+                           main_lds_bytes(a.nl, sizeof(double)), a.st, c->dc, (const double *)a.part, (const double *)a.tpart, a.opa, a.opb,
+                           a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, (u32)a.imap, a.ni, a.pack, keyf);
+      };
+      // up to four limbs LDS holds three workgroups per CU: the pair phase in two halves fits their registers
+      if constexpr (decltype(NL)::value <= 4) {
+        if (!c->sw.main_two_per_cu) return launch(std::true_type{});
+      }
+      launch(std::false_type{});
     });
   });
   return true;
