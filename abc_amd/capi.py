@@ -35,6 +35,7 @@ SYMBOLS = [
     "abc_hip_ntt_limbs",
     "abc_hip_graph_begin", "abc_hip_graph_end", "abc_hip_graph_launch", "abc_hip_graph_destroy",
     "abc_hip_encrypt_keyed", "abc_hip_keygen_keyed", "abc_hip_keyed_small", "abc_hip_keyed_uniform", "abc_hip_keyed_small_host",
+    "abc_hip_apply_galois_hoisted", "abc_hip_rotate_hoisted",
 ]
 
 
@@ -61,6 +62,8 @@ def lib():
         L.abc_hip_cached_bytes.argtypes = [C.c_void_p]
         L.abc_hip_galois_elt_from_step.restype = C.c_uint32
         L.abc_hip_route.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_char_p, C.c_size_t]
+        L.abc_hip_apply_galois_hoisted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.c_int, C.c_size_t]
+        L.abc_hip_rotate_hoisted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_size_t]
         L.abc_hip_encrypt_keyed.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_size_t]
         L.abc_hip_keygen_keyed.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
         L.abc_hip_keyed_small.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_size_t]
@@ -328,6 +331,29 @@ class Context:
         a4 = self._batch(ct, 3)
         r = self._run("apply_galois", [a4], a4.shape, a4.shape[2], C.c_uint32(elt), C.c_size_t(a4.shape[0]))
         return r if np.ndim(ct) == 4 else r[0]
+
+    def _hoisted(self, name, ct, ctype, items):
+        a4 = self._batch(ct, 3)
+        items = [int(x) for x in items]
+        arr = (ctype * max(len(items), 1))(*items)
+        shp = (len(items),) + a4.shape
+        cb = self.upload(a4)
+        out = self.alloc(int(np.prod(shp)) * 8)
+        try:
+            _chk(getattr(lib(), "abc_hip_" + name)(self.h, cb.ptr, out.ptr, a4.shape[2], arr, len(items), a4.shape[0]))
+            r = self.download(out, shp)
+        finally:
+            cb.free(); out.free()
+        return r if np.ndim(ct) == 4 else r[:, 0]
+
+    def apply_galois_hoisted(self, ct, elts):
+        """several Galois elements of one input (hoisted form): [H][(count,) 2][nl][N], slab r for elts[r].
+        Groundwork: slower than H rotate calls until the kernels share the decomposition."""
+        return self._hoisted("apply_galois_hoisted", ct, C.c_uint32, elts)
+
+    def rotate_hoisted(self, ct, steps):
+        """the same for rotation steps; step 0 is a copy, a step without a key of its own is an error"""
+        return self._hoisted("rotate_hoisted", ct, C.c_int, steps)
 
     def _plain_op(self, name, ct, plain):
         a4 = self._batch(ct, 3)

@@ -217,19 +217,51 @@ const double *key_twin_lookup(const abc_hip_ctx *c, const u64 *key) {  // no bui
   auto it = c->key_mirrors.find(key);
   return it == c->key_mirrors.end() ? nullptr : it->second.twin;
 }
-void refresh_key_mirrors(abc_hip_ctx *c, const u64 *key) {
+// The permuted key of a hoisted rotation: an index permutation of every row (k_galois in NTT form over the L * 2 polynomials of K
+// limbs).  Not subject to no_key_twin: without it the hoisted form has no key to switch with.
+static int fill_permuted(abc_hip_ctx *c, const u64 *key, u64 *perm, u32 ginv) {
+  return launch_galois(c, key, perm, c->K, (size_t)c->L * 2, ginv, true);
+}
+const u64 *key_permuted(abc_hip_ctx *c, const u64 *key, u32 ginv) {
+  auto it = c->key_mirrors.find(key);
+  if (it != c->key_mirrors.end() && it->second.perm) return it->second.perm;
+  if (c->buffers.capturing) { set_error("permuted Galois key not built during graph capture: run the sequence once eagerly first"); return nullptr; }
+  u64 *d = nullptr;
+  if (alloc_context_buffer(c, (void **)&d, c->key_words() * 8, true) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("no device memory for the permuted Galois key");
+    return nullptr;
+  }
+  if (fill_permuted(c, key, d, ginv)) { retire_buffer(c, d); return nullptr; }
+  abc_hip_ctx::KeyMirror &m = c->key_mirrors[key];
+  m.perm = d;
+  m.perm_ginv = ginv;
+  return d;
+}
+int refresh_key_mirrors(abc_hip_ctx *c, const u64 *key) {
+  // the permuted keys first: they are keys with twins of their own, filled from them in the second pass (one stream: in order)
+  const u64 *perm_of_key = nullptr;
+  for (auto &kv : c->key_mirrors)
+    if ((!key || kv.first == key) && kv.second.perm) {
+      if (fill_permuted(c, kv.first, kv.second.perm, kv.second.perm_ginv)) return 1;  // a stale permuted key must not go unseen
+      if (key) perm_of_key = kv.second.perm;
+    }
   for (auto &kv : c->key_mirrors)  // whatever the switches say now: a recorded circuit may read the mirrors
-    if (!key || kv.first == key) {
+    if (!key || kv.first == key || kv.first == perm_of_key) {
       if (kv.second.twin) fill_mirror(c, k_key_to_fp, kv.first, kv.second.twin);
       if (kv.second.shoup) fill_mirror(c, k_key_to_shoup, kv.first, kv.second.shoup);
     }
+  ABC_HIP_CHECK(hipGetLastError());
+  return 0;
 }
 void release_key(abc_hip_ctx *c, u64 *key) {
   auto it = c->key_mirrors.find(key);
   if (it != c->key_mirrors.end()) {
+    u64 *perm = it->second.perm;
     retire_buffer(c, it->second.twin);
     retire_buffer(c, it->second.shoup);
     c->key_mirrors.erase(it);
+    if (perm) release_key(c, perm);  // and the mirrors of the permuted key
   }
   retire_buffer(c, key);
 }

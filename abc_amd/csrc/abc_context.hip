@@ -436,6 +436,41 @@ static int rotate(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, int steps, si
   return 0;
 }
 
+// Several Galois elements of one input, out[r] = (g(ks0 + c0), g(ks1)) with ks = KeySwitch(c1, key'_g) on the UNPERMUTED c1
+// (DESIGN.md section 4).  elts[r] == 0: slab r is a copy of the input (rotate_hoisted's step 0).  Every argument is checked before
+// anything is launched; the permuted keys are built next (mirrors of keys: a later failure leaves them, as a first use of a key's
+// fp64 twin would), and the arena grows last, so a call that fails has written no ciphertext and no scratch.  Per element the key
+// switch is the plain one of this level (route_keyswitch): nothing is shared between the elements yet.
+static int hoisted(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, const std::vector<uint32_t> &elts, size_t count) {
+  const size_t N = (size_t)c->n, pw = (size_t)nl * N, ctw = count * 2 * pw;
+  const uint64_t m = 2 * (uint64_t)N;
+  std::vector<const u64 *> keys(elts.size(), nullptr);
+  for (size_t r = 0; r < elts.size(); r++) {
+    if (!elts[r]) continue;
+    auto it = c->d_galois.find(elts[r]);
+    if (it == c->d_galois.end()) { set_error("Galois key not present"); return 1; }
+    keys[r] = it->second;
+  }
+  if (elts.empty() || !count) return 0;
+  const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out;
+  if (i0 < o0 + elts.size() * ctw * 8 && o0 < i0 + ctw * 8) { set_error("hoisted rotations: d_out must not overlap d_in"); return 1; }
+  for (size_t r = 0; r < elts.size(); r++)  // inside a capture they must exist already
+    if (keys[r] && !(keys[r] = key_permuted(c, keys[r], (uint32_t)host::invmod(elts[r], m)))) return 1;
+  if (ensure_aux(c, 0, ctw * 8)) return 1;
+  const bool ntt_form = (c->scheme == ABC_HIP_SCHEME_CKKS);
+  u64 *ks = (u64 *)c->aux[0];
+  for (size_t r = 0; r < elts.size(); r++) {
+    u64 *slab = out + r * ctw;
+    if (!elts[r]) {
+      ABC_HIP_CHECK(hipMemcpyAsync(slab, in, ctw * 8, hipMemcpyDeviceToDevice, c->stream));
+      continue;
+    }
+    if (keyswitch(c, in + pw, 2 * pw, keys[r], ks, nl, count, in, 2 * pw, false)) return 1;
+    if (launch_galois(c, ks, slab, nl, count * 2, elts[r], ntt_form)) return 1;
+  }
+  return 0;
+}
+
 static int relinearize(abc_hip_ctx *c, const u64 *ct3, u64 *out2, int nl, size_t count) {
   if (!c->d_relin) { set_error("relinearize: no relinearisation key"); return 1; }
   const size_t pw = (size_t)nl * c->n;
@@ -738,7 +773,7 @@ static int load_key(abc_hip_ctx *c, uint64_t **slot, const uint64_t *h, size_t w
   const bool fresh = !*slot;
   if (fresh) ABC_HIP_CHECK(alloc_context_buffer(c, (void **)slot, words * 8, false));
   ABC_HIP_CHECK(hipMemcpy(*slot, h, words * 8, hipMemcpyHostToDevice));
-  if (!fresh) refresh_key_mirrors(c, *slot);
+  if (!fresh && refresh_key_mirrors(c, *slot)) return 1;
   ABC_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -900,6 +935,26 @@ int abc_hip_apply_galois(abc_hip_ctx *c, const uint64_t *in, uint64_t *out, int 
   if (check_level(c, nl)) return 1;
   if (in == out) { set_error("apply_galois: in-place not supported, use abc_hip_rotate"); return 1; }
   return apply_galois(c, in, out, nl, elt, count);
+}
+int abc_hip_apply_galois_hoisted(abc_hip_ctx *c, const uint64_t *in, uint64_t *out, int nl, const uint32_t *h_elts, int n_elts,
+                                 size_t count) {
+  CTX_GUARD(c);
+  if (check_level(c, nl)) return 1;
+  if (n_elts < 0 || (n_elts && !h_elts)) { set_error("apply_galois_hoisted: bad element list"); return 1; }
+  for (int r = 0; r < n_elts; r++)
+    if (!(h_elts[r] & 1) || h_elts[r] >= 2u * (uint32_t)c->n) { set_error("Galois element must be odd and below 2N"); return 1; }
+  return guarded([&] { return hoisted(c, in, out, nl, std::vector<uint32_t>(h_elts, h_elts + n_elts), count); });
+}
+int abc_hip_rotate_hoisted(abc_hip_ctx *c, const uint64_t *in, uint64_t *out, int nl, const int *h_steps, int n_steps, size_t count) {
+  CTX_GUARD(c);
+  if (check_level(c, nl)) return 1;
+  if (n_steps < 0 || (n_steps && !h_steps)) { set_error("rotate_hoisted: bad step list"); return 1; }
+  std::vector<uint32_t> elts((size_t)n_steps, 0);
+  for (int r = 0; r < n_steps; r++) {
+    if (!h_steps[r]) continue;  // a copy
+    if (!(elts[r] = elt_from_step(c, h_steps[r]))) { set_error("step count too large"); return 1; }
+  }
+  return guarded([&] { return hoisted(c, in, out, nl, elts, count); });
 }
 int abc_hip_multiply_plain(abc_hip_ctx *c, const uint64_t *ct, const uint64_t *plain, size_t plain_stride, uint64_t *out, int size,
                            int nl, size_t count) {

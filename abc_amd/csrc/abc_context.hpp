@@ -158,10 +158,13 @@ struct abc_hip_ctx {
   uint64_t *d_sk = nullptr, *d_pk = nullptr, *d_relin = nullptr;
   std::map<uint32_t, uint64_t *> d_galois;
   // mirrors of key-switching keys (fp64 twin: centred doubles; Shoup quotients; same layout), built on first use, rebuilt in place
-  // when the key they mirror is rewritten (abc_buffers.hip)
+  // when the key they mirror is rewritten (abc_buffers.hip).  perm: the Galois key with every [N] row permuted by the inverse
+  // element perm_ginv (hoisted rotations); it is a key-switching key itself and has an entry, and so mirrors, of its own.
   struct KeyMirror {
     double *twin = nullptr;
     uint64_t *shoup = nullptr;
+    uint64_t *perm = nullptr;
+    uint32_t perm_ginv = 0;
   };
   std::unordered_map<const uint64_t *, KeyMirror> key_mirrors;
   std::vector<uint32_t> galois_order;
@@ -344,9 +347,13 @@ int bsplit_back13(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const doubl
 const double *key_twin(abc_hip_ctx *c, const u64 *key);
 const double *key_twin_lookup(const abc_hip_ctx *c, const u64 *key);  // never builds: safe once the lanes have forked
 const u64 *key_shoup(abc_hip_ctx *c, const u64 *key);
+// key'_g of a hoisted rotation: `key` with every [N] row permuted by ginv = g^-1 mod 2N in NTT form.  Built on
+// c->stream on first use, whatever ABC_HIP_NO_KEY_TWIN says (it is semantics, not an optimisation); nullptr with the error set:
+// allocation failed, or a capture is in progress and it is not built yet
+const u64 *key_permuted(abc_hip_ctx *c, const u64 *key, u32 ginv);
 // rewrite the existing mirrors of `key` (nullptr: of every key) from its current words, in the same buffers, on c->stream: a
 // recorded circuit keeps their addresses and reads the new key
-void refresh_key_mirrors(abc_hip_ctx *c, const u64 *key /* nullptr: all */);
+int refresh_key_mirrors(abc_hip_ctx *c, const u64 *key /* nullptr: all */);  // non-zero: a launch failed, error set
 // a key-switching key that goes (keygen drops a non-default Galois element): the key and its mirrors are retired
 void release_key(abc_hip_ctx *c, u64 *key);
 // internal lanes (streams forked off the context's stream): chunks of one call alternate over them (abc_kernels_fused.hip)

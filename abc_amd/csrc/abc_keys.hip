@@ -378,7 +378,7 @@ static int keygen_with(abc_hip_ctx *c, D &draws) {
   }
   ABC_HIP_CHECK(st.wipe());  // before anything is released
   for (auto &kv : old_galois) release_key(c, kv.second);  // held back while a live graph may read it
-  refresh_key_mirrors(c, nullptr);
+  if (refresh_key_mirrors(c, nullptr)) return 1;
   ABC_HIP_CHECK(hipGetLastError());
   return 0;
 }

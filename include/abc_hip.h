@@ -184,6 +184,26 @@ int abc_hip_mul_relin(abc_hip_ctx *ctx, const uint64_t *d_a, const uint64_t *d_b
 int abc_hip_rotate(abc_hip_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, int nl, int steps, size_t count);
 /* Evaluator::apply_galois for one element */
 int abc_hip_apply_galois(abc_hip_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, int nl, uint32_t galois_elt, size_t count);
+/* Several Galois elements of ONE input in one call, in the HOISTED FORM of a rotation (definition, and why this form: DESIGN.md
+ * section 4).  d_in [count][2][nl][N] -> d_out [n_elts][count][2][nl][N], for an odd g = h_elts[r] < 2N with a Galois key:
+ *   out[r] = ( s_g(ks0 + c0), s_g(ks1) ),  (ks0, ks1) = KeySwitch(c1, key'_g),
+ * s_g the automorphism x -> x^g in the ciphertext's own form (NTT-index permutation for CKKS, coefficient permutation with
+ * sign for BFV), key'_g the key of g with every [N] row permuted by g^-1 mod 2N in NTT form (a device mirror of the key, built
+ * on first use).  The key switch runs on the UNPERMUTED c1, so its decomposition does not depend on g.  The result decrypts to
+ * the same plaintext as abc_hip_apply_galois's, with the same noise distribution; it is NOT bit-identical to it.
+ * GROUNDWORK, NOT A FAST PATH: the kernels do not share the decomposition between the elements yet.  Each element costs a whole key
+ * switch and a permutation pass, measured 16 % SLOWER than the same number of abc_hip_rotate calls, and one
+ * more key-sized device buffer per element used.  Call abc_hip_rotate unless this form itself is what is wanted.
+ * Duplicate elements are allowed, each gets its own slab; n_elts == 0 and count == 0 succeed and enqueue nothing.  Fails for an
+ * even or out-of-range element, an element without a key, a bad level, or d_out overlapping d_in: nothing is then written to d_out
+ * or to scratch (where a later step fails, allocation say, permuted keys of earlier elements may have been built: mirrors only).
+ * h_elts is read during the call only.  Capturable, under the "run once eagerly first" rule of abc_hip_graph_begin. */
+int abc_hip_apply_galois_hoisted(abc_hip_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, int nl, const uint32_t *h_elts, int n_elts,
+                                 size_t count);
+/* The same for rotation steps, as abc_hip_rotate counts them; step 0 copies the input.  A step without a key of its own fails
+ * ("Galois key not present"): a NAF chain is sequential and has nothing to hoist. */
+int abc_hip_rotate_hoisted(abc_hip_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, int nl, const int *h_steps, int n_steps,
+                           size_t count);
 /* The three plaintext operations.  d_out may be d_ct (the reference's *_inplace call sites); size = 2 or 3.
  * plain_stride, in words, is the distance from ciphertext i's plaintext to ciphertext i + 1's:
  *   0            one plaintext, broadcast to the batch (d_plain holds N words for BFV, nl * N for CKKS);

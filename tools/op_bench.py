@@ -51,6 +51,31 @@ def main():
         res[k] = {"batch": B, "ms": ms, "ops_per_s": B / ms * 1e3}
         print("%-40s %8.3f ms / %d  -> %10.0f op/s" % (k, ms, B, B / ms * 1e3), flush=True)
     del a, b, out
+    # ---- H rotations of one input at nl = 3 (the level of config 3's rotations): H abc_hip_rotate calls against one
+    # abc_hip_rotate_hoisted call, alternating in one process, the separate calls repeated so that their own spread shows ----
+    for H in (2, 8):
+        names = ["ckks14_L3_rotate_x%d_%s" % (H, kind) for kind in ("separate", "hoisted")]
+        if not any(only in k for k in names):
+            continue
+        steps = [1 << i for i in range(H)]
+        a, nb = rand_ct(g, rng, B, 2, 3)
+        outs = g.alloc(H * nb)
+        slab = [C.c_void_p(outs.ptr.value + r * nb) for r in range(H)]
+        arr = (C.c_int * H)(*steps)
+
+        def separate():
+            for r in range(H):
+                g.op("rotate", a.ptr, slab[r], 3, steps[r], cb)
+        runs = {names[0]: [], names[1]: []}
+        for rep in range(5):  # separate, hoisted, separate, hoisted, separate
+            k = names[rep & 1]
+            if only in k:
+                runs[k].append(timeit(g, separate if not rep & 1 else lambda: g.op("rotate_hoisted", a.ptr, outs.ptr, 3, arr, H, cb)))
+        for k, ms in runs.items():
+            if ms:
+                res[k] = {"batch": B, "rotations": H, "ms": min(ms), "ms_runs": ms, "route": g.route("keyswitch" if k == names[1] else "rotate", 3, B)}
+                print("%-40s %s ms / %d x %d  (%s)" % (k, " ".join("%8.3f" % v for v in ms), H, B, res[k]["route"]), flush=True)
+        del a, outs
     g.close()
     # ---- CKKS slot codec (abc_hip_ckks_encode / _decode), batch 256; bytes = the minimum HBM traffic of the sequence ----
     hbm = 8e12  # MI355X HBM3E peak, bytes/s
