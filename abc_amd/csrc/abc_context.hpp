@@ -112,6 +112,34 @@ __device__ __forceinline__ FpTable fp_table(const DevCtx &c, int mid) {
   t.itw = (const ABC_CONST_AS double *)(b + (size_t)c.n);
   return t;
 }
+// modulus constants and twiddle table of an arithmetic policy (abc_ntt.hpp), each fetched the way its kernels always did
+template <class A>
+__device__ __forceinline__ Mod arith_mod(const DevCtx &c, int id) {
+  if constexpr (std::is_same_v<typename A::E, double>) return mod_at(c, id);
+  else return c.mods[id];
+}
+template <class A>
+__device__ __forceinline__ typename A::Table arith_table(const DevCtx &c, int mid) {
+  if constexpr (std::is_same_v<typename A::E, double>) return fp_table(c, mid);
+  else return ntt_table(c, mid);
+}
+// p^-1 mod q_j for the two dropped primes there are: the special prime (key-switch mod-down), limb l = nl - 1 (rescale)
+__device__ __forceinline__ DropInv inv_special_at(const DevCtx &c, int j) {
+  return DropInv{c.cst->inv_special[j], c.cst->inv_special_s[j], c.cst->inv_special_c[j], c.cst->inv_special_cq[j]};
+}
+__device__ __forceinline__ DropInv inv_qlast_at(const DevCtx &c, int l, int j) {
+  return DropInv{c.cst->inv_qlast[l][j], c.cst->inv_qlast_s[l][j], c.cst->inv_qlast_c[l][j], c.cst->inv_qlast_cq[l][j]};
+}
+// The `members` workgroups that read one shared polynomial are 8 apart in blockIdx: workgroups go round-robin over the 8 XCDs,
+// so they share one L2 and the polynomial is fetched from HBM once, not `members` times.  Polynomials are taken eight at a time;
+// the last group may be ragged.  -> member j of polynomial p
+__device__ __forceinline__ void xcd_slot(unsigned bid, int members, int npoly, int &j, size_t &p) {
+  const unsigned per = 8u * (unsigned)members;
+  const unsigned grp = bid / per, rem = bid % per;
+  const unsigned left = (unsigned)npoly - grp * 8u, gsz = left < 8u ? left : 8u;
+  j = (int)(rem / gsz);
+  p = (size_t)grp * 8 + rem % gsz;
+}
 
 }  // namespace abc
 

@@ -7,6 +7,9 @@
 // Key switching follows seal::Evaluator::switch_key_inplace: decomposition limb J is reduced modulo
 // every key-level prime, transformed, multiplied with key[J] and accumulated; the special-prime limb is
 // then divided out with rounding.  All outputs are fully reduced, hence bit-comparable with oracle/.
+// That division and rescale's are one piece of mathematics (abc_ntt.hpp, "divide by a dropped prime"): the generic pair
+// k_divround_tmod / k_divround_finish serves both, and rescale's LDS-resident kernels call the bodies the key switch's mod-down
+// calls (divround_to_coef, divround_finish).
 #include <cstdlib>
 
 #include "abc_context.hpp"
@@ -123,52 +126,62 @@ __global__ __launch_bounds__(256) void k_ks_inner(DevCtx c, const u64 *dec, cons
   }
 }
 
-// tmod[ct][comp][j][k] = ((prodS + half) mod q_sp) mod q_j  + (q_j - half mod q_j)
-__global__ __launch_bounds__(256) void k_ks_tmod(DevCtx c, const u64 *prodS, u64 *tmod, int nl, size_t polys) {
+// ---- divide by a dropped prime with rounding, one thread per coefficient (abc_ntt.hpp has the mathematics): the pair of kernels
+// around the stand-alone transforms, for the key switch's special prime and for rescale's last limb ----
+// tmod[poly][j < nrem][k] = ((last + half) mod p) mod q_j + fix(p, q_j),  p = prime `drop`, last = its limb in coefficient form
+__global__ __launch_bounds__(256) void k_divround_tmod(DevCtx c, const u64 *last, u64 *tmod, int drop, int nrem, size_t polys) {
   const size_t items = polys * c.n;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const Mod msp = c.mods[c.K - 1];
-  const u64 half = msp.q >> 1;
+  const Mod md = c.mods[drop];
+  const u64 half = md.q >> 1;
   for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride) {
     const size_t p = it >> c.logn, k = it & (c.n - 1);
-    const u64 last = add_mod(prodS[it], half, msp.q);
-    for (int j = 0; j < nl; j++) {
+    const u64 v = add_mod(last[it], half, md.q);
+    for (int j = 0; j < nrem; j++) {
       const Mod m = c.mods[j];
-      const u64 fix = m.q - reduce64(half, m);
-      tmod[(p * nl + j) * c.n + k] = add_mod(reduce64(last, m), fix == m.q ? 0 : fix, m.q);
+      tmod[(p * nrem + j) * c.n + k] = add_mod(reduce64(v, m), round_fix(half, m), m.q);
     }
   }
 }
 
-// out[ct][comp][j][k] = (prodD - tmod) * q_sp^-1 mod q_j  (+ addend)
-__global__ __launch_bounds__(256) void k_ks_finish(DevCtx c, const u64 *prodD, const u64 *tmod, u64 *out, const u64 *addend,
-                                                   size_t addend_stride, int add_c1, int nl, size_t count) {
-  const size_t pw = (size_t)nl * c.n;
-  const size_t items = count * 2 * pw;
+// out[poly][j < nrem][k] = (in[poly][j] - tmod) * p^-1 mod q_j  (+ addend);  in: in_limbs limbs per polynomial; inv, inv_s: p^-1 mod
+// q_j and its Shoup quotient (a row of DevConst); polynomials are (ct, comp) pairs where there is an addend
+__global__ __launch_bounds__(256) void k_divround_finish(DevCtx c, const u64 *in, int in_limbs, const u64 *tmod, u64 *out, const u64 *inv,
+                                                         const u64 *inv_s, const u64 *addend, size_t addend_stride, int add_c1, int nrem,
+                                                         size_t polys) {
+  const size_t items = polys * nrem * (size_t)c.n;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride) {
-    const size_t ct = it / (2 * pw), r = it % (2 * pw);
-    const int comp = (int)(r / pw);
-    const size_t w = r % pw;
-    const int j = (int)(w >> c.logn);
+    const size_t limb = it >> c.logn, k = it & (c.n - 1);
+    const size_t p = limb / nrem;
+    const int j = (int)(limb % nrem);
     const u64 q = c.mods[j].q;
-    u64 v = mul_shoup(sub_mod(prodD[it], tmod[it], q), c.cst->inv_special[j], c.cst->inv_special_s[j], q);
-    if (addend && (comp == 0 || add_c1)) v = add_mod(v, addend[ct * addend_stride + r], q);
+    u64 v = mul_shoup(sub_mod(in[(p * in_limbs + j) * c.n + k], tmod[it], q), inv[j], inv_s[j], q);
+    if (addend && ((p & 1) == 0 || add_c1)) v = add_mod(v, addend[(p >> 1) * addend_stride + ((p & 1) * nrem + j) * c.n + k], q);
     out[it] = v;
   }
 }
 
-int launch_ks_tmod(abc_hip_ctx *c, const u64 *prodS, u64 *tmod, int nl, size_t polys) {
-  hipLaunchKernelGGL(k_ks_tmod, dim3(grid_for(polys * c->n, 256)), dim3(256), 0, c->stream, c->dc, prodS, tmod, nl, polys);
+static int launch_divround_tmod(abc_hip_ctx *c, const u64 *last, u64 *tmod, int drop, int nrem, size_t polys) {
+  hipLaunchKernelGGL(k_divround_tmod, dim3(grid_for(polys * c->n, 256)), dim3(256), 0, c->stream, c->dc, last, tmod, drop, nrem, polys);
   ABC_HIP_CHECK(hipGetLastError());
   return 0;
 }
-int launch_ks_finish(abc_hip_ctx *c, const u64 *prodD, const u64 *tmod, u64 *out, const u64 *addend, size_t addend_stride,
-                     bool add_c1, int nl, size_t count) {
-  hipLaunchKernelGGL(k_ks_finish, dim3(grid_for(count * 2 * nl * (size_t)c->n, 256)), dim3(256), 0, c->stream, c->dc, prodD, tmod,
-                     out, addend, addend_stride, add_c1 ? 1 : 0, nl, count);
+static int launch_divround_finish(abc_hip_ctx *c, const u64 *in, int in_limbs, const u64 *tmod, u64 *out, const u64 *inv, const u64 *inv_s,
+                                  const u64 *addend, size_t addend_stride, bool add_c1, int nrem, size_t polys) {
+  hipLaunchKernelGGL(k_divround_finish, dim3(grid_for(polys * nrem * (size_t)c->n, 256)), dim3(256), 0, c->stream, c->dc, in, in_limbs,
+                     tmod, out, inv, inv_s, addend, addend_stride, add_c1 ? 1 : 0, nrem, polys);
   ABC_HIP_CHECK(hipGetLastError());
   return 0;
+}
+// the key switch's: p = the special prime
+int launch_ks_tmod(abc_hip_ctx *c, const u64 *prodS, u64 *tmod, int nl, size_t polys) {
+  return launch_divround_tmod(c, prodS, tmod, c->K - 1, nl, polys);
+}
+int launch_ks_finish(abc_hip_ctx *c, const u64 *prodD, const u64 *tmod, u64 *out, const u64 *addend, size_t addend_stride,
+                     bool add_c1, int nl, size_t count) {
+  return launch_divround_finish(c, prodD, nl, tmod, out, c->dc.cst->inv_special, c->dc.cst->inv_special_s, addend, addend_stride, add_c1,
+                                nl, count * 2);
 }
 
 // ---- N = 2^15 / 2^16, integer arithmetic (a key prime above 2^50: config 5's 55-bit chain): decomposition and inner product
@@ -310,7 +323,7 @@ __global__ __launch_bounds__((1 << LB) / 16, 3) void k_iks_special(DevCtx c, con
 // BFV: everything behind k_iks_special in one kernel -- (ct, component, 256 positions): the strided last stages of the special
 // limb's inverse transform, N^-1, + q_sp/2 -> t (2^R values in registers); then per data prime the same stages on its limb,
 // N^-1, minus (t mod q_j + the rounding fix), times q_sp^-1, plus the addend -> coefficient form.  Replaces two strided passes
-// (in place: a read and a write of 2 (nl + 1) limbs), k_ks_tmod (2 nl limbs written, read back) and k_ks_finish.
+// (in place: a read and a write of 2 (nl + 1) limbs), k_divround_tmod (2 nl limbs written, read back) and k_divround_finish.
 template <int R>
 __global__ __launch_bounds__(256) void k_iks_finish(DevCtx c, const u64 *__restrict__ prodD, const u64 *__restrict__ prodS,
                                                     const u64 *addend, size_t addend_stride, int add_c1, u64 *out /* may be the addend */,
@@ -357,7 +370,7 @@ __global__ __launch_bounds__(256) void k_iks_finish(DevCtx c, const u64 *__restr
 #pragma unroll
     for (int k = 0; k < (1 << R); k++) x[k] = src[(size_t)k * G];
     inverse_stages(x, m, ntt_table(c, j));
-    const u64 fix0 = m.q - reduce64(half, m), fix = fix0 == m.q ? 0 : fix0;
+    const u64 fix = round_fix(half, m);
     const u64 inv = c.cst->inv_special[j], inv_s = c.cst->inv_special_s[j];
     u64 *o = out + (cc * nl + j) * N + p;
     const u64 *cin = add ? addend + ct * addend_stride + ((size_t)comp * nl + j) * N + p : nullptr;
@@ -531,40 +544,16 @@ __global__ __launch_bounds__(256) void k_gather_last(DevCtx c, const u64 *in, u6
     last[it] = in[(p * nl + (nl - 1)) * c.n + k];
   }
 }
-__global__ __launch_bounds__(256) void k_rescale_tmod(DevCtx c, const u64 *last, u64 *tmod, int nl, size_t polys) {
-  const size_t items = polys * c.n;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const Mod ml = c.mods[nl - 1];
-  const u64 half = ml.q >> 1;
-  for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride) {
-    const size_t p = it >> c.logn, k = it & (c.n - 1);
-    const u64 v = add_mod(last[it], half, ml.q);
-    for (int j = 0; j < nl - 1; j++) {
-      const Mod m = c.mods[j];
-      const u64 hm = reduce64(half, m);
-      tmod[(p * (nl - 1) + j) * c.n + k] = add_mod(reduce64(v, m), hm ? m.q - hm : 0, m.q);
-    }
-  }
-}
-__global__ __launch_bounds__(256) void k_rescale_finish(DevCtx c, const u64 *in, const u64 *tmod, u64 *out, int nl, size_t polys) {
-  const int nlo = nl - 1;
-  const size_t items = polys * nlo * (size_t)c.n;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t it = (size_t)blockIdx.x * blockDim.x + threadIdx.x; it < items; it += stride) {
-    const size_t limb = it >> c.logn, k = it & (c.n - 1);
-    const size_t p = limb / nlo;
-    const int j = (int)(limb % nlo);
-    const u64 q = c.mods[j].q;
-    const u64 x = in[(p * nl + j) * c.n + k];
-    out[it] = mul_shoup(sub_mod(x, tmod[it], q), c.cst->inv_qlast[nl - 1][j], c.cst->inv_qlast_s[nl - 1][j], q);
-  }
-}
 
-// ---- the same for rings that fit LDS and primes below 2^50: two kernels instead of five ----
+// ---- the same for rings that fit LDS: two kernels instead of five (steps A and B of abc_ntt.hpp's "divide and round") ----
 // R1 (poly): inverse transform of the last limb, read in place, + q_last/2 -> scratch.
-// R2 (poly, j < nl-1): scratch + rounding fix as operand of a forward transform modulo q_j in LDS (no reduction: the
-//     fp64 bound absorbs a 50-bit operand), then (in_j - transform) * q_last^-1 -> out_j.  The nl-1 workgroups that read one
-//     scratch polynomial are 8 apart in blockIdx (one XCD, one L2).  7 + 2 limb transfers per polynomial instead of 23.
+// R2 (poly, j < nl-1): scratch + rounding fix as operand of a forward transform modulo q_j in LDS, then
+//     (in_j - transform) * q_last^-1 -> out_j.  The nl-1 workgroups that read one scratch polynomial share an L2 (xcd_slot).
+//     7 + 2 limb transfers per polynomial instead of 23.
+// !MIXED: every prime below 2^50, fp64 throughout (no reduction of the operand: the fp64 bound absorbs a 50-bit one).
+// MIXED (chains that contain a prime above 2^50): the arithmetic chosen per prime -- the inverse transform runs in that of the
+// dropped prime (fp_last), each forward transform in that of its own prime j (bit j of fpmask: below 2^50), workgroup-uniform.
+// R1 keeps its all-fp64 form as a kernel of its own: as an instantiation of the mixed one its register count changed.
 template <int LB>
 __global__ __launch_bounds__((1 << LB) / 16) void k_rescale_intt_fp(DevCtx c, const u64 *__restrict__ in, u64 *__restrict__ last,
                                                                     int nl) {
@@ -581,110 +570,51 @@ __global__ __launch_bounds__((1 << LB) / 16) void k_rescale_intt_fp(DevCtx c, co
       0);
 }
 template <int LB>
-__global__ __launch_bounds__((1 << LB) / 16) void k_rescale_ntt_fp(DevCtx c, const u64 *__restrict__ in, const u64 *__restrict__ last,
-                                                                   u64 *__restrict__ out, int nl, int npoly) {
-  __shared__ double lds[lds_words(LB)];
-  const int nlo = nl - 1;
-  const unsigned per = 8u * (unsigned)nlo;
-  const unsigned grp = blockIdx.x / per, rem = blockIdx.x % per;
-  const unsigned left = (unsigned)npoly - grp * 8u, gsz = left < 8u ? left : 8u;  // the last group may be ragged
-  const int j = (int)(rem / gsz);
-  const size_t p = (size_t)grp * 8 + rem % gsz;
-  const size_t N = (size_t)1 << LB;
-  const Mod m = mod_at(c, j);
-  const FpTable t = fp_table(c, j);
-  const u64 half = c.mods[nl - 1].q >> 1;
-  const u64 hm = reduce64(half, m);
-  const double fix = hm ? (double)(m.q - hm) : 0.0;
-  const double inv = c.cst->inv_qlast_c[nl - 1][j], inv_q = c.cst->inv_qlast_cq[nl - 1][j];
-  const u64 *__restrict__ src = last + p * N;
-  const u64 *__restrict__ x = in + (p * nl + j) * N;
-  u64 *__restrict__ o = out + (p * nlo + j) * N;
-  ntt_fwd_block_a<LB, FpArith>(
-      lds, [&](int, int i) { return fp_from_u64(src[i]) + fix; },
-      [&](int, int i, double v) { o[i] = fp_to_canon(fp_mul_lazy(fp_from_u64(x[i]) - v, inv, inv_q, m.qd), m.qd, m.qinv); }, t, m, 0,
-      0);
-}
-template <int LB>
-static int launch_rescale_fp(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, size_t polys) {
-  const size_t N = (size_t)1 << LB;
-  if (ensure_workspace(c, polys * N * 8)) return 1;
-  u64 *last = (u64 *)c->ws;
-  const dim3 block((1 << LB) / 16);
-  hipLaunchKernelGGL(k_rescale_intt_fp<LB>, dim3((unsigned)polys), block, 0, c->stream, c->dc, in, last, nl);
-  hipLaunchKernelGGL(k_rescale_ntt_fp<LB>, dim3((unsigned)(polys * (nl - 1))), block, 0, c->stream, c->dc, in, last, out, nl,
-                     (int)polys);
-  ABC_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
-// The same two kernels with the arithmetic chosen per prime (chains that contain a prime above 2^50): the inverse transform runs in
-// the arithmetic of the dropped prime, each forward transform in that of its own prime j (bit j of fpmask: below 2^50).
-template <int LB>
 __global__ __launch_bounds__((1 << LB) / 16) void k_rescale_intt_mixed(DevCtx c, const u64 *__restrict__ in, u64 *__restrict__ last, int nl,
                                                                        int fp_last) {
   __shared__ u64 lds_raw[lds_words(LB)];
   const size_t N = (size_t)1 << LB;
   const u64 *__restrict__ src = in + ((size_t)blockIdx.x * nl + (nl - 1)) * N;
   u64 *__restrict__ dst = last + (size_t)blockIdx.x * N;
-  if (fp_last) {
-    const Mod m = mod_at(c, nl - 1);
-    const FpTable t = fp_table(c, nl - 1);
-    const double half = (double)(m.q >> 1);
-    ntt_inv_block_a<LB, FpArith>(
-        reinterpret_cast<double *>(lds_raw), [&](int, int i) { return fp_from_u64(src[i]); },
-        [&](int, int i, double v) { dst[i] = fp_to_canon(fp_mul_lazy(v, m.inv_n_c, m.inv_n_cq, m.qd) + half, m.qd, m.qinv); }, t, m, 0, 0);
-  } else {
-    const Mod m = c.mods[nl - 1];
-    const NttTable t = ntt_table(c, nl - 1);
-    const u64 half = m.q >> 1;
-    ntt_inv_block<LB>(
-        lds_raw, [&](int, int i) { return src[i]; }, [&](int, int i, u64 v) { dst[i] = add_mod(scale_inv_n(v, m), half, m.q); }, t, m, 0, 0);
-  }
+  if (fp_last)
+    divround_to_coef<LB, FpArith>(reinterpret_cast<double *>(lds_raw), mod_at(c, nl - 1), fp_table(c, nl - 1), src, dst);
+  else
+    divround_to_coef<LB, IntArith<true>>(lds_raw, c.mods[nl - 1], ntt_table(c, nl - 1), src, dst);
 }
-template <int LB>
-__global__ __launch_bounds__((1 << LB) / 16) void k_rescale_ntt_mixed(DevCtx c, const u64 *__restrict__ in, const u64 *__restrict__ last,
-                                                                      u64 *__restrict__ out, int nl, int npoly, u32 fpmask) {
+template <int LB, bool MIXED>
+__global__ __launch_bounds__((1 << LB) / 16) void k_rescale_ntt(DevCtx c, const u64 *__restrict__ in, const u64 *__restrict__ last,
+                                                                u64 *__restrict__ out, int nl, int npoly, u32 fpmask) {
   __shared__ u64 lds_raw[lds_words(LB)];
-  const int nlo = nl - 1;
-  const unsigned per = 8u * (unsigned)nlo;
-  const unsigned grp = blockIdx.x / per, rem = blockIdx.x % per;
-  const unsigned left = (unsigned)npoly - grp * 8u, gsz = left < 8u ? left : 8u;  // the last group may be ragged
-  const int j = (int)(rem / gsz);
-  const size_t p = (size_t)grp * 8 + rem % gsz;
+  int j;
+  size_t p;
+  xcd_slot(blockIdx.x, nl - 1, npoly, j, p);
   const size_t N = (size_t)1 << LB;
-  const Mod mi = c.mods[j];
-  const u64 half = c.mods[nl - 1].q >> 1;
-  const u64 hm = reduce64(half, mi);
-  const u64 fixu = hm ? mi.q - hm : 0;
+  const Mod m = MIXED ? c.mods[j] : mod_at(c, j);
+  // MIXED: the dropped prime may be wider than 2^52 -- the rounding fix stays an integer and the fp64 load reduces first (REDUCE)
+  const auto fix = round_fix<std::conditional_t<MIXED, u64, double>>(c.mods[nl - 1].q >> 1, m);
+  const DropInv d = inv_qlast_at(c, nl - 1, j);
   const u64 *__restrict__ src = last + p * N;
   const u64 *__restrict__ x = in + (p * nl + j) * N;
-  u64 *__restrict__ o = out + (p * nlo + j) * N;
-  if ((fpmask >> j) & 1u) {  // workgroup-uniform
-    const Mod m = mod_at(c, j);
-    const FpTable t = fp_table(c, j);
-    const double inv = c.cst->inv_qlast_c[nl - 1][j], inv_q = c.cst->inv_qlast_cq[nl - 1][j];
-    // the dropped prime may be wider than 2^52: reduce modulo q_j as an integer first (canonical, + fix, below 2 q_j)
-    ntt_fwd_block_a<LB, FpArith>(
-        reinterpret_cast<double *>(lds_raw), [&](int, int i) { return fp_from_u64(add_mod(reduce64(src[i], mi), fixu, mi.q)); },
-        [&](int, int i, double v) { o[i] = fp_to_canon(fp_mul_lazy(fp_from_u64(x[i]) - v, inv, inv_q, m.qd), m.qd, m.qinv); }, t, m, 0, 0);
-  } else {
-    const NttTable t = ntt_table(c, j);
-    const u64 inv = c.cst->inv_qlast[nl - 1][j], inv_s = c.cst->inv_qlast_s[nl - 1][j];
-    ntt_fwd_block<LB, true>(
-        lds_raw, [&](int, int i) { return add_mod(reduce64(src[i], mi), fixu, mi.q); },
-        [&](int, int i, u64 v) { o[i] = mul_shoup(sub_mod(x[i], canon_fwd<true>(v, mi), mi.q), inv, inv_s, mi.q); }, t, mi, 0, 0);
-  }
+  u64 *__restrict__ o = out + (p * (nl - 1) + j) * N;
+  if constexpr (!MIXED)
+    divround_finish<LB, FpArith, false, false>(reinterpret_cast<double *>(lds_raw), m, fp_table(c, j), fix, d, src, x, nullptr, o);
+  else if ((fpmask >> j) & 1u)
+    divround_finish<LB, FpArith, true, false>(reinterpret_cast<double *>(lds_raw), mod_at(c, j), fp_table(c, j), fix, d, src, x, nullptr, o);
+  else
+    divround_finish<LB, IntArith<true>, false, false>(lds_raw, m, ntt_table(c, j), fix, d, src, x, nullptr, o);
 }
-template <int LB>
-static int launch_rescale_mixed(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, size_t polys, u32 fpmask) {
+template <int LB, bool MIXED>
+static int launch_rescale_lds(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, size_t polys, u32 fpmask) {
   const size_t N = (size_t)1 << LB;
   if (ensure_workspace(c, polys * N * 8)) return 1;
   u64 *last = (u64 *)c->ws;
   const dim3 block((1 << LB) / 16);
-  hipLaunchKernelGGL(k_rescale_intt_mixed<LB>, dim3((unsigned)polys), block, 0, c->stream, c->dc, in, last, nl, (int)((fpmask >> (nl - 1)) & 1u));
-  hipLaunchKernelGGL(k_rescale_ntt_mixed<LB>, dim3((unsigned)(polys * (nl - 1))), block, 0, c->stream, c->dc, in, last, out, nl, (int)polys,
-                     fpmask);
+  if constexpr (MIXED)
+    hipLaunchKernelGGL(k_rescale_intt_mixed<LB>, dim3((unsigned)polys), block, 0, c->stream, c->dc, in, last, nl, (int)((fpmask >> (nl - 1)) & 1u));
+  else
+    hipLaunchKernelGGL(k_rescale_intt_fp<LB>, dim3((unsigned)polys), block, 0, c->stream, c->dc, in, last, nl);
+  hipLaunchKernelGGL((k_rescale_ntt<LB, MIXED>), dim3((unsigned)(polys * (nl - 1))), block, 0, c->stream, c->dc, in, last, out, nl,
+                     (int)polys, fpmask);
   ABC_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -695,9 +625,9 @@ int launch_rescale(abc_hip_ctx *c, const u64 *in, u64 *out, int size, int nl, si
   if (!polys) return 0;
   const RescaleRoute r = route_rescale(c->facts, nl, in == out);
   if (r.kind == Rescale::mixed)  // a prime above 2^50 in the chain
-    return dispatch_logn<10, 14>(c->logn, [&](auto LB) { return launch_rescale_mixed<decltype(LB)::value>(c, in, out, nl, polys, r.fpmask); });
+    return dispatch_logn<10, 14>(c->logn, [&](auto LB) { return launch_rescale_lds<decltype(LB)::value, true>(c, in, out, nl, polys, r.fpmask); });
   if (r.kind == Rescale::fp)
-    return dispatch_logn<10, 14>(c->logn, [&](auto LB) { return launch_rescale_fp<decltype(LB)::value>(c, in, out, nl, polys); });
+    return dispatch_logn<10, 14>(c->logn, [&](auto LB) { return launch_rescale_lds<decltype(LB)::value, false>(c, in, out, nl, polys, 0u); });
   if (ensure_workspace(c, (polys * N + polys * (nl - 1) * N) * 8)) return 1;
   u64 *last = (u64 *)c->ws, *tmod = last + polys * N;
   hipLaunchKernelGGL(k_gather_last, dim3(grid_for(polys * N, 256)), dim3(256), 0, c->stream, c->dc, in, last, nl, polys);
@@ -705,13 +635,10 @@ int launch_rescale(abc_hip_ctx *c, const u64 *in, u64 *out, int size, int nl, si
   LimbMap lmap{};
   lmap.id[0] = nl - 1;
   if (launch_ntt_inv(c, last, lmap, 1, polys)) return 1;
-  hipLaunchKernelGGL(k_rescale_tmod, dim3(grid_for(polys * N, 256)), dim3(256), 0, c->stream, c->dc, last, tmod, nl, polys);
-  ABC_HIP_CHECK(hipGetLastError());
+  if (launch_divround_tmod(c, last, tmod, nl - 1, nl - 1, polys)) return 1;
   if (launch_ntt_fwd(c, tmod, key_limb_map(c, nl - 1), nl - 1, polys * (nl - 1))) return 1;
-  hipLaunchKernelGGL(k_rescale_finish, dim3(grid_for(polys * (nl - 1) * N, 256)), dim3(256), 0, c->stream, c->dc, in, tmod, out,
-                     nl, polys);
-  ABC_HIP_CHECK(hipGetLastError());
-  return 0;
+  return launch_divround_finish(c, in, nl, tmod, out, c->dc.cst->inv_qlast[nl - 1], c->dc.cst->inv_qlast_s[nl - 1], nullptr, 0, false, nl - 1,
+                                polys);
 }
 
 int launch_drop_last(abc_hip_ctx *c, const u64 *in, u64 *out, int size, int nl, size_t count) {

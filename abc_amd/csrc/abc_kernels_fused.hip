@@ -9,6 +9,9 @@
 // Which sequence a call takes -- the split fp64 kernels at N = 2^14, the LDS-resident fp64 or integer kernels, or one of the
 // other translation units' -- is decided in abc_route.hpp and tabulated in DESIGN.md section 3b; the launch functions at the end
 // of this file switch over that route.  tests/test_gpu_paths.py holds every route bit-identical to the oracle.
+// The operand transform and the decomposition are templates over the arithmetic policy (IntArith<GUARD> / FpArith, abc_ntt.hpp),
+// whose element operations spell the loads and stores around a transform; the integer mod-down is abc_ntt.hpp's "divide and
+// round" step B.  The other mod-down kernels keep one kernel per arithmetic ("Where the twins stay", above K2c).
 // Algorithmic HBM bytes per multiply: 8N(6L + 2L(L+1)); measured: DESIGN.md section 4.
 #include <type_traits>
 
@@ -49,21 +52,26 @@ __global__ __launch_bounds__((1 << LB) / 16) void k_fused_tensor_intt(DevCtx c, 
       [&](int, int i, u64 v) { dcoef[i] = scale_inv_n(v, m); }, t, m, 0, 0);
 }
 
+// The next two kernels are written once over the arithmetic policy A (abc_ntt.hpp): IntArith<GUARD>, or FpArith when every key
+// prime is below 2^50.  Same buffers, same u64 memory format, bit-identical results; only the arithmetic between the HBM load
+// and the HBM store differs, and that is spelt by the policy's element operations.
+//
 // inverse transform of the key-switch operand when it arrives in NTT form (CKKS rotations):
 // src limb (ct, j) at src + ct*src_stride + j*N  ->  dst[ct][j]
-template <int LB>
+template <int LB, class A>
 __global__ __launch_bounds__((1 << LB) / 16) void k_fused_operand_intt(DevCtx c, const u64 *__restrict__ src, size_t src_stride,
                                                                        u64 *__restrict__ dst, int nl) {
-  __shared__ u64 lds[lds_words(LB)];
+  using E = typename A::E;
+  __shared__ E lds[lds_words(LB)];
   const size_t N = (size_t)1 << LB;
   const int j = blockIdx.x % nl;
   const size_t ct = blockIdx.x / nl;
-  const Mod m = c.mods[j];
-  const NttTable t = ntt_table(c, j);
+  const Mod m = arith_mod<A>(c, j);
+  const typename A::Table t = arith_table<A>(c, j);
   const u64 *__restrict__ s = src + ct * src_stride + (size_t)j * N;
   u64 *__restrict__ d = dst + (size_t)blockIdx.x * N;
-  ntt_inv_block<LB>(
-      lds, [&](int, int i) { return s[i]; }, [&](int, int i, u64 v) { d[i] = scale_inv_n(v, m); }, t, m, 0, 0);
+  ntt_inv_block_a<LB, A>(
+      lds, [&](int, int i) { return A::from_u64(s[i]); }, [&](int, int i, E v) { d[i] = A::canon(A::scale_n(v, m), m); }, t, m, 0, 0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -72,30 +80,31 @@ __global__ __launch_bounds__((1 << LB) / 16) void k_fused_operand_intt(DevCtx c,
 // ---------------------------------------------------------------------------------------------------------------
 // K2a: dec[ct][I][J] = NTT_I( operand_J mod q_I )
 // LAZY (unguarded transforms over primes <= 55 bits): the transform's raw outputs (< 64q) are stored as they are;
-// the inner product accumulates 128-bit products and reduces once, so it needs no canonical operands.
-template <int LB, bool GUARD, bool LAZY>
+// the inner product accumulates 128-bit products and reduces once, so it needs no canonical operands.  fp64 always stores
+// non-negative lazy representatives (A::fwd_out).
+template <int LB, class A, bool LAZY>
 __global__ __launch_bounds__((1 << LB) / 16) void k_fused_ks_decomp_ntt(DevCtx c, const u64 *__restrict__ coef, size_t coef_stride,
                                                                         u64 *__restrict__ dec, int nl, int skip_diagonal) {
-  __shared__ u64 lds[lds_words(LB)];
+  using E = typename A::E;
+  __shared__ E lds[lds_words(LB)];
   const int J = blockIdx.x % nl;
   const int I = (blockIdx.x / nl) % (nl + 1);
   const size_t ct = blockIdx.x / ((size_t)nl * (nl + 1));
   if (skip_diagonal && J == I) return;
   const size_t N = (size_t)1 << LB;
   const int ki = (I == nl) ? c.K - 1 : I;
-  const Mod m = c.mods[ki];
-  const NttTable t = ntt_table(c, ki);
+  const Mod m = arith_mod<A>(c, ki);
+  const typename A::Table t = arith_table<A>(c, ki);
   const u64 *__restrict__ src = coef + ct * coef_stride + (size_t)J * N;
   u64 *__restrict__ dst = dec + ((ct * (nl + 1) + I) * nl + J) * N;
-  // residues are < q_J already; the guarded transform accepts inputs < 4q, the unguarded one < 8q (57q of growth
-  // on top stays below the 64q its consumers assume).  Workgroup-uniform choice between two straight-line bodies,
-  // so the sixteen coefficient loads of a lane are issued back to back in either.
-  const bool need_reduce = GUARD ? (c.mods[J].q > m.q) : ((c.mods[J].q >> 3) >= m.q);
-  auto st = [&](int, int i, u64 v) { dst[i] = LAZY ? v : canon_fwd<GUARD>(v, m); };
-  if (need_reduce)
-    ntt_fwd_block<LB, GUARD>(lds, [&](int, int i) { return reduce64(src[i], m); }, st, t, m, 0, 0);
+  // residues are < q_J already: reduced only where the transform would not accept them (A::fwd_accepts; fp64: never).
+  // Workgroup-uniform choice between two straight-line bodies, so the sixteen coefficient loads of a lane are issued back to
+  // back in either.
+  auto st = [&](int, int i, E v) { dst[i] = A::template fwd_out<LAZY>(v, m); };
+  if (!A::fwd_accepts(c.mods[J].q, m))
+    ntt_fwd_block_a<LB, A>(lds, [&](int, int i) { return A::from_u64(reduce64(src[i], m)); }, st, t, m, 0, 0);
   else
-    ntt_fwd_block<LB, GUARD>(lds, [&](int, int i) { return src[i]; }, st, t, m, 0, 0);
+    ntt_fwd_block_a<LB, A>(lds, [&](int, int i) { return A::from_u64(src[i]); }, st, t, m, 0, 0);
 }
 
 // K2b: acc_comp[k] = sum_J x_J[k] * key[J][comp][I][k]; data primes -> ksacc[ct][comp][I], special -> tsp[ct][comp]
@@ -136,6 +145,10 @@ __global__ __launch_bounds__(256) void k_fused_ks_mac(DevCtx c, const u64 *__res
   }
 }
 
+// Where the twins stay.  K2c (step A of abc_ntt.hpp's "divide and round") and the fp64 and BFV forms of K3 keep one kernel per
+// arithmetic: folded into divround_to_coef / divround_finish or into one template over the policy, some of their instantiations
+// came out with other register counts (profiles/r08_divide_round_ab.log), and this file's rule is that a fold may not do that.
+// The integer K3 and rescale's kernels (abc_kernels_eval.hip) do share the bodies.
 // K2c: special-prime limb back to coefficients, plus q_sp/2 (rounding of the division by q_sp)
 template <int LB>
 __global__ __launch_bounds__((1 << LB) / 16) void k_fused_ks_special_intt(DevCtx c, const u64 *__restrict__ tsp,
@@ -152,11 +165,12 @@ __global__ __launch_bounds__((1 << LB) / 16) void k_fused_ks_special_intt(DevCtx
       0, 0);
 }
 
-// K3, CKKS: out[ct][comp][j] = (ksacc - NTT_j(tlast mod q_j + fix)) * q_sp^-1 (+ addend)
+// K3, CKKS: out[ct][comp][j] = (ksacc - NTT_j(tlast mod q_j + fix)) * q_sp^-1 (+ addend): step B, abc_ntt.hpp's divround_finish
 template <int LB, bool GUARD>
 __global__ __launch_bounds__((1 << LB) / 16) void k_fused_ks_moddown(DevCtx c, const u64 *__restrict__ ksacc,
                                                                      const u64 *__restrict__ tlast, const u64 *__restrict__ addend,
                                                                      size_t addend_stride, int add_c1, u64 *__restrict__ out, int nl) {
+  using A = IntArith<GUARD>;
   __shared__ u64 lds[lds_words(LB)];
   const int j = blockIdx.x % nl;
   const size_t cc = blockIdx.x / nl;  // ct*2 + comp
@@ -165,32 +179,15 @@ __global__ __launch_bounds__((1 << LB) / 16) void k_fused_ks_moddown(DevCtx c, c
   const size_t N = (size_t)1 << LB;
   const Mod m = c.mods[j];
   const NttTable t = ntt_table(c, j);
-  const u64 half = c.mods[c.K - 1].q >> 1;
-  const u64 hm = reduce64(half, m);
-  const u64 fix = hm ? m.q - hm : 0;
-  const u64 inv = c.cst->inv_special[j], inv_s = c.cst->inv_special_s[j];
+  const u64 fix = round_fix(c.mods[c.K - 1].q >> 1, m);
+  const DropInv d = inv_special_at(c, j);
   const u64 *__restrict__ src = tlast + cc * N;
   const u64 *__restrict__ ks = ksacc + (cc * nl + j) * N;
   u64 *__restrict__ o = out + (cc * nl + j) * N;
-  auto ld = [&](int, int i) { return add_mod(reduce64(src[i], m), fix, m.q); };
-  if (addend && (comp == 0 || add_c1)) {  // workgroup-uniform: two straight-line bodies, no per-element select
-    const u64 *__restrict__ cin = addend + ct * addend_stride + ((size_t)comp * nl + j) * N;
-    ntt_fwd_block<LB, GUARD>(
-        lds, ld,
-        [&](int, int i, u64 v) {  // unguarded: v < 64q, so ks + 64q - v stays positive and mul_shoup reduces it
-          const u64 d = GUARD ? sub_mod(ks[i], canon4(v, m), m.q) : ks[i] + (m.two_q << 5) - v;
-          o[i] = add_mod(mul_shoup(d, inv, inv_s, m.q), cin[i], m.q);
-        },
-        t, m, 0, 0);
-  } else {
-    ntt_fwd_block<LB, GUARD>(
-        lds, ld,
-        [&](int, int i, u64 v) {
-          const u64 d = GUARD ? sub_mod(ks[i], canon4(v, m), m.q) : ks[i] + (m.two_q << 5) - v;
-          o[i] = mul_shoup(d, inv, inv_s, m.q);
-        },
-        t, m, 0, 0);
-  }
+  if (addend && (comp == 0 || add_c1))  // workgroup-uniform: two straight-line bodies, no per-element select
+    divround_finish<LB, A, false, true>(lds, m, t, fix, d, src, ks, addend + ct * addend_stride + ((size_t)comp * nl + j) * N, o);
+  else
+    divround_finish<LB, A, false, false>(lds, m, t, fix, d, src, ks, nullptr, o);
 }
 
 // K3, BFV: out[ct][comp][j] = (INTT_j(ksacc) - (tlast mod q_j + fix)) * q_sp^-1 (+ addend), coefficient form
@@ -208,8 +205,7 @@ __global__ __launch_bounds__((1 << LB) / 16) void k_fused_ks_moddown_bfv(DevCtx 
   const Mod m = c.mods[j];
   const NttTable t = ntt_table(c, j);
   const u64 half = c.mods[c.K - 1].q >> 1;
-  const u64 hm = reduce64(half, m);
-  const u64 fix = hm ? m.q - hm : 0;
+  const u64 fix = round_fix(half, m);
   const u64 inv = c.cst->inv_special[j], inv_s = c.cst->inv_special_s[j];
   const u64 *__restrict__ src = tlast + cc * N;
   const u64 *__restrict__ ks = ksacc + (cc * nl + j) * N;
@@ -236,9 +232,8 @@ __global__ __launch_bounds__((1 << LB) / 16) void k_fused_ks_moddown_bfv(DevCtx 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// fp64 twins of the transform kernels above, taken when every key prime is below 2^50 (abc_ntt.hpp, "fp64 residue
-// arithmetic").  Same buffers, same u64 memory format, bit-identical results; only the arithmetic between the HBM
-// load and the HBM store differs.
+// fp64-only kernels (every key prime below 2^50: abc_ntt.hpp, "fp64 residue arithmetic"): the fused multiply front end
+// and the split sequences
 // ---------------------------------------------------------------------------------------------------------------
 // four consecutive words as two adjacent 16-byte stores
 __device__ __forceinline__ void store_run4(u64 *p, const u64 (&v)[4]) {
@@ -287,45 +282,7 @@ struct TensorFront {
   }
 };
 
-template <int LB>
-__global__ __launch_bounds__((1 << LB) / 16) void k_fused_operand_intt_fp(DevCtx c, const u64 *__restrict__ src, size_t src_stride,
-                                                                          u64 *__restrict__ dst, int nl) {
-  __shared__ double lds[lds_words(LB)];
-  const size_t N = (size_t)1 << LB;
-  const int j = blockIdx.x % nl;
-  const size_t ct = blockIdx.x / nl;
-  const Mod m = mod_at(c, j);
-  const FpTable t = fp_table(c, j);
-  const u64 *__restrict__ s = src + ct * src_stride + (size_t)j * N;
-  u64 *__restrict__ d = dst + (size_t)blockIdx.x * N;
-  ntt_inv_block_a<LB, FpArith>(
-      lds, [&](int, int i) { return fp_from_u64(s[i]); },
-      [&](int, int i, double v) { d[i] = fp_to_canon(fp_mul_lazy(v, m.inv_n_c, m.inv_n_cq, m.qd), m.qd, m.qinv); }, t, m, 0, 0);
-}
-
-// K2a.  No reduction of the operand limb modulo the target prime is needed at all: a forward transform tolerates
-// inputs up to 2^50 for targets below 2^49 (growth (1 + 2^-5)^14), and the 49/50-bit targets, which re-centre at
-// every pass, accept the at most 2q such an operand amounts to.  Outputs are stored as non-negative lazy
-// representatives in [q/2, 3q/2] (the inner product reduces anyway).
-template <int LB>
-__global__ __launch_bounds__((1 << LB) / 16) void k_fused_ks_decomp_ntt_fp(DevCtx c, const u64 *__restrict__ coef, size_t coef_stride,
-                                                                           u64 *__restrict__ dec, int nl, int skip_diagonal) {
-  __shared__ double lds[lds_words(LB)];
-  const int J = blockIdx.x % nl;
-  const int I = (blockIdx.x / nl) % (nl + 1);
-  const size_t ct = blockIdx.x / ((size_t)nl * (nl + 1));
-  if (skip_diagonal && J == I) return;
-  const size_t N = (size_t)1 << LB;
-  const int ki = (I == nl) ? c.K - 1 : I;
-  const Mod m = mod_at(c, ki);
-  const FpTable t = fp_table(c, ki);
-  const u64 *__restrict__ src = coef + ct * coef_stride + (size_t)J * N;
-  u64 *__restrict__ dst = dec + ((ct * (nl + 1) + I) * nl + J) * N;
-  ntt_fwd_block_a<LB, FpArith>(
-      lds, [&](int, int i) { return fp_from_u64(src[i]); }, [&](int, int i, double v) { dst[i] = fp_to_lazy(v, m.qd, m.qinv); }, t,
-      m, 0, 0);
-}
-
+// fp64 twins of K2c and K3 (see "Where the twins stay" above K2c)
 template <int LB>
 __global__ __launch_bounds__((1 << LB) / 16) void k_fused_ks_special_intt_fp(DevCtx c, const u64 *__restrict__ tsp,
                                                                              u64 *__restrict__ tlast) {
@@ -345,14 +302,14 @@ __global__ __launch_bounds__((1 << LB) / 16) void k_fused_ks_special_intt_fp(Dev
 // K3, CKKS.  The special-prime polynomial (< q_sp <= 2^50) plus the rounding fix enters the transform unreduced
 // (see K2a); the subtraction, the scaling by q_sp^-1 and the addend stay in doubles until the single
 // canonicalisation of the store.
-template <int LB, bool GAL>
+template <int LB>
 __global__ __launch_bounds__((1 << LB) / 16) void k_fused_ks_moddown_fp(DevCtx c, const u64 *__restrict__ ksacc,
                                                                         const u64 *__restrict__ tlast, const u64 *__restrict__ addend,
                                                                         size_t addend_stride, int add_c1, u64 *__restrict__ out, int nl,
-                                                                        int ncc, u32 gelt) {
+                                                                        int ncc) {
   __shared__ double lds[lds_words(LB)];
-  // The nl workgroups that read the same special-prime polynomial (ct, comp) are 8 apart in blockIdx: workgroups go
-  // round-robin over the 8 XCDs, so they share one L2 and the polynomial is fetched from HBM once, not nl times.
+  // The nl workgroups that read the same special-prime polynomial (ct, comp) are 8 apart in blockIdx: abc_context.hpp's xcd_slot,
+  // spelt out here -- through the helper this kernel (alone of its callers) compiles to other register counts.
   const unsigned per = 8u * (unsigned)nl;
   const unsigned grp = blockIdx.x / per, rem = blockIdx.x % per;
   const unsigned left = (unsigned)ncc - grp * 8u, gsz = left < 8u ? left : 8u;  // the last group may be ragged
@@ -364,8 +321,7 @@ __global__ __launch_bounds__((1 << LB) / 16) void k_fused_ks_moddown_fp(DevCtx c
   const Mod m = mod_at(c, j);
   const FpTable t = fp_table(c, j);
   const u64 half = c.mods[c.K - 1].q >> 1;
-  const u64 hm = reduce64(half, m);
-  const double fix = hm ? (double)(m.q - hm) : 0.0;
+  const double fix = round_fix<double>(half, m);
   const double inv = c.cst->inv_special_c[j], inv_q = c.cst->inv_special_cq[j];
   const u64 *__restrict__ src = tlast + cc * N;
   const u64 *__restrict__ ks = ksacc + (cc * nl + j) * N;
@@ -377,7 +333,7 @@ __global__ __launch_bounds__((1 << LB) / 16) void k_fused_ks_moddown_fp(DevCtx c
         lds, ld,
         [&](int, int i, double v) {
           const double d = fp_from_u64(ks[i]) - v;
-          o[i] = fp_to_canon(fp_mul_lazy(d, inv, inv_q, m.qd) + fp_from_u64(cin[galois_ntt_src<GAL>((u32)i, gelt, LB)]), m.qd, m.qinv);
+          o[i] = fp_to_canon(fp_mul_lazy(d, inv, inv_q, m.qd) + fp_from_u64(cin[(u32)i]), m.qd, m.qinv);
         },
         t, m, 0, 0);
   } else {
@@ -406,8 +362,7 @@ __global__ __launch_bounds__((1 << LB) / 16) void k_fused_ks_moddown_bfv_fp(DevC
   const Mod m = mod_at(c, j);
   const FpTable t = fp_table(c, j);
   const u64 half = c.mods[c.K - 1].q >> 1;
-  const u64 hm = reduce64(half, m);
-  const double fix = hm ? (double)(m.q - hm) : 0.0;
+  const double fix = round_fix<double>(half, m);
   const double inv = c.cst->inv_special_c[j], inv_q = c.cst->inv_special_cq[j];
   const u64 *__restrict__ src = tlast + cc * N;
   const u64 *__restrict__ ks = ksacc + (cc * nl + j) * N;
@@ -745,8 +700,7 @@ __global__ __launch_bounds__(256) void k_split3_pass_fp(DevCtx c, const double *
     const Mod m = mod_at(c, j);
     const FpTable t = fp_table(c, j);
     const FpK kk = FpArith::consts(m);
-    const u64 hm = reduce64(half, m);
-    const double fix = hm ? (double)(m.q - hm) : 0.0;
+    const double fix = round_fix<double>(half, m);
     double y[16];
 #pragma unroll
     for (int k = 0; k < 16; k++) y[k] = x[k] + fix;
@@ -1162,45 +1116,33 @@ static int keyswitch_stage(abc_hip_ctx *c, hipStream_t st, const FusedScratch &s
   const size_t N = (size_t)1 << LB;
   const dim3 block((1 << LB) / 16);
   const bool ckks = (c->scheme == 2);
-  const bool guard = k.guard, lazy = k.lazy;
   const unsigned g2a = (unsigned)(cc * (nl + 1) * nl);
   const unsigned g3 = (unsigned)(cc * 2 * nl);
-  if (fp) {
+  // A: the policy of the forward transforms (a type tag); K2c and K3 are still one kernel per arithmetic
+  auto run = [&](auto arith, auto lazy) {
+    using A = decltype(arith);
+    constexpr bool FP = std::is_same_v<A, FpArith>;
     if (!dec_ready)
-      hipLaunchKernelGGL(k_fused_ks_decomp_ntt_fp<LB>, dim3(g2a), block, 0, st, c->dc, coef, coef_stride, s.dec, nl, ckks ? 1 : 0);
+      hipLaunchKernelGGL((k_fused_ks_decomp_ntt<LB, A, decltype(lazy)::value>), dim3(g2a), block, 0, st, c->dc, coef, coef_stride, s.dec,
+                         nl, ckks ? 1 : 0);
     hipLaunchKernelGGL(k_fused_ks_mac, dim3(grid_for(cc * (nl + 1) * (N / 2), 256)), dim3(256), 0, st, c->dc, s.dec,
                        ckks ? ntt : (const u64 *)nullptr, ntt_stride, key, s.ksacc, s.tsp, nl, cc);
-    hipLaunchKernelGGL(k_fused_ks_special_intt_fp<LB>, dim3((unsigned)(cc * 2)), block, 0, st, c->dc, s.tsp, s.tlast);
-    if (ckks)
-      hipLaunchKernelGGL((k_fused_ks_moddown_fp<LB, false>), dim3(g3), block, 0, st, c->dc, s.ksacc, s.tlast, addend, addend_stride,
-                         add_c1 ? 1 : 0, out, nl, (int)(cc * 2), 0u);
+    hipLaunchKernelGGL((FP ? k_fused_ks_special_intt_fp<LB> : k_fused_ks_special_intt<LB>), dim3((unsigned)(cc * 2)), block, 0, st, c->dc,
+                       s.tsp, s.tlast);
+    if (!ckks)
+      hipLaunchKernelGGL((FP ? k_fused_ks_moddown_bfv_fp<LB> : k_fused_ks_moddown_bfv<LB>), dim3(g3), block, 0, st, c->dc, s.ksacc, s.tlast,
+                         addend, addend_stride, add_c1 ? 1 : 0, out, nl);
+    else if constexpr (FP)
+      hipLaunchKernelGGL(k_fused_ks_moddown_fp<LB>, dim3(g3), block, 0, st, c->dc, s.ksacc, s.tlast, addend, addend_stride, add_c1 ? 1 : 0,
+                         out, nl, (int)(cc * 2));
     else
-      hipLaunchKernelGGL(k_fused_ks_moddown_bfv_fp<LB>, dim3(g3), block, 0, st, c->dc, s.ksacc, s.tlast, addend, addend_stride,
-                         add_c1 ? 1 : 0, out, nl);
-    ABC_HIP_CHECK(hipGetLastError());
-    return 0;
-  }
-  if (guard)
-    hipLaunchKernelGGL((k_fused_ks_decomp_ntt<LB, true, false>), dim3(g2a), block, 0, st, c->dc, coef, coef_stride, s.dec, nl,
-                       ckks ? 1 : 0);
-  else if (lazy)
-    hipLaunchKernelGGL((k_fused_ks_decomp_ntt<LB, false, true>), dim3(g2a), block, 0, st, c->dc, coef, coef_stride, s.dec, nl,
-                       ckks ? 1 : 0);
-  else
-    hipLaunchKernelGGL((k_fused_ks_decomp_ntt<LB, false, false>), dim3(g2a), block, 0, st, c->dc, coef, coef_stride, s.dec, nl,
-                       ckks ? 1 : 0);
-  hipLaunchKernelGGL(k_fused_ks_mac, dim3(grid_for(cc * (nl + 1) * (N / 2), 256)), dim3(256), 0, st, c->dc, s.dec,
-                     ckks ? ntt : (const u64 *)nullptr, ntt_stride, key, s.ksacc, s.tsp, nl, cc);
-  hipLaunchKernelGGL(k_fused_ks_special_intt<LB>, dim3((unsigned)(cc * 2)), block, 0, st, c->dc, s.tsp, s.tlast);
-  if (!ckks)
-    hipLaunchKernelGGL(k_fused_ks_moddown_bfv<LB>, dim3(g3), block, 0, st, c->dc, s.ksacc, s.tlast, addend, addend_stride,
-                       add_c1 ? 1 : 0, out, nl);
-  else if (guard)
-    hipLaunchKernelGGL((k_fused_ks_moddown<LB, true>), dim3(g3), block, 0, st, c->dc, s.ksacc, s.tlast, addend, addend_stride,
-                       add_c1 ? 1 : 0, out, nl);
-  else
-    hipLaunchKernelGGL((k_fused_ks_moddown<LB, false>), dim3(g3), block, 0, st, c->dc, s.ksacc, s.tlast, addend, addend_stride,
-                       add_c1 ? 1 : 0, out, nl);
+      hipLaunchKernelGGL((k_fused_ks_moddown<LB, std::is_same_v<A, IntArith<true>>>), dim3(g3), block, 0, st, c->dc, s.ksacc, s.tlast, addend,
+                         addend_stride, add_c1 ? 1 : 0, out, nl);
+  };
+  if (fp) run(FpArith{}, std::true_type{});
+  else if (k.guard) run(IntArith<true>{}, std::false_type{});
+  else if (k.lazy) run(IntArith<false>{}, std::true_type{});
+  else run(IntArith<false>{}, std::false_type{});
   ABC_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -1346,12 +1288,8 @@ static int run_keyswitch(abc_hip_ctx *c, Seq seq, const u64 *target, size_t targ
     const u64 *coef = tg;
     size_t coef_stride = target_stride;
     if (ckks) {  // operand arrives in NTT form: coefficient form via one in-LDS inverse transform per limb
-      if (fp)
-        hipLaunchKernelGGL(k_fused_operand_intt_fp<LB>, dim3((unsigned)(cc * nl)), dim3((1 << LB) / 16), 0, st, c->dc, tg,
-                           target_stride, s.coef, nl);
-      else
-        hipLaunchKernelGGL(k_fused_operand_intt<LB>, dim3((unsigned)(cc * nl)), dim3((1 << LB) / 16), 0, st, c->dc, tg, target_stride,
-                           s.coef, nl);
+      hipLaunchKernelGGL((fp ? k_fused_operand_intt<LB, FpArith> : k_fused_operand_intt<LB, IntArith<true>>), dim3((unsigned)(cc * nl)),
+                         dim3((1 << LB) / 16), 0, st, c->dc, tg, target_stride, s.coef, nl);
       coef = s.coef;
       coef_stride = (size_t)nl * N;
     }

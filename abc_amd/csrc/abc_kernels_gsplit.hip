@@ -423,8 +423,7 @@ __global__ __launch_bounds__(256) void k_gsplit_pass(DevCtx c, const double *__r
       const Mod m = mod_at(c, j);
       const FpTable t = fp_table(c, j);
       const FpK kk = FpArith::consts(m);
-      const u64 hm = reduce64(halfq, m);
-      const double fix = hm ? (double)(m.q - hm) : 0.0;
+      const double fix = round_fix<double>(halfq, m);
       double *__restrict__ dst = tpart + (cc * nl + j) * PS + (size_t)(pg * X::P);
       X::forward(lds, tid, x, fix, t, kk, [&](int k, int p, double v) { dst[((size_t)k << 10) + p] = v; });
     }
@@ -454,8 +453,7 @@ __global__ __launch_bounds__(256) void k_gsplit_pass(DevCtx c, const double *__r
     const Mod m = mod_at(c, j);
     const FpTable t = fp_table(c, j);
     const FpK kk = FpArith::consts(m);
-    const u64 hm = reduce64(half, m);
-    const double fix = hm ? (double)(m.q - hm) : 0.0;
+    const double fix = round_fix<double>(half, m);
     double y[NB];
 #pragma unroll
     for (int k = 0; k < NB; k++) y[k] = x[k] + fix;
@@ -835,7 +833,7 @@ int bsplit_back13(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const doubl
 // B3 k_bsplit_tcoef   : special limb back to canonical coefficients (+ q_sp/2) -- once per (ct, comp), where the N = 2^14 finish
 //                     kernel recomputes it per data prime from registers (16 values; here it would be 64)
 // B4 k_bsplit_finish_big: inverse cross pass of data limb I, N^-1, subtract, q_sp^-1, addend -> coefficient form
-// Replaces, for these rings, k_ks_expand_strided_fp + block transforms + k_ks_inner + transforms + k_ks_tmod + k_ks_finish.
+// Replaces, for these rings, k_ks_expand_strided_fp + block transforms + k_ks_inner + transforms + k_divround_tmod + k_divround_finish.
 template <int LOGN>
 __global__ __launch_bounds__(256) void k_bsplit_pass0(DevCtx c, const u64 *__restrict__ src, size_t src_stride, double *__restrict__ part,
                                                       int nl, u32 ginv = 0 /* BFV rotation: elt^-1 mod 2N, the permutation folded into the load */) {
@@ -916,8 +914,7 @@ __global__ __launch_bounds__(256) void k_bsplit_finish_big(DevCtx c, const doubl
     for (int k = 0; k < NB; k++) x[k] = fp_centre(src[(k << 10) + p], kk.q, kk.qinv);
     inv_cross<LOGNB>(x, tb, kk);
   }
-  const u64 hm = reduce64(c.mods[c.K - 1].q >> 1, m);
-  const double fix = hm ? (double)(m.q - hm) : 0.0;
+  const double fix = round_fix<double>(c.mods[c.K - 1].q >> 1, m);
   const ABC_CONST_AS DevConst *cst = (const ABC_CONST_AS DevConst *)c.cst;
   const double inv = cst->inv_special_c[I], inv_q = cst->inv_special_cq[I];
   const double *__restrict__ tsrc = tco + cc * PS;
@@ -1058,8 +1055,7 @@ __global__ __launch_bounds__(256) void k_bsplit_finish_lds(DevCtx c, const doubl
     }
   }
   __syncthreads();
-  const u64 hm = reduce64(c.mods[c.K - 1].q >> 1, m);
-  const double fix = hm ? (double)(m.q - hm) : 0.0;
+  const double fix = round_fix<double>(c.mods[c.K - 1].q >> 1, m);
   const ABC_CONST_AS DevConst *cst = (const ABC_CONST_AS DevConst *)c.cst;
   const double inv = cst->inv_special_c[I], inv_q = cst->inv_special_cq[I];
   const double *__restrict__ tsrc = tco + cc * PS + (size_t)(pg * P);

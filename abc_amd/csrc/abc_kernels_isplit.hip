@@ -292,8 +292,7 @@ __global__ __launch_bounds__(256) void k_isplit_pass(DevCtx c, const u64 *__rest
   using A = IntArith<GUARD>;
   for (int j = 0; j < nl; j++) {
     const Mod m = c.mods[j];
-    const u64 hm = reduce64(ms.q >> 1, m);
-    const u64 fix = hm ? m.q - hm : 0;
+    const u64 fix = round_fix(ms.q >> 1, m);
     u64 *__restrict__ dst = tpart + (cc * nl + j) * PS;
     if ((fpmask >> j) & 1u) {
       const Mod mf = mod_at(c, j);

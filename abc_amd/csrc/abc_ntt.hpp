@@ -16,6 +16,8 @@
 // strided global pass in abc_ntt.hip.
 #pragma once
 
+#include <type_traits>
+
 #include "abc_modarith.hpp"
 
 namespace abc {
@@ -166,6 +168,38 @@ template <> struct Sched<14> { static constexpr int R0 = 4, R1 = 4, R2 = 4, R3 =
 template <int LB> struct TailSched;
 template <> struct TailSched<10> { static constexpr int R0 = 3, R1 = 4, R2 = 3, R3 = 0; };
 
+// lazily reduced [0,4q) -> [0,q)
+__device__ __forceinline__ u64 canon4(u64 v, const Mod &m) { return csub(csub(v, m.two_q), m.q); }
+// output of an unguarded forward transform, [0,64q) -> [0,q)
+__device__ __forceinline__ u64 canon32(u64 v, const Mod &m) {
+  v = csub(v, m.two_q << 4);
+  v = csub(v, m.two_q << 3);
+  v = csub(v, m.two_q << 2);
+  v = csub(v, m.two_q << 1);
+  return canon4(v, m);
+}
+template <bool GUARD>
+__device__ __forceinline__ u64 canon_fwd(u64 v, const Mod &m) { return GUARD ? canon4(v, m) : canon32(v, m); }
+// a modulus may take the unguarded butterflies when 64 q <= 2^64
+__host__ __device__ __forceinline__ bool unguarded_ok(u32 bits) { return bits <= 57; }
+// scale by N^-1 and canonicalise (input [0,2q) or any 64-bit value)
+__device__ __forceinline__ u64 scale_inv_n(u64 v, const Mod &m) { return mul_shoup(v, m.inv_n, m.inv_n_s, m.q); }
+
+// ---- divide by a dropped prime p, with rounding (key-switch mod-down, rescale) -------------------------------------------------
+// t = (x_p + floor(p/2)) mod p in coefficient form; per remaining prime q_j:  out_j = (x_j - (t mod q_j + fix)) p^-1  (mod q_j).
+// fix(p, q_j) = -floor(p/2) mod q_j takes the rounding offset out again; `half` = floor(p/2); E = u64, or double for fp64 operands
+template <class E = u64>
+__device__ __forceinline__ E round_fix(u64 half, const Mod &m) {
+  const u64 hm = reduce64(half, m);
+  return hm ? (E)(m.q - hm) : (E)0;
+}
+// p^-1 mod q_j as the integer kernels want it ({value, Shoup quotient}) and as the fp64 ones do ({centred value, that / q_j}):
+// DevConst's inv_special*[j] (p = the special prime) or inv_qlast*[nl - 1][j] (p = limb nl - 1): abc_context.hpp
+struct DropInv {
+  u64 w, ws;
+  double c, cq;
+};
+
 // ---- arithmetic policies of the register passes ---------------------------------------------------------
 // Integer (Harvey lazy) butterflies.
 // GUARD = false: no per-stage correction of X and the cheaper quotient estimate (mul_shoup_lazy4, product in
@@ -203,6 +237,25 @@ struct IntArith {
   }
   template <int PASS> __device__ __forceinline__ static void fwd_begin(E (&)[16], const K &) {}
   template <int PASS> __device__ __forceinline__ static void inv_begin(E (&)[16], const K &) {}
+  // ---- element operations of the functors around a transform (the same names on every policy) ----
+  __device__ __forceinline__ static E from_u64(u64 v) { return v; }  // canonical residue -> E
+  // may a canonical residue of a prime q_from enter the forward transform modulo m as it is?  (guarded: inputs < 4q; unguarded: < 8q,
+  // 57q of growth on top stays below the 64q its consumers assume)
+  __device__ __forceinline__ static bool fwd_accepts(u64 q_from, const Mod &m) { return GUARD ? q_from <= m.q : (q_from >> 3) < m.q; }
+  // forward-transform output -> memory: canonical, or LAZY as it is (< 64q: consumers that reduce anyway)
+  template <bool LAZY> __device__ __forceinline__ static u64 fwd_out(E v, const Mod &m) { return LAZY ? v : canon_fwd<GUARD>(v, m); }
+  // inverse-transform output times N^-1; for this policy the result is canonical already
+  __device__ __forceinline__ static E scale_n(E v, const Mod &m) { return scale_inv_n(v, m); }
+  // r (what scale_n / diff_mul_fwd return) [+ a canonical c] -> canonical u64
+  __device__ __forceinline__ static u64 canon(E r, const Mod &) { return r; }
+  __device__ __forceinline__ static u64 canon_add(E r, E c, const Mod &m) { return add_mod(r, c, m.q); }
+  // residue t of the dropped prime, fix = round_fix<E> -> t mod q + fix, the operand of step B
+  __device__ __forceinline__ static E reduce_fix(u64 t, E fix, const Mod &m) { return add_mod(reduce64(t, m), fix, m.q); }
+  // (x - y) p^-1 for canonical x and a forward-transform output y (unguarded: y < 64q, so x + 64q - y stays positive and mul_shoup
+  // reduces it)
+  __device__ __forceinline__ static E diff_mul_fwd(E x, E y, const DropInv &d, const Mod &m) {
+    return mul_shoup(GUARD ? sub_mod(x, canon4(y, m), m.q) : x + (m.two_q << 5) - y, d.w, d.ws, m.q);
+  }
 };
 
 // fp64 butterflies.  Forward: X = a + v, Y = a - v.  Inverse: X = a + b (doubles every stage: 16x per pass, so
@@ -238,6 +291,19 @@ struct FpArith {
   template <int PASS> __device__ __forceinline__ static void inv_begin(E (&x)[16], const K &k) {
     if (PASS > 0 || k.red) centre16(x, k);
   }
+  // ---- element operations (see IntArith): values stay lazy doubles until the single canonicalisation of canon / canon_add ----
+  __device__ __forceinline__ static E from_u64(u64 v) { return fp_from_u64(v); }
+  // no reduction at all: a forward transform tolerates inputs up to 2^50 for targets below 2^49 (growth (1 + 2^-5)^14), and the
+  // 49/50-bit targets, which re-centre at every pass, accept the at most 2q such an operand amounts to
+  __device__ __forceinline__ static bool fwd_accepts(u64, const Mod &) { return true; }
+  // always a non-negative lazy representative in [q/2, 3q/2]
+  template <bool LAZY> __device__ __forceinline__ static u64 fwd_out(E v, const Mod &m) { return fp_to_lazy(v, m.qd, m.qinv); }
+  __device__ __forceinline__ static E scale_n(E v, const Mod &m) { return fp_mul_lazy(v, m.inv_n_c, m.inv_n_cq, m.qd); }
+  __device__ __forceinline__ static u64 canon(E r, const Mod &m) { return fp_to_canon(r, m.qd, m.qinv); }
+  __device__ __forceinline__ static u64 canon_add(E r, E c, const Mod &m) { return fp_to_canon(r + c, m.qd, m.qinv); }
+  // dropped prime below 2^50 only: t + fix enters the transform unreduced (fwd_accepts)
+  __device__ __forceinline__ static E reduce_fix(u64 t, E fix, const Mod &m) { return fp_from_u64(t) + fix; }
+  __device__ __forceinline__ static E diff_mul_fwd(E x, E y, const DropInv &d, const Mod &m) { return fp_mul_lazy(x - y, d.c, d.cq, m.qd); }
 };
 
 // Forward 1024-point BLOCK TAILS that start from a CENTRED input, |x| <= q/2: the per-stage bound Y -> Y (1 + 1.5 q 2^-53) + q/2
@@ -697,21 +763,39 @@ __device__ __forceinline__ void ntt_inv_block(u64 *lds, Load load, Store store, 
   ntt_inv_block_a<LB, IntArith<true>>(lds, load, store, t, m, S0, b);
 }
 
-// lazily reduced [0,4q) -> [0,q)
-__device__ __forceinline__ u64 canon4(u64 v, const Mod &m) { return csub(csub(v, m.two_q), m.q); }
-// output of an unguarded forward transform, [0,64q) -> [0,q)
-__device__ __forceinline__ u64 canon32(u64 v, const Mod &m) {
-  v = csub(v, m.two_q << 4);
-  v = csub(v, m.two_q << 3);
-  v = csub(v, m.two_q << 2);
-  v = csub(v, m.two_q << 1);
-  return canon4(v, m);
+// ---- divide and round, LDS-resident (one workgroup per limb): the two steps of "divide by a dropped prime" above -------------
+// Step A: the dropped limb (NTT form at src; m, t: the dropped prime) -> coefficients, N^-1, + floor(p/2) -> dst, canonical
+template <int LB, class A>
+__device__ __forceinline__ void divround_to_coef(typename A::E *lds, const Mod m, const typename A::Table t,
+                                                 const u64 *__restrict__ src, u64 *__restrict__ dst) {
+  using E = typename A::E;
+  const E half = (E)(m.q >> 1);
+  ntt_inv_block_a<LB, A>(
+      lds, [&](int, int i) { return A::from_u64(src[i]); }, [&](int, int i, E v) { dst[i] = A::canon_add(A::scale_n(v, m), half, m); }, t, m,
+      0, 0);
 }
-template <bool GUARD>
-__device__ __forceinline__ u64 canon_fwd(u64 v, const Mod &m) { return GUARD ? canon4(v, m) : canon32(v, m); }
-// a modulus may take the unguarded butterflies when 64 q <= 2^64
-__host__ __device__ __forceinline__ bool unguarded_ok(u32 bits) { return bits <= 57; }
-// scale by N^-1 and canonicalise (input [0,2q) or any 64-bit value)
-__device__ __forceinline__ u64 scale_inv_n(u64 v, const Mod &m) { return mul_shoup(v, m.inv_n, m.inv_n_s, m.q); }
+// Step B for one remaining prime (m, t):  o = (x - NTT(tl mod q + fix)) p^-1 (+ cin), with tl = step A's output, d = p^-1 mod q,
+// cin = the addend's limb (ADD; callers choose by a workgroup-uniform branch: two straight-line bodies, no per-element select).
+// REDUCE: t is reduced modulo q as an integer whatever the policy, and fix = round_fix<u64> -- FpArith where the dropped prime
+// may be wider than 2^52 (canonical, + fix, below 2q).  Otherwise fix = round_fix<A::E> and the policy's own load.
+template <int LB, class A, bool REDUCE, bool ADD>
+__device__ __forceinline__ void divround_finish(typename A::E *lds, const Mod m, const typename A::Table t,
+                                                const std::conditional_t<REDUCE, u64, typename A::E> fix, const DropInv d,
+                                                const u64 *__restrict__ tl, const u64 *__restrict__ x, const u64 *__restrict__ cin,
+                                                u64 *__restrict__ o) {
+  using E = typename A::E;
+  ntt_fwd_block_a<LB, A>(
+      lds,
+      [&](int, int i) {
+        if constexpr (REDUCE) return A::from_u64(IntArith<true>::reduce_fix(tl[i], fix, m));
+        else return A::reduce_fix(tl[i], fix, m);
+      },
+      [&](int, int i, E v) {
+        const E r = A::diff_mul_fwd(A::from_u64(x[i]), v, d, m);
+        if constexpr (ADD) o[i] = A::canon_add(r, A::from_u64(cin[i]), m);
+        else o[i] = A::canon(r, m);
+      },
+      t, m, 0, 0);
+}
 
 }  // namespace abc

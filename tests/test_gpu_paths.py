@@ -309,9 +309,9 @@ def test_fp64_and_integer_paths_agree_on_random_residues(oracle14, capi, monkeyp
 # with and without the lazy 128-bit inner product (<= 55 bits)
 # ---------------------------------------------------------------------------------------------------------------------
 WIDE_CHAINS = {
-    "60_40_40_60": [60, 40, 40, 60],      # guarded butterflies (k_fused_ks_decomp_ntt<LB,true,false>, moddown<LB,true>)
-    "57_45_45_57": [57, 45, 45, 57],      # unguarded, non-lazy inner product (<LB,false,false>, moddown<LB,false>)
-    "55_52_51_55": [55, 52, 51, 55],      # unguarded + lazy (<LB,false,true>) with every prime above the fp64 limit
+    "60_40_40_60": [60, 40, 40, 60],      # guarded butterflies (k_fused_ks_decomp_ntt<LB,IntArith<true>,false>, moddown<LB,true>)
+    "57_45_45_57": [57, 45, 45, 57],      # unguarded, non-lazy inner product (<LB,IntArith<false>,false>, moddown<LB,false>)
+    "55_52_51_55": [55, 52, 51, 55],      # unguarded + lazy (<LB,IntArith<false>,true>) with every prime above the fp64 limit
     "60_50_40_50": [60, 50, 40, 50],      # mixed: fp64-capable data primes next to a 60-bit one (those limbs take the fp64 kernels)
     "60_40_40_40_60": [60, 40, 40, 40, 60],  # bench.py's value_60bit_primes chain: integer ends, fp64 middle
     "50_40_58_40_50": [50, 40, 58, 40, 50],  # an integer prime between fp64 ones (the main kernels' prime maps are not contiguous)
