@@ -36,6 +36,7 @@ SYMBOLS = [
     "abc_hip_graph_begin", "abc_hip_graph_end", "abc_hip_graph_launch", "abc_hip_graph_destroy",
     "abc_hip_encrypt_keyed", "abc_hip_keygen_keyed", "abc_hip_keyed_small", "abc_hip_keyed_uniform", "abc_hip_keyed_small_host",
     "abc_hip_apply_galois_hoisted", "abc_hip_rotate_hoisted",
+    "abc_hip_rotate_add", "abc_hip_apply_galois_add", "abc_hip_rotate_sum",
 ]
 
 
@@ -64,6 +65,9 @@ def lib():
         L.abc_hip_route.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_char_p, C.c_size_t]
         L.abc_hip_apply_galois_hoisted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.c_int, C.c_size_t]
         L.abc_hip_rotate_hoisted.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_size_t]
+        L.abc_hip_rotate_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t]
+        L.abc_hip_apply_galois_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_size_t]
+        L.abc_hip_rotate_sum.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_size_t]
         L.abc_hip_encrypt_keyed.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_size_t]
         L.abc_hip_keygen_keyed.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
         L.abc_hip_keyed_small.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_size_t]
@@ -193,7 +197,7 @@ class Context:
     def reload_env(self):
         _chk(lib().abc_hip_ctx_reload_env(self.h))
 
-    ROUTE_OPS = {"mul_relin": 0, "keyswitch": 1, "relinearize": 1, "rotate": 2, "rescale": 3, "multiply": 4}
+    ROUTE_OPS = {"mul_relin": 0, "keyswitch": 1, "relinearize": 1, "rotate": 2, "rescale": 3, "multiply": 4, "rotate_add": 5}
 
     def route(self, op, nl, count=1, in_place=False):
         """the kernel sequence such a call takes, as the string of abc_route.hpp's formatter"""
@@ -354,6 +358,26 @@ class Context:
     def rotate_hoisted(self, ct, steps):
         """the same for rotation steps; step 0 is a copy, a step without a key of its own is an error"""
         return self._hoisted("rotate_hoisted", ct, C.c_int, steps)
+
+    def rotate_add(self, ct, addend, steps):
+        """addend + rotate(ct, steps) as one call (abc_hip_rotate_add): the add is fused into the key switch where route("rotate_add") says so"""
+        a4, b4 = self._batch(ct, 3), self._batch(addend, 3)
+        r = self._run("rotate_add", [a4, b4], a4.shape, a4.shape[2], int(steps), C.c_size_t(a4.shape[0]))
+        return r if np.ndim(ct) == 4 else r[0]
+
+    def apply_galois_add(self, ct, addend, elt):
+        """the same for one Galois element"""
+        a4, b4 = self._batch(ct, 3), self._batch(addend, 3)
+        r = self._run("apply_galois_add", [a4, b4], a4.shape, a4.shape[2], C.c_uint32(elt), C.c_size_t(a4.shape[0]))
+        return r if np.ndim(ct) == 4 else r[0]
+
+    def rotate_sum(self, ct, steps):
+        """the rotate-and-sum tree: acc = ct; acc = acc + rotate(acc, s) for each s in steps, in order"""
+        a4 = self._batch(ct, 3)
+        steps = [int(x) for x in steps]
+        arr = (C.c_int * max(len(steps), 1))(*steps)
+        r = self._run("rotate_sum", [a4], a4.shape, a4.shape[2], arr, len(steps), C.c_size_t(a4.shape[0]))
+        return r if np.ndim(ct) == 4 else r[0]
 
     def _plain_op(self, name, ct, plain):
         a4 = self._batch(ct, 3)

@@ -42,6 +42,7 @@ void read_switches(abc_hip_ctx *c) {
   s.no_lean_front = env_on("ABC_HIP_NO_LEAN_FRONT");
   s.no_tensor_intt = env_on("ABC_HIP_NO_TENSOR_INTT");
   s.no_galois_fusion = env_on("ABC_HIP_NO_GALOIS_FUSION");
+  s.no_rotate_add_fusion = env_on("ABC_HIP_NO_ROTATE_ADD_FUSION");
   s.main_two_per_cu = env_on("ABC_HIP_MAIN_TWO_PER_CU");
   s.host_sampling = env_on("ABC_HIP_HOST_SAMPLING");
   if (const char *e = std::getenv("ABC_HIP_CHUNK")) s.chunk = (size_t)std::atol(e);
@@ -383,32 +384,46 @@ static int keyswitch(abc_hip_ctx *c, const u64 *target, size_t target_stride, co
   return launch_keyswitch(c, route_keyswitch(c->facts, nl), target, target_stride, key, out2, nl, count, addend, addend_stride, add_c1);
 }
 
-static int apply_galois(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, uint32_t elt, size_t count) {
+// one Galois element along route r; acc (RotAddRoute::fused only): a second ciphertext added in the key switch's last kernel
+static int apply_galois_routed(abc_hip_ctx *c, const RotRoute &r, const u64 *in, u64 *out, int nl, uint32_t elt, size_t count,
+                               const u64 *acc = nullptr) {
   auto it = c->d_galois.find(elt);
   if (it == c->d_galois.end()) { set_error("Galois key not present"); return 1; }
   if (!count) return 0;
   const size_t N = (size_t)c->n, pw = (size_t)nl * N;
   const bool ntt_form = (c->scheme == ABC_HIP_SCHEME_CKKS);
   // out = (g(c0) + ks0, ks1) with ks = KeySwitch(g(c1))
-  const RotRoute r = route_rotate(c->facts, nl, in == out);
   if (r.fold)  // the permutation is a gather inside the key-switch kernels
-    return launch_keyswitch(c, r.ks, in + pw, 2 * pw, it->second, out, nl, count, in, 2 * pw, false, elt);
+    return launch_keyswitch(c, r.ks, in + pw, 2 * pw, it->second, out, nl, count, in, 2 * pw, false, elt, acc);
+  if (acc) { set_error("apply_galois: a second addend needs the folded permutation"); return 1; }
   // g(c0), g(c1) live in arena 0 (keyswitch_generic uses c->ws)
   if (ensure_aux(c, 0, count * 2 * pw * 8)) return 1;
   u64 *g = (u64 *)c->aux[0];
   if (launch_galois(c, in, g, nl, count * 2, elt, ntt_form)) return 1;
   return launch_keyswitch(c, r.ks, g + pw, 2 * pw, it->second, out, nl, count, g, 2 * pw, false);
 }
+static int apply_galois(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, uint32_t elt, size_t count) {
+  return apply_galois_routed(c, route_rotate(c->facts, nl, in == out), in, out, nl, elt, count);
+}
 
-static int rotate(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, int steps, size_t count) {
-  const size_t bytes = count * 2 * nl * (size_t)c->n * 8;
-  if (steps == 0) {
-    if (in != out) ABC_HIP_CHECK(hipMemcpyAsync(out, in, bytes, hipMemcpyDeviceToDevice, c->stream));
-    return 0;
-  }
+// out = addend + g(in) (abc_hip_apply_galois_add, and the last hop of rotate_add).  Fused: one more operand of the key switch's
+// last kernel; `out` may be `addend` there, and is never `in`.  Otherwise the rotation lands in arena `tmp_arena` and the add
+// kernel follows -- elementwise, so every aliasing of the three pointers is fine.
+static int apply_galois_add(abc_hip_ctx *c, const u64 *in, const u64 *addend, u64 *out, int nl, uint32_t elt, size_t count, int tmp_arena) {
+  if (!c->d_galois.count(elt)) { set_error("Galois key not present"); return 1; }
+  if (!count) return 0;
+  const RotAddRoute r = route_rotate_add(c->facts, nl, in == out);
+  if (r.fused) return apply_galois_routed(c, r.rot, in, out, nl, elt, count, addend);
+  if (ensure_aux(c, tmp_arena, count * 2 * nl * (size_t)c->n * 8)) return 1;
+  u64 *tmp = (u64 *)c->aux[tmp_arena];
+  if (apply_galois_routed(c, r.rot, in, tmp, nl, elt, count)) return 1;
+  return launch_addsub(c, addend, tmp, out, nl, count * 2, 0);
+}
+
+// the hops of one rotation: the step itself where it has a key, else its non-adjacent form; fails before anything is launched
+static int rotation_terms(abc_hip_ctx *c, int steps, std::vector<int> &terms) {
   const uint32_t elt = elt_from_step(c, steps);
   if (!elt) { set_error("step count too large"); return 1; }
-  std::vector<int> terms;
   if (c->d_galois.count(elt)) {
     terms.push_back(steps);
   } else {
@@ -419,6 +434,17 @@ static int rotate(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, int steps, si
     for (int s : terms)
       if (!c->d_galois.count(elt_from_step(c, s))) { set_error("Galois key not present"); return 1; }
   }
+  return 0;
+}
+
+static int rotate(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, int steps, size_t count) {
+  const size_t bytes = count * 2 * nl * (size_t)c->n * 8;
+  if (steps == 0) {
+    if (in != out) ABC_HIP_CHECK(hipMemcpyAsync(out, in, bytes, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+  }
+  std::vector<int> terms;
+  if (rotation_terms(c, steps, terms)) return 1;
   // apply_galois is out of place: ping-pong through arenas 1 and 2, last hop lands in `out`
   const u64 *cur = in;
   for (size_t i = 0; i < terms.size(); i++) {
@@ -433,6 +459,48 @@ static int rotate(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, int steps, si
     cur = dst;
   }
   if (cur != out) ABC_HIP_CHECK(hipMemcpyAsync(out, cur, bytes, hipMemcpyDeviceToDevice, c->stream));
+  return 0;
+}
+
+// out = addend + rotate(in, steps): every hop but the last as rotate() runs it, the last one with the add (fused where the route
+// allows it; its temporary otherwise is the arena the ping-pong would use next)
+static int rotate_add(abc_hip_ctx *c, const u64 *in, const u64 *addend, u64 *out, int nl, int steps, size_t count) {
+  if (steps == 0) return count ? launch_addsub(c, addend, in, out, nl, count * 2, 0) : 0;
+  std::vector<int> terms;
+  if (rotation_terms(c, steps, terms)) return 1;
+  if (!count) return 0;
+  const size_t bytes = count * 2 * nl * (size_t)c->n * 8;
+  const u64 *cur = in;
+  for (size_t i = 0; i + 1 < terms.size(); i++) {
+    const int which = 1 + (int)(i & 1);
+    if (ensure_aux(c, which, bytes)) return 1;
+    u64 *dst = (u64 *)c->aux[which];
+    if (apply_galois(c, cur, dst, nl, elt_from_step(c, terms[i]), count)) return 1;
+    cur = dst;
+  }
+  return apply_galois_add(c, cur, addend, out, nl, elt_from_step(c, terms.back()), count, 1 + (int)((terms.size() - 1) & 1));
+}
+
+// acc = in; acc = acc + rotate(acc, s) for each step in order; out = acc.  The running sums ping-pong through arenas 3 and 4
+// (0 .. 2 belong to the rotations), only the last one lands in `out`, which may therefore be `in`.
+static int rotate_sum(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, const std::vector<int> &steps, size_t count) {
+  for (int s : steps) {  // every step is checked before the first launch
+    std::vector<int> terms;
+    if (s && rotation_terms(c, s, terms)) return 1;
+  }
+  if (!count) return 0;
+  const size_t bytes = count * 2 * nl * (size_t)c->n * 8;
+  if (steps.empty()) {
+    if (in != out) ABC_HIP_CHECK(hipMemcpyAsync(out, in, bytes, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+  }
+  if (steps.size() > 1 && (ensure_aux(c, 3, bytes) || (steps.size() > 2 && ensure_aux(c, 4, bytes)))) return 1;
+  const u64 *acc = in;
+  for (size_t i = 0; i < steps.size(); i++) {
+    u64 *dst = (i + 1 == steps.size()) ? out : (u64 *)c->aux[3 + (i & 1)];
+    if (rotate_add(c, acc, acc, dst, nl, steps[i], count)) return 1;
+    acc = dst;
+  }
   return 0;
 }
 
@@ -935,6 +1003,22 @@ int abc_hip_apply_galois(abc_hip_ctx *c, const uint64_t *in, uint64_t *out, int 
   if (check_level(c, nl)) return 1;
   if (in == out) { set_error("apply_galois: in-place not supported, use abc_hip_rotate"); return 1; }
   return apply_galois(c, in, out, nl, elt, count);
+}
+int abc_hip_rotate_add(abc_hip_ctx *c, const uint64_t *in, const uint64_t *addend, uint64_t *out, int nl, int steps, size_t count) {
+  CTX_GUARD(c);
+  if (check_level(c, nl)) return 1;
+  return guarded([&] { return rotate_add(c, in, addend, out, nl, steps, count); });
+}
+int abc_hip_apply_galois_add(abc_hip_ctx *c, const uint64_t *in, const uint64_t *addend, uint64_t *out, int nl, uint32_t elt, size_t count) {
+  CTX_GUARD(c);
+  if (check_level(c, nl)) return 1;
+  return apply_galois_add(c, in, addend, out, nl, elt, count, 1);
+}
+int abc_hip_rotate_sum(abc_hip_ctx *c, const uint64_t *in, uint64_t *out, int nl, const int *h_steps, int n_steps, size_t count) {
+  CTX_GUARD(c);
+  if (check_level(c, nl)) return 1;
+  if (n_steps < 0 || (n_steps && !h_steps)) { set_error("rotate_sum: bad step list"); return 1; }
+  return guarded([&] { return rotate_sum(c, in, out, nl, std::vector<int>(h_steps, h_steps + n_steps), count); });
 }
 int abc_hip_apply_galois_hoisted(abc_hip_ctx *c, const uint64_t *in, uint64_t *out, int nl, const uint32_t *h_elts, int n_elts,
                                  size_t count) {

@@ -196,13 +196,13 @@ struct abc_hip_ctx {
   };
   std::unordered_map<const uint64_t *, KeyMirror> key_mirrors;
   std::vector<uint32_t> galois_order;
-  // workspace (kernel-sequence scratch) and three caller-level arenas (products, rotation ping-pong buffers);
+  // workspace (kernel-sequence scratch) and five caller-level arenas (0: permuted input, 1 / 2: products and rotation ping-pong, 3 / 4: rotate_sum's running sums);
   // all grow on demand and are reused, so steady-state calls perform no hipMalloc / hipFree; one that grows while a graph owns
   // it is held back, not freed (ensure_arena in abc_buffers.hip)
   void *ws = nullptr;
   size_t ws_bytes = 0;
-  void *aux[3] = {nullptr, nullptr, nullptr};
-  size_t aux_bytes[3] = {0, 0, 0};
+  void *aux[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  size_t aux_bytes[5] = {0, 0, 0, 0, 0};
   size_t limb_words() const { return (size_t)n; }
   size_t key_words() const { return (size_t)L * 2 * K * n; }
 };
@@ -303,15 +303,16 @@ int keyed_small(abc_hip_ctx *c, const uint8_t key[32], uint64_t nonce, int8_t *d
 int keyed_uniform(abc_hip_ctx *c, const uint8_t key[32], uint64_t stream, int nkeys, u64 *d_a);
 
 // the key switch of route r (abc_kernels_fused.hip; any sequence); gelt: the Galois element of a rotation folded into it
-// (RotRoute::fold), with target = c1, addend = c0 of the ciphertext
+// (RotRoute::fold), with target = c1, addend = c0 of the ciphertext; acc: a second ciphertext [count][2][nl][N] added in the last
+// kernel (RotAddRoute::fused: only with gelt, only the sequences route_rotate_add names)
 int launch_keyswitch(abc_hip_ctx *c, const KsRoute &r, const u64 *target, size_t target_stride, const u64 *key, u64 *out2, int nl, size_t count,
-                     const u64 *addend, size_t addend_stride, bool add_c1, u32 gelt = 0);
+                     const u64 *addend, size_t addend_stride, bool add_c1, u32 gelt = 0, const u64 *acc = nullptr);
 // CKKS multiply + relinearise in one sequence (every Seq but bmul and generic)
 int launch_mul_relin(abc_hip_ctx *c, Seq seq, const u64 *a, const u64 *b, u64 *out, int nl, size_t count);
 // split key switch without LDS-resident limbs (abc_kernels_gsplit.hip): N = 2^15, and the first step at N = 2^14 for small batches
 size_t gsplit_scratch_words(const abc_hip_ctx *c, int nl);
 int gsplit_chunk15(abc_hip_ctx *c, hipStream_t st, u64 *scratch, size_t cc, int nl, int mode, const u64 *opa, const u64 *opb,
-                   size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt);
+                   size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt, const u64 *acc = nullptr);
 void gsplit_front14(hipStream_t st, abc_hip_ctx *c, size_t cc, int nl, int mode, const u64 *opa, const u64 *opb, size_t opa_stride,
                     double *hinv, double *part, u32 gelt, int pack = 0);
 // ---- the main step of the split key switch (k_split4_main_fp, k_gsplit_main[_deep], k_isplit_main[_deep]): host side ----
@@ -330,8 +331,19 @@ struct MainArgs {
   u64 imap;  // nibble s = data prime of grid slot s (kAllSlots with ni = nl: all of them; the 512-thread kernels read eight nibbles)
   int ni;    // slots
   int pack;  // the half-done limbs are packed (abc_ntt.hpp; k_split4_main_fp only)
+  const u64 *acc = nullptr;  // mode 1 with gelt: a second, ungathered ciphertext [cc][2][nl][N] to add (RotAddRoute::fused), or null
 };
 constexpr u64 kAllSlots = 0xfedcba9876543210ull;
+// The last kernels of the split key switches take the second addend of rotate_add as a trailing template parameter PACK: empty
+// for every instantiation that existed (same name, same argument list, same code), <.., WithAcc> with one more argument, the
+// pointer, for the fused form.
+struct WithAcc {};
+template <class>
+struct AccArg {
+  const u64 *p;
+};
+__host__ __device__ inline const u64 *acc_ptr() { return nullptr; }
+__host__ __device__ inline const u64 *acc_ptr(AccArg<WithAcc> a) { return a.p; }
 // nl + 1 transform buffers + the block's twiddle table, 1024 entries of tw_bytes = sizeof(A::TW): 8 (fp64) or 16 (integer)
 constexpr size_t main_lds_bytes(int nl, int tw_bytes) { return (size_t)((nl + 1) * lds_words(10)) * 8 + 1024 * (size_t)tw_bytes; }
 // (mode, gelt) -> f(MODE, GAL) as integral constants: multiply / key switch with the Galois gather folded in / plain key switch
@@ -366,9 +378,9 @@ inline void dispatch_nl(int nl, Fn f) {
 bool split4_main(abc_hip_ctx *c, int mode, const MainArgs &a);
 void gsplit_main15(abc_hip_ctx *c, int mode, const MainArgs &a);
 int bsplit_big(abc_hip_ctx *c, const u64 *target, size_t target_stride, const u64 *key, u64 *out, int nl, size_t count, const u64 *addend,
-               size_t addend_stride, bool add_c1, u32 ginv = 0);
+               size_t addend_stride, bool add_c1, u32 ginv = 0, const u64 *acc = nullptr);
 int bsplit_back14(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const double *part, double *half, const u64 *key, const u64 *addend,
-                  size_t addend_stride, int add_c1, u64 *out, u32 ginv = 0);
+                  size_t addend_stride, int add_c1, u64 *out, u32 ginv = 0, const u64 *acc = nullptr);
 int bsplit_back13(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const double *part, double *half, const u64 *key, const u64 *addend,
                   size_t addend_stride, int add_c1, u64 *out, u32 ginv = 0);
 // the mirrors of a key-switching key (nullptr: not available -- capture in progress and not built yet, or allocation failed)

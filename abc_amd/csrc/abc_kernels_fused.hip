@@ -710,13 +710,19 @@ __global__ __launch_bounds__(256) void k_split3_pass_fp(DevCtx c, const double *
   }
 }
 
-template <int MODE, bool GAL, int NL>
+// A = WithAcc (MODE 1, one more argument): a second, ungathered ciphertext `acc` [ct][2][nl][N] is added, read at the thread's own
+// index (rotate_add: out = acc + rotate(in)).  `out` may be `acc`: a thread loads its two coefficients of either component before
+// it stores them.  Without it the pack is empty and the kernel is, name and code, the one it was.
+template <int MODE, bool GAL, int NL, class... A>
 __global__ __launch_bounds__(NL ? (NL + 1) * 64 : 832) void k_split3_main_fp(DevCtx c, const double *__restrict__ part,
                                                                               const double *__restrict__ tpart,
                                                                               const u64 *__restrict__ opa, const u64 *__restrict__ opb,
                                                                               size_t opa_stride, size_t opb_stride, int add_c1,
                                                                               const u64 *__restrict__ key, u64 *__restrict__ out, int nl_rt,
-                                                                              u32 gelt) {
+                                                                              u32 gelt, AccArg<A>... acc_) {
+  constexpr bool ACC = sizeof...(A) != 0;
+  static_assert(!ACC || MODE == 1, "the second addend belongs to the key switch");
+  [[maybe_unused]] const u64 *acc = acc_ptr(acc_...);
   extern __shared__ double dyn[];  // nl + 1 buffers of one 1024-point block: nl - 1 decomposition limbs, 2 mod-down limbs
   const int nl = NL ? NL : nl_rt;
   const int W = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -772,8 +778,16 @@ __global__ __launch_bounds__(NL ? (NL + 1) * 64 : 832) void k_split3_main_fp(Dev
             x[k] = fp_from_u64(xl[si]);
             if (opb) {
               const u64 *ad = opb + ct * opb_stride + (size_t)I * N;
-              d0[k] = fp_from_u64(ad[si]);
-              if (add_c1) d1[k] = fp_from_u64(ad[pw + si]);
+              if constexpr (ACC) {
+                // two canonical residues added as integers: below 2q <= 2^51, so the conversion stays exact; behind
+                // fp_mul_lazy (|.| <= q) fp_to_canon then sees less than 3q < 2^52 and still centres exactly
+                const u64 *ac = acc + ct * 2 * pw + (size_t)I * N + base + e + k;
+                d0[k] = fp_from_u64(ad[si] + ac[0]);
+                d1[k] = fp_from_u64(add_c1 ? ad[pw + si] + ac[pw] : ac[pw]);
+              } else {
+                d0[k] = fp_from_u64(ad[si]);
+                if (add_c1) d1[k] = fp_from_u64(ad[pw + si]);
+              }
             }
           }
         }
@@ -814,6 +828,23 @@ static void launch_split3_main(abc_hip_ctx *c, const MainArgs &a) {
   const int nl = a.nl;
   const dim3 grid((unsigned)(a.cc * nl * 16)), block(64 * (nl + 1));
   const size_t lds = (size_t)((nl + 1) * lds_words(10)) * 8;
+  if constexpr (MODE == 1 && GAL) {
+    if (a.acc) {
+#define ABC_TM3A(NLV)                                                                                                                  \
+  hipLaunchKernelGGL((k_split3_main_fp<1, true, NLV, WithAcc>), grid, block, lds, a.st, c->dc, (const double *)a.part,               \
+                     (const double *)a.tpart, a.opa, a.opb, a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, nl, a.gelt,          \
+                     AccArg<WithAcc>{a.acc})
+      switch (nl) {
+        case 1: ABC_TM3A(1); break;
+        case 2: ABC_TM3A(2); break;
+        case 3: ABC_TM3A(3); break;
+        case 4: ABC_TM3A(4); break;
+        default: ABC_TM3A(0); break;
+      }
+#undef ABC_TM3A
+      return;
+    }
+  }
 #define ABC_TM3(NLV)                                                                                                             \
   hipLaunchKernelGGL((k_split3_main_fp<MODE, GAL, NLV>), grid, block, lds, a.st, c->dc, (const double *)a.part, (const double *)a.tpart, \
                      a.opa, a.opb, a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, nl, a.gelt)
@@ -846,12 +877,19 @@ struct PairOps {
   u64 xs[2], d0s[2], d1s[2];      // MODE 1
 };
 
-template <int MODE, bool GAL, int NL, bool HALVES>
+// A = WithAcc (MODE 1, one more argument): the second, ungathered ciphertext of rotate_add, as in k_split3_main_fp.  Its words are
+// added to the gathered addend as integers when the operands are loaded -- d0s < 2q <= 2^51, d1s < q (2q with add_c1) -- so PairOps
+// holds what it held, and both forms still load every operand before their first store.
+template <int MODE, bool GAL, int NL, bool HALVES, class... A>
 __global__ __launch_bounds__(512, HALVES ? 6 : NL <= 4 ? 4 : 2) void k_split4_main_fp(DevCtx c, const double *__restrict__ part,
                                                                    const double *__restrict__ tpart, const u64 *__restrict__ opa,
                                                                    const u64 *__restrict__ opb, size_t opa_stride, size_t opb_stride,
                                                                    int add_c1, const u64 *__restrict__ key, u64 *__restrict__ out, u32 gelt,
-                                                                   u32 imap, int ni, int pack, const double *__restrict__ keyf) {
+                                                                   u32 imap, int ni, int pack, const double *__restrict__ keyf,
+                                                                   AccArg<A>... acc_) {
+  constexpr bool ACC = sizeof...(A) != 0;
+  static_assert(!ACC || MODE == 1, "the second addend belongs to the key switch");
+  [[maybe_unused]] const u64 *acc = acc_ptr(acc_...);
   // grid (ct, slot, block), slot < ni; the data prime of a slot is nibble `slot` of imap (all of them: 0x76543210, ni = nl; a subset
   // when a chain mixes fp64-capable and wider primes: abc_kernels_isplit.hip)
   // pack: the half-done limbs of `part` / `tpart` modulo primes of at most 48 bits arrive packed (abc_ntt.hpp)
@@ -867,7 +905,8 @@ __global__ __launch_bounds__(512, HALVES ? 6 : NL <= 4 ? 4 : 2) void k_split4_ma
   // prefetched, 20 bytes of scratch per lane -- scratch reloads go through the same in-order vmcnt as the prefetch.  The last
   // digit's eight registers are therefore loaded late: its words come out of L2 and are used last, behind the other digits'
   // products (123 VGPRs, no scratch).  HALVES requests everything late.
-  constexpr int LATE = (!HALVES && MODE == 0 && NL == 4) ? 1 : 0;
+  // (the second addend's two loads put the one-piece key switch at four limbs in the same place: 36 bytes of scratch without it)
+  constexpr int LATE = (!HALVES && (MODE == 0 || ACC) && NL == 4) ? 1 : 0;
   using Ops = PairOps<MODE, NL, HALVES>;
   const int W = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = threadIdx.x & 63;
@@ -938,6 +977,14 @@ __global__ __launch_bounds__(512, HALVES ? 6 : NL <= 4 ? 4 : 2) void k_split4_ma
           o.d0s[k] = ad[si];
           if (add_c1) o.d1s[k] = ad[pw + si];
         }
+      }
+      if constexpr (ACC) {  // the thread's own pair of either component: one 16-byte load each
+        const u64 *ac = acc + ct * 2 * pw + (size_t)I * N + base + e;
+        const u64x2 c0 = *reinterpret_cast<const u64x2 *>(ac), c1 = *reinterpret_cast<const u64x2 *>(ac + pw);
+        // canonical residues: each sum is below 2q <= 2^51 (d1s with add_c1 too), exact in fp_from_u64; fp_mul_lazy's |.| <= q
+        // plus it is below 3q < 2^52 in fp_to_canon, which centres any such value exactly
+        o.d0s[0] += c0.x; o.d0s[1] += c0.y;
+        o.d1s[0] += c1.x; o.d1s[1] += c1.y;
       }
     }
   };
@@ -1082,6 +1129,15 @@ bool split4_main(abc_hip_ctx *c, int mode, const MainArgs &a) {
   dispatch_mode(mode, a.gelt, [&](auto M, auto G) {
     dispatch_nl<1, 7>(a.nl, [&](auto NL) {
       auto launch = [&](auto H) {
+        if constexpr (decltype(M)::value == 1 && decltype(G)::value) {
+          if (a.acc) {
+            hipLaunchKernelGGL((k_split4_main_fp<1, true, decltype(NL)::value, decltype(H)::value, WithAcc>), grid, block,
+                               main_lds_bytes(a.nl, sizeof(double)), a.st, c->dc, (const double *)a.part, (const double *)a.tpart, a.opa, a.opb,
+                               a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, (u32)a.imap, a.ni, a.pack, keyf,
+                               AccArg<WithAcc>{a.acc});
+            return;
+          }
+        }
         hipLaunchKernelGGL((k_split4_main_fp<decltype(M)::value, decltype(G)::value, decltype(NL)::value, decltype(H)::value>), grid, block,
                            main_lds_bytes(a.nl, sizeof(double)), a.st, c->dc, (const double *)a.part, (const double *)a.tpart, a.opa, a.opb,
                            a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, (u32)a.imap, a.ni, a.pack, keyf);
@@ -1176,13 +1232,14 @@ static int run_isplit(abc_hip_ctx *c, int mode, const u64 *opa, const u64 *opb, 
 
 // N = 2^15 (abc_kernels_gsplit.hip)
 static int run_gsplit15(abc_hip_ctx *c, int mode, const u64 *opa, const u64 *opb, size_t opa_stride, size_t opb_stride, bool add_c1,
-                        const u64 *key, u64 *out, int nl, size_t count, u32 gelt) {
+                        const u64 *key, u64 *out, int nl, size_t count, u32 gelt, const u64 *acc = nullptr) {
   const size_t N = (size_t)c->n;
   const ChunkPlan p = plan_chunks(c->facts, nl, count);
   return for_each_chunk(c, count, p.chunk, p.lanes, gsplit_scratch_words(c, nl), nullptr,
                         [&](hipStream_t st, u64 *scratch, size_t off, size_t cc) {
                           return gsplit_chunk15(c, st, scratch, cc, nl, mode, opa + off * opa_stride, opb ? opb + off * opb_stride : nullptr,
-                                                opa_stride, opb_stride, add_c1 ? 1 : 0, key, out + off * 2 * (size_t)nl * N, gelt);
+                                                opa_stride, opb_stride, add_c1 ? 1 : 0, key, out + off * 2 * (size_t)nl * N, gelt,
+                                                acc ? acc + off * 2 * (size_t)nl * N : nullptr);
                         });
 }
 
@@ -1241,7 +1298,7 @@ int launch_mul_relin(abc_hip_ctx *c, Seq seq, const u64 *a, const u64 *b, u64 *o
 // target: [nl][N] per ciphertext at target + ct*target_stride, in the ciphertext's own form (BFV coefficient, CKKS NTT)
 template <int LB>
 static int run_keyswitch(abc_hip_ctx *c, Seq seq, const u64 *target, size_t target_stride, const u64 *key, u64 *out, int nl, size_t count,
-                         const u64 *addend, size_t addend_stride, bool add_c1, u32 gelt) {
+                         const u64 *addend, size_t addend_stride, bool add_c1, u32 gelt, const u64 *acc) {
   const size_t N = (size_t)1 << LB;
   const bool ckks = (c->scheme == 2);
   const ChunkPlan p = plan_chunks(c->facts, nl, count);
@@ -1253,6 +1310,7 @@ static int run_keyswitch(abc_hip_ctx *c, Seq seq, const u64 *target, size_t targ
   const u32 ginv = (!ckks && gelt) ? (u32)host::invmod(gelt, 2 * (uint64_t)N) : 0u;
   if (ginv && !splitb) { set_error("run_keyswitch: a BFV permutation is only folded into the split sequence"); return 1; }
   if (ckks && gelt && !splitc) { set_error("run_keyswitch: a CKKS permutation is only folded into the split sequence"); return 1; }
+  if (acc && !(gelt && (splitc || splitb))) { set_error("run_keyswitch: a second addend is only taken with a folded permutation"); return 1; }
   const size_t SN = (splitc || splitb) ? (size_t)c->dc.ps : N;
   const size_t per_ct = fused_scratch_limbs(nl) * SN;
   // the split kernels read the key's fp64 twin (BFV: the inner-product kernel)
@@ -1262,6 +1320,7 @@ static int run_keyswitch(abc_hip_ctx *c, Seq seq, const u64 *target, size_t targ
     const u64 *tg = target + off * target_stride;
     const u64 *ad = addend ? addend + off * addend_stride : nullptr;
     u64 *o = out + off * 2 * nl * N;
+    const u64 *ac = acc ? acc + off * 2 * nl * N : nullptr;
     if constexpr (LB == 14) {
       if (splitc) {
         if (k.lean)
@@ -1271,7 +1330,7 @@ static int run_keyswitch(abc_hip_ctx *c, Seq seq, const u64 *target, size_t targ
                              dim3((unsigned)(cc * nl)), dim3((1 << LB) / 16), 0, st, c->dc, tg, target_stride, (double *)s.dec, nl, 0,
                              gelt, 1 | (k.pack ? 2 : 0));
         launch_split3(c, s, 1, MainArgs{st, cc, nl, nullptr, nullptr, tg, ad, target_stride, addend_stride, add_c1 ? 1 : 0, key, o, gelt,
-                                        kAllSlots, nl, k.pack},
+                                        kAllSlots, nl, k.pack, ac},
                       k.main4);
         ABC_HIP_CHECK(hipGetLastError());
         return 0;
@@ -1281,7 +1340,7 @@ static int run_keyswitch(abc_hip_ctx *c, Seq seq, const u64 *target, size_t targ
         hipLaunchKernelGGL((k_fused_operand_pass0_fp<LB, false, false>), dim3((unsigned)(cc * nl * (k.per_target ? nl + 1 : 1))),
                            dim3((1 << LB) / 16), 0, st, c->dc, tg, target_stride, (double *)s.dec, nl, k.per_target ? 1 : 0, ginv, 1);
         // inner product + inverse tails for every key prime, then the register-only finish (a rotation's addend g(c0): gathered there)
-        return bsplit_back14(c, st, cc, nl, (const double *)s.dec, (double *)s.ksacc, key, ad, addend_stride, add_c1 ? 1 : 0, o, ginv);
+        return bsplit_back14(c, st, cc, nl, (const double *)s.dec, (double *)s.ksacc, key, ad, addend_stride, add_c1 ? 1 : 0, o, ginv, ac);
       }
     }
     // LDS-resident kernels (smaller rings, wider primes, ABC_HIP_NO_SPLIT)
@@ -1298,14 +1357,15 @@ static int run_keyswitch(abc_hip_ctx *c, Seq seq, const u64 *target, size_t targ
 }
 
 int launch_keyswitch(abc_hip_ctx *c, const KsRoute &r, const u64 *target, size_t target_stride, const u64 *key, u64 *out, int nl, size_t count,
-                     const u64 *addend, size_t addend_stride, bool add_c1, u32 gelt) {
+                     const u64 *addend, size_t addend_stride, bool add_c1, u32 gelt, const u64 *acc) {
   if (!count) return 0;
+  if (acc && (r.seq == Seq::isplit || r.seq == Seq::generic)) { set_error("launch_keyswitch: this sequence takes no second addend"); return 1; }
   switch (r.seq) {
-    case Seq::gsplit15: return run_gsplit15(c, 1, target, addend, target_stride, addend_stride, add_c1, key, out, nl, count, gelt);
+    case Seq::gsplit15: return run_gsplit15(c, 1, target, addend, target_stride, addend_stride, add_c1, key, out, nl, count, gelt, acc);
     case Seq::isplit: return run_isplit(c, 1, target, addend, target_stride, addend_stride, add_c1, key, out, nl, count, gelt);
     case Seq::bsplit_big:  // BFV, coefficient form: the signed permutation folded into the first step's load and the last step's addend
       return bsplit_big(c, target, target_stride, key, out, nl, count, addend, addend_stride, add_c1,
-                        gelt ? (u32)host::invmod(gelt, 2 * (uint64_t)c->n) : 0u);
+                        gelt ? (u32)host::invmod(gelt, 2 * (uint64_t)c->n) : 0u, acc);
     case Seq::generic:
       return keyswitch_generic(c, r.front, target, target_stride, key, out, nl, count, addend, addend_stride, add_c1,
                                gelt ? (u32)host::invmod(gelt, 2 * (uint64_t)c->n) : 0u);
@@ -1314,7 +1374,7 @@ int launch_keyswitch(abc_hip_ctx *c, const KsRoute &r, const u64 *target, size_t
     case Seq::lds_fp:
     case Seq::lds_int:
       return dispatch_logn<10, 14>(c->logn, [&](auto LB) {
-        return run_keyswitch<decltype(LB)::value>(c, r.seq, target, target_stride, key, out, nl, count, addend, addend_stride, add_c1, gelt);
+        return run_keyswitch<decltype(LB)::value>(c, r.seq, target, target_stride, key, out, nl, count, addend, addend_stride, add_c1, gelt, acc);
       });
     default: set_error("launch_keyswitch: not a key-switch sequence"); return 1;
   }

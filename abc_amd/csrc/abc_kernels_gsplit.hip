@@ -472,11 +472,17 @@ struct GPairOps {
   u64 xs[2], d0s[2], d1s[2];
 };
 
-template <int LOGN, int MODE, bool GAL, int NL>
+// A = WithAcc (MODE 1, one more argument): a second, ungathered ciphertext `acc` [ct][2][nl][N] is added, read at the thread's own
+// index (rotate_add: out = acc + rotate(in), cf. k_split4_main_fp).  `out` may be `acc`: every operand is loaded ahead of the
+// transform.  Without it the pack is empty and the kernel is, name and code, the one it was.
+template <int LOGN, int MODE, bool GAL, int NL, class... A>
 __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_gsplit_main(DevCtx c, const double *__restrict__ part, const double *__restrict__ tpart,
                                                         const u64 *__restrict__ opa, const u64 *__restrict__ opb, size_t opa_stride,
                                                         size_t opb_stride, int add_c1, const u64 *__restrict__ key, u64 *__restrict__ out,
-                                                        u32 gelt, u32 imap, int ni) {
+                                                        u32 gelt, u32 imap, int ni, AccArg<A>... acc_) {
+  constexpr bool ACC = sizeof...(A) != 0;
+  static_assert(!ACC || MODE == 1, "the second addend belongs to the key switch");
+  [[maybe_unused]] const u64 *acc = acc_ptr(acc_...);
   // grid (ct, slot, block), slot < ni; the data prime of a slot is nibble `slot` of imap (all: 0x76543210, ni = nl; a subset for
   // chains that mix fp64-capable and wider primes: abc_kernels_isplit.hip)
   constexpr int LOGNB = LOGN - 10, NB = 1 << LOGNB, nl = NL, NT = 512, PER = 2;
@@ -534,6 +540,14 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_gsplit_main(DevCtx c, 
         o.d0s[k] = ad[si];
         if (add_c1) o.d1s[k] = ad[pw + si];
       }
+    }
+    if constexpr (ACC) {
+      const u64 *ac = acc + ct * 2 * pw + (size_t)I * N + base + e;
+      const u64x2 c0 = *reinterpret_cast<const u64x2 *>(ac), c1 = *reinterpret_cast<const u64x2 *>(ac + pw);
+      // canonical residues added as integers: below 2q <= 2^51, exact in fp_from_u64; with fp_mul_lazy's |.| <= q the sum that
+      // fp_to_canon centres stays below 3q < 2^52
+      o.d0s[0] += c0.x; o.d0s[1] += c0.y;
+      o.d1s[0] += c1.x; o.d1s[1] += c1.y;
     }
   }
   block_twiddles_store<10, double, PER>(ltw, (int)threadIdx.x, NT, twv);
@@ -736,6 +750,14 @@ static void launch_gsplit_main(abc_hip_ctx *c, int mode, const MainArgs &a) {
                          a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, a.nl, a.imap, a.ni);
     else
       dispatch_nl<1, 7>(a.nl, [&](auto NL) {
+        if constexpr (MODE == 1 && GAL) {
+          if (a.acc) {
+            hipLaunchKernelGGL((k_gsplit_main<LOGN, 1, true, decltype(NL)::value, WithAcc>), gmain, dim3(512), main_lds_bytes(a.nl, sizeof(double)),
+                               a.st, c->dc, part, tpart, a.opa, a.opb, a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, (u32)a.imap, a.ni,
+                               AccArg<WithAcc>{a.acc});
+            return;
+          }
+        }
         hipLaunchKernelGGL((k_gsplit_main<LOGN, MODE, GAL, decltype(NL)::value>), gmain, dim3(512), main_lds_bytes(a.nl, sizeof(double)), a.st, c->dc, part,
                            tpart, a.opa, a.opb, a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, (u32)a.imap, a.ni);
       });
@@ -764,12 +786,13 @@ size_t gsplit_scratch_words(const abc_hip_ctx *c, int nl) {
 }
 // one chunk at N = 2^15: mode 0 multiply (opa = a, opb = b), mode 1 key switch (opa = operand in NTT form, opb = addend)
 int gsplit_chunk15(abc_hip_ctx *c, hipStream_t st, u64 *scratch, size_t cc, int nl, int mode, const u64 *opa, const u64 *opb,
-                   size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt) {
+                   size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt, const u64 *acc) {
+  if (acc && (nl > 7 || !gelt || mode != 1)) { set_error("gsplit_chunk15: no main kernel takes a second addend here"); return 1; }
   const size_t PS = (size_t)c->dc.ps;
   double *hinv = (double *)scratch, *part = hinv + cc * (size_t)nl * PS, *tpart = part + cc * (size_t)nl * (nl + 1) * PS,
          *tsp = tpart + cc * 2 * (size_t)nl * PS;
   launch_gsplit_front<15>(st, c, cc, nl, mode, opa, opb, opa_stride, hinv, part, gelt);
-  launch_gsplit_back<15>(c, mode, MainArgs{st, cc, nl, part, tpart, opa, opb, opa_stride, opb_stride, add_c1, key, out, gelt, kAllSlots, nl, 0},
+  launch_gsplit_back<15>(c, mode, MainArgs{st, cc, nl, part, tpart, opa, opb, opa_stride, opb_stride, add_c1, key, out, gelt, kAllSlots, nl, 0, acc},
                          tsp);
   ABC_HIP_CHECK(hipGetLastError());
   return 0;
@@ -783,9 +806,9 @@ int gsplit_chunk15(abc_hip_ctx *c, hipStream_t st, u64 *scratch, size_t cc, int 
 // limb's cross pass per data prime from registers was 1 - 3 % slower.)
 template <int LOGN>
 __global__ void k_bsplit_tcoef(DevCtx c, const double *__restrict__ half, double *__restrict__ tco, int nl);
-template <int LOGN>
+template <int LOGN, class... A>
 __global__ void k_bsplit_finish_big(DevCtx c, const double *__restrict__ half, const double *__restrict__ tco, const u64 *__restrict__ addend,
-                                    size_t addend_stride, int add_c1, u64 *__restrict__ out, int nl, u32 ginv);
+                                    size_t addend_stride, int add_c1, u64 *__restrict__ out, int nl, u32 ginv, AccArg<A>... acc_);
 
 // half: [cc][nl+1][2] limbs at stride c->dc.ps; part as written by k_fused_operand_pass0_fp<14, false, false> (padded layout)
 // B2 of the BFV sequences: inner product + inverse tails for every key prime, nl digits
@@ -802,13 +825,17 @@ static void launch_bsplit_special(abc_hip_ctx *c, hipStream_t st, size_t cc, int
     });
 }
 int bsplit_back14(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const double *part, double *half, const u64 *key, const u64 *addend,
-                  size_t addend_stride, int add_c1, u64 *out, u32 ginv) {
+                  size_t addend_stride, int add_c1, u64 *out, u32 ginv, const u64 *acc) {
   launch_bsplit_special<14>(c, st, cc, nl, part, key, half);
   // half occupies the ksacc + tsp regions of the caller's scratch (2 nl + 2 limbs per ciphertext), tco the tlast region behind them
   double *tco = half + cc * 2 * (size_t)(nl + 1) * (size_t)c->dc.ps;
   hipLaunchKernelGGL((k_bsplit_tcoef<14>), dim3((unsigned)(cc * 2 * 4)), dim3(256), 0, st, c->dc, half, tco, nl);
-  hipLaunchKernelGGL((k_bsplit_finish_big<14>), dim3((unsigned)(cc * 2 * nl * 4)), dim3(256), 0, st, c->dc, half, tco, addend,
-                     addend_stride, add_c1, out, nl, ginv);
+  if (acc)
+    hipLaunchKernelGGL((k_bsplit_finish_big<14, WithAcc>), dim3((unsigned)(cc * 2 * nl * 4)), dim3(256), 0, st, c->dc, half, tco, addend,
+                       addend_stride, add_c1, out, nl, ginv, AccArg<WithAcc>{acc});
+  else
+    hipLaunchKernelGGL((k_bsplit_finish_big<14>), dim3((unsigned)(cc * 2 * nl * 4)), dim3(256), 0, st, c->dc, half, tco, addend,
+                       addend_stride, add_c1, out, nl, ginv);
   ABC_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -893,10 +920,17 @@ __global__ __launch_bounds__(256) void k_bsplit_tcoef(DevCtx c, const double *__
   }
 }
 
-template <int LOGN>
+// A = WithAcc (one more argument): a second ciphertext `acc` [ct][2][nl][N], unsigned and ungathered, is added to either component
+// (rotate_add: out = acc + rotate(in)).  It joins the sign-flipped gathered c0 as an integer: two canonical residues, below
+// 2q <= 2^51, exact in fp_from_u64; r is fp_mul_lazy's |.| <= q, so fp_to_canon centres less than 3q < 2^52.  `out` may be `acc`: a
+// thread reads a word of it just before it writes that word.  Without it the pack is empty: the kernel it was, name and code.
+template <int LOGN, class... A>
 __global__ __launch_bounds__(256) void k_bsplit_finish_big(DevCtx c, const double *__restrict__ half, const double *__restrict__ tco,
                                                            const u64 *__restrict__ addend, size_t addend_stride, int add_c1,
-                                                           u64 *__restrict__ out, int nl, u32 ginv /* BFV rotation: gather the addend */) {
+                                                           u64 *__restrict__ out, int nl, u32 ginv /* BFV rotation: gather the addend */,
+                                                           AccArg<A>... acc_) {
+  constexpr bool ACC = sizeof...(A) != 0;
+  [[maybe_unused]] const u64 *acc = acc_ptr(acc_...);
   constexpr int LOGNB = LOGN - 10, NB = 1 << LOGNB;
   const int p = (int)((blockIdx.x & 3) << 8) + (int)threadIdx.x;
   const int I = (int)((blockIdx.x >> 2) % (unsigned)nl);
@@ -925,7 +959,19 @@ __global__ __launch_bounds__(256) void k_bsplit_finish_big(DevCtx c, const doubl
   for (int k = 0; k < NB; k++) {
     const double d = fp_mul_lazy(x[k], m.inv_n_c, m.inv_n_cq, m.qd) - (tsrc[(k << 10) + p] + fix);
     double r = fp_mul_lazy(d, inv, inv_q, m.qd);
-    if (add) {
+    if constexpr (ACC) {
+      u64 w = acc[(cc * nl + I) * N + (size_t)((k << 10) + p)];
+      if (add) {
+        if (ginv) {  // workgroup-uniform
+          bool neg;
+          const u64 v = cin[galois_coef_src((u32)((k << 10) + p), ginv, LOGN, neg)];
+          w += neg ? neg_mod(v, m.q) : v;
+        } else {
+          w += cin[(k << 10) + p];
+        }
+      }
+      r += fp_from_u64(w);
+    } else if (add) {
       if (ginv) {  // workgroup-uniform
         bool neg;
         const u64 v = cin[galois_coef_src((u32)((k << 10) + p), ginv, LOGN, neg)];
@@ -1018,10 +1064,14 @@ __global__ __launch_bounds__(256) void k_bsplit_pass0_lds(DevCtx c, const u64 *_
 // removed: 256 VGPRs, one wavefront per SIMD, 1.6 TB/s on its bytes).  Workgroup ((ct, comp), I, group of 32 positions); stages R-1..RB run on RA
 // consecutive block indices (thread = (group of 2^RA blocks, position)), stages RB-1..0 on blocks 2^RA apart (thread = (block
 // index mod 2^RA, position)), which then finishes its 2^RB coefficients: N^-1, subtract the special limb, q_sp^-1, addend.
-template <int LOGN>
+// A = WithAcc: the second addend, as in k_bsplit_finish_big.
+template <int LOGN, class... A>
 __global__ __launch_bounds__(256) void k_bsplit_finish_lds(DevCtx c, const double *__restrict__ half, const double *__restrict__ tco,
                                                            const u64 *__restrict__ addend, size_t addend_stride, int add_c1,
-                                                           u64 *__restrict__ out, int nl, u32 ginv /* BFV rotation: gather the addend */) {
+                                                           u64 *__restrict__ out, int nl, u32 ginv /* BFV rotation: gather the addend */,
+                                                           AccArg<A>... acc_) {
+  constexpr bool ACC = sizeof...(A) != 0;
+  [[maybe_unused]] const u64 *acc = acc_ptr(acc_...);
   constexpr int R = LOGN - 10, NB = 1 << R, RA = 3, RB = R - RA, P = 32;
   __shared__ double lds[NB * P];
   const int pg = blockIdx.x & 31;
@@ -1081,7 +1131,19 @@ __global__ __launch_bounds__(256) void k_bsplit_finish_lds(DevCtx c, const doubl
       const size_t e = (size_t)((h << RA) + j) * 1024 + p;
       const double d = fp_mul_lazy(y[h], m.inv_n_c, m.inv_n_cq, m.qd) - (tsrc[e] + fix);
       double r = fp_mul_lazy(d, inv, inv_q, m.qd);
-      if (add) {
+      if constexpr (ACC) {
+        u64 w = acc[(cc * nl + I) * N + (size_t)(pg * P) + e];
+        if (add) {
+          if (ginv) {  // workgroup-uniform
+            bool neg;
+            const u64 v = (cin - (size_t)(pg * P))[galois_coef_src((u32)(e + (size_t)(pg * P)), ginv, LOGN, neg)];
+            w += neg ? neg_mod(v, m.q) : v;
+          } else {
+            w += cin[e];
+          }
+        }
+        r += fp_from_u64(w);  // below 2q <= 2^51: exact; r below 3q < 2^52
+      } else if (add) {
         if (ginv) {  // workgroup-uniform
           bool neg;
           const u64 v = (cin - (size_t)(pg * P))[galois_coef_src((u32)(e + (size_t)(pg * P)), ginv, LOGN, neg)];
@@ -1098,7 +1160,8 @@ __global__ __launch_bounds__(256) void k_bsplit_finish_lds(DevCtx c, const doubl
 // N = 2^13 (BFVDefault(8192): eight 1024-point blocks, radix-8 cross passes in registers) takes the same sequence
 template <int LOGN>
 static int bsplit_big_chunk(abc_hip_ctx *c, hipStream_t st, double *scratch, size_t cc, int nl, const u64 *target, size_t target_stride,
-                            const u64 *key, const u64 *addend, size_t addend_stride, int add_c1, u64 *out, u32 ginv = 0) {
+                            const u64 *key, const u64 *addend, size_t addend_stride, int add_c1, u64 *out, u32 ginv = 0,
+                            const u64 *acc = nullptr) {
   const size_t PS = (size_t)c->dc.ps;
   double *part = scratch, *half = part + cc * (size_t)nl * (nl + 1) * PS, *tco = half + cc * 2 * (size_t)(nl + 1) * PS;
   constexpr bool REG = LOGN < 15;  // cross passes of at most 16 values stay in registers
@@ -1109,19 +1172,28 @@ static int bsplit_big_chunk(abc_hip_ctx *c, hipStream_t st, double *scratch, siz
     hipLaunchKernelGGL((k_bsplit_pass0_lds<LOGN>), dim3((unsigned)(cc * nl * 32)), dim3(256), 0, st, c->dc, target, target_stride, part, nl, ginv);
   launch_bsplit_special<LOGN>(c, st, cc, nl, part, key, half);
   hipLaunchKernelGGL((k_bsplit_tcoef<LOGN>), dim3((unsigned)(cc * 2 * 4)), dim3(256), 0, st, c->dc, half, tco, nl);
-  if constexpr (REG)
-    hipLaunchKernelGGL((k_bsplit_finish_big<LOGN>), dim3((unsigned)(cc * 2 * nl * 4)), dim3(256), 0, st, c->dc, half, tco, addend,
-                       addend_stride, add_c1, out, nl, ginv);
-  else
-    hipLaunchKernelGGL((k_bsplit_finish_lds<LOGN>), dim3((unsigned)(cc * 2 * nl * 32)), dim3(256), 0, st, c->dc, half, tco, addend,
-                       addend_stride, add_c1, out, nl, ginv);
+  if constexpr (REG) {
+    if (acc)
+      hipLaunchKernelGGL((k_bsplit_finish_big<LOGN, WithAcc>), dim3((unsigned)(cc * 2 * nl * 4)), dim3(256), 0, st, c->dc, half, tco, addend,
+                         addend_stride, add_c1, out, nl, ginv, AccArg<WithAcc>{acc});
+    else
+      hipLaunchKernelGGL((k_bsplit_finish_big<LOGN>), dim3((unsigned)(cc * 2 * nl * 4)), dim3(256), 0, st, c->dc, half, tco, addend,
+                         addend_stride, add_c1, out, nl, ginv);
+  } else {
+    if (acc)
+      hipLaunchKernelGGL((k_bsplit_finish_lds<LOGN, WithAcc>), dim3((unsigned)(cc * 2 * nl * 32)), dim3(256), 0, st, c->dc, half, tco, addend,
+                         addend_stride, add_c1, out, nl, ginv, AccArg<WithAcc>{acc});
+    else
+      hipLaunchKernelGGL((k_bsplit_finish_lds<LOGN>), dim3((unsigned)(cc * 2 * nl * 32)), dim3(256), 0, st, c->dc, half, tco, addend,
+                         addend_stride, add_c1, out, nl, ginv);
+  }
   ABC_HIP_CHECK(hipGetLastError());
   return 0;
 }
 
 // whole call: chunks of at most 1 GiB (N = 2^13) / 4 GiB of scratch on the context's stream (a chunk at these sizes fills the device by itself)
 int bsplit_big(abc_hip_ctx *c, const u64 *target, size_t target_stride, const u64 *key, u64 *out, int nl, size_t count, const u64 *addend,
-               size_t addend_stride, bool add_c1, u32 ginv) {
+               size_t addend_stride, bool add_c1, u32 ginv, const u64 *acc) {
   const size_t N = (size_t)c->n, PS = (size_t)c->dc.ps;
   const size_t per_ct = ((size_t)nl * (nl + 1) + 2 * (size_t)(nl + 1) + 2) * PS;  // part | half | tco (words)
   // N = 2^15 / 2^16: 4 GiB of scratch, i.e. 85 ciphertexts per launch group at N = 2^16, L = 8 (1 GiB = 21: config 5 -3.5 % -- a key
@@ -1134,13 +1206,14 @@ int bsplit_big(abc_hip_ctx *c, const u64 *target, size_t target_stride, const u6
     const u64 *tg = target + off * target_stride;
     const u64 *ad = addend ? addend + off * addend_stride : nullptr;
     u64 *o = out + off * 2 * (size_t)nl * N;
+    const u64 *ac = acc ? acc + off * 2 * (size_t)nl * N : nullptr;
     if (c->logn == 13) {
-      if (bsplit_big_chunk<13>(c, c->stream, (double *)c->ws, cc, nl, tg, target_stride, key, ad, addend_stride, add_c1 ? 1 : 0, o, ginv)) return 1;
+      if (bsplit_big_chunk<13>(c, c->stream, (double *)c->ws, cc, nl, tg, target_stride, key, ad, addend_stride, add_c1 ? 1 : 0, o, ginv, ac)) return 1;
       continue;
     }
     const int rc = (c->logn == 15)
-                       ? bsplit_big_chunk<15>(c, c->stream, (double *)c->ws, cc, nl, tg, target_stride, key, ad, addend_stride, add_c1 ? 1 : 0, o, ginv)
-                       : bsplit_big_chunk<16>(c, c->stream, (double *)c->ws, cc, nl, tg, target_stride, key, ad, addend_stride, add_c1 ? 1 : 0, o, ginv);
+                       ? bsplit_big_chunk<15>(c, c->stream, (double *)c->ws, cc, nl, tg, target_stride, key, ad, addend_stride, add_c1 ? 1 : 0, o, ginv, ac)
+                       : bsplit_big_chunk<16>(c, c->stream, (double *)c->ws, cc, nl, tg, target_stride, key, ad, addend_stride, add_c1 ? 1 : 0, o, ginv, ac);
     if (rc) return rc;
   }
   return 0;

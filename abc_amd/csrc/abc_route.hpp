@@ -21,6 +21,7 @@ namespace abc {
 struct Switches {
   bool no_fused = false, no_split = false, no_split4 = false, no_isplit = false, no_gsplit = false, no_lean_front = false, no_bsplit = false, no_mixed = false, no_pack = false, no_key_twin = false, no_bmul = false, no_iks = false, no_tensor_intt = false;
   bool no_galois_fusion = false;
+  bool no_rotate_add_fusion = false;  // ABC_HIP_NO_ROTATE_ADD_FUSION: rotate_add as a rotation into an arena, then the add kernel
   bool main_two_per_cu = false;  // ABC_HIP_MAIN_TWO_PER_CU: k_split4_main_fp in its one-piece pair phase at nl <= 4 (same step, same route: a form of the kernel)
   bool host_sampling = false;  // ABC_HIP_HOST_SAMPLING: the keyed entries (the OS-keyed ones call them) draw with the host twin of the keyed spec (no route depends on it)
   size_t chunk = 0, few_limbs = 48, lean_limit = 96, bfv_scratch_mb = 0, pass0_target_limit = 128;
@@ -94,6 +95,10 @@ struct MulRoute {
 struct RotRoute {
   bool fold;  // the permutation is folded into the key switch `ks`; otherwise k_galois first, then `ks`
   KsRoute ks;
+};
+struct RotAddRoute {
+  RotRoute rot;
+  bool fused;  // the second ciphertext is one more operand of the key switch's last kernel; otherwise rotate into an arena, then add
 };
 struct RescaleRoute {
   Rescale kind;
@@ -196,6 +201,17 @@ inline RotRoute route_rotate(const RouteFacts &f, int nl, bool in_place) {
   return {false, route_keyswitch(f, nl)};
 }
 
+// addend + one Galois element at level nl; in_place: d_out == d_in (the gather reads whole limbs of d_in, so that call is never
+// fused).  Only the last kernels of these four sequences take the ungathered operand (k_split4_main_fp / k_split3_main_fp,
+// k_gsplit_main up to seven limbs, k_bsplit_finish_big / k_bsplit_finish_lds).  `rot` is the rotation either way: the unfused
+// sequence rotates into an arena, never in place, whatever d_out is.
+inline RotAddRoute route_rotate_add(const RouteFacts &f, int nl, bool in_place) {
+  const RotRoute rot = route_rotate(f, nl, false);
+  const Seq s = rot.ks.seq;
+  const bool takes_acc = s == Seq::split14 || s == Seq::bsplit14 || s == Seq::bsplit_big || (s == Seq::gsplit15 && nl <= 7);
+  return {rot, rot.fold && takes_acc && !in_place && !f.sw.no_rotate_add_fusion};
+}
+
 inline RescaleRoute route_rescale(const RouteFacts &f, int nl, bool in_place) {
   if (f.logn > 14 || f.logn < 10 || in_place || f.sw.no_fused) return {Rescale::generic, 0u};
   if (f.use_fp && f.data_fp(nl)) return {Rescale::fp, 0u};
@@ -288,7 +304,7 @@ inline void format_ks(char *buf, size_t cap, const RouteFacts &f, const KsRoute 
 }
 // The route of one call into buf: what abc_hip_route returns.  op: include/abc_hip.h, ABC_HIP_ROUTE_*.  Returns the length,
 // -1 if cap is too small, -2 for an unknown op.
-enum RouteOp { kRouteMulRelin = 0, kRouteKeyswitch = 1, kRouteRotate = 2, kRouteRescale = 3, kRouteMultiply = 4 };
+enum RouteOp { kRouteMulRelin = 0, kRouteKeyswitch = 1, kRouteRotate = 2, kRouteRescale = 3, kRouteMultiply = 4, kRouteRotateAdd = 5 };
 inline int format_op(char *buf, size_t cap, const RouteFacts &f, int op, int nl, size_t count, bool in_place) {
   char ks[80];
   int n = -2;
@@ -303,6 +319,10 @@ inline int format_op(char *buf, size_t cap, const RouteFacts &f, int op, int nl,
     const RotRoute r = route_rotate(f, nl, in_place);
     format_ks(ks, sizeof ks, f, r.ks, nl, count);
     n = snprintf(buf, cap, "%s %s", r.fold ? "fold" : "permute", ks);
+  } else if (op == kRouteRotateAdd) {
+    const RotAddRoute r = route_rotate_add(f, nl, in_place);
+    format_ks(ks, sizeof ks, f, r.rot.ks, nl, count);
+    n = r.fused ? snprintf(buf, cap, "fold+add %s", ks) : snprintf(buf, cap, "%s add=separate %s", r.rot.fold ? "fold" : "permute", ks);
   } else if (op == kRouteRescale) {
     const RescaleRoute r = route_rescale(f, nl, in_place);
     n = r.kind == Rescale::mixed ? snprintf(buf, cap, "mixed fpmask=0x%x", (unsigned)r.fpmask) : snprintf(buf, cap, "%s", name(r.kind));

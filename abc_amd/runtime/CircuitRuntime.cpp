@@ -4,6 +4,7 @@
 #include <iostream>
 
 #include "GraphCapable.hpp"
+#include "RotateAddCapable.hpp"
 
 namespace {
 typedef CircuitRuntime::Token Token;
@@ -258,10 +259,38 @@ std::unique_ptr<AbstractValue> CircuitRuntime::relational() {
   }
   return lhs;
 }
+// `rotate(identifier, [-]integer)` at token `at`, exactly, with no multiplicative operator behind it: the tokens it spans, else 0.
+// Anything else -- a malformed call included -- is left to primary(), which words the errors.
+size_t CircuitRuntime::plainRotateCall(size_t at, std::string &id, int &steps) const {
+  auto punct = [&](size_t k, const char *p) { return peek(at + k).kind == Token::Punct && peek(at + k).text == p; };
+  if (!(peek(at).kind == Token::Ident && peek(at).text == "rotate" && punct(1, "(") && peek(at + 2).kind == Token::Ident && punct(3, ",")))
+    return 0;
+  const size_t neg = punct(4, "-") ? 1 : 0;
+  if (peek(at + 4 + neg).kind != Token::Int || !punct(5 + neg, ")")) return 0;
+  for (const char *mul : {"*", "***", "/", "%"})
+    if (punct(6 + neg, mul)) return 0;  // rotate(..) *** z binds tighter than the sum
+  id = peek(at + 2).text;
+  steps = neg ? -(int)peek(at + 4 + neg).value : (int)peek(at + 4 + neg).value;
+  return 6 + neg;
+}
+
 std::unique_ptr<AbstractValue> CircuitRuntime::additive() {
   auto lhs = multiplicative();
   while (peek().kind == Token::Punct && (peek().text == "+" || peek().text == "-" || peek().text == "+++" || peek().text == "---")) {
     const std::string op = next().text;
+    // lhs + rotate(v, k) on a ciphertext that offers RotateAddCapable: one fused operation instead of rotateRows + add_inplace
+    if (op == "+" || op == "+++") {
+      std::string id;
+      int steps = 0;
+      auto fused = isCiphertext(lhs.get()) ? dynamic_cast<RotateAddCapable *>(lhs.get()) : nullptr;
+      const size_t span = fused ? plainRotateCall(0, id, steps) : 0;
+      auto it = span ? vars.find(id) : vars.end();
+      if (it != vars.end() && it->second.secret) {
+        pos += span;
+        fused->addRotatedInplace(*it->second.ctxt, steps);
+        continue;
+      }
+    }
     lhs = binary(op, std::move(lhs), multiplicative());
   }
   return lhs;

@@ -90,6 +90,7 @@ class CircuitRuntime {
   std::unique_ptr<AbstractValue> expression();
   std::unique_ptr<AbstractValue> relational();
   std::unique_ptr<AbstractValue> additive();
+  size_t plainRotateCall(size_t at, std::string &id, int &steps) const;
   std::unique_ptr<AbstractValue> multiplicative();
   std::unique_ptr<AbstractValue> primary();
   std::unique_ptr<AbstractValue> binary(const std::string &op, std::unique_ptr<AbstractValue> lhs,

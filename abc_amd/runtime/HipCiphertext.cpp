@@ -229,6 +229,21 @@ void HipCiphertext::rotateRowsInplace(int steps) {
   adopt(std::move(t));
 }
 
+void HipCiphertext::addRotatedInplace(const AbstractCiphertext &src, int steps) {
+  const HipCiphertext &s = cast(src);
+  const auto &f = getFactory();
+  if (!f.fusesRotateAdd() || s.nl != nl) {  // the two calls: they also bring operands at different levels together
+    auto r = s.rotateRows(steps);
+    addInplace(*r);
+    return;
+  }
+  if (f.isCkks()) checkScales(sc, s.sc);
+  auto t = allocate(f, nl);  // never the own buffer: `x +++ rotate(x, k)` would rotate in place, which no key switch gathers from
+  abcHipCheck(abc_hip_rotate_add(f.context(), s.in(), in(), t->p, nl, steps, f.batchSize()), "rotate_add");
+  f.countFusedRotateAdd();
+  adopt(std::move(t));
+}
+
 // ---- ctxt-plain ----
 std::unique_ptr<AbstractCiphertext> HipCiphertext::addPlain(const ICleartext &operand) const {
   auto r = clone_impl();

@@ -12,8 +12,9 @@
 #include "plugin_api.hpp"
 
 #include "HipCiphertextFactory.hpp"
+#include "RotateAddCapable.hpp"
 
-class HipCiphertext : public AbstractCiphertext {
+class HipCiphertext : public AbstractCiphertext, public RotateAddCapable {
   // Device buffer [B][2][L][N] (B = the factory's batch size, 1 by default), shared copy-on-write: clone() and the
   // copy constructor only take another reference (the interpreter clones on EVERY variable read,
   // src/runtime/RuntimeVisitor.cpp:431-437, and most clones are only ever read), and an in-place operation on a shared
@@ -85,6 +86,11 @@ class HipCiphertext : public AbstractCiphertext {
   void subtractPlainInplace(const ICleartext &operand) override;
   std::unique_ptr<AbstractCiphertext> rotateRows(int steps) const override;
   void rotateRowsInplace(int steps) override;
+  // RotateAddCapable: *this += rotate(src, steps) as one abc_hip_rotate_add into a fresh buffer (so that the key switch can take
+  // this value as one more operand: the call fuses only when its output is not the rotated input).  Levels, scales and factories
+  // are checked as addInplace checks them; operands at different levels, and a factory with fuseRotateAdd off, take rotateRows +
+  // addInplace.
+  void addRotatedInplace(const AbstractCiphertext &src, int steps) override;
   std::unique_ptr<AbstractCiphertext> clone() const override;
 
   void add_inplace(const AbstractValue &other) override;

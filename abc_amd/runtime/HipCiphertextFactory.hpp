@@ -31,6 +31,9 @@ struct HipSchemeConfig {
   size_t batch = 1;
   // CKKS slot codec on the host (CkksEncoder.hpp) instead of the device (abc_hip_ckks_encode / _decode): for A/B runs
   bool hostCkksCodec = false;
+  // `lhs +++ rotate(v, k)` as one abc_hip_rotate_add (HipCiphertext::addRotatedInplace); off: rotateRows + addInplace, for A/B
+  // runs and so that a test can compare both paths in one process
+  bool fuseRotateAdd = true;
 };
 
 class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapable {
@@ -62,6 +65,8 @@ class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapab
   uint64_t plainModulus = 0;    // BFV t (0 for CKKS)
   CkksEncoder ckksEncoder;    // host twin of the device codec (HipSchemeConfig::hostCkksCodec)
   bool hostCkksCodec = false;
+  bool fuseRotateAdd = true;
+  mutable size_t fusedRotateAdds = 0;  // abc_hip_rotate_add calls issued by addRotatedInplace
   struct CachedCkksPlain {
     std::vector<double> values;
     int level;
@@ -93,6 +98,10 @@ class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapab
   [[nodiscard]] size_t ciphertextWords() const { return batch * 2 * limbs * ciphertextSlotSize; }  // of one (batched) value
   [[nodiscard]] size_t ciphertextWords(int level) const { return batch * 2 * (size_t)level * ciphertextSlotSize; }
   [[nodiscard]] bool isCkks() const { return ckksMode; }
+  [[nodiscard]] bool fusesRotateAdd() const { return fuseRotateAdd; }
+  void setFuseRotateAdd(bool on) { fuseRotateAdd = on; }
+  [[nodiscard]] size_t fusedRotateAddCalls() const { return fusedRotateAdds; }
+  void countFusedRotateAdd() const { ++fusedRotateAdds; }
   [[nodiscard]] double defaultScale() const { return ckksScale; }
   // CKKS: largest relative difference between the scales of two addends that is drift, not a mismatch
   [[nodiscard]] double scaleTolerance() const { return ckksScaleTol; }

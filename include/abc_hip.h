@@ -73,6 +73,7 @@ int abc_hip_ctx_reload_env(abc_hip_ctx *ctx);
 #define ABC_HIP_ROUTE_ROTATE 2    /* one Galois element */
 #define ABC_HIP_ROUTE_RESCALE 3
 #define ABC_HIP_ROUTE_MULTIPLY 4
+#define ABC_HIP_ROUTE_ROTATE_ADD 5 /* one Galois element plus a second ciphertext; in_place: d_out aliases d_in */
 int abc_hip_route(abc_hip_ctx *ctx, int op, int nl, size_t count, int in_place, char *buf, size_t cap);
 
 /* ---- device memory (so that FFI callers need no HIP runtime binding) ----
@@ -204,6 +205,22 @@ int abc_hip_apply_galois_hoisted(abc_hip_ctx *ctx, const uint64_t *d_in, uint64_
  * ("Galois key not present"): a NAF chain is sequential and has nothing to hoist. */
 int abc_hip_rotate_hoisted(abc_hip_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, int nl, const int *h_steps, int n_steps,
                            size_t count);
+/* Evaluator::rotate_rows (SealCiphertext.cpp:55,60) followed by Evaluator::add (:92,114) as one call:
+ * d_out = d_addend + rotate(d_in, steps); all three [count][2][nl][N].  Bit-identical to abc_hip_rotate into a temporary followed by
+ * abc_hip_add, under every aliasing of the three pointers.  Where the route allows it (abc_hip_route, ABC_HIP_ROUTE_ROTATE_ADD:
+ * a folded rotation of the split sequences with d_out != d_in) the addend is one more operand of the key switch's last kernel;
+ * otherwise the rotation lands in an arena and the add kernel follows.  Step 0: d_addend + d_in.  A step without a key of its
+ * own runs its NAF chain as abc_hip_rotate does; only the last hop can take the addend.  Errors are those of abc_hip_rotate, found
+ * before anything is written.  Capturable, under the "run once eagerly first" rule of abc_hip_graph_begin. */
+int abc_hip_rotate_add(abc_hip_ctx *ctx, const uint64_t *d_in, const uint64_t *d_addend, uint64_t *d_out, int nl, int steps,
+                       size_t count);
+/* the same for one Galois element (2N - 1: conjugation / column swap) */
+int abc_hip_apply_galois_add(abc_hip_ctx *ctx, const uint64_t *d_in, const uint64_t *d_addend, uint64_t *d_out, int nl,
+                             uint32_t galois_elt, size_t count);
+/* The rotate-and-sum tree: acc = in; for each step s in order: acc = acc + rotate(acc, s); out = acc.  Every step is checked before
+ * the first launch; the intermediate sums live in arenas and only the last one lands in d_out, which may be d_in.  n_steps == 0
+ * copies.  h_steps is read during the call only.  Capturable like abc_hip_rotate_add. */
+int abc_hip_rotate_sum(abc_hip_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, int nl, const int *h_steps, int n_steps, size_t count);
 /* The three plaintext operations.  d_out may be d_ct (the reference's *_inplace call sites); size = 2 or 3.
  * plain_stride, in words, is the distance from ciphertext i's plaintext to ciphertext i + 1's:
  *   0            one plaintext, broadcast to the batch (d_plain holds N words for BFV, nl * N for CKKS);

@@ -24,6 +24,48 @@ def rand_ct(g, rng, batch, size, nl):
     return g.upload(x), x.nbytes
 
 
+def rotate_add_ab(res, only, rng):
+    """addend + rotate(in, 1) as abc_hip_rotate into a temporary followed by abc_hip_add, against one abc_hip_rotate_add: alternating in
+    one process, five runs each, so that the spread of the separate runs shows (the bar a fused route has to meet: DESIGN.md section 7)"""
+    shapes = [  # tag, context, level or None for L, batches
+        ("ckks14", lambda: capi.Context(capi.CKKS, 16384, capi.create_primes(16384, [50, 40, 40, 40, 50])), (3, 4), (512, 32)),
+        ("ckks15", lambda: capi.Context(capi.CKKS, 32768, capi.create_primes(32768, [50, 40, 40, 50])), (3,), (256, 32)),
+        ("bfv16384", lambda: capi.Context.bfv_default(16384), (None,), (256,)),
+        ("bfv8192", lambda: capi.Context.bfv_default(8192), (None,), (512,)),
+    ]
+    for tag, make, levels, batches in shapes:
+        if only and only not in "%s_rotate_add" % tag and "rotate_add" not in only:  # no entry of this context can match
+            continue
+        g = make()
+        g.keygen(1)
+        for level in levels:
+            nl = level or g.L
+            for B in batches:
+                names = ["%s_L%d_b%d_rotate_add_%s" % (tag, nl, B, kind) for kind in ("separate", "fused")]
+                if not any(only in k for k in names):
+                    continue
+                cb = C.c_size_t(B)
+                a, nb = rand_ct(g, rng, B, 2, nl)
+                b, _ = rand_ct(g, rng, B, 2, nl)
+                tmp, out = g.alloc(nb), g.alloc(nb)
+
+                def separate():
+                    g.op("rotate", a.ptr, tmp.ptr, nl, 1, cb)
+                    g.op("add", b.ptr, tmp.ptr, out.ptr, 2, nl, cb)
+
+                def fused():
+                    g.op("rotate_add", a.ptr, b.ptr, out.ptr, nl, 1, cb)
+                runs = {names[0]: [], names[1]: []}
+                for rep in range(10):  # separate, fused, separate, fused, ...
+                    runs[names[rep & 1]].append(timeit(g, fused if rep & 1 else separate))
+                for k, ms in runs.items():
+                    route = g.route("rotate_add" if k == names[1] else "rotate", nl, B)
+                    res[k] = {"batch": B, "ms": min(ms), "ms_median": sorted(ms)[len(ms) // 2], "ms_runs": ms, "route": route}
+                    print("%-44s %s ms / %d  (%s)" % (k, " ".join("%8.3f" % v for v in ms), B, route), flush=True)
+                del a, b, tmp, out
+        g.close()
+
+
 def main():
     # --only SUBSTRING: the entries whose name contains it (the contexts are still created)
     only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else ""
@@ -164,6 +206,7 @@ def main():
         print("%-40s %8.3f ms (batch 1, HIP graph replay)" % ("bfv%d_mul_relin latency" % n, ms), flush=True)
         del a, b, out, dec, plains
         g.close()
+    rotate_add_ab(res, only, rng)
     os.makedirs("gpurun_out", exist_ok=True)
     json.dump(res, open("gpurun_out/op_bench.json", "w"), indent=1)
 

@@ -102,6 +102,7 @@ class Ckks:
         return list(self.g.download(re, shp, np.float64) + 1j * self.g.download(im, shp, np.float64))
 
 
+FUSED_ROTATE_ADD = False  # --fused-rotate-add: configs 3 and 4 run their rotate-and-sum trees through abc_hip_rotate_add
 GRAPH = {}  # config -> seconds of one recorded-circuit replay (abc_hip_graph_*: the whole circuit as ONE launch)
 
 
@@ -186,11 +187,17 @@ def config3(dev, rank, world, batch, ph):
 
     def circuit():
         g.op("mul_relin", cx.ptr, cy.ptr, m.ptr, 4, cb)
-        g.op("rescale", m.ptr, r.ptr, 2, 4, cb)
+        # fused: r + rotate(r) in one call, ping-ponging two buffers; thirteen steps that start in t end in r
+        cur, oth = (t, r) if FUSED_ROTATE_ADD else (r, t)
+        g.op("rescale", m.ptr, cur.ptr, 2, 4, cb)
         step = n // 4
         while step >= 1:
-            g.op("rotate", r.ptr, t.ptr, 3, step, cb)
-            g.op("add", r.ptr, t.ptr, r.ptr, 2, 3, cb)
+            if FUSED_ROTATE_ADD:
+                g.op("rotate_add", cur.ptr, cur.ptr, oth.ptr, 3, step, cb)
+                cur, oth = oth, cur
+            else:
+                g.op("rotate", r.ptr, t.ptr, 3, step, cb)
+                g.op("add", r.ptr, t.ptr, r.ptr, 2, 3, cb)
             step //= 2
 
     circuit(); g.sync()
@@ -220,9 +227,14 @@ def config4(dev, rank, world, batch, ph):
 
     def circuit():
         g.op("memcpy_d2d", acc.ptr, ct.ptr, C.c_size_t(cnt * 2 * 3 * n * 8))
+        cur, oth = acc, t
         for r in (1, 2, 4, 64, 128, 256):
-            g.op("rotate", acc.ptr, t.ptr, 3, r, cb)
-            g.op("add", acc.ptr, t.ptr, acc.ptr, 2, 3, cb)
+            if FUSED_ROTATE_ADD:  # six steps: the sum ends in acc again
+                g.op("rotate_add", cur.ptr, cur.ptr, oth.ptr, 3, r, cb)
+                cur, oth = oth, cur
+            else:
+                g.op("rotate", acc.ptr, t.ptr, 3, r, cb)
+                g.op("add", acc.ptr, t.ptr, acc.ptr, 2, 3, cb)
 
     circuit(); g.sync()
     t0 = time.perf_counter(); ph.run("t_computation", g, circuit); dt = time.perf_counter() - t0
@@ -325,9 +337,11 @@ def main():
     ap.add_argument("--os-keyed", action="store_true",
                     help="keys and encryption randomness from the OS-keyed entry points (abc_hip_keygen_secure / abc_hip_encrypt_secure) "
                          "instead of the seeded test spec; ABC_HIP_HOST_SAMPLING=1 then draws the same spec with its host twin")
+    ap.add_argument("--fused-rotate-add", action="store_true",
+                    help="configs 3 and 4: each (rotate, add) pair of the tree as one abc_hip_rotate_add call (off: the recorded figures' two calls)")
     args = ap.parse_args()
-    global HOST_CODEC, OS_KEYED
-    HOST_CODEC, OS_KEYED = args.host_codec, args.os_keyed
+    global HOST_CODEC, OS_KEYED, FUSED_ROTATE_ADD
+    HOST_CODEC, OS_KEYED, FUSED_ROTATE_ADD = args.host_codec, args.os_keyed, args.fused_rotate_add
     if args.gpus > 1 and "RANK" not in os.environ:
         # nothing above this line has imported torch or touched HIP: the ranks are fresh processes (abc_amd/launcher.py)
         from abc_amd.launcher import launch_ranks
@@ -348,6 +362,8 @@ def main():
         ph = Phases()
         ok, cnt, dt, digest = fn(dev, rank, world, batch, ph)
         line = {"config": cfg, "rank": rank, "circuits": cnt, "verified": ok, "seconds": dt, "circuits_per_s": cnt / dt}
+        if FUSED_ROTATE_ADD and cfg in (3, 4):
+            line["fused_rotate_add"] = True
         if OS_KEYED:
             line["os_keyed"] = "host sampling" if os.environ.get("ABC_HIP_HOST_SAMPLING", "0") != "0" else "device sampling"
         line.update({k: round(v, 3) for k, v in ph.ms.items()})  # ms, the reference's CSV columns (ref:examples/main.cpp:41)
