@@ -379,9 +379,14 @@ static std::vector<int> naf(int value) {
   return out;
 }
 
-static int keyswitch(abc_hip_ctx *c, const u64 *target, size_t target_stride, const u64 *key, u64 *out2, int nl, size_t count,
-                     const u64 *addend, size_t addend_stride, bool add_c1) {
-  return launch_keyswitch(c, route_keyswitch(c->facts, nl), target, target_stride, key, out2, nl, count, addend, addend_stride, add_c1);
+// the record of a key switch over whole ciphertexts at `ct`, `size` polynomials each: the last one is switched, (c0, c1) -- c0 alone
+// at size 2 -- is the addend
+static KsOperands ks_of_ciphertexts(const abc_hip_ctx *c, const u64 *ct, int size, const u64 *key, u64 *out, int nl, size_t count) {
+  const size_t pw = (size_t)nl * c->n;
+  KsOperands o;
+  o.target = ct + (size - 1) * pw, o.addend = ct, o.target_stride = o.addend_stride = size * pw, o.add_c1 = size == 3;
+  o.key = key, o.out = out, o.nl = nl, o.count = count;
+  return o;
 }
 
 // one Galois element along route r; acc (RotAddRoute::fused only): a second ciphertext added in the key switch's last kernel
@@ -390,17 +395,16 @@ static int apply_galois_routed(abc_hip_ctx *c, const RotRoute &r, const u64 *in,
   auto it = c->d_galois.find(elt);
   if (it == c->d_galois.end()) { set_error("Galois key not present"); return 1; }
   if (!count) return 0;
-  const size_t N = (size_t)c->n, pw = (size_t)nl * N;
-  const bool ntt_form = (c->scheme == ABC_HIP_SCHEME_CKKS);
-  // out = (g(c0) + ks0, ks1) with ks = KeySwitch(g(c1))
-  if (r.fold)  // the permutation is a gather inside the key-switch kernels
-    return launch_keyswitch(c, r.ks, in + pw, 2 * pw, it->second, out, nl, count, in, 2 * pw, false, elt, acc);
-  if (acc) { set_error("apply_galois: a second addend needs the folded permutation"); return 1; }
-  // g(c0), g(c1) live in arena 0 (keyswitch_generic uses c->ws)
-  if (ensure_aux(c, 0, count * 2 * pw * 8)) return 1;
-  u64 *g = (u64 *)c->aux[0];
-  if (launch_galois(c, in, g, nl, count * 2, elt, ntt_form)) return 1;
-  return launch_keyswitch(c, r.ks, g + pw, 2 * pw, it->second, out, nl, count, g, 2 * pw, false);
+  // out = (g(c0) + ks0, ks1) with ks = KeySwitch(g(c1)); r.fold: the permutation is a gather inside the key-switch kernels
+  if (!r.fold) {  // g(c0), g(c1) live in arena 0 (keyswitch_generic uses c->ws)
+    if (ensure_aux(c, 0, count * 2 * (size_t)nl * c->n * 8)) return 1;
+    if (launch_galois(c, in, (u64 *)c->aux[0], nl, count * 2, elt, c->scheme == ABC_HIP_SCHEME_CKKS)) return 1;
+    in = (const u64 *)c->aux[0];
+  }
+  KsOperands o = ks_of_ciphertexts(c, in, 2, it->second, out, nl, count);
+  o.gelt = r.fold ? elt : 0u;
+  o.acc = acc;
+  return launch_keyswitch(c, r.ks, o);
 }
 static int apply_galois(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, uint32_t elt, size_t count) {
   return apply_galois_routed(c, route_rotate(c->facts, nl, in == out), in, out, nl, elt, count);
@@ -437,6 +441,19 @@ static int rotation_terms(abc_hip_ctx *c, int steps, std::vector<int> &terms) {
   return 0;
 }
 
+// hops first .. last - 1 of a rotation from `cur`, ping-ponging through arenas 1 and 2 (apply_galois is out of place): hop i lands in
+// arena 1 + (i & 1); `cur` follows
+static int rotate_hops(abc_hip_ctx *c, const u64 *&cur, int nl, const std::vector<int> &terms, size_t first, size_t last, size_t count) {
+  for (size_t i = first; i < last; i++) {
+    const int which = 1 + (int)(i & 1);
+    if (ensure_aux(c, which, count * 2 * nl * (size_t)c->n * 8)) return 1;
+    u64 *dst = (u64 *)c->aux[which];
+    if (apply_galois(c, cur, dst, nl, elt_from_step(c, terms[i]), count)) return 1;
+    cur = dst;
+  }
+  return 0;
+}
+
 static int rotate(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, int steps, size_t count) {
   const size_t bytes = count * 2 * nl * (size_t)c->n * 8;
   if (steps == 0) {
@@ -445,20 +462,13 @@ static int rotate(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, int steps, si
   }
   std::vector<int> terms;
   if (rotation_terms(c, steps, terms)) return 1;
-  // apply_galois is out of place: ping-pong through arenas 1 and 2, last hop lands in `out`
+  // the last hop lands in `out`, or -- where it would read what it writes -- in the next arena and is copied
   const u64 *cur = in;
-  for (size_t i = 0; i < terms.size(); i++) {
-    const bool last = (i + 1 == terms.size());
-    u64 *dst = out;
-    if (!last || out == cur) {
-      const int which = 1 + (int)(i & 1);
-      if (ensure_aux(c, which, bytes)) return 1;
-      dst = (u64 *)c->aux[which];
-    }
-    if (apply_galois(c, cur, dst, nl, elt_from_step(c, terms[i]), count)) return 1;
-    cur = dst;
-  }
-  if (cur != out) ABC_HIP_CHECK(hipMemcpyAsync(out, cur, bytes, hipMemcpyDeviceToDevice, c->stream));
+  const size_t last = terms.size() - 1;
+  if (rotate_hops(c, cur, nl, terms, 0, last, count)) return 1;
+  if (out != cur) return apply_galois(c, cur, out, nl, elt_from_step(c, terms[last]), count);
+  if (rotate_hops(c, cur, nl, terms, last, last + 1, count)) return 1;
+  ABC_HIP_CHECK(hipMemcpyAsync(out, cur, bytes, hipMemcpyDeviceToDevice, c->stream));
   return 0;
 }
 
@@ -469,16 +479,10 @@ static int rotate_add(abc_hip_ctx *c, const u64 *in, const u64 *addend, u64 *out
   std::vector<int> terms;
   if (rotation_terms(c, steps, terms)) return 1;
   if (!count) return 0;
-  const size_t bytes = count * 2 * nl * (size_t)c->n * 8;
   const u64 *cur = in;
-  for (size_t i = 0; i + 1 < terms.size(); i++) {
-    const int which = 1 + (int)(i & 1);
-    if (ensure_aux(c, which, bytes)) return 1;
-    u64 *dst = (u64 *)c->aux[which];
-    if (apply_galois(c, cur, dst, nl, elt_from_step(c, terms[i]), count)) return 1;
-    cur = dst;
-  }
-  return apply_galois_add(c, cur, addend, out, nl, elt_from_step(c, terms.back()), count, 1 + (int)((terms.size() - 1) & 1));
+  const size_t last = terms.size() - 1;
+  if (rotate_hops(c, cur, nl, terms, 0, last, count)) return 1;
+  return apply_galois_add(c, cur, addend, out, nl, elt_from_step(c, terms[last]), count, 1 + (int)(last & 1));
 }
 
 // acc = in; acc = acc + rotate(acc, s) for each step in order; out = acc.  The running sums ping-pong through arenas 3 and 4
@@ -533,7 +537,7 @@ static int hoisted(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, const std::v
       ABC_HIP_CHECK(hipMemcpyAsync(slab, in, ctw * 8, hipMemcpyDeviceToDevice, c->stream));
       continue;
     }
-    if (keyswitch(c, in + pw, 2 * pw, keys[r], ks, nl, count, in, 2 * pw, false)) return 1;
+    if (launch_keyswitch(c, route_keyswitch(c->facts, nl), ks_of_ciphertexts(c, in, 2, keys[r], ks, nl, count))) return 1;
     if (launch_galois(c, ks, slab, nl, count * 2, elts[r], ntt_form)) return 1;
   }
   return 0;
@@ -541,9 +545,8 @@ static int hoisted(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, const std::v
 
 static int relinearize(abc_hip_ctx *c, const u64 *ct3, u64 *out2, int nl, size_t count) {
   if (!c->d_relin) { set_error("relinearize: no relinearisation key"); return 1; }
-  const size_t pw = (size_t)nl * c->n;
   // target = c2 (poly 2 of each size-3 ciphertext); addend = (c0, c1)
-  return keyswitch(c, ct3 + 2 * pw, 3 * pw, c->d_relin, out2, nl, count, ct3, 3 * pw, true);
+  return launch_keyswitch(c, route_keyswitch(c->facts, nl), ks_of_ciphertexts(c, ct3, 3, c->d_relin, out2, nl, count));
 }
 
 }  // namespace abc
@@ -989,8 +992,7 @@ int abc_hip_mul_relin(abc_hip_ctx *c, const uint64_t *a, const uint64_t *b, uint
   if (ensure_aux(c, 1, bytes ? bytes : 8)) return 1;
   u64 *t3 = (u64 *)c->aux[1];
   int rc = (c->scheme == ABC_HIP_SCHEME_CKKS) ? launch_ckks_tensor(c, a, b, t3, nl, count) : bfv_multiply(c, r.mul, a, b, t3, count);
-  const size_t pw = (size_t)nl * c->n;  // target = c2, addend = (c0, c1), as in relinearize
-  if (!rc) rc = launch_keyswitch(c, r.ks, t3 + 2 * pw, 3 * pw, c->d_relin, out, nl, count, t3, 3 * pw, true);
+  if (!rc) rc = launch_keyswitch(c, r.ks, ks_of_ciphertexts(c, t3, 3, c->d_relin, out, nl, count));  // as in relinearize
   return rc;
 }
 int abc_hip_rotate(abc_hip_ctx *c, const uint64_t *in, uint64_t *out, int nl, int steps, size_t count) {
@@ -1113,7 +1115,9 @@ int abc_hip_keyswitch(abc_hip_ctx *c, const uint64_t *target, uint32_t key_kind,
   if (key_kind == 0) key = c->d_relin;
   else if (c->d_galois.count(key_kind)) key = c->d_galois[key_kind];
   if (!key) { set_error("keyswitch: key not present"); return 1; }
-  return keyswitch(c, target, (size_t)nl * c->n, key, out2, nl, count, nullptr, 0, false);
+  KsOperands o;  // one polynomial per ciphertext, no addend
+  o.target = target, o.target_stride = (size_t)nl * c->n, o.key = key, o.out = out2, o.nl = nl, o.count = count;
+  return launch_keyswitch(c, route_keyswitch(c->facts, nl), o);
 }
 
 // ---- graph capture ----

@@ -232,6 +232,36 @@ inline unsigned grid_for(size_t items, int block) {
     if ((c)->buffers.capturing) { abc::set_error(what ": not capturable (host transfer / synchronisation inside abc_hip_graph_begin..end)"); return 1; } \
   } while (0)
 
+// One key switch as every layer from the C ABI to the launch passes it on: out[ct] = KeySwitch(target[ct]) (+ addend[ct]) (+ acc[ct])
+// for `count` ciphertexts of nl limbs.  mode 0 is the CKKS multiply + relinearise of the split sequences: target / addend are the
+// factors a / b, both [2][nl][N] per ciphertext.
+struct KsOperands {
+  int mode = 1;  // 0 multiply, 1 key switch (dispatch_mode)
+  // target: the polynomial to switch, [nl][N] at target + ct * target_stride, in the ciphertext's own form (BFV coefficient, CKKS NTT);
+  // addend: (c0, c1) -- c0 alone unless add_c1 -- at addend + ct * addend_stride, added to the result, or null
+  const u64 *target = nullptr, *addend = nullptr;
+  size_t target_stride = 0, addend_stride = 0;
+  bool add_c1 = false;
+  const u64 *key = nullptr;  // the key-switching key
+  u64 *out = nullptr;        // [count][2][nl][N]
+  const u64 *acc = nullptr;  // with gelt only: a second, ungathered ciphertext [count][2][nl][N] added in the last kernel (RotAddRoute::fused)
+  u32 gelt = 0;              // the Galois element of a rotation folded into the sequence (RotRoute::fold): target = c1, addend = c0
+  u32 gather = 0;            // what the kernels gather with: gelt (CKKS, NTT form) or gelt^-1 mod 2N (BFV); launch_keyswitch fills it
+  int nl = 0;
+  size_t count = 0;
+  // the record of ciphertexts off .. off + cc - 1: the one place a chunk's pointers are computed
+  KsOperands slice(size_t off, size_t cc, size_t N) const {
+    const size_t ctw = 2 * (size_t)nl * N;
+    KsOperands s = *this;
+    s.target = target + off * target_stride;
+    if (addend) s.addend = addend + off * addend_stride;
+    s.out = out + off * ctw;
+    if (acc) s.acc = acc + off * ctw;
+    s.count = cc;
+    return s;
+  }
+};
+
 // ---- abc_buffers.hip: every allocation a recorded circuit may read, and the bodies of the C entry points of that name ----
 int buffer_malloc(abc_hip_ctx *c, void **d_ptr, size_t bytes);
 int buffer_free(abc_hip_ctx *c, void *d_ptr);
@@ -265,8 +295,7 @@ int big_block_log(void);
 
 int launch_addsub(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out, int nl, size_t polys, int op);  // 0 add 1 sub 2 neg
 int launch_ckks_tensor(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out3, int nl, size_t count);
-int keyswitch_generic(abc_hip_ctx *c, KsFront front, const u64 *target, size_t target_stride, const u64 *key, u64 *out2, int nl,
-                      size_t count, const u64 *addend, size_t addend_stride, bool add_c1, u32 ginv = 0);
+int keyswitch_generic(abc_hip_ctx *c, KsFront front, const KsOperands &o);
 int launch_ks_tmod(abc_hip_ctx *c, const u64 *prodS, u64 *tmod, int nl, size_t polys);
 int launch_ks_finish(abc_hip_ctx *c, const u64 *prodD, const u64 *tmod, u64 *out, const u64 *addend, size_t addend_stride,
                      bool add_c1, int nl, size_t count);
@@ -302,38 +331,26 @@ int keygen_keyed(abc_hip_ctx *c, const uint8_t key_sec[32], const uint8_t key_pu
 int keyed_small(abc_hip_ctx *c, const uint8_t key[32], uint64_t nonce, int8_t *d_small, size_t count);
 int keyed_uniform(abc_hip_ctx *c, const uint8_t key[32], uint64_t stream, int nkeys, u64 *d_a);
 
-// the key switch of route r (abc_kernels_fused.hip; any sequence); gelt: the Galois element of a rotation folded into it
-// (RotRoute::fold), with target = c1, addend = c0 of the ciphertext; acc: a second ciphertext [count][2][nl][N] added in the last
-// kernel (RotAddRoute::fused: only with gelt, only the sequences route_rotate_add names)
-int launch_keyswitch(abc_hip_ctx *c, const KsRoute &r, const u64 *target, size_t target_stride, const u64 *key, u64 *out2, int nl, size_t count,
-                     const u64 *addend, size_t addend_stride, bool add_c1, u32 gelt = 0, const u64 *acc = nullptr);
+// the key switch o along route r (abc_kernels_fused.hip; any sequence).  o.gelt and o.acc are checked here, once, against what the
+// sequence can do (seq_folds_permutation, seq_takes_acc); the sequences below check nothing again
+int launch_keyswitch(abc_hip_ctx *c, const KsRoute &r, const KsOperands &o);
 // CKKS multiply + relinearise in one sequence (every Seq but bmul and generic)
 int launch_mul_relin(abc_hip_ctx *c, Seq seq, const u64 *a, const u64 *b, u64 *out, int nl, size_t count);
 // split key switch without LDS-resident limbs (abc_kernels_gsplit.hip): N = 2^15, and the first step at N = 2^14 for small batches
 size_t gsplit_scratch_words(const abc_hip_ctx *c, int nl);
-int gsplit_chunk15(abc_hip_ctx *c, hipStream_t st, u64 *scratch, size_t cc, int nl, int mode, const u64 *opa, const u64 *opb,
-                   size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt, const u64 *acc = nullptr);
-void gsplit_front14(hipStream_t st, abc_hip_ctx *c, size_t cc, int nl, int mode, const u64 *opa, const u64 *opb, size_t opa_stride,
-                    double *hinv, double *part, u32 gelt, int pack = 0);
+int gsplit_chunk15(abc_hip_ctx *c, hipStream_t st, u64 *scratch, const KsOperands &o);  // o: one chunk
+void gsplit_front14(hipStream_t st, abc_hip_ctx *c, const KsOperands &o, double *hinv, double *part, int pack);
 // ---- the main step of the split key switch (k_split4_main_fp, k_gsplit_main[_deep], k_isplit_main[_deep]): host side ----
 // its arguments, as the launchers pass them along (the kernels' own argument lists are spelled once, at the launch)
-struct MainArgs {
-  hipStream_t st;
-  size_t cc;  // ciphertexts in the chunk
-  int nl;
-  const void *part, *tpart;  // half-done decomposition / mod-down limbs (doubles or u64: the arithmetic of the kernel)
-  const u64 *opa, *opb;      // mode 0: a, b; mode 1: operand in NTT form, addend (or null)
-  size_t opa_stride, opb_stride;
-  int add_c1;
-  const u64 *key;
-  u64 *out;
-  u32 gelt;
-  u64 imap;  // nibble s = data prime of grid slot s (kAllSlots with ni = nl: all of them; the 512-thread kernels read eight nibbles)
-  int ni;    // slots
-  int pack;  // the half-done limbs are packed (abc_ntt.hpp; k_split4_main_fp only)
-  const u64 *acc = nullptr;  // mode 1 with gelt: a second, ungathered ciphertext [cc][2][nl][N] to add (RotAddRoute::fused), or null
-};
 constexpr u64 kAllSlots = 0xfedcba9876543210ull;
+struct MainArgs {
+  hipStream_t st = nullptr;
+  KsOperands ops;                                // the chunk
+  const void *part = nullptr, *tpart = nullptr;  // half-done decomposition / mod-down limbs (doubles or u64: the arithmetic of the kernel)
+  u64 imap = kAllSlots;  // nibble s = data prime of grid slot s (kAllSlots with ni = nl: all of them; the 512-thread kernels read eight nibbles)
+  int ni = 0;            // slots
+  int pack = 0;          // the half-done limbs are packed (abc_ntt.hpp; k_split4_main_fp only)
+};
 // The last kernels of the split key switches take the second addend of rotate_add as a trailing template parameter PACK: empty
 // for every instantiation that existed (same name, same argument list, same code), <.., WithAcc> with one more argument, the
 // pointer, for the fused form.
@@ -346,7 +363,7 @@ __host__ __device__ inline const u64 *acc_ptr() { return nullptr; }
 __host__ __device__ inline const u64 *acc_ptr(AccArg<WithAcc> a) { return a.p; }
 // nl + 1 transform buffers + the block's twiddle table, 1024 entries of tw_bytes = sizeof(A::TW): 8 (fp64) or 16 (integer)
 constexpr size_t main_lds_bytes(int nl, int tw_bytes) { return (size_t)((nl + 1) * lds_words(10)) * 8 + 1024 * (size_t)tw_bytes; }
-// (mode, gelt) -> f(MODE, GAL) as integral constants: multiply / key switch with the Galois gather folded in / plain key switch
+// (o.mode, o.gather) -> f(MODE, GAL) as integral constants: multiply / key switch with the Galois gather folded in / plain key switch
 template <class Fn>
 inline void dispatch_mode(int mode, u32 gelt, Fn f) {
   if (mode == 0) f(std::integral_constant<int, 0>{}, std::false_type{});
@@ -375,14 +392,13 @@ inline void dispatch_nl(int nl, Fn f) {
 }
 // over the slots of a.imap: all data primes, or the fp64-capable ones of a mixed chain (abc_kernels_isplit.hip).
 // split4_main (N = 2^14): false = not applicable (more than seven limbs); gsplit_main15: any nl <= 15 (above seven: the deep kernel)
-bool split4_main(abc_hip_ctx *c, int mode, const MainArgs &a);
-void gsplit_main15(abc_hip_ctx *c, int mode, const MainArgs &a);
-int bsplit_big(abc_hip_ctx *c, const u64 *target, size_t target_stride, const u64 *key, u64 *out, int nl, size_t count, const u64 *addend,
-               size_t addend_stride, bool add_c1, u32 ginv = 0, const u64 *acc = nullptr);
-int bsplit_back14(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const double *part, double *half, const u64 *key, const u64 *addend,
-                  size_t addend_stride, int add_c1, u64 *out, u32 ginv = 0, const u64 *acc = nullptr);
-int bsplit_back13(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const double *part, double *half, const u64 *key, const u64 *addend,
-                  size_t addend_stride, int add_c1, u64 *out, u32 ginv = 0);
+bool split4_main(abc_hip_ctx *c, const MainArgs &a);
+void gsplit_main15(abc_hip_ctx *c, const MainArgs &a);
+int bsplit_big(abc_hip_ctx *c, const KsOperands &o);
+// BFV, N = 2^LOGN (13, 14): the steps behind a `part` already written, on one chunk; reads o's key, addend, out, gather, acc
+// (N = 2^14 only)
+template <int LOGN>
+int bsplit_back(abc_hip_ctx *c, hipStream_t st, const double *part, double *half, const KsOperands &o);
 // the mirrors of a key-switching key (nullptr: not available -- capture in progress and not built yet, or allocation failed)
 const double *key_twin(abc_hip_ctx *c, const u64 *key);
 const double *key_twin_lookup(const abc_hip_ctx *c, const u64 *key);  // never builds: safe once the lanes have forked
@@ -468,7 +484,6 @@ int bmul_split(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out, size_t coun
 int bmul_big(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out3, size_t count);                 // BfvMul::big
 // integer twins of the split kernels (abc_kernels_isplit.hip)
 size_t isplit_scratch_words(const abc_hip_ctx *c, int nl);
-int isplit_chunk(abc_hip_ctx *c, hipStream_t st, u64 *scratch, size_t cc, int nl, int mode, const u64 *opa, const u64 *opb,
-                 size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt, const ChunkRoute &k);
+int isplit_chunk(abc_hip_ctx *c, hipStream_t st, u64 *scratch, const KsOperands &o, const ChunkRoute &k);  // o: one chunk
 
 }  // namespace abc

@@ -492,18 +492,21 @@ int bmul_split(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out, size_t coun
     double *X = (double *)scratch, *Y = X + cc * Xw;
     const u64 *pa = a + off * 2 * L * N, *pb = b + off * 2 * L * N;
     u64 *po = out + off * (relin ? 2 : 3) * L * N;
+    // the key switch behind the product: k_bmul_back left (c0, c1) in po, which is addend and output at once
+    KsOperands ks;
+    ks.addend = ks.out = po, ks.addend_stride = 2 * (size_t)L * N, ks.add_c1 = true, ks.key = c->d_relin, ks.nl = L, ks.count = cc;
     if (n13) {  // four data limbs, eight blocks (reached with relin only: the plain multiply of this ring is bmul_big's)
       hipLaunchKernelGGL((k_bmul_front<13, 3, 4, 4>), dim3((unsigned)(cc * 4 * 16)), dim3(512), lds, st, c->dc, pa, pb, X);
       hipLaunchKernelGGL((k_bmul_mid<13, 10>), dim3((unsigned)(cc * nlm * 8)), dim3(256), (size_t)(4 * lds_words(10)) * 8, st, c->dc, (const double *)X, Y, nlm, L);
       hipLaunchKernelGGL((k_bmul_back<13, 3, 4, 4>), dim3((unsigned)(cc * 3 * 16)), dim3(512), lds, st, c->dc, (const double *)Y, po, X, 0);
       ABC_HIP_CHECK(hipGetLastError());
-      return bsplit_back13(c, st, cc, L, (const double *)X, Y, c->d_relin, po, 2 * (size_t)L * N, 1, po);
+      return bsplit_back<13>(c, st, (const double *)X, Y, ks);
     }
     hipLaunchKernelGGL((k_bmul_front<14, 4, 8, 8>), dim3((unsigned)(cc * 4 * 32)), dim3(512), lds, st, c->dc, pa, pb, X);
     hipLaunchKernelGGL((k_bmul_mid<14, 10>), dim3((unsigned)(cc * nlm * 16)), dim3(256), (size_t)(4 * lds_words(10)) * 8, st, c->dc, (const double *)X, Y, nlm, L);
     hipLaunchKernelGGL((k_bmul_back<14, 4, 8, 8>), dim3((unsigned)(cc * 3 * 32)), dim3(512), lds, st, c->dc, (const double *)Y, po, X, relin ? 0 : 1);
     ABC_HIP_CHECK(hipGetLastError());
-    return relin ? bsplit_back14(c, st, cc, L, (const double *)X, Y, c->d_relin, po, 2 * (size_t)L * N, 1, po) : 0;
+    return relin ? bsplit_back<14>(c, st, (const double *)X, Y, ks) : 0;
   });
 }
 

@@ -170,7 +170,7 @@ static int launch_divround_tmod(abc_hip_ctx *c, const u64 *last, u64 *tmod, int 
 static int launch_divround_finish(abc_hip_ctx *c, const u64 *in, int in_limbs, const u64 *tmod, u64 *out, const u64 *inv, const u64 *inv_s,
                                   const u64 *addend, size_t addend_stride, bool add_c1, int nrem, size_t polys) {
   hipLaunchKernelGGL(k_divround_finish, dim3(grid_for(polys * nrem * (size_t)c->n, 256)), dim3(256), 0, c->stream, c->dc, in, in_limbs,
-                     tmod, out, inv, inv_s, addend, addend_stride, add_c1 ? 1 : 0, nrem, polys);
+                     tmod, out, inv, inv_s, addend, addend_stride, (int)add_c1, nrem, polys);
   ABC_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -391,15 +391,12 @@ __global__ __launch_bounds__(256) void k_iks_finish(DevCtx c, const u64 *__restr
     }
   }
 }
-static int iks_finish(abc_hip_ctx *c, const u64 *prodD, const u64 *prodS, const u64 *addend, size_t addend_stride, bool add_c1, u64 *out,
-                      int nl, size_t cc, u32 ginv) {
+static int iks_finish(abc_hip_ctx *c, const u64 *prodD, const u64 *prodS, const KsOperands &o) {
   const int S0 = c->logn - big_block_log();
   const int G = c->n >> S0;
-  const dim3 grid((unsigned)(cc * 2 * (G / 256)));
-  if (S0 == 3)
-    hipLaunchKernelGGL(k_iks_finish<3>, grid, dim3(256), 0, c->stream, c->dc, prodD, prodS, addend, addend_stride, add_c1 ? 1 : 0, out, nl, ginv);
-  else
-    hipLaunchKernelGGL(k_iks_finish<4>, grid, dim3(256), 0, c->stream, c->dc, prodD, prodS, addend, addend_stride, add_c1 ? 1 : 0, out, nl, ginv);
+  const dim3 grid((unsigned)(o.count * 2 * (G / 256)));
+  hipLaunchKernelGGL((S0 == 3 ? k_iks_finish<3> : k_iks_finish<4>), grid, dim3(256), 0, c->stream, c->dc, prodD, prodS, o.addend, o.addend_stride,
+                     o.add_c1, o.out, o.nl, o.gather);
   ABC_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -436,12 +433,13 @@ static int iks_front(abc_hip_ctx *c, const u64 *tc, size_t tcs, const u64 *key, 
   return 0;
 }
 
-int keyswitch_generic(abc_hip_ctx *c, KsFront front, const u64 *target, size_t target_stride, const u64 *key, u64 *out2, int nl, size_t count,
-                      const u64 *addend, size_t addend_stride, bool add_c1, u32 ginv) {
+// o.gather: BFV with front == iks only (seq_folds_permutation)
+int keyswitch_generic(abc_hip_ctx *c, KsFront front, const KsOperands &all) {
+  const size_t count = all.count, N = (size_t)c->n;
+  const int nl = all.nl;
+  const u64 *key = all.key;
   if (!count) return 0;
   const bool ckks = (c->scheme == 2);
-  if (ginv && (front != KsFront::iks || ckks)) { set_error("keyswitch_generic: a folded permutation needs the fused integer sequence"); return 1; }
-  const size_t N = (size_t)c->n;
   // workspace per ciphertext (words): tcoef nl + dec nl(nl+1) + prodD 2nl + prodS 2 + tmod 2nl
   const size_t per_ct = ((size_t)nl + (size_t)nl * (nl + 1) + 2 * nl + 2 + 2 * nl) * N;
   const size_t chunk = even_chunks((size_t)(c->logn > 14 ? 4 : 1) << 30, per_ct, count);  // <= 1 GiB of scratch per chunk (big rings: 4 GiB)
@@ -456,11 +454,11 @@ int keyswitch_generic(abc_hip_ctx *c, KsFront front, const u64 *target, size_t t
   smap.id[0] = c->K - 1;
   for (size_t off = 0; off < count; off += chunk) {
     const size_t cc = (count - off < chunk) ? count - off : chunk;
-    const u64 *tg = target + off * target_stride;
-    const u64 *tc = tg;
-    size_t tcs = target_stride;
+    const KsOperands o = all.slice(off, cc, N);
+    const u64 *tc = o.target;
+    size_t tcs = o.target_stride;
     if (ckks) {  // CKKS targets are in NTT form: back to coefficients first
-      ABC_HIP_CHECK(hipMemcpy2DAsync(tcoef, nl * N * 8, tg, target_stride * 8, nl * N * 8, cc, hipMemcpyDeviceToDevice,
+      ABC_HIP_CHECK(hipMemcpy2DAsync(tcoef, nl * N * 8, o.target, o.target_stride * 8, nl * N * 8, cc, hipMemcpyDeviceToDevice,
                                      c->stream));
       if (launch_ntt_inv(c, tcoef, dmap, nl, cc * nl)) return 1;
       tc = tcoef;
@@ -468,10 +466,9 @@ int keyswitch_generic(abc_hip_ctx *c, KsFront front, const u64 *target, size_t t
     }
     if (front == KsFront::fp && launch_ks_expand_ntt_fp(c, tc, tcs, dec, dmap, nl, cc)) return 1;
     const bool iks = front == KsFront::iks;
-    if (iks && iks_front(c, tc, tcs, key, dec, prodD, prodS, nl, cc, ginv, c->facts.guard)) return 1;
+    if (iks && iks_front(c, tc, tcs, key, dec, prodD, prodS, nl, cc, o.gather, c->facts.guard)) return 1;
     if (iks && !ckks) {  // inner products done, block stages of the inverse transforms too: one kernel does the rest
-      if (iks_finish(c, prodD, prodS, addend ? addend + off * addend_stride : nullptr, addend_stride, add_c1, out2 + off * 2 * nl * N, nl, cc, ginv))
-        return 1;
+      if (iks_finish(c, prodD, prodS, o)) return 1;
       continue;
     }
     if (iks) {  // CKKS: the special limb's strided stages (integers, like its block stages: k_iks_special), then as ever
@@ -495,9 +492,7 @@ int keyswitch_generic(abc_hip_ctx *c, KsFront front, const u64 *target, size_t t
         if (launch_ntt_inv(c, prodD, dmap, nl, cc * 2 * nl)) return 1;
       }
     }
-    if (launch_ks_finish(c, prodD, tmod, out2 + off * 2 * nl * N, addend ? addend + off * addend_stride : nullptr, addend_stride,
-                         add_c1, nl, cc))
-      return 1;
+    if (launch_ks_finish(c, prodD, tmod, o.out, o.addend, o.addend_stride, o.add_c1, nl, cc)) return 1;
   }
   return 0;
 }

@@ -825,15 +825,16 @@ __global__ __launch_bounds__(NL ? (NL + 1) * 64 : 832) void k_split3_main_fp(Dev
 
 template <int MODE, bool GAL>
 static void launch_split3_main(abc_hip_ctx *c, const MainArgs &a) {
-  const int nl = a.nl;
-  const dim3 grid((unsigned)(a.cc * nl * 16)), block(64 * (nl + 1));
+  const KsOperands &o = a.ops;
+  const int nl = o.nl;
+  const dim3 grid((unsigned)(o.count * nl * 16)), block(64 * (nl + 1));
   const size_t lds = (size_t)((nl + 1) * lds_words(10)) * 8;
   if constexpr (MODE == 1 && GAL) {
-    if (a.acc) {
+    if (o.acc) {
 #define ABC_TM3A(NLV)                                                                                                                  \
   hipLaunchKernelGGL((k_split3_main_fp<1, true, NLV, WithAcc>), grid, block, lds, a.st, c->dc, (const double *)a.part,               \
-                     (const double *)a.tpart, a.opa, a.opb, a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, nl, a.gelt,          \
-                     AccArg<WithAcc>{a.acc})
+                     (const double *)a.tpart, o.target, o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, nl,      \
+                     o.gather, AccArg<WithAcc>{o.acc})
       switch (nl) {
         case 1: ABC_TM3A(1); break;
         case 2: ABC_TM3A(2); break;
@@ -847,7 +848,7 @@ static void launch_split3_main(abc_hip_ctx *c, const MainArgs &a) {
   }
 #define ABC_TM3(NLV)                                                                                                             \
   hipLaunchKernelGGL((k_split3_main_fp<MODE, GAL, NLV>), grid, block, lds, a.st, c->dc, (const double *)a.part, (const double *)a.tpart, \
-                     a.opa, a.opb, a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, nl, a.gelt)
+                     o.target, o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, nl, o.gather)
   switch (nl) {
     case 1: ABC_TM3(1); break;
     case 2: ABC_TM3(2); break;
@@ -1119,28 +1120,29 @@ __global__ __launch_bounds__(512, HALVES ? 6 : NL <= 4 ? 4 : 2) void k_split4_ma
   else compute_pair(e0, ops, std::false_type{});
 }
 
-// over the slots of a.imap; mode 0 multiply, mode 1 key switch
-bool split4_main(abc_hip_ctx *c, int mode, const MainArgs &a) {
-  if (a.nl < 1 || a.nl > 7) return false;  // nl + 1 transform buffers of 8.5 KiB + the 8 KiB table: LDS allows two workgroups per CU up to nl = 7
+// over the slots of a.imap
+bool split4_main(abc_hip_ctx *c, const MainArgs &a) {
+  const KsOperands &o = a.ops;
+  if (o.nl < 1 || o.nl > 7) return false;  // nl + 1 transform buffers of 8.5 KiB + the 8 KiB table: LDS allows two workgroups per CU up to nl = 7
   if (a.ni == 0) return true;
-  const dim3 grid((unsigned)(a.cc * a.ni * 16)), block(512);
-  const double *keyf = key_twin_lookup(c, a.key);
+  const dim3 grid((unsigned)(o.count * a.ni * 16)), block(512);
+  const double *keyf = key_twin_lookup(c, o.key);
   // a.part / a.tpart: raw or packed doubles here (a mixed chain's fp64 limbs: written as doubles by the integer sequence's first steps)
-  dispatch_mode(mode, a.gelt, [&](auto M, auto G) {
-    dispatch_nl<1, 7>(a.nl, [&](auto NL) {
+  dispatch_mode(o.mode, o.gather, [&](auto M, auto G) {
+    dispatch_nl<1, 7>(o.nl, [&](auto NL) {
       auto launch = [&](auto H) {
         if constexpr (decltype(M)::value == 1 && decltype(G)::value) {
-          if (a.acc) {
+          if (o.acc) {
             hipLaunchKernelGGL((k_split4_main_fp<1, true, decltype(NL)::value, decltype(H)::value, WithAcc>), grid, block,
-                               main_lds_bytes(a.nl, sizeof(double)), a.st, c->dc, (const double *)a.part, (const double *)a.tpart, a.opa, a.opb,
-                               a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, (u32)a.imap, a.ni, a.pack, keyf,
-                               AccArg<WithAcc>{a.acc});
+                               main_lds_bytes(o.nl, sizeof(double)), a.st, c->dc, (const double *)a.part, (const double *)a.tpart, o.target,
+                               o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, o.gather, (u32)a.imap, a.ni, a.pack, keyf,
+                               AccArg<WithAcc>{o.acc});
             return;
           }
         }
         hipLaunchKernelGGL((k_split4_main_fp<decltype(M)::value, decltype(G)::value, decltype(NL)::value, decltype(H)::value>), grid, block,
-                           main_lds_bytes(a.nl, sizeof(double)), a.st, c->dc, (const double *)a.part, (const double *)a.tpart, a.opa, a.opb,
-                           a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, (u32)a.imap, a.ni, a.pack, keyf);
+                           main_lds_bytes(o.nl, sizeof(double)), a.st, c->dc, (const double *)a.part, (const double *)a.tpart, o.target,
+                           o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, o.gather, (u32)a.imap, a.ni, a.pack, keyf);
       };
       // up to four limbs LDS holds three workgroups per CU: the pair phase in two halves fits their registers
       if constexpr (decltype(NL)::value <= 4) {
@@ -1152,24 +1154,24 @@ bool split4_main(abc_hip_ctx *c, int mode, const MainArgs &a) {
   return true;
 }
 
-// K2a..K2c on one chunk (the half-done decomposition limbs are in s.dec; a.part / a.tpart are filled in here)
-static void launch_split3(abc_hip_ctx *c, const FusedScratch &s, int mode, MainArgs a, bool main4) {
-  a.part = s.dec;
-  a.tpart = s.ksacc;
-  launch_split_special(a.st, c, a.cc, a.nl, (const double *)s.dec, a.key, (double *)s.tsp);
-  hipLaunchKernelGGL(k_split3_pass_fp<14>, dim3((unsigned)(a.cc * 2 * 4)), dim3(256), 0, a.st, c->dc, (const double *)s.tsp,
-                     (double *)s.ksacc, a.nl, a.pack);
-  if (main4 && split4_main(c, mode, a)) return;
-  dispatch_mode(mode, a.gelt, [&](auto M, auto G) { launch_split3_main<decltype(M)::value, decltype(G)::value>(c, a); });
+// K2a..K2c on the chunk o (the half-done decomposition limbs are in s.dec)
+static void launch_split3(abc_hip_ctx *c, hipStream_t st, const FusedScratch &s, const KsOperands &o, const ChunkRoute &k) {
+  MainArgs a;
+  a.st = st, a.ops = o, a.part = s.dec, a.tpart = s.ksacc, a.ni = o.nl, a.pack = k.pack;
+  launch_split_special(st, c, o.count, o.nl, (const double *)s.dec, o.key, (double *)s.tsp);
+  hipLaunchKernelGGL(k_split3_pass_fp<14>, dim3((unsigned)(o.count * 2 * 4)), dim3(256), 0, st, c->dc, (const double *)s.tsp,
+                     (double *)s.ksacc, o.nl, a.pack);
+  if (k.main4 && split4_main(c, a)) return;
+  dispatch_mode(o.mode, o.gather, [&](auto M, auto G) { launch_split3_main<decltype(M)::value, decltype(G)::value>(c, a); });
 }
 
-// K2a..K3 on one chunk: operand given by (coef, coef_stride) [+ (ntt, ntt_stride) for CKKS], addends by (addend, stride)
+// K2a..K3 on the chunk o: operand given by (coef, coef_stride) [+ (ntt, ntt_stride) for CKKS]; key, addend and out are o's
 template <int LB>
 static int keyswitch_stage(abc_hip_ctx *c, hipStream_t st, const FusedScratch &s, const u64 *coef, size_t coef_stride, const u64 *ntt,
-                           size_t ntt_stride, const u64 *key, const u64 *addend, size_t addend_stride, bool add_c1, u64 *out, int nl,
-                           size_t cc, bool fp /* Seq::lds_fp, else lds_int with k's guard / lazy */, const ChunkRoute &k,
-                           int dec_ready = 0 /* 1: dec already holds the transformed decomposition limbs */) {
-  const size_t N = (size_t)1 << LB;
+                           size_t ntt_stride, const KsOperands &o, bool fp /* Seq::lds_fp, else lds_int with k's guard / lazy */,
+                           const ChunkRoute &k, int dec_ready = 0 /* 1: dec already holds the transformed decomposition limbs */) {
+  const size_t N = (size_t)1 << LB, cc = o.count;
+  const int nl = o.nl;
   const dim3 block((1 << LB) / 16);
   const bool ckks = (c->scheme == 2);
   const unsigned g2a = (unsigned)(cc * (nl + 1) * nl);
@@ -1182,18 +1184,18 @@ static int keyswitch_stage(abc_hip_ctx *c, hipStream_t st, const FusedScratch &s
       hipLaunchKernelGGL((k_fused_ks_decomp_ntt<LB, A, decltype(lazy)::value>), dim3(g2a), block, 0, st, c->dc, coef, coef_stride, s.dec,
                          nl, ckks ? 1 : 0);
     hipLaunchKernelGGL(k_fused_ks_mac, dim3(grid_for(cc * (nl + 1) * (N / 2), 256)), dim3(256), 0, st, c->dc, s.dec,
-                       ckks ? ntt : (const u64 *)nullptr, ntt_stride, key, s.ksacc, s.tsp, nl, cc);
+                       ckks ? ntt : (const u64 *)nullptr, ntt_stride, o.key, s.ksacc, s.tsp, nl, cc);
     hipLaunchKernelGGL((FP ? k_fused_ks_special_intt_fp<LB> : k_fused_ks_special_intt<LB>), dim3((unsigned)(cc * 2)), block, 0, st, c->dc,
                        s.tsp, s.tlast);
     if (!ckks)
       hipLaunchKernelGGL((FP ? k_fused_ks_moddown_bfv_fp<LB> : k_fused_ks_moddown_bfv<LB>), dim3(g3), block, 0, st, c->dc, s.ksacc, s.tlast,
-                         addend, addend_stride, add_c1 ? 1 : 0, out, nl);
+                         o.addend, o.addend_stride, o.add_c1, o.out, nl);
     else if constexpr (FP)
-      hipLaunchKernelGGL(k_fused_ks_moddown_fp<LB>, dim3(g3), block, 0, st, c->dc, s.ksacc, s.tlast, addend, addend_stride, add_c1 ? 1 : 0,
-                         out, nl, (int)(cc * 2));
+      hipLaunchKernelGGL(k_fused_ks_moddown_fp<LB>, dim3(g3), block, 0, st, c->dc, s.ksacc, s.tlast, o.addend, o.addend_stride, o.add_c1,
+                         o.out, nl, (int)(cc * 2));
     else
-      hipLaunchKernelGGL((k_fused_ks_moddown<LB, std::is_same_v<A, IntArith<true>>>), dim3(g3), block, 0, st, c->dc, s.ksacc, s.tlast, addend,
-                         addend_stride, add_c1 ? 1 : 0, out, nl);
+      hipLaunchKernelGGL((k_fused_ks_moddown<LB, std::is_same_v<A, IntArith<true>>>), dim3(g3), block, 0, st, c->dc, s.ksacc, s.tlast, o.addend,
+                         o.addend_stride, o.add_c1, o.out, nl);
   };
   if (fp) run(FpArith{}, std::true_type{});
   else if (k.guard) run(IntArith<true>{}, std::false_type{});
@@ -1218,164 +1220,146 @@ int join_lanes(abc_hip_ctx *c, int lanes) {
   return 0;
 }
 
-static int run_isplit(abc_hip_ctx *c, int mode, const u64 *opa, const u64 *opb, size_t opa_stride, size_t opb_stride, bool add_c1,
-                      const u64 *key, u64 *out, int nl, size_t count, u32 gelt) {
-  const size_t N = (size_t)c->n;
-  const ChunkPlan p = plan_chunks(c->facts, nl, count);
-  const ChunkRoute k = route_chunk(c->facts, Seq::isplit, nl, p.chunk);  // nothing in it depends on the chunk
-  return for_each_chunk(c, count, p.chunk, p.lanes, isplit_scratch_words(c, nl), k.fp_twin ? key : nullptr,
-                        [&](hipStream_t st, u64 *scratch, size_t off, size_t cc) {
-                          return isplit_chunk(c, st, scratch, cc, nl, mode, opa + off * opa_stride, opb ? opb + off * opb_stride : nullptr,
-                                              opa_stride, opb_stride, add_c1 ? 1 : 0, key, out + off * 2 * (size_t)nl * N, gelt, k);
-                        });
+static int run_isplit(abc_hip_ctx *c, const KsOperands &o) {
+  const ChunkPlan p = plan_chunks(c->facts, o.nl, o.count);
+  const ChunkRoute k = route_chunk(c->facts, Seq::isplit, o.nl, p.chunk);  // nothing in it depends on the chunk
+  return for_each_chunk(c, o.count, p.chunk, p.lanes, isplit_scratch_words(c, o.nl), k.fp_twin ? o.key : nullptr,
+                        [&](hipStream_t st, u64 *scratch, size_t off, size_t cc) { return isplit_chunk(c, st, scratch, o.slice(off, cc, (size_t)c->n), k); });
 }
 
 // N = 2^15 (abc_kernels_gsplit.hip)
-static int run_gsplit15(abc_hip_ctx *c, int mode, const u64 *opa, const u64 *opb, size_t opa_stride, size_t opb_stride, bool add_c1,
-                        const u64 *key, u64 *out, int nl, size_t count, u32 gelt, const u64 *acc = nullptr) {
-  const size_t N = (size_t)c->n;
-  const ChunkPlan p = plan_chunks(c->facts, nl, count);
-  return for_each_chunk(c, count, p.chunk, p.lanes, gsplit_scratch_words(c, nl), nullptr,
-                        [&](hipStream_t st, u64 *scratch, size_t off, size_t cc) {
-                          return gsplit_chunk15(c, st, scratch, cc, nl, mode, opa + off * opa_stride, opb ? opb + off * opb_stride : nullptr,
-                                                opa_stride, opb_stride, add_c1 ? 1 : 0, key, out + off * 2 * (size_t)nl * N, gelt,
-                                                acc ? acc + off * 2 * (size_t)nl * N : nullptr);
-                        });
+static int run_gsplit15(abc_hip_ctx *c, const KsOperands &o) {
+  const ChunkPlan p = plan_chunks(c->facts, o.nl, o.count);
+  return for_each_chunk(c, o.count, p.chunk, p.lanes, gsplit_scratch_words(c, o.nl), nullptr,
+                        [&](hipStream_t st, u64 *scratch, size_t off, size_t cc) { return gsplit_chunk15(c, st, scratch, o.slice(off, cc, (size_t)c->n)); });
 }
 
-// ---- CKKS multiply + relinearise: Seq::split14 (its scratch limbs are c->dc.ps words apart), lds_fp, lds_int ----
+// ---- CKKS multiply + relinearise (all is the mode-0 record of the call): Seq::split14 (its scratch limbs are c->dc.ps words
+// apart), lds_fp, lds_int ----
 template <int LB>
-static int run_mul_relin(abc_hip_ctx *c, Seq seq, const u64 *a, const u64 *b, u64 *out, int nl, size_t count) {
+static int run_mul_relin(abc_hip_ctx *c, Seq seq, const KsOperands &all) {
   const size_t N = (size_t)1 << LB;
-  const ChunkPlan p = plan_chunks(c->facts, nl, count);
+  const int nl = all.nl;
+  const ChunkPlan p = plan_chunks(c->facts, nl, all.count);
   const bool split = seq == Seq::split14, fp = seq != Seq::lds_int;
   const size_t SN = split ? (size_t)c->dc.ps : N;
   const size_t per_ct = fused_scratch_limbs(nl) * SN;
-  const size_t ctw = 2 * (size_t)nl * N;
-  return for_each_chunk(c, count, p.chunk, p.lanes, per_ct, split ? c->d_relin : nullptr, [&](hipStream_t st, u64 *scratch, size_t off, size_t cc) {
+  return for_each_chunk(c, all.count, p.chunk, p.lanes, per_ct, split ? all.key : nullptr, [&](hipStream_t st, u64 *scratch, size_t off, size_t cc) {
     const FusedScratch s = carve(scratch, p.chunk, nl, SN);
     const ChunkRoute k = route_chunk(c->facts, seq, nl, cc);
+    const KsOperands o = all.slice(off, cc, N);
+    const u64 *a = o.target, *b = o.addend;
     if constexpr (LB == 14) {
       if (split) {
         // lean: the block-wise inverse tails + register cross pass of abc_kernels_gsplit.hip spread over the chip
         if (k.lean)
-          gsplit_front14(st, c, cc, nl, 0, a + off * ctw, b + off * ctw, 0, (double *)s.coef, (double *)s.dec, 0u, k.pack);
+          gsplit_front14(st, c, o, (double *)s.coef, (double *)s.dec, k.pack);
         else
-          hipLaunchKernelGGL(k_split2_tensor_pass0_fp<LB>, dim3((unsigned)(cc * nl)), dim3((1 << LB) / 16), 0, st, c->dc, a + off * ctw,
-                             b + off * ctw, (double *)s.dec, nl, (int)k.pack);
-        launch_split3(c, s, 0, MainArgs{st, cc, nl, nullptr, nullptr, a + off * ctw, b + off * ctw, 0, 0, 0, c->d_relin, out + off * ctw, 0u,
-                                        kAllSlots, nl, k.pack},
-                      k.main4);
+          hipLaunchKernelGGL(k_split2_tensor_pass0_fp<LB>, dim3((unsigned)(cc * nl)), dim3((1 << LB) / 16), 0, st, c->dc, a, b, (double *)s.dec,
+                             nl, (int)k.pack);
+        launch_split3(c, st, s, o, k);
         ABC_HIP_CHECK(hipGetLastError());
         return 0;
       }
     }
     if (fp)  // tensor product, inverse transform and the forward transforms of the decomposition in one LDS-resident kernel
-      hipLaunchKernelGGL(k_fused_tensor_decomp_fp<LB>, dim3((unsigned)(cc * nl)), dim3((1 << LB) / 16), 0, st, c->dc, a + off * ctw,
-                         b + off * ctw, s.c01, s.ntt, s.dec, nl);
+      hipLaunchKernelGGL(k_fused_tensor_decomp_fp<LB>, dim3((unsigned)(cc * nl)), dim3((1 << LB) / 16), 0, st, c->dc, a, b, s.c01, s.ntt,
+                         s.dec, nl);
     else
-      hipLaunchKernelGGL(k_fused_tensor_intt<LB>, dim3((unsigned)(cc * nl)), dim3((1 << LB) / 16), 0, st, c->dc, a + off * ctw,
-                         b + off * ctw, s.c01, s.coef, s.ntt, nl);
-    return keyswitch_stage<LB>(c, st, s, s.coef, (size_t)nl * N, s.ntt, (size_t)nl * N, c->d_relin, s.c01, ctw, true, out + off * ctw, nl,
-                               cc, fp, k, fp ? 1 : 0);
+      hipLaunchKernelGGL(k_fused_tensor_intt<LB>, dim3((unsigned)(cc * nl)), dim3((1 << LB) / 16), 0, st, c->dc, a, b, s.c01, s.coef, s.ntt, nl);
+    // the key switch of the product's third polynomial, (c0, c1) of the product as its addend
+    KsOperands ks = o;
+    ks.mode = 1, ks.addend = s.c01, ks.addend_stride = 2 * (size_t)nl * N, ks.add_c1 = true;
+    return keyswitch_stage<LB>(c, st, s, s.coef, (size_t)nl * N, s.ntt, (size_t)nl * N, ks, fp, k, fp ? 1 : 0);
   });
 }
 
 int launch_mul_relin(abc_hip_ctx *c, Seq seq, const u64 *a, const u64 *b, u64 *out, int nl, size_t count) {
   if (!count) return 0;
-  const size_t ctw = 2 * (size_t)nl * c->n;
+  KsOperands o;
+  o.mode = 0, o.target = a, o.addend = b, o.target_stride = o.addend_stride = 2 * (size_t)nl * c->n;
+  o.key = c->d_relin, o.out = out, o.nl = nl, o.count = count;
   switch (seq) {
-    case Seq::gsplit15: return run_gsplit15(c, 0, a, b, ctw, ctw, false, c->d_relin, out, nl, count, 0u);
-    case Seq::isplit: return run_isplit(c, 0, a, b, ctw, ctw, false, c->d_relin, out, nl, count, 0u);
+    case Seq::gsplit15: return run_gsplit15(c, o);
+    case Seq::isplit: return run_isplit(c, o);
     case Seq::split14:
     case Seq::lds_fp:
-    case Seq::lds_int: return dispatch_logn<10, 14>(c->logn, [&](auto LB) { return run_mul_relin<decltype(LB)::value>(c, seq, a, b, out, nl, count); });
+    case Seq::lds_int: return dispatch_logn<10, 14>(c->logn, [&](auto LB) { return run_mul_relin<decltype(LB)::value>(c, seq, o); });
     default: set_error("launch_mul_relin: not a multiply + relinearise sequence of this file"); return 1;
   }
 }
 
-// ---- general key switch: out[ct] = KeySwitch(target[ct]) (+ addend): Seq::split14, bsplit14, lds_fp, lds_int ----
-// target: [nl][N] per ciphertext at target + ct*target_stride, in the ciphertext's own form (BFV coefficient, CKKS NTT)
+// ---- general key switch: Seq::split14, bsplit14, lds_fp, lds_int ----
 template <int LB>
-static int run_keyswitch(abc_hip_ctx *c, Seq seq, const u64 *target, size_t target_stride, const u64 *key, u64 *out, int nl, size_t count,
-                         const u64 *addend, size_t addend_stride, bool add_c1, u32 gelt, const u64 *acc) {
+static int run_keyswitch(abc_hip_ctx *c, Seq seq, const KsOperands &all) {
   const size_t N = (size_t)1 << LB;
+  const int nl = all.nl;
   const bool ckks = (c->scheme == 2);
-  const ChunkPlan p = plan_chunks(c->facts, nl, count);
+  const ChunkPlan p = plan_chunks(c->facts, nl, all.count);
   // split sequences (N = 2^14, every key prime below 2^50): CKKS as in run_mul_relin; BFV (coefficient-form operand) the
   // register pass + abc_kernels_gsplit.hip's k_gsplit_special<14, NL, true> (k_bsplit_special8x2 for eight digits) / k_bsplit_tcoef /
   // k_bsplit_finish_big
   const bool splitc = seq == Seq::split14, splitb = seq == Seq::bsplit14, fp = seq != Seq::lds_int;
-  // BFV rotation (coefficient form): the kernels gather with elt^-1 mod 2N
-  const u32 ginv = (!ckks && gelt) ? (u32)host::invmod(gelt, 2 * (uint64_t)N) : 0u;
-  if (ginv && !splitb) { set_error("run_keyswitch: a BFV permutation is only folded into the split sequence"); return 1; }
-  if (ckks && gelt && !splitc) { set_error("run_keyswitch: a CKKS permutation is only folded into the split sequence"); return 1; }
-  if (acc && !(gelt && (splitc || splitb))) { set_error("run_keyswitch: a second addend is only taken with a folded permutation"); return 1; }
   const size_t SN = (splitc || splitb) ? (size_t)c->dc.ps : N;
   const size_t per_ct = fused_scratch_limbs(nl) * SN;
   // the split kernels read the key's fp64 twin (BFV: the inner-product kernel)
-  return for_each_chunk(c, count, p.chunk, p.lanes, per_ct, (splitc || splitb) ? key : nullptr, [&](hipStream_t st, u64 *scratch, size_t off, size_t cc) {
+  return for_each_chunk(c, all.count, p.chunk, p.lanes, per_ct, (splitc || splitb) ? all.key : nullptr, [&](hipStream_t st, u64 *scratch, size_t off, size_t cc) {
     const FusedScratch s = carve(scratch, p.chunk, nl, SN);
     const ChunkRoute k = route_chunk(c->facts, seq, nl, cc);
-    const u64 *tg = target + off * target_stride;
-    const u64 *ad = addend ? addend + off * addend_stride : nullptr;
-    u64 *o = out + off * 2 * nl * N;
-    const u64 *ac = acc ? acc + off * 2 * nl * N : nullptr;
+    const KsOperands o = all.slice(off, cc, N);
     if constexpr (LB == 14) {
       if (splitc) {
         if (k.lean)
-          gsplit_front14(st, c, cc, nl, 1, tg, nullptr, target_stride, (double *)s.coef, (double *)s.dec, gelt, k.pack);
+          gsplit_front14(st, c, o, (double *)s.coef, (double *)s.dec, k.pack);
         else
-          hipLaunchKernelGGL((gelt ? k_fused_operand_pass0_fp<LB, true, true> : k_fused_operand_pass0_fp<LB, true, false>),
-                             dim3((unsigned)(cc * nl)), dim3((1 << LB) / 16), 0, st, c->dc, tg, target_stride, (double *)s.dec, nl, 0,
-                             gelt, 1 | (k.pack ? 2 : 0));
-        launch_split3(c, s, 1, MainArgs{st, cc, nl, nullptr, nullptr, tg, ad, target_stride, addend_stride, add_c1 ? 1 : 0, key, o, gelt,
-                                        kAllSlots, nl, k.pack, ac},
-                      k.main4);
+          hipLaunchKernelGGL((o.gather ? k_fused_operand_pass0_fp<LB, true, true> : k_fused_operand_pass0_fp<LB, true, false>),
+                             dim3((unsigned)(cc * nl)), dim3((1 << LB) / 16), 0, st, c->dc, o.target, o.target_stride, (double *)s.dec, nl, 0,
+                             o.gather, 1 | (k.pack ? 2 : 0));
+        launch_split3(c, st, s, o, k);
         ABC_HIP_CHECK(hipGetLastError());
         return 0;
       }
       if (splitb) {
         // few ciphertexts in flight (k.per_target): one workgroup per (ct, J, target I) instead of per (ct, J)
         hipLaunchKernelGGL((k_fused_operand_pass0_fp<LB, false, false>), dim3((unsigned)(cc * nl * (k.per_target ? nl + 1 : 1))),
-                           dim3((1 << LB) / 16), 0, st, c->dc, tg, target_stride, (double *)s.dec, nl, k.per_target ? 1 : 0, ginv, 1);
+                           dim3((1 << LB) / 16), 0, st, c->dc, o.target, o.target_stride, (double *)s.dec, nl, k.per_target ? 1 : 0, o.gather, 1);
         // inner product + inverse tails for every key prime, then the register-only finish (a rotation's addend g(c0): gathered there)
-        return bsplit_back14(c, st, cc, nl, (const double *)s.dec, (double *)s.ksacc, key, ad, addend_stride, add_c1 ? 1 : 0, o, ginv, ac);
+        return bsplit_back<14>(c, st, (const double *)s.dec, (double *)s.ksacc, o);
       }
     }
     // LDS-resident kernels (smaller rings, wider primes, ABC_HIP_NO_SPLIT)
-    const u64 *coef = tg;
-    size_t coef_stride = target_stride;
+    const u64 *coef = o.target;
+    size_t coef_stride = o.target_stride;
     if (ckks) {  // operand arrives in NTT form: coefficient form via one in-LDS inverse transform per limb
       hipLaunchKernelGGL((fp ? k_fused_operand_intt<LB, FpArith> : k_fused_operand_intt<LB, IntArith<true>>), dim3((unsigned)(cc * nl)),
-                         dim3((1 << LB) / 16), 0, st, c->dc, tg, target_stride, s.coef, nl);
+                         dim3((1 << LB) / 16), 0, st, c->dc, o.target, o.target_stride, s.coef, nl);
       coef = s.coef;
       coef_stride = (size_t)nl * N;
     }
-    return keyswitch_stage<LB>(c, st, s, coef, coef_stride, tg, target_stride, key, ad, addend_stride, add_c1, o, nl, cc, fp, k, 0);
+    return keyswitch_stage<LB>(c, st, s, coef, coef_stride, o.target, o.target_stride, o, fp, k, 0);
   });
 }
 
-int launch_keyswitch(abc_hip_ctx *c, const KsRoute &r, const u64 *target, size_t target_stride, const u64 *key, u64 *out, int nl, size_t count,
-                     const u64 *addend, size_t addend_stride, bool add_c1, u32 gelt, const u64 *acc) {
-  if (!count) return 0;
-  if (acc && (r.seq == Seq::isplit || r.seq == Seq::generic)) { set_error("launch_keyswitch: this sequence takes no second addend"); return 1; }
+// what the kernels gather with: CKKS (NTT form) the element itself, BFV (coefficient form) its inverse mod 2N
+static u32 gather_elt(const KsOperands &o, int scheme, size_t N) {
+  return (scheme == 2 || !o.gelt) ? o.gelt : (u32)host::invmod(o.gelt, 2 * (uint64_t)N);
+}
+
+int launch_keyswitch(abc_hip_ctx *c, const KsRoute &r, const KsOperands &in) {
+  if (!in.count) return 0;
+  if (in.gelt && !seq_folds_permutation(c->facts, r)) { set_error("launch_keyswitch: this sequence folds no permutation"); return 1; }
+  if (in.acc && !(in.gelt && seq_takes_acc(c->facts, r, in.nl))) { set_error("launch_keyswitch: a second addend needs a folded permutation and a sequence that takes one"); return 1; }
+  KsOperands o = in;
+  o.mode = 1, o.gather = gather_elt(o, c->scheme, (size_t)c->n);
   switch (r.seq) {
-    case Seq::gsplit15: return run_gsplit15(c, 1, target, addend, target_stride, addend_stride, add_c1, key, out, nl, count, gelt, acc);
-    case Seq::isplit: return run_isplit(c, 1, target, addend, target_stride, addend_stride, add_c1, key, out, nl, count, gelt);
-    case Seq::bsplit_big:  // BFV, coefficient form: the signed permutation folded into the first step's load and the last step's addend
-      return bsplit_big(c, target, target_stride, key, out, nl, count, addend, addend_stride, add_c1,
-                        gelt ? (u32)host::invmod(gelt, 2 * (uint64_t)c->n) : 0u, acc);
-    case Seq::generic:
-      return keyswitch_generic(c, r.front, target, target_stride, key, out, nl, count, addend, addend_stride, add_c1,
-                               gelt ? (u32)host::invmod(gelt, 2 * (uint64_t)c->n) : 0u);
+    case Seq::gsplit15: return run_gsplit15(c, o);
+    case Seq::isplit: return run_isplit(c, o);
+    case Seq::bsplit_big: return bsplit_big(c, o);  // BFV, coefficient form: the signed permutation folded into the first step's load and the last step's addend
+    case Seq::generic: return keyswitch_generic(c, r.front, o);
     case Seq::split14:
     case Seq::bsplit14:
     case Seq::lds_fp:
-    case Seq::lds_int:
-      return dispatch_logn<10, 14>(c->logn, [&](auto LB) {
-        return run_keyswitch<decltype(LB)::value>(c, r.seq, target, target_stride, key, out, nl, count, addend, addend_stride, add_c1, gelt, acc);
-      });
+    case Seq::lds_int: return dispatch_logn<10, 14>(c->logn, [&](auto LB) { return run_keyswitch<decltype(LB)::value>(c, r.seq, o); });
     default: set_error("launch_keyswitch: not a key-switch sequence"); return 1;
   }
 }

@@ -718,82 +718,84 @@ __global__ __launch_bounds__(1024) void k_gsplit_main_deep(DevCtx c, const doubl
 // ---- host side ----
 // first step only (the half-done decomposition limbs): used by the N = 2^14 sequence for small batches
 template <int LOGN>
-static void launch_gsplit_front(hipStream_t st, abc_hip_ctx *c, size_t cc, int nl, int mode, const u64 *opa, const u64 *opb,
-                                size_t opa_stride, double *hinv, double *part, u32 gelt, int pack = 0) {
+static void launch_gsplit_front(hipStream_t st, abc_hip_ctx *c, const KsOperands &o, double *hinv, double *part, int pack) {
   constexpr int NB = 1 << (LOGN - 10);
+  const size_t cc = o.count;
+  const int nl = o.nl;
   const dim3 g1((unsigned)(((cc + 3) / 4) * nl * NB)), g2((unsigned)(cc * nl * (LOGN > 14 ? 32 : 4)));
   const size_t lds = (size_t)(4 * lds_words(10)) * 8 + 1024 * sizeof(double);
-  dispatch_mode(mode, gelt, [&](auto M, auto G) {
+  dispatch_mode(o.mode, o.gather, [&](auto M, auto G) {
     constexpr int MODE = decltype(M)::value;
-    hipLaunchKernelGGL((k_gsplit_inv_tails<LOGN, MODE, decltype(G)::value>), g1, dim3(256), lds, st, c->dc, opa, MODE ? nullptr : opb,
-                       MODE ? opa_stride : 0, hinv, nl, (int)cc, gelt);
+    hipLaunchKernelGGL((k_gsplit_inv_tails<LOGN, MODE, decltype(G)::value>), g1, dim3(256), lds, st, c->dc, o.target, MODE ? nullptr : o.addend,
+                       MODE ? o.target_stride : 0, hinv, nl, (int)cc, o.gather);
   });
   hipLaunchKernelGGL((k_gsplit_cross<LOGN>), g2, dim3(256), 0, st, c->dc, hinv, part, nl, pack);
 }
-void gsplit_front14(hipStream_t st, abc_hip_ctx *c, size_t cc, int nl, int mode, const u64 *opa, const u64 *opb, size_t opa_stride,
-                    double *hinv, double *part, u32 gelt, int pack) {
-  launch_gsplit_front<14>(st, c, cc, nl, mode, opa, opb, opa_stride, hinv, part, gelt, pack);
+void gsplit_front14(hipStream_t st, abc_hip_ctx *c, const KsOperands &o, double *hinv, double *part, int pack) {
+  launch_gsplit_front<14>(st, c, o, hinv, part, pack);
 }
 
 // G2c over the slots of a.imap: up to seven limbs k_gsplit_main, deep chains (one wavefront per limb still, up to sixteen of
 // them) k_gsplit_main_deep
 template <int LOGN>
-static void launch_gsplit_main(abc_hip_ctx *c, int mode, const MainArgs &a) {
+static void launch_gsplit_main(abc_hip_ctx *c, const MainArgs &a) {
   if (a.ni < 1) return;
-  const dim3 gmain((unsigned)(a.cc * a.ni * (1 << (LOGN - 10))));
+  const KsOperands &o = a.ops;
+  const dim3 gmain((unsigned)(o.count * a.ni * (1 << (LOGN - 10))));
   const double *part = (const double *)a.part, *tpart = (const double *)a.tpart;  // the limbs of the slots in a.imap are doubles
-  dispatch_mode(mode, a.gelt, [&](auto M, auto G) {
+  dispatch_mode(o.mode, o.gather, [&](auto M, auto G) {
     constexpr int MODE = decltype(M)::value;
     constexpr bool GAL = decltype(G)::value;
-    if (a.nl > 7)
-      hipLaunchKernelGGL((k_gsplit_main_deep<LOGN, MODE, GAL>), gmain, dim3(1024), main_lds_bytes(a.nl, sizeof(double)), a.st, c->dc, part, tpart, a.opa, a.opb,
-                         a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, a.nl, a.imap, a.ni);
+    if (o.nl > 7)
+      hipLaunchKernelGGL((k_gsplit_main_deep<LOGN, MODE, GAL>), gmain, dim3(1024), main_lds_bytes(o.nl, sizeof(double)), a.st, c->dc, part, tpart, o.target,
+                         o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, o.gather, o.nl, a.imap, a.ni);
     else
-      dispatch_nl<1, 7>(a.nl, [&](auto NL) {
+      dispatch_nl<1, 7>(o.nl, [&](auto NL) {
         if constexpr (MODE == 1 && GAL) {
-          if (a.acc) {
-            hipLaunchKernelGGL((k_gsplit_main<LOGN, 1, true, decltype(NL)::value, WithAcc>), gmain, dim3(512), main_lds_bytes(a.nl, sizeof(double)),
-                               a.st, c->dc, part, tpart, a.opa, a.opb, a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, (u32)a.imap, a.ni,
-                               AccArg<WithAcc>{a.acc});
+          if (o.acc) {
+            hipLaunchKernelGGL((k_gsplit_main<LOGN, 1, true, decltype(NL)::value, WithAcc>), gmain, dim3(512), main_lds_bytes(o.nl, sizeof(double)),
+                               a.st, c->dc, part, tpart, o.target, o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, o.gather,
+                               (u32)a.imap, a.ni, AccArg<WithAcc>{o.acc});
             return;
           }
         }
-        hipLaunchKernelGGL((k_gsplit_main<LOGN, MODE, GAL, decltype(NL)::value>), gmain, dim3(512), main_lds_bytes(a.nl, sizeof(double)), a.st, c->dc, part,
-                           tpart, a.opa, a.opb, a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, (u32)a.imap, a.ni);
+        hipLaunchKernelGGL((k_gsplit_main<LOGN, MODE, GAL, decltype(NL)::value>), gmain, dim3(512), main_lds_bytes(o.nl, sizeof(double)), a.st, c->dc, part,
+                           tpart, o.target, o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, o.gather, (u32)a.imap, a.ni);
       });
   });
 }
-void gsplit_main15(abc_hip_ctx *c, int mode, const MainArgs &a) { launch_gsplit_main<15>(c, mode, a); }
+void gsplit_main15(abc_hip_ctx *c, const MainArgs &a) { launch_gsplit_main<15>(c, a); }
 
 // G2a..G2c; a.part, a.tpart: the chunk's scratch
 template <int LOGN>
-static void launch_gsplit_back(abc_hip_ctx *c, int mode, const MainArgs &a, double *tsp) {
+static void launch_gsplit_back(abc_hip_ctx *c, const MainArgs &a, double *tsp) {
   constexpr int NB = 1 << (LOGN - 10);
-  const int nl = a.nl;
+  const KsOperands &o = a.ops;
+  const int nl = o.nl;
   const size_t lds_sp = (size_t)((nl < 2 ? 2 : nl) * lds_words(10)) * 8;
   dispatch_nl<1, 15>(nl, [&](auto NL) {
-    hipLaunchKernelGGL((k_gsplit_special<LOGN, decltype(NL)::value, false>), dim3((unsigned)(a.cc * NB)), dim3(64 * decltype(NL)::value), lds_sp,
-                       a.st, c->dc, (const double *)a.part, a.key, key_twin_lookup(c, a.key), tsp, (int)a.cc);
+    hipLaunchKernelGGL((k_gsplit_special<LOGN, decltype(NL)::value, false>), dim3((unsigned)(o.count * NB)), dim3(64 * decltype(NL)::value), lds_sp,
+                       a.st, c->dc, (const double *)a.part, o.key, key_twin_lookup(c, o.key), tsp, (int)o.count);
   });
-  hipLaunchKernelGGL((k_gsplit_pass<LOGN>), dim3((unsigned)(a.cc * 2 * (LOGN > 14 ? 32 : 4))), dim3(256), 0, a.st, c->dc, tsp,
+  hipLaunchKernelGGL((k_gsplit_pass<LOGN>), dim3((unsigned)(o.count * 2 * (LOGN > 14 ? 32 : 4))), dim3(256), 0, a.st, c->dc, tsp,
                      (double *)a.tpart, nl);
-  launch_gsplit_main<LOGN>(c, mode, a);
+  launch_gsplit_main<LOGN>(c, a);
 }
 
 // scratch (words, limb stride c->dc.ps): hinv nl | part nl(nl+1) | tpart 2 nl | tsp_half 2
 size_t gsplit_scratch_words(const abc_hip_ctx *c, int nl) {
   return ((size_t)nl + (size_t)nl * (nl + 1) + 2 * (size_t)nl + 2) * (size_t)c->dc.ps;
 }
-// one chunk at N = 2^15: mode 0 multiply (opa = a, opb = b), mode 1 key switch (opa = operand in NTT form, opb = addend)
-int gsplit_chunk15(abc_hip_ctx *c, hipStream_t st, u64 *scratch, size_t cc, int nl, int mode, const u64 *opa, const u64 *opb,
-                   size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt, const u64 *acc) {
-  if (acc && (nl > 7 || !gelt || mode != 1)) { set_error("gsplit_chunk15: no main kernel takes a second addend here"); return 1; }
-  const size_t PS = (size_t)c->dc.ps;
+// one chunk at N = 2^15
+int gsplit_chunk15(abc_hip_ctx *c, hipStream_t st, u64 *scratch, const KsOperands &o) {
+  const size_t PS = (size_t)c->dc.ps, cc = o.count;
+  const int nl = o.nl;
   double *hinv = (double *)scratch, *part = hinv + cc * (size_t)nl * PS, *tpart = part + cc * (size_t)nl * (nl + 1) * PS,
          *tsp = tpart + cc * 2 * (size_t)nl * PS;
-  launch_gsplit_front<15>(st, c, cc, nl, mode, opa, opb, opa_stride, hinv, part, gelt);
-  launch_gsplit_back<15>(c, mode, MainArgs{st, cc, nl, part, tpart, opa, opb, opa_stride, opb_stride, add_c1, key, out, gelt, kAllSlots, nl, 0, acc},
-                         tsp);
+  launch_gsplit_front<15>(st, c, o, hinv, part, 0);
+  MainArgs a;
+  a.st = st, a.ops = o, a.part = part, a.tpart = tpart, a.ni = nl;
+  launch_gsplit_back<15>(c, a, tsp);
   ABC_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -824,33 +826,37 @@ static void launch_bsplit_special(abc_hip_ctx *c, hipStream_t st, size_t cc, int
                          key_twin_lookup(c, key), half, (int)cc);
     });
 }
-int bsplit_back14(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const double *part, double *half, const u64 *key, const u64 *addend,
-                  size_t addend_stride, int add_c1, u64 *out, u32 ginv, const u64 *acc) {
-  launch_bsplit_special<14>(c, st, cc, nl, part, key, half);
+// B4, the last kernel of a BFV sequence (k_bsplit_finish_big / k_bsplit_finish_lds), per_limb workgroups per output limb: K<LOGN, WithAcc>
+// with the second addend as one more argument where the chunk has one, K<LOGN> otherwise
+using BsplitFinishAcc = void (*)(DevCtx, const double *, const double *, const u64 *, size_t, int, u64 *, int, u32, AccArg<WithAcc>);
+using BsplitFinish = void (*)(DevCtx, const double *, const double *, const u64 *, size_t, int, u64 *, int, u32);
+static void launch_bsplit_finish(BsplitFinishAcc with_acc, BsplitFinish plain, unsigned per_limb, abc_hip_ctx *c, hipStream_t st,
+                                 const double *half, const double *tco, const KsOperands &o) {
+  const dim3 grid((unsigned)(o.count * 2 * o.nl * per_limb));
+  if (o.acc)
+    hipLaunchKernelGGL(with_acc, grid, dim3(256), 0, st, c->dc, half, tco, o.addend, o.addend_stride, o.add_c1, o.out, o.nl, o.gather,
+                       AccArg<WithAcc>{o.acc});
+  else
+    hipLaunchKernelGGL(plain, grid, dim3(256), 0, st, c->dc, half, tco, o.addend, o.addend_stride, o.add_c1, o.out, o.nl, o.gather);
+}
+// B2..B4 behind a `part` of 1 << (LOGN - 10) blocks (N = 2^13: abc_kernels_bmul.hip writes it behind the floor, as at 2^14)
+template <int LOGN>
+int bsplit_back(abc_hip_ctx *c, hipStream_t st, const double *part, double *half, const KsOperands &o) {
+  const size_t cc = o.count;
+  const int nl = o.nl;
+  if (LOGN != 14 && o.acc) { set_error("bsplit_back: a second addend is taken at N = 2^14 only"); return 1; }
+  launch_bsplit_special<LOGN>(c, st, cc, nl, part, o.key, half);
   // half occupies the ksacc + tsp regions of the caller's scratch (2 nl + 2 limbs per ciphertext), tco the tlast region behind them
   double *tco = half + cc * 2 * (size_t)(nl + 1) * (size_t)c->dc.ps;
-  hipLaunchKernelGGL((k_bsplit_tcoef<14>), dim3((unsigned)(cc * 2 * 4)), dim3(256), 0, st, c->dc, half, tco, nl);
-  if (acc)
-    hipLaunchKernelGGL((k_bsplit_finish_big<14, WithAcc>), dim3((unsigned)(cc * 2 * nl * 4)), dim3(256), 0, st, c->dc, half, tco, addend,
-                       addend_stride, add_c1, out, nl, ginv, AccArg<WithAcc>{acc});
-  else
-    hipLaunchKernelGGL((k_bsplit_finish_big<14>), dim3((unsigned)(cc * 2 * nl * 4)), dim3(256), 0, st, c->dc, half, tco, addend,
-                       addend_stride, add_c1, out, nl, ginv);
+  hipLaunchKernelGGL((k_bsplit_tcoef<LOGN>), dim3((unsigned)(cc * 2 * 4)), dim3(256), 0, st, c->dc, half, tco, nl);
+  BsplitFinishAcc with_acc = nullptr;
+  if constexpr (LOGN == 14) with_acc = k_bsplit_finish_big<14, WithAcc>;
+  launch_bsplit_finish(with_acc, k_bsplit_finish_big<LOGN>, 4, c, st, half, tco, o);
   ABC_HIP_CHECK(hipGetLastError());
   return 0;
 }
-
-// the same three launches behind a `part` of eight blocks (N = 2^13: abc_kernels_bmul.hip writes it behind the floor, as at 2^14)
-int bsplit_back13(abc_hip_ctx *c, hipStream_t st, size_t cc, int nl, const double *part, double *half, const u64 *key, const u64 *addend,
-                  size_t addend_stride, int add_c1, u64 *out, u32 ginv) {
-  launch_bsplit_special<13>(c, st, cc, nl, part, key, half);
-  double *tco = half + cc * 2 * (size_t)(nl + 1) * (size_t)c->dc.ps;
-  hipLaunchKernelGGL((k_bsplit_tcoef<13>), dim3((unsigned)(cc * 2 * 4)), dim3(256), 0, st, c->dc, half, tco, nl);
-  hipLaunchKernelGGL((k_bsplit_finish_big<13>), dim3((unsigned)(cc * 2 * nl * 4)), dim3(256), 0, st, c->dc, half, tco, addend,
-                     addend_stride, add_c1, out, nl, ginv);
-  ABC_HIP_CHECK(hipGetLastError());
-  return 0;
-}
+template int bsplit_back<14>(abc_hip_ctx *, hipStream_t, const double *, double *, const KsOperands &);
+template int bsplit_back<13>(abc_hip_ctx *, hipStream_t, const double *, double *, const KsOperands &);
 
 // ---- BFV, N = 2^15 / 2^16 (coefficient-form ciphertexts, every key prime below 2^50): the same three steps with NB = 32 / 64 ----
 // B1 k_bsplit_pass0   (ct, J, key prime I, quarter): digit J of the operand, read as it lies (no reduction modulo q_I is needed in
@@ -1159,61 +1165,41 @@ __global__ __launch_bounds__(256) void k_bsplit_finish_lds(DevCtx c, const doubl
 
 // N = 2^13 (BFVDefault(8192): eight 1024-point blocks, radix-8 cross passes in registers) takes the same sequence
 template <int LOGN>
-static int bsplit_big_chunk(abc_hip_ctx *c, hipStream_t st, double *scratch, size_t cc, int nl, const u64 *target, size_t target_stride,
-                            const u64 *key, const u64 *addend, size_t addend_stride, int add_c1, u64 *out, u32 ginv = 0,
-                            const u64 *acc = nullptr) {
-  const size_t PS = (size_t)c->dc.ps;
+static int bsplit_big_chunk(abc_hip_ctx *c, hipStream_t st, double *scratch, const KsOperands &o) {
+  const size_t PS = (size_t)c->dc.ps, cc = o.count;
+  const int nl = o.nl;
   double *part = scratch, *half = part + cc * (size_t)nl * (nl + 1) * PS, *tco = half + cc * 2 * (size_t)(nl + 1) * PS;
   constexpr bool REG = LOGN < 15;  // cross passes of at most 16 values stay in registers
   if constexpr (REG)
-    hipLaunchKernelGGL((k_bsplit_pass0<LOGN>), dim3((unsigned)(cc * nl * (nl + 1) * 4)), dim3(256), 0, st, c->dc, target, target_stride, part,
-                       nl, ginv);
+    hipLaunchKernelGGL((k_bsplit_pass0<LOGN>), dim3((unsigned)(cc * nl * (nl + 1) * 4)), dim3(256), 0, st, c->dc, o.target, o.target_stride, part,
+                       nl, o.gather);
   else
-    hipLaunchKernelGGL((k_bsplit_pass0_lds<LOGN>), dim3((unsigned)(cc * nl * 32)), dim3(256), 0, st, c->dc, target, target_stride, part, nl, ginv);
-  launch_bsplit_special<LOGN>(c, st, cc, nl, part, key, half);
+    hipLaunchKernelGGL((k_bsplit_pass0_lds<LOGN>), dim3((unsigned)(cc * nl * 32)), dim3(256), 0, st, c->dc, o.target, o.target_stride, part, nl,
+                       o.gather);
+  launch_bsplit_special<LOGN>(c, st, cc, nl, part, o.key, half);
   hipLaunchKernelGGL((k_bsplit_tcoef<LOGN>), dim3((unsigned)(cc * 2 * 4)), dim3(256), 0, st, c->dc, half, tco, nl);
-  if constexpr (REG) {
-    if (acc)
-      hipLaunchKernelGGL((k_bsplit_finish_big<LOGN, WithAcc>), dim3((unsigned)(cc * 2 * nl * 4)), dim3(256), 0, st, c->dc, half, tco, addend,
-                         addend_stride, add_c1, out, nl, ginv, AccArg<WithAcc>{acc});
-    else
-      hipLaunchKernelGGL((k_bsplit_finish_big<LOGN>), dim3((unsigned)(cc * 2 * nl * 4)), dim3(256), 0, st, c->dc, half, tco, addend,
-                         addend_stride, add_c1, out, nl, ginv);
-  } else {
-    if (acc)
-      hipLaunchKernelGGL((k_bsplit_finish_lds<LOGN, WithAcc>), dim3((unsigned)(cc * 2 * nl * 32)), dim3(256), 0, st, c->dc, half, tco, addend,
-                         addend_stride, add_c1, out, nl, ginv, AccArg<WithAcc>{acc});
-    else
-      hipLaunchKernelGGL((k_bsplit_finish_lds<LOGN>), dim3((unsigned)(cc * 2 * nl * 32)), dim3(256), 0, st, c->dc, half, tco, addend,
-                         addend_stride, add_c1, out, nl, ginv);
-  }
+  if constexpr (REG) launch_bsplit_finish(k_bsplit_finish_big<LOGN, WithAcc>, k_bsplit_finish_big<LOGN>, 4, c, st, half, tco, o);
+  else launch_bsplit_finish(k_bsplit_finish_lds<LOGN, WithAcc>, k_bsplit_finish_lds<LOGN>, 32, c, st, half, tco, o);
   ABC_HIP_CHECK(hipGetLastError());
   return 0;
 }
 
 // whole call: chunks of at most 1 GiB (N = 2^13) / 4 GiB of scratch on the context's stream (a chunk at these sizes fills the device by itself)
-int bsplit_big(abc_hip_ctx *c, const u64 *target, size_t target_stride, const u64 *key, u64 *out, int nl, size_t count, const u64 *addend,
-               size_t addend_stride, bool add_c1, u32 ginv, const u64 *acc) {
+int bsplit_big(abc_hip_ctx *c, const KsOperands &o) {
   const size_t N = (size_t)c->n, PS = (size_t)c->dc.ps;
+  const int nl = o.nl;
   const size_t per_ct = ((size_t)nl * (nl + 1) + 2 * (size_t)(nl + 1) + 2) * PS;  // part | half | tco (words)
   // N = 2^15 / 2^16: 4 GiB of scratch, i.e. 85 ciphertexts per launch group at N = 2^16, L = 8 (1 GiB = 21: config 5 -3.5 % -- a key
   // slice is fetched once per launch group and XCD, k_bsplit_special8x2)
-  const size_t chunk = even_chunks((size_t)(c->logn > 14 ? 4 : 1) << 30, per_ct, count);
+  const size_t chunk = even_chunks((size_t)(c->logn > 14 ? 4 : 1) << 30, per_ct, o.count);
   if (ensure_workspace(c, chunk * per_ct * 8)) return 1;
-  (void)key_twin(c, key);  // the inner-product kernels read the key's fp64 twin where it exists
-  for (size_t off = 0; off < count; off += chunk) {
-    const size_t cc = (count - off < chunk) ? count - off : chunk;
-    const u64 *tg = target + off * target_stride;
-    const u64 *ad = addend ? addend + off * addend_stride : nullptr;
-    u64 *o = out + off * 2 * (size_t)nl * N;
-    const u64 *ac = acc ? acc + off * 2 * (size_t)nl * N : nullptr;
-    if (c->logn == 13) {
-      if (bsplit_big_chunk<13>(c, c->stream, (double *)c->ws, cc, nl, tg, target_stride, key, ad, addend_stride, add_c1 ? 1 : 0, o, ginv, ac)) return 1;
-      continue;
-    }
-    const int rc = (c->logn == 15)
-                       ? bsplit_big_chunk<15>(c, c->stream, (double *)c->ws, cc, nl, tg, target_stride, key, ad, addend_stride, add_c1 ? 1 : 0, o, ginv, ac)
-                       : bsplit_big_chunk<16>(c, c->stream, (double *)c->ws, cc, nl, tg, target_stride, key, ad, addend_stride, add_c1 ? 1 : 0, o, ginv, ac);
+  (void)key_twin(c, o.key);  // the inner-product kernels read the key's fp64 twin where it exists
+  for (size_t off = 0; off < o.count; off += chunk) {
+    const KsOperands oc = o.slice(off, (o.count - off < chunk) ? o.count - off : chunk, N);
+    const int rc = dispatch_logn<13, 16>(c->logn, [&](auto LB) {
+      if constexpr (decltype(LB)::value == 14) return set_error("bsplit_big: N = 2^14 is bsplit14's"), 1;
+      else return bsplit_big_chunk<decltype(LB)::value>(c, c->stream, (double *)c->ws, oc);
+    });
     if (rc) return rc;
   }
   return 0;

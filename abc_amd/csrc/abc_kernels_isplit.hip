@@ -567,9 +567,11 @@ __global__ __launch_bounds__(1024) void k_isplit_main_deep(DevCtx c, const u64 *
 // wide data primes (up to seven limbs k_isplit_main, deep chains of N = 2^15 k_isplit_main_deep), the fp64 kernels of
 // abc_kernels_fused.hip / abc_kernels_gsplit.hip over the others
 template <bool GUARD, int LOGN>
-static void launch_isplit_tail(abc_hip_ctx *c, int mode, const MainArgs &a, u64 *tsp_half, u32 fpmask) {
+static void launch_isplit_tail(abc_hip_ctx *c, const MainArgs &a, u64 *tsp_half, u32 fpmask) {
   constexpr int NB = 1 << (LOGN - 10);
-  const int nl = a.nl;
+  const KsOperands &o = a.ops;
+  const int nl = o.nl;
+  const size_t cc = o.count;
   const size_t lds_sp = (size_t)((nl < 2 ? 2 : nl) * lds_words(10)) * 8;
   // data primes of the integer main kernel / of the fp64 main kernel, one nibble each
   MainArgs ai = a, af = a;
@@ -582,31 +584,31 @@ static void launch_isplit_tail(abc_hip_ctx *c, int mode, const MainArgs &a, u64 
   // one scratch, two arithmetic classes: limbs modulo the primes of fpmask hold doubles (af), the others u64 (ai)
   const u64 *part = (const u64 *)a.part, *tpart = (const u64 *)a.tpart;
   dispatch_nl<1, (LOGN == 15 ? 15 : 7)>(nl, [&](auto NL) {
-    hipLaunchKernelGGL((k_isplit_special<GUARD, decltype(NL)::value, LOGN>), dim3((unsigned)(a.cc * NB)), dim3(64 * decltype(NL)::value), lds_sp,
-                       a.st, c->dc, part, a.key, tsp_half);
+    hipLaunchKernelGGL((k_isplit_special<GUARD, decltype(NL)::value, LOGN>), dim3((unsigned)(cc * NB)), dim3(64 * decltype(NL)::value), lds_sp,
+                       a.st, c->dc, part, o.key, tsp_half);
   });
-  hipLaunchKernelGGL((k_isplit_pass<LOGN, GUARD>), dim3((unsigned)(a.cc * 2 * 4)), dim3(256), 0, a.st, c->dc, tsp_half, (u64 *)a.tpart, nl,
+  hipLaunchKernelGGL((k_isplit_pass<LOGN, GUARD>), dim3((unsigned)(cc * 2 * 4)), dim3(256), 0, a.st, c->dc, tsp_half, (u64 *)a.tpart, nl,
                      fpmask);
   if (ai.ni) {
-    const dim3 gmain((unsigned)(a.cc * ai.ni * NB));
-    dispatch_mode(mode, a.gelt, [&](auto M, auto G) {
+    const dim3 gmain((unsigned)(cc * ai.ni * NB));
+    dispatch_mode(o.mode, o.gather, [&](auto M, auto G) {
       constexpr int MODE = decltype(M)::value;
       constexpr bool GAL = decltype(G)::value;
       if constexpr (LOGN == 15) {
         if (nl > 7) {
           hipLaunchKernelGGL((k_isplit_main_deep<MODE, GAL, GUARD, LOGN>), gmain, dim3(1024), main_lds_bytes(nl, sizeof(u64x2)), a.st, c->dc, part, tpart,
-                             a.opa, a.opb, a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, nl, ai.imap, ai.ni);
+                             o.target, o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, o.gather, nl, ai.imap, ai.ni);
           return;
         }
       }
       dispatch_nl<1, 7>(nl, [&](auto NL) {
         hipLaunchKernelGGL((k_isplit_main<MODE, GAL, decltype(NL)::value, GUARD, LOGN>), gmain, dim3(512), main_lds_bytes(nl, sizeof(u64x2)), a.st, c->dc,
-                           part, tpart, a.opa, a.opb, a.opa_stride, a.opb_stride, a.add_c1, a.key, a.out, a.gelt, (u32)ai.imap, ai.ni);
+                           part, tpart, o.target, o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, o.gather, (u32)ai.imap, ai.ni);
       });
     });
   }
-  if (af.ni && LOGN == 14) split4_main(c, mode, af);
-  else if (af.ni) gsplit_main15(c, mode, af);
+  if (af.ni && LOGN == 14) split4_main(c, af);
+  else if (af.ni) gsplit_main15(c, af);
 }
 
 // scratch (words, limb stride c->dc.ps): part nl(nl+1) | tpart 2 nl | tsp_half 2
@@ -615,35 +617,36 @@ size_t isplit_scratch_words(const abc_hip_ctx *c, int nl) {
   return ((size_t)nl * (nl + 1) + 2 * (size_t)nl + 2 + (c->logn == 15 ? (size_t)nl : 0)) * (size_t)c->dc.ps;
 }
 
-// one chunk of a multiply (mode 0: opa = a, opb = b) or of a key switch (mode 1: opa = operand in NTT form, opb = addend)
-int isplit_chunk(abc_hip_ctx *c, hipStream_t st, u64 *scratch, size_t cc, int nl, int mode, const u64 *opa, const u64 *opb,
-                 size_t opa_stride, size_t opb_stride, int add_c1, const u64 *key, u64 *out, u32 gelt, const ChunkRoute &k) {
-  const size_t PS = (size_t)c->dc.ps;
+// one chunk of a multiply or of a key switch (o.mode)
+int isplit_chunk(abc_hip_ctx *c, hipStream_t st, u64 *scratch, const KsOperands &o, const ChunkRoute &k) {
+  const size_t PS = (size_t)c->dc.ps, cc = o.count;
+  const int nl = o.nl;
   u64 *part = scratch, *tpart = part + cc * (size_t)nl * (nl + 1) * PS, *tsp = tpart + cc * 2 * (size_t)nl * PS;
   const bool guard = k.guard;
   const u32 fpmask = k.fpmask;  // data primes below 2^50 take the fp64 kernels (ABC_HIP_NO_FP64 / ABC_HIP_NO_MIXED: integers throughout)
-  const MainArgs a{st, cc, nl, part, tpart, opa, opb, opa_stride, opb_stride, add_c1, key, out, gelt, kAllSlots, nl, 0};
+  MainArgs a;
+  a.st = st, a.ops = o, a.part = part, a.tpart = tpart, a.ni = nl;
   auto with_guard = [&](auto GD) {
     constexpr bool GUARD = decltype(GD)::value;
     if (c->logn == 15) {
       u64 *hinv = tsp + cc * 2 * PS;
       const dim3 ga((unsigned)(((cc + 3) / 4) * nl * 32)), gb((unsigned)(cc * nl * 4));
       const size_t lds = (size_t)(4 * lds_words(10)) * 8 + 1024 * 16;
-      dispatch_mode(mode, gelt, [&](auto M, auto G) {
+      dispatch_mode(o.mode, o.gather, [&](auto M, auto G) {
         constexpr int MODE = decltype(M)::value;
-        hipLaunchKernelGGL((k_igsplit_inv_tails<15, MODE, decltype(G)::value>), ga, dim3(256), lds, st, c->dc, opa, MODE ? nullptr : opb,
-                           MODE ? opa_stride : 0, hinv, nl, (int)cc, gelt);
+        hipLaunchKernelGGL((k_igsplit_inv_tails<15, MODE, decltype(G)::value>), ga, dim3(256), lds, st, c->dc, o.target,
+                           MODE ? nullptr : o.addend, MODE ? o.target_stride : 0, hinv, nl, (int)cc, o.gather);
       });
       hipLaunchKernelGGL((k_igsplit_cross<15, GUARD>), gb, dim3(256), 0, st, c->dc, hinv, part, nl, fpmask);
-      launch_isplit_tail<GUARD, 15>(c, mode, a, tsp, fpmask);
+      launch_isplit_tail<GUARD, 15>(c, a, tsp, fpmask);
       return;
     }
-    dispatch_mode(mode, gelt, [&](auto M, auto G) {
+    dispatch_mode(o.mode, o.gather, [&](auto M, auto G) {
       constexpr bool KS = decltype(M)::value != 0;
-      hipLaunchKernelGGL((k_isplit_pass0<14, GUARD, KS, decltype(G)::value>), dim3((unsigned)(cc * nl)), dim3((1 << 14) / 16), 0, st, c->dc, opa,
-                         KS ? nullptr : opb, KS ? opa_stride : 0, part, nl, gelt, fpmask);
+      hipLaunchKernelGGL((k_isplit_pass0<14, GUARD, KS, decltype(G)::value>), dim3((unsigned)(cc * nl)), dim3((1 << 14) / 16), 0, st, c->dc, o.target,
+                         KS ? nullptr : o.addend, KS ? o.target_stride : 0, part, nl, o.gather, fpmask);
     });
-    launch_isplit_tail<GUARD, 14>(c, mode, a, tsp, fpmask);
+    launch_isplit_tail<GUARD, 14>(c, a, tsp, fpmask);
   };
   if (guard) with_guard(std::true_type{});
   else with_guard(std::false_type{});

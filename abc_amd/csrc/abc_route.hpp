@@ -72,7 +72,7 @@ enum class Seq {
   split14,     // CKKS, N = 2^14, fp64: tensor / operand pass 0 (lean or fat), special, pass, main (split4 or split3)
   gsplit15,    // CKKS, N = 2^15, fp64 (abc_kernels_gsplit.hip)
   isplit,      // CKKS, N = 2^14 / 2^15, a prime above 2^50: integer split kernels, fp64 for the limbs in fpmask (abc_kernels_isplit.hip)
-  bsplit14,    // BFV, N = 2^14, fp64: operand pass 0 + bsplit_back14
+  bsplit14,    // BFV, N = 2^14, fp64: operand pass 0 + bsplit_back<14>
   bsplit_big,  // BFV, N = 2^13 / 2^15 / 2^16, fp64 (bsplit_big)
   lds_fp,      // LDS-resident limbs, fp64
   lds_int,     // LDS-resident limbs, integers (guard / lazy)
@@ -179,37 +179,35 @@ inline MulRoute route_mul_relin(const RouteFacts &f, int nl) {
   return {Seq::generic, route_bfv_multiply(f), route_keyswitch(f, nl)};
 }
 
-// one Galois element at level nl
+// ---- what the launch code of a sequence can do (launch_keyswitch checks a call against these, once) ----
+// the Galois gather folded into the first and the last kernels: the CKKS split sequences; BFV: the split sequences and the
+// fused integer front of the big rings (k_iks_pass0 / k_iks_finish).  The LDS-resident kernels take the permuted ciphertext
+inline bool seq_folds_permutation(const RouteFacts &f, const KsRoute &r) {
+  const Seq s = r.seq;
+  if (f.scheme == 2) return s == Seq::split14 || s == Seq::isplit || s == Seq::gsplit15;
+  return s == Seq::bsplit14 || s == Seq::bsplit_big || (s == Seq::generic && r.front == KsFront::iks);
+}
+// a second, ungathered ciphertext as one more operand of the last kernel (k_split4_main_fp / k_split3_main_fp, k_gsplit_main up to
+// seven limbs -- k_gsplit_main_deep does not -- k_bsplit_finish_big / k_bsplit_finish_lds)
+inline bool seq_takes_acc(const RouteFacts &, const KsRoute &r, int nl) {
+  const Seq s = r.seq;
+  return s == Seq::split14 || s == Seq::bsplit14 || s == Seq::bsplit_big || (s == Seq::gsplit15 && nl <= 7);
+}
+
+// one Galois element at level nl: the key switch of the level, with the permutation folded into it where its sequence gathers
 inline RotRoute route_rotate(const RouteFacts &f, int nl, bool in_place) {
-  using namespace route_detail;
-  const bool may_fold = !in_place && !f.sw.no_galois_fusion;
-  if (may_fold && f.logn == 15 && gsplit_ok(f, nl)) return {true, {Seq::gsplit15, KsFront::plain}};
-  if (may_fold && f.logn == 15 && f.scheme == 2 && !f.all_fp && isplit_ok(f, nl)) return {true, {Seq::isplit, KsFront::plain}};
-  if (may_fold && f.scheme == 1) {
-    if (!f.sw.no_split && !f.sw.no_fused) {
-      if (f.logn == 14 && bsplit_ok(f, nl)) return {true, {Seq::bsplit14, KsFront::plain}};
-      if (bsplit_big_ok(f, nl)) return {true, {Seq::bsplit_big, KsFront::plain}};
-    }
-    // a big ring with a prime above 2^50: k_iks_pass0 / k_iks_finish gather
-    if ((f.logn == 15 || f.logn == 16) && route_ks_front(f, nl) == KsFront::iks && !bsplit_big_ok(f, nl)) return {true, {Seq::generic, KsFront::iks}};
-  }
-  if (may_fold && f.logn == 14 && f.scheme == 2 && !f.sw.no_split && !f.sw.no_fused) {
-    // only the split sequences gather; the LDS-resident kernels (all-fp chains above twelve limbs) take the permuted ciphertext
-    const Seq s = lds_seq(f, nl, false);
-    if (s == Seq::split14 || s == Seq::isplit) return {true, {s, KsFront::plain}};
-  }
-  return {false, route_keyswitch(f, nl)};
+  const KsRoute ks = route_keyswitch(f, nl);
+  bool fold = !in_place && !f.sw.no_galois_fusion && seq_folds_permutation(f, ks);
+  // bsplit_big is chosen whatever these two say, but a rotation under either switch takes the permuted ciphertext (A/B, tests)
+  if (ks.seq == Seq::bsplit_big && (f.sw.no_split || f.sw.no_fused)) fold = false;
+  return {fold, ks};
 }
 
 // addend + one Galois element at level nl; in_place: d_out == d_in (the gather reads whole limbs of d_in, so that call is never
-// fused).  Only the last kernels of these four sequences take the ungathered operand (k_split4_main_fp / k_split3_main_fp,
-// k_gsplit_main up to seven limbs, k_bsplit_finish_big / k_bsplit_finish_lds).  `rot` is the rotation either way: the unfused
-// sequence rotates into an arena, never in place, whatever d_out is.
+// fused).  `rot` is the rotation either way: the unfused sequence rotates into an arena, never in place, whatever d_out is.
 inline RotAddRoute route_rotate_add(const RouteFacts &f, int nl, bool in_place) {
   const RotRoute rot = route_rotate(f, nl, false);
-  const Seq s = rot.ks.seq;
-  const bool takes_acc = s == Seq::split14 || s == Seq::bsplit14 || s == Seq::bsplit_big || (s == Seq::gsplit15 && nl <= 7);
-  return {rot, rot.fold && takes_acc && !in_place && !f.sw.no_rotate_add_fusion};
+  return {rot, rot.fold && seq_takes_acc(f, rot.ks, nl) && !in_place && !f.sw.no_rotate_add_fusion};
 }
 
 inline RescaleRoute route_rescale(const RouteFacts &f, int nl, bool in_place) {

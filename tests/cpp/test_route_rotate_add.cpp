@@ -96,6 +96,40 @@ int main() {
     EXPECT_TRUE(fused_n > 100 && separate_n > 100);
   });
 
+  // The launch code checks a call against seq_folds_permutation / seq_takes_acc (launch_keyswitch) and nothing else: a route that
+  // folds or fuses must name a sequence that can.  Both schemes on every ring 2^10 .. 2^16, chains with every prime fp64-capable and
+  // with wider ones, every switch, every level.
+  t.run("a route folds / fuses only where the sequence can; fused is the old expression", [&] {
+    const std::vector<std::vector<int>> chains = {
+        HEAD, {60, 40, 40, 40, 60}, {55, 52, 51, 55}, {50, 40, 58, 40, 50}, chain(48, 48, 8, 49), chain(55, 55, 7, 56), chain(50, 40, 14, 50),
+        chain(60, 40, 14, 60), {36, 36, 37}};
+    size_t folds = 0, fused_n = 0, total = 0;
+    for (int scheme : {BFV, CKKS})
+      for (int logn = 10; logn <= 16; logn++)
+        for (const std::vector<int> &bits : chains)
+          for (bool behz_fp : {true, false})
+            for (const Set &set : switches)
+              for (int nl = 1; nl <= (int)bits.size() - 1; nl++)
+                for (bool in_place : {false, true}) {
+                  RouteFacts f = facts(scheme, logn, bits, behz_fp);
+                  set(f);
+                  f.finish();
+                  const RotRoute rot = route_rotate(f, nl, in_place);
+                  if (rot.fold) EXPECT_TRUE(seq_folds_permutation(f, rot.ks));
+                  const RotAddRoute r = route_rotate_add(f, nl, in_place);
+                  if (r.fused) EXPECT_TRUE(r.rot.fold && seq_folds_permutation(f, r.rot.ks) && seq_takes_acc(f, r.rot.ks, nl));
+                  // what route_rotate_add computed before the predicates existed, word for word
+                  const Seq s = r.rot.ks.seq;
+                  const bool takes_acc = s == Seq::split14 || s == Seq::bsplit14 || s == Seq::bsplit_big || (s == Seq::gsplit15 && nl <= 7);
+                  EXPECT_TRUE(r.fused == (r.rot.fold && takes_acc && !in_place && !f.sw.no_rotate_add_fusion));
+                  EXPECT_TRUE(seq_takes_acc(f, r.rot.ks, nl) == takes_acc);
+                  folds += rot.fold;
+                  fused_n += r.fused;
+                  total++;
+                }
+    EXPECT_TRUE(folds > 1000 && fused_n > 1000 && total - folds > 1000);
+  });
+
   t.run("the documented strings", [&] {
     const RouteFacts f = facts(CKKS, 14, HEAD);
     EQ(radd(f, 4), "fold+add split14 front=lean pack=1 main=split4");

@@ -66,6 +66,30 @@ def rotate_add_ab(res, only, rng):
         g.close()
 
 
+def keyswitch_batch1(res, only, rng):
+    """one ciphertext per call at nl = 4: relinearise, rotate and rotate_add on the two CKKS split rings -- the calls in which the
+    host side of the key switch (routes, operand record, launches) is the largest share"""
+    for n in (16384, 32768):
+        names = ["ckks%d_b1_%s" % (n.bit_length() - 1, op) for op in ("relinearize", "rotate", "rotate_add")]
+        if not any(only in k for k in names):
+            continue
+        g = capi.Context(capi.CKKS, n, capi.create_primes(n, [50, 40, 40, 40, 50]))
+        g.keygen(1)
+        one = C.c_size_t(1)
+        (a, nb), (b, _), (t3, _) = rand_ct(g, rng, 1, 2, 4), rand_ct(g, rng, 1, 2, 4), rand_ct(g, rng, 1, 3, 4)
+        out = g.alloc(nb)
+        ops = (lambda: g.op("relinearize", t3.ptr, out.ptr, 4, one), lambda: g.op("rotate", a.ptr, out.ptr, 4, 1, one),
+               lambda: g.op("rotate_add", a.ptr, b.ptr, out.ptr, 4, 1, one))
+        for k, fn in zip(names, ops):
+            if only in k:
+                timeit(g, fn, reps=20)
+                ms = timeit(g, fn, reps=300)
+                res[k] = {"batch": 1, "ms": ms, "route": g.route(k.split("_b1_")[1], 4, 1)}
+                print("%-40s %8.3f us (batch 1; %s)" % (k, ms * 1e3, res[k]["route"]), flush=True)
+        del a, b, t3, out
+        g.close()
+
+
 def main():
     # --only SUBSTRING: the entries whose name contains it (the contexts are still created)
     only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else ""
@@ -207,6 +231,7 @@ def main():
         del a, b, out, dec, plains
         g.close()
     rotate_add_ab(res, only, rng)
+    keyswitch_batch1(res, only, rng)
     os.makedirs("gpurun_out", exist_ok=True)
     json.dump(res, open("gpurun_out/op_bench.json", "w"), indent=1)
 
