@@ -37,6 +37,7 @@ SYMBOLS = [
     "abc_hip_encrypt_keyed", "abc_hip_keygen_keyed", "abc_hip_keyed_small", "abc_hip_keyed_uniform", "abc_hip_keyed_small_host",
     "abc_hip_apply_galois_hoisted", "abc_hip_rotate_hoisted",
     "abc_hip_rotate_add", "abc_hip_apply_galois_add", "abc_hip_rotate_sum",
+    "abc_hip_rotate_mac_plain", "abc_hip_apply_galois_mac_plain", "abc_hip_diag_matvec",
 ]
 
 
@@ -68,6 +69,10 @@ def lib():
         L.abc_hip_rotate_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t]
         L.abc_hip_apply_galois_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_size_t]
         L.abc_hip_rotate_sum.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_size_t]
+        if hasattr(L, "abc_hip_rotate_mac_plain"):  # not in a build older than these calls (ABC_HIP_LIB: A/B against a parent build)
+            L.abc_hip_rotate_mac_plain.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t]
+            L.abc_hip_apply_galois_mac_plain.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_size_t]
+            L.abc_hip_diag_matvec.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int, C.c_size_t]
         L.abc_hip_encrypt_keyed.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_size_t]
         L.abc_hip_keygen_keyed.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
         L.abc_hip_keyed_small.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_size_t]
@@ -197,7 +202,8 @@ class Context:
     def reload_env(self):
         _chk(lib().abc_hip_ctx_reload_env(self.h))
 
-    ROUTE_OPS = {"mul_relin": 0, "keyswitch": 1, "relinearize": 1, "rotate": 2, "rescale": 3, "multiply": 4, "rotate_add": 5}
+    ROUTE_OPS = {"mul_relin": 0, "keyswitch": 1, "relinearize": 1, "rotate": 2, "rescale": 3, "multiply": 4, "rotate_add": 5,
+                 "rotate_mac_plain": 7}
 
     def route(self, op, nl, count=1, in_place=False):
         """the kernel sequence such a call takes, as the string of abc_route.hpp's formatter"""
@@ -377,6 +383,51 @@ class Context:
         steps = [int(x) for x in steps]
         arr = (C.c_int * max(len(steps), 1))(*steps)
         r = self._run("rotate_sum", [a4], a4.shape, a4.shape[2], arr, len(steps), C.c_size_t(a4.shape[0]))
+        return r if np.ndim(ct) == 4 else r[0]
+
+    def _mac_plain(self, name, ct, plain, addend, arg):
+        a4 = self._batch(ct, 3)
+        count, nl = a4.shape[0], a4.shape[2]
+        plain = np.ascontiguousarray(plain, dtype=np.uint64)
+        # [nl][N]: broadcast; [count][rows][N] with rows >= nl: one per ciphertext, rows * N apart (rows encoded for a higher level)
+        stride = 0 if plain.ndim == 2 else plain.shape[1] * self.n
+        bufs = [self.upload(a4), self.upload(plain)]
+        if addend is not None:
+            bufs.append(self.upload(self._batch(addend, 3)))
+        out = self.alloc(a4.nbytes)
+        try:
+            self.op(name, bufs[0].ptr, bufs[1].ptr, C.c_size_t(stride), bufs[2].ptr if addend is not None else None, out.ptr, nl, arg,
+                    C.c_size_t(count))
+            r = self.download(out, a4.shape)
+        finally:
+            for b in bufs + [out]:
+                b.free()
+        return r if np.ndim(ct) == 4 else r[0]
+
+    def rotate_mac_plain(self, ct, plain, addend, steps):
+        """addend + plain (.) rotate(ct, steps) as one call (abc_hip_rotate_mac_plain), CKKS; addend may be None.  plain: [nl][N] for
+        the batch, or [count][rows >= nl][N], one per ciphertext.  Fused into the key switch where route("rotate_mac_plain") says so"""
+        return self._mac_plain("rotate_mac_plain", ct, plain, addend, int(steps))
+
+    def apply_galois_mac_plain(self, ct, plain, addend, elt):
+        """the same for one Galois element"""
+        return self._mac_plain("apply_galois_mac_plain", ct, plain, addend, C.c_uint32(elt))
+
+    def diag_matvec(self, ct, diags, steps):
+        """sum over r of diags[r] (.) rotate(ct, steps[r]) (abc_hip_diag_matvec), CKKS; diags [len(steps)][rows >= nl][N], one set for the batch"""
+        a4 = self._batch(ct, 3)
+        steps = [int(x) for x in steps]
+        diags = np.ascontiguousarray(diags, dtype=np.uint64).reshape(len(steps), -1, self.n) if steps else np.zeros((0, a4.shape[2], self.n), np.uint64)
+        arr = (C.c_int * max(len(steps), 1))(*steps)
+        cb, db = self.upload(a4), self.upload(diags if diags.size else np.zeros(1, dtype=np.uint64))
+        out = self.alloc(a4.nbytes)
+        try:
+            stride = diags.shape[1] * self.n
+            self.op("diag_matvec", cb.ptr, db.ptr, C.c_size_t(stride), arr, len(steps), out.ptr, a4.shape[2], C.c_size_t(a4.shape[0]))
+            r = self.download(out, a4.shape)
+        finally:
+            for b in (cb, db, out):
+                b.free()
         return r if np.ndim(ct) == 4 else r[0]
 
     def _plain_op(self, name, ct, plain):

@@ -43,6 +43,7 @@ void read_switches(abc_hip_ctx *c) {
   s.no_tensor_intt = env_on("ABC_HIP_NO_TENSOR_INTT");
   s.no_galois_fusion = env_on("ABC_HIP_NO_GALOIS_FUSION");
   s.no_rotate_add_fusion = env_on("ABC_HIP_NO_ROTATE_ADD_FUSION");
+  s.no_rotate_mac_fusion = env_on("ABC_HIP_NO_ROTATE_MAC_FUSION");
   s.main_two_per_cu = env_on("ABC_HIP_MAIN_TWO_PER_CU");
   s.host_sampling = env_on("ABC_HIP_HOST_SAMPLING");
   if (const char *e = std::getenv("ABC_HIP_CHUNK")) s.chunk = (size_t)std::atol(e);
@@ -389,9 +390,10 @@ static KsOperands ks_of_ciphertexts(const abc_hip_ctx *c, const u64 *ct, int siz
   return o;
 }
 
-// one Galois element along route r; acc (RotAddRoute::fused only): a second ciphertext added in the key switch's last kernel
+// one Galois element along route r; acc (RotAddRoute::fused only): a second ciphertext added in the key switch's last kernel;
+// plain (RotMacRoute::fused only): a plaintext that multiplies the result there, before acc -- then optional -- is added
 static int apply_galois_routed(abc_hip_ctx *c, const RotRoute &r, const u64 *in, u64 *out, int nl, uint32_t elt, size_t count,
-                               const u64 *acc = nullptr) {
+                               const u64 *acc = nullptr, const u64 *plain = nullptr, size_t plain_stride = 0) {
   auto it = c->d_galois.find(elt);
   if (it == c->d_galois.end()) { set_error("Galois key not present"); return 1; }
   if (!count) return 0;
@@ -403,7 +405,7 @@ static int apply_galois_routed(abc_hip_ctx *c, const RotRoute &r, const u64 *in,
   }
   KsOperands o = ks_of_ciphertexts(c, in, 2, it->second, out, nl, count);
   o.gelt = r.fold ? elt : 0u;
-  o.acc = acc;
+  o.acc = acc, o.plain = plain, o.plain_stride = plain_stride;
   return launch_keyswitch(c, r.ks, o);
 }
 static int apply_galois(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, uint32_t elt, size_t count) {
@@ -483,6 +485,69 @@ static int rotate_add(abc_hip_ctx *c, const u64 *in, const u64 *addend, u64 *out
   const size_t last = terms.size() - 1;
   if (rotate_hops(c, cur, nl, terms, 0, last, count)) return 1;
   return apply_galois_add(c, cur, addend, out, nl, elt_from_step(c, terms[last]), count, 1 + (int)(last & 1));
+}
+
+// out = addend + plain (.) x for a ciphertext x that no output overlaps (step 0's input, or a rotation in an arena): the product in
+// place on x where it is scratch, else in arena `tmp_arena`, then the add kernel; without an addend the product lands in `out`
+static int mac_separate(abc_hip_ctx *c, u64 *x_scratch, const u64 *x, const u64 *plain, size_t plain_stride, const u64 *addend, u64 *out,
+                        int nl, size_t count, int tmp_arena) {
+  if (!addend) return ckks_multiply_plain(c, x, plain, plain_stride, out, 2, nl, count);
+  if (!x_scratch) {
+    if (ensure_aux(c, tmp_arena, count * 2 * nl * (size_t)c->n * 8)) return 1;
+    x_scratch = (u64 *)c->aux[tmp_arena];
+  }
+  if (ckks_multiply_plain(c, x, plain, plain_stride, x_scratch, 2, nl, count)) return 1;
+  return launch_addsub(c, addend, x_scratch, out, nl, count * 2, 0);
+}
+
+// out = addend + plain (.) g(in), CKKS (abc_hip_apply_galois_mac_plain, and the last hop of rotate_mac_plain); addend may be null.
+// Fused: plaintext and addend are operands of the key switch's last kernel; `out` may be `addend` there, and is never `in`.
+// Otherwise the rotation lands in arena `tmp_arena`, multiply_plain runs on it in place, and the add kernel follows.
+static int apply_galois_mac(abc_hip_ctx *c, const u64 *in, const u64 *plain, size_t plain_stride, const u64 *addend, u64 *out, int nl,
+                            uint32_t elt, size_t count, int tmp_arena) {
+  if (!c->d_galois.count(elt)) { set_error("Galois key not present"); return 1; }
+  if (!count) return 0;
+  const RotMacRoute r = route_rotate_mac(c->facts, nl, in == out);
+  if (r.fused) return apply_galois_routed(c, r.rot, in, out, nl, elt, count, addend, plain, plain_stride);
+  if (ensure_aux(c, tmp_arena, count * 2 * nl * (size_t)c->n * 8)) return 1;
+  u64 *tmp = (u64 *)c->aux[tmp_arena];
+  if (apply_galois_routed(c, r.rot, in, tmp, nl, elt, count)) return 1;
+  return mac_separate(c, tmp, tmp, plain, plain_stride, addend, out, nl, count, tmp_arena);
+}
+
+// out = addend + plain (.) rotate(in, steps): every hop but the last as rotate() runs it, the last one with the plaintext and the
+// addend.  Step 0 has no key switch: multiply_plain, then add.
+static int rotate_mac(abc_hip_ctx *c, const u64 *in, const u64 *plain, size_t plain_stride, const u64 *addend, u64 *out, int nl, int steps,
+                      size_t count) {
+  if (steps == 0) return count ? mac_separate(c, nullptr, in, plain, plain_stride, addend, out, nl, count, 1) : 0;
+  std::vector<int> terms;
+  if (rotation_terms(c, steps, terms)) return 1;
+  if (!count) return 0;
+  const u64 *cur = in;
+  const size_t last = terms.size() - 1;
+  if (rotate_hops(c, cur, nl, terms, 0, last, count)) return 1;
+  return apply_galois_mac(c, cur, plain, plain_stride, addend, out, nl, elt_from_step(c, terms[last]), count, 1 + (int)(last & 1));
+}
+
+// out = sum_r diags[r] (.) rotate(in, steps[r]), in the order given: the running sum lives in `out`, every term after the first is
+// one rotate_mac with out as its addend
+static int diag_matvec(abc_hip_ctx *c, const u64 *in, const u64 *diags, size_t diag_stride, const std::vector<int> &steps, u64 *out, int nl,
+                       size_t count) {
+  const size_t ctw = count * 2 * (size_t)nl * c->n;
+  for (int s : steps) {  // every step and every key is checked before the first launch
+    std::vector<int> terms;
+    if (s && rotation_terms(c, s, terms)) return 1;
+  }
+  if (!count) return 0;
+  const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out;
+  if (i0 < o0 + ctw * 8 && o0 < i0 + ctw * 8) { set_error("diag_matvec: d_out must not overlap d_in"); return 1; }
+  if (steps.empty()) {
+    ABC_HIP_CHECK(hipMemsetAsync(out, 0, ctw * 8, c->stream));
+    return 0;
+  }
+  for (size_t r = 0; r < steps.size(); r++)
+    if (rotate_mac(c, in, diags + r * diag_stride, 0, r ? out : nullptr, out, nl, steps[r], count)) return 1;
+  return 0;
 }
 
 // acc = in; acc = acc + rotate(acc, s) for each step in order; out = acc.  The running sums ping-pong through arenas 3 and 4
@@ -945,6 +1010,18 @@ static int check_plain_stride(abc_hip_ctx *c, const char *op, size_t plain_strid
   set_error(std::string(op) + (ckks ? ": plain_stride must be 0 or at least nl * N" : ": plain_stride must be 0 or N"));
   return 1;
 }
+// what the plaintext calls check before anything else: a CKKS context, the stride, and that `plain` (rows of nl * N words, `rows`
+// of them `stride` apart) stays clear of the `out_words` words at `out`
+static int check_mac_plain(abc_hip_ctx *c, const char *op, const u64 *plain, size_t stride, size_t rows, const u64 *out, size_t out_words,
+                           int nl) {
+  if (c->scheme != ABC_HIP_SCHEME_CKKS) { set_error(std::string(op) + ": CKKS only (a BFV plaintext product needs transforms and is no fold of the key switch)"); return 1; }
+  if (check_plain_stride(c, op, stride, nl)) return 1;
+  const size_t plain_words = rows ? (rows - 1) * stride + (size_t)nl * c->n : 0;
+  const uintptr_t p0 = (uintptr_t)plain, o0 = (uintptr_t)out;
+  if (plain_words && out_words && p0 < o0 + out_words * 8 && o0 < p0 + plain_words * 8) { set_error(std::string(op) + ": the plaintext must not overlap d_out"); return 1; }
+  return 0;
+}
+
 int abc_hip_route(abc_hip_ctx *c, int op, int nl, size_t count, int in_place, char *buf, size_t cap) {
   CTX_GUARD(c);
   if (check_level(c, nl)) return 1;  // nl as the operation itself takes it (BFV: L, also for multiply)
@@ -1015,6 +1092,27 @@ int abc_hip_apply_galois_add(abc_hip_ctx *c, const uint64_t *in, const uint64_t 
   CTX_GUARD(c);
   if (check_level(c, nl)) return 1;
   return apply_galois_add(c, in, addend, out, nl, elt, count, 1);
+}
+int abc_hip_rotate_mac_plain(abc_hip_ctx *c, const uint64_t *in, const uint64_t *plain, size_t plain_stride, const uint64_t *addend,
+                             uint64_t *out, int nl, int steps, size_t count) {
+  CTX_GUARD(c);
+  if (check_level(c, nl) || check_mac_plain(c, "rotate_mac_plain", plain, plain_stride, plain_stride ? count : 1, out, count * 2 * (size_t)nl * c->n, nl)) return 1;
+  return guarded([&] { return rotate_mac(c, in, plain, plain_stride, addend, out, nl, steps, count); });
+}
+int abc_hip_apply_galois_mac_plain(abc_hip_ctx *c, const uint64_t *in, const uint64_t *plain, size_t plain_stride, const uint64_t *addend,
+                                   uint64_t *out, int nl, uint32_t elt, size_t count) {
+  CTX_GUARD(c);
+  if (check_level(c, nl) || check_mac_plain(c, "apply_galois_mac_plain", plain, plain_stride, plain_stride ? count : 1, out, count * 2 * (size_t)nl * c->n, nl)) return 1;
+  return apply_galois_mac(c, in, plain, plain_stride, addend, out, nl, elt, count, 1);
+}
+int abc_hip_diag_matvec(abc_hip_ctx *c, const uint64_t *in, const uint64_t *diags, size_t diag_stride, const int *h_steps, int n_steps,
+                        uint64_t *out, int nl, size_t count) {
+  CTX_GUARD(c);
+  if (check_level(c, nl)) return 1;
+  if (n_steps < 0 || (n_steps && !h_steps)) { set_error("diag_matvec: bad step list"); return 1; }
+  if (diag_stride < (size_t)nl * c->n) { set_error("diag_matvec: diag_stride must be at least nl * N"); return 1; }
+  if (check_mac_plain(c, "diag_matvec", diags, diag_stride, (size_t)n_steps, out, count * 2 * (size_t)nl * c->n, nl)) return 1;
+  return guarded([&] { return diag_matvec(c, in, diags, diag_stride, std::vector<int>(h_steps, h_steps + n_steps), out, nl, count); });
 }
 int abc_hip_rotate_sum(abc_hip_ctx *c, const uint64_t *in, uint64_t *out, int nl, const int *h_steps, int n_steps, size_t count) {
   CTX_GUARD(c);

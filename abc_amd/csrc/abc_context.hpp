@@ -232,8 +232,8 @@ inline unsigned grid_for(size_t items, int block) {
     if ((c)->buffers.capturing) { abc::set_error(what ": not capturable (host transfer / synchronisation inside abc_hip_graph_begin..end)"); return 1; } \
   } while (0)
 
-// One key switch as every layer from the C ABI to the launch passes it on: out[ct] = KeySwitch(target[ct]) (+ addend[ct]) (+ acc[ct])
-// for `count` ciphertexts of nl limbs.  mode 0 is the CKKS multiply + relinearise of the split sequences: target / addend are the
+// One key switch as every layer from the C ABI to the launch passes it on: out[ct] = KeySwitch(target[ct]) (+ addend[ct]) (+ acc[ct]),
+// or acc[ct] + plain[ct] (.) (KeySwitch(target[ct]) + addend[ct]) with a plaintext, for `count` ciphertexts of nl limbs.  mode 0 is the CKKS multiply + relinearise of the split sequences: target / addend are the
 // factors a / b, both [2][nl][N] per ciphertext.
 struct KsOperands {
   int mode = 1;  // 0 multiply, 1 key switch (dispatch_mode)
@@ -245,6 +245,10 @@ struct KsOperands {
   const u64 *key = nullptr;  // the key-switching key
   u64 *out = nullptr;        // [count][2][nl][N]
   const u64 *acc = nullptr;  // with gelt only: a second, ungathered ciphertext [count][2][nl][N] added in the last kernel (RotAddRoute::fused)
+  // with gelt only: a CKKS plaintext, [nl][N] at plain + ct * plain_stride (0: one for all), that multiplies either component of the
+  // result before acc -- which may then be null -- is added (RotMacRoute::fused)
+  const u64 *plain = nullptr;
+  size_t plain_stride = 0;
   u32 gelt = 0;              // the Galois element of a rotation folded into the sequence (RotRoute::fold): target = c1, addend = c0
   u32 gather = 0;            // what the kernels gather with: gelt (CKKS, NTT form) or gelt^-1 mod 2N (BFV); launch_keyswitch fills it
   int nl = 0;
@@ -257,6 +261,7 @@ struct KsOperands {
     if (addend) s.addend = addend + off * addend_stride;
     s.out = out + off * ctw;
     if (acc) s.acc = acc + off * ctw;
+    if (plain) s.plain = plain + off * plain_stride;
     s.count = cc;
     return s;
   }
@@ -331,8 +336,8 @@ int keygen_keyed(abc_hip_ctx *c, const uint8_t key_sec[32], const uint8_t key_pu
 int keyed_small(abc_hip_ctx *c, const uint8_t key[32], uint64_t nonce, int8_t *d_small, size_t count);
 int keyed_uniform(abc_hip_ctx *c, const uint8_t key[32], uint64_t stream, int nkeys, u64 *d_a);
 
-// the key switch o along route r (abc_kernels_fused.hip; any sequence).  o.gelt and o.acc are checked here, once, against what the
-// sequence can do (seq_folds_permutation, seq_takes_acc); the sequences below check nothing again
+// the key switch o along route r (abc_kernels_fused.hip; any sequence).  o.gelt, o.acc and o.plain are checked here, once, against what the
+// sequence can do (seq_folds_permutation, seq_takes_acc, seq_takes_plain); the sequences below check nothing again
 int launch_keyswitch(abc_hip_ctx *c, const KsRoute &r, const KsOperands &o);
 // CKKS multiply + relinearise in one sequence (every Seq but bmul and generic)
 int launch_mul_relin(abc_hip_ctx *c, Seq seq, const u64 *a, const u64 *b, u64 *out, int nl, size_t count);
@@ -361,6 +366,25 @@ struct AccArg {
 };
 __host__ __device__ inline const u64 *acc_ptr() { return nullptr; }
 __host__ __device__ inline const u64 *acc_ptr(AccArg<WithAcc> a) { return a.p; }
+// <.., WithMac>: rotate_mac_plain, out = acc + plain (.) result.  One more argument again, the three operands: the plaintext
+// [nl][N] at plain + ct * plain_stride, read like acc at the thread's own index, and acc itself, null where there is none
+// (a workgroup-uniform branch).  The finished pair is multiplied and added in registers ahead of its only store.
+struct WithMac {};
+template <>
+struct AccArg<WithMac> {
+  const u64 *plain;
+  size_t plain_stride;
+  const u64 *p;
+};
+__host__ __device__ inline const u64 *acc_ptr(AccArg<WithMac> a) { return a.p; }
+__host__ __device__ inline AccArg<WithMac> mac_arg() { return {nullptr, 0, nullptr}; }
+template <class T>
+__host__ __device__ inline AccArg<WithMac> mac_arg(AccArg<T>) { return {nullptr, 0, nullptr}; }
+__host__ __device__ inline AccArg<WithMac> mac_arg(AccArg<WithMac> a) { return a; }
+template <class... A>
+inline constexpr bool kWithAcc = (std::is_same_v<A, WithAcc> || ...);
+template <class... A>
+inline constexpr bool kWithMac = (std::is_same_v<A, WithMac> || ...);
 // nl + 1 transform buffers + the block's twiddle table, 1024 entries of tw_bytes = sizeof(A::TW): 8 (fp64) or 16 (integer)
 constexpr size_t main_lds_bytes(int nl, int tw_bytes) { return (size_t)((nl + 1) * lds_words(10)) * 8 + 1024 * (size_t)tw_bytes; }
 // (o.mode, o.gather) -> f(MODE, GAL) as integral constants: multiply / key switch with the Galois gather folded in / plain key switch

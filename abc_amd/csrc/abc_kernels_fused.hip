@@ -713,6 +713,10 @@ __global__ __launch_bounds__(256) void k_split3_pass_fp(DevCtx c, const double *
 // A = WithAcc (MODE 1, one more argument): a second, ungathered ciphertext `acc` [ct][2][nl][N] is added, read at the thread's own
 // index (rotate_add: out = acc + rotate(in)).  `out` may be `acc`: a thread loads its two coefficients of either component before
 // it stores them.  Without it the pack is empty and the kernel is, name and code, the one it was.
+// A = WithMac (MODE 1, rotate_mac_plain): out = acc + plain (.) rotate(in).  The plaintext multiplies the finished, centred pair of
+// either component -- |r| <= q/2 times a canonical word, |product| < q -- and the canonical acc word joins it: below 2q, which
+// fp_to_canon centres exactly.  The rotation's own c0 stays in d0 (it is multiplied too), so acc cannot be pre-added there.  All
+// three pairs are loaded ahead of the thread's stores: `out` may be `acc`.  A null acc is a workgroup-uniform branch.
 template <int MODE, bool GAL, int NL, class... A>
 __global__ __launch_bounds__(NL ? (NL + 1) * 64 : 832) void k_split3_main_fp(DevCtx c, const double *__restrict__ part,
                                                                               const double *__restrict__ tpart,
@@ -720,9 +724,10 @@ __global__ __launch_bounds__(NL ? (NL + 1) * 64 : 832) void k_split3_main_fp(Dev
                                                                               size_t opa_stride, size_t opb_stride, int add_c1,
                                                                               const u64 *__restrict__ key, u64 *__restrict__ out, int nl_rt,
                                                                               u32 gelt, AccArg<A>... acc_) {
-  constexpr bool ACC = sizeof...(A) != 0;
-  static_assert(!ACC || MODE == 1, "the second addend belongs to the key switch");
+  constexpr bool ACC = kWithAcc<A...>, MAC = kWithMac<A...>;
+  static_assert(!(ACC || MAC) || MODE == 1, "the second addend belongs to the key switch");
   [[maybe_unused]] const u64 *acc = acc_ptr(acc_...);
+  [[maybe_unused]] const AccArg<WithMac> mac = mac_arg(acc_...);
   extern __shared__ double dyn[];  // nl + 1 buffers of one 1024-point block: nl - 1 decomposition limbs, 2 mod-down limbs
   const int nl = NL ? NL : nl_rt;
   const int W = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -753,6 +758,15 @@ __global__ __launch_bounds__(NL ? (NL + 1) * 64 : 832) void k_split3_main_fp(Dev
   const double *tt0 = dyn + (nl - 1) * lds_words(10), *tt1 = dyn + nl * lds_words(10);
   for (int e = 2 * (int)threadIdx.x; e < 1024; e += 2 * (int)blockDim.x) {  // this thread: coefficients e, e + 1 of the block
     double s0[2] = {0.0, 0.0}, s1[2] = {0.0, 0.0}, d0[2] = {0.0, 0.0}, d1[2] = {0.0, 0.0};
+    [[maybe_unused]] u64x2 mp = {0, 0}, ma0 = {0, 0}, ma1 = {0, 0};
+    if constexpr (MAC) {  // the thread's own pair of the plaintext and of either component of acc, ahead of the stores
+      mp = *reinterpret_cast<const u64x2 *>(mac.plain + ct * mac.plain_stride + (size_t)I * N + base + e);
+      if (acc) {
+        const u64 *ac = acc + ct * 2 * pw + (size_t)I * N + base + e;
+        ma0 = *reinterpret_cast<const u64x2 *>(ac);
+        ma1 = *reinterpret_cast<const u64x2 *>(ac + pw);
+      }
+    }
 #pragma unroll
     for (int Jx = 0; Jx < (NL ? NL : 12); Jx++) {
       if (!NL && Jx >= nl) break;
@@ -814,6 +828,16 @@ __global__ __launch_bounds__(NL ? (NL + 1) * 64 : 832) void k_split3_main_fp(Dev
     const f64x2 u0 = *reinterpret_cast<const f64x2 *>(tt0 + lds_pad(e)), u1 = *reinterpret_cast<const f64x2 *>(tt1 + lds_pad(e));
     // (sum + q_sp (c0, c1) - NTT(t)) q_sp^-1
     u64x2 r;
+    if constexpr (MAC) {
+      const double p0 = fp_from_u64(mp.x), p1 = fp_from_u64(mp.y);
+      r.x = fp_mac_canon(fp_mul_lazy(s0[0] - u0.x, inv, inv_q, q) + d0[0], p0, ma0.x, q, qinv);
+      r.y = fp_mac_canon(fp_mul_lazy(s0[1] - u0.y, inv, inv_q, q) + d0[1], p1, ma0.y, q, qinv);
+      *reinterpret_cast<u64x2 *>(out + ((ct * 2 + 0) * nl + I) * N + base + e) = r;
+      r.x = fp_mac_canon(fp_mul_lazy(s1[0] - u1.x, inv, inv_q, q) + d1[0], p0, ma1.x, q, qinv);
+      r.y = fp_mac_canon(fp_mul_lazy(s1[1] - u1.y, inv, inv_q, q) + d1[1], p1, ma1.y, q, qinv);
+      *reinterpret_cast<u64x2 *>(out + ((ct * 2 + 1) * nl + I) * N + base + e) = r;
+      continue;
+    }
     r.x = fp_to_canon(fp_mul_lazy(s0[0] - u0.x, inv, inv_q, q) + d0[0], q, qinv);
     r.y = fp_to_canon(fp_mul_lazy(s0[1] - u0.y, inv, inv_q, q) + d0[1], q, qinv);
     *reinterpret_cast<u64x2 *>(out + ((ct * 2 + 0) * nl + I) * N + base + e) = r;
@@ -830,6 +854,21 @@ static void launch_split3_main(abc_hip_ctx *c, const MainArgs &a) {
   const dim3 grid((unsigned)(o.count * nl * 16)), block(64 * (nl + 1));
   const size_t lds = (size_t)((nl + 1) * lds_words(10)) * 8;
   if constexpr (MODE == 1 && GAL) {
+    if (o.plain) {
+#define ABC_TM3M(NLV)                                                                                                                  \
+  hipLaunchKernelGGL((k_split3_main_fp<1, true, NLV, WithMac>), grid, block, lds, a.st, c->dc, (const double *)a.part,               \
+                     (const double *)a.tpart, o.target, o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, nl,      \
+                     o.gather, AccArg<WithMac>{o.plain, o.plain_stride, o.acc})
+      switch (nl) {
+        case 1: ABC_TM3M(1); break;
+        case 2: ABC_TM3M(2); break;
+        case 3: ABC_TM3M(3); break;
+        case 4: ABC_TM3M(4); break;
+        default: ABC_TM3M(0); break;
+      }
+#undef ABC_TM3M
+      return;
+    }
     if (o.acc) {
 #define ABC_TM3A(NLV)                                                                                                                  \
   hipLaunchKernelGGL((k_split3_main_fp<1, true, NLV, WithAcc>), grid, block, lds, a.st, c->dc, (const double *)a.part,               \
@@ -881,6 +920,8 @@ struct PairOps {
 // A = WithAcc (MODE 1, one more argument): the second, ungathered ciphertext of rotate_add, as in k_split3_main_fp.  Its words are
 // added to the gathered addend as integers when the operands are loaded -- d0s < 2q <= 2^51, d1s < q (2q with add_c1) -- so PairOps
 // holds what it held, and both forms still load every operand before their first store.
+// A = WithMac (MODE 1, rotate_mac_plain): out = acc + plain (.) rotate(in), as in k_split3_main_fp: `finish` multiplies the centred
+// pair by the thread's own plaintext pair and adds acc's.  d0s keeps the rotation's own c0 alone: the plaintext multiplies it too.
 template <int MODE, bool GAL, int NL, bool HALVES, class... A>
 __global__ __launch_bounds__(512, HALVES ? 6 : NL <= 4 ? 4 : 2) void k_split4_main_fp(DevCtx c, const double *__restrict__ part,
                                                                    const double *__restrict__ tpart, const u64 *__restrict__ opa,
@@ -888,9 +929,10 @@ __global__ __launch_bounds__(512, HALVES ? 6 : NL <= 4 ? 4 : 2) void k_split4_ma
                                                                    int add_c1, const u64 *__restrict__ key, u64 *__restrict__ out, u32 gelt,
                                                                    u32 imap, int ni, int pack, const double *__restrict__ keyf,
                                                                    AccArg<A>... acc_) {
-  constexpr bool ACC = sizeof...(A) != 0;
-  static_assert(!ACC || MODE == 1, "the second addend belongs to the key switch");
+  constexpr bool ACC = kWithAcc<A...>, MAC = kWithMac<A...>;
+  static_assert(!(ACC || MAC) || MODE == 1, "the second addend belongs to the key switch");
   [[maybe_unused]] const u64 *acc = acc_ptr(acc_...);
+  [[maybe_unused]] const AccArg<WithMac> mac = mac_arg(acc_...);
   // grid (ct, slot, block), slot < ni; the data prime of a slot is nibble `slot` of imap (all of them: 0x76543210, ni = nl; a subset
   // when a chain mixes fp64-capable and wider primes: abc_kernels_isplit.hip)
   // pack: the half-done limbs of `part` / `tpart` modulo primes of at most 48 bits arrive packed (abc_ntt.hpp)
@@ -907,7 +949,14 @@ __global__ __launch_bounds__(512, HALVES ? 6 : NL <= 4 ? 4 : 2) void k_split4_ma
   // digit's eight registers are therefore loaded late: its words come out of L2 and are used last, behind the other digits'
   // products (123 VGPRs, no scratch).  HALVES requests everything late.
   // (the second addend's two loads put the one-piece key switch at four limbs in the same place: 36 bytes of scratch without it)
-  constexpr int LATE = (!HALVES && (MODE == 0 || ACC) && NL == 4) ? 1 : 0;
+  constexpr int LATE = (!HALVES && (MODE == 0 || ACC || MAC) && NL == 4) ? 1 : 0;
+  // MAC_LATE: up to four limbs the one-piece form (128 VGPRs for four workgroups per CU) requests the plaintext and acc pairs
+  // after the transform as well: ahead of it they cost 12 to 16 bytes of scratch at three and four limbs
+  constexpr bool MAC_LATE = !HALVES && MAC && NL <= 4;
+  // MAC_INNER: HALVES at four limbs sits at 70 of its 80 VGPRs; there each half requests its pairs behind its sum, when the key
+  // words are dead: 80 VGPRs, no scratch (with the operands: 80 and 28 bytes of scratch).  Measured against the one-piece form
+  // (117 VGPRs, two workgroups per CU) at batch 512: 1.18 - 1.22 ms against 1.25 - 1.28 per call, so HALVES stays
+  constexpr bool MAC_INNER = HALVES && MAC && NL == 4;
   using Ops = PairOps<MODE, NL, HALVES>;
   const int W = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = threadIdx.x & 63;
@@ -989,11 +1038,24 @@ __global__ __launch_bounds__(512, HALVES ? 6 : NL <= 4 ? 4 : 2) void k_split4_ma
       }
     }
   };
+  // MAC: the thread's own pair of the plaintext and of acc's component comp, ahead of that component's store.  HALVES takes acc one
+  // component per half (four registers instead of eight): the second half's pair is at an index that no store of the first half
+  // touches, so `out` may still be `acc`.  (MAC_INNER reads the plaintext pair again in the second half: an L2 hit, four registers
+  // less across the first half's store)
+  [[maybe_unused]] u64x2 mp = {0, 0}, ma[2] = {{0, 0}, {0, 0}};
+  auto load_mac = [&](int e, int comp) {
+    if (comp == 0 || MAC_INNER) mp = *reinterpret_cast<const u64x2 *>(mac.plain + ct * mac.plain_stride + (size_t)I * N + base + e);
+    if (acc) ma[comp] = *reinterpret_cast<const u64x2 *>(acc + (ct * 2 + comp) * pw + (size_t)I * N + base + e);  // workgroup-uniform
+  };
   Ops ops;
   const int e0 = 2 * (int)threadIdx.x;
   if (!HALVES) {
     load_key(e0, ops, 0, NL - LATE, 0);
     load_operands(e0, ops);
+    if constexpr (MAC && !MAC_LATE) {
+      load_mac(e0, 0);
+      load_mac(e0, 1);
+    }
   }
 
   block_twiddles_store<10, double, PER>(ltw, (int)threadIdx.x, NT, twv);
@@ -1028,8 +1090,13 @@ __global__ __launch_bounds__(512, HALVES ? 6 : NL <= 4 ? 4 : 2) void k_split4_ma
   if (HALVES) {
     load_key(e0, ops, 0, NL, 0);
     load_operands(e0, ops);
+    if constexpr (MAC && !MAC_INNER) load_mac(e0, 0);
   }
   if (LATE) load_key(e0, ops, NL - LATE, NL, 0);
+  if constexpr (MAC && MAC_LATE) {
+    load_mac(e0, 0);
+    load_mac(e0, 1);
+  }
   __syncthreads();
   auto compute_pair = [&](int e, Ops &o, auto twin) {
     constexpr bool TW = decltype(twin)::value;
@@ -1063,8 +1130,13 @@ __global__ __launch_bounds__(512, HALVES ? 6 : NL <= 4 ? 4 : 2) void k_split4_ma
     auto finish = [&](int comp, const double *s, const double *d) {  // (sum + q_sp c - NTT(t)) q_sp^-1
       const f64x2 u = *reinterpret_cast<const f64x2 *>(dyn + (nl - 1 + comp) * lds_words(10) + lds_pad(e));
       u64x2 r;
-      r.x = fp_to_canon(fp_mul_lazy(s[0] - u.x, inv, inv_q, q) + d[0], q, qinv);
-      r.y = fp_to_canon(fp_mul_lazy(s[1] - u.y, inv, inv_q, q) + d[1], q, qinv);
+      if constexpr (MAC) {  // acc + plain (.) r
+        r.x = fp_mac_canon(fp_mul_lazy(s[0] - u.x, inv, inv_q, q) + d[0], fp_from_u64(mp.x), ma[comp].x, q, qinv);
+        r.y = fp_mac_canon(fp_mul_lazy(s[1] - u.y, inv, inv_q, q) + d[1], fp_from_u64(mp.y), ma[comp].y, q, qinv);
+      } else {
+        r.x = fp_to_canon(fp_mul_lazy(s[0] - u.x, inv, inv_q, q) + d[0], q, qinv);
+        r.y = fp_to_canon(fp_mul_lazy(s[1] - u.y, inv, inv_q, q) + d[1], q, qinv);
+      }
       *reinterpret_cast<u64x2 *>(out + ((ct * 2 + comp) * nl + I) * N + base + e) = r;
     };
     if constexpr (HALVES) {
@@ -1082,11 +1154,16 @@ __global__ __launch_bounds__(512, HALVES ? 6 : NL <= 4 ? 4 : 2) void k_split4_ma
           s[0] += fp_mulmod(x[0], kd(o.k[Jx].x), q, qinv);
           s[1] += fp_mulmod(x[1], kd(o.k[Jx].y), q, qinv);
         }
+        if constexpr (MAC_INNER) {
+          __builtin_amdgcn_sched_barrier(0);
+          load_mac(e, decltype(comp)::value);
+        }
         finish(decltype(comp)::value, s, d);
       };
       half(std::integral_constant<int, 0>{}, d0);
       __builtin_amdgcn_sched_barrier(0);  // the second half's requests stay behind the first half's store (78 -> 70 VGPRs at four limbs)
       load_key(e, o, 0, NL, 1);
+      if constexpr (MAC && !MAC_INNER) load_mac(e, 1);
       half(std::integral_constant<int, 1>{}, d1);
     } else {
       double s0[2] = {0.0, 0.0}, s1[2] = {0.0, 0.0};
@@ -1132,6 +1209,15 @@ bool split4_main(abc_hip_ctx *c, const MainArgs &a) {
     dispatch_nl<1, 7>(o.nl, [&](auto NL) {
       auto launch = [&](auto H) {
         if constexpr (decltype(M)::value == 1 && decltype(G)::value) {
+          if constexpr (decltype(NL)::value <= 5) {  // Seq::split14 comes here up to five limbs (route_chunk), and nothing else with a plaintext
+            if (o.plain) {
+              hipLaunchKernelGGL((k_split4_main_fp<1, true, decltype(NL)::value, decltype(H)::value, WithMac>), grid, block,
+                                 main_lds_bytes(o.nl, sizeof(double)), a.st, c->dc, (const double *)a.part, (const double *)a.tpart, o.target,
+                                 o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, o.gather, (u32)a.imap, a.ni, a.pack, keyf,
+                                 AccArg<WithMac>{o.plain, o.plain_stride, o.acc});
+              return;
+            }
+          }
           if (o.acc) {
             hipLaunchKernelGGL((k_split4_main_fp<1, true, decltype(NL)::value, decltype(H)::value, WithAcc>), grid, block,
                                main_lds_bytes(o.nl, sizeof(double)), a.st, c->dc, (const double *)a.part, (const double *)a.tpart, o.target,
@@ -1348,7 +1434,11 @@ static u32 gather_elt(const KsOperands &o, int scheme, size_t N) {
 int launch_keyswitch(abc_hip_ctx *c, const KsRoute &r, const KsOperands &in) {
   if (!in.count) return 0;
   if (in.gelt && !seq_folds_permutation(c->facts, r)) { set_error("launch_keyswitch: this sequence folds no permutation"); return 1; }
-  if (in.acc && !(in.gelt && seq_takes_acc(c->facts, r, in.nl))) { set_error("launch_keyswitch: a second addend needs a folded permutation and a sequence that takes one"); return 1; }
+  if (in.plain ? !(in.gelt && seq_takes_plain(c->facts, r, in.nl))
+               : in.acc && !(in.gelt && seq_takes_acc(c->facts, r, in.nl))) {
+    set_error("launch_keyswitch: a second addend or a plaintext needs a folded permutation and a sequence that takes one");
+    return 1;
+  }
   KsOperands o = in;
   o.mode = 1, o.gather = gather_elt(o, c->scheme, (size_t)c->n);
   switch (r.seq) {

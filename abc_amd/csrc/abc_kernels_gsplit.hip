@@ -475,14 +475,17 @@ struct GPairOps {
 // A = WithAcc (MODE 1, one more argument): a second, ungathered ciphertext `acc` [ct][2][nl][N] is added, read at the thread's own
 // index (rotate_add: out = acc + rotate(in), cf. k_split4_main_fp).  `out` may be `acc`: every operand is loaded ahead of the
 // transform.  Without it the pack is empty and the kernel is, name and code, the one it was.
+// A = WithMac (MODE 1, rotate_mac_plain): out = acc + plain (.) rotate(in), as in k_split3_main_fp; the three pairs are loaded with
+// the other operands.
 template <int LOGN, int MODE, bool GAL, int NL, class... A>
 __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_gsplit_main(DevCtx c, const double *__restrict__ part, const double *__restrict__ tpart,
                                                         const u64 *__restrict__ opa, const u64 *__restrict__ opb, size_t opa_stride,
                                                         size_t opb_stride, int add_c1, const u64 *__restrict__ key, u64 *__restrict__ out,
                                                         u32 gelt, u32 imap, int ni, AccArg<A>... acc_) {
-  constexpr bool ACC = sizeof...(A) != 0;
-  static_assert(!ACC || MODE == 1, "the second addend belongs to the key switch");
+  constexpr bool ACC = kWithAcc<A...>, MAC = kWithMac<A...>;
+  static_assert(!(ACC || MAC) || MODE == 1, "the second addend belongs to the key switch");
   [[maybe_unused]] const u64 *acc = acc_ptr(acc_...);
+  [[maybe_unused]] const AccArg<WithMac> mac = mac_arg(acc_...);
   // grid (ct, slot, block), slot < ni; the data prime of a slot is nibble `slot` of imap (all: 0x76543210, ni = nl; a subset for
   // chains that mix fp64-capable and wider primes: abc_kernels_isplit.hip)
   constexpr int LOGNB = LOGN - 10, NB = 1 << LOGNB, nl = NL, NT = 512, PER = 2;
@@ -550,6 +553,19 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_gsplit_main(DevCtx c, 
       o.d1s[0] += c1.x; o.d1s[1] += c1.y;
     }
   }
+  // MAC: the thread's own pairs of the plaintext and of either component of acc, with the other operands.  At seven limbs they are
+  // requested after the transform (ahead of it: 133 VGPRs, one workgroup per CU where every other form of the kernel has two)
+  constexpr bool MAC_LATE = MAC && NL == 7;
+  [[maybe_unused]] u64x2 mp = {0, 0}, ma0 = {0, 0}, ma1 = {0, 0};
+  auto load_mac = [&]() {
+    mp = *reinterpret_cast<const u64x2 *>(mac.plain + ct * mac.plain_stride + (size_t)I * N + base + e);
+    if (acc) {  // workgroup-uniform
+      const u64 *ac = acc + ct * 2 * pw + (size_t)I * N + base + e;
+      ma0 = *reinterpret_cast<const u64x2 *>(ac);
+      ma1 = *reinterpret_cast<const u64x2 *>(ac + pw);
+    }
+  };
+  if constexpr (MAC && !MAC_LATE) load_mac();
   block_twiddles_store<10, double, PER>(ltw, (int)threadIdx.x, NT, twv);
   __syncthreads();
   if (has_limb) {
@@ -558,6 +574,7 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_gsplit_main(DevCtx c, 
     for (int r = 0; r < 16; r++) xin[r] = fp_centre(xin[r], q, qinv);
     ntt_fwd_tail1024_pairs<FpTail>(buf, xin, [&](int, int i, double v) { buf[lds_pad(i)] = v; }, t, m, LOGNB, blk, lane, ltw);
   }
+  if constexpr (MAC_LATE) load_mac();
   __syncthreads();
   const double *tt0 = dyn + (nl - 1) * lds_words(10), *tt1 = dyn + nl * lds_words(10);
   double s0[2] = {0.0, 0.0}, s1[2] = {0.0, 0.0}, d0[2] = {0.0, 0.0}, d1[2] = {0.0, 0.0};
@@ -595,6 +612,16 @@ __global__ __launch_bounds__(512, NL <= 4 ? 4 : 2) void k_gsplit_main(DevCtx c, 
   }
   const f64x2 u0 = *reinterpret_cast<const f64x2 *>(tt0 + lds_pad(e)), u1 = *reinterpret_cast<const f64x2 *>(tt1 + lds_pad(e));
   u64x2 r;
+  if constexpr (MAC) {  // acc + plain (.) r
+    const double p0 = fp_from_u64(mp.x), p1 = fp_from_u64(mp.y);
+    r.x = fp_mac_canon(fp_mul_lazy(s0[0] - u0.x, inv, inv_q, q) + d0[0], p0, ma0.x, q, qinv);
+    r.y = fp_mac_canon(fp_mul_lazy(s0[1] - u0.y, inv, inv_q, q) + d0[1], p1, ma0.y, q, qinv);
+    *reinterpret_cast<u64x2 *>(out + ((ct * 2 + 0) * nl + I) * N + base + e) = r;
+    r.x = fp_mac_canon(fp_mul_lazy(s1[0] - u1.x, inv, inv_q, q) + d1[0], p0, ma1.x, q, qinv);
+    r.y = fp_mac_canon(fp_mul_lazy(s1[1] - u1.y, inv, inv_q, q) + d1[1], p1, ma1.y, q, qinv);
+    *reinterpret_cast<u64x2 *>(out + ((ct * 2 + 1) * nl + I) * N + base + e) = r;
+    return;
+  }
   r.x = fp_to_canon(fp_mul_lazy(s0[0] - u0.x, inv, inv_q, q) + d0[0], q, qinv);
   r.y = fp_to_canon(fp_mul_lazy(s0[1] - u0.y, inv, inv_q, q) + d0[1], q, qinv);
   *reinterpret_cast<u64x2 *>(out + ((ct * 2 + 0) * nl + I) * N + base + e) = r;
@@ -752,6 +779,12 @@ static void launch_gsplit_main(abc_hip_ctx *c, const MainArgs &a) {
     else
       dispatch_nl<1, 7>(o.nl, [&](auto NL) {
         if constexpr (MODE == 1 && GAL) {
+          if (o.plain) {
+            hipLaunchKernelGGL((k_gsplit_main<LOGN, 1, true, decltype(NL)::value, WithMac>), gmain, dim3(512), main_lds_bytes(o.nl, sizeof(double)),
+                               a.st, c->dc, part, tpart, o.target, o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, o.gather,
+                               (u32)a.imap, a.ni, AccArg<WithMac>{o.plain, o.plain_stride, o.acc});
+            return;
+          }
           if (o.acc) {
             hipLaunchKernelGGL((k_gsplit_main<LOGN, 1, true, decltype(NL)::value, WithAcc>), gmain, dim3(512), main_lds_bytes(o.nl, sizeof(double)),
                                a.st, c->dc, part, tpart, o.target, o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, o.gather,

@@ -111,6 +111,11 @@ __device__ __forceinline__ u64 fp_to_canon(double x, double q, double qinv) {
   r += __longlong_as_double((long long)add);
   return (u64)__double_as_longlong(r + 4503599627370496.0) & 0x000fffffffffffffull;
 }
+// acc + p * x -> canonical, for a lazy x, a canonical plaintext word p (as a double) and a canonical acc: x is centred first
+// (|.| <= q/2), the product is fp_mulmod's |.| < q, with acc below 2q <= 2^51
+__device__ __forceinline__ u64 fp_mac_canon(double x, double p, u64 acc, double q, double qinv) {
+  return fp_to_canon(fp_mulmod(fp_centre(x, q, qinv), p, q, qinv) + fp_from_u64(acc), q, qinv);
+}
 // any lazy value -> a non-negative representative in [q/2, 3q/2] as u64 (for consumers that reduce anyway)
 __device__ __forceinline__ u64 fp_to_lazy(double x, double q, double qinv) {
   const double r = fp_centre(x, q, qinv);

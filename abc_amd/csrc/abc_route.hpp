@@ -22,6 +22,7 @@ struct Switches {
   bool no_fused = false, no_split = false, no_split4 = false, no_isplit = false, no_gsplit = false, no_lean_front = false, no_bsplit = false, no_mixed = false, no_pack = false, no_key_twin = false, no_bmul = false, no_iks = false, no_tensor_intt = false;
   bool no_galois_fusion = false;
   bool no_rotate_add_fusion = false;  // ABC_HIP_NO_ROTATE_ADD_FUSION: rotate_add as a rotation into an arena, then the add kernel
+  bool no_rotate_mac_fusion = false;  // ABC_HIP_NO_ROTATE_MAC_FUSION: rotate_mac_plain as a rotation into an arena, multiply_plain on it, then the add kernel
   bool main_two_per_cu = false;  // ABC_HIP_MAIN_TWO_PER_CU: k_split4_main_fp in its one-piece pair phase at nl <= 4 (same step, same route: a form of the kernel)
   bool host_sampling = false;  // ABC_HIP_HOST_SAMPLING: the keyed entries (the OS-keyed ones call them) draw with the host twin of the keyed spec (no route depends on it)
   size_t chunk = 0, few_limbs = 48, lean_limit = 96, bfv_scratch_mb = 0, pass0_target_limit = 128;
@@ -99,6 +100,10 @@ struct RotRoute {
 struct RotAddRoute {
   RotRoute rot;
   bool fused;  // the second ciphertext is one more operand of the key switch's last kernel; otherwise rotate into an arena, then add
+};
+struct RotMacRoute {
+  RotRoute rot;
+  bool fused;  // the plaintext and the second ciphertext are operands of the key switch's last kernel; otherwise rotate into an arena, multiply_plain there, then add
 };
 struct RescaleRoute {
   Rescale kind;
@@ -193,6 +198,12 @@ inline bool seq_takes_acc(const RouteFacts &, const KsRoute &r, int nl) {
   const Seq s = r.seq;
   return s == Seq::split14 || s == Seq::bsplit14 || s == Seq::bsplit_big || (s == Seq::gsplit15 && nl <= 7);
 }
+// a plaintext [nl][N] that multiplies the finished pair, and a second ciphertext added to the product, in the last kernel
+// (k_split4_main_fp / k_split3_main_fp, k_gsplit_main up to seven limbs): the CKKS sequences among seq_takes_acc's -- a BFV
+// plaintext product needs transforms
+inline bool seq_takes_plain(const RouteFacts &, const KsRoute &r, int nl) {
+  return r.seq == Seq::split14 || (r.seq == Seq::gsplit15 && nl <= 7);
+}
 
 // one Galois element at level nl: the key switch of the level, with the permutation folded into it where its sequence gathers
 inline RotRoute route_rotate(const RouteFacts &f, int nl, bool in_place) {
@@ -208,6 +219,13 @@ inline RotRoute route_rotate(const RouteFacts &f, int nl, bool in_place) {
 inline RotAddRoute route_rotate_add(const RouteFacts &f, int nl, bool in_place) {
   const RotRoute rot = route_rotate(f, nl, false);
   return {rot, rot.fold && seq_takes_acc(f, rot.ks, nl) && !in_place && !f.sw.no_rotate_add_fusion};
+}
+
+// addend + plain (.) one Galois element at level nl (CKKS); in_place and `rot` as in route_rotate_add.  The unfused sequence
+// rotates into an arena, multiplies there in place, then adds.
+inline RotMacRoute route_rotate_mac(const RouteFacts &f, int nl, bool in_place) {
+  const RotRoute rot = route_rotate(f, nl, false);
+  return {rot, rot.fold && seq_takes_plain(f, rot.ks, nl) && !in_place && !f.sw.no_rotate_mac_fusion};
 }
 
 inline RescaleRoute route_rescale(const RouteFacts &f, int nl, bool in_place) {
@@ -302,7 +320,7 @@ inline void format_ks(char *buf, size_t cap, const RouteFacts &f, const KsRoute 
 }
 // The route of one call into buf: what abc_hip_route returns.  op: include/abc_hip.h, ABC_HIP_ROUTE_*.  Returns the length,
 // -1 if cap is too small, -2 for an unknown op.
-enum RouteOp { kRouteMulRelin = 0, kRouteKeyswitch = 1, kRouteRotate = 2, kRouteRescale = 3, kRouteMultiply = 4, kRouteRotateAdd = 5 };
+enum RouteOp { kRouteMulRelin = 0, kRouteKeyswitch = 1, kRouteRotate = 2, kRouteRescale = 3, kRouteMultiply = 4, kRouteRotateAdd = 5, kRouteRotateMacPlain = 7 };  // 6 stays unassigned: the host tests probe it as the unknown operation
 inline int format_op(char *buf, size_t cap, const RouteFacts &f, int op, int nl, size_t count, bool in_place) {
   char ks[80];
   int n = -2;
@@ -321,6 +339,10 @@ inline int format_op(char *buf, size_t cap, const RouteFacts &f, int op, int nl,
     const RotAddRoute r = route_rotate_add(f, nl, in_place);
     format_ks(ks, sizeof ks, f, r.rot.ks, nl, count);
     n = r.fused ? snprintf(buf, cap, "fold+add %s", ks) : snprintf(buf, cap, "%s add=separate %s", r.rot.fold ? "fold" : "permute", ks);
+  } else if (op == kRouteRotateMacPlain) {
+    const RotMacRoute r = route_rotate_mac(f, nl, in_place);
+    format_ks(ks, sizeof ks, f, r.rot.ks, nl, count);
+    n = r.fused ? snprintf(buf, cap, "fold+mac %s", ks) : snprintf(buf, cap, "%s mac=separate %s", r.rot.fold ? "fold" : "permute", ks);
   } else if (op == kRouteRescale) {
     const RescaleRoute r = route_rescale(f, nl, in_place);
     n = r.kind == Rescale::mixed ? snprintf(buf, cap, "mixed fpmask=0x%x", (unsigned)r.fpmask) : snprintf(buf, cap, "%s", name(r.kind));

@@ -74,6 +74,7 @@ int abc_hip_ctx_reload_env(abc_hip_ctx *ctx);
 #define ABC_HIP_ROUTE_RESCALE 3
 #define ABC_HIP_ROUTE_MULTIPLY 4
 #define ABC_HIP_ROUTE_ROTATE_ADD 5 /* one Galois element plus a second ciphertext; in_place: d_out aliases d_in */
+#define ABC_HIP_ROUTE_ROTATE_MAC_PLAIN 7 /* CKKS: addend + plaintext (.) one Galois element; in_place: d_out aliases d_in (6 is unassigned) */
 int abc_hip_route(abc_hip_ctx *ctx, int op, int nl, size_t count, int in_place, char *buf, size_t cap);
 
 /* ---- device memory (so that FFI callers need no HIP runtime binding) ----
@@ -221,6 +222,33 @@ int abc_hip_apply_galois_add(abc_hip_ctx *ctx, const uint64_t *d_in, const uint6
  * the first launch; the intermediate sums live in arenas and only the last one lands in d_out, which may be d_in.  n_steps == 0
  * copies.  h_steps is read during the call only.  Capturable like abc_hip_rotate_add. */
 int abc_hip_rotate_sum(abc_hip_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, int nl, const int *h_steps, int n_steps, size_t count);
+/* CKKS only: Evaluator::rotate_vector, multiply_plain and add as one call, the term of a matrix-vector product by diagonals:
+ * d_out = d_addend + d_plain (.) rotate(d_in, steps); the ciphertexts [count][2][nl][N], d_plain and plain_stride exactly as
+ * abc_hip_multiply_plain takes them (0: one plaintext for the batch; >= nl * N: one per ciphertext, its first nl limbs read).
+ * d_addend == NULL: no addend.  Bit-identical to abc_hip_rotate into a temporary, abc_hip_multiply_plain on it, then abc_hip_add
+ * with the addend, under every aliasing of d_in, d_addend and d_out.  Where the route allows it (abc_hip_route,
+ * ABC_HIP_ROUTE_ROTATE_MAC_PLAIN: a folded rotation of the N = 2^14 split sequence, or of the N = 2^15 one up to seven limbs, with
+ * d_out != d_in) plaintext and addend are operands of the key switch's last kernel; otherwise the rotation lands in an arena,
+ * the product is formed there and the add kernel follows.  No rescale: the result is at the scale of the product.  Step 0 has
+ * no key switch: multiply_plain, then add.  A step without a key of its own runs its NAF chain as abc_hip_rotate does; only the
+ * last hop takes the plaintext and the addend.  Fails for a BFV context, for d_plain overlapping d_out, and wherever
+ * abc_hip_rotate or abc_hip_multiply_plain would; every error is found before anything is written.  Capturable, under the
+ * "run once eagerly first" rule of abc_hip_graph_begin. */
+int abc_hip_rotate_mac_plain(abc_hip_ctx *ctx, const uint64_t *d_in, const uint64_t *d_plain, size_t plain_stride,
+                             const uint64_t *d_addend, uint64_t *d_out, int nl, int steps, size_t count);
+/* the same for one Galois element (2N - 1: conjugation) */
+int abc_hip_apply_galois_mac_plain(abc_hip_ctx *ctx, const uint64_t *d_in, const uint64_t *d_plain, size_t plain_stride,
+                                   const uint64_t *d_addend, uint64_t *d_out, int nl, uint32_t galois_elt, size_t count);
+/* CKKS only: a matrix-vector product by diagonals, d_out = sum over r of diag_r (.) rotate(d_in, h_steps[r]), accumulated in the
+ * order given.  One set of diagonals for the whole batch: row r starts at d_diags + r * diag_stride, diag_stride >= nl * N words,
+ * and its first nl limbs are read, so rows encoded at a higher level ([n_steps][L][N], stride L * N) apply at nl < L.  The running
+ * sum lives in d_out: a step 0 term is a plain product, every other one abc_hip_rotate_mac_plain with d_addend == d_out.
+ * Duplicate steps are allowed.  n_steps == 0 writes zeros; count == 0 succeeds and enqueues nothing.  Every step and every key is
+ * checked before the first launch; d_out overlapping d_in or d_diags, a bad stride, a step without a key (or a NAF chain of
+ * keys) or a BFV context fail the call with nothing written.  h_steps is read during the call only.  Capturable like
+ * abc_hip_rotate_mac_plain. */
+int abc_hip_diag_matvec(abc_hip_ctx *ctx, const uint64_t *d_in, const uint64_t *d_diags, size_t diag_stride, const int *h_steps,
+                        int n_steps, uint64_t *d_out, int nl, size_t count);
 /* The three plaintext operations.  d_out may be d_ct (the reference's *_inplace call sites); size = 2 or 3.
  * plain_stride, in words, is the distance from ciphertext i's plaintext to ciphertext i + 1's:
  *   0            one plaintext, broadcast to the batch (d_plain holds N words for BFV, nl * N for CKKS);

@@ -66,6 +66,76 @@ def rotate_add_ab(res, only, rng):
         g.close()
 
 
+def _alternate(g, res, names, fns, routes, B):
+    """fns[0], fns[1], fns[0], ...: five runs each.  The first run of fns[0] sizes the arenas and is left out of its minimum."""
+    runs = {names[0]: [], names[1]: []}
+    for rep in range(10):
+        runs[names[rep & 1]].append(timeit(g, fns[rep & 1]))
+    for i, (k, ms) in enumerate(runs.items()):
+        kept = ms[1:] if i == 0 else ms
+        res[k] = {"batch": B, "ms": min(kept), "ms_median": sorted(kept)[len(kept) // 2], "ms_runs": ms, "route": routes[i]}
+        print("%-44s %s ms / %d  (%s)" % (k, " ".join("%8.3f" % v for v in ms), B, routes[i]), flush=True)
+
+
+def rotate_mac_ab(res, only, rng):
+    """addend + plain (.) rotate(in, 1) as abc_hip_rotate into a temporary, abc_hip_multiply_plain on it and abc_hip_add, against one
+    abc_hip_rotate_mac_plain; and an eight-diagonal abc_hip_diag_matvec against eight such triples (the first without its add).  Alternating in one process, five
+    runs each; a shape stays on the fused route only if every fused run beats the fastest separate one."""
+    shapes = [  # tag, context, levels, batches
+        ("ckks14", lambda: capi.Context(capi.CKKS, 16384, capi.create_primes(16384, [50, 40, 40, 40, 50])), (3, 4), (512, 32)),
+        ("ckks15", lambda: capi.Context(capi.CKKS, 32768, capi.create_primes(32768, [50, 40, 40, 50])), (3,), (256, 32)),
+    ]
+    for tag, make, levels, batches in shapes:
+        if only and only not in "%s_rotate_mac" % tag and "rotate_mac" not in only:  # no entry of this context can match
+            continue
+        g = make()
+        g.keygen(1)
+        for nl in levels:
+            for B in batches:
+                names = ["%s_L%d_b%d_rotate_mac_%s" % (tag, nl, B, kind) for kind in ("separate", "fused")]
+                if not any(only in k for k in names):
+                    continue
+                cb, zero = C.c_size_t(B), C.c_size_t(0)
+                a, nb = rand_ct(g, rng, B, 2, nl)
+                b, _ = rand_ct(g, rng, B, 2, nl)
+                p, _ = rand_ct(g, rng, 1, 1, nl)  # one plaintext [nl][N], broadcast
+                tmp, out = g.alloc(nb), g.alloc(nb)
+
+                def separate():
+                    g.op("rotate", a.ptr, tmp.ptr, nl, 1, cb)
+                    g.op("multiply_plain", tmp.ptr, p.ptr, zero, tmp.ptr, 2, nl, cb)
+                    g.op("add", b.ptr, tmp.ptr, out.ptr, 2, nl, cb)
+
+                def fused():
+                    g.op("rotate_mac_plain", a.ptr, p.ptr, zero, b.ptr, out.ptr, nl, 1, cb)
+                _alternate(g, res, names, (separate, fused), (g.route("rotate", nl, B), g.route("rotate_mac_plain", nl, B)), B)
+                del a, b, p, tmp, out
+        names = ["%s_L3_b512_rotate_mac_diag8_%s" % (tag, kind) for kind in ("separate", "fused")]
+        if tag == "ckks14" and any(only in k for k in names):
+            nl, B, H = 3, 512, 8
+            steps = [1 << i for i in range(H)]
+            cb, zero = C.c_size_t(B), C.c_size_t(0)
+            a, nb = rand_ct(g, rng, B, 2, nl)
+            d, db = rand_ct(g, rng, H, 1, nl)  # [H][nl][N]
+            row = [C.c_void_p(d.ptr.value + r * (db // H)) for r in range(H)]
+            tmp, out = g.alloc(nb), g.alloc(nb)
+            arr = (C.c_int * H)(*steps)
+
+            def separate():
+                for r in range(H):
+                    dst = tmp if r else out
+                    g.op("rotate", a.ptr, dst.ptr, nl, steps[r], cb)
+                    g.op("multiply_plain", dst.ptr, row[r], zero, dst.ptr, 2, nl, cb)
+                    if r:
+                        g.op("add", out.ptr, tmp.ptr, out.ptr, 2, nl, cb)
+
+            def fused():
+                g.op("diag_matvec", a.ptr, d.ptr, C.c_size_t(nl * g.n), arr, H, out.ptr, nl, cb)
+            _alternate(g, res, names, (separate, fused), (g.route("rotate", nl, B), g.route("rotate_mac_plain", nl, B)), B)
+            del a, d, tmp, out
+        g.close()
+
+
 def keyswitch_batch1(res, only, rng):
     """one ciphertext per call at nl = 4: relinearise, rotate and rotate_add on the two CKKS split rings -- the calls in which the
     host side of the key switch (routes, operand record, launches) is the largest share"""
@@ -231,6 +301,7 @@ def main():
         del a, b, out, dec, plains
         g.close()
     rotate_add_ab(res, only, rng)
+    rotate_mac_ab(res, only, rng)
     keyswitch_batch1(res, only, rng)
     os.makedirs("gpurun_out", exist_ok=True)
     json.dump(res, open("gpurun_out/op_bench.json", "w"), indent=1)
