@@ -390,10 +390,16 @@ static KsOperands ks_of_ciphertexts(const abc_hip_ctx *c, const u64 *ct, int siz
   return o;
 }
 
-// one Galois element along route r; acc (RotAddRoute::fused only): a second ciphertext added in the key switch's last kernel;
-// plain (RotMacRoute::fused only): a plaintext that multiplies the result there, before acc -- then optional -- is added
+// a [a, a + a_bytes) and b [b, b + b_bytes) share a byte
+static bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// one Galois element along route r; tail (a fused route only): the key switch's last kernel adds tail.addend, or multiplies by
+// tail.plain and then adds tail.addend where there is one
 static int apply_galois_routed(abc_hip_ctx *c, const RotRoute &r, const u64 *in, u64 *out, int nl, uint32_t elt, size_t count,
-                               const u64 *acc = nullptr, const u64 *plain = nullptr, size_t plain_stride = 0) {
+                               const RotTail &tail = {}) {
   auto it = c->d_galois.find(elt);
   if (it == c->d_galois.end()) { set_error("Galois key not present"); return 1; }
   if (!count) return 0;
@@ -405,25 +411,43 @@ static int apply_galois_routed(abc_hip_ctx *c, const RotRoute &r, const u64 *in,
   }
   KsOperands o = ks_of_ciphertexts(c, in, 2, it->second, out, nl, count);
   o.gelt = r.fold ? elt : 0u;
-  o.acc = acc, o.plain = plain, o.plain_stride = plain_stride;
+  o.acc = tail.addend, o.plain = tail.plain, o.plain_stride = tail.plain_stride;
   return launch_keyswitch(c, r.ks, o);
 }
-static int apply_galois(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, uint32_t elt, size_t count) {
-  return apply_galois_routed(c, route_rotate(c->facts, nl, in == out), in, out, nl, elt, count);
+
+// out = tail applied to a ciphertext x that `out` is or does not overlap (step 0's input, or a rotation in an arena), as separate kernels:
+// the product with the plaintext -- into `out` without an addend, else in place on x where it is scratch (x_scratch), else in
+// arena `tmp_arena` -- then the add kernel (elementwise, so every aliasing of its three pointers is fine); a copy for an empty tail
+static int finish_separate(abc_hip_ctx *c, u64 *x_scratch, const u64 *x, const RotTail &tail, u64 *out, int nl, size_t count, int tmp_arena) {
+  const size_t bytes = count * 2 * nl * (size_t)c->n * 8;
+  if (tail.plain) {
+    if (!tail.addend) return ckks_multiply_plain(c, x, tail.plain, tail.plain_stride, out, 2, nl, count);
+    if (!x_scratch) {
+      if (ensure_aux(c, tmp_arena, bytes)) return 1;
+      x_scratch = (u64 *)c->aux[tmp_arena];
+    }
+    if (ckks_multiply_plain(c, x, tail.plain, tail.plain_stride, x_scratch, 2, nl, count)) return 1;
+    x = x_scratch;
+  }
+  if (tail.addend) return launch_addsub(c, tail.addend, x, out, nl, count * 2, 0);
+  if (x != out) ABC_HIP_CHECK(hipMemcpyAsync(out, x, bytes, hipMemcpyDeviceToDevice, c->stream));
+  return 0;
 }
 
-// out = addend + g(in) (abc_hip_apply_galois_add, and the last hop of rotate_add).  Fused: one more operand of the key switch's
-// last kernel; `out` may be `addend` there, and is never `in`.  Otherwise the rotation lands in arena `tmp_arena` and the add
-// kernel follows -- elementwise, so every aliasing of the three pointers is fine.
-static int apply_galois_add(abc_hip_ctx *c, const u64 *in, const u64 *addend, u64 *out, int nl, uint32_t elt, size_t count, int tmp_arena) {
+// out = tail applied to g(in): every abc_hip_apply_galois* entry, and each hop of rotate_tail.  Fused: the tail's operands go to
+// the key switch's last kernel; `out` may be the addend there, and is never `in`.  A plain rotation is "fused" whenever it is out
+// of place.  Otherwise the rotation lands in arena `tmp_arena` -- never in place, whatever `out` is -- and finish_separate follows.
+static int apply_galois_tail(abc_hip_ctx *c, const u64 *in, const RotTail &tail, u64 *out, int nl, uint32_t elt, size_t count, int tmp_arena) {
   if (!c->d_galois.count(elt)) { set_error("Galois key not present"); return 1; }
   if (!count) return 0;
-  const RotAddRoute r = route_rotate_add(c->facts, nl, in == out);
-  if (r.fused) return apply_galois_routed(c, r.rot, in, out, nl, elt, count, addend);
+  const RotTailRoute r = tail.plain    ? route_rotate_mac(c->facts, nl, in == out)
+                         : tail.addend ? route_rotate_add(c->facts, nl, in == out)
+                                       : RotTailRoute{route_rotate(c->facts, nl, false), in != out};
+  if (r.fused) return apply_galois_routed(c, r.rot, in, out, nl, elt, count, tail);
   if (ensure_aux(c, tmp_arena, count * 2 * nl * (size_t)c->n * 8)) return 1;
   u64 *tmp = (u64 *)c->aux[tmp_arena];
   if (apply_galois_routed(c, r.rot, in, tmp, nl, elt, count)) return 1;
-  return launch_addsub(c, addend, tmp, out, nl, count * 2, 0);
+  return finish_separate(c, tmp, tmp, tail, out, nl, count, tmp_arena);
 }
 
 // the hops of one rotation: the step itself where it has a key, else its non-adjacent form; fails before anything is launched
@@ -443,120 +467,57 @@ static int rotation_terms(abc_hip_ctx *c, int steps, std::vector<int> &terms) {
   return 0;
 }
 
-// hops first .. last - 1 of a rotation from `cur`, ping-ponging through arenas 1 and 2 (apply_galois is out of place): hop i lands in
-// arena 1 + (i & 1); `cur` follows
-static int rotate_hops(abc_hip_ctx *c, const u64 *&cur, int nl, const std::vector<int> &terms, size_t first, size_t last, size_t count) {
-  for (size_t i = first; i < last; i++) {
-    const int which = 1 + (int)(i & 1);
-    if (ensure_aux(c, which, count * 2 * nl * (size_t)c->n * 8)) return 1;
-    u64 *dst = (u64 *)c->aux[which];
-    if (apply_galois(c, cur, dst, nl, elt_from_step(c, terms[i]), count)) return 1;
-    cur = dst;
-  }
-  return 0;
-}
-
-static int rotate(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, int steps, size_t count) {
-  const size_t bytes = count * 2 * nl * (size_t)c->n * 8;
-  if (steps == 0) {
-    if (in != out) ABC_HIP_CHECK(hipMemcpyAsync(out, in, bytes, hipMemcpyDeviceToDevice, c->stream));
-    return 0;
-  }
-  std::vector<int> terms;
-  if (rotation_terms(c, steps, terms)) return 1;
-  // the last hop lands in `out`, or -- where it would read what it writes -- in the next arena and is copied
-  const u64 *cur = in;
-  const size_t last = terms.size() - 1;
-  if (rotate_hops(c, cur, nl, terms, 0, last, count)) return 1;
-  if (out != cur) return apply_galois(c, cur, out, nl, elt_from_step(c, terms[last]), count);
-  if (rotate_hops(c, cur, nl, terms, last, last + 1, count)) return 1;
-  ABC_HIP_CHECK(hipMemcpyAsync(out, cur, bytes, hipMemcpyDeviceToDevice, c->stream));
-  return 0;
-}
-
-// out = addend + rotate(in, steps): every hop but the last as rotate() runs it, the last one with the add (fused where the route
-// allows it; its temporary otherwise is the arena the ping-pong would use next)
-static int rotate_add(abc_hip_ctx *c, const u64 *in, const u64 *addend, u64 *out, int nl, int steps, size_t count) {
-  if (steps == 0) return count ? launch_addsub(c, addend, in, out, nl, count * 2, 0) : 0;
-  std::vector<int> terms;
-  if (rotation_terms(c, steps, terms)) return 1;
-  if (!count) return 0;
-  const u64 *cur = in;
-  const size_t last = terms.size() - 1;
-  if (rotate_hops(c, cur, nl, terms, 0, last, count)) return 1;
-  return apply_galois_add(c, cur, addend, out, nl, elt_from_step(c, terms[last]), count, 1 + (int)(last & 1));
-}
-
-// out = addend + plain (.) x for a ciphertext x that no output overlaps (step 0's input, or a rotation in an arena): the product in
-// place on x where it is scratch, else in arena `tmp_arena`, then the add kernel; without an addend the product lands in `out`
-static int mac_separate(abc_hip_ctx *c, u64 *x_scratch, const u64 *x, const u64 *plain, size_t plain_stride, const u64 *addend, u64 *out,
-                        int nl, size_t count, int tmp_arena) {
-  if (!addend) return ckks_multiply_plain(c, x, plain, plain_stride, out, 2, nl, count);
-  if (!x_scratch) {
-    if (ensure_aux(c, tmp_arena, count * 2 * nl * (size_t)c->n * 8)) return 1;
-    x_scratch = (u64 *)c->aux[tmp_arena];
-  }
-  if (ckks_multiply_plain(c, x, plain, plain_stride, x_scratch, 2, nl, count)) return 1;
-  return launch_addsub(c, addend, x_scratch, out, nl, count * 2, 0);
-}
-
-// out = addend + plain (.) g(in), CKKS (abc_hip_apply_galois_mac_plain, and the last hop of rotate_mac_plain); addend may be null.
-// Fused: plaintext and addend are operands of the key switch's last kernel; `out` may be `addend` there, and is never `in`.
-// Otherwise the rotation lands in arena `tmp_arena`, multiply_plain runs on it in place, and the add kernel follows.
-static int apply_galois_mac(abc_hip_ctx *c, const u64 *in, const u64 *plain, size_t plain_stride, const u64 *addend, u64 *out, int nl,
-                            uint32_t elt, size_t count, int tmp_arena) {
-  if (!c->d_galois.count(elt)) { set_error("Galois key not present"); return 1; }
-  if (!count) return 0;
-  const RotMacRoute r = route_rotate_mac(c->facts, nl, in == out);
-  if (r.fused) return apply_galois_routed(c, r.rot, in, out, nl, elt, count, addend, plain, plain_stride);
-  if (ensure_aux(c, tmp_arena, count * 2 * nl * (size_t)c->n * 8)) return 1;
-  u64 *tmp = (u64 *)c->aux[tmp_arena];
-  if (apply_galois_routed(c, r.rot, in, tmp, nl, elt, count)) return 1;
-  return mac_separate(c, tmp, tmp, plain, plain_stride, addend, out, nl, count, tmp_arena);
-}
-
-// out = addend + plain (.) rotate(in, steps): every hop but the last as rotate() runs it, the last one with the plaintext and the
-// addend.  Step 0 has no key switch: multiply_plain, then add.
-static int rotate_mac(abc_hip_ctx *c, const u64 *in, const u64 *plain, size_t plain_stride, const u64 *addend, u64 *out, int nl, int steps,
-                      size_t count) {
-  if (steps == 0) return count ? mac_separate(c, nullptr, in, plain, plain_stride, addend, out, nl, count, 1) : 0;
-  std::vector<int> terms;
-  if (rotation_terms(c, steps, terms)) return 1;
-  if (!count) return 0;
-  const u64 *cur = in;
-  const size_t last = terms.size() - 1;
-  if (rotate_hops(c, cur, nl, terms, 0, last, count)) return 1;
-  return apply_galois_mac(c, cur, plain, plain_stride, addend, out, nl, elt_from_step(c, terms[last]), count, 1 + (int)(last & 1));
-}
-
-// out = sum_r diags[r] (.) rotate(in, steps[r]), in the order given: the running sum lives in `out`, every term after the first is
-// one rotate_mac with out as its addend
-static int diag_matvec(abc_hip_ctx *c, const u64 *in, const u64 *diags, size_t diag_stride, const std::vector<int> &steps, u64 *out, int nl,
-                       size_t count) {
-  const size_t ctw = count * 2 * (size_t)nl * c->n;
-  for (int s : steps) {  // every step and every key is checked before the first launch
+// every step of a list and every key it needs, before the first launch of the call
+static int check_steps(abc_hip_ctx *c, const std::vector<int> &steps) {
+  for (int s : steps) {
     std::vector<int> terms;
     if (s && rotation_terms(c, s, terms)) return 1;
   }
+  return 0;
+}
+
+// out = tail applied to rotate(in, steps): abc_hip_rotate (empty tail), abc_hip_rotate_add, abc_hip_rotate_mac_plain.  Step 0 has no
+// key switch (a plaintext with an addend multiplies into arena 1).  Hop i of the chain lands in arena 1 + (i & 1) (every hop is out
+// of place); the last one takes the tail and lands in `out`, with the arena the ping-pong would use next as its temporary where
+// its route does not fuse -- a plain rotation in place included, which is that hop into the arena and a copy.
+static int rotate_tail(abc_hip_ctx *c, const u64 *in, const RotTail &tail, u64 *out, int nl, int steps, size_t count) {
+  if (steps == 0) return count ? finish_separate(c, nullptr, in, tail, out, nl, count, 1) : 0;
+  std::vector<int> terms;
+  if (rotation_terms(c, steps, terms)) return 1;
   if (!count) return 0;
-  const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out;
-  if (i0 < o0 + ctw * 8 && o0 < i0 + ctw * 8) { set_error("diag_matvec: d_out must not overlap d_in"); return 1; }
+  const u64 *cur = in;
+  const size_t last = terms.size() - 1;
+  for (size_t i = 0; i < last; i++) {
+    const int which = 1 + (int)(i & 1);
+    if (ensure_aux(c, which, count * 2 * nl * (size_t)c->n * 8)) return 1;
+    u64 *dst = (u64 *)c->aux[which];
+    if (apply_galois_tail(c, cur, {}, dst, nl, elt_from_step(c, terms[i]), count, which)) return 1;
+    cur = dst;
+  }
+  return apply_galois_tail(c, cur, tail, out, nl, elt_from_step(c, terms[last]), count, 1 + (int)(last & 1));
+}
+
+// out = sum_r diags[r] (.) rotate(in, steps[r]), in the order given: the running sum lives in `out`, every term after the first is
+// one rotate_tail with out as its addend
+static int diag_matvec(abc_hip_ctx *c, const u64 *in, const u64 *diags, size_t diag_stride, const std::vector<int> &steps, u64 *out, int nl,
+                       size_t count) {
+  const size_t bytes = count * 2 * (size_t)nl * c->n * 8;
+  if (check_steps(c, steps)) return 1;
+  if (!count) return 0;
+  if (ranges_overlap(in, bytes, out, bytes)) { set_error("diag_matvec: d_out must not overlap d_in"); return 1; }
   if (steps.empty()) {
-    ABC_HIP_CHECK(hipMemsetAsync(out, 0, ctw * 8, c->stream));
+    ABC_HIP_CHECK(hipMemsetAsync(out, 0, bytes, c->stream));
     return 0;
   }
   for (size_t r = 0; r < steps.size(); r++)
-    if (rotate_mac(c, in, diags + r * diag_stride, 0, r ? out : nullptr, out, nl, steps[r], count)) return 1;
+    if (rotate_tail(c, in, {r ? out : nullptr, diags + r * diag_stride, 0}, out, nl, steps[r], count)) return 1;
   return 0;
 }
 
 // acc = in; acc = acc + rotate(acc, s) for each step in order; out = acc.  The running sums ping-pong through arenas 3 and 4
 // (0 .. 2 belong to the rotations), only the last one lands in `out`, which may therefore be `in`.
 static int rotate_sum(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, const std::vector<int> &steps, size_t count) {
-  for (int s : steps) {  // every step is checked before the first launch
-    std::vector<int> terms;
-    if (s && rotation_terms(c, s, terms)) return 1;
-  }
+  if (check_steps(c, steps)) return 1;
   if (!count) return 0;
   const size_t bytes = count * 2 * nl * (size_t)c->n * 8;
   if (steps.empty()) {
@@ -567,7 +528,7 @@ static int rotate_sum(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, const std
   const u64 *acc = in;
   for (size_t i = 0; i < steps.size(); i++) {
     u64 *dst = (i + 1 == steps.size()) ? out : (u64 *)c->aux[3 + (i & 1)];
-    if (rotate_add(c, acc, acc, dst, nl, steps[i], count)) return 1;
+    if (rotate_tail(c, acc, {acc}, dst, nl, steps[i], count)) return 1;
     acc = dst;
   }
   return 0;
@@ -589,8 +550,7 @@ static int hoisted(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, const std::v
     keys[r] = it->second;
   }
   if (elts.empty() || !count) return 0;
-  const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out;
-  if (i0 < o0 + elts.size() * ctw * 8 && o0 < i0 + ctw * 8) { set_error("hoisted rotations: d_out must not overlap d_in"); return 1; }
+  if (ranges_overlap(in, ctw * 8, out, elts.size() * ctw * 8)) { set_error("hoisted rotations: d_out must not overlap d_in"); return 1; }
   for (size_t r = 0; r < elts.size(); r++)  // inside a capture they must exist already
     if (keys[r] && !(keys[r] = key_permuted(c, keys[r], (uint32_t)host::invmod(elts[r], m)))) return 1;
   if (ensure_aux(c, 0, ctw * 8)) return 1;
@@ -1017,8 +977,7 @@ static int check_mac_plain(abc_hip_ctx *c, const char *op, const u64 *plain, siz
   if (c->scheme != ABC_HIP_SCHEME_CKKS) { set_error(std::string(op) + ": CKKS only (a BFV plaintext product needs transforms and is no fold of the key switch)"); return 1; }
   if (check_plain_stride(c, op, stride, nl)) return 1;
   const size_t plain_words = rows ? (rows - 1) * stride + (size_t)nl * c->n : 0;
-  const uintptr_t p0 = (uintptr_t)plain, o0 = (uintptr_t)out;
-  if (plain_words && out_words && p0 < o0 + out_words * 8 && o0 < p0 + plain_words * 8) { set_error(std::string(op) + ": the plaintext must not overlap d_out"); return 1; }
+  if (plain_words && out_words && ranges_overlap(plain, plain_words * 8, out, out_words * 8)) { set_error(std::string(op) + ": the plaintext must not overlap d_out"); return 1; }
   return 0;
 }
 
@@ -1075,35 +1034,35 @@ int abc_hip_mul_relin(abc_hip_ctx *c, const uint64_t *a, const uint64_t *b, uint
 int abc_hip_rotate(abc_hip_ctx *c, const uint64_t *in, uint64_t *out, int nl, int steps, size_t count) {
   CTX_GUARD(c);
   if (check_level(c, nl)) return 1;
-  return rotate(c, in, out, nl, steps, count);
+  return guarded([&] { return rotate_tail(c, in, {}, out, nl, steps, count); });
 }
 int abc_hip_apply_galois(abc_hip_ctx *c, const uint64_t *in, uint64_t *out, int nl, uint32_t elt, size_t count) {
   CTX_GUARD(c);
   if (check_level(c, nl)) return 1;
   if (in == out) { set_error("apply_galois: in-place not supported, use abc_hip_rotate"); return 1; }
-  return apply_galois(c, in, out, nl, elt, count);
+  return guarded([&] { return apply_galois_tail(c, in, {}, out, nl, elt, count, 1); });
 }
 int abc_hip_rotate_add(abc_hip_ctx *c, const uint64_t *in, const uint64_t *addend, uint64_t *out, int nl, int steps, size_t count) {
   CTX_GUARD(c);
   if (check_level(c, nl)) return 1;
-  return guarded([&] { return rotate_add(c, in, addend, out, nl, steps, count); });
+  return guarded([&] { return rotate_tail(c, in, {addend}, out, nl, steps, count); });
 }
 int abc_hip_apply_galois_add(abc_hip_ctx *c, const uint64_t *in, const uint64_t *addend, uint64_t *out, int nl, uint32_t elt, size_t count) {
   CTX_GUARD(c);
   if (check_level(c, nl)) return 1;
-  return apply_galois_add(c, in, addend, out, nl, elt, count, 1);
+  return guarded([&] { return apply_galois_tail(c, in, {addend}, out, nl, elt, count, 1); });
 }
 int abc_hip_rotate_mac_plain(abc_hip_ctx *c, const uint64_t *in, const uint64_t *plain, size_t plain_stride, const uint64_t *addend,
                              uint64_t *out, int nl, int steps, size_t count) {
   CTX_GUARD(c);
   if (check_level(c, nl) || check_mac_plain(c, "rotate_mac_plain", plain, plain_stride, plain_stride ? count : 1, out, count * 2 * (size_t)nl * c->n, nl)) return 1;
-  return guarded([&] { return rotate_mac(c, in, plain, plain_stride, addend, out, nl, steps, count); });
+  return guarded([&] { return rotate_tail(c, in, {addend, plain, plain_stride}, out, nl, steps, count); });
 }
 int abc_hip_apply_galois_mac_plain(abc_hip_ctx *c, const uint64_t *in, const uint64_t *plain, size_t plain_stride, const uint64_t *addend,
                                    uint64_t *out, int nl, uint32_t elt, size_t count) {
   CTX_GUARD(c);
   if (check_level(c, nl) || check_mac_plain(c, "apply_galois_mac_plain", plain, plain_stride, plain_stride ? count : 1, out, count * 2 * (size_t)nl * c->n, nl)) return 1;
-  return apply_galois_mac(c, in, plain, plain_stride, addend, out, nl, elt, count, 1);
+  return guarded([&] { return apply_galois_tail(c, in, {addend, plain, plain_stride}, out, nl, elt, count, 1); });
 }
 int abc_hip_diag_matvec(abc_hip_ctx *c, const uint64_t *in, const uint64_t *diags, size_t diag_stride, const int *h_steps, int n_steps,
                         uint64_t *out, int nl, size_t count) {

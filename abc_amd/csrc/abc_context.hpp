@@ -244,9 +244,9 @@ struct KsOperands {
   bool add_c1 = false;
   const u64 *key = nullptr;  // the key-switching key
   u64 *out = nullptr;        // [count][2][nl][N]
-  const u64 *acc = nullptr;  // with gelt only: a second, ungathered ciphertext [count][2][nl][N] added in the last kernel (RotAddRoute::fused)
+  const u64 *acc = nullptr;  // with gelt only: a second, ungathered ciphertext [count][2][nl][N] added in the last kernel (RotTailRoute::fused)
   // with gelt only: a CKKS plaintext, [nl][N] at plain + ct * plain_stride (0: one for all), that multiplies either component of the
-  // result before acc -- which may then be null -- is added (RotMacRoute::fused)
+  // result before acc -- which may then be null -- is added (RotTailRoute::fused)
   const u64 *plain = nullptr;
   size_t plain_stride = 0;
   u32 gelt = 0;              // the Galois element of a rotation folded into the sequence (RotRoute::fold): target = c1, addend = c0
@@ -265,6 +265,11 @@ struct KsOperands {
     s.count = cc;
     return s;
   }
+};
+// what the last hop of a rotation does with the rotated ciphertext r: out = r (nothing set), addend + r, or addend + plain (.) r (addend optional)
+struct RotTail {
+  const u64 *addend = nullptr, *plain = nullptr;
+  size_t plain_stride = 0;
 };
 
 // ---- abc_buffers.hip: every allocation a recorded circuit may read, and the bodies of the C entry points of that name ----
@@ -356,12 +361,14 @@ struct MainArgs {
   int ni = 0;            // slots
   int pack = 0;          // the half-done limbs are packed (abc_ntt.hpp; k_split4_main_fp only)
 };
-// The last kernels of the split key switches take the second addend of rotate_add as a trailing template parameter PACK: empty
-// for every instantiation that existed (same name, same argument list, same code), <.., WithAcc> with one more argument, the
-// pointer, for the fused form.
+// The last kernels of the split key switches take the tail of a rotation (RotTail, as o.acc / o.plain / o.plain_stride) as a
+// trailing template parameter PACK: empty without a tail (the name, argument list and code the kernel had before there were
+// tails), <.., WithAcc> with one more argument, the pointer, for the second addend of rotate_add, <.., WithMac> below.  The host
+// launches each of them once, from dispatch_tail: `tag` names the pack an argument belongs to.
 struct WithAcc {};
-template <class>
+template <class T>
 struct AccArg {
+  using tag = T;
   const u64 *p;
 };
 __host__ __device__ inline const u64 *acc_ptr() { return nullptr; }
@@ -372,6 +379,7 @@ __host__ __device__ inline const u64 *acc_ptr(AccArg<WithAcc> a) { return a.p; }
 struct WithMac {};
 template <>
 struct AccArg<WithMac> {
+  using tag = WithMac;
   const u64 *plain;
   size_t plain_stride;
   const u64 *p;
@@ -393,6 +401,19 @@ inline void dispatch_mode(int mode, u32 gelt, Fn f) {
   if (mode == 0) f(std::integral_constant<int, 0>{}, std::false_type{});
   else if (gelt) f(std::integral_constant<int, 1>{}, std::true_type{});
   else f(std::integral_constant<int, 1>{}, std::false_type{});
+}
+// the trailing operands of o as the pack its last kernel is instantiated with: f(), f(AccArg<WithAcc>) or f(AccArg<WithMac>).
+// ACC_OK / MAC_OK: the launch site has that form of its kernel (launch_keyswitch has checked o against the sequence: the forms
+// a site lacks do not reach it); f is instantiated for those alone
+template <bool ACC_OK, bool MAC_OK, class Fn>
+inline void dispatch_tail(const KsOperands &o, Fn f) {
+  if constexpr (MAC_OK) {
+    if (o.plain) return f(AccArg<WithMac>{o.plain, o.plain_stride, o.acc});
+  }
+  if constexpr (ACC_OK) {
+    if (o.acc) return f(AccArg<WithAcc>{o.acc});
+  }
+  f();
 }
 // logn -> f(LB) as an integral constant and its result; a ring outside [LO, HI] is an error (the routes keep it from happening)
 template <int LO, int HI, class Fn>

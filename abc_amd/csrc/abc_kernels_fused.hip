@@ -853,49 +853,13 @@ static void launch_split3_main(abc_hip_ctx *c, const MainArgs &a) {
   const int nl = o.nl;
   const dim3 grid((unsigned)(o.count * nl * 16)), block(64 * (nl + 1));
   const size_t lds = (size_t)((nl + 1) * lds_words(10)) * 8;
-  if constexpr (MODE == 1 && GAL) {
-    if (o.plain) {
-#define ABC_TM3M(NLV)                                                                                                                  \
-  hipLaunchKernelGGL((k_split3_main_fp<1, true, NLV, WithMac>), grid, block, lds, a.st, c->dc, (const double *)a.part,               \
-                     (const double *)a.tpart, o.target, o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, nl,      \
-                     o.gather, AccArg<WithMac>{o.plain, o.plain_stride, o.acc})
-      switch (nl) {
-        case 1: ABC_TM3M(1); break;
-        case 2: ABC_TM3M(2); break;
-        case 3: ABC_TM3M(3); break;
-        case 4: ABC_TM3M(4); break;
-        default: ABC_TM3M(0); break;
-      }
-#undef ABC_TM3M
-      return;
-    }
-    if (o.acc) {
-#define ABC_TM3A(NLV)                                                                                                                  \
-  hipLaunchKernelGGL((k_split3_main_fp<1, true, NLV, WithAcc>), grid, block, lds, a.st, c->dc, (const double *)a.part,               \
-                     (const double *)a.tpart, o.target, o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, nl,      \
-                     o.gather, AccArg<WithAcc>{o.acc})
-      switch (nl) {
-        case 1: ABC_TM3A(1); break;
-        case 2: ABC_TM3A(2); break;
-        case 3: ABC_TM3A(3); break;
-        case 4: ABC_TM3A(4); break;
-        default: ABC_TM3A(0); break;
-      }
-#undef ABC_TM3A
-      return;
-    }
-  }
-#define ABC_TM3(NLV)                                                                                                             \
-  hipLaunchKernelGGL((k_split3_main_fp<MODE, GAL, NLV>), grid, block, lds, a.st, c->dc, (const double *)a.part, (const double *)a.tpart, \
-                     o.target, o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, nl, o.gather)
-  switch (nl) {
-    case 1: ABC_TM3(1); break;
-    case 2: ABC_TM3(2); break;
-    case 3: ABC_TM3(3); break;
-    case 4: ABC_TM3(4); break;
-    default: ABC_TM3(0); break;
-  }
-#undef ABC_TM3
+  dispatch_nl<0, 4>(nl <= 4 ? nl : 0, [&](auto NL) {  // 0: the form with a run-time limb count
+    dispatch_tail<MODE == 1 && GAL, MODE == 1 && GAL>(o, [&](auto... tail) {
+      hipLaunchKernelGGL((k_split3_main_fp<MODE, GAL, decltype(NL)::value, typename decltype(tail)::tag...>), grid, block, lds, a.st, c->dc,
+                         (const double *)a.part, (const double *)a.tpart, o.target, o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key,
+                         o.out, nl, o.gather, tail...);
+    });
+  });
 }
 
 
@@ -1207,31 +1171,19 @@ bool split4_main(abc_hip_ctx *c, const MainArgs &a) {
   // a.part / a.tpart: raw or packed doubles here (a mixed chain's fp64 limbs: written as doubles by the integer sequence's first steps)
   dispatch_mode(o.mode, o.gather, [&](auto M, auto G) {
     dispatch_nl<1, 7>(o.nl, [&](auto NL) {
+      constexpr int MODE = decltype(M)::value, NLV = decltype(NL)::value;
+      constexpr bool GAL = decltype(G)::value;
       auto launch = [&](auto H) {
-        if constexpr (decltype(M)::value == 1 && decltype(G)::value) {
-          if constexpr (decltype(NL)::value <= 5) {  // Seq::split14 comes here up to five limbs (route_chunk), and nothing else with a plaintext
-            if (o.plain) {
-              hipLaunchKernelGGL((k_split4_main_fp<1, true, decltype(NL)::value, decltype(H)::value, WithMac>), grid, block,
-                                 main_lds_bytes(o.nl, sizeof(double)), a.st, c->dc, (const double *)a.part, (const double *)a.tpart, o.target,
-                                 o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, o.gather, (u32)a.imap, a.ni, a.pack, keyf,
-                                 AccArg<WithMac>{o.plain, o.plain_stride, o.acc});
-              return;
-            }
-          }
-          if (o.acc) {
-            hipLaunchKernelGGL((k_split4_main_fp<1, true, decltype(NL)::value, decltype(H)::value, WithAcc>), grid, block,
-                               main_lds_bytes(o.nl, sizeof(double)), a.st, c->dc, (const double *)a.part, (const double *)a.tpart, o.target,
-                               o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, o.gather, (u32)a.imap, a.ni, a.pack, keyf,
-                               AccArg<WithAcc>{o.acc});
-            return;
-          }
-        }
-        hipLaunchKernelGGL((k_split4_main_fp<decltype(M)::value, decltype(G)::value, decltype(NL)::value, decltype(H)::value>), grid, block,
-                           main_lds_bytes(o.nl, sizeof(double)), a.st, c->dc, (const double *)a.part, (const double *)a.tpart, o.target,
-                           o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, o.gather, (u32)a.imap, a.ni, a.pack, keyf);
+        // with a plaintext up to five limbs: Seq::split14 comes here up to there (route_chunk), and nothing else has one
+        dispatch_tail<MODE == 1 && GAL, MODE == 1 && GAL && NLV <= 5>(o, [&](auto... tail) {
+          hipLaunchKernelGGL((k_split4_main_fp<MODE, GAL, NLV, decltype(H)::value, typename decltype(tail)::tag...>), grid, block,
+                             main_lds_bytes(o.nl, sizeof(double)), a.st, c->dc, (const double *)a.part, (const double *)a.tpart, o.target,
+                             o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, o.gather, (u32)a.imap, a.ni, a.pack, keyf,
+                             tail...);
+        });
       };
       // up to four limbs LDS holds three workgroups per CU: the pair phase in two halves fits their registers
-      if constexpr (decltype(NL)::value <= 4) {
+      if constexpr (NLV <= 4) {
         if (!c->sw.main_two_per_cu) return launch(std::true_type{});
       }
       launch(std::false_type{});

@@ -778,22 +778,11 @@ static void launch_gsplit_main(abc_hip_ctx *c, const MainArgs &a) {
                          o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, o.gather, o.nl, a.imap, a.ni);
     else
       dispatch_nl<1, 7>(o.nl, [&](auto NL) {
-        if constexpr (MODE == 1 && GAL) {
-          if (o.plain) {
-            hipLaunchKernelGGL((k_gsplit_main<LOGN, 1, true, decltype(NL)::value, WithMac>), gmain, dim3(512), main_lds_bytes(o.nl, sizeof(double)),
-                               a.st, c->dc, part, tpart, o.target, o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, o.gather,
-                               (u32)a.imap, a.ni, AccArg<WithMac>{o.plain, o.plain_stride, o.acc});
-            return;
-          }
-          if (o.acc) {
-            hipLaunchKernelGGL((k_gsplit_main<LOGN, 1, true, decltype(NL)::value, WithAcc>), gmain, dim3(512), main_lds_bytes(o.nl, sizeof(double)),
-                               a.st, c->dc, part, tpart, o.target, o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, o.gather,
-                               (u32)a.imap, a.ni, AccArg<WithAcc>{o.acc});
-            return;
-          }
-        }
-        hipLaunchKernelGGL((k_gsplit_main<LOGN, MODE, GAL, decltype(NL)::value>), gmain, dim3(512), main_lds_bytes(o.nl, sizeof(double)), a.st, c->dc, part,
-                           tpart, o.target, o.addend, o.target_stride, o.addend_stride, o.add_c1, o.key, o.out, o.gather, (u32)a.imap, a.ni);
+        dispatch_tail<MODE == 1 && GAL, MODE == 1 && GAL>(o, [&](auto... tail) {
+          hipLaunchKernelGGL((k_gsplit_main<LOGN, MODE, GAL, decltype(NL)::value, typename decltype(tail)::tag...>), gmain, dim3(512),
+                             main_lds_bytes(o.nl, sizeof(double)), a.st, c->dc, part, tpart, o.target, o.addend, o.target_stride, o.addend_stride,
+                             o.add_c1, o.key, o.out, o.gather, (u32)a.imap, a.ni, tail...);
+        });
       });
   });
 }

@@ -97,14 +97,14 @@ struct RotRoute {
   bool fold;  // the permutation is folded into the key switch `ks`; otherwise k_galois first, then `ks`
   KsRoute ks;
 };
-struct RotAddRoute {
+struct RotTailRoute {
   RotRoute rot;
-  bool fused;  // the second ciphertext is one more operand of the key switch's last kernel; otherwise rotate into an arena, then add
+  // what follows the rotation (a second ciphertext to add; a plaintext to multiply by, then the second ciphertext) is an operand of
+  // the key switch's last kernel; otherwise rotate into an arena, then multiply_plain there where there is a plaintext, then add
+  bool fused;
 };
-struct RotMacRoute {
-  RotRoute rot;
-  bool fused;  // the plaintext and the second ciphertext are operands of the key switch's last kernel; otherwise rotate into an arena, multiply_plain there, then add
-};
+using RotAddRoute = RotTailRoute;  // per operation, as tests/cpp name it
+using RotMacRoute = RotTailRoute;
 struct RescaleRoute {
   Rescale kind;
   uint32_t fpmask;  // mixed: limbs that take the fp64 butterflies
@@ -216,14 +216,14 @@ inline RotRoute route_rotate(const RouteFacts &f, int nl, bool in_place) {
 
 // addend + one Galois element at level nl; in_place: d_out == d_in (the gather reads whole limbs of d_in, so that call is never
 // fused).  `rot` is the rotation either way: the unfused sequence rotates into an arena, never in place, whatever d_out is.
-inline RotAddRoute route_rotate_add(const RouteFacts &f, int nl, bool in_place) {
+inline RotTailRoute route_rotate_add(const RouteFacts &f, int nl, bool in_place) {
   const RotRoute rot = route_rotate(f, nl, false);
   return {rot, rot.fold && seq_takes_acc(f, rot.ks, nl) && !in_place && !f.sw.no_rotate_add_fusion};
 }
 
 // addend + plain (.) one Galois element at level nl (CKKS); in_place and `rot` as in route_rotate_add.  The unfused sequence
 // rotates into an arena, multiplies there in place, then adds.
-inline RotMacRoute route_rotate_mac(const RouteFacts &f, int nl, bool in_place) {
+inline RotTailRoute route_rotate_mac(const RouteFacts &f, int nl, bool in_place) {
   const RotRoute rot = route_rotate(f, nl, false);
   return {rot, rot.fold && seq_takes_plain(f, rot.ks, nl) && !in_place && !f.sw.no_rotate_mac_fusion};
 }
@@ -336,11 +336,11 @@ inline int format_op(char *buf, size_t cap, const RouteFacts &f, int op, int nl,
     format_ks(ks, sizeof ks, f, r.ks, nl, count);
     n = snprintf(buf, cap, "%s %s", r.fold ? "fold" : "permute", ks);
   } else if (op == kRouteRotateAdd) {
-    const RotAddRoute r = route_rotate_add(f, nl, in_place);
+    const RotTailRoute r = route_rotate_add(f, nl, in_place);
     format_ks(ks, sizeof ks, f, r.rot.ks, nl, count);
     n = r.fused ? snprintf(buf, cap, "fold+add %s", ks) : snprintf(buf, cap, "%s add=separate %s", r.rot.fold ? "fold" : "permute", ks);
   } else if (op == kRouteRotateMacPlain) {
-    const RotMacRoute r = route_rotate_mac(f, nl, in_place);
+    const RotTailRoute r = route_rotate_mac(f, nl, in_place);
     format_ks(ks, sizeof ks, f, r.rot.ks, nl, count);
     n = r.fused ? snprintf(buf, cap, "fold+mac %s", ks) : snprintf(buf, cap, "%s mac=separate %s", r.rot.fold ? "fold" : "permute", ks);
   } else if (op == kRouteRescale) {

@@ -137,26 +137,28 @@ def rotate_mac_ab(res, only, rng):
 
 
 def keyswitch_batch1(res, only, rng):
-    """one ciphertext per call at nl = 4: relinearise, rotate and rotate_add on the two CKKS split rings -- the calls in which the
-    host side of the key switch (routes, operand record, launches) is the largest share"""
+    """one ciphertext per call at nl = 4: relinearise, rotate, rotate_add and rotate_mac_plain (one plaintext, one addend) on the two
+    CKKS split rings -- the calls in which the host side of the key switch (routes, operand record, launches) is the largest share"""
     for n in (16384, 32768):
-        names = ["ckks%d_b1_%s" % (n.bit_length() - 1, op) for op in ("relinearize", "rotate", "rotate_add")]
+        names = ["ckks%d_b1_%s" % (n.bit_length() - 1, op) for op in ("relinearize", "rotate", "rotate_add", "rotate_mac_plain")]
         if not any(only in k for k in names):
             continue
         g = capi.Context(capi.CKKS, n, capi.create_primes(n, [50, 40, 40, 40, 50]))
         g.keygen(1)
-        one = C.c_size_t(1)
-        (a, nb), (b, _), (t3, _) = rand_ct(g, rng, 1, 2, 4), rand_ct(g, rng, 1, 2, 4), rand_ct(g, rng, 1, 3, 4)
+        one, zero = C.c_size_t(1), C.c_size_t(0)
+        (a, nb), (b, _), (t3, _), (p, _) = rand_ct(g, rng, 1, 2, 4), rand_ct(g, rng, 1, 2, 4), rand_ct(g, rng, 1, 3, 4), rand_ct(g, rng, 1, 1, 4)
         out = g.alloc(nb)
-        ops = (lambda: g.op("relinearize", t3.ptr, out.ptr, 4, one), lambda: g.op("rotate", a.ptr, out.ptr, 4, 1, one),
-               lambda: g.op("rotate_add", a.ptr, b.ptr, out.ptr, 4, 1, one))
+        ops = [lambda: g.op("relinearize", t3.ptr, out.ptr, 4, one), lambda: g.op("rotate", a.ptr, out.ptr, 4, 1, one),
+               lambda: g.op("rotate_add", a.ptr, b.ptr, out.ptr, 4, 1, one)]
+        if hasattr(capi.lib(), "abc_hip_rotate_mac_plain"):  # not in a build older than the call (ABC_HIP_LIB)
+            ops.append(lambda: g.op("rotate_mac_plain", a.ptr, p.ptr, zero, b.ptr, out.ptr, 4, 1, one))
         for k, fn in zip(names, ops):
             if only in k:
                 timeit(g, fn, reps=20)
                 ms = timeit(g, fn, reps=300)
                 res[k] = {"batch": 1, "ms": ms, "route": g.route(k.split("_b1_")[1], 4, 1)}
                 print("%-40s %8.3f us (batch 1; %s)" % (k, ms * 1e3, res[k]["route"]), flush=True)
-        del a, b, t3, out
+        del a, b, t3, p, out
         g.close()
 
 
