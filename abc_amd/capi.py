@@ -38,6 +38,7 @@ SYMBOLS = [
     "abc_hip_apply_galois_hoisted", "abc_hip_rotate_hoisted",
     "abc_hip_rotate_add", "abc_hip_apply_galois_add", "abc_hip_rotate_sum",
     "abc_hip_rotate_mac_plain", "abc_hip_apply_galois_mac_plain", "abc_hip_diag_matvec",
+    "abc_hip_multiply_plain_rescale",
 ]
 
 
@@ -203,7 +204,7 @@ class Context:
         _chk(lib().abc_hip_ctx_reload_env(self.h))
 
     ROUTE_OPS = {"mul_relin": 0, "keyswitch": 1, "relinearize": 1, "rotate": 2, "rescale": 3, "multiply": 4, "rotate_add": 5,
-                 "rotate_mac_plain": 7}
+                 "rotate_mac_plain": 7, "multiply_plain_rescale": 10}
 
     def route(self, op, nl, count=1, in_place=False):
         """the kernel sequence such a call takes, as the string of abc_route.hpp's formatter"""
@@ -458,6 +459,23 @@ class Context:
         a4 = self._batch(ct, 3)
         shp = (a4.shape[0], a4.shape[1], a4.shape[2] - 1, self.n)
         r = self._run("rescale", [a4], shp, a4.shape[1], a4.shape[2], C.c_size_t(a4.shape[0]))
+        return r if np.ndim(ct) == 4 else r[0]
+
+    def multiply_plain_rescale(self, ct, plain):
+        """rescale(ct (.) plain) as one call (abc_hip_multiply_plain_rescale), CKKS.  plain: [nl][N] for the batch, or
+        [count][rows >= nl][N], one per ciphertext.  The product is formed in the rescale's loads where route("multiply_plain_rescale") says so"""
+        a4 = self._batch(ct, 3)
+        count, size, nl = a4.shape[:3]
+        plain = np.ascontiguousarray(plain, dtype=np.uint64)
+        stride = 0 if plain.ndim == 2 else plain.shape[1] * self.n
+        shp = (count, size, nl - 1, self.n)
+        bufs = [self.upload(a4), self.upload(plain), self.alloc(max(int(np.prod(shp)), 1) * 8)]
+        try:
+            self.op("multiply_plain_rescale", bufs[0].ptr, bufs[1].ptr, C.c_size_t(stride), bufs[2].ptr, size, nl, C.c_size_t(count))
+            r = self.download(bufs[2], shp)
+        finally:
+            for b in bufs:
+                b.free()
         return r if np.ndim(ct) == 4 else r[0]
 
     def mod_switch(self, ct):

@@ -44,6 +44,7 @@ void read_switches(abc_hip_ctx *c) {
   s.no_galois_fusion = env_on("ABC_HIP_NO_GALOIS_FUSION");
   s.no_rotate_add_fusion = env_on("ABC_HIP_NO_ROTATE_ADD_FUSION");
   s.no_rotate_mac_fusion = env_on("ABC_HIP_NO_ROTATE_MAC_FUSION");
+  s.no_mulplain_rescale_fusion = env_on("ABC_HIP_NO_MULPLAIN_RESCALE_FUSION");
   s.main_two_per_cu = env_on("ABC_HIP_MAIN_TWO_PER_CU");
   s.host_sampling = env_on("ABC_HIP_HOST_SAMPLING");
   if (const char *e = std::getenv("ABC_HIP_CHUNK")) s.chunk = (size_t)std::atol(e);
@@ -985,6 +986,7 @@ int abc_hip_route(abc_hip_ctx *c, int op, int nl, size_t count, int in_place, ch
   CTX_GUARD(c);
   if (check_level(c, nl)) return 1;  // nl as the operation itself takes it (BFV: L, also for multiply)
   if (op == kRouteRescale && (nl < 2 || c->scheme != ABC_HIP_SCHEME_CKKS)) { set_error("route: rescale needs CKKS and nl >= 2"); return 1; }
+  if (op == kRouteMulPlainRescale && (nl < 2 || c->scheme != ABC_HIP_SCHEME_CKKS)) { set_error("route: multiply_plain_rescale needs CKKS and nl >= 2"); return 1; }
   const int n = buf ? format_op(buf, cap, c->facts, op, nl, count, in_place != 0) : -1;
   if (n == -2) { set_error("route: unknown operation"); return 1; }
   if (n < 0) { set_error("route: buffer too small"); return 1; }
@@ -1126,6 +1128,21 @@ int abc_hip_rescale(abc_hip_ctx *c, const uint64_t *in, uint64_t *out, int size,
   if (check_level(c, nl)) return 1;
   if (in == out) { set_error("rescale: d_out must not alias d_in (the output has one limb less per polynomial)"); return 1; }
   return launch_rescale(c, in, out, size, nl, count);
+}
+int abc_hip_multiply_plain_rescale(abc_hip_ctx *c, const uint64_t *ct, const uint64_t *plain, size_t plain_stride, uint64_t *out, int size,
+                                   int nl, size_t count) {
+  CTX_GUARD(c);
+  if (c->scheme != ABC_HIP_SCHEME_CKKS) { set_error("multiply_plain_rescale is a CKKS operation"); return 1; }
+  if (check_level(c, nl)) return 1;
+  if (nl < 2) { set_error("multiply_plain_rescale: no limb left to drop"); return 1; }
+  if (size != 2 && size != 3) { set_error("multiply_plain_rescale: size must be 2 or 3"); return 1; }
+  const size_t N = (size_t)c->n, out_words = count * size * (size_t)(nl - 1) * N;
+  if (check_mac_plain(c, "multiply_plain_rescale", plain, plain_stride, plain_stride ? count : 1, out, out_words, nl)) return 1;
+  if (out_words && ranges_overlap(ct, count * size * (size_t)nl * N * 8, out, out_words * 8)) {
+    set_error("multiply_plain_rescale: d_out must not overlap d_ct (the output has one limb less per polynomial)");
+    return 1;
+  }
+  return launch_mulplain_rescale(c, ct, plain, plain_stride, out, size, nl, count);
 }
 int abc_hip_mod_switch(abc_hip_ctx *c, const uint64_t *in, uint64_t *out, int size, int nl, size_t count) {
   CTX_GUARD(c);

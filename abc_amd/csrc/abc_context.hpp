@@ -196,7 +196,7 @@ struct abc_hip_ctx {
   };
   std::unordered_map<const uint64_t *, KeyMirror> key_mirrors;
   std::vector<uint32_t> galois_order;
-  // workspace (kernel-sequence scratch) and five caller-level arenas (0: permuted input, 1 / 2: products and rotation ping-pong, 3 / 4: rotate_sum's running sums);
+  // workspace (kernel-sequence scratch) and five caller-level arenas (0: permuted input, 1 / 2: products (multiply_plain_rescale's separate route among them) and rotation ping-pong, 3 / 4: rotate_sum's running sums);
   // all grow on demand and are reused, so steady-state calls perform no hipMalloc / hipFree; one that grows while a graph owns
   // it is held back, not freed (ensure_arena in abc_buffers.hip)
   void *ws = nullptr;
@@ -311,6 +311,7 @@ int launch_ks_finish(abc_hip_ctx *c, const u64 *prodD, const u64 *tmod, u64 *out
                      bool add_c1, int nl, size_t count);
 int launch_galois(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, size_t polys, uint32_t elt, bool ntt_form);
 int launch_rescale(abc_hip_ctx *c, const u64 *in, u64 *out, int size, int nl, size_t count);
+int launch_mulplain_rescale(abc_hip_ctx *c, const u64 *ct, const u64 *plain, size_t plain_stride, u64 *out, int size, int nl, size_t count);
 int launch_drop_last(abc_hip_ctx *c, const u64 *in, u64 *out, int size, int nl, size_t count);
 
 int bfv_multiply(abc_hip_ctx *c, BfvMul m, const u64 *a, const u64 *b, u64 *out3, size_t count);

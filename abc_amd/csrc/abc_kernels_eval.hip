@@ -636,6 +636,94 @@ int launch_rescale(abc_hip_ctx *c, const u64 *in, u64 *out, int size, int nl, si
                                 polys);
 }
 
+// ---- multiply_plain + rescale in one: the product with the plaintext formed in the loads of R1 and R2 (the policies' mul_u64) ----
+// Kernels of their own beside the unfused ones, whose device code stays what it was.  Polynomial p belongs to ciphertext p / size, whose
+// plaintext row starts at (p / size) * plain_stride ([nl][N], stride 0: one row for the batch).  R2's nl - 1 workgroups of a polynomial
+// share an L2 as before (xcd_slot); with one row for the batch, limb j of the plaintext is shared by every workgroup of that limb.
+template <int LB>
+__global__ __launch_bounds__((1 << LB) / 16) void k_mulplain_rescale_intt_fp(DevCtx c, const u64 *__restrict__ in, const u64 *__restrict__ plain,
+                                                                             size_t plain_stride, u64 *__restrict__ last, int size, int nl) {
+  __shared__ double lds[lds_words(LB)];
+  const size_t N = (size_t)1 << LB, p = blockIdx.x;
+  divround_to_coef<LB, FpArith, true>(lds, mod_at(c, nl - 1), fp_table(c, nl - 1), in + (p * nl + (nl - 1)) * N, last + p * N,
+                                      plain + (p / size) * plain_stride + (size_t)(nl - 1) * N);
+}
+template <int LB>
+__global__ __launch_bounds__((1 << LB) / 16) void k_mulplain_rescale_intt_mixed(DevCtx c, const u64 *__restrict__ in, const u64 *__restrict__ plain,
+                                                                                size_t plain_stride, u64 *__restrict__ last, int size, int nl,
+                                                                                int fp_last) {
+  __shared__ u64 lds_raw[lds_words(LB)];
+  const size_t N = (size_t)1 << LB, p = blockIdx.x;
+  const u64 *__restrict__ src = in + (p * nl + (nl - 1)) * N;
+  const u64 *__restrict__ pl = plain + (p / size) * plain_stride + (size_t)(nl - 1) * N;
+  u64 *__restrict__ dst = last + p * N;
+  if (fp_last)
+    divround_to_coef<LB, FpArith, true>(reinterpret_cast<double *>(lds_raw), mod_at(c, nl - 1), fp_table(c, nl - 1), src, dst, pl);
+  else
+    divround_to_coef<LB, IntArith<true>, true>(lds_raw, c.mods[nl - 1], ntt_table(c, nl - 1), src, dst, pl);
+}
+template <int LB, bool MIXED>
+__global__ __launch_bounds__((1 << LB) / 16) void k_mulplain_rescale_ntt(DevCtx c, const u64 *__restrict__ in, const u64 *__restrict__ plain,
+                                                                         size_t plain_stride, const u64 *__restrict__ last, u64 *__restrict__ out,
+                                                                         int size, int nl, int npoly, u32 fpmask) {
+  __shared__ u64 lds_raw[lds_words(LB)];
+  int j;
+  size_t p;
+  xcd_slot(blockIdx.x, nl - 1, npoly, j, p);
+  const size_t N = (size_t)1 << LB;
+  const Mod m = MIXED ? c.mods[j] : mod_at(c, j);
+  const auto fix = round_fix<std::conditional_t<MIXED, u64, double>>(c.mods[nl - 1].q >> 1, m);
+  const DropInv d = inv_qlast_at(c, nl - 1, j);
+  const u64 *__restrict__ src = last + p * N;
+  const u64 *__restrict__ x = in + (p * nl + j) * N;
+  const u64 *__restrict__ pl = plain + (p / size) * plain_stride + (size_t)j * N;
+  u64 *__restrict__ o = out + (p * (nl - 1) + j) * N;
+  if constexpr (!MIXED)
+    divround_finish<LB, FpArith, false, false, true>(reinterpret_cast<double *>(lds_raw), m, fp_table(c, j), fix, d, src, x, nullptr, o, pl);
+  else if ((fpmask >> j) & 1u)
+    divround_finish<LB, FpArith, true, false, true>(reinterpret_cast<double *>(lds_raw), mod_at(c, j), fp_table(c, j), fix, d, src, x, nullptr, o, pl);
+  else
+    divround_finish<LB, IntArith<true>, false, false, true>(lds_raw, m, ntt_table(c, j), fix, d, src, x, nullptr, o, pl);
+}
+template <int LB, bool MIXED>
+static int launch_mulplain_rescale_lds(abc_hip_ctx *c, const u64 *in, const u64 *plain, size_t plain_stride, u64 *out, int size, int nl,
+                                       size_t polys, u32 fpmask) {
+  const size_t N = (size_t)1 << LB;
+  if (ensure_workspace(c, polys * N * 8)) return 1;
+  u64 *last = (u64 *)c->ws;
+  const dim3 block((1 << LB) / 16);
+  if constexpr (MIXED)
+    hipLaunchKernelGGL(k_mulplain_rescale_intt_mixed<LB>, dim3((unsigned)polys), block, 0, c->stream, c->dc, in, plain, plain_stride, last, size, nl,
+                       (int)((fpmask >> (nl - 1)) & 1u));
+  else
+    hipLaunchKernelGGL(k_mulplain_rescale_intt_fp<LB>, dim3((unsigned)polys), block, 0, c->stream, c->dc, in, plain, plain_stride, last, size, nl);
+  hipLaunchKernelGGL((k_mulplain_rescale_ntt<LB, MIXED>), dim3((unsigned)(polys * (nl - 1))), block, 0, c->stream, c->dc, in, plain, plain_stride,
+                     last, out, size, nl, (int)polys, fpmask);
+  ABC_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// out [count][size][nl-1][N] = rescale(ct (.) plain): fused into the LDS-resident rescale, or the product into arena 1 (the products'
+// arena: abc_context.hpp) and launch_rescale on it.  The caller has checked the scheme, the stride and the overlaps.
+int launch_mulplain_rescale(abc_hip_ctx *c, const u64 *ct, const u64 *plain, size_t plain_stride, u64 *out, int size, int nl, size_t count) {
+  if (nl < 2) { set_error("multiply_plain_rescale: no limb left to drop"); return 1; }
+  const size_t polys = count * size;
+  if (!polys) return 0;
+  const MulPlainRescaleRoute r = route_mulplain_rescale(c->facts, nl);
+  if (r.fused && r.rescale.kind == Rescale::mixed)
+    return dispatch_logn<10, 14>(c->logn, [&](auto LB) {
+      return launch_mulplain_rescale_lds<decltype(LB)::value, true>(c, ct, plain, plain_stride, out, size, nl, polys, r.rescale.fpmask);
+    });
+  if (r.fused)
+    return dispatch_logn<10, 14>(c->logn, [&](auto LB) {
+      return launch_mulplain_rescale_lds<decltype(LB)::value, false>(c, ct, plain, plain_stride, out, size, nl, polys, 0u);
+    });
+  if (ensure_aux(c, 1, polys * nl * (size_t)c->n * 8)) return 1;
+  u64 *prod = (u64 *)c->aux[1];
+  if (ckks_multiply_plain(c, ct, plain, plain_stride, prod, size, nl, count)) return 1;
+  return launch_rescale(c, prod, out, size, nl, count);
+}
+
 int launch_drop_last(abc_hip_ctx *c, const u64 *in, u64 *out, int size, int nl, size_t count) {
   if (nl < 2) { set_error("mod_switch: no limb left to drop"); return 1; }
   const size_t N = (size_t)c->n, polys = count * size;

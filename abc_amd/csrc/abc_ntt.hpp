@@ -244,6 +244,8 @@ struct IntArith {
   template <int PASS> __device__ __forceinline__ static void inv_begin(E (&)[16], const K &) {}
   // ---- element operations of the functors around a transform (the same names on every policy) ----
   __device__ __forceinline__ static E from_u64(u64 v) { return v; }  // canonical residue -> E
+  // product of two canonical residues -> E, as from_u64 of the canonical product would enter (a plaintext folded into a load)
+  __device__ __forceinline__ static E mul_u64(u64 a, u64 b, const Mod &m) { return mul_mod(a, b, m); }
   // may a canonical residue of a prime q_from enter the forward transform modulo m as it is?  (guarded: inputs < 4q; unguarded: < 8q,
   // 57q of growth on top stays below the 64q its consumers assume)
   __device__ __forceinline__ static bool fwd_accepts(u64 q_from, const Mod &m) { return GUARD ? q_from <= m.q : (q_from >> 3) < m.q; }
@@ -298,6 +300,10 @@ struct FpArith {
   }
   // ---- element operations (see IntArith): values stay lazy doubles until the single canonicalisation of canon / canon_add ----
   __device__ __forceinline__ static E from_u64(u64 v) { return fp_from_u64(v); }
+  // the split product of fp_mulmod on the two converted words: exact, |result| < q -- the magnitude from_u64 of a canonical word
+  // has, so every bound of the transforms holds as it stands (the integer product and one conversion is the longer form:
+  // DESIGN.md section 4, "Plaintext product in the rescale's loads")
+  __device__ __forceinline__ static E mul_u64(u64 a, u64 b, const Mod &m) { return fp_mulmod(fp_from_u64(a), fp_from_u64(b), m.qd, m.qinv); }
   // no reduction at all: a forward transform tolerates inputs up to 2^50 for targets below 2^49 (growth (1 + 2^-5)^14), and the
   // 49/50-bit targets, which re-centre at every pass, accept the at most 2q such an operand amounts to
   __device__ __forceinline__ static bool fwd_accepts(u64, const Mod &) { return true; }
@@ -770,24 +776,31 @@ __device__ __forceinline__ void ntt_inv_block(u64 *lds, Load load, Store store, 
 
 // ---- divide and round, LDS-resident (one workgroup per limb): the two steps of "divide by a dropped prime" above -------------
 // Step A: the dropped limb (NTT form at src; m, t: the dropped prime) -> coefficients, N^-1, + floor(p/2) -> dst, canonical
-template <int LB, class A>
+// MUL: the limb is src (.) pl, the product with a plaintext limb formed in the load (multiply_plain + rescale in one)
+template <int LB, class A, bool MUL = false>
 __device__ __forceinline__ void divround_to_coef(typename A::E *lds, const Mod m, const typename A::Table t,
-                                                 const u64 *__restrict__ src, u64 *__restrict__ dst) {
+                                                 const u64 *__restrict__ src, u64 *__restrict__ dst,
+                                                 const u64 *__restrict__ pl = nullptr) {
   using E = typename A::E;
   const E half = (E)(m.q >> 1);
   ntt_inv_block_a<LB, A>(
-      lds, [&](int, int i) { return A::from_u64(src[i]); }, [&](int, int i, E v) { dst[i] = A::canon_add(A::scale_n(v, m), half, m); }, t, m,
-      0, 0);
+      lds,
+      [&](int, int i) {
+        if constexpr (MUL) return A::mul_u64(src[i], pl[i], m);
+        else return A::from_u64(src[i]);
+      },
+      [&](int, int i, E v) { dst[i] = A::canon_add(A::scale_n(v, m), half, m); }, t, m, 0, 0);
 }
 // Step B for one remaining prime (m, t):  o = (x - NTT(tl mod q + fix)) p^-1 (+ cin), with tl = step A's output, d = p^-1 mod q,
 // cin = the addend's limb (ADD; callers choose by a workgroup-uniform branch: two straight-line bodies, no per-element select).
 // REDUCE: t is reduced modulo q as an integer whatever the policy, and fix = round_fix<u64> -- FpArith where the dropped prime
 // may be wider than 2^52 (canonical, + fix, below 2q).  Otherwise fix = round_fix<A::E> and the policy's own load.
-template <int LB, class A, bool REDUCE, bool ADD>
+// MUL: x is x (.) pl, as in step A.
+template <int LB, class A, bool REDUCE, bool ADD, bool MUL = false>
 __device__ __forceinline__ void divround_finish(typename A::E *lds, const Mod m, const typename A::Table t,
                                                 const std::conditional_t<REDUCE, u64, typename A::E> fix, const DropInv d,
                                                 const u64 *__restrict__ tl, const u64 *__restrict__ x, const u64 *__restrict__ cin,
-                                                u64 *__restrict__ o) {
+                                                u64 *__restrict__ o, const u64 *__restrict__ pl = nullptr) {
   using E = typename A::E;
   ntt_fwd_block_a<LB, A>(
       lds,
@@ -796,7 +809,10 @@ __device__ __forceinline__ void divround_finish(typename A::E *lds, const Mod m,
         else return A::reduce_fix(tl[i], fix, m);
       },
       [&](int, int i, E v) {
-        const E r = A::diff_mul_fwd(A::from_u64(x[i]), v, d, m);
+        E xi;
+        if constexpr (MUL) xi = A::mul_u64(x[i], pl[i], m);
+        else xi = A::from_u64(x[i]);
+        const E r = A::diff_mul_fwd(xi, v, d, m);
         if constexpr (ADD) o[i] = A::canon_add(r, A::from_u64(cin[i]), m);
         else o[i] = A::canon(r, m);
       },

@@ -23,6 +23,7 @@ struct Switches {
   bool no_galois_fusion = false;
   bool no_rotate_add_fusion = false;  // ABC_HIP_NO_ROTATE_ADD_FUSION: rotate_add as a rotation into an arena, then the add kernel
   bool no_rotate_mac_fusion = false;  // ABC_HIP_NO_ROTATE_MAC_FUSION: rotate_mac_plain as a rotation into an arena, multiply_plain on it, then the add kernel
+  bool no_mulplain_rescale_fusion = false;  // ABC_HIP_NO_MULPLAIN_RESCALE_FUSION: multiply_plain_rescale as multiply_plain into an arena, then rescale
   bool main_two_per_cu = false;  // ABC_HIP_MAIN_TWO_PER_CU: k_split4_main_fp in its one-piece pair phase at nl <= 4 (same step, same route: a form of the kernel)
   bool host_sampling = false;  // ABC_HIP_HOST_SAMPLING: the keyed entries (the OS-keyed ones call them) draw with the host twin of the keyed spec (no route depends on it)
   size_t chunk = 0, few_limbs = 48, lean_limit = 96, bfv_scratch_mb = 0, pass0_target_limit = 128;
@@ -108,6 +109,10 @@ using RotMacRoute = RotTailRoute;
 struct RescaleRoute {
   Rescale kind;
   uint32_t fpmask;  // mixed: limbs that take the fp64 butterflies
+};
+struct MulPlainRescaleRoute {
+  RescaleRoute rescale;  // the rescale, out of place
+  bool fused;            // the plaintext product is formed in that rescale's loads; otherwise multiply_plain into an arena, then the rescale on it
 };
 
 namespace route_detail {
@@ -235,6 +240,13 @@ inline RescaleRoute route_rescale(const RouteFacts &f, int nl, bool in_place) {
   return {Rescale::mixed, (f.use_fp && !f.sw.no_mixed) ? f.fp_data_mask(nl) : 0u};  // a prime above 2^50 in the chain
 }
 
+// rescale(ct (.) plain) at level nl (CKKS): the LDS-resident rescale kernels take the plaintext as an operand of their loads; the
+// generic sequence does not
+inline MulPlainRescaleRoute route_mulplain_rescale(const RouteFacts &f, int nl) {
+  const RescaleRoute r = route_rescale(f, nl, false);
+  return {r, r.kind != Rescale::generic && !f.sw.no_mulplain_rescale_fusion};
+}
+
 // ---- per chunk ----
 struct ChunkPlan {
   size_t chunk;
@@ -320,7 +332,7 @@ inline void format_ks(char *buf, size_t cap, const RouteFacts &f, const KsRoute 
 }
 // The route of one call into buf: what abc_hip_route returns.  op: include/abc_hip.h, ABC_HIP_ROUTE_*.  Returns the length,
 // -1 if cap is too small, -2 for an unknown op.
-enum RouteOp { kRouteMulRelin = 0, kRouteKeyswitch = 1, kRouteRotate = 2, kRouteRescale = 3, kRouteMultiply = 4, kRouteRotateAdd = 5, kRouteRotateMacPlain = 7 };  // 6 stays unassigned: the host tests probe it as the unknown operation
+enum RouteOp { kRouteMulRelin = 0, kRouteKeyswitch = 1, kRouteRotate = 2, kRouteRescale = 3, kRouteMultiply = 4, kRouteRotateAdd = 5, kRouteRotateMacPlain = 7, kRouteMulPlainRescale = 10 };  // 6, 8 and 9 stay unassigned: the host tests probe them as unknown operations
 inline int format_op(char *buf, size_t cap, const RouteFacts &f, int op, int nl, size_t count, bool in_place) {
   char ks[80];
   int n = -2;
@@ -346,6 +358,11 @@ inline int format_op(char *buf, size_t cap, const RouteFacts &f, int op, int nl,
   } else if (op == kRouteRescale) {
     const RescaleRoute r = route_rescale(f, nl, in_place);
     n = r.kind == Rescale::mixed ? snprintf(buf, cap, "mixed fpmask=0x%x", (unsigned)r.fpmask) : snprintf(buf, cap, "%s", name(r.kind));
+  } else if (op == kRouteMulPlainRescale) {
+    const MulPlainRescaleRoute r = route_mulplain_rescale(f, nl);
+    const char *how = r.fused ? "fused" : "separate";
+    n = r.rescale.kind == Rescale::mixed ? snprintf(buf, cap, "mixed fpmask=0x%x mulplain=%s", (unsigned)r.rescale.fpmask, how)
+                                         : snprintf(buf, cap, "%s mulplain=%s", name(r.rescale.kind), how);
   } else if (op == kRouteMultiply) {
     n = snprintf(buf, cap, "%s", f.scheme == 1 ? name(route_bfv_multiply(f)) : "tensor");
   }

@@ -291,14 +291,28 @@ void HipCiphertext::multiplyPlainInplace(const ICleartext &operand) {
     const auto vals = realCleartext(operand, "MULTIPLY");
     bool allMinusOne = !vals.empty();
     for (double v : vals) allMinusOne = allMinusOne && v == -1.0;
-    auto t = target();
     if (allMinusOne) {  // negation shortcut, src/runtime/SealCiphertext.cpp:192-193: no level is spent
+      auto t = target();
       abcHipCheck(abc_hip_negate(getFactory().context(), in(), t->p, 2, nl, getFactory().batchSize()), "negate");
       adopt(std::move(t));
       return;
     }
     const double ps = getFactory().defaultScale();
     const uint64_t *pl = getFactory().cachedCkksPlaintext(vals, nl, ps);
+    if (nl >= 2 && getFactory().fusesMultiplyPlainRescale()) {
+      // product and rescale as one call: the words of the two calls below, bookkeeping as rescaleIfPossible does it; the check
+      // throws before anything is enqueued
+      const auto &f = getFactory();
+      checkScaleFits(sc * ps, nl);
+      auto r = allocate(f, nl - 1);
+      abcHipCheck(abc_hip_multiply_plain_rescale(f.context(), in(), pl, 0, r->p, 2, nl, f.batchSize()), "multiply_plain_rescale");
+      f.countFusedMultiplyPlainRescale();
+      sc = sc * ps / (double)f.prime(nl - 1);
+      buf = std::move(r);
+      --nl;
+      return;
+    }
+    auto t = target();
     abcHipCheck(abc_hip_multiply_plain(getFactory().context(), in(), pl, 0, t->p, 2, nl, getFactory().batchSize()), "multiply_plain");
     adopt(std::move(t));
     sc *= ps;

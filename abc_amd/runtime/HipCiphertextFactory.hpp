@@ -34,6 +34,9 @@ struct HipSchemeConfig {
   // `lhs +++ rotate(v, k)` as one abc_hip_rotate_add (HipCiphertext::addRotatedInplace); off: rotateRows + addInplace, for A/B
   // runs and so that a test can compare both paths in one process
   bool fuseRotateAdd = true;
+  // CKKS `ct * weights` as one abc_hip_multiply_plain_rescale (HipCiphertext::multiplyPlainInplace at two limbs or more); off:
+  // abc_hip_multiply_plain, then abc_hip_rescale.  The words are the same either way, so it stays on; off is for A/B runs and tests
+  bool fuseMultiplyPlainRescale = true;
 };
 
 class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapable {
@@ -67,6 +70,8 @@ class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapab
   bool hostCkksCodec = false;
   bool fuseRotateAdd = true;
   mutable size_t fusedRotateAdds = 0;  // abc_hip_rotate_add calls issued by addRotatedInplace
+  bool fuseMultiplyPlainRescale = true;
+  mutable size_t fusedMultiplyPlainRescales = 0;  // abc_hip_multiply_plain_rescale calls issued by multiplyPlainInplace
   struct CachedCkksPlain {
     std::vector<double> values;
     int level;
@@ -102,6 +107,10 @@ class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapab
   void setFuseRotateAdd(bool on) { fuseRotateAdd = on; }
   [[nodiscard]] size_t fusedRotateAddCalls() const { return fusedRotateAdds; }
   void countFusedRotateAdd() const { ++fusedRotateAdds; }
+  [[nodiscard]] bool fusesMultiplyPlainRescale() const { return fuseMultiplyPlainRescale; }
+  void setFuseMultiplyPlainRescale(bool on) { fuseMultiplyPlainRescale = on; }
+  [[nodiscard]] size_t fusedMultiplyPlainRescaleCalls() const { return fusedMultiplyPlainRescales; }
+  void countFusedMultiplyPlainRescale() const { ++fusedMultiplyPlainRescales; }
   [[nodiscard]] double defaultScale() const { return ckksScale; }
   // CKKS: largest relative difference between the scales of two addends that is drift, not a mismatch
   [[nodiscard]] double scaleTolerance() const { return ckksScaleTol; }

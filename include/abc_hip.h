@@ -67,7 +67,7 @@ int abc_hip_ctx_reload_env(abc_hip_ctx *ctx);
  * to buf as a short string such as "split14 front=lean pack=1 main=split4"; per-chunk fields are those of the first
  * chunk.  in_place: d_out aliases d_in (rotate, rescale).  Read-only: allocates nothing, launches nothing, touches no
  * stream (legal inside abc_hip_graph_begin..end).  nl is checked as the operation itself checks it (BFV: nl = L for every
- * op, multiply included; rescale: CKKS and nl >= 2).  Non-zero on a bad op / nl or a buffer too small (80 bytes hold any). */
+ * op, multiply included; rescale and multiply_plain_rescale: CKKS and nl >= 2).  Non-zero on a bad op / nl or a buffer too small (80 bytes hold any). */
 #define ABC_HIP_ROUTE_MUL_RELIN 0
 #define ABC_HIP_ROUTE_KEYSWITCH 1 /* relinearize, keyswitch */
 #define ABC_HIP_ROUTE_ROTATE 2    /* one Galois element */
@@ -75,6 +75,7 @@ int abc_hip_ctx_reload_env(abc_hip_ctx *ctx);
 #define ABC_HIP_ROUTE_MULTIPLY 4
 #define ABC_HIP_ROUTE_ROTATE_ADD 5 /* one Galois element plus a second ciphertext; in_place: d_out aliases d_in */
 #define ABC_HIP_ROUTE_ROTATE_MAC_PLAIN 7 /* CKKS: addend + plaintext (.) one Galois element; in_place: d_out aliases d_in (6 is unassigned) */
+#define ABC_HIP_ROUTE_MULTIPLY_PLAIN_RESCALE 10 /* CKKS, nl >= 2: the rescale's route plus mulplain=fused / mulplain=separate (8 and 9 are unassigned) */
 int abc_hip_route(abc_hip_ctx *ctx, int op, int nl, size_t count, int in_place, char *buf, size_t cap);
 
 /* ---- device memory (so that FFI callers need no HIP runtime binding) ----
@@ -270,6 +271,17 @@ int abc_hip_sub_plain(abc_hip_ctx *ctx, const uint64_t *d_ct, const uint64_t *d_
  * d_in [count][size][nl][N] -> d_out [count][size][nl-1][N]; d_out must not alias d_in (error otherwise). */
 int abc_hip_rescale(abc_hip_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, int size, int nl, size_t count);
 int abc_hip_mod_switch(abc_hip_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, int size, int nl, size_t count);
+/* CKKS only: Evaluator::multiply_plain and rescale_to_next as one call, the weight step of a linear layer.
+ * d_ct [count][size][nl][N] -> d_out [count][size][nl-1][N], size = 2 or 3; d_plain and plain_stride exactly as
+ * abc_hip_multiply_plain takes them (0: one plaintext for the batch; >= nl * N: one per ciphertext, its first nl limbs read, so
+ * rows encoded at a higher level apply at a lower one).  Bit-identical to abc_hip_multiply_plain into a temporary followed by
+ * abc_hip_rescale.  Where the route allows it (abc_hip_route, ABC_HIP_ROUTE_MULTIPLY_PLAIN_RESCALE: the LDS-resident rescale of
+ * the rings 2^10 .. 2^14) the product is formed in the loads of the two rescale kernels and never reaches memory; otherwise the
+ * product lands in an arena and the rescale runs on it.  Fails with nothing written or enqueued for a BFV context, nl < 2 or a
+ * bad level, a bad stride, a size other than 2 or 3, and d_out overlapping d_ct or d_plain.  count == 0 succeeds and enqueues
+ * nothing.  Capturable, under the "run once eagerly first" rule of abc_hip_graph_begin. */
+int abc_hip_multiply_plain_rescale(abc_hip_ctx *ctx, const uint64_t *d_ct, const uint64_t *d_plain, size_t plain_stride,
+                                   uint64_t *d_out, int size, int nl, size_t count);
 
 /* ---- HIP-graph capture of an operation sequence (a recorded circuit in place of the
  * eager per-call dispatch of SpecialRuntimeVisitor, src/runtime/RuntimeVisitor.cpp:40-159).

@@ -19,6 +19,10 @@ def kernels(path):
             out[name] = []
         elif line.startswith("\t.amdgpu_metadata") or line.startswith("\t.ident"):  # behind the last kernel: the file's own tail
             name = None
+        elif name and line.startswith("\t.p2alignl"):  # the padding behind the file's last kernel opens that tail (".text" before it)
+            if out[name] and out[name][-1] == ".text":
+                out[name].pop()
+            name = None
         text = re.sub(r"(\.L[A-Za-z_]+?)\d+", r"\1", line.split(";")[0]).strip()
         # a ".section .text.<kernel>" line opens the NEXT kernel's section, ahead of its marker: emission order again
         if name and text and "__hip_cuid_" not in text and not text.startswith(".section\t.text"):

@@ -66,11 +66,11 @@ def rotate_add_ab(res, only, rng):
         g.close()
 
 
-def _alternate(g, res, names, fns, routes, B):
+def _alternate(g, res, names, fns, routes, B, reps=10):
     """fns[0], fns[1], fns[0], ...: five runs each.  The first run of fns[0] sizes the arenas and is left out of its minimum."""
     runs = {names[0]: [], names[1]: []}
     for rep in range(10):
-        runs[names[rep & 1]].append(timeit(g, fns[rep & 1]))
+        runs[names[rep & 1]].append(timeit(g, fns[rep & 1], reps))
     for i, (k, ms) in enumerate(runs.items()):
         kept = ms[1:] if i == 0 else ms
         res[k] = {"batch": B, "ms": min(kept), "ms_median": sorted(kept)[len(kept) // 2], "ms_runs": ms, "route": routes[i]}
@@ -133,6 +133,40 @@ def rotate_mac_ab(res, only, rng):
                 g.op("diag_matvec", a.ptr, d.ptr, C.c_size_t(nl * g.n), arr, H, out.ptr, nl, cb)
             _alternate(g, res, names, (separate, fused), (g.route("rotate", nl, B), g.route("rotate_mac_plain", nl, B)), B)
             del a, d, tmp, out
+        g.close()
+
+
+def mulplain_rescale_ab(res, only, rng):
+    """rescale(ct (.) plain), one plaintext for the batch, as abc_hip_multiply_plain into a temporary followed by abc_hip_rescale, against
+    one abc_hip_multiply_plain_rescale.  Alternating in one process, five runs each; a shape stays on the fused route only if its fused
+    median is not above its separate median."""
+    shapes = [  # tag, context, levels, batches
+        ("ckks14", lambda: capi.Context(capi.CKKS, 16384, capi.create_primes(16384, [50, 40, 40, 40, 50])), (4, 3), (512, 32)),
+        ("ckks12", lambda: capi.Context(capi.CKKS, 4096, capi.create_primes(4096, [50, 40, 40, 50])), (3,), (1024,)),
+    ]
+    for tag, make, levels, batches in shapes:
+        if only and only not in "%s_mulplain_rescale" % tag and "mulplain_rescale" not in only:  # no entry of this context can match
+            continue
+        g = make()
+        for nl in levels:
+            for B in batches:
+                names = ["%s_L%d_b%d_mulplain_rescale_%s" % (tag, nl, B, kind) for kind in ("separate", "fused")]
+                if not any(only in k for k in names):
+                    continue
+                cb, zero = C.c_size_t(B), C.c_size_t(0)
+                a, nb = rand_ct(g, rng, B, 2, nl)
+                p, _ = rand_ct(g, rng, 1, 1, nl)  # one plaintext [nl][N], broadcast
+                tmp, out = g.alloc(nb), g.alloc(nb // nl * (nl - 1))
+
+                def separate():
+                    g.op("multiply_plain", a.ptr, p.ptr, zero, tmp.ptr, 2, nl, cb)
+                    g.op("rescale", tmp.ptr, out.ptr, 2, nl, cb)
+
+                def fused():
+                    g.op("multiply_plain_rescale", a.ptr, p.ptr, zero, out.ptr, 2, nl, cb)
+                _alternate(g, res, names, (separate, fused), (g.route("rescale", nl, B), g.route("multiply_plain_rescale", nl, B)), B,
+                           reps=200)  # calls of 0.04 .. 0.7 ms: a run is 8 .. 140 ms of device time
+                del a, p, tmp, out
         g.close()
 
 
@@ -304,6 +338,7 @@ def main():
         g.close()
     rotate_add_ab(res, only, rng)
     rotate_mac_ab(res, only, rng)
+    mulplain_rescale_ab(res, only, rng)
     keyswitch_batch1(res, only, rng)
     os.makedirs("gpurun_out", exist_ok=True)
     json.dump(res, open("gpurun_out/op_bench.json", "w"), indent=1)
