@@ -10,6 +10,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import keyed_spec as ks  # noqa: E402
+from key_material_spec import key_equation  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -218,7 +219,7 @@ def test_key_equation(oracle_mod, capi):
     o = _oracle(oracle_mod, "chain1024")
     g = _context(capi, o)
     g.keygen_keyed(KEY_SEC, KEY_PUB)
-    n, K, L, primes = o.n, o.K, o.L, o.primes
+    n, L, primes = o.n, o.L, o.primes
     sk = g.get_key("sk")
     s = ks.secret(KEY_SEC, n).astype(np.int64)
     for j, q in enumerate(primes):
@@ -227,15 +228,9 @@ def test_key_equation(oracle_mod, capi):
 
     def check(what, key, stream, nkeys, new_key):
         a = ks.key_uniform(KEY_PUB, stream, n, primes, nkeys)
-        e = ks.key_errors(KEY_SEC, stream, n, nkeys).astype(np.int64)
-        for i in range(nkeys):
-            for j, q in enumerate(primes):
-                _same("%s a[%d][%d]" % (what, i, j), key[i][1][j], a[i][j])
-                v = key[i][0][j].astype(object) + a[i][j].astype(object) * sko[j]
-                if new_key is not None and j == i:
-                    v = v - (primes[K - 1] % primes[i]) * new_key[i].astype(object)
-                coeffs = o.intt(j, (v % q).astype(np.uint64))
-                _same("%s -e[%d] limb %d" % (what, i, j), coeffs, ((-e[i]) % q).astype(np.uint64))
+        e = ks.key_errors(KEY_SEC, stream, n, nkeys)
+        assert len(key) == nkeys
+        key_equation(o, key, a, e, sk, new_key, what)  # tests/key_material_spec.py
 
     check("pk", g.get_key("pk")[None], 1, 1, None)
     check("relin", g.get_key("relin"), 2, L, np.stack([(sko[j] * sko[j] % q).astype(np.uint64) for j, q in enumerate(primes)]))
