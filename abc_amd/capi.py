@@ -39,6 +39,7 @@ SYMBOLS = [
     "abc_hip_rotate_add", "abc_hip_apply_galois_add", "abc_hip_rotate_sum",
     "abc_hip_rotate_mac_plain", "abc_hip_apply_galois_mac_plain", "abc_hip_diag_matvec",
     "abc_hip_multiply_plain_rescale",
+    "abc_hip_multiply_sum", "abc_hip_mul_sum_relin",
 ]
 
 
@@ -74,6 +75,9 @@ def lib():
             L.abc_hip_rotate_mac_plain.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t]
             L.abc_hip_apply_galois_mac_plain.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_size_t]
             L.abc_hip_diag_matvec.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int, C.c_size_t]
+        if hasattr(L, "abc_hip_mul_sum_relin"):
+            for f in (L.abc_hip_multiply_sum, L.abc_hip_mul_sum_relin):
+                f.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int, C.c_size_t]
         L.abc_hip_encrypt_keyed.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_size_t]
         L.abc_hip_keygen_keyed.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
         L.abc_hip_keyed_small.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_size_t]
@@ -204,7 +208,7 @@ class Context:
         _chk(lib().abc_hip_ctx_reload_env(self.h))
 
     ROUTE_OPS = {"mul_relin": 0, "keyswitch": 1, "relinearize": 1, "rotate": 2, "rescale": 3, "multiply": 4, "rotate_add": 5,
-                 "rotate_mac_plain": 7, "multiply_plain_rescale": 10}
+                 "rotate_mac_plain": 7, "multiply_plain_rescale": 10, "mul_sum_relin": 12}
 
     def route(self, op, nl, count=1, in_place=False):
         """the kernel sequence such a call takes, as the string of abc_route.hpp's formatter"""
@@ -332,6 +336,46 @@ class Context:
         a4, b4 = self._batch(a, 3), self._batch(b, 3)
         r = self._run("mul_relin", [a4, b4], a4.shape, a4.shape[2], C.c_size_t(a4.shape[0]))
         return r if np.ndim(a) == 4 else r[0]
+
+    @staticmethod
+    def term_pointers(ptrs):
+        """a host array of device pointers, as abc_hip_multiply_sum / abc_hip_mul_sum_relin take their terms"""
+        ptrs = [(p.value if isinstance(p, C.c_void_p) else p) or 0 for p in ptrs]
+        return (C.c_void_p * max(len(ptrs), 1))(*ptrs)
+
+    def _mul_sum(self, name, size, as_, bs, nl, count):
+        if len(as_) != len(bs):
+            raise ValueError("as many left factors as right factors")
+        a4 = [self._batch(a, 3) for a in as_]
+        b4 = [self._batch(b, 3) for b in bs]
+        if a4:
+            count, nl = a4[0].shape[0], a4[0].shape[2]
+        elif nl is None:
+            raise ValueError("an empty sum needs nl (and count)")
+        if any(x.shape != (count, 2, nl, self.n) for x in a4 + b4):
+            raise ValueError("every factor is [count][2][nl][N] at one level")
+        bufs = {}
+        for i, x in enumerate(list(as_) + list(bs)):  # one upload per distinct array: a square or a repeated factor stays one pointer
+            if id(x) not in bufs:
+                bufs[id(x)] = self.upload((a4 + b4)[i])
+        out = self.alloc(max(count * size * nl * self.n * 8, 8))
+        try:
+            pa = self.term_pointers([bufs[id(x)].ptr for x in as_])
+            pb = self.term_pointers([bufs[id(x)].ptr for x in bs])
+            self.op(name, pa, pb, len(a4), out.ptr, nl, C.c_size_t(count))
+            r = self.download(out, (count, size, nl, self.n))
+        finally:
+            for b in list(bufs.values()) + [out]:
+                b.free()
+        return r if not as_ or np.ndim(as_[0]) == 4 else r[0]
+
+    def multiply_sum(self, as_, bs, nl=None, count=1):
+        """sum over k of as_[k] (x) bs[k] at size 3 (abc_hip_multiply_sum); nl / count: the shape of an empty sum"""
+        return self._mul_sum("multiply_sum", 3, as_, bs, nl, count)
+
+    def mul_sum_relin(self, as_, bs, nl=None, count=1):
+        """relinearize(sum over k of as_[k] (x) bs[k]) with one key switch (abc_hip_mul_sum_relin): route("mul_sum_relin") names the sequence"""
+        return self._mul_sum("mul_sum_relin", 2, as_, bs, nl, count)
 
     def rotate(self, ct, steps):
         a4 = self._batch(ct, 3)

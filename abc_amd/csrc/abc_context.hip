@@ -45,6 +45,7 @@ void read_switches(abc_hip_ctx *c) {
   s.no_rotate_add_fusion = env_on("ABC_HIP_NO_ROTATE_ADD_FUSION");
   s.no_rotate_mac_fusion = env_on("ABC_HIP_NO_ROTATE_MAC_FUSION");
   s.no_mulplain_rescale_fusion = env_on("ABC_HIP_NO_MULPLAIN_RESCALE_FUSION");
+  s.no_tensor_sum = env_on("ABC_HIP_NO_TENSOR_SUM");
   s.main_two_per_cu = env_on("ABC_HIP_MAIN_TWO_PER_CU");
   s.host_sampling = env_on("ABC_HIP_HOST_SAMPLING");
   if (const char *e = std::getenv("ABC_HIP_CHUNK")) s.chunk = (size_t)std::atol(e);
@@ -575,6 +576,42 @@ static int relinearize(abc_hip_ctx *c, const u64 *ct3, u64 *out2, int nl, size_t
   return launch_keyswitch(c, route_keyswitch(c->facts, nl), ks_of_ciphertexts(c, ct3, 3, c->d_relin, out2, nl, count));
 }
 
+// out = sum over k of a[k] (x) b[k], size 3 (relin false: out is [count][3][nl][N]) or relinearised (out [count][2][nl][N]).  The
+// caller has checked the level, the pointers, the overlaps and the key.  The batch goes in groups of ciphertexts (mul_sum_group):
+// per group the size-3 sum is formed -- in place in `out`, or in arena 1 where the key switch follows -- by the K-term kernel, or,
+// on the per-term route, product by product through arena 2 and the add kernel; then the group's key switch writes its slice of
+// `out`.  A term that IS `out` (relin only) is therefore read by its own group before that group's slice is written, and by no other.
+static int mul_sum(abc_hip_ctx *c, const std::vector<const u64 *> &a, const std::vector<const u64 *> &b, u64 *out, bool relin, int nl,
+                   size_t count) {
+  if (!count) return 0;
+  const size_t pw = (size_t)nl * c->n, K = a.size();
+  if (!K) {
+    ABC_HIP_CHECK(hipMemsetAsync(out, 0, count * (relin ? 2 : 3) * pw * 8, c->stream));
+    return 0;
+  }
+  const MulSumRoute r = route_mul_sum(c->facts, nl);
+  const size_t group = mul_sum_group(c->facts, nl, count);
+  if (relin && ensure_aux(c, 1, group * 3 * pw * 8)) return 1;
+  if (!r.sum && K > 1 && ensure_aux(c, 2, group * 3 * pw * 8)) return 1;
+  std::vector<const u64 *> ga(K), gb(K);
+  for (size_t off = 0; off < count; off += group) {
+    const size_t cc = count - off < group ? count - off : group;
+    u64 *sum3 = relin ? (u64 *)c->aux[1] : out + off * 3 * pw;
+    for (size_t k = 0; k < K; k++) ga[k] = a[k] + off * 2 * pw, gb[k] = b[k] + off * 2 * pw;
+    if (r.sum) {
+      if (launch_ckks_tensor_sum(c, ga.data(), gb.data(), (int)K, sum3, nl, cc)) return 1;
+    } else {
+      for (size_t k = 0; k < K; k++) {
+        u64 *dst = k ? (u64 *)c->aux[2] : sum3;
+        if (c->scheme == ABC_HIP_SCHEME_CKKS ? launch_ckks_tensor(c, ga[k], gb[k], dst, nl, cc) : bfv_multiply(c, route_bfv_multiply(c->facts), ga[k], gb[k], dst, cc)) return 1;
+        if (k && launch_addsub(c, sum3, dst, sum3, nl, cc * 3, 0)) return 1;
+      }
+    }
+    if (relin && launch_keyswitch(c, r.ks, ks_of_ciphertexts(c, sum3, 3, c->d_relin, out + off * 2 * pw, nl, cc))) return 1;
+  }
+  return 0;
+}
+
 }  // namespace abc
 
 using namespace abc;
@@ -1032,6 +1069,42 @@ int abc_hip_mul_relin(abc_hip_ctx *c, const uint64_t *a, const uint64_t *b, uint
   int rc = (c->scheme == ABC_HIP_SCHEME_CKKS) ? launch_ckks_tensor(c, a, b, t3, nl, count) : bfv_multiply(c, r.mul, a, b, t3, count);
   if (!rc) rc = launch_keyswitch(c, r.ks, ks_of_ciphertexts(c, t3, 3, c->d_relin, out, nl, count));  // as in relinearize
   return rc;
+}
+// what both sum-of-products calls check before anything is written or enqueued; exact_ok: a term may BE d_out (mul_sum_relin)
+static int check_mul_sum(abc_hip_ctx *c, const char *op, const uint64_t *const *h_a, const uint64_t *const *h_b, int n_terms, const uint64_t *out,
+                         int out_size, bool exact_ok, int nl, size_t count) {
+  if (check_level(c, nl)) return 1;
+  if (n_terms < 0 || (n_terms && (!h_a || !h_b))) { set_error(std::string(op) + ": bad term list"); return 1; }
+  const size_t pw = (size_t)nl * c->n;
+  for (int k = 0; k < n_terms; k++) {
+    if (!h_a[k] || !h_b[k]) { set_error(std::string(op) + ": null term pointer"); return 1; }
+    for (const uint64_t *t : {h_a[k], h_b[k]}) {
+      if (exact_ok && t == out) continue;
+      if (count && ranges_overlap(t, count * 2 * pw * 8, out, count * out_size * pw * 8)) {
+        set_error(std::string(op) + (exact_ok ? ": d_out may be a term, but must not overlap one otherwise" : ": d_out3 must not overlap a term"));
+        return 1;
+      }
+    }
+  }
+  if (!out && count) { set_error(std::string(op) + ": null output"); return 1; }
+  return 0;
+}
+int abc_hip_multiply_sum(abc_hip_ctx *c, const uint64_t *const *h_a, const uint64_t *const *h_b, int n_terms, uint64_t *out3, int nl,
+                         size_t count) {
+  CTX_GUARD(c);
+  if (check_mul_sum(c, "multiply_sum", h_a, h_b, n_terms, out3, 3, false, nl, count)) return 1;
+  return guarded([&] {
+    return mul_sum(c, std::vector<const u64 *>(h_a, h_a + n_terms), std::vector<const u64 *>(h_b, h_b + n_terms), out3, false, nl, count);
+  });
+}
+int abc_hip_mul_sum_relin(abc_hip_ctx *c, const uint64_t *const *h_a, const uint64_t *const *h_b, int n_terms, uint64_t *out, int nl,
+                          size_t count) {
+  CTX_GUARD(c);
+  if (check_mul_sum(c, "mul_sum_relin", h_a, h_b, n_terms, out, 2, true, nl, count)) return 1;
+  if (!c->d_relin) { set_error("mul_sum_relin: no relinearisation key"); return 1; }
+  return guarded([&] {
+    return mul_sum(c, std::vector<const u64 *>(h_a, h_a + n_terms), std::vector<const u64 *>(h_b, h_b + n_terms), out, true, nl, count);
+  });
 }
 int abc_hip_rotate(abc_hip_ctx *c, const uint64_t *in, uint64_t *out, int nl, int steps, size_t count) {
   CTX_GUARD(c);

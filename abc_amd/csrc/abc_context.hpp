@@ -305,6 +305,10 @@ int big_block_log(void);
 
 int launch_addsub(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out, int nl, size_t polys, int op);  // 0 add 1 sub 2 neg
 int launch_ckks_tensor(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out3, int nl, size_t count);
+// out3 [count][3][nl][N] = sum over k < n_terms of a[k] (x) b[k] (CKKS; a, b: HOST arrays of device pointers, read during the call):
+// k_ckks_tensor_sum, kTensorSumTerms pointer pairs per launch by value in the kernel arguments; n_terms >= 1
+constexpr int kTensorSumTerms = 8;
+int launch_ckks_tensor_sum(abc_hip_ctx *c, const u64 *const *a, const u64 *const *b, int n_terms, u64 *out3, int nl, size_t count);
 int keyswitch_generic(abc_hip_ctx *c, KsFront front, const KsOperands &o);
 int launch_ks_tmod(abc_hip_ctx *c, const u64 *prodS, u64 *tmod, int nl, size_t polys);
 int launch_ks_finish(abc_hip_ctx *c, const u64 *prodD, const u64 *tmod, u64 *out, const u64 *addend, size_t addend_stride,

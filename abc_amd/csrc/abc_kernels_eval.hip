@@ -78,6 +78,160 @@ int launch_ckks_tensor(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out3, in
   return 0;
 }
 
+// ---- CKKS tensor sum: out3 (+)= sum over the launch's terms of a_k (x) b_k, the front of abc_hip_multiply_sum / mul_sum_relin ----
+// A streaming kernel: one workgroup owns kTensorSumSpan consecutive coefficients of ONE limb of one ciphertext, so the modulus is
+// workgroup-uniform (scalar), every lane moves 16 bytes per load and store, and a term's four loads are issued before the previous
+// term's arithmetic.  The term pointers travel by value (no device-side table, no copy: the call stays capturable); the loop over
+// them is unrolled, so the record is only ever indexed by constants and stays in scalar registers.  A call of more than
+// kTensorSumTerms terms takes several launches; ACC: this launch adds to the canonical (c0, c1, c2) an earlier one left in out3.
+// Results are exact modular sums in canonical form, whatever the order: bit-identical to k_ckks_tensor + k_addsub per term.
+struct TensorSumTerms {
+  const u64 *a[kTensorSumTerms], *b[kTensorSumTerms];
+};
+constexpr int kTensorSumSpan = 512;  // coefficients per workgroup: 256 lanes x u64x2; divides every ring (N >= 2^10)
+// Integer limbs accumulate the 128-bit products lazily and reduce once per launch.  A launch sums at most 2 * kTensorSumTerms
+// products into c1, plus the carried value (below q: less than one product): (2 T + 1) (q - 1)^2 < 2^128 must hold for the widest
+// prime a context accepts, 2^60 (abc_hip_ctx_create) -- 2^(128 - 2 * 60) = 256 products, so T could be 127; the launch boundary is
+// the intermediate reduction.  barrett_reduce itself wants x < 2^(k+63): reduce128 folds the high word first.
+constexpr unsigned kTensorSumPrimeBits = kIsplitBits;  // 60: the widest data prime
+static_assert(2 * kTensorSumTerms + 1 <= (1 << (128 - 2 * kTensorSumPrimeBits)), "tensor sum: the 128-bit accumulator would overflow within one launch");
+// fp64 limbs (q < 2^50): products |.| < q (fp_mulmod) are summed as integer-valued doubles, exact below 2^53 > 8 q.  c1 takes two
+// per term, so every accumulator is re-centred (|.| <= q/2) after kTensorSumFpTerms = 3 terms: the carried value (below q when it
+// is the canonical word of an earlier launch, else <= q/2) plus six products stays below 7 q < 2^53.
+constexpr int kTensorSumFpTerms = 3;
+static_assert((2 * kTensorSumFpTerms + 1) <= 8, "tensor sum: the fp64 accumulator would pass 2^53 between two re-centrings");
+
+// x (any 128-bit value) mod q: hi * 2^64 + lo = reduce64(hi) * r64 + lo (mod q), r64 = 2^64 mod q; the right side is below
+// q^2 + 2^64 < 2^(k+63)
+__device__ __forceinline__ u64 reduce128(const U128 &x, u64 r64, const Mod &m) {
+  U128 t = mul_wide(reduce64(x.hi, m), r64);
+  add128(t, U128{x.lo, 0});
+  return barrett_reduce(t, m);
+}
+
+struct TensorSumLoad {
+  u64x2 a0, a1, b0, b1;
+};
+__device__ __forceinline__ TensorSumLoad tensor_sum_load(const u64 *a, const u64 *b, size_t off, size_t pw) {
+  TensorSumLoad t;
+  t.a0 = *reinterpret_cast<const u64x2 *>(a + off);
+  t.a1 = *reinterpret_cast<const u64x2 *>(a + off + pw);
+  t.b0 = *reinterpret_cast<const u64x2 *>(b + off);
+  t.b1 = *reinterpret_cast<const u64x2 *>(b + off + pw);
+  return t;
+}
+
+// one tile on the integers
+template <bool ACC>
+__device__ __forceinline__ void tensor_sum_int(const TensorSumTerms &t, int nt, const Mod &m, size_t in_off, size_t pw, u64 *po) {
+  U128 c0x{0, 0}, c0y{0, 0}, c1x{0, 0}, c1y{0, 0}, c2x{0, 0}, c2y{0, 0};
+  if constexpr (ACC) {
+    const u64x2 r0 = *reinterpret_cast<const u64x2 *>(po), r1 = *reinterpret_cast<const u64x2 *>(po + pw),
+                r2 = *reinterpret_cast<const u64x2 *>(po + 2 * pw);
+    c0x.lo = r0.x, c0y.lo = r0.y, c1x.lo = r1.x, c1y.lo = r1.y, c2x.lo = r2.x, c2y.lo = r2.y;
+  }
+  TensorSumLoad cur = tensor_sum_load(t.a[0], t.b[0], in_off, pw), nxt = cur;
+#pragma unroll
+  for (int k = 0; k < kTensorSumTerms; k++) {
+    if (k < nt) {  // workgroup-uniform
+      if (k + 1 < kTensorSumTerms && k + 1 < nt) nxt = tensor_sum_load(t.a[k + 1], t.b[k + 1], in_off, pw);
+      mac128(c0x, cur.a0.x, cur.b0.x), mac128(c0y, cur.a0.y, cur.b0.y);
+      mac128(c1x, cur.a0.x, cur.b1.x), mac128(c1y, cur.a0.y, cur.b1.y);
+      mac128(c1x, cur.a1.x, cur.b0.x), mac128(c1y, cur.a1.y, cur.b0.y);
+      mac128(c2x, cur.a1.x, cur.b1.x), mac128(c2y, cur.a1.y, cur.b1.y);
+      cur = nxt;
+    }
+  }
+  const u64 r64 = reduce64(0ull - m.q, m);  // 2^64 mod q
+  *reinterpret_cast<u64x2 *>(po) = u64x2{reduce128(c0x, r64, m), reduce128(c0y, r64, m)};
+  *reinterpret_cast<u64x2 *>(po + pw) = u64x2{reduce128(c1x, r64, m), reduce128(c1y, r64, m)};
+  *reinterpret_cast<u64x2 *>(po + 2 * pw) = u64x2{reduce128(c2x, r64, m), reduce128(c2y, r64, m)};
+}
+
+// one tile in fp64 (q < 2^50)
+template <bool ACC>
+__device__ __forceinline__ void tensor_sum_fp(const TensorSumTerms &t, int nt, const Mod &m, size_t in_off, size_t pw, u64 *po) {
+  const double q = m.qd, qinv = m.qinv;
+  double c0x = 0, c0y = 0, c1x = 0, c1y = 0, c2x = 0, c2y = 0;
+  if constexpr (ACC) {
+    const u64x2 r0 = *reinterpret_cast<const u64x2 *>(po), r1 = *reinterpret_cast<const u64x2 *>(po + pw),
+                r2 = *reinterpret_cast<const u64x2 *>(po + 2 * pw);
+    c0x = fp_from_u64(r0.x), c0y = fp_from_u64(r0.y), c1x = fp_from_u64(r1.x), c1y = fp_from_u64(r1.y);
+    c2x = fp_from_u64(r2.x), c2y = fp_from_u64(r2.y);
+  }
+  TensorSumLoad cur = tensor_sum_load(t.a[0], t.b[0], in_off, pw), nxt = cur;
+#pragma unroll
+  for (int k = 0; k < kTensorSumTerms; k++) {
+    if (k < nt) {  // workgroup-uniform
+      if (k + 1 < kTensorSumTerms && k + 1 < nt) nxt = tensor_sum_load(t.a[k + 1], t.b[k + 1], in_off, pw);
+      const double a0x = fp_from_u64(cur.a0.x), a0y = fp_from_u64(cur.a0.y), a1x = fp_from_u64(cur.a1.x), a1y = fp_from_u64(cur.a1.y);
+      const double b0x = fp_from_u64(cur.b0.x), b0y = fp_from_u64(cur.b0.y), b1x = fp_from_u64(cur.b1.x), b1y = fp_from_u64(cur.b1.y);
+      c0x += fp_mulmod(a0x, b0x, q, qinv), c0y += fp_mulmod(a0y, b0y, q, qinv);
+      c1x += fp_mulmod(a0x, b1x, q, qinv), c1y += fp_mulmod(a0y, b1y, q, qinv);
+      c1x += fp_mulmod(a1x, b0x, q, qinv), c1y += fp_mulmod(a1y, b0y, q, qinv);
+      c2x += fp_mulmod(a1x, b1x, q, qinv), c2y += fp_mulmod(a1y, b1y, q, qinv);
+      // carried value + 2 * kTensorSumFpTerms products < 7 q < 2^53 up to here (see kTensorSumFpTerms); the last group of the
+      // launch is centred by fp_to_canon
+      if ((k + 1) % kTensorSumFpTerms == 0 && k + 1 < kTensorSumTerms) {
+        c0x = fp_centre(c0x, q, qinv), c0y = fp_centre(c0y, q, qinv), c1x = fp_centre(c1x, q, qinv), c1y = fp_centre(c1y, q, qinv);
+        c2x = fp_centre(c2x, q, qinv), c2y = fp_centre(c2y, q, qinv);
+      }
+      cur = nxt;
+    }
+  }
+  *reinterpret_cast<u64x2 *>(po) = u64x2{fp_to_canon(c0x, q, qinv), fp_to_canon(c0y, q, qinv)};
+  *reinterpret_cast<u64x2 *>(po + pw) = u64x2{fp_to_canon(c1x, q, qinv), fp_to_canon(c1y, q, qinv)};
+  *reinterpret_cast<u64x2 *>(po + 2 * pw) = u64x2{fp_to_canon(c2x, q, qinv), fp_to_canon(c2y, q, qinv)};
+}
+
+// tiles = count * nl * (N / kTensorSumSpan), tile -> (ciphertext, limb, span) with scalar arithmetic; fpmask bit j: limb j in fp64.
+// HAS_FP / HAS_INT: which arithmetic the chain's first nl limbs need (both: a mixed chain, a workgroup-uniform branch)
+template <bool HAS_FP, bool HAS_INT, bool ACC>
+__global__ __launch_bounds__(256) void k_ckks_tensor_sum(DevCtx c, TensorSumTerms t, int nt, u64 *out3, int nl, size_t tiles, u32 fpmask) {
+  const u32 spans = (u32)c.n / kTensorSumSpan;
+  const size_t pw = (size_t)nl * c.n;
+  for (size_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const size_t limb = tile / spans;  // ct * nl + j
+    const u32 span = (u32)(tile - limb * spans);
+    const size_t ct = limb / (u32)nl;
+    const int j = (int)(limb - ct * (u32)nl);
+    const size_t w = (size_t)j * c.n + (size_t)span * kTensorSumSpan + 2 * threadIdx.x;  // word inside a polynomial
+    const Mod m = mod_at(c, j);
+    u64 *po = out3 + ct * 3 * pw + w;
+    const size_t in_off = ct * 2 * pw + w;
+    if (HAS_FP && (!HAS_INT || ((fpmask >> j) & 1u))) tensor_sum_fp<ACC>(t, nt, m, in_off, pw, po);
+    else tensor_sum_int<ACC>(t, nt, m, in_off, pw, po);
+  }
+}
+
+// out3 = sum over k < n_terms of a[k] (x) b[k]; n_terms >= 1 (the caller writes the zeros of an empty sum), on stream c->stream
+int launch_ckks_tensor_sum(abc_hip_ctx *c, const u64 *const *a, const u64 *const *b, int n_terms, u64 *out3, int nl, size_t count) {
+  const size_t tiles = count * nl * ((size_t)c->n / kTensorSumSpan);
+  if (!tiles || n_terms < 1) return 0;
+  const u32 full = (1u << nl) - 1u;
+  const u32 fpmask = (c->use_fp && (c->facts.data_fp(nl) || !c->sw.no_mixed)) ? c->facts.fp_data_mask(nl) : 0u;
+  const size_t cap = 256 * 8 * 16;  // workgroups: every CU several times over, the tile loop beyond
+  const dim3 grid((unsigned)(tiles < cap ? tiles : cap));
+  for (int k0 = 0; k0 < n_terms; k0 += kTensorSumTerms) {
+    const int nt = n_terms - k0 < kTensorSumTerms ? n_terms - k0 : kTensorSumTerms;
+    TensorSumTerms t;
+    for (int k = 0; k < kTensorSumTerms; k++) t.a[k] = a[k0 + (k < nt ? k : 0)], t.b[k] = b[k0 + (k < nt ? k : 0)];
+    auto go = [&](auto has_fp, auto has_int, auto acc) {
+      hipLaunchKernelGGL((k_ckks_tensor_sum<decltype(has_fp)::value, decltype(has_int)::value, decltype(acc)::value>), grid, dim3(256), 0,
+                         c->stream, c->dc, t, nt, out3, nl, tiles, fpmask);
+    };
+    auto by_acc = [&](auto has_fp, auto has_int) {
+      if (k0) go(has_fp, has_int, std::true_type{});
+      else go(has_fp, has_int, std::false_type{});
+    };
+    if (fpmask == full) by_acc(std::true_type{}, std::false_type{});
+    else if (!fpmask) by_acc(std::false_type{}, std::true_type{});
+    else by_acc(std::true_type{}, std::true_type{});
+    ABC_HIP_CHECK(hipGetLastError());
+  }
+  return 0;
+}
+
 // ---- key switching, generic path ----
 // dec[ct][J][I][k] = tcoef[ct][J][k] mod q_{ki(I)}
 __global__ __launch_bounds__(256) void k_ks_expand(DevCtx c, const u64 *tcoef, size_t tstride, u64 *dec, int nl, size_t count) {

@@ -24,6 +24,7 @@ struct Switches {
   bool no_rotate_add_fusion = false;  // ABC_HIP_NO_ROTATE_ADD_FUSION: rotate_add as a rotation into an arena, then the add kernel
   bool no_rotate_mac_fusion = false;  // ABC_HIP_NO_ROTATE_MAC_FUSION: rotate_mac_plain as a rotation into an arena, multiply_plain on it, then the add kernel
   bool no_mulplain_rescale_fusion = false;  // ABC_HIP_NO_MULPLAIN_RESCALE_FUSION: multiply_plain_rescale as multiply_plain into an arena, then rescale
+  bool no_tensor_sum = false;  // ABC_HIP_NO_TENSOR_SUM: multiply_sum / mul_sum_relin form every product on its own (tensor into an arena, then the add kernel)
   bool main_two_per_cu = false;  // ABC_HIP_MAIN_TWO_PER_CU: k_split4_main_fp in its one-piece pair phase at nl <= 4 (same step, same route: a form of the kernel)
   bool host_sampling = false;  // ABC_HIP_HOST_SAMPLING: the keyed entries (the OS-keyed ones call them) draw with the host twin of the keyed spec (no route depends on it)
   size_t chunk = 0, few_limbs = 48, lean_limit = 96, bfv_scratch_mb = 0, pass0_target_limit = 128;
@@ -113,6 +114,11 @@ struct RescaleRoute {
 struct MulPlainRescaleRoute {
   RescaleRoute rescale;  // the rescale, out of place
   bool fused;            // the plaintext product is formed in that rescale's loads; otherwise multiply_plain into an arena, then the rescale on it
+};
+// relinearize(sum of K ciphertext products): the size-3 sum lands in an arena, then the key switch of the level
+struct MulSumRoute {
+  KsRoute ks;
+  bool sum;  // CKKS: one K-term tensor-sum kernel (k_ckks_tensor_sum); otherwise each product by the multiply of the scheme into a second arena, then the add kernel
 };
 
 namespace route_detail {
@@ -247,6 +253,12 @@ inline MulPlainRescaleRoute route_mulplain_rescale(const RouteFacts &f, int nl) 
   return {r, r.kind != Rescale::generic && !f.sw.no_mulplain_rescale_fusion};
 }
 
+// sum of products at level nl, then one relinearisation.  BFV's product is BEHZ: the sum has to be taken behind its floor to stay
+// bit-identical to multiply + add, so it goes term by term
+inline MulSumRoute route_mul_sum(const RouteFacts &f, int nl) {
+  return {route_keyswitch(f, nl), f.scheme == 2 && !f.sw.no_tensor_sum};
+}
+
 // ---- per chunk ----
 struct ChunkPlan {
   size_t chunk;
@@ -267,6 +279,18 @@ inline ChunkPlan plan_chunks(const RouteFacts &f, int nl, size_t count) {
   }
   if (p.chunk > count) p.chunk = count;
   return p;
+}
+// mul_sum_relin's size-3 sum lives in an arena, so the batch goes in groups of ciphertexts: a multiple of chunk * lanes (the key
+// switch inside a group chunks as a whole call of that many would), as many of them as keep the arena within the 4 GiB of
+// plan_chunks' cap; with ABC_HIP_CHUNK set, exactly chunk * lanes
+inline size_t mul_sum_group(const RouteFacts &f, int nl, size_t count) {
+  const ChunkPlan p = plan_chunks(f, nl, count);
+  const size_t unit = p.chunk * (size_t)p.lanes;
+  if (f.sw.chunk || unit >= count) return unit < count ? unit : count;
+  const size_t per_ct_bytes = 3 * (size_t)nl * ((size_t)1 << f.logn) * 8;
+  const size_t units = ((size_t)4 << 30) / per_ct_bytes / unit;
+  const size_t group = unit * (units ? units : 1);
+  return group < count ? group : count;
 }
 // the choices that depend on the cc ciphertexts of one chunk (a ragged last chunk may differ from the others); fields a
 // sequence does not read stay false / 0
@@ -332,7 +356,7 @@ inline void format_ks(char *buf, size_t cap, const RouteFacts &f, const KsRoute 
 }
 // The route of one call into buf: what abc_hip_route returns.  op: include/abc_hip.h, ABC_HIP_ROUTE_*.  Returns the length,
 // -1 if cap is too small, -2 for an unknown op.
-enum RouteOp { kRouteMulRelin = 0, kRouteKeyswitch = 1, kRouteRotate = 2, kRouteRescale = 3, kRouteMultiply = 4, kRouteRotateAdd = 5, kRouteRotateMacPlain = 7, kRouteMulPlainRescale = 10 };  // 6, 8 and 9 stay unassigned: the host tests probe them as unknown operations
+enum RouteOp { kRouteMulRelin = 0, kRouteKeyswitch = 1, kRouteRotate = 2, kRouteRescale = 3, kRouteMultiply = 4, kRouteRotateAdd = 5, kRouteRotateMacPlain = 7, kRouteMulPlainRescale = 10, kRouteMulSumRelin = 12 };  // 6, 8, 9 and 11 stay unassigned: the host tests probe them as unknown operations
 inline int format_op(char *buf, size_t cap, const RouteFacts &f, int op, int nl, size_t count, bool in_place) {
   char ks[80];
   int n = -2;
@@ -363,6 +387,10 @@ inline int format_op(char *buf, size_t cap, const RouteFacts &f, int op, int nl,
     const char *how = r.fused ? "fused" : "separate";
     n = r.rescale.kind == Rescale::mixed ? snprintf(buf, cap, "mixed fpmask=0x%x mulplain=%s", (unsigned)r.rescale.fpmask, how)
                                          : snprintf(buf, cap, "%s mulplain=%s", name(r.rescale.kind), how);
+  } else if (op == kRouteMulSumRelin) {
+    const MulSumRoute r = route_mul_sum(f, nl);
+    format_ks(ks, sizeof ks, f, r.ks, nl, mul_sum_group(f, nl, count));  // per-chunk fields: those of the first group's first chunk
+    n = snprintf(buf, cap, "%s tensor=%s", ks, r.sum ? "sum" : "per_term");
   } else if (op == kRouteMultiply) {
     n = snprintf(buf, cap, "%s", f.scheme == 1 ? name(route_bfv_multiply(f)) : "tensor");
   }

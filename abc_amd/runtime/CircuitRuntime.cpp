@@ -4,6 +4,7 @@
 #include <iostream>
 
 #include "GraphCapable.hpp"
+#include "MulSumCapable.hpp"
 #include "RotateAddCapable.hpp"
 
 namespace {
@@ -274,8 +275,45 @@ size_t CircuitRuntime::plainRotateCall(size_t at, std::string &id, int &steps) c
   return 6 + neg;
 }
 
+// A run `x *** y +++ u *** v (+++ ...)` at the current token: two or more products, joined by + / +++, each of exactly two declared
+// secret variables with nothing that binds tighter behind it (a third factor, an index, a call).  -> the tokens the run spans and
+// its factors, else 0.  A product that does not qualify ends the run in front of its `+`; everything else is multiplicative()'s.
+size_t CircuitRuntime::productRun(std::vector<std::pair<std::string, std::string>> &terms) const {
+  auto punct = [&](size_t k, const char *p) { return peek(k).kind == Token::Punct && peek(k).text == p; };
+  auto secretVar = [&](size_t k) {
+    if (peek(k).kind != Token::Ident) return false;
+    auto it = vars.find(peek(k).text);
+    return it != vars.end() && it->second.secret && it->second.ctxt;
+  };
+  size_t at = 0, span = 0;
+  for (;;) {
+    if (!(secretVar(at) && (punct(at + 1, "***") || punct(at + 1, "*")) && secretVar(at + 2))) break;
+    bool tighter = false;
+    for (const char *p : {"*", "***", "/", "%", "[", "("}) tighter = tighter || punct(at + 3, p);
+    if (tighter) break;
+    terms.emplace_back(peek(at).text, peek(at + 2).text);
+    span = at + 3;
+    if (!(punct(at + 3, "+") || punct(at + 3, "+++"))) break;
+    at += 4;
+  }
+  if (terms.size() < 2) { terms.clear(); return 0; }
+  return span;
+}
+
 std::unique_ptr<AbstractValue> CircuitRuntime::additive() {
-  auto lhs = multiplicative();
+  std::unique_ptr<AbstractValue> lhs;
+  {  // a sum of products on a backend that relinearises lazily: one MulSumCapable call for the whole run
+    std::vector<std::pair<std::string, std::string>> names;
+    const size_t span = productRun(names);
+    auto lazy = span ? dynamic_cast<const MulSumCapable *>(vars.find(names[0].first)->second.ctxt.get()) : nullptr;
+    if (lazy && lazy->lazyRelinearize()) {
+      MulSumCapable::Terms terms;
+      for (const auto &n : names) terms.emplace_back(vars.find(n.first)->second.ctxt.get(), vars.find(n.second)->second.ctxt.get());
+      pos += span;
+      lhs = lazy->mulSum(terms);
+    }
+  }
+  if (!lhs) lhs = multiplicative();
   while (peek().kind == Token::Punct && (peek().text == "+" || peek().text == "-" || peek().text == "+++" || peek().text == "---")) {
     const std::string op = next().text;
     // lhs + rotate(v, k) on a ciphertext that offers RotateAddCapable: one fused operation instead of rotateRows + add_inplace

@@ -244,6 +244,36 @@ void HipCiphertext::addRotatedInplace(const AbstractCiphertext &src, int steps) 
   adopt(std::move(t));
 }
 
+bool HipCiphertext::lazyRelinearize() const { return getFactory().lazyRelinearizes(); }
+
+std::unique_ptr<AbstractCiphertext> HipCiphertext::mulSum(const Terms &terms) const {
+  const auto &f = getFactory();
+  bool one_level = !terms.empty();
+  for (const auto &t : terms) one_level = one_level && cast(*t.first).nl == nl && cast(*t.second).nl == nl;
+  if (!one_level || !f.lazyRelinearizes()) {  // the calls per term: they also bring operands at different levels together
+    if (terms.empty()) throw std::runtime_error("mulSum: no terms");
+    auto r = terms[0].first->multiply(*terms[0].second);
+    for (size_t k = 1; k < terms.size(); ++k) r->addInplace(*terms[k].first->multiply(*terms[k].second));
+    return r;
+  }
+  const double scale = f.isCkks() ? cast(*terms[0].first).sc * cast(*terms[0].second).sc : 1.0;
+  std::vector<const uint64_t *> a, b;
+  for (const auto &t : terms) {
+    if (f.isCkks()) checkScales(scale, cast(*t.first).sc * cast(*t.second).sc);
+    a.push_back(cast(*t.first).in());
+    b.push_back(cast(*t.second).in());
+  }
+  auto r = fresh(nl);
+  abcHipCheck(abc_hip_mul_sum_relin(f.context(), a.data(), b.data(), (int)terms.size(), r->buf->p, nl, f.batchSize()), "mul_sum_relin");
+  f.countMulSum();
+  if (f.isCkks()) {
+    r->sc = scale;
+    r->checkScaleFits(r->sc, r->nl);
+    r->rescaleIfPossible();
+  }
+  return r;
+}
+
 // ---- ctxt-plain ----
 std::unique_ptr<AbstractCiphertext> HipCiphertext::addPlain(const ICleartext &operand) const {
   auto r = clone_impl();

@@ -12,9 +12,10 @@
 #include "plugin_api.hpp"
 
 #include "HipCiphertextFactory.hpp"
+#include "MulSumCapable.hpp"
 #include "RotateAddCapable.hpp"
 
-class HipCiphertext : public AbstractCiphertext, public RotateAddCapable {
+class HipCiphertext : public AbstractCiphertext, public RotateAddCapable, public MulSumCapable {
   // Device buffer [B][2][L][N] (B = the factory's batch size, 1 by default), shared copy-on-write: clone() and the
   // copy constructor only take another reference (the interpreter clones on EVERY variable read,
   // src/runtime/RuntimeVisitor.cpp:431-437, and most clones are only ever read), and an in-place operation on a shared
@@ -91,6 +92,11 @@ class HipCiphertext : public AbstractCiphertext, public RotateAddCapable {
   // are checked as addInplace checks them; operands at different levels, and a factory with fuseRotateAdd off, take rotateRows +
   // addInplace.
   void addRotatedInplace(const AbstractCiphertext &src, int steps) override;
+  // MulSumCapable: the sum of the products as one abc_hip_mul_sum_relin over the operands' buffers into a fresh one (CKKS: then the
+  // rescale a product gets).  Every term must sit at this value's level and, under CKKS, have the first product's scale
+  // (checkScales); terms at different levels take multiply + addInplace per term, which bring them together.
+  bool lazyRelinearize() const override;
+  std::unique_ptr<AbstractCiphertext> mulSum(const Terms &terms) const override;
   std::unique_ptr<AbstractCiphertext> clone() const override;
 
   void add_inplace(const AbstractValue &other) override;

@@ -37,6 +37,10 @@ struct HipSchemeConfig {
   // CKKS `ct * weights` as one abc_hip_multiply_plain_rescale (HipCiphertext::multiplyPlainInplace at two limbs or more); off:
   // abc_hip_multiply_plain, then abc_hip_rescale.  The words are the same either way, so it stays on; off is for A/B runs and tests
   bool fuseMultiplyPlainRescale = true;
+  // `x *** y +++ u *** v (+++ ...)` as ONE abc_hip_mul_sum_relin (HipCiphertext::mulSum; CircuitRuntime recognises the run): the sum
+  // of the size-3 products is relinearised once.  OFF by default: the result decrypts to the same values, with one key switch's
+  // noise instead of one per product, but its words are not those of the per-product sequence
+  bool lazyRelinearize = false;
 };
 
 class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapable {
@@ -72,6 +76,8 @@ class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapab
   mutable size_t fusedRotateAdds = 0;  // abc_hip_rotate_add calls issued by addRotatedInplace
   bool fuseMultiplyPlainRescale = true;
   mutable size_t fusedMultiplyPlainRescales = 0;  // abc_hip_multiply_plain_rescale calls issued by multiplyPlainInplace
+  bool lazyRelin = false;
+  mutable size_t lazyMulSums = 0;  // abc_hip_mul_sum_relin calls issued by HipCiphertext::mulSum
   struct CachedCkksPlain {
     std::vector<double> values;
     int level;
@@ -111,6 +117,10 @@ class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapab
   void setFuseMultiplyPlainRescale(bool on) { fuseMultiplyPlainRescale = on; }
   [[nodiscard]] size_t fusedMultiplyPlainRescaleCalls() const { return fusedMultiplyPlainRescales; }
   void countFusedMultiplyPlainRescale() const { ++fusedMultiplyPlainRescales; }
+  [[nodiscard]] bool lazyRelinearizes() const { return lazyRelin; }
+  void setLazyRelinearize(bool on) { lazyRelin = on; }
+  [[nodiscard]] size_t mulSumCalls() const { return lazyMulSums; }
+  void countMulSum() const { ++lazyMulSums; }
   [[nodiscard]] double defaultScale() const { return ckksScale; }
   // CKKS: largest relative difference between the scales of two addends that is drift, not a mismatch
   [[nodiscard]] double scaleTolerance() const { return ckksScaleTol; }

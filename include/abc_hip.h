@@ -76,6 +76,7 @@ int abc_hip_ctx_reload_env(abc_hip_ctx *ctx);
 #define ABC_HIP_ROUTE_ROTATE_ADD 5 /* one Galois element plus a second ciphertext; in_place: d_out aliases d_in */
 #define ABC_HIP_ROUTE_ROTATE_MAC_PLAIN 7 /* CKKS: addend + plaintext (.) one Galois element; in_place: d_out aliases d_in (6 is unassigned) */
 #define ABC_HIP_ROUTE_MULTIPLY_PLAIN_RESCALE 10 /* CKKS, nl >= 2: the rescale's route plus mulplain=fused / mulplain=separate (8 and 9 are unassigned) */
+#define ABC_HIP_ROUTE_MUL_SUM_RELIN 12 /* relinearize(sum of products): the key switch's route plus tensor=sum / tensor=per_term; per-chunk fields: the first group's (11 is unassigned) */
 int abc_hip_route(abc_hip_ctx *ctx, int op, int nl, size_t count, int in_place, char *buf, size_t cap);
 
 /* ---- device memory (so that FFI callers need no HIP runtime binding) ----
@@ -183,6 +184,27 @@ int abc_hip_multiply(abc_hip_ctx *ctx, const uint64_t *d_a, const uint64_t *d_b,
 int abc_hip_relinearize(abc_hip_ctx *ctx, const uint64_t *d_ct3, uint64_t *d_out2, int nl, size_t count);
 /* SealCiphertext::multiply / multiplyInplace = multiply + relinearize (:102-107,:121-124) -- THE hot path */
 int abc_hip_mul_relin(abc_hip_ctx *ctx, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, int nl, size_t count);
+/* A sum of ciphertext products with ONE relinearisation (lazy relinearisation): replaces n_terms x Evaluator::multiply (:104,:122),
+ * n_terms - 1 x Evaluator::add (:92,:114) on the size-3 products, and -- abc_hip_mul_sum_relin -- one Evaluator::relinearize_inplace
+ * (:105,:123) in place of one per product.
+ *   abc_hip_multiply_sum:   d_out3 [count][3][nl][N] = a_0 (x) b_0 + ... + a_{K-1} (x) b_{K-1}, no relinearisation;
+ *   abc_hip_mul_sum_relin:  d_out  [count][2][nl][N] = relinearize(that sum).
+ * h_a, h_b: HOST arrays of n_terms device pointers, each [count][2][nl][N]; read during the call only.  h_a[k] == h_b[k] (a square)
+ * and one pointer in several terms are fine.  Both calls are bit-identical to abc_hip_multiply per term, abc_hip_add at size 3 and
+ * (the second) abc_hip_relinearize; n_terms == 1 gives the words of abc_hip_multiply / abc_hip_mul_relin.  The result of the second
+ * call decrypts to what the sum of n_terms abc_hip_mul_relin results decrypts to, with one key switch's noise instead of n_terms;
+ * its WORDS differ from that sum.  CKKS forms the size-3 sum with one K-term kernel (abc_hip_route,
+ * ABC_HIP_ROUTE_MUL_SUM_RELIN: tensor=sum; the term pointers travel in the kernel's arguments, eight per launch); BFV, whose
+ * product rounds (BEHZ), and ABC_HIP_NO_TENSOR_SUM=1 form each product on its own in a second arena and add (tensor=per_term).
+ * abc_hip_mul_sum_relin keeps the sum in a context arena and walks the batch in groups of ciphertexts (a multiple of the key
+ * switch's chunk * lanes, the arena capped at 4 GiB; with ABC_HIP_CHUNK=c exactly c * lanes), so d_out may BE one of the terms.
+ * n_terms == 0 writes zeros; count == 0 succeeds and enqueues nothing.  Fails with nothing written or enqueued for: n_terms < 0, a
+ * null term pointer, a bad level (BFV: nl = L), no relinearisation key (second call), d_out3 overlapping a term, d_out overlapping
+ * a term without being exactly that term's pointer.  Capturable, under the "run once eagerly first" rule of abc_hip_graph_begin. */
+int abc_hip_multiply_sum(abc_hip_ctx *ctx, const uint64_t *const *h_a, const uint64_t *const *h_b, int n_terms, uint64_t *d_out3,
+                         int nl, size_t count);
+int abc_hip_mul_sum_relin(abc_hip_ctx *ctx, const uint64_t *const *h_a, const uint64_t *const *h_b, int n_terms, uint64_t *d_out,
+                          int nl, size_t count);
 /* Evaluator::rotate_rows(_inplace) (:55,:60), incl. SEAL's NAF decomposition for steps without a key */
 int abc_hip_rotate(abc_hip_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, int nl, int steps, size_t count);
 /* Evaluator::apply_galois for one element */

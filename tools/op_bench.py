@@ -170,6 +170,72 @@ def mulplain_rescale_ab(res, only, rng):
         g.close()
 
 
+def mul_sum_ab(res, only, rng):
+    """relinearize(sum of K ciphertext products), three ways, alternating in one process, five runs each:
+    (a) `eager`: K x abc_hip_mul_relin and K - 1 x abc_hip_add -- what a caller had before the call existed;
+    (b) `per_term`: abc_hip_mul_sum_relin under ABC_HIP_NO_TENSOR_SUM=1 (tensor per term, add kernel, one key switch);
+    (c) `sum`: abc_hip_mul_sum_relin, the K-term tensor-sum kernel and one key switch (CKKS; BFV has (a) and (b) only).
+    The 2 K operands are distinct buffers (device copies of one random batch: the kernels have no data-dependent path)."""
+    shapes = [  # tag, context, levels (None: L), batches
+        ("ckks14", lambda: capi.Context(capi.CKKS, 16384, capi.create_primes(16384, [50, 40, 40, 40, 50])), (3, 4), (512, 32)),
+        ("ckks15", lambda: capi.Context(capi.CKKS, 32768, capi.create_primes(32768, [50, 40, 40, 50])), (3,), (256,)),
+        ("ckks12", lambda: capi.Context(capi.CKKS, 4096, capi.create_primes(4096, [50, 40, 40, 50])), (3,), (1024,)),
+        ("bfv16384", lambda: capi.Context.bfv_default(16384), (None,), (64,)),
+    ]
+    switch = "ABC_HIP_NO_TENSOR_SUM"
+    for tag, make, levels, batches in shapes:
+        if only and only not in "%s_mul_sum" % tag and "mul_sum" not in only:
+            continue
+        g = make()
+        g.keygen(1)
+        ckks = g.scheme == capi.CKKS
+        kinds = ("eager", "per_term", "sum") if ckks else ("eager", "per_term")
+        for level in levels:
+            nl = level or g.L
+            for B in batches:
+                cb = C.c_size_t(B)
+                first, nb = rand_ct(g, rng, B, 2, nl)
+                pool = [first]
+                for _ in range(2 * 16 - 1):
+                    pool.append(g.alloc(nb))
+                    g.op("memcpy_d2d", pool[-1].ptr, first.ptr, C.c_size_t(nb))
+                tmp, out = g.alloc(nb), g.alloc(nb)
+                for K in (2, 4, 8, 16):
+                    names = ["%s_L%d_b%d_mul_sum_K%d_%s" % (tag, nl, B, K, kind) for kind in kinds]
+                    if not any(only in k for k in names):
+                        continue
+                    pa, pb = g.term_pointers([x.ptr for x in pool[:K]]), g.term_pointers([x.ptr for x in pool[16:16 + K]])
+
+                    def eager():
+                        g.op("mul_relin", pool[0].ptr, pool[16].ptr, out.ptr, nl, cb)
+                        for k in range(1, K):
+                            g.op("mul_relin", pool[k].ptr, pool[16 + k].ptr, tmp.ptr, nl, cb)
+                            g.op("add", out.ptr, tmp.ptr, out.ptr, 2, nl, cb)
+
+                    def one_call():
+                        g.op("mul_sum_relin", pa, pb, K, out.ptr, nl, cb)
+                    runs, routes = {k: [] for k in names}, {}
+                    reps = 10 if B * K >= 256 else 50
+                    for rep in range(5):
+                        for kind, name in zip(kinds, names):
+                            if kind == "per_term":
+                                os.environ[switch] = "1"
+                            else:
+                                os.environ.pop(switch, None)
+                            g.reload_env()
+                            routes[name] = g.route("mul_relin" if kind == "eager" else "mul_sum_relin", nl, B)
+                            runs[name].append(timeit(g, eager if kind == "eager" else one_call, reps))
+                    os.environ.pop(switch, None)
+                    g.reload_env()
+                    for k, ms in runs.items():
+                        kept = ms[1:]  # the first run of each sizes its arenas
+                        res[k] = {"batch": B, "terms": K, "ms": min(kept), "ms_median": sorted(kept)[len(kept) // 2], "ms_runs": ms,
+                                  "us_per_ct": min(kept) * 1e3 / B, "route": routes[k]}
+                        print("%-44s %s ms / %d  (%s)" % (k, " ".join("%8.3f" % v for v in ms), B, routes[k]), flush=True)
+                del pool, first, tmp, out
+        g.close()
+
+
 def keyswitch_batch1(res, only, rng):
     """one ciphertext per call at nl = 4: relinearise, rotate, rotate_add and rotate_mac_plain (one plaintext, one addend) on the two
     CKKS split rings -- the calls in which the host side of the key switch (routes, operand record, launches) is the largest share"""
@@ -196,11 +262,8 @@ def keyswitch_batch1(res, only, rng):
         g.close()
 
 
-def main():
-    # --only SUBSTRING: the entries whose name contains it (the contexts are still created)
-    only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else ""
-    res = {}
-    rng = np.random.default_rng(0)
+def single_ops(res, only, rng):
+    """the single operations: every context of this part is created whatever --only says"""
     # ---- CKKS N=2^14, 4 limbs ----
     n, B = 16384, 512
     g = capi.Context(capi.CKKS, n, capi.create_primes(n, [50, 40, 40, 40, 50]))
@@ -336,9 +399,19 @@ def main():
         print("%-40s %8.3f ms (batch 1, HIP graph replay)" % ("bfv%d_mul_relin latency" % n, ms), flush=True)
         del a, b, out, dec, plains
         g.close()
+
+
+def main():
+    # --only SUBSTRING: the entries whose name contains it (the contexts of single_ops are still created)
+    only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else ""
+    res = {}
+    rng = np.random.default_rng(0)
+    if not (only and "mul_sum" in only):  # that A/B has its own contexts and 2 x 16 operand batches: nothing else is set up
+        single_ops(res, only, rng)
     rotate_add_ab(res, only, rng)
     rotate_mac_ab(res, only, rng)
     mulplain_rescale_ab(res, only, rng)
+    mul_sum_ab(res, only, rng)
     keyswitch_batch1(res, only, rng)
     os.makedirs("gpurun_out", exist_ok=True)
     json.dump(res, open("gpurun_out/op_bench.json", "w"), indent=1)
