@@ -40,6 +40,7 @@ SYMBOLS = [
     "abc_hip_rotate_mac_plain", "abc_hip_apply_galois_mac_plain", "abc_hip_diag_matvec",
     "abc_hip_multiply_plain_rescale",
     "abc_hip_multiply_sum", "abc_hip_mul_sum_relin",
+    "abc_hip_multiply_plain_sum", "abc_hip_rotate_plain", "abc_hip_diag_matvec_bsgs",
 ]
 
 
@@ -78,7 +79,13 @@ def lib():
         if hasattr(L, "abc_hip_mul_sum_relin"):
             for f in (L.abc_hip_multiply_sum, L.abc_hip_mul_sum_relin):
                 f.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int, C.c_size_t]
-        L.abc_hip_encrypt_keyed.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_size_t]
+        if hasattr(L, "abc_hip_multiply_plain_sum"):
+            L.abc_hip_multiply_plain_sum.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_size_t, C.c_int, C.c_void_p,
+                                                     C.c_void_p, C.c_int, C.c_int, C.c_size_t]
+            L.abc_hip_rotate_plain.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t]
+            L.abc_hip_diag_matvec_bsgs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int),
+                                                   C.c_int, C.c_void_p, C.c_int, C.c_size_t]
+        L.abc_hip_encrypt_keyed.argtypes =[C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_size_t]
         L.abc_hip_keygen_keyed.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
         L.abc_hip_keyed_small.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_size_t]
         L.abc_hip_keyed_uniform.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_void_p]
@@ -208,7 +215,7 @@ class Context:
         _chk(lib().abc_hip_ctx_reload_env(self.h))
 
     ROUTE_OPS = {"mul_relin": 0, "keyswitch": 1, "relinearize": 1, "rotate": 2, "rescale": 3, "multiply": 4, "rotate_add": 5,
-                 "rotate_mac_plain": 7, "multiply_plain_rescale": 10, "mul_sum_relin": 12}
+                 "rotate_mac_plain": 7, "multiply_plain_rescale": 10, "mul_sum_relin": 12, "diag_matvec_bsgs": 13}
 
     def route(self, op, nl, count=1, in_place=False):
         """the kernel sequence such a call takes, as the string of abc_route.hpp's formatter"""
@@ -469,6 +476,78 @@ class Context:
         try:
             stride = diags.shape[1] * self.n
             self.op("diag_matvec", cb.ptr, db.ptr, C.c_size_t(stride), arr, len(steps), out.ptr, a4.shape[2], C.c_size_t(a4.shape[0]))
+            r = self.download(out, a4.shape)
+        finally:
+            for b in (cb, db, out):
+                b.free()
+        return r if np.ndim(ct) == 4 else r[0]
+
+    def multiply_plain_sum(self, cts, plains, addend=None, size=2, nl=None, count=1):
+        """(addend or 0) + sum over k of plains[k] (.) cts[k] as one call (abc_hip_multiply_plain_sum), CKKS.  cts[k]: [count][size][nl][N]
+        (or one ciphertext); plains: all [nl][N], one per term for the batch, or all [count][rows >= nl][N], one per ciphertext.
+        size / nl / count: the shape of an empty sum without an addend"""
+        if len(cts) != len(plains):
+            raise ValueError("as many plaintexts as ciphertexts")
+        c4 = [self._batch(x, 3) for x in cts]
+        p = [np.ascontiguousarray(x, dtype=np.uint64) for x in plains]
+        a4 = None if addend is None else self._batch(addend, 3)
+        shape = c4[0].shape if c4 else a4.shape if a4 is not None else (count, size, nl, self.n)
+        if shape[2] is None:
+            raise ValueError("an empty sum without an addend needs nl (and size, count)")
+        if any(x.shape != shape for x in c4 + ([a4] if a4 is not None else [])):
+            raise ValueError("every ciphertext is [count][size][nl][N] at one level")
+        if any(x.ndim != p[0].ndim or x.shape != p[0].shape for x in p):
+            raise ValueError("every plaintext has one form")
+        stride = 0 if not p or p[0].ndim == 2 else p[0].shape[1] * self.n
+        bufs = {}
+        for orig, arr in zip(list(cts) + list(plains), c4 + p):  # one upload per distinct array: a repeated operand stays one pointer
+            if id(orig) not in bufs:
+                bufs[id(orig)] = self.upload(arr)
+        ab = self.upload(a4) if a4 is not None else None
+        out = self.alloc(max(int(np.prod(shape)) * 8, 8))
+        try:
+            pc = self.term_pointers([bufs[id(x)].ptr for x in cts])
+            pp = self.term_pointers([bufs[id(x)].ptr for x in plains])
+            self.op("multiply_plain_sum", pc, pp, C.c_size_t(stride), len(c4), ab.ptr if ab else None, out.ptr, shape[1], shape[2],
+                    C.c_size_t(shape[0]))
+            r = self.download(out, shape)
+        finally:
+            for b in list(bufs.values()) + [out] + ([ab] if ab else []):
+                b.free()
+        one = (cts and np.ndim(cts[0]) == 3) or (not cts and addend is not None and np.ndim(addend) == 3)
+        return r[0] if one else r
+
+    def rotate_plain(self, plain, steps):
+        """the slot rotation of CKKS plaintexts [rows][nl][N] (or [nl][N]) in NTT form (abc_hip_rotate_plain): no key, any sign of steps"""
+        p = np.ascontiguousarray(plain, dtype=np.uint64)
+        p3 = p if p.ndim == 3 else p[None]
+        r = self._run("rotate_plain", [p3], p3.shape, p3.shape[1], int(steps), C.c_size_t(p3.shape[0]))
+        return r if p.ndim == 3 else r[0]
+
+    def bsgs_diagonals(self, diags, baby, giant):
+        """the rows abc_hip_diag_matvec_bsgs takes, from plain diagonals: diags[j * len(baby) + i] is the encoded diagonal of step
+        giant[j] + baby[i], [rows][N] each; row (j, i) of the result is rotate_plain(that, -giant[j])"""
+        d = np.ascontiguousarray(diags, dtype=np.uint64)
+        d = d.reshape(len(giant), len(baby), -1, self.n)
+        out = np.empty_like(d)
+        for j, g in enumerate(giant):
+            if len(baby):
+                out[j] = self.rotate_plain(d[j], -int(g))
+        return out.reshape(len(giant) * len(baby), -1, self.n)
+
+    def diag_matvec_bsgs(self, ct, bsgs_diags, baby, giant):
+        """sum over j of rotate(sum over i of bsgs_diags[j * len(baby) + i] (.) rotate(ct, baby[i]), giant[j]) (abc_hip_diag_matvec_bsgs),
+        CKKS; bsgs_diags [len(giant) * len(baby)][rows >= nl][N] as bsgs_diagonals makes them, one set for the batch"""
+        a4 = self._batch(ct, 3)
+        baby, giant = [int(x) for x in baby], [int(x) for x in giant]
+        rows = len(baby) * len(giant)
+        d = np.ascontiguousarray(bsgs_diags, dtype=np.uint64).reshape(rows, -1, self.n) if rows else np.zeros((0, a4.shape[2], self.n), np.uint64)
+        ab, ag = (C.c_int * max(len(baby), 1))(*baby), (C.c_int * max(len(giant), 1))(*giant)
+        cb, db = self.upload(a4), self.upload(d if d.size else np.zeros(1, dtype=np.uint64))
+        out = self.alloc(a4.nbytes)
+        try:
+            self.op("diag_matvec_bsgs", cb.ptr, db.ptr, C.c_size_t(d.shape[1] * self.n), ab, len(baby), ag, len(giant), out.ptr, a4.shape[2],
+                    C.c_size_t(a4.shape[0]))
             r = self.download(out, a4.shape)
         finally:
             for b in (cb, db, out):

@@ -46,6 +46,7 @@ void read_switches(abc_hip_ctx *c) {
   s.no_rotate_mac_fusion = env_on("ABC_HIP_NO_ROTATE_MAC_FUSION");
   s.no_mulplain_rescale_fusion = env_on("ABC_HIP_NO_MULPLAIN_RESCALE_FUSION");
   s.no_tensor_sum = env_on("ABC_HIP_NO_TENSOR_SUM");
+  s.no_plain_mac_sum = env_on("ABC_HIP_NO_PLAIN_MAC_SUM");
   s.main_two_per_cu = env_on("ABC_HIP_MAIN_TWO_PER_CU");
   s.host_sampling = env_on("ABC_HIP_HOST_SAMPLING");
   if (const char *e = std::getenv("ABC_HIP_CHUNK")) s.chunk = (size_t)std::atol(e);
@@ -612,6 +613,80 @@ static int mul_sum(abc_hip_ctx *c, const std::vector<const u64 *> &a, const std:
   return 0;
 }
 
+// out = (addend or 0) + sum over k of plain[k] (.) ct[k], [count][size][nl][N] (CKKS); out may BE addend and overlaps nothing else
+// (the caller has checked).  One K-term kernel, or -- kernel false -- term by term: the product lands in `out` where nothing is
+// carried yet, else in arena 2 (idle between two rotations), and the add kernel follows.
+static int plain_mac_sum(abc_hip_ctx *c, bool kernel, const std::vector<const u64 *> &ct, const std::vector<const u64 *> &plain, size_t plain_stride,
+                         const u64 *addend, u64 *out, int size, int nl, size_t count) {
+  if (!count) return 0;
+  const size_t bytes = count * size * (size_t)nl * c->n * 8;
+  if (ct.empty()) {
+    if (!addend) ABC_HIP_CHECK(hipMemsetAsync(out, 0, bytes, c->stream));
+    else if (addend != out) ABC_HIP_CHECK(hipMemcpyAsync(out, addend, bytes, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+  }
+  if (kernel) return launch_ckks_plain_mac_sum(c, ct.data(), plain.data(), plain_stride, (int)ct.size(), addend, out, size, nl, count);
+  if ((addend || ct.size() > 1) && ensure_aux(c, 2, bytes)) return 1;
+  const u64 *carry = addend;
+  for (size_t k = 0; k < ct.size(); k++) {
+    u64 *dst = carry ? (u64 *)c->aux[2] : out;
+    if (ckks_multiply_plain(c, ct[k], plain[k], plain_stride, dst, size, nl, count)) return 1;
+    if (carry && launch_addsub(c, carry, dst, out, nl, count * size, 0)) return 1;
+    carry = out;
+  }
+  return 0;
+}
+
+// out = sum_j rotate( sum_i D[j * n_baby + i] (.) rotate(in, baby[i]), giant[j] ), in the order given (abc_hip.h).  The batch goes
+// in groups of ciphertexts (matvec_bsgs_group).  Per group: the baby rotations land in arena 3, one slab per non-zero step (step 0
+// is the input itself); per giant step the inner sum over the slabs lands in arena 4 and one rotate_tail adds its rotation to the
+// group's slice of `out` -- the first giant step writes the slice, a giant step of 0 has no rotation: its inner sum is formed
+// onto the slice directly.  Arenas 0 .. 2 belong to the rotations (and to the per-term inner sum between them).
+static int diag_matvec_bsgs(abc_hip_ctx *c, const u64 *in, const u64 *diags, size_t diag_stride, const std::vector<int> &baby,
+                            const std::vector<int> &giant, u64 *out, int nl, size_t count) {
+  const size_t pw = (size_t)nl * c->n, bytes = count * 2 * pw * 8;
+  if (check_steps(c, baby) || check_steps(c, giant)) return 1;
+  if (!count) return 0;
+  if (ranges_overlap(in, bytes, out, bytes)) { set_error("diag_matvec_bsgs: d_out must not overlap d_in"); return 1; }
+  if (baby.empty() || giant.empty()) {
+    ABC_HIP_CHECK(hipMemsetAsync(out, 0, bytes, c->stream));
+    return 0;
+  }
+  const MatvecBsgsRoute r = route_matvec_bsgs(c->facts, nl);
+  const size_t nb = baby.size();
+  size_t slabs = 0;
+  for (int s : baby) slabs += s != 0;
+  const size_t group = matvec_bsgs_group(c->facts, nl, count, (int)slabs);
+  if (slabs && ensure_aux(c, 3, slabs * group * 2 * pw * 8)) return 1;
+  bool inner_arena = false;
+  for (int g : giant) inner_arena |= g != 0;
+  if (inner_arena && ensure_aux(c, 4, group * 2 * pw * 8)) return 1;
+  std::vector<const u64 *> x(nb), d(nb);
+  for (size_t off = 0; off < count; off += group) {
+    const size_t cc = count - off < group ? count - off : group;
+    const u64 *gin = in + off * 2 * pw;
+    u64 *gout = out + off * 2 * pw;
+    size_t slab = 0;
+    for (size_t i = 0; i < nb; i++) {
+      if (!baby[i]) { x[i] = gin; continue; }
+      u64 *dst = (u64 *)c->aux[3] + slab++ * group * 2 * pw;
+      if (rotate_tail(c, gin, {}, dst, nl, baby[i], cc)) return 1;
+      x[i] = dst;
+    }
+    for (size_t j = 0; j < giant.size(); j++) {
+      for (size_t i = 0; i < nb; i++) d[i] = diags + (j * nb + i) * diag_stride;
+      if (!giant[j]) {
+        if (plain_mac_sum(c, r.macsum, x, d, 0, j ? gout : nullptr, gout, 2, nl, cc)) return 1;
+        continue;
+      }
+      u64 *inner = (u64 *)c->aux[4];
+      if (plain_mac_sum(c, r.macsum, x, d, 0, nullptr, inner, 2, nl, cc)) return 1;
+      if (rotate_tail(c, inner, {j ? gout : nullptr}, gout, nl, giant[j], cc)) return 1;
+    }
+  }
+  return 0;
+}
+
 }  // namespace abc
 
 using namespace abc;
@@ -1024,7 +1099,8 @@ int abc_hip_route(abc_hip_ctx *c, int op, int nl, size_t count, int in_place, ch
   if (check_level(c, nl)) return 1;  // nl as the operation itself takes it (BFV: L, also for multiply)
   if (op == kRouteRescale && (nl < 2 || c->scheme != ABC_HIP_SCHEME_CKKS)) { set_error("route: rescale needs CKKS and nl >= 2"); return 1; }
   if (op == kRouteMulPlainRescale && (nl < 2 || c->scheme != ABC_HIP_SCHEME_CKKS)) { set_error("route: multiply_plain_rescale needs CKKS and nl >= 2"); return 1; }
-  const int n = buf ? format_op(buf, cap, c->facts, op, nl, count, in_place != 0) : -1;
+  if (op == kRouteDiagMatvecBsgs && c->scheme != ABC_HIP_SCHEME_CKKS) { set_error("route: diag_matvec_bsgs needs CKKS"); return 1; }
+  const int n = !buf ? -1 : op == kRouteDiagMatvecBsgs ? format_matvec_bsgs(buf, cap, c->facts, nl, count) : format_op(buf, cap, c->facts, op, nl, count, in_place != 0);
   if (n == -2) { set_error("route: unknown operation"); return 1; }
   if (n < 0) { set_error("route: buffer too small"); return 1; }
   return 0;
@@ -1147,6 +1223,58 @@ int abc_hip_diag_matvec(abc_hip_ctx *c, const uint64_t *in, const uint64_t *diag
   if (diag_stride < (size_t)nl * c->n) { set_error("diag_matvec: diag_stride must be at least nl * N"); return 1; }
   if (check_mac_plain(c, "diag_matvec", diags, diag_stride, (size_t)n_steps, out, count * 2 * (size_t)nl * c->n, nl)) return 1;
   return guarded([&] { return diag_matvec(c, in, diags, diag_stride, std::vector<int>(h_steps, h_steps + n_steps), out, nl, count); });
+}
+int abc_hip_multiply_plain_sum(abc_hip_ctx *c, const uint64_t *const *h_ct, const uint64_t *const *h_plain, size_t plain_stride, int n_terms,
+                               const uint64_t *addend, uint64_t *out, int size, int nl, size_t count) {
+  CTX_GUARD(c);
+  const char *op = "multiply_plain_sum";
+  if (c->scheme != ABC_HIP_SCHEME_CKKS) { set_error("multiply_plain_sum: CKKS only (a BFV plaintext product needs transforms)"); return 1; }
+  if (check_level(c, nl) || check_plain_stride(c, op, plain_stride, nl)) return 1;
+  if (size != 2 && size != 3) { set_error("multiply_plain_sum: size must be 2 or 3"); return 1; }
+  if (n_terms < 0 || (n_terms && (!h_ct || !h_plain))) { set_error("multiply_plain_sum: bad term list"); return 1; }
+  if (!out && count) { set_error("multiply_plain_sum: null output"); return 1; }
+  const size_t pw = (size_t)nl * c->n, words = count * size * pw;
+  for (int k = 0; k < n_terms; k++) {
+    if (!h_ct[k] || !h_plain[k]) { set_error("multiply_plain_sum: null term pointer"); return 1; }
+    if (words && ranges_overlap(h_ct[k], words * 8, out, words * 8)) { set_error("multiply_plain_sum: d_out must not overlap a ciphertext term"); return 1; }
+    if (check_mac_plain(c, op, h_plain[k], plain_stride, plain_stride ? count : 1, out, words, nl)) return 1;
+  }
+  if (addend && addend != out && words && ranges_overlap(addend, words * 8, out, words * 8)) {
+    set_error("multiply_plain_sum: d_out may be d_addend, but must not overlap it otherwise");
+    return 1;
+  }
+  return guarded([&] {
+    return plain_mac_sum(c, route_plain_mac_sum(c->facts, nl), std::vector<const u64 *>(h_ct, h_ct + n_terms),
+                         std::vector<const u64 *>(h_plain, h_plain + n_terms), plain_stride, addend, out, size, nl, count);
+  });
+}
+int abc_hip_rotate_plain(abc_hip_ctx *c, const uint64_t *plain, uint64_t *out, int nl, int steps, size_t rows) {
+  CTX_GUARD(c);
+  if (c->scheme != ABC_HIP_SCHEME_CKKS) { set_error("rotate_plain: CKKS only"); return 1; }
+  if (check_level(c, nl)) return 1;
+  const uint32_t elt = elt_from_step(c, steps);
+  if (!elt) { set_error("step count too large"); return 1; }
+  const size_t bytes = rows * (size_t)nl * c->n * 8;
+  if (!bytes) return 0;
+  if (ranges_overlap(plain, bytes, out, bytes)) { set_error("rotate_plain: d_out must not overlap d_plain"); return 1; }
+  if (!steps) {
+    ABC_HIP_CHECK(hipMemcpyAsync(out, plain, bytes, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+  }
+  return launch_galois(c, plain, out, nl, rows, elt, true);
+}
+int abc_hip_diag_matvec_bsgs(abc_hip_ctx *c, const uint64_t *in, const uint64_t *diags, size_t diag_stride, const int *h_baby, int n_baby,
+                             const int *h_giant, int n_giant, uint64_t *out, int nl, size_t count) {
+  CTX_GUARD(c);
+  if (check_level(c, nl)) return 1;
+  if ((ptrdiff_t)count < 0) { set_error("diag_matvec_bsgs: negative count"); return 1; }
+  if (n_baby < 0 || n_giant < 0 || (n_baby && !h_baby) || (n_giant && !h_giant)) { set_error("diag_matvec_bsgs: bad step list"); return 1; }
+  if (diag_stride < (size_t)nl * c->n) { set_error("diag_matvec_bsgs: diag_stride must be at least nl * N"); return 1; }
+  if (check_mac_plain(c, "diag_matvec_bsgs", diags, diag_stride, (size_t)n_baby * n_giant, out, count * 2 * (size_t)nl * c->n, nl)) return 1;
+  return guarded([&] {
+    return diag_matvec_bsgs(c, in, diags, diag_stride, std::vector<int>(h_baby, h_baby + n_baby), std::vector<int>(h_giant, h_giant + n_giant), out,
+                            nl, count);
+  });
 }
 int abc_hip_rotate_sum(abc_hip_ctx *c, const uint64_t *in, uint64_t *out, int nl, const int *h_steps, int n_steps, size_t count) {
   CTX_GUARD(c);

@@ -309,6 +309,12 @@ int launch_ckks_tensor(abc_hip_ctx *c, const u64 *a, const u64 *b, u64 *out3, in
 // k_ckks_tensor_sum, kTensorSumTerms pointer pairs per launch by value in the kernel arguments; n_terms >= 1
 constexpr int kTensorSumTerms = 8;
 int launch_ckks_tensor_sum(abc_hip_ctx *c, const u64 *const *a, const u64 *const *b, int n_terms, u64 *out3, int nl, size_t count);
+// out [count][size][nl][N] = (addend or 0) + sum over k < n_terms of plain[k] (.) ct[k] (CKKS; ct, plain: HOST arrays of device
+// pointers, read during the call; plain_stride as ckks_multiply_plain takes it; out may be addend): k_ckks_plain_mac_sum,
+// kPlainMacTerms pointer pairs per launch by value in the kernel arguments; n_terms >= 1
+constexpr int kPlainMacTerms = kTensorSumTerms;
+int launch_ckks_plain_mac_sum(abc_hip_ctx *c, const u64 *const *ct, const u64 *const *plain, size_t plain_stride, int n_terms, const u64 *addend,
+                              u64 *out, int size, int nl, size_t count);
 int keyswitch_generic(abc_hip_ctx *c, KsFront front, const KsOperands &o);
 int launch_ks_tmod(abc_hip_ctx *c, const u64 *prodS, u64 *tmod, int nl, size_t polys);
 int launch_ks_finish(abc_hip_ctx *c, const u64 *prodD, const u64 *tmod, u64 *out, const u64 *addend, size_t addend_stride,

@@ -924,4 +924,159 @@ int ckks_add_plain(abc_hip_ctx *c, const u64 *ct, const u64 *plain, size_t plain
   return 0;
 }
 
+// ---- CKKS plaintext multiply-accumulate sum: out = (carry or 0) + sum over the launch's terms of plain_k (.) ct_k ----
+// The plaintext twin of k_ckks_tensor_sum, for abc_hip_multiply_plain_sum and the inner sums of abc_hip_diag_matvec_bsgs.  One
+// workgroup owns kTensorSumSpan consecutive coefficients of ONE limb of one ciphertext and all SIZE components of it: the modulus is
+// workgroup-uniform, a term's plaintext words are loaded once for the 2 or 3 components, every lane moves 16 bytes per load and
+// store, and a term's 1 + SIZE loads are issued before the previous term's arithmetic.  The term pointers travel by value and the
+// loop over them is unrolled (the record is indexed by constants only).  The carried value is a POINTER: the addend on a call's
+// first launch, `out` on the later ones, null where there is neither.  A lane reads its own words of it before it writes them to
+// `out`, so out == carry needs no copy.  Results are exact modular sums in canonical form, whatever the order: bit-identical to
+// k_ckks_plain per term and k_addsub.
+struct PlainMacTerms {
+  const u64 *ct[kPlainMacTerms], *plain[kPlainMacTerms];
+};
+// Integer limbs: the 128-bit products accumulate lazily and are reduced once per launch.  A launch sums at most kPlainMacTerms
+// products, each at most (q - 1)^2, and the carried word (below q: less than one product): (T + 1) (q - 1)^2 < 2^128 must hold for
+// the widest prime a context accepts, 2^60 -- 2^(128 - 2 * 60) = 256, so T could be 255; the launch boundary is the reduction.
+static_assert(kPlainMacTerms + 1 <= (1 << (128 - 2 * kTensorSumPrimeBits)), "plain mac sum: the 128-bit accumulator would overflow within one launch");
+// fp64 limbs (q < 2^50): the carried word is below q, every product is |.| < q (fp_mulmod), and integer-valued doubles are exact up
+// to 2^53 >= 8 q.  So at most 7 products may follow the carried word -- or a re-centred accumulator, |.| <= q/2 -- before the next
+// re-centring.  The accumulators are re-centred after every kPlainMacFpTerms = 4 terms of a launch (carried + 4 products < 5 q,
+// then q/2 + 4 products < 4.5 q); a launch of 8 terms cannot do without one (1 + 8 > 8).  fp_to_canon centres the last group.
+constexpr int kPlainMacFpTerms = 4;
+static_assert(kPlainMacFpTerms + 1 <= 8, "plain mac sum: the fp64 accumulator would pass 2^53 between two re-centrings");
+
+template <int SIZE>
+struct PlainMacLoad {
+  u64x2 p, c[SIZE];
+};
+template <int SIZE>
+__device__ __forceinline__ PlainMacLoad<SIZE> plain_mac_load(const u64 *ct, const u64 *plain, size_t ct_off, size_t plain_off, size_t pw) {
+  PlainMacLoad<SIZE> t;
+  t.p = *reinterpret_cast<const u64x2 *>(plain + plain_off);
+#pragma unroll
+  for (int s = 0; s < SIZE; s++) t.c[s] = *reinterpret_cast<const u64x2 *>(ct + ct_off + s * pw);
+  return t;
+}
+
+// one tile on the integers; pc: this lane's words of the carried value, or null
+template <int SIZE>
+__device__ __forceinline__ void plain_mac_int(const PlainMacTerms &t, int nt, const Mod &m, size_t ct_off, size_t plain_off, size_t pw,
+                                              const u64 *pc, u64 *po) {
+  U128 ax[SIZE], ay[SIZE];
+#pragma unroll
+  for (int s = 0; s < SIZE; s++) ax[s] = U128{0, 0}, ay[s] = U128{0, 0};
+  if (pc) {  // workgroup-uniform
+#pragma unroll
+    for (int s = 0; s < SIZE; s++) {
+      const u64x2 r = *reinterpret_cast<const u64x2 *>(pc + s * pw);
+      ax[s].lo = r.x, ay[s].lo = r.y;
+    }
+  }
+  PlainMacLoad<SIZE> cur = plain_mac_load<SIZE>(t.ct[0], t.plain[0], ct_off, plain_off, pw), nxt = cur;
+#pragma unroll
+  for (int k = 0; k < kPlainMacTerms; k++) {
+    if (k < nt) {  // workgroup-uniform
+      if (k + 1 < kPlainMacTerms && k + 1 < nt) nxt = plain_mac_load<SIZE>(t.ct[k + 1], t.plain[k + 1], ct_off, plain_off, pw);
+#pragma unroll
+      for (int s = 0; s < SIZE; s++) mac128(ax[s], cur.c[s].x, cur.p.x), mac128(ay[s], cur.c[s].y, cur.p.y);
+      cur = nxt;
+    }
+  }
+  const u64 r64 = reduce64(0ull - m.q, m);  // 2^64 mod q
+#pragma unroll
+  for (int s = 0; s < SIZE; s++) *reinterpret_cast<u64x2 *>(po + s * pw) = u64x2{reduce128(ax[s], r64, m), reduce128(ay[s], r64, m)};
+}
+
+// one tile in fp64 (q < 2^50)
+template <int SIZE>
+__device__ __forceinline__ void plain_mac_fp(const PlainMacTerms &t, int nt, const Mod &m, size_t ct_off, size_t plain_off, size_t pw,
+                                             const u64 *pc, u64 *po) {
+  const double q = m.qd, qinv = m.qinv;
+  double ax[SIZE], ay[SIZE];
+#pragma unroll
+  for (int s = 0; s < SIZE; s++) ax[s] = 0, ay[s] = 0;
+  if (pc) {  // workgroup-uniform
+#pragma unroll
+    for (int s = 0; s < SIZE; s++) {
+      const u64x2 r = *reinterpret_cast<const u64x2 *>(pc + s * pw);
+      ax[s] = fp_from_u64(r.x), ay[s] = fp_from_u64(r.y);
+    }
+  }
+  PlainMacLoad<SIZE> cur = plain_mac_load<SIZE>(t.ct[0], t.plain[0], ct_off, plain_off, pw), nxt = cur;
+#pragma unroll
+  for (int k = 0; k < kPlainMacTerms; k++) {
+    if (k < nt) {  // workgroup-uniform
+      if (k + 1 < kPlainMacTerms && k + 1 < nt) nxt = plain_mac_load<SIZE>(t.ct[k + 1], t.plain[k + 1], ct_off, plain_off, pw);
+      const double px = fp_from_u64(cur.p.x), py = fp_from_u64(cur.p.y);
+#pragma unroll
+      for (int s = 0; s < SIZE; s++) {
+        ax[s] += fp_mulmod(fp_from_u64(cur.c[s].x), px, q, qinv);
+        ay[s] += fp_mulmod(fp_from_u64(cur.c[s].y), py, q, qinv);
+      }
+      // carried value + kPlainMacFpTerms products < 5 q < 2^53 up to here (see kPlainMacFpTerms)
+      if ((k + 1) % kPlainMacFpTerms == 0 && k + 1 < kPlainMacTerms) {
+#pragma unroll
+        for (int s = 0; s < SIZE; s++) ax[s] = fp_centre(ax[s], q, qinv), ay[s] = fp_centre(ay[s], q, qinv);
+      }
+      cur = nxt;
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < SIZE; s++) *reinterpret_cast<u64x2 *>(po + s * pw) = u64x2{fp_to_canon(ax[s], q, qinv), fp_to_canon(ay[s], q, qinv)};
+}
+
+// tiles = count * nl * (N / kTensorSumSpan), tile -> (ciphertext, limb, span) with scalar arithmetic; fpmask, HAS_FP / HAS_INT as in
+// k_ckks_tensor_sum.  carry: [count][SIZE][nl][N] like out (and possibly out itself), or null
+template <bool HAS_FP, bool HAS_INT, int SIZE>
+__global__ __launch_bounds__(256) void k_ckks_plain_mac_sum(DevCtx c, PlainMacTerms t, int nt, size_t plain_stride, const u64 *carry, u64 *out,
+                                                            int nl, size_t tiles, u32 fpmask) {
+  const u32 spans = (u32)c.n / kTensorSumSpan;
+  const size_t pw = (size_t)nl * c.n;
+  for (size_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const size_t limb = tile / spans;  // ct * nl + j
+    const u32 span = (u32)(tile - limb * spans);
+    const size_t ct = limb / (u32)nl;
+    const int j = (int)(limb - ct * (u32)nl);
+    const size_t w = (size_t)j * c.n + (size_t)span * kTensorSumSpan + 2 * threadIdx.x;  // word inside a polynomial
+    const Mod m = mod_at(c, j);
+    const size_t ct_off = ct * SIZE * pw + w, plain_off = ct * plain_stride + w;
+    const u64 *pc = carry ? carry + ct_off : nullptr;
+    if (HAS_FP && (!HAS_INT || ((fpmask >> j) & 1u))) plain_mac_fp<SIZE>(t, nt, m, ct_off, plain_off, pw, pc, out + ct_off);
+    else plain_mac_int<SIZE>(t, nt, m, ct_off, plain_off, pw, pc, out + ct_off);
+  }
+}
+
+// out [count][size][nl][N] = (addend or 0) + sum over k < n_terms of plain[k] (.) ct[k]; ct, plain: HOST arrays of device pointers;
+// n_terms >= 1 (the caller copies the addend, or writes the zeros, of an empty sum), size 2 or 3, on stream c->stream
+int launch_ckks_plain_mac_sum(abc_hip_ctx *c, const u64 *const *ct, const u64 *const *plain, size_t plain_stride, int n_terms, const u64 *addend,
+                              u64 *out, int size, int nl, size_t count) {
+  const size_t tiles = count * nl * ((size_t)c->n / kTensorSumSpan);
+  if (!tiles || n_terms < 1) return 0;
+  const u32 full = (1u << nl) - 1u;
+  const u32 fpmask = (c->use_fp && (c->facts.data_fp(nl) || !c->sw.no_mixed)) ? c->facts.fp_data_mask(nl) : 0u;
+  const size_t cap = 256 * 8 * 16;  // workgroups: every CU several times over, the tile loop beyond
+  const dim3 grid((unsigned)(tiles < cap ? tiles : cap));
+  for (int k0 = 0; k0 < n_terms; k0 += kPlainMacTerms) {
+    const int nt = n_terms - k0 < kPlainMacTerms ? n_terms - k0 : kPlainMacTerms;
+    PlainMacTerms t;
+    for (int k = 0; k < kPlainMacTerms; k++) t.ct[k] = ct[k0 + (k < nt ? k : 0)], t.plain[k] = plain[k0 + (k < nt ? k : 0)];
+    const u64 *carry = k0 ? out : addend;
+    auto go = [&](auto has_fp, auto has_int, auto sz) {
+      hipLaunchKernelGGL((k_ckks_plain_mac_sum<decltype(has_fp)::value, decltype(has_int)::value, decltype(sz)::value>), grid, dim3(256), 0,
+                         c->stream, c->dc, t, nt, plain_stride, carry, out, nl, tiles, fpmask);
+    };
+    auto by_size = [&](auto has_fp, auto has_int) {
+      if (size == 3) go(has_fp, has_int, std::integral_constant<int, 3>{});
+      else go(has_fp, has_int, std::integral_constant<int, 2>{});
+    };
+    if (fpmask == full) by_size(std::true_type{}, std::false_type{});
+    else if (!fpmask) by_size(std::false_type{}, std::true_type{});
+    else by_size(std::true_type{}, std::true_type{});
+    ABC_HIP_CHECK(hipGetLastError());
+  }
+  return 0;
+}
+
 }  // namespace abc

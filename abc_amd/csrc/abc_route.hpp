@@ -25,6 +25,7 @@ struct Switches {
   bool no_rotate_mac_fusion = false;  // ABC_HIP_NO_ROTATE_MAC_FUSION: rotate_mac_plain as a rotation into an arena, multiply_plain on it, then the add kernel
   bool no_mulplain_rescale_fusion = false;  // ABC_HIP_NO_MULPLAIN_RESCALE_FUSION: multiply_plain_rescale as multiply_plain into an arena, then rescale
   bool no_tensor_sum = false;  // ABC_HIP_NO_TENSOR_SUM: multiply_sum / mul_sum_relin form every product on its own (tensor into an arena, then the add kernel)
+  bool no_plain_mac_sum = false;  // ABC_HIP_NO_PLAIN_MAC_SUM: multiply_plain_sum (and the inner sums of diag_matvec_bsgs) as multiply_plain into an arena, then the add kernel, per term
   bool main_two_per_cu = false;  // ABC_HIP_MAIN_TWO_PER_CU: k_split4_main_fp in its one-piece pair phase at nl <= 4 (same step, same route: a form of the kernel)
   bool host_sampling = false;  // ABC_HIP_HOST_SAMPLING: the keyed entries (the OS-keyed ones call them) draw with the host twin of the keyed spec (no route depends on it)
   size_t chunk = 0, few_limbs = 48, lean_limit = 96, bfv_scratch_mb = 0, pass0_target_limit = 128;
@@ -119,6 +120,14 @@ struct MulPlainRescaleRoute {
 struct MulSumRoute {
   KsRoute ks;
   bool sum;  // CKKS: one K-term tensor-sum kernel (k_ckks_tensor_sum); otherwise each product by the multiply of the scheme into a second arena, then the add kernel
+};
+
+// a matrix-vector product by diagonals, baby-step giant-step: the baby rotations (plain rotations, out of place, into an arena), one
+// plaintext multiply-accumulate sum per giant step, then addend + rotate(inner sum) with d_out as addend and output
+struct MatvecBsgsRoute {
+  RotRoute baby;
+  bool macsum;         // one K-term kernel (k_ckks_plain_mac_sum); otherwise multiply_plain into an arena and the add kernel, per term
+  RotTailRoute giant;  // route_rotate_add, out of place
 };
 
 namespace route_detail {
@@ -259,6 +268,13 @@ inline MulSumRoute route_mul_sum(const RouteFacts &f, int nl) {
   return {route_keyswitch(f, nl), f.scheme == 2 && !f.sw.no_tensor_sum};
 }
 
+// (addend or 0) + sum of K plaintext products at level nl (CKKS): the K-term kernel at every ring, chain and level
+inline bool route_plain_mac_sum(const RouteFacts &f, int) { return f.scheme == 2 && !f.sw.no_plain_mac_sum; }
+
+inline MatvecBsgsRoute route_matvec_bsgs(const RouteFacts &f, int nl) {
+  return {route_rotate(f, nl, false), route_plain_mac_sum(f, nl), route_rotate_add(f, nl, false)};
+}
+
 // ---- per chunk ----
 struct ChunkPlan {
   size_t chunk;
@@ -280,17 +296,22 @@ inline ChunkPlan plan_chunks(const RouteFacts &f, int nl, size_t count) {
   if (p.chunk > count) p.chunk = count;
   return p;
 }
-// mul_sum_relin's size-3 sum lives in an arena, so the batch goes in groups of ciphertexts: a multiple of chunk * lanes (the key
-// switch inside a group chunks as a whole call of that many would), as many of them as keep the arena within the 4 GiB of
-// plan_chunks' cap; with ABC_HIP_CHUNK set, exactly chunk * lanes
-inline size_t mul_sum_group(const RouteFacts &f, int nl, size_t count) {
+// A call that keeps polys_per_ct polynomials per ciphertext in an arena walks the batch in groups of ciphertexts: a multiple of
+// chunk * lanes (the key switch inside a group chunks as a whole call of that many would), as many of them as keep the arena within
+// the 4 GiB of plan_chunks' cap; with ABC_HIP_CHUNK set, exactly chunk * lanes.  mul_sum_relin: its size-3 sum
+inline size_t arena_group(const RouteFacts &f, int nl, size_t count, size_t polys_per_ct) {
   const ChunkPlan p = plan_chunks(f, nl, count);
   const size_t unit = p.chunk * (size_t)p.lanes;
   if (f.sw.chunk || unit >= count) return unit < count ? unit : count;
-  const size_t per_ct_bytes = 3 * (size_t)nl * ((size_t)1 << f.logn) * 8;
+  const size_t per_ct_bytes = polys_per_ct * (size_t)nl * ((size_t)1 << f.logn) * 8;
   const size_t units = ((size_t)4 << 30) / per_ct_bytes / unit;
   const size_t group = unit * (units ? units : 1);
   return group < count ? group : count;
+}
+inline size_t mul_sum_group(const RouteFacts &f, int nl, size_t count) { return arena_group(f, nl, count, 3); }
+// diag_matvec_bsgs keeps n_baby rotated ciphertexts per input in an arena: the same rule with 2 * n_baby polynomials per ciphertext
+inline size_t matvec_bsgs_group(const RouteFacts &f, int nl, size_t count, int n_baby) {
+  return arena_group(f, nl, count, 2 * (size_t)(n_baby > 0 ? n_baby : 1));
 }
 // the choices that depend on the cc ciphertexts of one chunk (a ragged last chunk may differ from the others); fields a
 // sequence does not read stay false / 0
@@ -395,6 +416,17 @@ inline int format_op(char *buf, size_t cap, const RouteFacts &f, int op, int nl,
     n = snprintf(buf, cap, "%s", f.scheme == 1 ? name(route_bfv_multiply(f)) : "tensor");
   }
   return n < 0 ? n : (size_t)n < cap ? n : -1;
+}
+// ABC_HIP_ROUTE_DIAG_MATVEC_BSGS (13) has a formatter of its own, which abc_hip_route calls for that number: format_op keeps the
+// set of operations it had (tests/cpp/test_route_mul_sum.cpp probes 13 there as an unknown operation).  The baby rotation's route,
+// macsum=, the giant step's add=; returns the length, or -1 if cap is too small.
+constexpr int kRouteDiagMatvecBsgs = 13;
+inline int format_matvec_bsgs(char *buf, size_t cap, const RouteFacts &f, int nl, size_t count) {
+  char ks[80];
+  const MatvecBsgsRoute r = route_matvec_bsgs(f, nl);
+  format_ks(ks, sizeof ks, f, r.baby.ks, nl, matvec_bsgs_group(f, nl, count, 1));  // per-chunk fields: those of the first group's first chunk
+  const int n = snprintf(buf, cap, "%s %s macsum=%s add=%s", r.baby.fold ? "fold" : "permute", ks, r.macsum ? "kernel" : "per_term", r.giant.fused ? "fused" : "separate");
+  return n < 0 ? -1 : (size_t)n < cap ? n : -1;
 }
 
 }  // namespace abc

@@ -77,6 +77,7 @@ int abc_hip_ctx_reload_env(abc_hip_ctx *ctx);
 #define ABC_HIP_ROUTE_ROTATE_MAC_PLAIN 7 /* CKKS: addend + plaintext (.) one Galois element; in_place: d_out aliases d_in (6 is unassigned) */
 #define ABC_HIP_ROUTE_MULTIPLY_PLAIN_RESCALE 10 /* CKKS, nl >= 2: the rescale's route plus mulplain=fused / mulplain=separate (8 and 9 are unassigned) */
 #define ABC_HIP_ROUTE_MUL_SUM_RELIN 12 /* relinearize(sum of products): the key switch's route plus tensor=sum / tensor=per_term; per-chunk fields: the first group's (11 is unassigned) */
+#define ABC_HIP_ROUTE_DIAG_MATVEC_BSGS 13 /* CKKS: the baby rotation's route (as ABC_HIP_ROUTE_ROTATE, out of place), macsum=kernel / macsum=per_term, then the giant step's add=fused / add=separate; per-chunk fields: the first group's */
 int abc_hip_route(abc_hip_ctx *ctx, int op, int nl, size_t count, int in_place, char *buf, size_t cap);
 
 /* ---- device memory (so that FFI callers need no HIP runtime binding) ----
@@ -272,6 +273,47 @@ int abc_hip_apply_galois_mac_plain(abc_hip_ctx *ctx, const uint64_t *d_in, const
  * abc_hip_rotate_mac_plain. */
 int abc_hip_diag_matvec(abc_hip_ctx *ctx, const uint64_t *d_in, const uint64_t *d_diags, size_t diag_stride, const int *h_steps,
                         int n_steps, uint64_t *d_out, int nl, size_t count);
+/* CKKS only: a plaintext-weighted sum of ciphertexts as one call -- a linear layer with one ciphertext per feature, a convolution
+ * over channels, the inner sum of a baby-step giant-step matvec.  Replaces n_terms x Evaluator::multiply_plain (:159,:196) and
+ * n_terms x Evaluator::add (:92,:114):
+ *   d_out [count][size][nl][N] = (d_addend or 0) + plain_0 (.) ct_0 + ... + plain_{K-1} (.) ct_{K-1},  size = 2 or 3.
+ * h_ct, h_plain: HOST arrays of n_terms device pointers, read during the call only; ct_k is [count][size][nl][N], and every plain_k
+ * takes plain_stride exactly as abc_hip_multiply_plain does (0: one plaintext per term for the whole batch; >= nl * N: one per
+ * ciphertext, its first nl limbs read, so rows encoded at a higher level apply at nl < L).  One pointer may appear in several
+ * terms.  d_addend == NULL: no addend; d_out may be exactly d_addend.  Bit-identical to abc_hip_multiply_plain per term and
+ * abc_hip_add in any order: the sums are exact and canonical.  One K-term kernel forms the sum (abc_hip_route,
+ * ABC_HIP_ROUTE_DIAG_MATVEC_BSGS: macsum=kernel; the term pointers travel in the kernel's arguments, eight per launch, and the
+ * running sum is carried by pointer from launch to launch); ABC_HIP_NO_PLAIN_MAC_SUM=1 forms each product on its own in an arena
+ * and adds (macsum=per_term).  n_terms == 0 writes the addend, or zeros without one; count == 0 succeeds and enqueues nothing.
+ * Fails with nothing written or enqueued for: a BFV context, a bad level, size or stride, n_terms < 0, a null term pointer, d_out
+ * overlapping any ct_k or plain_k, d_out overlapping d_addend without being equal to it.  Capturable, under the "run once eagerly
+ * first" rule of abc_hip_graph_begin. */
+int abc_hip_multiply_plain_sum(abc_hip_ctx *ctx, const uint64_t *const *h_ct, const uint64_t *const *h_plain, size_t plain_stride,
+                               int n_terms, const uint64_t *d_addend, uint64_t *d_out, int size, int nl, size_t count);
+/* CKKS only: the slot rotation of PLAINTEXTS, d_plain [rows][nl][N] in NTT form -> d_out likewise: the index permutation
+ * Evaluator::rotate_rows (:55,:60) applies to either component of a ciphertext, with no key and no key switch.  Negative steps
+ * rotate the other way; step 0 is a copy.  rotate_plain(encode(v), s) is encode(v rotated by s), word for word.  Fails for a BFV
+ * context, a bad level, |steps| >= N / 2, or d_out overlapping d_plain.  Capturable. */
+int abc_hip_rotate_plain(abc_hip_ctx *ctx, const uint64_t *d_plain, uint64_t *d_out, int nl, int steps, size_t rows);
+/* CKKS only: a matrix-vector product by diagonals, baby-step giant-step: n_baby + n_giant rotations serve n_baby * n_giant
+ * diagonals, where abc_hip_diag_matvec pays one key switch per diagonal.
+ *   d_out = sum over j of rotate( sum over i of D[j * n_baby + i] (.) rotate(d_in, h_baby[i]),  h_giant[j] ).
+ * Row (j, i) of D starts at d_diags + (j * n_baby + i) * diag_stride; diag_stride >= nl * N and the first nl limbs are read; one
+ * set for the batch, as in abc_hip_diag_matvec.  THE CALLER SUPPLIES ROWS ALREADY ROTATED BY -h_giant[j]:
+ *   D[j, i] = rotate_plain(diag_{h_giant[j] + h_baby[i]}, -h_giant[j]),
+ * because  diag (.) rot(rot(x, b), g) = rot( rot_plain(diag, -g) (.) rot(x, b), g ):  a rotation distributes over the slot-wise
+ * product, so the giant rotation can be taken once, behind the inner sum (abc_hip_rotate_plain does the pre-rotation).
+ * Sequence: the baby rotations run as abc_hip_rotate does (Evaluator::rotate_rows :55,:60; NAF chains included; step 0 is d_in
+ * itself) into an arena; per giant step one abc_hip_multiply_plain_sum (Evaluator::multiply_plain :159,:196, add :92,:114) over
+ * the n_baby rotated ciphertexts lands in a second arena; then d_out = d_out + rotate(inner_j, h_giant[j]) as abc_hip_rotate_add
+ * does, fused where its route says so.  A giant step of 0 is a plain add; the first j writes d_out.  Order is as given,
+ * duplicates are allowed.  The batch is walked in groups of ciphertexts that keep the baby arena within 4 GiB (the rule of
+ * abc_hip_mul_sum_relin; with ABC_HIP_CHUNK=c exactly c * lanes).  n_baby == 0 or n_giant == 0 writes zeros; count == 0 succeeds
+ * and enqueues nothing.  Every step and every key is checked before the first launch; a BFV context, a bad level or stride, a
+ * negative count, a null step list, a step without a key (or a NAF chain of keys), d_out overlapping d_in or d_diags fail the call
+ * with nothing written.  The step lists are read during the call only.  Capturable like abc_hip_rotate_add. */
+int abc_hip_diag_matvec_bsgs(abc_hip_ctx *ctx, const uint64_t *d_in, const uint64_t *d_diags, size_t diag_stride, const int *h_baby,
+                             int n_baby, const int *h_giant, int n_giant, uint64_t *d_out, int nl, size_t count);
 /* The three plaintext operations.  d_out may be d_ct (the reference's *_inplace call sites); size = 2 or 3.
  * plain_stride, in words, is the distance from ciphertext i's plaintext to ciphertext i + 1's:
  *   0            one plaintext, broadcast to the batch (d_plain holds N words for BFV, nl * N for CKKS);

@@ -236,6 +236,136 @@ def mul_sum_ab(res, only, rng):
         g.close()
 
 
+def _three_ways(g, res, names, kinds, fns, routes, switch, B, reps, extra=None):
+    """the variants in turn, five rounds; kind "per_term" runs under `switch`.  The first run of each sizes its arenas and is left out."""
+    runs, route = {k: [] for k in names}, {}
+    for rep in range(5):
+        for kind, name, fn in zip(kinds, names, fns):
+            if kind == "per_term":
+                os.environ[switch] = "1"
+            else:
+                os.environ.pop(switch, None)
+            g.reload_env()
+            route[name] = routes(kind)
+            runs[name].append(timeit(g, fn, reps))
+    os.environ.pop(switch, None)
+    g.reload_env()
+    for i, (k, ms) in enumerate(runs.items()):
+        kept = ms[1:]
+        res[k] = {"batch": B, "ms": min(kept), "ms_median": sorted(kept)[len(kept) // 2], "ms_runs": ms, "us_per_ct": min(kept) * 1e3 / B,
+                  "route": route[k]}
+        res[k].update(extra[i] if extra else {})
+        note = "  [%s]" % ", ".join("%s %s" % kv for kv in extra[i].items()) if extra else ""
+        print("%-48s %s ms / %d  (%s)%s" % (k, " ".join("%8.3f" % v for v in ms), B, route[k], note), flush=True)
+
+
+def plain_mac_sum_ab(res, only, rng):
+    """sum over K terms of plain_k (.) ct_k, one plaintext per term for the batch, three ways, alternating in one process, five runs each:
+    (a) `composed`: K x abc_hip_multiply_plain and K - 1 x abc_hip_add -- what a caller had before the call existed;
+    (b) `per_term`: abc_hip_multiply_plain_sum under ABC_HIP_NO_PLAIN_MAC_SUM=1;
+    (c) `kernel`: abc_hip_multiply_plain_sum, the K-term kernel.
+    The K ciphertext operands are distinct buffers (device copies of one random batch: the kernels have no data-dependent path)."""
+    shapes = [  # tag, context, levels, batches
+        ("ckks14", lambda: capi.Context(capi.CKKS, 16384, capi.create_primes(16384, [50, 40, 40, 40, 50])), (4, 3), (512, 32)),
+        ("ckks15", lambda: capi.Context(capi.CKKS, 32768, capi.create_primes(32768, [50, 40, 40, 50])), (3,), (256,)),
+        ("ckks12", lambda: capi.Context(capi.CKKS, 4096, capi.create_primes(4096, [50, 40, 40, 50])), (3,), (1024,)),
+    ]
+    kinds = ("composed", "per_term", "kernel")
+    for tag, make, levels, batches in shapes:
+        if only and only not in "%s_plain_mac_sum" % tag and "plain_mac_sum" not in only:
+            continue
+        g = make()
+        for nl in levels:
+            for B in batches:
+                cb, zero = C.c_size_t(B), C.c_size_t(0)
+                first, nb = rand_ct(g, rng, B, 2, nl)
+                pool = [first]
+                for _ in range(15):
+                    pool.append(g.alloc(nb))
+                    g.op("memcpy_d2d", pool[-1].ptr, first.ptr, C.c_size_t(nb))
+                plains = [rand_ct(g, rng, 1, 1, nl)[0] for _ in range(16)]  # [nl][N] each
+                tmp, out = g.alloc(nb), g.alloc(nb)
+                for K in (2, 4, 8, 16):
+                    names = ["%s_L%d_b%d_plain_mac_sum_K%d_%s" % (tag, nl, B, K, kind) for kind in kinds]
+                    if not any(only in k for k in names):
+                        continue
+                    pc, pp = g.term_pointers([x.ptr for x in pool[:K]]), g.term_pointers([x.ptr for x in plains[:K]])
+
+                    def composed():
+                        g.op("multiply_plain", pool[0].ptr, plains[0].ptr, zero, out.ptr, 2, nl, cb)
+                        for k in range(1, K):
+                            g.op("multiply_plain", pool[k].ptr, plains[k].ptr, zero, tmp.ptr, 2, nl, cb)
+                            g.op("add", out.ptr, tmp.ptr, out.ptr, 2, nl, cb)
+
+                    def one_call():
+                        g.op("multiply_plain_sum", pc, pp, zero, K, None, out.ptr, 2, nl, cb)
+                    _three_ways(g, res, names, kinds, (composed, one_call, one_call),
+                                lambda kind: "composed" if kind == "composed" else g.route("diag_matvec_bsgs", nl, B).split(" add=")[0].split(" ")[-1],
+                                "ABC_HIP_NO_PLAIN_MAC_SUM", B, 10 if B * K >= 256 else 50)
+                del pool, first, plains, tmp, out
+        g.close()
+
+
+def _naf(value):
+    out, sign, value, i = [], value < 0, abs(value), 0
+    while value:
+        zi = 2 - (value & 3) if value & 1 else 0
+        value = (value - zi) >> 1
+        if zi:
+            out.append((-zi if sign else zi) << i)
+        i += 1
+    return out
+
+
+def _key_switches(g, steps):
+    """key switches abc_hip_rotate performs for these steps under the context's key set: one with a key of its own, else the NAF chain's"""
+    have = set(g.galois_elts())
+    return sum(0 if s == 0 else 1 if g.elt_from_step(s) in have else len(_naf(s)) for s in steps)
+
+
+def matvec_bsgs_ab(res, only, rng):
+    """a matrix of n diagonals (steps 0 .. n - 1) times a batch of ciphertexts: abc_hip_diag_matvec, one rotation per diagonal, against
+    abc_hip_diag_matvec_bsgs on the same diagonals as a square grid (16 = 4 x 4, 64 = 8 x 8), alternating in one process, five runs
+    each.  The default key set on both sides, so both pay NAF chains; the number of key switches of each side is printed with its time."""
+    shapes = [  # tag, context, level, batches
+        ("ckks14", lambda: capi.Context(capi.CKKS, 16384, capi.create_primes(16384, [50, 40, 40, 40, 50])), 3, (512, 32)),
+        ("ckks15", lambda: capi.Context(capi.CKKS, 32768, capi.create_primes(32768, [50, 40, 40, 50])), 3, (256,)),
+    ]
+    kinds = ("diag_matvec", "bsgs")
+    for tag, make, nl, batches in shapes:
+        if only and only not in "%s_matvec_bsgs" % tag and "matvec_bsgs" not in only:
+            continue
+        g = make()
+        g.keygen(1)
+        for B in batches:
+            cb = C.c_size_t(B)
+            a, nb = rand_ct(g, rng, B, 2, nl)
+            d, _ = rand_ct(g, rng, 64, 1, nl)  # [64][nl][N]: the words do not matter to the time, so one set serves both sides
+            out = g.alloc(nb)
+            for side in (4, 8):
+                n = side * side
+                names = ["%s_L%d_b%d_matvec_bsgs_%dx%d_%s" % (tag, nl, B, side, side, kind) for kind in kinds]
+                if not any(only in k for k in names):
+                    continue
+                steps, baby, giant = list(range(n)), list(range(side)), [side * j for j in range(side)]
+                c_steps, c_baby, c_giant = (C.c_int * n)(*steps), (C.c_int * side)(*baby), (C.c_int * side)(*giant)
+                stride = C.c_size_t(nl * g.n)
+
+                def diag():
+                    g.op("diag_matvec", a.ptr, d.ptr, stride, c_steps, n, out.ptr, nl, cb)
+
+                def bsgs():
+                    g.op("diag_matvec_bsgs", a.ptr, d.ptr, stride, c_baby, side, c_giant, side, out.ptr, nl, cb)
+                extra = ({"key_switches": _key_switches(g, steps)}, {"key_switches": _key_switches(g, baby) + _key_switches(g, giant)})
+                _three_ways(g, res, names, kinds, (diag, bsgs),
+                            lambda kind: g.route("rotate_mac_plain" if kind == "diag_matvec" else "diag_matvec_bsgs", nl, B), "ABC_HIP_NO_PLAIN_MAC_SUM",
+                            B, 3, extra)
+                t_d, t_b = res[names[0]]["ms_median"], res[names[1]]["ms_median"]
+                print("    time ratio %.2f, key-switch ratio %.2f" % (t_d / t_b, extra[0]["key_switches"] / extra[1]["key_switches"]), flush=True)
+            del a, d, out
+        g.close()
+
+
 def keyswitch_batch1(res, only, rng):
     """one ciphertext per call at nl = 4: relinearise, rotate, rotate_add and rotate_mac_plain (one plaintext, one addend) on the two
     CKKS split rings -- the calls in which the host side of the key switch (routes, operand record, launches) is the largest share"""
@@ -406,12 +536,14 @@ def main():
     only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else ""
     res = {}
     rng = np.random.default_rng(0)
-    if not (only and "mul_sum" in only):  # that A/B has its own contexts and 2 x 16 operand batches: nothing else is set up
+    if not (only and any(x in only for x in ("mul_sum", "plain_mac_sum", "matvec_bsgs"))):  # those A/Bs have their own contexts and operand batches: nothing else is set up
         single_ops(res, only, rng)
     rotate_add_ab(res, only, rng)
     rotate_mac_ab(res, only, rng)
     mulplain_rescale_ab(res, only, rng)
     mul_sum_ab(res, only, rng)
+    plain_mac_sum_ab(res, only, rng)
+    matvec_bsgs_ab(res, only, rng)
     keyswitch_batch1(res, only, rng)
     os.makedirs("gpurun_out", exist_ok=True)
     json.dump(res, open("gpurun_out/op_bench.json", "w"), indent=1)
