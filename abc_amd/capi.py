@@ -41,6 +41,7 @@ SYMBOLS = [
     "abc_hip_multiply_plain_rescale",
     "abc_hip_multiply_sum", "abc_hip_mul_sum_relin",
     "abc_hip_multiply_plain_sum", "abc_hip_rotate_plain", "abc_hip_diag_matvec_bsgs",
+    "abc_hip_bfv_plain_to_ntt", "abc_hip_bfv_multiply_plain_sum", "abc_hip_bfv_diag_matvec_bsgs",
 ]
 
 
@@ -85,6 +86,12 @@ def lib():
             L.abc_hip_rotate_plain.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t]
             L.abc_hip_diag_matvec_bsgs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int),
                                                    C.c_int, C.c_void_p, C.c_int, C.c_size_t]
+        if hasattr(L, "abc_hip_bfv_multiply_plain_sum"):
+            L.abc_hip_bfv_plain_to_ntt.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+            L.abc_hip_bfv_multiply_plain_sum.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_size_t, C.c_int,
+                                                         C.c_void_p, C.c_void_p, C.c_int, C.c_size_t]
+            L.abc_hip_bfv_diag_matvec_bsgs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.c_int,
+                                                       C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_size_t]
         L.abc_hip_encrypt_keyed.argtypes =[C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_size_t]
         L.abc_hip_keygen_keyed.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
         L.abc_hip_keyed_small.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_size_t]
@@ -215,7 +222,8 @@ class Context:
         _chk(lib().abc_hip_ctx_reload_env(self.h))
 
     ROUTE_OPS = {"mul_relin": 0, "keyswitch": 1, "relinearize": 1, "rotate": 2, "rescale": 3, "multiply": 4, "rotate_add": 5,
-                 "rotate_mac_plain": 7, "multiply_plain_rescale": 10, "mul_sum_relin": 12, "diag_matvec_bsgs": 13}
+                 "rotate_mac_plain": 7, "multiply_plain_rescale": 10, "mul_sum_relin": 12, "diag_matvec_bsgs": 13,
+                 "bfv_plain_sum": 14, "bfv_matvec_bsgs": 15}
 
     def route(self, op, nl, count=1, in_place=False):
         """the kernel sequence such a call takes, as the string of abc_route.hpp's formatter"""
@@ -547,6 +555,83 @@ class Context:
         out = self.alloc(a4.nbytes)
         try:
             self.op("diag_matvec_bsgs", cb.ptr, db.ptr, C.c_size_t(d.shape[1] * self.n), ab, len(baby), ag, len(giant), out.ptr, a4.shape[2],
+                    C.c_size_t(a4.shape[0]))
+            r = self.download(out, a4.shape)
+        finally:
+            for b in (cb, db, out):
+                b.free()
+        return r if np.ndim(ct) == 4 else r[0]
+
+    # ---- BFV: plaintext-weighted sums with one inverse transform ----
+    CT_COEFF, CT_NTT = 0, 1
+
+    def bfv_plain_to_ntt(self, plain):
+        """BFV plaintexts [rows][N] (or [N]) mod t -> [rows][L][N] lifted and in NTT form (abc_hip_bfv_plain_to_ntt)"""
+        p = np.ascontiguousarray(plain, dtype=np.uint64)
+        p2 = p.reshape(-1, self.n)
+        shape = (p2.shape[0], self.L, self.n)
+        r = self._run("bfv_plain_to_ntt", [p2], shape, C.c_size_t(p2.shape[0])) if p2.shape[0] else np.zeros(shape, np.uint64)
+        return r[0] if p.ndim == 1 else r
+
+    def bfv_multiply_plain_sum(self, cts, plains_ntt, addend=None, size=2, count=1, ct_form=0):
+        """(addend or 0) + sum over k of plains_ntt[k] * cts[k] with one inverse transform (abc_hip_bfv_multiply_plain_sum), BFV.
+        cts[k]: [count][size][L][N] (or one ciphertext) in the form ct_form says; plains_ntt as bfv_plain_to_ntt makes them: all
+        [L][N], one per term for the batch, or all [count][L][N], one per ciphertext.  cts and plains_ntt are LISTS (or tuples) of
+        arrays: an array that appears twice in them is uploaded once and stays one pointer.  size / count: the shape of an empty sum
+        without an addend"""
+        cts, plains_ntt = list(cts), list(plains_ntt)  # held for the call: the de-duplication below goes by object identity
+        if len(cts) != len(plains_ntt):
+            raise ValueError("as many plaintexts as ciphertexts")
+        c4 = [self._batch(x, 3) for x in cts]
+        p = [np.ascontiguousarray(x, dtype=np.uint64) for x in plains_ntt]
+        a4 = None if addend is None else self._batch(addend, 3)
+        shape = c4[0].shape if c4 else a4.shape if a4 is not None else (count, size, self.L, self.n)
+        if any(x.shape != shape for x in c4 + ([a4] if a4 is not None else [])):
+            raise ValueError("every ciphertext is [count][size][L][N]")
+        if any(x.shape != p[0].shape for x in p):
+            raise ValueError("every plaintext has one form")
+        stride = 0 if not p or p[0].ndim == 2 else self.L * self.n
+        bufs = {}
+        for orig, arr in zip(list(cts) + list(plains_ntt), c4 + p):  # one upload per distinct array: a repeated operand stays one pointer
+            if id(orig) not in bufs:
+                bufs[id(orig)] = self.upload(arr)
+        ab = self.upload(a4) if a4 is not None else None
+        out = self.alloc(max(int(np.prod(shape)) * 8, 8))
+        try:
+            pc = self.term_pointers([bufs[id(x)].ptr for x in cts])
+            pp = self.term_pointers([bufs[id(x)].ptr for x in plains_ntt])
+            self.op("bfv_multiply_plain_sum", pc, int(ct_form), pp, C.c_size_t(stride), len(c4), ab.ptr if ab else None, out.ptr, shape[1],
+                    C.c_size_t(shape[0]))
+            r = self.download(out, shape)
+        finally:
+            for b in list(bufs.values()) + [out] + ([ab] if ab else []):
+                b.free()
+        one = (len(cts) > 0 and np.ndim(cts[0]) == 3) or (len(cts) == 0 and addend is not None and np.ndim(addend) == 3)
+        return r[0] if one else r
+
+    def bfv_bsgs_diagonals(self, diags_cleartext, baby, giant):
+        """the rows abc_hip_bfv_diag_matvec_bsgs takes, from cleartext diagonals: diags_cleartext[j * len(baby) + i] holds the N slot
+        values of the diagonal of step giant[j] + baby[i]; each half-row is rolled by -giant[j], then batch_encode, then
+        bfv_plain_to_ntt.  [len(giant) * len(baby)][L][N]"""
+        rows = len(baby) * len(giant)
+        if not rows:
+            return np.zeros((0, self.L, self.n), dtype=np.uint64)
+        d = np.ascontiguousarray(diags_cleartext, dtype=np.int64).reshape(len(giant), len(baby), 2, self.n // 2)
+        rolled = np.stack([np.roll(d[j], int(g), axis=2) for j, g in enumerate(giant)])  # roll right by g: the slots of rotate(., -g)
+        return self.bfv_plain_to_ntt(self.batch_encode(rolled.reshape(rows, self.n)))
+
+    def bfv_diag_matvec_bsgs(self, ct, bsgs_diags_ntt, baby, giant):
+        """sum over j of rotate(sum over i of bsgs_diags_ntt[j * len(baby) + i] * rotate(ct, baby[i]), giant[j])
+        (abc_hip_bfv_diag_matvec_bsgs), BFV; bsgs_diags_ntt [len(giant) * len(baby)][L][N] as bfv_bsgs_diagonals makes them"""
+        a4 = self._batch(ct, 3)
+        baby, giant = [int(x) for x in baby], [int(x) for x in giant]
+        rows = len(baby) * len(giant)
+        d = np.ascontiguousarray(bsgs_diags_ntt, dtype=np.uint64).reshape(rows, self.L, self.n) if rows else np.zeros((0, self.L, self.n), np.uint64)
+        ab, ag = (C.c_int * max(len(baby), 1))(*baby), (C.c_int * max(len(giant), 1))(*giant)
+        cb, db = self.upload(a4), self.upload(d if d.size else np.zeros(1, dtype=np.uint64))
+        out = self.alloc(a4.nbytes)
+        try:
+            self.op("bfv_diag_matvec_bsgs", cb.ptr, db.ptr, C.c_size_t(self.L * self.n), ab, len(baby), ag, len(giant), out.ptr,
                     C.c_size_t(a4.shape[0]))
             r = self.download(out, a4.shape)
         finally:

@@ -642,6 +642,10 @@ static int plain_mac_sum(abc_hip_ctx *c, bool kernel, const std::vector<const u6
 // is the input itself); per giant step the inner sum over the slabs lands in arena 4 and one rotate_tail adds its rotation to the
 // group's slice of `out` -- the first giant step writes the slice, a giant step of 0 has no rotation: its inner sum is formed
 // onto the slice directly.  Arenas 0 .. 2 belong to the rotations (and to the per-term inner sum between them).
+// BFV (abc_hip_bfv_diag_matvec_bsgs; diags in NTT form, bfv_plain_to_ntt): the slabs are transformed to NTT form once -- the rotated
+// ones in place, in one launch where the group fills its slabs; step 0 gets a slab of its own behind them, a transformed copy,
+// because `in` stays untouched -- and every inner sum is bfv_multiply_plain_sum on NTT-form terms: no forward transform at all
+// (arena 2: its partial sum, or its sum under an addend).
 static int diag_matvec_bsgs(abc_hip_ctx *c, const u64 *in, const u64 *diags, size_t diag_stride, const std::vector<int> &baby,
                             const std::vector<int> &giant, u64 *out, int nl, size_t count) {
   const size_t pw = (size_t)nl * c->n, bytes = count * 2 * pw * 8;
@@ -652,35 +656,57 @@ static int diag_matvec_bsgs(abc_hip_ctx *c, const u64 *in, const u64 *diags, siz
     ABC_HIP_CHECK(hipMemsetAsync(out, 0, bytes, c->stream));
     return 0;
   }
+  const bool bfv = c->scheme == ABC_HIP_SCHEME_BFV;
   const MatvecBsgsRoute r = route_matvec_bsgs(c->facts, nl);
+  const LimbMap qmap = bfv ? key_limb_map(c, nl) : LimbMap{};  // the BFV transforms alone read it
   const size_t nb = baby.size();
-  size_t slabs = 0;
-  for (int s : baby) slabs += s != 0;
+  size_t rotated = 0;
+  for (int s : baby) rotated += s != 0;
+  const size_t slabs = bfv ? nb : rotated;
   const size_t group = matvec_bsgs_group(c->facts, nl, count, (int)slabs);
   if (slabs && ensure_aux(c, 3, slabs * group * 2 * pw * 8)) return 1;
   bool inner_arena = false;
   for (int g : giant) inner_arena |= g != 0;
   if (inner_arena && ensure_aux(c, 4, group * 2 * pw * 8)) return 1;
   std::vector<const u64 *> x(nb), d(nb);
+  auto inner_sum = [&](const u64 *addend, u64 *dst, size_t cc) {
+    return bfv ? bfv_multiply_plain_sum(c, x.data(), true, d.data(), 0, (int)nb, addend, dst, 2, cc) : plain_mac_sum(c, r.macsum, x, d, 0, addend, dst, 2, nl, cc);
+  };
   for (size_t off = 0; off < count; off += group) {
     const size_t cc = count - off < group ? count - off : group;
     const u64 *gin = in + off * 2 * pw;
     u64 *gout = out + off * 2 * pw;
-    size_t slab = 0;
+    size_t slab = 0, copies = rotated;
     for (size_t i = 0; i < nb; i++) {
-      if (!baby[i]) { x[i] = gin; continue; }
+      if (!baby[i]) {
+        x[i] = gin;
+        if (bfv) {
+          u64 *dst = (u64 *)c->aux[3] + copies++ * group * 2 * pw;
+          if (launch_ntt_fwd_from(c, gin, dst, qmap, nl, cc * 2 * nl)) return 1;
+          x[i] = dst;
+        }
+        continue;
+      }
       u64 *dst = (u64 *)c->aux[3] + slab++ * group * 2 * pw;
       if (rotate_tail(c, gin, {}, dst, nl, baby[i], cc)) return 1;
       x[i] = dst;
     }
+    if (bfv && rotated) {
+      if (cc == group) {
+        if (launch_ntt_fwd(c, (u64 *)c->aux[3], qmap, nl, rotated * cc * 2 * nl)) return 1;
+      } else {  // a ragged last group leaves gaps between its slabs
+        for (size_t s = 0; s < rotated; s++)
+          if (launch_ntt_fwd(c, (u64 *)c->aux[3] + s * group * 2 * pw, qmap, nl, cc * 2 * nl)) return 1;
+      }
+    }
     for (size_t j = 0; j < giant.size(); j++) {
       for (size_t i = 0; i < nb; i++) d[i] = diags + (j * nb + i) * diag_stride;
       if (!giant[j]) {
-        if (plain_mac_sum(c, r.macsum, x, d, 0, j ? gout : nullptr, gout, 2, nl, cc)) return 1;
+        if (inner_sum(j ? gout : nullptr, gout, cc)) return 1;
         continue;
       }
       u64 *inner = (u64 *)c->aux[4];
-      if (plain_mac_sum(c, r.macsum, x, d, 0, nullptr, inner, 2, nl, cc)) return 1;
+      if (inner_sum(nullptr, inner, cc)) return 1;
       if (rotate_tail(c, inner, {j ? gout : nullptr}, gout, nl, giant[j], cc)) return 1;
     }
   }
@@ -1100,7 +1126,12 @@ int abc_hip_route(abc_hip_ctx *c, int op, int nl, size_t count, int in_place, ch
   if (op == kRouteRescale && (nl < 2 || c->scheme != ABC_HIP_SCHEME_CKKS)) { set_error("route: rescale needs CKKS and nl >= 2"); return 1; }
   if (op == kRouteMulPlainRescale && (nl < 2 || c->scheme != ABC_HIP_SCHEME_CKKS)) { set_error("route: multiply_plain_rescale needs CKKS and nl >= 2"); return 1; }
   if (op == kRouteDiagMatvecBsgs && c->scheme != ABC_HIP_SCHEME_CKKS) { set_error("route: diag_matvec_bsgs needs CKKS"); return 1; }
-  const int n = !buf ? -1 : op == kRouteDiagMatvecBsgs ? format_matvec_bsgs(buf, cap, c->facts, nl, count) : format_op(buf, cap, c->facts, op, nl, count, in_place != 0);
+  if ((op == kRouteBfvPlainSum || op == kRouteBfvMatvecBsgs) && c->scheme != ABC_HIP_SCHEME_BFV) { set_error("route: bfv_multiply_plain_sum and bfv_diag_matvec_bsgs need BFV"); return 1; }
+  const int n = !buf                        ? -1
+                : op == kRouteDiagMatvecBsgs ? format_matvec_bsgs(buf, cap, c->facts, nl, count)
+                : op == kRouteBfvPlainSum    ? format_bfv_plain_sum(buf, cap, c->facts, count)
+                : op == kRouteBfvMatvecBsgs  ? format_bfv_matvec_bsgs(buf, cap, c->facts, count)
+                                             : format_op(buf, cap, c->facts, op, nl, count, in_place != 0);
   if (n == -2) { set_error("route: unknown operation"); return 1; }
   if (n < 0) { set_error("route: buffer too small"); return 1; }
   return 0;
@@ -1274,6 +1305,53 @@ int abc_hip_diag_matvec_bsgs(abc_hip_ctx *c, const uint64_t *in, const uint64_t 
   return guarded([&] {
     return diag_matvec_bsgs(c, in, diags, diag_stride, std::vector<int>(h_baby, h_baby + n_baby), std::vector<int>(h_giant, h_giant + n_giant), out,
                             nl, count);
+  });
+}
+int abc_hip_bfv_plain_to_ntt(abc_hip_ctx *c, const uint64_t *plain, uint64_t *plain_ntt, size_t rows) {
+  CTX_GUARD(c);
+  if (c->scheme != ABC_HIP_SCHEME_BFV) { set_error("bfv_plain_to_ntt: BFV only"); return 1; }
+  if ((ptrdiff_t)rows < 0) { set_error("bfv_plain_to_ntt: negative row count"); return 1; }
+  if (rows && (!plain || !plain_ntt)) { set_error("bfv_plain_to_ntt: null pointer"); return 1; }
+  if (rows && ranges_overlap(plain, rows * c->n * 8, plain_ntt, rows * (size_t)c->L * c->n * 8)) { set_error("bfv_plain_to_ntt: d_plain_ntt must not overlap d_plain"); return 1; }
+  return bfv_plain_to_ntt(c, plain, plain_ntt, rows);
+}
+int abc_hip_bfv_multiply_plain_sum(abc_hip_ctx *c, const uint64_t *const *h_ct, int ct_form, const uint64_t *const *h_plain_ntt,
+                                   size_t plain_stride, int n_terms, const uint64_t *addend, uint64_t *out, int size, size_t count) {
+  CTX_GUARD(c);
+  if (c->scheme != ABC_HIP_SCHEME_BFV) { set_error("bfv_multiply_plain_sum: BFV only (CKKS: abc_hip_multiply_plain_sum)"); return 1; }
+  if (size != 2 && size != 3) { set_error("bfv_multiply_plain_sum: size must be 2 or 3"); return 1; }
+  const size_t pw = (size_t)c->L * c->n;
+  if (plain_stride && plain_stride != pw) { set_error("bfv_multiply_plain_sum: plain_stride must be 0 or L * N"); return 1; }
+  if (ct_form != ABC_HIP_CT_COEFF && ct_form != ABC_HIP_CT_NTT) { set_error("bfv_multiply_plain_sum: ct_form must be ABC_HIP_CT_COEFF or ABC_HIP_CT_NTT"); return 1; }
+  if ((ptrdiff_t)count < 0) { set_error("bfv_multiply_plain_sum: negative count"); return 1; }
+  if (n_terms < 0 || (n_terms && (!h_ct || !h_plain_ntt))) { set_error("bfv_multiply_plain_sum: bad term list"); return 1; }
+  if (!out && count) { set_error("bfv_multiply_plain_sum: null output"); return 1; }
+  const size_t words = count * size * pw, plain_words = count ? (plain_stride ? count * pw : pw) : 0;
+  for (int k = 0; k < n_terms; k++) {
+    if (!h_ct[k] || !h_plain_ntt[k]) { set_error("bfv_multiply_plain_sum: null term pointer"); return 1; }
+    if (words && ranges_overlap(h_ct[k], words * 8, out, words * 8)) { set_error("bfv_multiply_plain_sum: d_out must not overlap a ciphertext term"); return 1; }
+    if (words && ranges_overlap(h_plain_ntt[k], plain_words * 8, out, words * 8)) { set_error("bfv_multiply_plain_sum: the plaintext must not overlap d_out"); return 1; }
+  }
+  if (addend && addend != out && words && ranges_overlap(addend, words * 8, out, words * 8)) {
+    set_error("bfv_multiply_plain_sum: d_out may be d_addend, but must not overlap it otherwise");
+    return 1;
+  }
+  return guarded([&] { return bfv_multiply_plain_sum(c, h_ct, ct_form == ABC_HIP_CT_NTT, h_plain_ntt, plain_stride, n_terms, addend, out, size, count); });
+}
+int abc_hip_bfv_diag_matvec_bsgs(abc_hip_ctx *c, const uint64_t *in, const uint64_t *diags_ntt, size_t diag_stride, const int *h_baby, int n_baby,
+                                 const int *h_giant, int n_giant, uint64_t *out, size_t count) {
+  CTX_GUARD(c);
+  const char *op = "bfv_diag_matvec_bsgs";
+  if (c->scheme != ABC_HIP_SCHEME_BFV) { set_error(std::string(op) + ": BFV only (CKKS: abc_hip_diag_matvec_bsgs)"); return 1; }
+  if ((ptrdiff_t)count < 0) { set_error(std::string(op) + ": negative count"); return 1; }
+  if (n_baby < 0 || n_giant < 0 || (n_baby && !h_baby) || (n_giant && !h_giant)) { set_error(std::string(op) + ": bad step list"); return 1; }
+  const size_t pw = (size_t)c->L * c->n, rows = (size_t)n_baby * n_giant, out_words = count * 2 * pw;
+  if (diag_stride < pw) { set_error(std::string(op) + ": diag_stride must be at least L * N"); return 1; }
+  if (count && (!in || !out || (rows && !diags_ntt))) { set_error(std::string(op) + ": null pointer"); return 1; }
+  if (rows && out_words && ranges_overlap(diags_ntt, ((rows - 1) * diag_stride + pw) * 8, out, out_words * 8)) { set_error(std::string(op) + ": the plaintext must not overlap d_out"); return 1; }
+  return guarded([&] {
+    return diag_matvec_bsgs(c, in, diags_ntt, diag_stride, std::vector<int>(h_baby, h_baby + n_baby), std::vector<int>(h_giant, h_giant + n_giant), out,
+                            c->L, count);
   });
 }
 int abc_hip_rotate_sum(abc_hip_ctx *c, const uint64_t *in, uint64_t *out, int nl, const int *h_steps, int n_steps, size_t count) {

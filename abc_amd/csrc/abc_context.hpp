@@ -326,6 +326,11 @@ int launch_drop_last(abc_hip_ctx *c, const u64 *in, u64 *out, int size, int nl, 
 
 int bfv_multiply(abc_hip_ctx *c, BfvMul m, const u64 *a, const u64 *b, u64 *out3, size_t count);
 int bfv_multiply_plain(abc_hip_ctx *c, const u64 *ct, const u64 *plain, size_t plain_stride, u64 *out, int size, size_t count);
+// the NTT-domain plaintext-weighted sum (abc_kernels_bfv.hip): plain [rows][N] mod t -> [rows][L][N] lifted and transformed;
+// (addend or 0) + sum_k plain_ntt[k] * ct[k] with one inverse transform, ct / plain_ntt HOST arrays of device pointers
+int bfv_plain_to_ntt(abc_hip_ctx *c, const u64 *plain, u64 *plain_ntt, size_t rows);
+int bfv_multiply_plain_sum(abc_hip_ctx *c, const u64 *const *ct, bool ct_ntt, const u64 *const *plain_ntt, size_t plain_stride, int n_terms,
+                           const u64 *addend, u64 *out, int size, size_t count);
 int bfv_addsub_plain(abc_hip_ctx *c, const u64 *ct, const u64 *plain, size_t plain_stride, u64 *out, int size, size_t count, int sub);
 int ckks_multiply_plain(abc_hip_ctx *c, const u64 *ct, const u64 *plain, size_t plain_stride, u64 *out, int size, int nl, size_t count);
 int ckks_add_plain(abc_hip_ctx *c, const u64 *ct, const u64 *plain, size_t plain_stride, u64 *out, int size, int nl, size_t count, int sub);

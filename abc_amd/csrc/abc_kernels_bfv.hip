@@ -604,6 +604,207 @@ int bfv_multiply_plain(abc_hip_ctx *c, const u64 *ct, const u64 *plain, size_t p
   return launch_ntt_inv(c, out, qmap, L, count * size * L);
 }
 
+// ---- plaintext-weighted sum with ONE inverse transform: out = (addend or 0) + sum_k INTT(NTT(ct_k) (.) plain_ntt_k) ----
+// The inverse transform is linear and every step is exact modulo q_i, so the K products are summed in NTT form and inverted once:
+// K + 1 transforms per output limb instead of 2K, no add kernels, and no plaintext transform at all -- the weights arrive in NTT
+// form (bfv_plain_to_ntt, once per weight).  Canonical results: bit-identical to bfv_multiply_plain per term and k_addsub.
+
+// Evaluator::transform_to_ntt(plain): the lift and the forward transforms bfv_multiply_plain pays on every call, once
+int bfv_plain_to_ntt(abc_hip_ctx *c, const u64 *plain, u64 *plain_ntt, size_t rows) {
+  if (!rows) return 0;
+  hipLaunchKernelGGL(k_plain_lift, dim3(grid_for(rows * c->n, 256)), dim3(256), 0, c->stream, c->dc, plain, plain_ntt, rows);
+  ABC_HIP_CHECK(hipGetLastError());
+  return launch_ntt_fwd(c, plain_ntt, key_limb_map(c, c->L), c->L, rows * c->L);
+}
+
+// Rings 2^10 .. 2^14, every data prime below 2^50 (the shape of k_bfv_mul_plain_fused_fp): workgroup (ct, comp, limb), N/16
+// lanes, sixteen fp64 accumulators per lane in the register layout the forward transform ends in and the inverse one starts from
+// (PassIdx<LB, LB - 2, 2>).  CT_NTT false: per term a forward transform in LDS, the product with the plaintext word added to the
+// accumulator in its store.  CT_NTT true: the terms are read in NTT form, no forward transform.  Then one inverse transform; N^-1
+// and the addend in its store.  One workgroup per component: a plaintext word is read `size` times, the second and third time from
+// L2 -- looping over the components inside a workgroup would keep 32 or 48 accumulators per lane.
+// The term pointers travel by value, kBfvPlainSumTerms per launch (no device-side pointer table: a recorded call replays with the
+// pointers it was recorded with, as every other call does).  All but the last launch leave the NTT-domain partial sum, canonical,
+// at `out` (an arena) and the next launch starts from it as `carry`; only the last launch inverts.  A lane reads its own words of
+// carry / addend before it writes them to out, so out == carry and out == addend need no copy.
+constexpr int kBfvPlainSumTerms = 8;
+struct BfvPlainSumTerms {
+  const u64 *ct[kBfvPlainSumTerms], *plain[kBfvPlainSumTerms];
+};
+// fp64 bound: a carried word is canonical (< q), a re-centred accumulator |.| <= q/2; every product is fp_mulmod's |.| < q of two
+// values |.| <= q (a canonical word, or a forward transform's output re-centred to |.| <= q/2); q < 2^50 and integer-valued doubles
+// are exact up to 2^53 = 8 * 2^50.  So at most 7 products may follow a carried word before the next re-centring: the accumulators are
+// re-centred after every kBfvPlainSumFpTerms = 4 terms of a launch (1 + 4 < 8, then 1/2 + 4 < 8), and once more before the inverse
+// transform, which starts from |.| <= q/2 as it does in k_bfv_mul_plain_fused_fp.
+constexpr int kBfvPlainSumFpTerms = 4;
+// 53 bits of exact integers over the kFpBits = 50 bits fp_ok admits (abc_route.hpp): 2^53 / 2^50 = 8 times q
+static_assert(kBfvPlainSumFpTerms + 1 <= (1 << (53 - (int)kFpBits)), "bfv plain sum: the fp64 accumulator would pass 2^53 between two re-centrings");
+static_assert(kBfvPlainSumTerms % kBfvPlainSumFpTerms == 0, "bfv plain sum: a launch ends on a re-centring boundary");
+static_assert(kBfvPlainSumTerms == 8 && kPlainMacTerms == 8, "bfv plain sum: bfv_plain_sum_arena_polys (abc_route.hpp) counts eight terms per launch on either route");
+
+// term k of the record, k workgroup-uniform: a chain of scalar selects over constant indices (the record stays in the kernel
+// arguments; a run-time index could move it to scratch memory)
+__device__ __forceinline__ const u64 *bfv_plain_sum_pick(const u64 *const (&p)[kBfvPlainSumTerms], int k) {
+  const u64 *r = p[0];
+#pragma unroll
+  for (int j = 1; j < kBfvPlainSumTerms; j++) r = (k == j) ? p[j] : r;
+  return r;
+}
+
+// TAIL: what follows the launch's terms -- compile-time, so every instantiation is one loop and at most one inverse transform in
+// a straight line (with run-time branches around two inverse bodies the 1024-lane form, 128 VGPRs, spilled)
+constexpr int kBfvSumPartial = 0, kBfvSumInvert = 1, kBfvSumInvertAdd = 2;
+template <int LB, bool CT_NTT, int TAIL>
+__global__ __launch_bounds__((1 << LB) / 16) void k_bfv_plain_sum_fp(DevCtx c, BfvPlainSumTerms t, int nt, size_t plain_stride,
+                                                                     const u64 *carry, const u64 *addend, u64 *out, int size) {
+  __shared__ double lds[lds_words(LB)];
+  const size_t N = (size_t)1 << LB;
+  const int L = c.L;
+  const int limb = blockIdx.x % L;
+  const size_t poly = blockIdx.x / L;  // ct * size + comp
+  const size_t ci = poly / size;
+  const Mod m = mod_at(c, limb);
+  const FpTable tb = fp_table(c, limb);
+  const double q = m.qd, qinv = m.qinv;
+  const size_t off = (poly * L + limb) * N, poff = ci * plain_stride + (size_t)limb * N;
+  using P = PassIdx<LB, LB - 2, 2>;  // slot r = 4 g + k holds word P::elem(hi[g], lo[g], k) of the limb
+  int hi[P::NG], lo[P::NG];
+  P::groups((int)threadIdx.x, hi, lo);
+  double acc[16];
+#pragma unroll
+  for (int r = 0; r < 16; r++) acc[r] = 0.0;
+  if (carry) {  // workgroup-uniform
+#pragma unroll
+    for (int r = 0; r < 16; r++) acc[r] = fp_from_u64(carry[off + P::elem(hi[r >> 2], lo[r >> 2], r & 3)]);
+  }
+  for (int k = 0; k < nt; k++) {  // nt <= kBfvPlainSumTerms, workgroup-uniform
+    const u64 *__restrict__ x = bfv_plain_sum_pick(t.ct, k) + off;
+    const u64 *__restrict__ pl = bfv_plain_sum_pick(t.plain, k) + poff;
+    if constexpr (CT_NTT) {
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const int i = P::elem(hi[r >> 2], lo[r >> 2], r & 3);
+        acc[r] += fp_mulmod(fp_from_u64(x[i]), fp_from_u64(pl[i]), q, qinv);
+      }
+    } else {
+      if (k) block_sync_lds();  // the previous term's last pass has read its LDS words
+      ntt_fwd_block_a<LB, FpArith>(
+          lds, [&](int, int i) { return fp_from_u64(x[i]); },
+          [&](int r, int i, double v) { acc[r] += fp_mulmod(fp_centre(v, q, qinv), fp_from_u64(pl[i]), q, qinv); }, tb, m, 0, 0);
+    }
+    if ((k + 1) % kBfvPlainSumFpTerms == 0) {  // see kBfvPlainSumFpTerms
+#pragma unroll
+      for (int r = 0; r < 16; r++) acc[r] = fp_centre(acc[r], q, qinv);
+    }
+  }
+  if constexpr (TAIL == kBfvSumPartial) {  // the partial sum stays in NTT form
+#pragma unroll
+    for (int r = 0; r < 16; r++) out[off + P::elem(hi[r >> 2], lo[r >> 2], r & 3)] = fp_to_canon(acc[r], q, qinv);
+  } else {
+    if constexpr (!CT_NTT) block_sync_lds();  // the last forward transform's last pass has read its LDS words
+    u64 *dst = out + off;
+    ntt_inv_block_a<LB, FpArith>(
+        lds, [&](int r, int) { return fp_centre(acc[r], q, qinv); },
+        [&](int, int i, double v) {
+          double s = fp_mul_lazy(v, m.inv_n_c, m.inv_n_cq, q);
+          if constexpr (TAIL == kBfvSumInvertAdd) s += fp_from_u64(addend[off + i]);  // addend is null in the other instantiations
+          dst[i] = fp_to_canon(s, q, qinv);
+        },
+        tb, m, 0, 0);
+  }
+}
+
+// one group of ciphertexts on the fused route; n_terms >= 1; arena 2 holds the partial sum between launches (K > kBfvPlainSumTerms)
+template <int LB>
+static int launch_bfv_plain_sum_fused(abc_hip_ctx *c, const u64 *const *ct, bool ct_ntt, const u64 *const *plain, size_t plain_stride,
+                                      int n_terms, const u64 *addend, u64 *out, int size, size_t count) {
+  u64 *partial = nullptr;
+  if (n_terms > kBfvPlainSumTerms) {
+    if (ensure_aux(c, 2, count * size * (size_t)c->L * c->n * 8)) return 1;
+    partial = (u64 *)c->aux[2];
+  }
+  const dim3 grid((unsigned)(count * size * c->L)), block((1 << LB) / 16);
+  for (int k0 = 0; k0 < n_terms; k0 += kBfvPlainSumTerms) {
+    const int nt = n_terms - k0 < kBfvPlainSumTerms ? n_terms - k0 : kBfvPlainSumTerms;
+    const int last = k0 + kBfvPlainSumTerms >= n_terms;
+    BfvPlainSumTerms t;
+    for (int k = 0; k < kBfvPlainSumTerms; k++) t.ct[k] = ct[k0 + (k < nt ? k : 0)], t.plain[k] = plain[k0 + (k < nt ? k : 0)];
+    const u64 *carry = k0 ? partial : nullptr;
+    auto go = [&](auto ntt, auto tail) {
+      hipLaunchKernelGGL((k_bfv_plain_sum_fp<LB, decltype(ntt)::value, decltype(tail)::value>), grid, block, 0, c->stream, c->dc, t, nt, plain_stride,
+                         carry, addend, last ? out : partial, size);
+    };
+    auto by_tail = [&](auto ntt) {
+      if (!last) go(ntt, std::integral_constant<int, kBfvSumPartial>{});
+      else if (addend) go(ntt, std::integral_constant<int, kBfvSumInvertAdd>{});
+      else go(ntt, std::integral_constant<int, kBfvSumInvert>{});
+    };
+    if (ct_ntt) by_tail(std::true_type{});
+    else by_tail(std::false_type{});
+    ABC_HIP_CHECK(hipGetLastError());
+  }
+  return 0;
+}
+
+// one group on the general route (N >= 2^15, a prime of 2^50 or above, ABC_HIP_NO_FUSED): no new arithmetic.  Coefficient-form terms
+// are transformed out of place into arena 3, up to kPlainMacTerms at a time; k_ckks_plain_mac_sum (scheme-agnostic on NTT-form data
+// at nl = L, its carry pointer continues the sum) accumulates -- into `out` without an addend, else into arena 2 --; one inverse
+// transform, then the add kernel for the addend (elementwise: out may be the addend).  n_terms >= 1
+static int bfv_plain_sum_general(abc_hip_ctx *c, const u64 *const *ct, bool ct_ntt, const u64 *const *plain, size_t plain_stride,
+                                 int n_terms, const u64 *addend, u64 *out, int size, size_t count) {
+  const int L = c->L;
+  const size_t words = count * size * (size_t)L * c->n;
+  const LimbMap qmap = key_limb_map(c, L);
+  const int per = n_terms < kPlainMacTerms ? n_terms : kPlainMacTerms;
+  if (addend && ensure_aux(c, 2, words * 8)) return 1;
+  if (!ct_ntt && ensure_aux(c, 3, (size_t)per * words * 8)) return 1;
+  u64 *sum = addend ? (u64 *)c->aux[2] : out;
+  const u64 *carry = nullptr;
+  for (int k0 = 0; k0 < n_terms; k0 += kPlainMacTerms) {
+    const int nt = n_terms - k0 < kPlainMacTerms ? n_terms - k0 : kPlainMacTerms;
+    const u64 *x[kPlainMacTerms];
+    for (int k = 0; k < nt; k++) {
+      x[k] = ct[k0 + k];
+      if (ct_ntt) continue;
+      u64 *dst = (u64 *)c->aux[3] + (size_t)k * words;
+      if (launch_ntt_fwd_from(c, ct[k0 + k], dst, qmap, L, count * size * L)) return 1;
+      x[k] = dst;
+    }
+    if (launch_ckks_plain_mac_sum(c, x, plain + k0, plain_stride, nt, carry, sum, size, L, count)) return 1;
+    carry = sum;
+  }
+  if (launch_ntt_inv(c, sum, qmap, L, count * size * L)) return 1;
+  return addend ? launch_addsub(c, addend, sum, out, L, count * size, 0) : 0;
+}
+
+// out [count][size][L][N] = (addend or 0) + sum over k < n_terms of plain_ntt[k] * ct[k]; ct, plain_ntt: HOST arrays of device
+// pointers; plain_stride 0 or L * N; out may be addend and overlaps nothing else (the caller has checked).  The batch goes in
+// groups of ciphertexts that keep the arenas within 4 GiB (bfv_plain_sum_group); the route is that of the whole call.
+int bfv_multiply_plain_sum(abc_hip_ctx *c, const u64 *const *ct, bool ct_ntt, const u64 *const *plain_ntt, size_t plain_stride, int n_terms,
+                           const u64 *addend, u64 *out, int size, size_t count) {
+  if (!count) return 0;
+  const size_t ctw = (size_t)size * c->L * c->n;
+  if (!n_terms) {
+    if (!addend) ABC_HIP_CHECK(hipMemsetAsync(out, 0, count * ctw * 8, c->stream));
+    else if (addend != out) ABC_HIP_CHECK(hipMemcpyAsync(out, addend, count * ctw * 8, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+  }
+  const BfvPlainSum route = route_bfv_plain_sum(c->facts, count);
+  const size_t group = bfv_plain_sum_group(c->facts, count, bfv_plain_sum_arena_polys(route, ct_ntt, n_terms, size, addend != nullptr));
+  std::vector<const u64 *> x((size_t)n_terms), p((size_t)n_terms);
+  for (size_t off = 0; off < count; off += group) {
+    const size_t cc = count - off < group ? count - off : group;
+    for (int k = 0; k < n_terms; k++) x[k] = ct[k] + off * ctw, p[k] = plain_ntt[k] + off * plain_stride;
+    const u64 *ga = addend ? addend + off * ctw : nullptr;
+    u64 *go = out + off * ctw;
+    const int rc = route == BfvPlainSum::fused
+                       ? dispatch_logn<10, 14>(c->logn, [&](auto LB) { return launch_bfv_plain_sum_fused<decltype(LB)::value>(c, x.data(), ct_ntt, p.data(), plain_stride, n_terms, ga, go, size, cc); })
+                       : bfv_plain_sum_general(c, x.data(), ct_ntt, p.data(), plain_stride, n_terms, ga, go, size, cc);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
 // ---- add_plain / sub_plain: c0 +/- round(q*m/t)  (multiply_add_plain_with_scaling_variant) ----
 __global__ __launch_bounds__(256) void k_plain_scale_addsub(DevCtx c, const u64 *ct, const u64 *plain, size_t plain_stride, u64 *out,
                                                             int size, size_t count, int sub) {

@@ -275,6 +275,47 @@ inline MatvecBsgsRoute route_matvec_bsgs(const RouteFacts &f, int nl) {
   return {route_rotate(f, nl, false), route_plain_mac_sum(f, nl), route_rotate_add(f, nl, false)};
 }
 
+// (addend or 0) + sum of K plaintext products with ONE inverse transform (BFV, abc_hip_bfv_multiply_plain_sum and the inner sums of
+// abc_hip_bfv_diag_matvec_bsgs), from ring, prime widths and batch only:
+//   fused       k_bfv_plain_sum_fp: forward transforms, products, sum and the inverse transform of a limb in one workgroup; rings
+//               2^10 .. 2^14 with every data prime below 2^50 -- where bfv_multiply_plain takes its fused kernel
+//   ntt_domain  transforms by the stand-alone launches, the sum by k_ckks_plain_mac_sum on NTT-form data: N >= 2^15, a prime of
+//               2^50 or above, no fp64, ABC_HIP_NO_FUSED, and at N = 2^14 a batch of at most kBfvPlainSumSmall ciphertext limbs
+//               (counted at size 2), where the stand-alone transforms spread a limb over many workgroups (bfv_multiply_plain's rule)
+enum class BfvPlainSum { fused, ntt_domain };
+constexpr size_t kBfvPlainSumSmall = 48;
+inline BfvPlainSum route_bfv_plain_sum(const RouteFacts &f, size_t count) {
+  const bool fp = f.use_fp && !f.sw.no_fused && f.logn >= 10 && f.logn <= 14 && f.L >= 1 && f.data_fp(f.L);
+  if (fp && (f.logn < 14 || count * 2 * (size_t)f.L > kBfvPlainSumSmall)) return BfvPlainSum::fused;
+  return BfvPlainSum::ntt_domain;
+}
+// polynomials per ciphertext the call keeps in context arenas.  fused: the NTT-domain partial sum between two launches, where the
+// terms do not fit one (terms_per_launch = 8: kBfvPlainSumTerms, and kPlainMacTerms on the other route).  ntt_domain: the forward
+// transforms of up to eight coefficient-form terms, and the sum where an addend keeps it out of d_out
+inline size_t bfv_plain_sum_arena_polys(BfvPlainSum r, bool ct_ntt, int n_terms, int size, bool addend, int terms_per_launch = 8) {
+  if (r == BfvPlainSum::fused) return n_terms > terms_per_launch ? (size_t)size : 0;
+  const int per = n_terms < terms_per_launch ? n_terms : terms_per_launch;
+  return (ct_ntt ? 0 : (size_t)per * size) + (addend ? (size_t)size : 0);
+}
+// ciphertexts per group of that call: as many as keep polys_per_ct polynomials of L limbs each within 4 GiB (plan_chunks' cap)
+inline size_t bfv_plain_sum_group(const RouteFacts &f, size_t count, size_t polys_per_ct) {
+  if (!polys_per_ct || !count) return count;
+  const size_t per_ct_bytes = polys_per_ct * (size_t)f.L * ((size_t)1 << f.logn) * 8;
+  const size_t cap = ((size_t)4 << 30) / per_ct_bytes;
+  const size_t group = cap ? cap : 1;
+  return group < count ? group : count;
+}
+// the BFV matvec by diagonals, baby-step giant-step: the baby rotations into an arena and ONE forward transform of the slabs, one
+// NTT-form inner sum per giant step (no forward transform at all), then addend + rotate(inner sum)
+struct BfvMatvecBsgsRoute {
+  RotRoute baby;
+  BfvPlainSum sum;     // of an inner sum over `group` ciphertexts
+  RotTailRoute giant;  // route_rotate_add, out of place
+};
+inline BfvMatvecBsgsRoute route_bfv_matvec_bsgs(const RouteFacts &f, size_t group) {
+  return {route_rotate(f, f.L, false), route_bfv_plain_sum(f, group), route_rotate_add(f, f.L, false)};
+}
+
 // ---- per chunk ----
 struct ChunkPlan {
   size_t chunk;
@@ -426,6 +467,23 @@ inline int format_matvec_bsgs(char *buf, size_t cap, const RouteFacts &f, int nl
   const MatvecBsgsRoute r = route_matvec_bsgs(f, nl);
   format_ks(ks, sizeof ks, f, r.baby.ks, nl, matvec_bsgs_group(f, nl, count, 1));  // per-chunk fields: those of the first group's first chunk
   const int n = snprintf(buf, cap, "%s %s macsum=%s add=%s", r.baby.fold ? "fold" : "permute", ks, r.macsum ? "kernel" : "per_term", r.giant.fused ? "fused" : "separate");
+  return n < 0 ? -1 : (size_t)n < cap ? n : -1;
+}
+// ABC_HIP_ROUTE_BFV_PLAIN_SUM (14) and ABC_HIP_ROUTE_BFV_MATVEC_BSGS (15), formatters of their own for the same reason.  14:
+// plainsum=fused / plainsum=ntt_domain for a call of `count` ciphertexts.  15: the baby rotation's route, the plainsum= of an inner
+// sum over the first group, the giant step's add=; per-chunk fields and the group: those of a one-step baby list.
+constexpr int kRouteBfvPlainSum = 14, kRouteBfvMatvecBsgs = 15;
+inline const char *name(BfvPlainSum s) { return s == BfvPlainSum::fused ? "fused" : "ntt_domain"; }
+inline int format_bfv_plain_sum(char *buf, size_t cap, const RouteFacts &f, size_t count) {
+  const int n = snprintf(buf, cap, "plainsum=%s", name(route_bfv_plain_sum(f, count)));
+  return n < 0 ? -1 : (size_t)n < cap ? n : -1;
+}
+inline int format_bfv_matvec_bsgs(char *buf, size_t cap, const RouteFacts &f, size_t count) {
+  char ks[80];
+  const size_t group = matvec_bsgs_group(f, f.L, count, 1);
+  const BfvMatvecBsgsRoute r = route_bfv_matvec_bsgs(f, group);
+  format_ks(ks, sizeof ks, f, r.baby.ks, f.L, group);
+  const int n = snprintf(buf, cap, "%s %s plainsum=%s add=%s", r.baby.fold ? "fold" : "permute", ks, name(r.sum), r.giant.fused ? "fused" : "separate");
   return n < 0 ? -1 : (size_t)n < cap ? n : -1;
 }
 

@@ -5,6 +5,7 @@
 
 #include "GraphCapable.hpp"
 #include "MulSumCapable.hpp"
+#include "PlainSumCapable.hpp"
 #include "RotateAddCapable.hpp"
 
 namespace {
@@ -300,6 +301,34 @@ size_t CircuitRuntime::productRun(std::vector<std::pair<std::string, std::string
   return span;
 }
 
+// A run `x *** p +++ y *** q (+++ ...)` at the current token: two or more products, joined by + / +++, each of one declared secret
+// variable and one declared non-secret variable, in either order, with nothing that binds tighter behind it -- productRun's
+// conditions.  -> the tokens the run spans and (secret, public) per product, else 0.
+size_t CircuitRuntime::plainProductRun(std::vector<std::pair<std::string, std::string>> &terms) const {
+  auto punct = [&](size_t k, const char *p) { return peek(k).kind == Token::Punct && peek(k).text == p; };
+  auto var = [&](size_t k, bool secret) {
+    if (peek(k).kind != Token::Ident) return false;
+    auto it = vars.find(peek(k).text);
+    if (it == vars.end() || it->second.secret != secret) return false;
+    return secret ? (bool)it->second.ctxt : (bool)it->second.clear;
+  };
+  size_t at = 0, span = 0;
+  for (;;) {
+    if (!(punct(at + 1, "***") || punct(at + 1, "*"))) break;
+    const bool secretFirst = var(at, true) && var(at + 2, false);
+    if (!secretFirst && !(var(at, false) && var(at + 2, true))) break;
+    bool tighter = false;
+    for (const char *p : {"*", "***", "/", "%", "[", "("}) tighter = tighter || punct(at + 3, p);
+    if (tighter) break;
+    terms.emplace_back(peek(secretFirst ? at : at + 2).text, peek(secretFirst ? at + 2 : at).text);
+    span = at + 3;
+    if (!(punct(at + 3, "+") || punct(at + 3, "+++"))) break;
+    at += 4;
+  }
+  if (terms.size() < 2) { terms.clear(); return 0; }
+  return span;
+}
+
 std::unique_ptr<AbstractValue> CircuitRuntime::additive() {
   std::unique_ptr<AbstractValue> lhs;
   {  // a sum of products on a backend that relinearises lazily: one MulSumCapable call for the whole run
@@ -311,6 +340,17 @@ std::unique_ptr<AbstractValue> CircuitRuntime::additive() {
       for (const auto &n : names) terms.emplace_back(vars.find(n.first)->second.ctxt.get(), vars.find(n.second)->second.ctxt.get());
       pos += span;
       lhs = lazy->mulSum(terms);
+    }
+  }
+  if (!lhs) {  // a sum of ciphertext-by-public-value products on a backend that sums them in one call: one PlainSumCapable call
+    std::vector<std::pair<std::string, std::string>> names;
+    const size_t span = plainProductRun(names);
+    auto fused = span ? dynamic_cast<const PlainSumCapable *>(vars.find(names[0].first)->second.ctxt.get()) : nullptr;
+    if (fused && fused->fusePlainSum()) {
+      PlainSumCapable::Terms terms;
+      for (const auto &n : names) terms.emplace_back(vars.find(n.first)->second.ctxt.get(), vars.find(n.second)->second.clear.get());
+      pos += span;
+      lhs = fused->plainSum(terms);
     }
   }
   if (!lhs) lhs = multiplicative();

@@ -92,6 +92,7 @@ class CircuitRuntime {
   std::unique_ptr<AbstractValue> additive();
   size_t plainRotateCall(size_t at, std::string &id, int &steps) const;
   size_t productRun(std::vector<std::pair<std::string, std::string>> &terms) const;
+  size_t plainProductRun(std::vector<std::pair<std::string, std::string>> &terms) const;
   std::unique_ptr<AbstractValue> multiplicative();
   std::unique_ptr<AbstractValue> primary();
   std::unique_ptr<AbstractValue> binary(const std::string &op, std::unique_ptr<AbstractValue> lhs,

@@ -246,7 +246,7 @@ void HipCiphertext::addRotatedInplace(const AbstractCiphertext &src, int steps) 
 
 bool HipCiphertext::lazyRelinearize() const { return getFactory().lazyRelinearizes(); }
 
-std::unique_ptr<AbstractCiphertext> HipCiphertext::mulSum(const Terms &terms) const {
+std::unique_ptr<AbstractCiphertext> HipCiphertext::mulSum(const MulSumCapable::Terms &terms) const {
   const auto &f = getFactory();
   bool one_level = !terms.empty();
   for (const auto &t : terms) one_level = one_level && cast(*t.first).nl == nl && cast(*t.second).nl == nl;
@@ -270,6 +270,42 @@ std::unique_ptr<AbstractCiphertext> HipCiphertext::mulSum(const Terms &terms) co
     r->sc = scale;
     r->checkScaleFits(r->sc, r->nl);
     r->rescaleIfPossible();
+  }
+  return r;
+}
+
+bool HipCiphertext::fusePlainSum() const { return getFactory().fusesPlainSum() && !getFactory().isCkks(); }
+
+std::unique_ptr<AbstractCiphertext> HipCiphertext::plainSum(const PlainSumCapable::Terms &terms) const {
+  const auto &f = getFactory();
+  if (terms.empty()) throw std::runtime_error("plainSum: no terms");
+  bool one_call = fusePlainSum();
+  for (const auto &t : terms) {
+    if (!one_call) break;
+    one_call = !intCleartext(*t.second, "MULTIPLY").allEqual(-1) && cast(*t.first).nl == nl;  // -1: multiplyPlain negates instead
+  }
+  if (!one_call) {  // the calls per term, as the interpreter issues them
+    auto r = terms[0].first->multiplyPlain(*terms[0].second);
+    for (size_t k = 1; k < terms.size(); ++k) r->addInplace(*terms[k].first->multiplyPlain(*terms[k].second));
+    return r;
+  }
+  // at most plainCacheEntries() terms per call, so that a slice's plaintexts fit the cache together; `held` keeps every block of the
+  // slice alive until the call is enqueued, whatever a later miss of the same slice evicts (a hit on the oldest entry followed by a
+  // miss on a full cache would otherwise free the block just gathered).  A later slice takes the sum so far as its addend
+  auto r = fresh(nl);
+  for (size_t k0 = 0; k0 < terms.size(); k0 += f.plainCacheEntries()) {
+    const size_t k1 = std::min(terms.size(), k0 + f.plainCacheEntries());
+    std::vector<const uint64_t *> a, p;
+    std::vector<std::shared_ptr<const HipCiphertextFactory::DeviceBlock>> held;
+    for (size_t k = k0; k < k1; ++k) {
+      a.push_back(cast(*terms[k].first).in());
+      held.push_back(f.cachedPlaintextNtt(intCleartext(*terms[k].second, "MULTIPLY").getData()));
+      p.push_back(held.back()->p);
+    }
+    abcHipCheck(abc_hip_bfv_multiply_plain_sum(f.context(), a.data(), ABC_HIP_CT_COEFF, p.data(), 0, (int)a.size(), k0 ? r->buf->p : nullptr,
+                                               r->buf->p, 2, f.batchSize()),
+                "bfv_multiply_plain_sum");
+    f.countPlainSum();
   }
   return r;
 }

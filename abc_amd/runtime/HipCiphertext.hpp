@@ -13,9 +13,10 @@
 
 #include "HipCiphertextFactory.hpp"
 #include "MulSumCapable.hpp"
+#include "PlainSumCapable.hpp"
 #include "RotateAddCapable.hpp"
 
-class HipCiphertext : public AbstractCiphertext, public RotateAddCapable, public MulSumCapable {
+class HipCiphertext : public AbstractCiphertext, public RotateAddCapable, public MulSumCapable, public PlainSumCapable {
   // Device buffer [B][2][L][N] (B = the factory's batch size, 1 by default), shared copy-on-write: clone() and the
   // copy constructor only take another reference (the interpreter clones on EVERY variable read,
   // src/runtime/RuntimeVisitor.cpp:431-437, and most clones are only ever read), and an in-place operation on a shared
@@ -96,7 +97,12 @@ class HipCiphertext : public AbstractCiphertext, public RotateAddCapable, public
   // rescale a product gets).  Every term must sit at this value's level and, under CKKS, have the first product's scale
   // (checkScales); terms at different levels take multiply + addInplace per term, which bring them together.
   bool lazyRelinearize() const override;
-  std::unique_ptr<AbstractCiphertext> mulSum(const Terms &terms) const override;
+  std::unique_ptr<AbstractCiphertext> mulSum(const MulSumCapable::Terms &terms) const override;
+  // PlainSumCapable, BFV only: the sum of the products as abc_hip_bfv_multiply_plain_sum over the operands' buffers and the factory's
+  // cached NTT-form plaintexts, into a fresh buffer -- the words of multiplyPlain per term and addInplace.  A term whose public value
+  // is all -1 (multiplyPlain negates there), CKKS and the option off take those calls per term.
+  bool fusePlainSum() const override;
+  std::unique_ptr<AbstractCiphertext> plainSum(const PlainSumCapable::Terms &terms) const override;
   std::unique_ptr<AbstractCiphertext> clone() const override;
 
   void add_inplace(const AbstractValue &other) override;

@@ -19,7 +19,7 @@ HipCiphertextFactory::HipCiphertextFactory(unsigned int numElementsPerCiphertext
 HipCiphertextFactory::HipCiphertextFactory(const HipSchemeConfig &cfg)
     : ciphertextSlotSize(cfg.ringDegree), keySeed(cfg.seed), batch(cfg.batch), ckksMode(cfg.ckks), ckksScale(cfg.ckksScale),
       ckksBits(cfg.ckksBits), hostCkksCodec(cfg.hostCkksCodec), fuseRotateAdd(cfg.fuseRotateAdd),
-      fuseMultiplyPlainRescale(cfg.fuseMultiplyPlainRescale), lazyRelin(cfg.lazyRelinearize) {
+      fuseMultiplyPlainRescale(cfg.fuseMultiplyPlainRescale), lazyRelin(cfg.lazyRelinearize), fusePlainSums(cfg.fusePlainSum) {
   if (!batch) throw std::runtime_error("HipCiphertextFactory: batch size must be at least 1");
   if (ckksMode && ckksBits.size() < 2) throw std::runtime_error("HipCiphertextFactory: a CKKS chain needs a data limb and the special prime");
   setupContext(cfg.device);
@@ -41,6 +41,7 @@ void HipCiphertextFactory::queueBatchedInput(std::vector<std::vector<int64_t>> p
 
 HipCiphertextFactory::~HipCiphertextFactory() {
   for (auto &e : plainCache) abc_hip_free(ctx, e.d_plain);
+  plainNttCache.clear();  // the blocks go with their last holder: nobody else holds one past a call
   for (auto &e : ckksPlainCache) abc_hip_free(ctx, e.d_plain);
   abc_hip_ctx_destroy(ctx);
 }
@@ -55,6 +56,26 @@ const uint64_t *HipCiphertextFactory::cachedPlaintext(const std::vector<int> &va
   }
   plainCache.push_back(CachedPlain{key, createPlaintext(key)});
   return plainCache.back().d_plain;
+}
+
+HipCiphertextFactory::DeviceBlock::~DeviceBlock() { abc_hip_free(ctx, p); }
+
+std::shared_ptr<const HipCiphertextFactory::DeviceBlock> HipCiphertextFactory::cachedPlaintextNtt(const std::vector<int> &value) const {
+  const std::vector<int64_t> key(value.begin(), value.end());
+  for (auto it = plainNttCache.begin(); it != plainNttCache.end(); ++it)
+    if (it->values == key) {  // a hit moves to the back: the entries a caller has just gathered are the last to go
+      CachedNttPlain e = std::move(*it);
+      plainNttCache.erase(it);
+      plainNttCache.push_back(std::move(e));
+      return plainNttCache.back().block;
+    }
+  const uint64_t *plain = cachedPlaintext(value);  // [N] modulo t; read by the transform below before anything can evict it
+  if (plainNttCache.size() >= kPlainCacheEntries) plainNttCache.pop_front();  // frees the block unless a caller still holds it
+  void *p = nullptr;
+  abcHipCheck(abc_hip_malloc(ctx, &p, (size_t)limbs * ciphertextSlotSize * 8), "plaintext allocation");
+  plainNttCache.push_back(CachedNttPlain{key, std::make_shared<const DeviceBlock>(ctx, static_cast<uint64_t *>(p))});
+  abcHipCheck(abc_hip_bfv_plain_to_ntt(ctx, plain, static_cast<uint64_t *>(p), 1), "bfv_plain_to_ntt");
+  return plainNttCache.back().block;
 }
 
 void HipCiphertextFactory::setupContext(int device) {

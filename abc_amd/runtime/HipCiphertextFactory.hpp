@@ -6,6 +6,7 @@
 #pragma once
 
 #include <deque>
+#include <memory>
 #include <iosfwd>
 #include <string>
 #include <vector>
@@ -41,6 +42,13 @@ struct HipSchemeConfig {
   // of the size-3 products is relinearised once.  OFF by default: the result decrypts to the same values, with one key switch's
   // noise instead of one per product, but its words are not those of the per-product sequence
   bool lazyRelinearize = false;
+  // BFV `x *** p +++ y *** q (+++ ...)` as ONE abc_hip_bfv_multiply_plain_sum (HipCiphertext::plainSum; CircuitRuntime recognises the
+  // run): one inverse transform for the sum, public values transformed once and cached.  The words are those of multiplyPlain per
+  // product and addInplace, so it stays on; off is for A/B runs and tests.  CKKS never fuses (multiplyPlain rescales per product)
+  // Recorded circuits: a recording holds the device pointers of the cached plaintexts it was recorded with (up to 32 per plainSum
+  // node; plainCache's single pointers likewise).  Public values used between compile and the last replay must not push those out of
+  // the 32-entry caches: a program that cycles through more distinct public values than that replays recordings before it does
+  bool fusePlainSum = true;
 };
 
 class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapable {
@@ -62,6 +70,25 @@ class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapab
   };
   mutable std::deque<CachedPlain> plainCache;
   static constexpr size_t kPlainCacheEntries = 32;
+  // The same operands lifted and in NTT form, [L][N] (abc_hip_bfv_plain_to_ntt), least recently used first.  An entry's block is
+  // shared with whoever asked for it: HipCiphertext::plainSum gathers up to kPlainCacheEntries of them before its one call, and an
+  // eviction by a later miss of the same gathering must not free a block gathered earlier -- the block goes when its last holder does
+ public:
+  struct DeviceBlock {
+    abc_hip_ctx *ctx;
+    uint64_t *p;
+    DeviceBlock(abc_hip_ctx *c, uint64_t *ptr) : ctx(c), p(ptr) {}
+    DeviceBlock(const DeviceBlock &) = delete;
+    DeviceBlock &operator=(const DeviceBlock &) = delete;
+    ~DeviceBlock();  // abc_hip_free: stream-ordered, so every call enqueued before this point has its operand
+  };
+
+ private:
+  struct CachedNttPlain {
+    std::vector<int64_t> values;
+    std::shared_ptr<const DeviceBlock> block;
+  };
+  mutable std::deque<CachedNttPlain> plainNttCache;
 
   // CKKS policy (empty / unused for BFV)
   bool ckksMode = false;
@@ -78,6 +105,8 @@ class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapab
   mutable size_t fusedMultiplyPlainRescales = 0;  // abc_hip_multiply_plain_rescale calls issued by multiplyPlainInplace
   bool lazyRelin = false;
   mutable size_t lazyMulSums = 0;  // abc_hip_mul_sum_relin calls issued by HipCiphertext::mulSum
+  bool fusePlainSums = true;
+  mutable size_t plainSums = 0;  // abc_hip_bfv_multiply_plain_sum calls issued by HipCiphertext::plainSum
   struct CachedCkksPlain {
     std::vector<double> values;
     int level;
@@ -121,6 +150,14 @@ class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapab
   void setLazyRelinearize(bool on) { lazyRelin = on; }
   [[nodiscard]] size_t mulSumCalls() const { return lazyMulSums; }
   void countMulSum() const { ++lazyMulSums; }
+  [[nodiscard]] bool fusesPlainSum() const { return fusePlainSums; }
+  void setFusePlainSum(bool on) { fusePlainSums = on; }
+  [[nodiscard]] size_t plainSumCalls() const { return plainSums; }
+  void countPlainSum() const { ++plainSums; }
+  [[nodiscard]] static constexpr size_t plainCacheEntries() { return kPlainCacheEntries; }
+  // BFV: device plaintext [L][N], lifted and in NTT form, of public values, from the factory's cache (least recently used out
+  // first).  The block lives as long as the cache or the caller holds it: hold it until the call that reads it has been enqueued
+  std::shared_ptr<const DeviceBlock> cachedPlaintextNtt(const std::vector<int> &value) const;
   [[nodiscard]] double defaultScale() const { return ckksScale; }
   // CKKS: largest relative difference between the scales of two addends that is drift, not a mismatch
   [[nodiscard]] double scaleTolerance() const { return ckksScaleTol; }

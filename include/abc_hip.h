@@ -78,6 +78,8 @@ int abc_hip_ctx_reload_env(abc_hip_ctx *ctx);
 #define ABC_HIP_ROUTE_MULTIPLY_PLAIN_RESCALE 10 /* CKKS, nl >= 2: the rescale's route plus mulplain=fused / mulplain=separate (8 and 9 are unassigned) */
 #define ABC_HIP_ROUTE_MUL_SUM_RELIN 12 /* relinearize(sum of products): the key switch's route plus tensor=sum / tensor=per_term; per-chunk fields: the first group's (11 is unassigned) */
 #define ABC_HIP_ROUTE_DIAG_MATVEC_BSGS 13 /* CKKS: the baby rotation's route (as ABC_HIP_ROUTE_ROTATE, out of place), macsum=kernel / macsum=per_term, then the giant step's add=fused / add=separate; per-chunk fields: the first group's */
+#define ABC_HIP_ROUTE_BFV_PLAIN_SUM 14 /* BFV: plainsum=fused / plainsum=ntt_domain for abc_hip_bfv_multiply_plain_sum of `count` ciphertexts */
+#define ABC_HIP_ROUTE_BFV_MATVEC_BSGS 15 /* BFV: the baby rotation's route (as ABC_HIP_ROUTE_ROTATE, out of place), the plainsum= of an inner sum, then the giant step's add=fused / add=separate; per-chunk fields and the group: those of a one-step baby list */
 int abc_hip_route(abc_hip_ctx *ctx, int op, int nl, size_t count, int in_place, char *buf, size_t cap);
 
 /* ---- device memory (so that FFI callers need no HIP runtime binding) ----
@@ -314,6 +316,49 @@ int abc_hip_rotate_plain(abc_hip_ctx *ctx, const uint64_t *d_plain, uint64_t *d_
  * with nothing written.  The step lists are read during the call only.  Capturable like abc_hip_rotate_add. */
 int abc_hip_diag_matvec_bsgs(abc_hip_ctx *ctx, const uint64_t *d_in, const uint64_t *d_diags, size_t diag_stride, const int *h_baby,
                              int n_baby, const int *h_giant, int n_giant, uint64_t *d_out, int nl, size_t count);
+/* ---- BFV: plaintext-weighted sums with ONE inverse transform ----
+ * A BFV Evaluator::multiply_plain (:159,:196) is INTT(NTT(ct) (.) NTT(lift(plain))) per limb.  The inverse transform is linear and
+ * every step is exact modulo q_i, so a weighted sum is accumulated in NTT form and inverted once, with weights transformed once. */
+/* Evaluator::transform_to_ntt(plain): d_plain [rows][N] mod t -> d_plain_ntt [rows][L][N]: the lift multiply_plain applies
+ * (values of (t + 1) / 2 and above move up by q_i - t) and the forward transform per data limb.  BFV only; d_plain_ntt must not
+ * overlap d_plain; rows == 0 enqueues nothing.  Capturable. */
+int abc_hip_bfv_plain_to_ntt(abc_hip_ctx *ctx, const uint64_t *d_plain, uint64_t *d_plain_ntt, size_t rows);
+#define ABC_HIP_CT_COEFF 0 /* terms as BFV ciphertexts travel everywhere else */
+#define ABC_HIP_CT_NTT 1   /* terms already transformed limb by limb (abc_hip_ntt_limbs, nl = L): Evaluator::transform_to_ntt_inplace */
+/* BFV only: replaces n_terms x Evaluator::multiply_plain (:159,:196) and n_terms x Evaluator::add (:92,:114):
+ *   d_out [count][size][L][N], coefficient form = (d_addend or 0) + plain_0 * ct_0 + ... + plain_{K-1} * ct_{K-1},  size = 2 or 3.
+ * h_ct, h_plain_ntt: HOST arrays of n_terms device pointers, read during the call only; ct_k is [count][size][L][N] in the form
+ * ct_form says, plain_k in NTT form as abc_hip_bfv_plain_to_ntt writes it: [L][N] for the whole batch (plain_stride 0) or
+ * [count][L][N] (plain_stride L * N).  One pointer may appear in several terms.  d_addend == NULL: no addend; d_out may be exactly
+ * d_addend; addend and output are always coefficient form.  With ct_form == ABC_HIP_CT_COEFF the result is bit-identical to
+ * abc_hip_multiply_plain per term and abc_hip_add in any order, and n_terms == 1 gives the words of abc_hip_multiply_plain: the sums
+ * are exact and canonical.  Route (abc_hip_route, ABC_HIP_ROUTE_BFV_PLAIN_SUM): plainsum=fused -- rings 2^10 .. 2^14 with every
+ * data prime below 2^50: one kernel transforms the terms of a limb in LDS, sums the products in registers and inverts once; the
+ * term pointers travel in the kernel's arguments, eight per launch, and an NTT-domain partial sum in a context arena connects the
+ * launches -- or plainsum=ntt_domain -- N >= 2^15, a prime of 2^50 or above, ABC_HIP_NO_FUSED=1, and at N = 2^14 a batch of at most
+ * 48 limbs (count * 2 * L): stand-alone transforms into an arena, the K-term kernel of abc_hip_multiply_plain_sum, one inverse
+ * transform, one add.  With ABC_HIP_CT_NTT neither route runs a forward transform.  The batch is walked in groups that keep the
+ * arenas within 4 GiB.  n_terms == 0 writes the addend, or zeros without one; count == 0 succeeds and enqueues nothing.  Fails with
+ * nothing written or enqueued for: a CKKS context, a size other than 2 or 3, a stride other than 0 or L * N, a ct_form other than
+ * 0 or 1, n_terms < 0, a null term pointer, d_out overlapping any ct_k or plain_k, d_out overlapping d_addend without being equal
+ * to it.  Capturable, under the "run once eagerly first" rule of abc_hip_graph_begin. */
+int abc_hip_bfv_multiply_plain_sum(abc_hip_ctx *ctx, const uint64_t *const *h_ct, int ct_form, const uint64_t *const *h_plain_ntt,
+                                   size_t plain_stride /* 0 or L*N */, int n_terms, const uint64_t *d_addend, uint64_t *d_out,
+                                   int size, size_t count);
+/* BFV only: abc_hip_diag_matvec_bsgs for BFV ciphertexts (Evaluator::rotate_rows :55,:60, multiply_plain :159,:196, add :92,:114):
+ *   d_out = sum over j of rotate( sum over i of D[j * n_baby + i] * rotate(d_in, h_baby[i]),  h_giant[j] ),  [count][2][L][N].
+ * Row (j, i) of D starts at d_diags_ntt + (j * n_baby + i) * diag_stride, diag_stride >= L * N, in NTT form
+ * (abc_hip_bfv_plain_to_ntt); one set for the batch.  THE CALLER SUPPLIES ROWS ALREADY ROTATED BY -h_giant[j]: encode the
+ * cleartext diagonal of step h_giant[j] + h_baby[i] with each half-row rolled by -h_giant[j], so no plaintext-rotation entry is
+ * needed.  Sequence: the baby rotations as abc_hip_rotate runs them, into an arena; ONE in-place forward transform of all baby
+ * slabs (step 0 gets a transformed copy: d_in stays untouched); per giant step one abc_hip_bfv_multiply_plain_sum with
+ * ABC_HIP_CT_NTT terms -- no forward transform -- into a second arena; then d_out = d_out + rotate(inner_j, h_giant[j]) as
+ * abc_hip_rotate_add does, fused where its route says so.  Bit-identical to that sequence of calls.  Order, duplicates, groups,
+ * empty lists and count == 0 as in abc_hip_diag_matvec_bsgs.  Every step and every key is checked before the first launch; a CKKS
+ * context, a bad stride, a negative count, a null step list, a null d_in, d_out or d_diags_ntt, a step without a key (or a NAF chain of keys), d_out overlapping d_in
+ * or d_diags_ntt fail the call with nothing written.  Route: ABC_HIP_ROUTE_BFV_MATVEC_BSGS.  Capturable like abc_hip_rotate_add. */
+int abc_hip_bfv_diag_matvec_bsgs(abc_hip_ctx *ctx, const uint64_t *d_in, const uint64_t *d_diags_ntt, size_t diag_stride /* >= L*N */,
+                                 const int *h_baby, int n_baby, const int *h_giant, int n_giant, uint64_t *d_out, size_t count);
 /* The three plaintext operations.  d_out may be d_ct (the reference's *_inplace call sites); size = 2 or 3.
  * plain_stride, in words, is the distance from ciphertext i's plaintext to ciphertext i + 1's:
  *   0            one plaintext, broadcast to the batch (d_plain holds N words for BFV, nl * N for CKKS);

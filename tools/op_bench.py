@@ -366,6 +366,113 @@ def matvec_bsgs_ab(res, only, rng):
         g.close()
 
 
+def _rounds(g, res, names, fns, routes, B, reps, extra=None):
+    """fns[0], fns[1], ..., fns[0], ...: five runs each in one process.  The first run of EVERY variant sizes its arenas and is left
+    out of its minimum, median and ratio (it is still printed, first in its row)."""
+    runs = {k: [] for k in names}
+    for _ in range(5):
+        for k, fn in zip(names, fns):
+            runs[k].append(timeit(g, fn, reps))
+    for i, (k, ms) in enumerate(runs.items()):
+        kept = ms[1:]
+        res[k] = {"batch": B, "ms": min(kept), "ms_median": sorted(kept)[len(kept) // 2], "ms_runs": ms, "route": routes[i]}
+        res[k].update(extra[i] if extra else {})
+        print("%-52s %s ms / %d  (%s)%s" % (k, " ".join("%8.3f" % v for v in ms), B, routes[i], "  %s" % extra[i] if extra else ""), flush=True)
+    base = res[names[0]]["ms_median"]
+    print("    composed / new call: " + ", ".join("%.2f" % (base / res[k]["ms_median"]) for k in names[1:]), flush=True)
+
+
+def bfv_plain_sum_ab(res, only, rng):
+    """BFV: sum over K terms of plain_k * ct_k, one plaintext per term for the batch, alternating in one process, five runs each:
+    (a) `composed`: K x abc_hip_multiply_plain (plaintexts modulo t: lifted and transformed on every call) and K - 1 x abc_hip_add;
+    (b) `sum_coeff`: abc_hip_bfv_multiply_plain_sum on coefficient-form terms, plaintexts transformed once beforehand;
+    (c) `sum_ntt`: the same call on terms already in NTT form (the inner sum of the matvec)."""
+    def chain15():
+        n = 32768
+        return capi.Context(capi.BFV, n, capi.create_primes(n, [55] * 16), capi.plain_modulus_batching(n, 20))
+    shapes = [("bfv16384", lambda: capi.Context.bfv_default(16384), 256), ("bfv8192", lambda: capi.Context.bfv_default(8192), 512),
+              ("bfv4096", lambda: capi.Context.bfv_default(4096), 1024), ("bfv32768x15", chain15, 64)]
+    kinds = ("composed", "sum_coeff", "sum_ntt")
+    for tag, make, B in shapes:
+        if only and only not in "%s_bfv_plain_sum" % tag and "bfv_plain_sum" not in only:
+            continue
+        g = make()
+        L, cb, zero = g.L, C.c_size_t(B), C.c_size_t(0)
+        first, nb = rand_ct(g, rng, B, 2, L)
+        pool = [first]
+        for _ in range(15):
+            pool.append(g.alloc(nb))
+            g.op("memcpy_d2d", pool[-1].ptr, first.ptr, C.c_size_t(nb))
+        plains = g.upload(rng.integers(0, g.t, size=(16, g.n), dtype=np.uint64))
+        plains_ntt = g.alloc(16 * L * g.n * 8)
+        g.op("bfv_plain_to_ntt", plains.ptr, plains_ntt.ptr, C.c_size_t(16))
+        tmp, out = g.alloc(nb), g.alloc(nb)
+        for K in (2, 4, 8, 16):
+            names = ["%s_b%d_bfv_plain_sum_K%d_%s" % (tag, B, K, kind) for kind in kinds]
+            if not any(only in k for k in names):
+                continue
+            pm = [C.c_void_p(plains.ptr.value + 8 * k * g.n) for k in range(K)]
+            pc = g.term_pointers([x.ptr for x in pool[:K]])
+            pp = g.term_pointers([C.c_void_p(plains_ntt.ptr.value + 8 * k * L * g.n) for k in range(K)])
+
+            def composed():
+                g.op("multiply_plain", pool[0].ptr, pm[0], zero, out.ptr, 2, L, cb)
+                for k in range(1, K):
+                    g.op("multiply_plain", pool[k].ptr, pm[k], zero, tmp.ptr, 2, L, cb)
+                    g.op("add", out.ptr, tmp.ptr, out.ptr, 2, L, cb)
+
+            def sum_coeff():
+                g.op("bfv_multiply_plain_sum", pc, 0, pp, zero, K, None, out.ptr, 2, cb)
+
+            def sum_ntt():
+                g.op("bfv_multiply_plain_sum", pc, 1, pp, zero, K, None, out.ptr, 2, cb)
+            route = g.route("bfv_plain_sum", L, B)
+            _rounds(g, res, names, (composed, sum_coeff, sum_ntt), ("composed", route, route), B, 5)
+        del pool, first, plains, plains_ntt, tmp, out
+        g.close()
+
+
+def bfv_matvec_bsgs_ab(res, only, rng):
+    """BFV: a matrix of n diagonals times a batch of ciphertexts: n x (abc_hip_rotate, abc_hip_multiply_plain, abc_hip_add) against
+    abc_hip_bfv_diag_matvec_bsgs on a square grid (16 = 4 x 4, 64 = 8 x 8), alternating in one process, five runs each.  The default
+    key set on both sides, so both pay NAF chains; the key switches of each side are printed with its time."""
+    shapes = [("bfv16384", lambda: capi.Context.bfv_default(16384), 256), ("bfv8192", lambda: capi.Context.bfv_default(8192), 512)]
+    kinds = ("composed", "bsgs")
+    for tag, make, B in shapes:
+        if only and only not in "%s_bfv_matvec_bsgs" % tag and "bfv_matvec_bsgs" not in only:
+            continue
+        g = make()
+        g.keygen(1)
+        L, cb, zero = g.L, C.c_size_t(B), C.c_size_t(0)
+        a, nb = rand_ct(g, rng, B, 2, L)
+        plains = g.upload(rng.integers(0, g.t, size=(64, g.n), dtype=np.uint64))
+        d = g.alloc(64 * L * g.n * 8)
+        g.op("bfv_plain_to_ntt", plains.ptr, d.ptr, C.c_size_t(64))
+        rot, tmp, out = g.alloc(nb), g.alloc(nb), g.alloc(nb)
+        for side in (4, 8):
+            n = side * side
+            names = ["%s_b%d_bfv_matvec_bsgs_%dx%d_%s" % (tag, B, side, side, kind) for kind in kinds]
+            if not any(only in k for k in names):
+                continue
+            steps, baby, giant = list(range(n)), list(range(side)), [side * j for j in range(side)]
+            c_baby, c_giant = (C.c_int * side)(*baby), (C.c_int * side)(*giant)
+            pm = [C.c_void_p(plains.ptr.value + 8 * k * g.n) for k in range(n)]
+
+            def composed():
+                g.op("multiply_plain", a.ptr, pm[0], zero, out.ptr, 2, L, cb)
+                for s in steps[1:]:
+                    g.op("rotate", a.ptr, rot.ptr, L, s, cb)
+                    g.op("multiply_plain", rot.ptr, pm[s], zero, tmp.ptr, 2, L, cb)
+                    g.op("add", out.ptr, tmp.ptr, out.ptr, 2, L, cb)
+
+            def bsgs():
+                g.op("bfv_diag_matvec_bsgs", a.ptr, d.ptr, C.c_size_t(L * g.n), c_baby, side, c_giant, side, out.ptr, cb)
+            extra = ({"key_switches": _key_switches(g, steps)}, {"key_switches": _key_switches(g, baby) + _key_switches(g, giant)})
+            _rounds(g, res, names, (composed, bsgs), (g.route("rotate", L, B), g.route("bfv_matvec_bsgs", L, B)), B, 2, extra)
+        del a, plains, d, rot, tmp, out
+        g.close()
+
+
 def keyswitch_batch1(res, only, rng):
     """one ciphertext per call at nl = 4: relinearise, rotate, rotate_add and rotate_mac_plain (one plaintext, one addend) on the two
     CKKS split rings -- the calls in which the host side of the key switch (routes, operand record, launches) is the largest share"""
@@ -536,15 +643,22 @@ def main():
     only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else ""
     res = {}
     rng = np.random.default_rng(0)
-    if not (only and any(x in only for x in ("mul_sum", "plain_mac_sum", "matvec_bsgs"))):  # those A/Bs have their own contexts and operand batches: nothing else is set up
-        single_ops(res, only, rng)
-    rotate_add_ab(res, only, rng)
-    rotate_mac_ab(res, only, rng)
-    mulplain_rescale_ab(res, only, rng)
-    mul_sum_ab(res, only, rng)
-    plain_mac_sum_ab(res, only, rng)
-    matvec_bsgs_ab(res, only, rng)
-    keyswitch_batch1(res, only, rng)
+    # the BFV plaintext-sum A/Bs are named by a prefix of their own, "bfv_plain_sum" / "bfv_matvec_bsgs": a filter that names one of them
+    # runs nothing else (and sets up no other context), and a filter that does not say "bfv_" -- `--only matvec_bsgs` -- leaves them out
+    bfv_sums = any(x in only for x in ("bfv_plain_sum", "bfv_matvec_bsgs"))
+    if not bfv_sums:
+        if not (only and any(x in only for x in ("mul_sum", "plain_mac_sum", "matvec_bsgs"))):  # those A/Bs have their own contexts and operand batches: nothing else is set up
+            single_ops(res, only, rng)
+        rotate_add_ab(res, only, rng)
+        rotate_mac_ab(res, only, rng)
+        mulplain_rescale_ab(res, only, rng)
+        mul_sum_ab(res, only, rng)
+        plain_mac_sum_ab(res, only, rng)
+        matvec_bsgs_ab(res, only, rng)
+        keyswitch_batch1(res, only, rng)
+    if not only or "bfv_" in only:
+        bfv_plain_sum_ab(res, only, rng)
+        bfv_matvec_bsgs_ab(res, only, rng)
     os.makedirs("gpurun_out", exist_ok=True)
     json.dump(res, open("gpurun_out/op_bench.json", "w"), indent=1)
 
