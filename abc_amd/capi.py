@@ -42,6 +42,7 @@ SYMBOLS = [
     "abc_hip_multiply_sum", "abc_hip_mul_sum_relin",
     "abc_hip_multiply_plain_sum", "abc_hip_rotate_plain", "abc_hip_diag_matvec_bsgs",
     "abc_hip_bfv_plain_to_ntt", "abc_hip_bfv_multiply_plain_sum", "abc_hip_bfv_diag_matvec_bsgs",
+    "abc_hip_multiply_plain_sum_rescale", "abc_hip_diag_matvec_bsgs_rescale",
 ]
 
 
@@ -92,6 +93,9 @@ def lib():
                                                          C.c_void_p, C.c_void_p, C.c_int, C.c_size_t]
             L.abc_hip_bfv_diag_matvec_bsgs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int), C.c_int,
                                                        C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_size_t]
+        if hasattr(L, "abc_hip_multiply_plain_sum_rescale"):
+            L.abc_hip_multiply_plain_sum_rescale.argtypes = L.abc_hip_multiply_plain_sum.argtypes
+            L.abc_hip_diag_matvec_bsgs_rescale.argtypes = L.abc_hip_diag_matvec_bsgs.argtypes
         L.abc_hip_encrypt_keyed.argtypes =[C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_size_t]
         L.abc_hip_keygen_keyed.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
         L.abc_hip_keyed_small.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_size_t]
@@ -223,11 +227,11 @@ class Context:
 
     ROUTE_OPS = {"mul_relin": 0, "keyswitch": 1, "relinearize": 1, "rotate": 2, "rescale": 3, "multiply": 4, "rotate_add": 5,
                  "rotate_mac_plain": 7, "multiply_plain_rescale": 10, "mul_sum_relin": 12, "diag_matvec_bsgs": 13,
-                 "bfv_plain_sum": 14, "bfv_matvec_bsgs": 15}
+                 "bfv_plain_sum": 14, "bfv_matvec_bsgs": 15, "plain_sum_rescale": 16, "diag_matvec_bsgs_rescale": 17}
 
     def route(self, op, nl, count=1, in_place=False):
         """the kernel sequence such a call takes, as the string of abc_route.hpp's formatter"""
-        buf = C.create_string_buffer(128)
+        buf = C.create_string_buffer(192)
         _chk(lib().abc_hip_route(self.h, self.ROUTE_OPS.get(op, op), nl, count, int(in_place), buf, len(buf)))
         return buf.value.decode()
 
@@ -494,6 +498,15 @@ class Context:
         """(addend or 0) + sum over k of plains[k] (.) cts[k] as one call (abc_hip_multiply_plain_sum), CKKS.  cts[k]: [count][size][nl][N]
         (or one ciphertext); plains: all [nl][N], one per term for the batch, or all [count][rows >= nl][N], one per ciphertext.
         size / nl / count: the shape of an empty sum without an addend"""
+        return self._plain_sum("multiply_plain_sum", 0, cts, plains, addend, size, nl, count)
+
+    def multiply_plain_sum_rescale(self, cts, plains, addend=None, size=2, nl=None, count=1):
+        """rescale((addend or 0) + sum over k of plains[k] (.) cts[k]) as one call (abc_hip_multiply_plain_sum_rescale), CKKS: operands as
+        multiply_plain_sum takes them, the result [count][size][nl - 1][N].  The sum of the last terms is formed in the rescale's loads
+        where route("plain_sum_rescale") says so"""
+        return self._plain_sum("multiply_plain_sum_rescale", 1, cts, plains, addend, size, nl, count)
+
+    def _plain_sum(self, name, drop, cts, plains, addend, size, nl, count):
         if len(cts) != len(plains):
             raise ValueError("as many plaintexts as ciphertexts")
         c4 = [self._batch(x, 3) for x in cts]
@@ -512,13 +525,13 @@ class Context:
             if id(orig) not in bufs:
                 bufs[id(orig)] = self.upload(arr)
         ab = self.upload(a4) if a4 is not None else None
-        out = self.alloc(max(int(np.prod(shape)) * 8, 8))
+        oshape = (shape[0], shape[1], shape[2] - drop, shape[3])
+        out = self.alloc(max(int(np.prod(oshape)) * 8, 8))
         try:
             pc = self.term_pointers([bufs[id(x)].ptr for x in cts])
             pp = self.term_pointers([bufs[id(x)].ptr for x in plains])
-            self.op("multiply_plain_sum", pc, pp, C.c_size_t(stride), len(c4), ab.ptr if ab else None, out.ptr, shape[1], shape[2],
-                    C.c_size_t(shape[0]))
-            r = self.download(out, shape)
+            self.op(name, pc, pp, C.c_size_t(stride), len(c4), ab.ptr if ab else None, out.ptr, shape[1], shape[2], C.c_size_t(shape[0]))
+            r = self.download(out, oshape)
         finally:
             for b in list(bufs.values()) + [out] + ([ab] if ab else []):
                 b.free()
@@ -546,17 +559,26 @@ class Context:
     def diag_matvec_bsgs(self, ct, bsgs_diags, baby, giant):
         """sum over j of rotate(sum over i of bsgs_diags[j * len(baby) + i] (.) rotate(ct, baby[i]), giant[j]) (abc_hip_diag_matvec_bsgs),
         CKKS; bsgs_diags [len(giant) * len(baby)][rows >= nl][N] as bsgs_diagonals makes them, one set for the batch"""
+        return self._matvec_bsgs("diag_matvec_bsgs", 0, ct, bsgs_diags, baby, giant)
+
+    def diag_matvec_bsgs_rescale(self, ct, bsgs_diags, baby, giant):
+        """the same with every inner sum rescaled before its giant rotation (abc_hip_diag_matvec_bsgs_rescale): the giant steps' key
+        switches run at nl - 1 limbs and the result, [count][2][nl - 1][N], arrives rescaled"""
+        return self._matvec_bsgs("diag_matvec_bsgs_rescale", 1, ct, bsgs_diags, baby, giant)
+
+    def _matvec_bsgs(self, name, drop, ct, bsgs_diags, baby, giant):
         a4 = self._batch(ct, 3)
         baby, giant = [int(x) for x in baby], [int(x) for x in giant]
         rows = len(baby) * len(giant)
         d = np.ascontiguousarray(bsgs_diags, dtype=np.uint64).reshape(rows, -1, self.n) if rows else np.zeros((0, a4.shape[2], self.n), np.uint64)
         ab, ag = (C.c_int * max(len(baby), 1))(*baby), (C.c_int * max(len(giant), 1))(*giant)
         cb, db = self.upload(a4), self.upload(d if d.size else np.zeros(1, dtype=np.uint64))
-        out = self.alloc(a4.nbytes)
+        oshape = (a4.shape[0], 2, a4.shape[2] - drop, self.n)
+        out = self.alloc(max(int(np.prod(oshape)) * 8, 8))
         try:
-            self.op("diag_matvec_bsgs", cb.ptr, db.ptr, C.c_size_t(d.shape[1] * self.n), ab, len(baby), ag, len(giant), out.ptr, a4.shape[2],
+            self.op(name, cb.ptr, db.ptr, C.c_size_t(d.shape[1] * self.n), ab, len(baby), ag, len(giant), out.ptr, a4.shape[2],
                     C.c_size_t(a4.shape[0]))
-            r = self.download(out, a4.shape)
+            r = self.download(out, oshape)
         finally:
             for b in (cb, db, out):
                 b.free()

@@ -47,6 +47,7 @@ void read_switches(abc_hip_ctx *c) {
   s.no_mulplain_rescale_fusion = env_on("ABC_HIP_NO_MULPLAIN_RESCALE_FUSION");
   s.no_tensor_sum = env_on("ABC_HIP_NO_TENSOR_SUM");
   s.no_plain_mac_sum = env_on("ABC_HIP_NO_PLAIN_MAC_SUM");
+  s.no_plain_sum_rescale_fusion = env_on("ABC_HIP_NO_PLAIN_SUM_RESCALE_FUSION");
   s.main_two_per_cu = env_on("ABC_HIP_MAIN_TWO_PER_CU");
   s.host_sampling = env_on("ABC_HIP_HOST_SAMPLING");
   if (const char *e = std::getenv("ABC_HIP_CHUNK")) s.chunk = (size_t)std::atol(e);
@@ -54,6 +55,7 @@ void read_switches(abc_hip_ctx *c) {
   if (const char *e = std::getenv("ABC_HIP_LEAN_LIMIT")) s.lean_limit = (size_t)std::atol(e);
   if (const char *e = std::getenv("ABC_HIP_PASS0_TARGET_LIMIT")) s.pass0_target_limit = (size_t)std::atol(e);
   if (const char *e = std::getenv("ABC_HIP_BFV_SCRATCH_MB")) s.bfv_scratch_mb = (size_t)std::atol(e);
+  if (const char *e = std::getenv("ABC_HIP_PLAIN_SUM_RESCALE_TERMS")) s.plain_sum_rescale_terms = std::atoi(e);
   if (const char *e = std::getenv("ABC_HIP_LANES")) {
     s.lanes = std::atoi(e);
     if (s.lanes < 1) s.lanes = 1;
@@ -637,6 +639,36 @@ static int plain_mac_sum(abc_hip_ctx *c, bool kernel, const std::vector<const u6
   return 0;
 }
 
+// out [count][size][nl-1][N] = rescale((addend or 0) + sum over k of plain[k] (.) ct[k]) (CKKS, nl >= 2); out overlaps no operand (the
+// caller has checked).  Fused (route_plain_sum_rescale: by measurement sums of up to four terms on large batches, every term in the
+// pair; under ABC_HIP_PLAIN_SUM_RESCALE_TERMS every sum): the terms the fused pair does not take (plain_sum_rescale_lead) are summed
+// into arena 1 by plain_mac_sum with the addend as their first carry, and the pair takes the rest with that arena (or the addend) as
+// its carry.  Separate: the whole sum into arena 1, then launch_rescale.  Arena 2 is plain_mac_sum's on its per-term route.
+static int plain_sum_rescale(abc_hip_ctx *c, const std::vector<const u64 *> &ct, const std::vector<const u64 *> &plain, size_t plain_stride,
+                             const u64 *addend, u64 *out, int size, int nl, size_t count) {
+  if (!count) return 0;
+  const size_t N = (size_t)c->n, in_bytes = count * size * (size_t)nl * N * 8;
+  const int K = (int)ct.size();
+  if (!K && !addend) {  // rescale(0) = 0
+    ABC_HIP_CHECK(hipMemsetAsync(out, 0, count * size * (size_t)(nl - 1) * N * 8, c->stream));
+    return 0;
+  }
+  if (!K) return launch_rescale(c, addend, out, size, nl, count);
+  const PlainSumRescaleRoute r = route_plain_sum_rescale(c->facts, nl, count * size, K);
+  const int lead = r.fused ? plain_sum_rescale_lead(K, r.fused_terms) : K;
+  const u64 *carry = addend;
+  if (lead) {
+    if (ensure_aux(c, 1, in_bytes)) return 1;
+    u64 *sum = (u64 *)c->aux[1];
+    if (plain_mac_sum(c, route_plain_mac_sum(c->facts, nl), std::vector<const u64 *>(ct.begin(), ct.begin() + lead),
+                      std::vector<const u64 *>(plain.begin(), plain.begin() + lead), plain_stride, addend, sum, size, nl, count))
+      return 1;
+    carry = sum;
+  }
+  if (!r.fused) return launch_rescale(c, carry, out, size, nl, count);
+  return launch_plain_sum_rescale(c, r.rescale, ct.data() + lead, plain.data() + lead, plain_stride, K - lead, carry, out, size, nl, count);
+}
+
 // out = sum_j rotate( sum_i D[j * n_baby + i] (.) rotate(in, baby[i]), giant[j] ), in the order given (abc_hip.h).  The batch goes
 // in groups of ciphertexts (matvec_bsgs_group).  Per group: the baby rotations land in arena 3, one slab per non-zero step (step 0
 // is the input itself); per giant step the inner sum over the slabs lands in arena 4 and one rotate_tail adds its rotation to the
@@ -708,6 +740,57 @@ static int diag_matvec_bsgs(abc_hip_ctx *c, const u64 *in, const u64 *diags, siz
       u64 *inner = (u64 *)c->aux[4];
       if (inner_sum(nullptr, inner, cc)) return 1;
       if (rotate_tail(c, inner, {j ? gout : nullptr}, gout, nl, giant[j], cc)) return 1;
+    }
+  }
+  return 0;
+}
+
+// out [count][2][nl-1][N] = sum_j rotate( rescale( sum_i D[j * n_baby + i] (.) rotate(in, baby[i]) ), giant[j] ) (CKKS, nl >= 2):
+// diag_matvec_bsgs with every inner sum rescaled before its giant rotation.  Groups and the baby arena (3) as there; per giant step
+// one plain_sum_rescale into arena 4 (nl - 1 limbs) and one rotate_tail at nl - 1 onto the group's slice of `out`; a giant step of 0
+// writes the slice where it is the first, else its rescaled inner sum goes to arena 4 and the add kernel follows.
+static int diag_matvec_bsgs_rescale(abc_hip_ctx *c, const u64 *in, const u64 *diags, size_t diag_stride, const std::vector<int> &baby,
+                                    const std::vector<int> &giant, u64 *out, int nl, size_t count) {
+  const size_t pw = (size_t)nl * c->n, ow = (size_t)(nl - 1) * c->n;
+  if (check_steps(c, baby) || check_steps(c, giant)) return 1;
+  if (!count) return 0;
+  if (ranges_overlap(in, count * 2 * pw * 8, out, count * 2 * ow * 8)) { set_error("diag_matvec_bsgs_rescale: d_out must not overlap d_in"); return 1; }
+  if (baby.empty() || giant.empty()) {
+    ABC_HIP_CHECK(hipMemsetAsync(out, 0, count * 2 * ow * 8, c->stream));
+    return 0;
+  }
+  const size_t nb = baby.size();
+  size_t slabs = 0;
+  for (int s : baby) slabs += s != 0;
+  const size_t group = matvec_bsgs_group(c->facts, nl, count, (int)slabs);
+  if (slabs && ensure_aux(c, 3, slabs * group * 2 * pw * 8)) return 1;
+  bool inner_arena = false;
+  for (size_t j = 0; j < giant.size(); j++) inner_arena |= giant[j] != 0 || j != 0;
+  if (inner_arena && ensure_aux(c, 4, group * 2 * ow * 8)) return 1;
+  std::vector<const u64 *> x(nb), d(nb);
+  for (size_t off = 0; off < count; off += group) {
+    const size_t cc = count - off < group ? count - off : group;
+    const u64 *gin = in + off * 2 * pw;
+    u64 *gout = out + off * 2 * ow;
+    size_t slab = 0;
+    for (size_t i = 0; i < nb; i++) {
+      if (!baby[i]) {
+        x[i] = gin;
+        continue;
+      }
+      u64 *dst = (u64 *)c->aux[3] + slab++ * group * 2 * pw;
+      if (rotate_tail(c, gin, {}, dst, nl, baby[i], cc)) return 1;
+      x[i] = dst;
+    }
+    for (size_t j = 0; j < giant.size(); j++) {
+      for (size_t i = 0; i < nb; i++) d[i] = diags + (j * nb + i) * diag_stride;
+      if (!giant[j] && !j) {
+        if (plain_sum_rescale(c, x, d, 0, nullptr, gout, 2, nl, cc)) return 1;
+        continue;
+      }
+      u64 *inner = (u64 *)c->aux[4];
+      if (plain_sum_rescale(c, x, d, 0, nullptr, inner, 2, nl, cc)) return 1;
+      if (!giant[j] ? launch_addsub(c, gout, inner, gout, nl - 1, cc * 2, 0) : rotate_tail(c, inner, {j ? gout : nullptr}, gout, nl - 1, giant[j], cc)) return 1;
     }
   }
   return 0;
@@ -1126,9 +1209,12 @@ int abc_hip_route(abc_hip_ctx *c, int op, int nl, size_t count, int in_place, ch
   if (op == kRouteRescale && (nl < 2 || c->scheme != ABC_HIP_SCHEME_CKKS)) { set_error("route: rescale needs CKKS and nl >= 2"); return 1; }
   if (op == kRouteMulPlainRescale && (nl < 2 || c->scheme != ABC_HIP_SCHEME_CKKS)) { set_error("route: multiply_plain_rescale needs CKKS and nl >= 2"); return 1; }
   if (op == kRouteDiagMatvecBsgs && c->scheme != ABC_HIP_SCHEME_CKKS) { set_error("route: diag_matvec_bsgs needs CKKS"); return 1; }
+  if ((op == kRoutePlainSumRescale || op == kRouteDiagMatvecBsgsRescale) && (nl < 2 || c->scheme != ABC_HIP_SCHEME_CKKS)) { set_error("route: multiply_plain_sum_rescale and diag_matvec_bsgs_rescale need CKKS and nl >= 2"); return 1; }
   if ((op == kRouteBfvPlainSum || op == kRouteBfvMatvecBsgs) && c->scheme != ABC_HIP_SCHEME_BFV) { set_error("route: bfv_multiply_plain_sum and bfv_diag_matvec_bsgs need BFV"); return 1; }
   const int n = !buf                        ? -1
                 : op == kRouteDiagMatvecBsgs ? format_matvec_bsgs(buf, cap, c->facts, nl, count)
+                : op == kRoutePlainSumRescale ? format_plain_sum_rescale(buf, cap, c->facts, nl, count)
+                : op == kRouteDiagMatvecBsgsRescale ? format_matvec_bsgs_rescale(buf, cap, c->facts, nl, count)
                 : op == kRouteBfvPlainSum    ? format_bfv_plain_sum(buf, cap, c->facts, count)
                 : op == kRouteBfvMatvecBsgs  ? format_bfv_matvec_bsgs(buf, cap, c->facts, count)
                                              : format_op(buf, cap, c->facts, op, nl, count, in_place != 0);
@@ -1305,6 +1391,47 @@ int abc_hip_diag_matvec_bsgs(abc_hip_ctx *c, const uint64_t *in, const uint64_t 
   return guarded([&] {
     return diag_matvec_bsgs(c, in, diags, diag_stride, std::vector<int>(h_baby, h_baby + n_baby), std::vector<int>(h_giant, h_giant + n_giant), out,
                             nl, count);
+  });
+}
+int abc_hip_multiply_plain_sum_rescale(abc_hip_ctx *c, const uint64_t *const *h_ct, const uint64_t *const *h_plain, size_t plain_stride, int n_terms,
+                                       const uint64_t *addend, uint64_t *out, int size, int nl, size_t count) {
+  CTX_GUARD(c);
+  const char *op = "multiply_plain_sum_rescale";
+  if (c->scheme != ABC_HIP_SCHEME_CKKS) { set_error("multiply_plain_sum_rescale is a CKKS operation"); return 1; }
+  if (check_level(c, nl) || check_plain_stride(c, op, plain_stride, nl)) return 1;
+  if (nl < 2) { set_error("multiply_plain_sum_rescale: no limb left to drop"); return 1; }
+  if (size != 2 && size != 3) { set_error("multiply_plain_sum_rescale: size must be 2 or 3"); return 1; }
+  if ((ptrdiff_t)count < 0) { set_error("multiply_plain_sum_rescale: negative count"); return 1; }
+  if (n_terms < 0 || (n_terms && (!h_ct || !h_plain))) { set_error("multiply_plain_sum_rescale: bad term list"); return 1; }
+  if (!out && count) { set_error("multiply_plain_sum_rescale: null output"); return 1; }
+  const size_t N = (size_t)c->n, in_words = count * size * (size_t)nl * N, out_words = count * size * (size_t)(nl - 1) * N;
+  for (int k = 0; k < n_terms; k++) {
+    if (!h_ct[k] || !h_plain[k]) { set_error("multiply_plain_sum_rescale: null term pointer"); return 1; }
+    if (out_words && ranges_overlap(h_ct[k], in_words * 8, out, out_words * 8)) { set_error("multiply_plain_sum_rescale: d_out must not overlap a ciphertext term (the output has one limb less per polynomial)"); return 1; }
+    if (check_mac_plain(c, op, h_plain[k], plain_stride, plain_stride ? count : 1, out, out_words, nl)) return 1;
+  }
+  if (addend && out_words && ranges_overlap(addend, in_words * 8, out, out_words * 8)) {
+    set_error("multiply_plain_sum_rescale: d_out must not overlap d_addend (the output has one limb less per polynomial)");
+    return 1;
+  }
+  return guarded([&] {
+    return plain_sum_rescale(c, std::vector<const u64 *>(h_ct, h_ct + n_terms), std::vector<const u64 *>(h_plain, h_plain + n_terms), plain_stride, addend,
+                             out, size, nl, count);
+  });
+}
+int abc_hip_diag_matvec_bsgs_rescale(abc_hip_ctx *c, const uint64_t *in, const uint64_t *diags, size_t diag_stride, const int *h_baby, int n_baby,
+                                     const int *h_giant, int n_giant, uint64_t *out, int nl, size_t count) {
+  CTX_GUARD(c);
+  if (c->scheme != ABC_HIP_SCHEME_CKKS) { set_error("diag_matvec_bsgs_rescale is a CKKS operation"); return 1; }
+  if (check_level(c, nl)) return 1;
+  if (nl < 2) { set_error("diag_matvec_bsgs_rescale: no limb left to drop"); return 1; }
+  if ((ptrdiff_t)count < 0) { set_error("diag_matvec_bsgs_rescale: negative count"); return 1; }
+  if (n_baby < 0 || n_giant < 0 || (n_baby && !h_baby) || (n_giant && !h_giant)) { set_error("diag_matvec_bsgs_rescale: bad step list"); return 1; }
+  if (diag_stride < (size_t)nl * c->n) { set_error("diag_matvec_bsgs_rescale: diag_stride must be at least nl * N"); return 1; }
+  if (check_mac_plain(c, "diag_matvec_bsgs_rescale", diags, diag_stride, (size_t)n_baby * n_giant, out, count * 2 * (size_t)(nl - 1) * c->n, nl)) return 1;
+  return guarded([&] {
+    return diag_matvec_bsgs_rescale(c, in, diags, diag_stride, std::vector<int>(h_baby, h_baby + n_baby), std::vector<int>(h_giant, h_giant + n_giant),
+                                    out, nl, count);
   });
 }
 int abc_hip_bfv_plain_to_ntt(abc_hip_ctx *c, const uint64_t *plain, uint64_t *plain_ntt, size_t rows) {

@@ -196,7 +196,7 @@ struct abc_hip_ctx {
   };
   std::unordered_map<const uint64_t *, KeyMirror> key_mirrors;
   std::vector<uint32_t> galois_order;
-  // workspace (kernel-sequence scratch) and five caller-level arenas (0: permuted input, 1 / 2: products (multiply_plain_rescale's separate route among them) and rotation ping-pong, 3 / 4: rotate_sum's running sums);
+  // workspace (kernel-sequence scratch) and five caller-level arenas (0: permuted input, 1 / 2: products (multiply_plain_rescale's separate route and multiply_plain_sum_rescale's leading sum among them) and rotation ping-pong, 3 / 4: rotate_sum's running sums);
   // all grow on demand and are reused, so steady-state calls perform no hipMalloc / hipFree; one that grows while a graph owns
   // it is held back, not freed (ensure_arena in abc_buffers.hip)
   void *ws = nullptr;
@@ -322,6 +322,10 @@ int launch_ks_finish(abc_hip_ctx *c, const u64 *prodD, const u64 *tmod, u64 *out
 int launch_galois(abc_hip_ctx *c, const u64 *in, u64 *out, int nl, size_t polys, uint32_t elt, bool ntt_form);
 int launch_rescale(abc_hip_ctx *c, const u64 *in, u64 *out, int size, int nl, size_t count);
 int launch_mulplain_rescale(abc_hip_ctx *c, const u64 *ct, const u64 *plain, size_t plain_stride, u64 *out, int size, int nl, size_t count);
+// out [count][size][nl-1][N] = rescale((carry or 0) + sum over k < n_terms of plain[k] (.) ct[k]): the K-term forms of the LDS-resident
+// rescale kernels (k_plainsum_rescale_*); r: a route_rescale that is not generic, n_terms <= kPlainMacTerms, a carry where n_terms is 0
+int launch_plain_sum_rescale(abc_hip_ctx *c, const RescaleRoute &r, const u64 *const *ct, const u64 *const *plain, size_t plain_stride, int n_terms,
+                             const u64 *carry, u64 *out, int size, int nl, size_t count);
 int launch_drop_last(abc_hip_ctx *c, const u64 *in, u64 *out, int size, int nl, size_t count);
 
 int bfv_multiply(abc_hip_ctx *c, BfvMul m, const u64 *a, const u64 *b, u64 *out3, size_t count);

@@ -1079,4 +1079,213 @@ int launch_ckks_plain_mac_sum(abc_hip_ctx *c, const u64 *const *ct, const u64 *c
   return 0;
 }
 
+// ---- K-term plaintext sum + rescale in one: carry + sum_k plain_k (.) ct_k formed in the loads of R1 and R2 ----
+// The K-term forms of k_mulplain_rescale_intt_fp / _mixed / _ntt above: what enters R1's inverse transform is the dropped limb of
+// (carry or 0) + sum over the launch's terms of plain_k (.) ct_k, and the same expression per limb j enters R2's diff_mul_fwd in place
+// of x[i].  The term pointers travel by value as in k_ckks_plain_mac_sum (indexed by constants only: the loop is unrolled), carry is
+// [count][size][nl][N] like a term's ciphertext, or null.  One functor per arithmetic forms the sums, kStage / kChunk coefficients of
+// a lane at a time with the loop over the terms OUTSIDE the one over the coefficients: a term's 2 * kChunk loads are in flight together
+// (coefficient by coefficient, the workgroup-uniform branch per term left two).  R1 stages its limb in the transform's LDS before
+// the transform, by coalesced loads (plain_sum_stage); R2 forms the sums behind its transform (divround_finish's XL).  The sum is
+// exact modulo q whatever its representative, so the result is bit-identical to k_ckks_plain_mac_sum followed by the rescale kernels.
+// fp64 (q < 2^50): the arithmetic of plain_mac_fp -- the carried word is below q, every product |.| < q, a re-centring after every
+// kPlainMacFpTerms products (carried + 4 products < 5 q, then q/2 + 4 products < 4.5 q; 1 + kPlainMacTerms products would pass
+// 8 q <= 2^53), and one more at the end: |result| <= q/2, inside the |.| < q that FpArith::mul_u64 hands to the same consumers.
+static_assert(kPlainMacFpTerms + 1 <= 8 && kPlainMacTerms <= 2 * kPlainMacFpTerms,
+              "plain sum rescale: the fp64 accumulator would pass 2^53 between two re-centrings");
+struct PlainSumLimbFp {
+  static constexpr int kStage = 16, kChunk = 4;  // coefficients at a time: R1 (nothing else is live), R2 (beside the transform's sixteen outputs)
+  const PlainMacTerms &t;
+  int nt;
+  const u64 *__restrict__ carry;  // this limb of the carried value, or null
+  size_t ct_off, plain_off;       // of this limb inside a term's ciphertext / plaintext
+  double q, qinv;
+  template <int C>
+  __device__ __forceinline__ void sums(const int (&i)[C], double (&out)[C]) const {
+    double acc[C];
+#pragma unroll
+    for (int e = 0; e < C; e++) acc[e] = 0.0;
+    if (carry) {  // workgroup-uniform
+#pragma unroll
+      for (int e = 0; e < C; e++) acc[e] = fp_from_u64(carry[i[e]]);
+    }
+#pragma unroll
+    for (int k = 0; k < kPlainMacTerms; k++) {
+      if (k < nt) {  // workgroup-uniform
+        const u64 *__restrict__ ct = t.ct[k] + ct_off, *__restrict__ pl = t.plain[k] + plain_off;
+        u64 cv[C], pv[C];
+#pragma unroll
+        for (int e = 0; e < C; e++) cv[e] = ct[i[e]], pv[e] = pl[i[e]];
+#pragma unroll
+        for (int e = 0; e < C; e++) acc[e] += fp_mulmod(fp_from_u64(cv[e]), fp_from_u64(pv[e]), q, qinv);
+        if ((k + 1) % kPlainMacFpTerms == 0 && k + 1 < kPlainMacTerms) {
+#pragma unroll
+          for (int e = 0; e < C; e++) acc[e] = fp_centre(acc[e], q, qinv);
+        }
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < C; e++) out[e] = fp_centre(acc[e], q, qinv);
+  }
+};
+// integers: the arithmetic of plain_mac_int -- (kPlainMacTerms + 1) (q - 1)^2 < 2^128 for the widest prime a context accepts (the
+// static_assert beside PlainMacTerms), one reduction: canonical, what IntArith::mul_u64 returns.  Eight coefficients at a time in
+// R1: their 128-bit accumulators and a term's loads are 64 VGPRs.
+struct PlainSumLimbInt {
+  static constexpr int kStage = 8, kChunk = 2;
+  const PlainMacTerms &t;
+  int nt;
+  const u64 *__restrict__ carry;
+  size_t ct_off, plain_off;
+  Mod m;
+  template <int C>
+  __device__ __forceinline__ void sums(const int (&i)[C], u64 (&out)[C]) const {
+    U128 acc[C];
+#pragma unroll
+    for (int e = 0; e < C; e++) acc[e] = U128{0, 0};
+    if (carry) {  // workgroup-uniform
+#pragma unroll
+      for (int e = 0; e < C; e++) acc[e].lo = carry[i[e]];
+    }
+#pragma unroll
+    for (int k = 0; k < kPlainMacTerms; k++) {
+      if (k < nt) {  // workgroup-uniform
+        const u64 *__restrict__ ct = t.ct[k] + ct_off, *__restrict__ pl = t.plain[k] + plain_off;
+        u64 cv[C], pv[C];
+#pragma unroll
+        for (int e = 0; e < C; e++) cv[e] = ct[i[e]], pv[e] = pl[i[e]];
+#pragma unroll
+        for (int e = 0; e < C; e++) mac128(acc[e], cv[e], pv[e]);
+      }
+    }
+    const u64 r64 = reduce64(0ull - m.q, m);  // 2^64 mod q
+#pragma unroll
+    for (int e = 0; e < C; e++) out[e] = reduce128(acc[e], r64, m);
+  }
+};
+__device__ __forceinline__ PlainSumLimbFp plain_sum_limb_fp(const PlainMacTerms &t, int nt, const u64 *carry, size_t ct_off, size_t plain_off,
+                                                            const Mod &m) {
+  return PlainSumLimbFp{t, nt, carry ? carry + ct_off : nullptr, ct_off, plain_off, m.qd, m.qinv};
+}
+__device__ __forceinline__ PlainSumLimbInt plain_sum_limb_int(const PlainMacTerms &t, int nt, const u64 *carry, size_t ct_off, size_t plain_off,
+                                                              const Mod &m) {
+  return PlainSumLimbInt{t, nt, carry ? carry + ct_off : nullptr, ct_off, plain_off, m};
+}
+// R1: the limb's N sums into the transform's LDS, lane `tid` those of the coefficients tid + e * (N / 16) (coalesced), then the
+// barrier; the transform's first pass reads word lds_pad(i) for coefficient i (LdsOperand) and writes back exactly the words it read
+template <int LB, class XL, class E>
+__device__ __forceinline__ void plain_sum_stage(E *lds, const XL &xl) {
+  constexpr int T = (1 << LB) / 16, C = XL::kStage;
+#pragma unroll
+  for (int c0 = 0; c0 < 16; c0 += C) {
+    int ii[C];
+    E xs[C];
+#pragma unroll
+    for (int e = 0; e < C; e++) ii[e] = (int)threadIdx.x + (c0 + e) * T;
+    xl.sums(ii, xs);
+#pragma unroll
+    for (int e = 0; e < C; e++) lds[lds_pad(ii[e])] = xs[e];
+  }
+  if constexpr (LB <= 10) wave_sync(); else block_sync_lds();
+}
+template <class E>
+struct LdsOperand {
+  const E *lds;
+  __device__ __forceinline__ E operator()(int i) const { return lds[lds_pad(i)]; }
+};
+
+template <int LB>
+__global__ __launch_bounds__((1 << LB) / 16) void k_plainsum_rescale_intt_fp(DevCtx c, PlainMacTerms t, int nt, size_t plain_stride,
+                                                                             const u64 *__restrict__ carry, u64 *__restrict__ last, int size, int nl) {
+  __shared__ double lds[lds_words(LB)];
+  const size_t N = (size_t)1 << LB, p = blockIdx.x;
+  const Mod m = mod_at(c, nl - 1);
+  plain_sum_stage<LB>(lds, plain_sum_limb_fp(t, nt, carry, (p * nl + (nl - 1)) * N, (p / size) * plain_stride + (size_t)(nl - 1) * N, m));
+  divround_to_coef<LB, FpArith, false, LdsOperand<double>>(lds, m, fp_table(c, nl - 1), nullptr, last + p * N, nullptr, LdsOperand<double>{lds});
+}
+template <int LB>
+__global__ __launch_bounds__((1 << LB) / 16) void k_plainsum_rescale_intt_mixed(DevCtx c, PlainMacTerms t, int nt, size_t plain_stride,
+                                                                                const u64 *__restrict__ carry, u64 *__restrict__ last, int size, int nl,
+                                                                                int fp_last) {
+  __shared__ u64 lds_raw[lds_words(LB)];
+  const size_t N = (size_t)1 << LB, p = blockIdx.x;
+  const size_t ct_off = (p * nl + (nl - 1)) * N, plain_off = (p / size) * plain_stride + (size_t)(nl - 1) * N;
+  u64 *__restrict__ dst = last + p * N;
+  if (fp_last) {
+    const Mod m = mod_at(c, nl - 1);
+    double *lds = reinterpret_cast<double *>(lds_raw);
+    plain_sum_stage<LB>(lds, plain_sum_limb_fp(t, nt, carry, ct_off, plain_off, m));
+    divround_to_coef<LB, FpArith, false, LdsOperand<double>>(lds, m, fp_table(c, nl - 1), nullptr, dst, nullptr, LdsOperand<double>{lds});
+  } else {
+    const Mod m = c.mods[nl - 1];
+    plain_sum_stage<LB>(lds_raw, plain_sum_limb_int(t, nt, carry, ct_off, plain_off, m));
+    divround_to_coef<LB, IntArith<true>, false, LdsOperand<u64>>(lds_raw, m, ntt_table(c, nl - 1), nullptr, dst, nullptr, LdsOperand<u64>{lds_raw});
+  }
+}
+template <int LB, bool MIXED>
+__global__ __launch_bounds__((1 << LB) / 16) void k_plainsum_rescale_ntt(DevCtx c, PlainMacTerms t, int nt, size_t plain_stride,
+                                                                         const u64 *__restrict__ carry, const u64 *__restrict__ last,
+                                                                         u64 *__restrict__ out, int size, int nl, int npoly, u32 fpmask) {
+  __shared__ u64 lds_raw[lds_words(LB)];
+  int j;
+  size_t p;
+  xcd_slot(blockIdx.x, nl - 1, npoly, j, p);
+  const size_t N = (size_t)1 << LB;
+  const Mod m = MIXED ? c.mods[j] : mod_at(c, j);
+  const auto fix = round_fix<std::conditional_t<MIXED, u64, double>>(c.mods[nl - 1].q >> 1, m);
+  const DropInv d = inv_qlast_at(c, nl - 1, j);
+  const u64 *__restrict__ src = last + p * N;
+  const size_t ct_off = (p * nl + j) * N, plain_off = (p / size) * plain_stride + (size_t)j * N;
+  u64 *__restrict__ o = out + (p * (nl - 1) + j) * N;
+  if constexpr (!MIXED) {
+    divround_finish<LB, FpArith, false, false, false, PlainSumLimbFp>(reinterpret_cast<double *>(lds_raw), m, fp_table(c, j), fix, d, src, nullptr, nullptr, o,
+                                                                      nullptr, plain_sum_limb_fp(t, nt, carry, ct_off, plain_off, m));
+  } else if ((fpmask >> j) & 1u) {
+    const Mod mf = mod_at(c, j);
+    divround_finish<LB, FpArith, true, false, false, PlainSumLimbFp>(reinterpret_cast<double *>(lds_raw), mf, fp_table(c, j), fix, d, src, nullptr, nullptr, o,
+                                                                     nullptr, plain_sum_limb_fp(t, nt, carry, ct_off, plain_off, mf));
+  } else {
+    divround_finish<LB, IntArith<true>, false, false, false, PlainSumLimbInt>(lds_raw, m, ntt_table(c, j), fix, d, src, nullptr, nullptr, o, nullptr,
+                                                                              plain_sum_limb_int(t, nt, carry, ct_off, plain_off, m));
+  }
+}
+template <int LB, bool MIXED>
+static int launch_plain_sum_rescale_lds(abc_hip_ctx *c, const PlainMacTerms &t, int nt, size_t plain_stride, const u64 *carry, u64 *out, int size, int nl,
+                                        size_t polys, u32 fpmask) {
+  const size_t N = (size_t)1 << LB;
+  if (ensure_workspace(c, polys * N * 8)) return 1;
+  u64 *last = (u64 *)c->ws;
+  const dim3 block((1 << LB) / 16);
+  if constexpr (MIXED)
+    hipLaunchKernelGGL(k_plainsum_rescale_intt_mixed<LB>, dim3((unsigned)polys), block, 0, c->stream, c->dc, t, nt, plain_stride, carry, last, size, nl,
+                       (int)((fpmask >> (nl - 1)) & 1u));
+  else
+    hipLaunchKernelGGL(k_plainsum_rescale_intt_fp<LB>, dim3((unsigned)polys), block, 0, c->stream, c->dc, t, nt, plain_stride, carry, last, size, nl);
+  hipLaunchKernelGGL((k_plainsum_rescale_ntt<LB, MIXED>), dim3((unsigned)(polys * (nl - 1))), block, 0, c->stream, c->dc, t, nt, plain_stride, carry,
+                     last, out, size, nl, (int)polys, fpmask);
+  ABC_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// out [count][size][nl-1][N] = rescale((carry or 0) + sum over k < n_terms of plain[k] (.) ct[k]) by the fused pair; the route r is not
+// generic, 0 <= n_terms <= kPlainMacTerms with a carry where n_terms is 0, nl >= 2 (plain_sum_rescale in abc_context.hip sees to all three)
+int launch_plain_sum_rescale(abc_hip_ctx *c, const RescaleRoute &r, const u64 *const *ct, const u64 *const *plain, size_t plain_stride, int n_terms,
+                             const u64 *carry, u64 *out, int size, int nl, size_t count) {
+  const size_t polys = count * size;
+  if (!polys) return 0;
+  if (r.kind == Rescale::generic || n_terms < 0 || n_terms > kPlainMacTerms || (!n_terms && !carry) || nl < 2) {
+    set_error("plain_sum_rescale: not a launch of the fused pair");
+    return 1;
+  }
+  PlainMacTerms t;  // unused slots repeat a valid pointer (the carry where there is no term: no slot is read then)
+  for (int k = 0; k < kPlainMacTerms; k++) t.ct[k] = n_terms ? ct[k < n_terms ? k : 0] : carry, t.plain[k] = n_terms ? plain[k < n_terms ? k : 0] : carry;
+  if (r.kind == Rescale::mixed)
+    return dispatch_logn<10, 14>(c->logn, [&](auto LB) {
+      return launch_plain_sum_rescale_lds<decltype(LB)::value, true>(c, t, n_terms, plain_stride, carry, out, size, nl, polys, r.fpmask);
+    });
+  return dispatch_logn<10, 14>(c->logn, [&](auto LB) {
+    return launch_plain_sum_rescale_lds<decltype(LB)::value, false>(c, t, n_terms, plain_stride, carry, out, size, nl, polys, 0u);
+  });
+}
+
 }  // namespace abc

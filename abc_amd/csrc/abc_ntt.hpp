@@ -777,16 +777,20 @@ __device__ __forceinline__ void ntt_inv_block(u64 *lds, Load load, Store store, 
 // ---- divide and round, LDS-resident (one workgroup per limb): the two steps of "divide by a dropped prime" above -------------
 // Step A: the dropped limb (NTT form at src; m, t: the dropped prime) -> coefficients, N^-1, + floor(p/2) -> dst, canonical
 // MUL: the limb is src (.) pl, the product with a plaintext limb formed in the load (multiply_plain + rescale in one)
-template <int LB, class A, bool MUL = false>
+// XL: a functor i -> A::E that supplies the limb instead of src (a K-term plaintext sum staged in LDS: abc_kernels_eval.hip); what it
+// returns lies in the range A::mul_u64 returns.  NoOperand: src, as above.
+struct NoOperand {};
+template <int LB, class A, bool MUL = false, class XL = NoOperand>
 __device__ __forceinline__ void divround_to_coef(typename A::E *lds, const Mod m, const typename A::Table t,
                                                  const u64 *__restrict__ src, u64 *__restrict__ dst,
-                                                 const u64 *__restrict__ pl = nullptr) {
+                                                 const u64 *__restrict__ pl = nullptr, const XL xl = {}) {
   using E = typename A::E;
   const E half = (E)(m.q >> 1);
   ntt_inv_block_a<LB, A>(
       lds,
       [&](int, int i) {
-        if constexpr (MUL) return A::mul_u64(src[i], pl[i], m);
+        if constexpr (!std::is_same_v<XL, NoOperand>) return xl(i);
+        else if constexpr (MUL) return A::mul_u64(src[i], pl[i], m);
         else return A::from_u64(src[i]);
       },
       [&](int, int i, E v) { dst[i] = A::canon_add(A::scale_n(v, m), half, m); }, t, m, 0, 0);
@@ -795,13 +799,42 @@ __device__ __forceinline__ void divround_to_coef(typename A::E *lds, const Mod m
 // cin = the addend's limb (ADD; callers choose by a workgroup-uniform branch: two straight-line bodies, no per-element select).
 // REDUCE: t is reduced modulo q as an integer whatever the policy, and fix = round_fix<u64> -- FpArith where the dropped prime
 // may be wider than 2^52 (canonical, + fix, below 2q).  Otherwise fix = round_fix<A::E> and the policy's own load.
-// MUL: x is x (.) pl, as in step A.
-template <int LB, class A, bool REDUCE, bool ADD, bool MUL = false>
+// MUL: x is x (.) pl, as in step A.  XL: x comes from a functor, XL::kChunk coefficients at a time -- xl.sums(i, out): out[e] = x at
+// index i[e], in the range A::mul_u64 returns -- AFTER the transform, whose sixteen outputs per lane wait in registers: the functor
+// loads its operands for a whole chunk at once, and nothing of it is live across the transform.
+template <int LB, class A, bool REDUCE, bool ADD, bool MUL = false, class XL = NoOperand>
 __device__ __forceinline__ void divround_finish(typename A::E *lds, const Mod m, const typename A::Table t,
                                                 const std::conditional_t<REDUCE, u64, typename A::E> fix, const DropInv d,
                                                 const u64 *__restrict__ tl, const u64 *__restrict__ x, const u64 *__restrict__ cin,
-                                                u64 *__restrict__ o, const u64 *__restrict__ pl = nullptr) {
+                                                u64 *__restrict__ o, const u64 *__restrict__ pl = nullptr, const XL xl = {}) {
   using E = typename A::E;
+  if constexpr (!std::is_same_v<XL, NoOperand>) {
+    E y[16];
+    int yi[16];
+    ntt_fwd_block_a<LB, A>(
+        lds,
+        [&](int, int i) {
+          if constexpr (REDUCE) return A::from_u64(IntArith<true>::reduce_fix(tl[i], fix, m));
+          else return A::reduce_fix(tl[i], fix, m);
+        },
+        [&](int r, int i, E v) { y[r] = v, yi[r] = i; }, t, m, 0, 0);
+    constexpr int C = XL::kChunk;
+#pragma unroll
+    for (int c0 = 0; c0 < 16; c0 += C) {
+      int ii[C];
+      E xs[C];
+#pragma unroll
+      for (int e = 0; e < C; e++) ii[e] = yi[c0 + e];
+      xl.sums(ii, xs);
+#pragma unroll
+      for (int e = 0; e < C; e++) {
+        const E r = A::diff_mul_fwd(xs[e], y[c0 + e], d, m);
+        if constexpr (ADD) o[ii[e]] = A::canon_add(r, A::from_u64(cin[ii[e]]), m);
+        else o[ii[e]] = A::canon(r, m);
+      }
+    }
+    return;
+  }
   ntt_fwd_block_a<LB, A>(
       lds,
       [&](int, int i) {

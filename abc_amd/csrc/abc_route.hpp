@@ -25,11 +25,13 @@ struct Switches {
   bool no_rotate_mac_fusion = false;  // ABC_HIP_NO_ROTATE_MAC_FUSION: rotate_mac_plain as a rotation into an arena, multiply_plain on it, then the add kernel
   bool no_mulplain_rescale_fusion = false;  // ABC_HIP_NO_MULPLAIN_RESCALE_FUSION: multiply_plain_rescale as multiply_plain into an arena, then rescale
   bool no_tensor_sum = false;  // ABC_HIP_NO_TENSOR_SUM: multiply_sum / mul_sum_relin form every product on its own (tensor into an arena, then the add kernel)
+  bool no_plain_sum_rescale_fusion = false;  // ABC_HIP_NO_PLAIN_SUM_RESCALE_FUSION: multiply_plain_sum_rescale (and the inner sums of diag_matvec_bsgs_rescale) as multiply_plain_sum into an arena, then rescale
   bool no_plain_mac_sum = false;  // ABC_HIP_NO_PLAIN_MAC_SUM: multiply_plain_sum (and the inner sums of diag_matvec_bsgs) as multiply_plain into an arena, then the add kernel, per term
   bool main_two_per_cu = false;  // ABC_HIP_MAIN_TWO_PER_CU: k_split4_main_fp in its one-piece pair phase at nl <= 4 (same step, same route: a form of the kernel)
   bool host_sampling = false;  // ABC_HIP_HOST_SAMPLING: the keyed entries (the OS-keyed ones call them) draw with the host twin of the keyed spec (no route depends on it)
   size_t chunk = 0, few_limbs = 48, lean_limit = 96, bfv_scratch_mb = 0, pass0_target_limit = 128;
   int lanes = 2;
+  int plain_sum_rescale_terms = -1;  // ABC_HIP_PLAIN_SUM_RESCALE_TERMS (0 .. 8): the fused sum-rescale pair at EVERY batch and term count, taking at most that many terms (A/B runs, parity tests); unset: the measured rule of route_plain_sum_rescale
 };
 
 // prime widths the kernels are exact for (abc_ntt.hpp: fp_ok, unguarded_ok)
@@ -271,6 +273,52 @@ inline MulSumRoute route_mul_sum(const RouteFacts &f, int nl) {
 // (addend or 0) + sum of K plaintext products at level nl (CKKS): the K-term kernel at every ring, chain and level
 inline bool route_plain_mac_sum(const RouteFacts &f, int) { return f.scheme == 2 && !f.sw.no_plain_mac_sum; }
 
+// rescale((addend or 0) + sum of K plaintext products) at level nl (CKKS), `polys` = count * size polynomials.  Fused: the K-term forms
+// of the LDS-resident rescale kernels form the sum of the last `fused_terms` terms (and the carried value) in their loads; the terms
+// before those go through multiply_plain_sum into an arena, which is the carry.  Separate: the whole sum into the arena, then the
+// rescale.  Fused needs an LDS-resident rescale and neither ABC_HIP_NO_PLAIN_SUM_RESCALE_FUSION nor ABC_HIP_NO_PLAIN_MAC_SUM (the
+// per-term form of the sum).  Among those shapes the measurement decides (profiles/plain_sum_rescale_ab.log):
+// the pair beats multiply_plain_sum + rescale for sums of up to kPlainSumRescaleTerms = 4 terms -- every term in the pair, no
+// leading launch -- once R1 has a workgroup per CU and 2^20 coefficients to transform; at 6 terms and above, with a leading
+// launch at any number of fused terms (8, 4, 2, the carry alone), and on small batches (R1 is one workgroup per polynomial; the
+// streaming kernel spreads the same loads over every CU) the two steps are as fast or faster.  ABC_HIP_PLAIN_SUM_RESCALE_TERMS=t
+// takes the measurement out: fused at every batch and term count, at most t terms in the pair.
+constexpr int kPlainSumRescaleTerms = 4;
+constexpr size_t kPlainSumRescaleMinPolys = 256, kPlainSumRescaleMinCoeffs = (size_t)1 << 20;
+struct PlainSumRescaleRoute {
+  RescaleRoute rescale;  // the rescale, out of place
+  bool fused;
+  int fused_terms;  // fused: the most terms the pair takes
+};
+// polys / n_terms default to a large batch and one term: "could this level fuse at all"
+inline PlainSumRescaleRoute route_plain_sum_rescale(const RouteFacts &f, int nl, size_t polys = (size_t)1 << 30, int n_terms = 1) {
+  const RescaleRoute r = route_rescale(f, nl, false);
+  if (r.kind == Rescale::generic || f.sw.no_plain_sum_rescale_fusion || f.sw.no_plain_mac_sum) return {r, false, 0};
+  if (f.sw.plain_sum_rescale_terms >= 0) return {r, true, f.sw.plain_sum_rescale_terms < 8 ? f.sw.plain_sum_rescale_terms : 8};
+  const bool wins = n_terms <= kPlainSumRescaleTerms && polys >= kPlainSumRescaleMinPolys && (polys << f.logn) >= kPlainSumRescaleMinCoeffs;
+  return {r, wins, kPlainSumRescaleTerms};
+}
+// terms of a K-term sum that the streaming kernel sums into the arena first: whole launches of terms_per_launch, as few as leave the
+// fused pair at most fused_terms
+inline int plain_sum_rescale_lead(int n_terms, int fused_terms, int terms_per_launch = 8) {
+  if (fused_terms < 0) fused_terms = 0;
+  if (fused_terms > terms_per_launch) fused_terms = terms_per_launch;
+  if (n_terms <= fused_terms) return 0;
+  const int lead = (n_terms - fused_terms + terms_per_launch - 1) / terms_per_launch * terms_per_launch;
+  return lead < n_terms ? lead : n_terms;
+}
+
+// the matvec with the rescale behind every inner sum: baby rotations at nl, one sum-rescale per giant step, giant rotate_adds at nl - 1
+struct MatvecBsgsRescaleRoute {
+  RotRoute baby;
+  PlainSumRescaleRoute sum;
+  RotTailRoute giant;  // route_rotate_add at nl - 1, out of place
+};
+// polys: of one group's inner sum; n_baby: its terms
+inline MatvecBsgsRescaleRoute route_matvec_bsgs_rescale(const RouteFacts &f, int nl, size_t polys = (size_t)1 << 30, int n_baby = 1) {
+  return {route_rotate(f, nl, false), route_plain_sum_rescale(f, nl, polys, n_baby), route_rotate_add(f, nl - 1, false)};
+}
+
 inline MatvecBsgsRoute route_matvec_bsgs(const RouteFacts &f, int nl) {
   return {route_rotate(f, nl, false), route_plain_mac_sum(f, nl), route_rotate_add(f, nl, false)};
 }
@@ -467,6 +515,29 @@ inline int format_matvec_bsgs(char *buf, size_t cap, const RouteFacts &f, int nl
   const MatvecBsgsRoute r = route_matvec_bsgs(f, nl);
   format_ks(ks, sizeof ks, f, r.baby.ks, nl, matvec_bsgs_group(f, nl, count, 1));  // per-chunk fields: those of the first group's first chunk
   const int n = snprintf(buf, cap, "%s %s macsum=%s add=%s", r.baby.fold ? "fold" : "permute", ks, r.macsum ? "kernel" : "per_term", r.giant.fused ? "fused" : "separate");
+  return n < 0 ? -1 : (size_t)n < cap ? n : -1;
+}
+// ABC_HIP_ROUTE_PLAIN_SUM_RESCALE (16) and ABC_HIP_ROUTE_DIAG_MATVEC_BSGS_RESCALE (17), formatters of their own like 13's.  16: the
+// rescale's route, then sumrescale=fused|separate.  17: the baby rotation's route at nl, sumrescale=, then the giant step's route at
+// nl - 1 with add=fused|separate; per-chunk fields: those of the first group's first chunk.  nl >= 2.  abc_hip_route has no argument
+// for the number of terms: both strings answer for a sum of `count` size-2 ciphertexts of up to kPlainSumRescaleTerms terms (17: of
+// the first group); a longer sum is separate unless ABC_HIP_PLAIN_SUM_RESCALE_TERMS is set.
+constexpr int kRoutePlainSumRescale = 16, kRouteDiagMatvecBsgsRescale = 17;
+inline int format_plain_sum_rescale(char *buf, size_t cap, const RouteFacts &f, int nl, size_t count) {
+  const PlainSumRescaleRoute r = route_plain_sum_rescale(f, nl, count * 2, 1);
+  const char *how = r.fused ? "fused" : "separate";
+  const int n = r.rescale.kind == Rescale::mixed ? snprintf(buf, cap, "mixed fpmask=0x%x sumrescale=%s", (unsigned)r.rescale.fpmask, how)
+                                                 : snprintf(buf, cap, "%s sumrescale=%s", name(r.rescale.kind), how);
+  return n < 0 ? -1 : (size_t)n < cap ? n : -1;
+}
+inline int format_matvec_bsgs_rescale(char *buf, size_t cap, const RouteFacts &f, int nl, size_t count) {
+  char baby[80], giant[80];
+  const size_t group = matvec_bsgs_group(f, nl, count, 1);
+  const MatvecBsgsRescaleRoute r = route_matvec_bsgs_rescale(f, nl, group * 2, 1);
+  format_ks(baby, sizeof baby, f, r.baby.ks, nl, group);
+  format_ks(giant, sizeof giant, f, r.giant.rot.ks, nl - 1, group);
+  const int n = snprintf(buf, cap, "%s %s sumrescale=%s %s %s add=%s", r.baby.fold ? "fold" : "permute", baby, r.sum.fused ? "fused" : "separate",
+                         r.giant.rot.fold ? "fold" : "permute", giant, r.giant.fused ? "fused" : "separate");
   return n < 0 ? -1 : (size_t)n < cap ? n : -1;
 }
 // ABC_HIP_ROUTE_BFV_PLAIN_SUM (14) and ABC_HIP_ROUTE_BFV_MATVEC_BSGS (15), formatters of their own for the same reason.  14:

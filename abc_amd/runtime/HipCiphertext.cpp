@@ -105,14 +105,18 @@ void HipCiphertext::rescaleIfPossible() {
   buf = std::move(t);
   --nl;
 }
+bool HipCiphertext::scalesAgree(double a, double b) const {
+  // written so that a NaN or a non-positive scale does not agree with anything
+  const double rel = std::fabs(a - b) / std::fmax(std::fabs(a), std::fabs(b));
+  return a > 0.0 && b > 0.0 && rel <= getFactory().scaleTolerance();
+}
 void HipCiphertext::checkScales(double a, double b) const {
   // after a rescale the scale is Delta^2 / q_l, a hair off Delta for a 40-bit prime next to Delta = 2^40, and that drift doubles
   // with every further squaring: adding values from different depths is what every CKKS program does (SEAL makes the user
   // overwrite the scale; here the left operand's scale stands).  The factory derives the bound from its chain
   // (HipCiphertextFactory::scaleTolerance); anything coarser is a real mismatch.  Written so that a NaN or a non-positive scale
   // fails too.
-  const double rel = std::fabs(a - b) / std::fmax(std::fabs(a), std::fabs(b));
-  if (!(a > 0.0) || !(b > 0.0) || !(rel <= getFactory().scaleTolerance()))
+  if (!scalesAgree(a, b))
     throw std::runtime_error("CKKS: scale mismatch between operands (" + std::to_string(a) + " vs " + std::to_string(b) + ")");
 }
 // a product's scale must leave room under the modulus of its level, or the message wraps around silently (SEAL throws
@@ -274,11 +278,64 @@ std::unique_ptr<AbstractCiphertext> HipCiphertext::mulSum(const MulSumCapable::T
   return r;
 }
 
-bool HipCiphertext::fusePlainSum() const { return getFactory().fusesPlainSum() && !getFactory().isCkks(); }
+bool HipCiphertext::fusePlainSum() const {
+  const auto &f = getFactory();
+  return f.fusesPlainSum() && (!f.isCkks() || f.lazyRescales());
+}
+
+// CKKS: one abc_hip_multiply_plain_sum_rescale where every term sits at this level (two limbs or more) and scale and no public value is
+// all -1; else null, and the caller takes the calls per term.  Runs longer than the plaintext cache go in slices: the leading ones
+// by abc_hip_multiply_plain_sum at nl with the sum so far as addend, the last one by the new call with that sum as its addend.
+// `held` keeps every block of a slice alive until its call is enqueued, whatever a later miss of the same slice evicts.
+std::unique_ptr<HipCiphertext> HipCiphertext::ckksPlainSumRescale(const PlainSumCapable::Terms &terms) const {
+  const auto &f = getFactory();
+  if (!fusePlainSum() || nl < 2) return nullptr;
+  std::vector<std::vector<double>> vals;
+  for (const auto &t : terms) {
+    const HipCiphertext &c = cast(*t.first);
+    vals.push_back(realCleartext(*t.second, "MULTIPLY"));
+    bool allMinusOne = !vals.back().empty();
+    for (double v : vals.back()) allMinusOne = allMinusOne && v == -1.0;
+    if (allMinusOne || c.nl != nl || !scalesAgree(sc, c.sc)) return nullptr;
+  }
+  const double ps = f.defaultScale();
+  checkScaleFits(sc * ps, nl);  // throws before anything is enqueued
+  std::shared_ptr<Buffer> sum;  // the leading slices' sum, nl limbs
+  std::unique_ptr<HipCiphertext> r;
+  for (size_t k0 = 0; k0 < terms.size(); k0 += f.plainCacheEntries()) {
+    const size_t k1 = std::min(terms.size(), k0 + f.plainCacheEntries());
+    std::vector<const uint64_t *> a, p;
+    std::vector<std::shared_ptr<const HipCiphertextFactory::DeviceBlock>> held;
+    for (size_t k = k0; k < k1; ++k) {
+      a.push_back(cast(*terms[k].first).in());
+      held.push_back(f.cachedCkksPlaintextBlock(vals[k], nl, ps));
+      p.push_back(held.back()->p);
+    }
+    if (k1 < terms.size()) {
+      const uint64_t *addend = sum ? sum->p : nullptr;
+      if (!sum) sum = allocate(f, nl);
+      abcHipCheck(abc_hip_multiply_plain_sum(f.context(), a.data(), p.data(), 0, (int)a.size(), addend, sum->p, 2, nl, f.batchSize()), "multiply_plain_sum");
+    } else {
+      r = fresh(nl - 1);
+      abcHipCheck(abc_hip_multiply_plain_sum_rescale(f.context(), a.data(), p.data(), 0, (int)a.size(), sum ? sum->p : nullptr, r->buf->p, 2, nl,
+                                                     f.batchSize()),
+                  "multiply_plain_sum_rescale");
+      f.countPlainSumRescale();
+    }
+  }
+  r->sc = sc * ps / (double)f.prime(nl - 1);
+  return r;
+}
 
 std::unique_ptr<AbstractCiphertext> HipCiphertext::plainSum(const PlainSumCapable::Terms &terms) const {
   const auto &f = getFactory();
   if (terms.empty()) throw std::runtime_error("plainSum: no terms");
+  if (f.isCkks()) {
+    if (auto r = ckksPlainSumRescale(terms)) return r;
+    auto r = terms[0].first->multiplyPlain(*terms[0].second);  // the calls per term, as the interpreter issues them
+    for (size_t k = 1; k < terms.size(); ++k) r->addInplace(*terms[k].first->multiplyPlain(*terms[k].second));
+    return r;
+  }
   bool one_call = fusePlainSum();
   for (const auto &t : terms) {
     if (!one_call) break;

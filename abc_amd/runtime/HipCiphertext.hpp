@@ -48,8 +48,10 @@ class HipCiphertext : public AbstractCiphertext, public RotateAddCapable, public
   // CKKS helpers
   void dropTo(int level);                       // mod_switch down (no-op at or below `level`)
   void rescaleIfPossible();                     // divide by the last prime of the current level
-  void checkScales(double a, double b) const;  // additions need (nearly) equal scales
+  bool scalesAgree(double a, double b) const;  // positive and within the factory's tolerance of each other
+  void checkScales(double a, double b) const;  // additions need (nearly) equal scales: throws unless scalesAgree
   void checkScaleFits(double scale, int level) const;  // a product's scale must stay below the modulus of its level
+  std::unique_ptr<HipCiphertext> ckksPlainSumRescale(const PlainSumCapable::Terms &terms) const;  // null: the calls per term
   // this and operand at a common level: returns the operand's pointer (possibly a temporary held in `keep`)
   const uint64_t *alignWith(const HipCiphertext &operand, std::shared_ptr<Buffer> &keep);
 
@@ -98,9 +100,12 @@ class HipCiphertext : public AbstractCiphertext, public RotateAddCapable, public
   // (checkScales); terms at different levels take multiply + addInplace per term, which bring them together.
   bool lazyRelinearize() const override;
   std::unique_ptr<AbstractCiphertext> mulSum(const MulSumCapable::Terms &terms) const override;
-  // PlainSumCapable, BFV only: the sum of the products as abc_hip_bfv_multiply_plain_sum over the operands' buffers and the factory's
-  // cached NTT-form plaintexts, into a fresh buffer -- the words of multiplyPlain per term and addInplace.  A term whose public value
-  // is all -1 (multiplyPlain negates there), CKKS and the option off take those calls per term.
+  // PlainSumCapable.  BFV: the sum of the products as abc_hip_bfv_multiply_plain_sum over the operands' buffers and the factory's
+  // cached NTT-form plaintexts, into a fresh buffer -- the words of multiplyPlain per term and addInplace.  CKKS, with the factory's
+  // lazyRescale on: the sum as ONE abc_hip_multiply_plain_sum_rescale at this value's level nl >= 2 -- plaintexts at the default
+  // scale ps, the result at level nl - 1 with scale sc * ps / q_{nl-1}: the values of the calls per term, one rescale rounding
+  // instead of one per product, other words.  A term whose public value is all -1 (multiplyPlain negates there), a term at another
+  // level, CKKS scales that do not agree or nl = 1, and the options off take the calls per term.
   bool fusePlainSum() const override;
   std::unique_ptr<AbstractCiphertext> plainSum(const PlainSumCapable::Terms &terms) const override;
   std::unique_ptr<AbstractCiphertext> clone() const override;

@@ -19,7 +19,8 @@ HipCiphertextFactory::HipCiphertextFactory(unsigned int numElementsPerCiphertext
 HipCiphertextFactory::HipCiphertextFactory(const HipSchemeConfig &cfg)
     : ciphertextSlotSize(cfg.ringDegree), keySeed(cfg.seed), batch(cfg.batch), ckksMode(cfg.ckks), ckksScale(cfg.ckksScale),
       ckksBits(cfg.ckksBits), hostCkksCodec(cfg.hostCkksCodec), fuseRotateAdd(cfg.fuseRotateAdd),
-      fuseMultiplyPlainRescale(cfg.fuseMultiplyPlainRescale), lazyRelin(cfg.lazyRelinearize), fusePlainSums(cfg.fusePlainSum) {
+      fuseMultiplyPlainRescale(cfg.fuseMultiplyPlainRescale), lazyRelin(cfg.lazyRelinearize), fusePlainSums(cfg.fusePlainSum),
+      lazyRescale(cfg.lazyRescale) {
   if (!batch) throw std::runtime_error("HipCiphertextFactory: batch size must be at least 1");
   if (ckksMode && ckksBits.size() < 2) throw std::runtime_error("HipCiphertextFactory: a CKKS chain needs a data limb and the special prime");
   setupContext(cfg.device);
@@ -42,7 +43,7 @@ void HipCiphertextFactory::queueBatchedInput(std::vector<std::vector<int64_t>> p
 HipCiphertextFactory::~HipCiphertextFactory() {
   for (auto &e : plainCache) abc_hip_free(ctx, e.d_plain);
   plainNttCache.clear();  // the blocks go with their last holder: nobody else holds one past a call
-  for (auto &e : ckksPlainCache) abc_hip_free(ctx, e.d_plain);
+  ckksPlainCache.clear();
   abc_hip_ctx_destroy(ctx);
 }
 
@@ -250,16 +251,18 @@ std::unique_ptr<AbstractCiphertext> HipCiphertextFactory::createCkksCiphertext(c
   return ctxt;
 }
 
-const uint64_t *HipCiphertextFactory::cachedCkksPlaintext(const std::vector<double> &value, int level, double scale) const {
+std::shared_ptr<const HipCiphertextFactory::DeviceBlock> HipCiphertextFactory::cachedCkksPlaintextBlock(const std::vector<double> &value, int level,
+                                                                                                 double scale) const {
   for (const auto &e : ckksPlainCache)
-    if (e.level == level && e.scale == scale && e.values == value) return e.d_plain;
-  if (ckksPlainCache.size() >= kPlainCacheEntries) {
-    abc_hip_free(ctx, ckksPlainCache.front().d_plain);
-    ckksPlainCache.pop_front();
-  }
+    if (e.level == level && e.scale == scale && e.values == value) return e.block;
+  if (ckksPlainCache.size() >= kPlainCacheEntries) ckksPlainCache.pop_front();  // frees the block unless a caller still holds it
   uint64_t *d_plain = encodeCkks(expandVector(value), 1, level, scale);
-  ckksPlainCache.push_back(CachedCkksPlain{value, level, scale, d_plain});
-  return ckksPlainCache.back().d_plain;
+  ckksPlainCache.push_back(CachedCkksPlain{value, level, scale, std::make_shared<const DeviceBlock>(ctx, d_plain)});
+  return ckksPlainCache.back().block;
+}
+
+const uint64_t *HipCiphertextFactory::cachedCkksPlaintext(const std::vector<double> &value, int level, double scale) const {
+  return cachedCkksPlaintextBlock(value, level, scale)->p;
 }
 
 void HipCiphertextFactory::decryptCiphertextRealBatch(AbstractCiphertext &abstractCiphertext, std::vector<std::vector<double>> &out) const {

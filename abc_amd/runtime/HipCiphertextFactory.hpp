@@ -44,11 +44,16 @@ struct HipSchemeConfig {
   bool lazyRelinearize = false;
   // BFV `x *** p +++ y *** q (+++ ...)` as ONE abc_hip_bfv_multiply_plain_sum (HipCiphertext::plainSum; CircuitRuntime recognises the
   // run): one inverse transform for the sum, public values transformed once and cached.  The words are those of multiplyPlain per
-  // product and addInplace, so it stays on; off is for A/B runs and tests.  CKKS never fuses (multiplyPlain rescales per product)
+  // product and addInplace, so it stays on; off is for A/B runs and tests.  CKKS fuses only with lazyRescale below (multiplyPlain
+  // rescales per product)
   // Recorded circuits: a recording holds the device pointers of the cached plaintexts it was recorded with (up to 32 per plainSum
   // node; plainCache's single pointers likewise).  Public values used between compile and the last replay must not push those out of
   // the 32-entry caches: a program that cycles through more distinct public values than that replays recordings before it does
   bool fusePlainSum = true;
+  // CKKS `x *** p +++ y *** q (+++ ...)` as ONE abc_hip_multiply_plain_sum_rescale (HipCiphertext::plainSum; needs fusePlainSum): the
+  // sum of the products is rescaled once.  OFF by default, like lazyRelinearize: the result decrypts to the same values, with one
+  // rescale rounding instead of one per product, but its words are not those of multiplyPlain per product and addInplace
+  bool lazyRescale = false;
 };
 
 class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapable {
@@ -107,11 +112,14 @@ class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapab
   mutable size_t lazyMulSums = 0;  // abc_hip_mul_sum_relin calls issued by HipCiphertext::mulSum
   bool fusePlainSums = true;
   mutable size_t plainSums = 0;  // abc_hip_bfv_multiply_plain_sum calls issued by HipCiphertext::plainSum
+  bool lazyRescale = false;
+  mutable size_t plainSumRescales = 0;  // abc_hip_multiply_plain_sum_rescale calls issued by HipCiphertext::plainSum
+  // oldest first; the block is shared with a caller that holds it (cachedCkksPlaintextBlock), as in plainNttCache
   struct CachedCkksPlain {
     std::vector<double> values;
     int level;
     double scale;
-    uint64_t *d_plain;
+    std::shared_ptr<const DeviceBlock> block;
   };
   mutable std::deque<CachedCkksPlain> ckksPlainCache;
 
@@ -154,6 +162,10 @@ class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapab
   void setFusePlainSum(bool on) { fusePlainSums = on; }
   [[nodiscard]] size_t plainSumCalls() const { return plainSums; }
   void countPlainSum() const { ++plainSums; }
+  [[nodiscard]] bool lazyRescales() const { return lazyRescale; }
+  void setLazyRescale(bool on) { lazyRescale = on; }
+  [[nodiscard]] size_t plainSumRescaleCalls() const { return plainSumRescales; }
+  void countPlainSumRescale() const { ++plainSumRescales; }
   [[nodiscard]] static constexpr size_t plainCacheEntries() { return kPlainCacheEntries; }
   // BFV: device plaintext [L][N], lifted and in NTT form, of public values, from the factory's cache (least recently used out
   // first).  The block lives as long as the cache or the caller holds it: hold it until the call that reads it has been enqueued
@@ -164,8 +176,12 @@ class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapab
   [[nodiscard]] uint64_t prime(int j) const { return chain[j]; }
   // slots a value may fill: N for BFV (two rows of N/2), N/2 for CKKS (one row; rotateRows rotates it cyclically)
   [[nodiscard]] unsigned int usableSlots() const { return ckksMode ? ciphertextSlotSize / 2 : ciphertextSlotSize; }
-  // CKKS: device plaintext [level][N] (NTT form) of public values at a given level and scale, from the factory's cache
+  // CKKS: device plaintext [level][N] (NTT form) of public values at a given level and scale, from the factory's cache: valid until
+  // kPlainCacheEntries further distinct operands have been encoded (the oldest entry goes on a miss; release is stream-ordered)
   const uint64_t *cachedCkksPlaintext(const std::vector<double> &value, int level, double scale) const;
+  // the same entry as a shared block, for a caller that gathers several before one call (HipCiphertext::plainSum): a later miss of
+  // the same gathering may push the entry out of the cache, the block lives until its last holder lets go
+  std::shared_ptr<const DeviceBlock> cachedCkksPlaintextBlock(const std::vector<double> &value, int level, double scale) const;
   // CKKS: all slot values of instance 0 as doubles (decryptCiphertext rounds them to the interface's int64)
   void decryptCiphertextReal(AbstractCiphertext &abstractCiphertext, std::vector<double> &out) const;
   void decryptCiphertextRealBatch(AbstractCiphertext &abstractCiphertext, std::vector<std::vector<double>> &out) const;

@@ -80,6 +80,8 @@ int abc_hip_ctx_reload_env(abc_hip_ctx *ctx);
 #define ABC_HIP_ROUTE_DIAG_MATVEC_BSGS 13 /* CKKS: the baby rotation's route (as ABC_HIP_ROUTE_ROTATE, out of place), macsum=kernel / macsum=per_term, then the giant step's add=fused / add=separate; per-chunk fields: the first group's */
 #define ABC_HIP_ROUTE_BFV_PLAIN_SUM 14 /* BFV: plainsum=fused / plainsum=ntt_domain for abc_hip_bfv_multiply_plain_sum of `count` ciphertexts */
 #define ABC_HIP_ROUTE_BFV_MATVEC_BSGS 15 /* BFV: the baby rotation's route (as ABC_HIP_ROUTE_ROTATE, out of place), the plainsum= of an inner sum, then the giant step's add=fused / add=separate; per-chunk fields and the group: those of a one-step baby list */
+#define ABC_HIP_ROUTE_PLAIN_SUM_RESCALE 16 /* CKKS, nl >= 2: the rescale's route plus sumrescale=fused / sumrescale=separate, for a sum of up to four terms over `count` size-2 ciphertexts (a longer sum is separate unless ABC_HIP_PLAIN_SUM_RESCALE_TERMS is set) */
+#define ABC_HIP_ROUTE_DIAG_MATVEC_BSGS_RESCALE 17 /* CKKS, nl >= 2: the baby rotation's route at nl, sumrescale=, then the giant step's route at nl - 1 with add=fused / add=separate; per-chunk fields: the first group's.  Two key-switch routes in one string: 160 bytes hold any */
 int abc_hip_route(abc_hip_ctx *ctx, int op, int nl, size_t count, int in_place, char *buf, size_t cap);
 
 /* ---- device memory (so that FFI callers need no HIP runtime binding) ----
@@ -316,6 +318,36 @@ int abc_hip_rotate_plain(abc_hip_ctx *ctx, const uint64_t *d_plain, uint64_t *d_
  * with nothing written.  The step lists are read during the call only.  Capturable like abc_hip_rotate_add. */
 int abc_hip_diag_matvec_bsgs(abc_hip_ctx *ctx, const uint64_t *d_in, const uint64_t *d_diags, size_t diag_stride, const int *h_baby,
                              int n_baby, const int *h_giant, int n_giant, uint64_t *d_out, int nl, size_t count);
+/* CKKS only, nl >= 2: a plaintext-weighted sum with ONE rescale behind it (a linear layer):
+ *   d_out [count][size][nl-1][N] = rescale( (d_addend or 0) + plain_0 (.) ct_0 + ... + plain_{K-1} (.) ct_{K-1} ),  size = 2 or 3.
+ * Operands exactly as abc_hip_multiply_plain_sum takes them; d_addend is [count][size][nl][N].  Bit-identical to
+ * abc_hip_multiply_plain_sum into a temporary followed by abc_hip_rescale; n_terms == 1 without an addend gives the words of
+ * abc_hip_multiply_plain_rescale.  The same VALUES as a rescale per product, with one rescale rounding instead of K -- other words.
+ * Route (abc_hip_route, ABC_HIP_ROUTE_PLAIN_SUM_RESCALE): sumrescale=fused -- the K-term forms of the two LDS-resident rescale
+ * kernels (rings 2^10 .. 2^14) form the sum in their loads, so it never reaches memory -- or sumrescale=separate -- the whole sum
+ * into a context arena by the K-term kernel of abc_hip_multiply_plain_sum, then the rescale: N >= 2^15, ABC_HIP_NO_FUSED=1,
+ * ABC_HIP_NO_ISPLIT=1 on a chain with a prime above 2^50, ABC_HIP_NO_PLAIN_SUM_RESCALE_FUSION=1, ABC_HIP_NO_PLAIN_MAC_SUM=1, and
+ * where the measurement has the two steps as fast or faster: more than four terms, fewer than 256 polynomials (count * size) or
+ * fewer than 2^20 coefficients among them.  ABC_HIP_PLAIN_SUM_RESCALE_TERMS=t (0 .. 8) fuses at every batch and term count: the
+ * pair takes the last t terms at most and the sum of the others, formed in the arena, as its carry.  n_terms == 0
+ * writes the rescaled addend, or zeros without one; count == 0 succeeds and enqueues nothing.  Fails with nothing written or
+ * enqueued for: a BFV context, nl < 2 or a bad level, size or stride, n_terms < 0, a null term pointer, d_out overlapping any ct_k,
+ * plain_k or d_addend (the shapes differ: equality is no exception).  Capturable, under the "run once eagerly first" rule of
+ * abc_hip_graph_begin. */
+int abc_hip_multiply_plain_sum_rescale(abc_hip_ctx *ctx, const uint64_t *const *h_ct, const uint64_t *const *h_plain, size_t plain_stride,
+                                       int n_terms, const uint64_t *d_addend, uint64_t *d_out, int size, int nl, size_t count);
+/* CKKS only, nl >= 2: abc_hip_diag_matvec_bsgs with every inner sum rescaled BEFORE its giant rotation:
+ *   d_out [count][2][nl-1][N] = sum over j of rotate( rescale( sum over i of D[j * n_baby + i] (.) rotate(d_in, h_baby[i]) ),  h_giant[j] ).
+ * The n_giant key switches of the giant steps run at nl - 1 limbs and the result arrives rescaled: another ciphertext than
+ * abc_hip_rescale(abc_hip_diag_matvec_bsgs(...)), word for word, that decrypts to the same values.  Rows pre-rotated and laid out as
+ * for abc_hip_diag_matvec_bsgs (nl limbs are read).  Sequence: the baby rotations at nl into an arena; per giant step one
+ * abc_hip_multiply_plain_sum_rescale into a second arena; then d_out = d_out + rotate(inner_j, h_giant[j]) at nl - 1 as
+ * abc_hip_rotate_add does.  A giant step of 0 writes d_out directly where it is the first, else abc_hip_add adds it.  Bit-identical
+ * to that sequence of calls.  Order, duplicates, groups, empty lists, count == 0, the checks before the first launch and the
+ * refusals as in abc_hip_diag_matvec_bsgs, and nl < 2.  Route: ABC_HIP_ROUTE_DIAG_MATVEC_BSGS_RESCALE.  Capturable like
+ * abc_hip_rotate_add. */
+int abc_hip_diag_matvec_bsgs_rescale(abc_hip_ctx *ctx, const uint64_t *d_in, const uint64_t *d_diags, size_t diag_stride, const int *h_baby,
+                                     int n_baby, const int *h_giant, int n_giant, uint64_t *d_out, int nl, size_t count);
 /* ---- BFV: plaintext-weighted sums with ONE inverse transform ----
  * A BFV Evaluator::multiply_plain (:159,:196) is INTT(NTT(ct) (.) NTT(lift(plain))) per limb.  The inverse transform is linear and
  * every step is exact modulo q_i, so a weighted sum is accumulated in NTT form and inverted once, with weights transformed once. */

@@ -366,6 +366,124 @@ def matvec_bsgs_ab(res, only, rng):
         g.close()
 
 
+def _env_rounds(g, res, names, fns, envs, route_op, nl, B, reps, extra=None):
+    """the variants in turn, five rounds, variant i under the environment envs[i] (read by reload_env, cleared afterwards).  The first run
+    of each sizes its arenas and is left out of its minimum and median."""
+    runs, route = {k: [] for k in names}, {}
+    keys = sorted({k for e in envs for k in e})
+    for _ in range(5):
+        for name, fn, env in zip(names, fns, envs):
+            for k in keys:
+                os.environ.pop(k, None)
+            os.environ.update(env)
+            g.reload_env()
+            route[name] = g.route(route_op, nl, B)
+            runs[name].append(timeit(g, fn, reps))
+    for k in keys:
+        os.environ.pop(k, None)
+    g.reload_env()
+    for i, (k, ms) in enumerate(runs.items()):
+        kept = ms[1:]
+        res[k] = {"batch": B, "ms": min(kept), "ms_median": sorted(kept)[len(kept) // 2], "ms_spread": max(kept) - min(kept), "ms_runs": ms,
+                  "us_per_ct": min(kept) * 1e3 / B, "route": route[k], "env": envs[i]}
+        res[k].update(extra[i] if extra else {})
+        note = "  [%s]" % ", ".join("%s %s" % kv for kv in extra[i].items()) if extra else ""
+        print("%-50s %s ms / %d  (%s)%s" % (k, " ".join("%8.3f" % v for v in ms), B, route[k], note), flush=True)
+
+
+def plain_sum_rescale_ab(res, only, rng):
+    """rescale(sum over K terms of plain_k (.) ct_k), one plaintext per term for the batch, alternating in one process, five runs each:
+    (a) `two_calls`: abc_hip_multiply_plain_sum into a temporary, then abc_hip_rescale -- what a caller had before the call existed;
+    (b) `separate`: abc_hip_multiply_plain_sum_rescale under ABC_HIP_NO_PLAIN_SUM_RESCALE_FUSION=1;
+    (c) `default`: the call as the route sends it (abc_route.hpp, route_plain_sum_rescale: the rule these numbers gave);
+    (d) `fused8` / `fused4` / `fused2` / `fused0`: the call with the fused pair at every shape, taking at most that many terms
+        (ABC_HIP_PLAIN_SUM_RESCALE_TERMS; 0: the carry alone), the streaming kernel the ones before."""
+    shapes = [  # tag, context, levels, batches
+        ("ckks14", lambda: capi.Context(capi.CKKS, 16384, capi.create_primes(16384, [50, 40, 40, 40, 50])), (4, 3), (512, 128, 64, 32)),
+        ("ckks12", lambda: capi.Context(capi.CKKS, 4096, capi.create_primes(4096, [50, 40, 40, 50])), (3,), (1024, 128, 64)),
+        ("ckks10", lambda: capi.Context(capi.CKKS, 1024, capi.create_primes(1024, [50, 40, 40, 50])), (3,), (1024, 256)),
+    ]
+    fused = (8, 4, 2, 0)
+    kinds = ("two_calls", "separate", "default") + tuple("fused%d" % f for f in fused)
+    envs = ({}, {"ABC_HIP_NO_PLAIN_SUM_RESCALE_FUSION": "1"}, {}) + tuple({"ABC_HIP_PLAIN_SUM_RESCALE_TERMS": str(f)} for f in fused)
+    for tag, make, levels, batches in shapes:
+        if only and only not in "%s_plain_sum_rescale" % tag and "plain_sum_rescale" not in only:
+            continue
+        g = make()
+        for nl in levels:
+            for B in batches:
+                cb, zero = C.c_size_t(B), C.c_size_t(0)
+                first, nb = rand_ct(g, rng, B, 2, nl)
+                pool = [first]
+                for _ in range(15):
+                    pool.append(g.alloc(nb))
+                    g.op("memcpy_d2d", pool[-1].ptr, first.ptr, C.c_size_t(nb))
+                plains = [rand_ct(g, rng, 1, 1, nl)[0] for _ in range(16)]  # [nl][N] each
+                tmp, out = g.alloc(nb), g.alloc(nb)
+                for K in (1, 2, 3, 4, 6, 8, 16):
+                    names = ["%s_L%d_b%d_plain_sum_rescale_K%d_%s" % (tag, nl, B, K, kind) for kind in kinds]
+                    if not any(only in k for k in names):
+                        continue
+                    pc, pp = g.term_pointers([x.ptr for x in pool[:K]]), g.term_pointers([x.ptr for x in plains[:K]])
+
+                    def two_calls():
+                        g.op("multiply_plain_sum", pc, pp, zero, K, None, tmp.ptr, 2, nl, cb)
+                        g.op("rescale", tmp.ptr, out.ptr, 2, nl, cb)
+
+                    def one_call():
+                        g.op("multiply_plain_sum_rescale", pc, pp, zero, K, None, out.ptr, 2, nl, cb)
+                    _env_rounds(g, res, names, (two_calls,) + (one_call,) * (len(kinds) - 1), envs, "plain_sum_rescale", nl, B, 10 if B * K >= 256 else 50)
+                    base = res[names[0]]
+                    print("    two calls / variant: " + ", ".join("%s %.2f" % (kind, base["ms_median"] / res[k]["ms_median"]) for kind, k in zip(kinds[1:], names[1:])) +
+                          "   (spread of the two calls: %.3f ms)" % base["ms_spread"], flush=True)
+                del pool, first, plains, tmp, out
+        g.close()
+
+
+def matvec_bsgs_rescale_ab(res, only, rng):
+    """rescale(abc_hip_diag_matvec_bsgs(...)) against abc_hip_diag_matvec_bsgs_rescale on the same pre-rotated rows, as a square grid (16 =
+    4 x 4, 64 = 8 x 8), alternating in one process, five runs each; the default key set, so both pay the same NAF chains.  Printed with
+    each time: the key switches and the limb count they run at (baby steps at nl on both sides; giant steps at nl against nl - 1)."""
+    shapes = [  # tag, context, level, batches
+        ("ckks14", lambda: capi.Context(capi.CKKS, 16384, capi.create_primes(16384, [50, 40, 40, 40, 50])), 3, (512, 32)),
+        ("ckks15", lambda: capi.Context(capi.CKKS, 32768, capi.create_primes(32768, [50, 40, 40, 50])), 3, (256,)),
+    ]
+    kinds = ("rescale_after", "rescale_before")
+    for tag, make, nl, batches in shapes:
+        if only and only not in "%s_matvec_bsgs_rescale" % tag and "matvec_bsgs_rescale" not in only:
+            continue
+        g = make()
+        g.keygen(1)
+        for B in batches:
+            cb = C.c_size_t(B)
+            a, nb = rand_ct(g, rng, B, 2, nl)
+            d, _ = rand_ct(g, rng, 64, 1, nl)  # [64][nl][N]: the words do not matter to the time
+            tmp, out = g.alloc(nb), g.alloc(nb)
+            for side in (4, 8):
+                names = ["%s_L%d_b%d_matvec_bsgs_rescale_%dx%d_%s" % (tag, nl, B, side, side, kind) for kind in kinds]
+                if not any(only in k for k in names):
+                    continue
+                baby, giant = list(range(side)), [side * j for j in range(side)]
+                c_baby, c_giant = (C.c_int * side)(*baby), (C.c_int * side)(*giant)
+                stride = C.c_size_t(nl * g.n)
+
+                def after():
+                    g.op("diag_matvec_bsgs", a.ptr, d.ptr, stride, c_baby, side, c_giant, side, tmp.ptr, nl, cb)
+                    g.op("rescale", tmp.ptr, out.ptr, 2, nl, cb)
+
+                def before():
+                    g.op("diag_matvec_bsgs_rescale", a.ptr, d.ptr, stride, c_baby, side, c_giant, side, out.ptr, nl, cb)
+                kb, kg = _key_switches(g, baby), _key_switches(g, giant)
+                extra = ({"key_switches": "%d at %d limbs + %d at %d" % (kb, nl, kg, nl), "rescales": 1},
+                         {"key_switches": "%d at %d limbs + %d at %d" % (kb, nl, kg, nl - 1), "rescales": side})
+                _env_rounds(g, res, names, (after, before), ({}, {}), "diag_matvec_bsgs_rescale", nl, B, 3, extra)
+                res[names[0]]["route"] = g.route("diag_matvec_bsgs", nl, B) + ", then " + g.route("rescale", nl, B)
+                print("    rescale after / rescale before: %.2f   (spread of rescale after: %.3f ms)" %
+                      (res[names[0]]["ms_median"] / res[names[1]]["ms_median"], res[names[0]]["ms_spread"]), flush=True)
+            del a, d, tmp, out
+        g.close()
+
+
 def _rounds(g, res, names, fns, routes, B, reps, extra=None):
     """fns[0], fns[1], ..., fns[0], ...: five runs each in one process.  The first run of EVERY variant sizes its arenas and is left
     out of its minimum, median and ratio (it is still printed, first in its row)."""
@@ -647,14 +765,17 @@ def main():
     # runs nothing else (and sets up no other context), and a filter that does not say "bfv_" -- `--only matvec_bsgs` -- leaves them out
     bfv_sums = any(x in only for x in ("bfv_plain_sum", "bfv_matvec_bsgs"))
     if not bfv_sums:
-        if not (only and any(x in only for x in ("mul_sum", "plain_mac_sum", "matvec_bsgs"))):  # those A/Bs have their own contexts and operand batches: nothing else is set up
+        if not (only and any(x in only for x in ("mul_sum", "plain_mac_sum", "matvec_bsgs", "plain_sum_rescale"))):  # those A/Bs have their own contexts and operand batches: nothing else is set up
             single_ops(res, only, rng)
         rotate_add_ab(res, only, rng)
         rotate_mac_ab(res, only, rng)
         mulplain_rescale_ab(res, only, rng)
         mul_sum_ab(res, only, rng)
         plain_mac_sum_ab(res, only, rng)
-        matvec_bsgs_ab(res, only, rng)
+        plain_sum_rescale_ab(res, only, rng)
+        if "matvec_bsgs_rescale" not in only:  # a filter that names the rescaling form sets up no context of the plain one
+            matvec_bsgs_ab(res, only, rng)
+        matvec_bsgs_rescale_ab(res, only, rng)
         keyswitch_batch1(res, only, rng)
     if not only or "bfv_" in only:
         bfv_plain_sum_ab(res, only, rng)
