@@ -43,6 +43,8 @@ SYMBOLS = [
     "abc_hip_multiply_plain_sum", "abc_hip_rotate_plain", "abc_hip_diag_matvec_bsgs",
     "abc_hip_bfv_plain_to_ntt", "abc_hip_bfv_multiply_plain_sum", "abc_hip_bfv_diag_matvec_bsgs",
     "abc_hip_multiply_plain_sum_rescale", "abc_hip_diag_matvec_bsgs_rescale",
+    "abc_hip_ckks_const_words", "abc_hip_multiply_const_sum", "abc_hip_multiply_const_sum_rescale",
+    "abc_hip_ckks_poly_eval_depth", "abc_hip_ckks_poly_eval",
 ]
 
 
@@ -96,6 +98,14 @@ def lib():
         if hasattr(L, "abc_hip_multiply_plain_sum_rescale"):
             L.abc_hip_multiply_plain_sum_rescale.argtypes = L.abc_hip_multiply_plain_sum.argtypes
             L.abc_hip_diag_matvec_bsgs_rescale.argtypes = L.abc_hip_diag_matvec_bsgs.argtypes
+        if hasattr(L, "abc_hip_multiply_const_sum"):
+            L.abc_hip_ckks_const_words.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int, u64p]
+            L.abc_hip_multiply_const_sum.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), u64p, C.c_int, u64p, C.c_void_p,
+                                                     C.c_void_p, C.c_int, C.c_int, C.c_size_t]
+            L.abc_hip_multiply_const_sum_rescale.argtypes = L.abc_hip_multiply_const_sum.argtypes
+            L.abc_hip_ckks_poly_eval_depth.argtypes = [C.c_int]
+            L.abc_hip_ckks_poly_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.c_int, C.c_double, C.c_void_p,
+                                                 C.c_int, C.c_size_t]
         L.abc_hip_encrypt_keyed.argtypes =[C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_size_t]
         L.abc_hip_keygen_keyed.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
         L.abc_hip_keyed_small.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_size_t]
@@ -227,7 +237,8 @@ class Context:
 
     ROUTE_OPS = {"mul_relin": 0, "keyswitch": 1, "relinearize": 1, "rotate": 2, "rescale": 3, "multiply": 4, "rotate_add": 5,
                  "rotate_mac_plain": 7, "multiply_plain_rescale": 10, "mul_sum_relin": 12, "diag_matvec_bsgs": 13,
-                 "bfv_plain_sum": 14, "bfv_matvec_bsgs": 15, "plain_sum_rescale": 16, "diag_matvec_bsgs_rescale": 17}
+                 "bfv_plain_sum": 14, "bfv_matvec_bsgs": 15, "plain_sum_rescale": 16, "diag_matvec_bsgs_rescale": 17,
+                 "const_sum_rescale": 18, "poly_eval": 19}
 
     def route(self, op, nl, count=1, in_place=False):
         """the kernel sequence such a call takes, as the string of abc_route.hpp's formatter"""
@@ -537,6 +548,101 @@ class Context:
                 b.free()
         one = (cts and np.ndim(cts[0]) == 3) or (not cts and addend is not None and np.ndim(addend) == 3)
         return r[0] if one else r
+
+    # ---- scalar constants and polynomial evaluation (CKKS) ----
+    def const_words(self, value, scale, nl=None):
+        """the words of the constant `value` at `scale` (abc_hip_ckks_const_words): uint64 [nl], round(value * scale) mod q_j; no GPU work"""
+        nl = self.L if nl is None else int(nl)
+        out = np.zeros(max(nl, 1), dtype=np.uint64)
+        _chk(lib().abc_hip_ckks_const_words(self.h, float(value), float(scale), nl, out.ctypes.data_as(u64p)))
+        return out[:nl]
+
+    @staticmethod
+    def const_sum_args(weights, const, ct_nl, n_terms, nl):
+        """the host operands of abc_hip_multiply_const_sum as ctypes values: (h_ct_nl or None, h_weights, h_const or None); keep the
+        returned arrays alive across the call"""
+        w = np.ascontiguousarray(weights, dtype=np.uint64).reshape(n_terms, nl) if n_terms else np.zeros((1, max(nl, 1)), dtype=np.uint64)
+        k = None if const is None else np.ascontiguousarray(const, dtype=np.uint64).reshape(nl)
+        l = None if ct_nl is None else (C.c_int * max(n_terms, 1))(*[int(x) for x in ct_nl])
+        return l, w, k
+
+    def _const_sum(self, name, drop, cts, weights, const, addend, size, nl, count):
+        c4 = [self._batch(x, 3) for x in cts]
+        a4 = None if addend is None else self._batch(addend, 3)
+        if nl is None:
+            nl = a4.shape[2] if a4 is not None else min(x.shape[2] for x in c4) if c4 else None
+        if nl is None:
+            raise ValueError("an empty sum without an addend needs nl (and size, count)")
+        first = c4[0] if c4 else a4
+        if first is not None:
+            count, size = first.shape[0], first.shape[1]
+        if any(x.shape[:2] != (count, size) or x.shape[3] != self.n for x in c4) or (a4 is not None and a4.shape != (count, size, nl, self.n)):
+            raise ValueError("every ciphertext is [count][size][its level][N], the addend at nl")
+        ct_nl = [x.shape[2] for x in c4]
+        l, w, k = self.const_sum_args(weights, const, ct_nl, len(c4), nl)
+        bufs = {}
+        for orig, arr in zip(cts, c4):  # one upload per distinct array: a repeated operand stays one pointer
+            if id(orig) not in bufs:
+                bufs[id(orig)] = self.upload(arr)
+        ab = self.upload(a4) if a4 is not None else None
+        oshape = (count, size, nl - drop, self.n)
+        out = self.alloc(max(int(np.prod(oshape)) * 8, 8))
+        try:
+            pc = self.term_pointers([bufs[id(x)].ptr for x in cts])
+            self.op(name, pc, l, w.ctypes.data_as(u64p), len(c4), None if k is None else k.ctypes.data_as(u64p), ab.ptr if ab else None, out.ptr,
+                    size, nl, C.c_size_t(count))
+            r = self.download(out, oshape)
+        finally:
+            for b in list(bufs.values()) + [out] + ([ab] if ab else []):
+                b.free()
+        one = (cts and np.ndim(cts[0]) == 3) or (not cts and addend is not None and np.ndim(addend) == 3)
+        return r[0] if one else r
+
+    def multiply_const_sum(self, cts, weights, const=None, addend=None, size=2, nl=None, count=1):
+        """(addend or 0) + const (component 0) + sum over k of weights[k] * cts[k] as one call (abc_hip_multiply_const_sum), CKKS.  cts[k]:
+        [count][size][its own level >= nl][N] (or one ciphertext), its first nl limbs read; weights [K][nl] and const [nl]: words as
+        const_words makes them.  nl: the lowest level among the terms unless given; size / nl / count: the shape of an empty sum"""
+        return self._const_sum("multiply_const_sum", 0, cts, weights, const, addend, size, nl, count)
+
+    def multiply_const_sum_rescale(self, cts, weights, const=None, addend=None, size=2, nl=None, count=1):
+        """rescale(multiply_const_sum(...)) as one call (abc_hip_multiply_const_sum_rescale): the result [count][size][nl - 1][N]"""
+        return self._const_sum("multiply_const_sum_rescale", 1, cts, weights, const, addend, size, nl, count)
+
+    def multiply_const(self, ct, value, scale):
+        """ct times the constant `value` at `scale`: the K = 1 form of multiply_const_sum (no encode, no plaintext); the result's scale is
+        the ciphertext's times `scale`"""
+        nl = np.shape(ct)[-2]
+        return self.multiply_const_sum([ct], [self.const_words(value, scale, nl)], nl=nl)
+
+    def add_const(self, ct, value, scale):
+        """ct plus the constant `value` at `scale` (the ciphertext's own): the K = 0 form of multiply_const_sum, component 0 only"""
+        nl = np.shape(ct)[-2]
+        return self.multiply_const_sum([], None, const=self.const_words(value, scale, nl), addend=ct, nl=nl)
+
+    @staticmethod
+    def poly_eval_depth(degree):
+        """levels a polynomial of this degree consumes (abc_hip_ckks_poly_eval_depth): ceil(log2 degree) + 1"""
+        d = int(lib().abc_hip_ckks_poly_eval_depth(int(degree)))
+        if d < 0:
+            raise AbcHipError(lib().abc_hip_last_error().decode())
+        return d
+
+    def poly_eval(self, x, x_scale, coeffs, out_scale):
+        """c_0 + c_1 x + ... + c_d x^d on x [count][2][nl][N] (or one ciphertext) at x_scale, by the fixed sequence of
+        abc_hip_ckks_poly_eval: the result [count][2][nl - poly_eval_depth(d)][N] at out_scale"""
+        a4 = self._batch(x, 3)
+        count, _, nl, _ = a4.shape
+        co = (C.c_double * max(len(coeffs), 1))(*[float(v) for v in coeffs])
+        degree = len(coeffs) - 1
+        onl = nl - (self.poly_eval_depth(degree) if degree >= 1 else 1)
+        xb = self.upload(a4)
+        out = self.alloc(max(count * 2 * max(onl, 0) * self.n * 8, 8))
+        try:
+            self.op("ckks_poly_eval", xb.ptr, C.c_double(x_scale), co, degree, C.c_double(out_scale), out.ptr, nl, C.c_size_t(count))
+            r = self.download(out, (count, 2, onl, self.n))
+        finally:
+            xb.free(); out.free()
+        return r if np.ndim(x) == 4 else r[0]
 
     def rotate_plain(self, plain, steps):
         """the slot rotation of CKKS plaintexts [rows][nl][N] (or [nl][N]) in NTT form (abc_hip_rotate_plain): no key, any sign of steps"""

@@ -6,6 +6,7 @@
 // tables (bit-reversed powers of the minimal primitive 2N-th root, with Shoup quotients), the BEHZ
 // auxiliary bases {B, m_sk, gamma, m~ = 2^32} and every scalar constant the kernels need, and uploads
 // them once; nothing is recomputed per operation.
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -48,6 +49,7 @@ void read_switches(abc_hip_ctx *c) {
   s.no_tensor_sum = env_on("ABC_HIP_NO_TENSOR_SUM");
   s.no_plain_mac_sum = env_on("ABC_HIP_NO_PLAIN_MAC_SUM");
   s.no_plain_sum_rescale_fusion = env_on("ABC_HIP_NO_PLAIN_SUM_RESCALE_FUSION");
+  s.no_const_mac_sum = env_on("ABC_HIP_NO_CONST_MAC_SUM");
   s.main_two_per_cu = env_on("ABC_HIP_MAIN_TWO_PER_CU");
   s.host_sampling = env_on("ABC_HIP_HOST_SAMPLING");
   if (const char *e = std::getenv("ABC_HIP_CHUNK")) s.chunk = (size_t)std::atol(e);
@@ -56,6 +58,7 @@ void read_switches(abc_hip_ctx *c) {
   if (const char *e = std::getenv("ABC_HIP_PASS0_TARGET_LIMIT")) s.pass0_target_limit = (size_t)std::atol(e);
   if (const char *e = std::getenv("ABC_HIP_BFV_SCRATCH_MB")) s.bfv_scratch_mb = (size_t)std::atol(e);
   if (const char *e = std::getenv("ABC_HIP_PLAIN_SUM_RESCALE_TERMS")) s.plain_sum_rescale_terms = std::atoi(e);
+  if (const char *e = std::getenv("ABC_HIP_CONST_SUM_RESCALE_FUSED")) s.const_sum_rescale_fused = std::atoi(e) ? 1 : 0;
   if (const char *e = std::getenv("ABC_HIP_LANES")) {
     s.lanes = std::atoi(e);
     if (s.lanes < 1) s.lanes = 1;
@@ -669,6 +672,88 @@ static int plain_sum_rescale(abc_hip_ctx *c, const std::vector<const u64 *> &ct,
   return launch_plain_sum_rescale(c, r.rescale, ct.data() + lead, plain.data() + lead, plain_stride, K - lead, carry, out, size, nl, count);
 }
 
+// value * scale, rounded to the nearest integer (ties away from zero), modulo the first nl data primes: the words of the constant
+// `value` at `scale` in NTT form (every word of limb j is w[j]).  |r| < 2^62 is the encoder's own limit.  No GPU work.
+static int const_words(abc_hip_ctx *c, const char *op, double value, double scale, int nl, u64 *w) {
+  const double r = std::round(value * scale);
+  if (!std::isfinite(r)) { set_error(std::string(op) + ": value * scale is not finite"); return 1; }
+  if (std::fabs(r) >= 4611686018427387904.0) { set_error(std::string(op) + ": |value * scale| must stay below 2^62"); return 1; }
+  const long long ri = (long long)r;
+  const u64 mag = ri < 0 ? (u64)(-ri) : (u64)ri;
+  for (int j = 0; j < nl; j++) {
+    const u64 q = c->primes[j], m = mag % q;
+    w[j] = (ri < 0 && m) ? q - m : m;
+  }
+  return 0;
+}
+
+// out [count][size][nl][N] = (addend or 0) + cst (component 0) + sum over k of w[k] * ct[k] (CKKS); term k is [count][size][ct_nl[k]][N],
+// ct_nl[k] >= nl; w: [K][nl] words, cst: [nl] words or null; out may BE addend and overlaps nothing else (the caller has checked).
+// One K-term kernel, or -- kernel false -- the sequence a caller composes: per term the first nl limbs copied out where the term is
+// held higher (mod_switch; arena 6 behind the constant plaintext), the weight filled into a plaintext (arena 6), multiply_plain --
+// into `out` where nothing is carried yet, else into arena 2 and the add kernel -- and last add_plain of the filled constant.
+static int const_mac_sum(abc_hip_ctx *c, bool kernel, const std::vector<const u64 *> &ct, const std::vector<int> &ct_nl, const u64 *w, const u64 *cst,
+                         const u64 *addend, u64 *out, int size, int nl, size_t count) {
+  if (!count) return 0;
+  const size_t pw = (size_t)nl * c->n, words = count * size * pw, bytes = words * 8;
+  if (ct.empty() && !cst) {
+    if (!addend) ABC_HIP_CHECK(hipMemsetAsync(out, 0, bytes, c->stream));
+    else if (addend != out) ABC_HIP_CHECK(hipMemcpyAsync(out, addend, bytes, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+  }
+  if (kernel) return launch_ckks_const_mac_sum(c, ct.data(), ct_nl.data(), w, (int)ct.size(), cst, addend, out, size, nl, count);
+  bool raised = false;
+  for (int l : ct_nl) raised |= l > nl;
+  if (ensure_aux(c, 6, (pw + (raised ? words : 0)) * 8)) return 1;
+  if ((addend || ct.size() > 1) && ensure_aux(c, 2, bytes)) return 1;
+  u64 *plain = (u64 *)c->aux[6], *lowered = plain + pw;
+  const u64 *carry = addend;
+  for (size_t k = 0; k < ct.size(); k++) {
+    const u64 *src = ct[k];
+    if (ct_nl[k] > nl) {
+      if (launch_drop_to(c, src, lowered, ct_nl[k], nl, count * size)) return 1;
+      src = lowered;
+    }
+    if (launch_const_plain_fill(c, w + k * nl, plain, nl)) return 1;
+    u64 *dst = carry ? (u64 *)c->aux[2] : out;
+    if (ckks_multiply_plain(c, src, plain, 0, dst, size, nl, count)) return 1;
+    if (carry && launch_addsub(c, carry, dst, out, nl, count * size, 0)) return 1;
+    carry = out;
+  }
+  if (cst) {
+    if (!carry) {
+      ABC_HIP_CHECK(hipMemsetAsync(out, 0, bytes, c->stream));
+      carry = out;
+    }
+    if (launch_const_plain_fill(c, cst, plain, nl)) return 1;
+    if (ckks_add_plain(c, carry, plain, 0, out, size, nl, count, 0)) return 1;
+  }
+  return 0;
+}
+
+// out [count][size][nl-1][N] = rescale(const_mac_sum(...)) (CKKS, nl >= 2); out overlaps no operand (the caller has checked).  Fused
+// (route_const_sum_rescale: up to four terms, all at nl, where the measurement has it faster): the K-term forms of the two
+// LDS-resident rescale kernels take addend, constant and terms, and the sum never reaches memory.  Separate: the whole sum into arena
+// 1, then launch_rescale; arenas 2 and 6 are const_mac_sum's on its composed route.
+static int const_sum_rescale(abc_hip_ctx *c, const std::vector<const u64 *> &ct, const std::vector<int> &ct_nl, const u64 *w, const u64 *cst,
+                             const u64 *addend, u64 *out, int size, int nl, size_t count) {
+  if (!count) return 0;
+  const size_t N = (size_t)c->n, in_bytes = count * size * (size_t)nl * N * 8;
+  if (ct.empty() && !cst && !addend) {  // rescale(0) = 0
+    ABC_HIP_CHECK(hipMemsetAsync(out, 0, count * size * (size_t)(nl - 1) * N * 8, c->stream));
+    return 0;
+  }
+  if (ct.empty() && !cst) return launch_rescale(c, addend, out, size, nl, count);
+  bool raised = false;
+  for (int l : ct_nl) raised |= l > nl;
+  const ConstSumRescaleRoute r = route_const_sum_rescale(c->facts, nl, count * size, (int)ct.size(), raised);
+  if (r.fused) return launch_const_sum_rescale(c, r.rescale, ct.data(), w, (int)ct.size(), cst, addend, out, size, nl, count);
+  if (ensure_aux(c, 1, in_bytes)) return 1;
+  u64 *sum = (u64 *)c->aux[1];
+  if (const_mac_sum(c, route_const_mac_sum(c->facts, nl), ct, ct_nl, w, cst, addend, sum, size, nl, count)) return 1;
+  return launch_rescale(c, sum, out, size, nl, count);
+}
+
 // out = sum_j rotate( sum_i D[j * n_baby + i] (.) rotate(in, baby[i]), giant[j] ), in the order given (abc_hip.h).  The batch goes
 // in groups of ciphertexts (matvec_bsgs_group).  Per group: the baby rotations land in arena 3, one slab per non-zero step (step 0
 // is the input itself); per giant step the inner sum over the slabs lands in arena 4 and one rotate_tail adds its rotation to the
@@ -1210,11 +1295,14 @@ int abc_hip_route(abc_hip_ctx *c, int op, int nl, size_t count, int in_place, ch
   if (op == kRouteMulPlainRescale && (nl < 2 || c->scheme != ABC_HIP_SCHEME_CKKS)) { set_error("route: multiply_plain_rescale needs CKKS and nl >= 2"); return 1; }
   if (op == kRouteDiagMatvecBsgs && c->scheme != ABC_HIP_SCHEME_CKKS) { set_error("route: diag_matvec_bsgs needs CKKS"); return 1; }
   if ((op == kRoutePlainSumRescale || op == kRouteDiagMatvecBsgsRescale) && (nl < 2 || c->scheme != ABC_HIP_SCHEME_CKKS)) { set_error("route: multiply_plain_sum_rescale and diag_matvec_bsgs_rescale need CKKS and nl >= 2"); return 1; }
+  if ((op == kRouteConstSumRescale || op == kRoutePolyEval) && (nl < 2 || c->scheme != ABC_HIP_SCHEME_CKKS)) { set_error("route: multiply_const_sum_rescale and ckks_poly_eval need CKKS and nl >= 2"); return 1; }
   if ((op == kRouteBfvPlainSum || op == kRouteBfvMatvecBsgs) && c->scheme != ABC_HIP_SCHEME_BFV) { set_error("route: bfv_multiply_plain_sum and bfv_diag_matvec_bsgs need BFV"); return 1; }
   const int n = !buf                        ? -1
                 : op == kRouteDiagMatvecBsgs ? format_matvec_bsgs(buf, cap, c->facts, nl, count)
                 : op == kRoutePlainSumRescale ? format_plain_sum_rescale(buf, cap, c->facts, nl, count)
                 : op == kRouteDiagMatvecBsgsRescale ? format_matvec_bsgs_rescale(buf, cap, c->facts, nl, count)
+                : op == kRouteConstSumRescale ? format_const_sum_rescale(buf, cap, c->facts, nl, count)
+                : op == kRoutePolyEval       ? format_poly_eval(buf, cap, c->facts, nl, count)
                 : op == kRouteBfvPlainSum    ? format_bfv_plain_sum(buf, cap, c->facts, count)
                 : op == kRouteBfvMatvecBsgs  ? format_bfv_matvec_bsgs(buf, cap, c->facts, count)
                                              : format_op(buf, cap, c->facts, op, nl, count, in_place != 0);
@@ -1248,10 +1336,9 @@ int abc_hip_relinearize(abc_hip_ctx *c, const uint64_t *ct3, uint64_t *out2, int
   if (check_level(c, nl)) return 1;
   return relinearize(c, ct3, out2, nl, count);
 }
-int abc_hip_mul_relin(abc_hip_ctx *c, const uint64_t *a, const uint64_t *b, uint64_t *out, int nl, size_t count) {
-  CTX_GUARD(c);
-  if (check_level(c, nl)) return 1;
-  if (!c->d_relin) { set_error("mul_relin: no relinearisation key"); return 1; }
+// multiply + relinearise along the route of the level; the caller has checked the level and the key (abc_hip_mul_relin, and every
+// product of ckks_poly_eval)
+static int mul_relin(abc_hip_ctx *c, const uint64_t *a, const uint64_t *b, uint64_t *out, int nl, size_t count) {
   const MulRoute r = route_mul_relin(c->facts, nl);
   if (r.seq == Seq::bmul) return bmul_split(c, a, b, out, count, true);
   if (r.seq != Seq::generic) return launch_mul_relin(c, r.seq, a, b, out, nl, count);
@@ -1262,6 +1349,12 @@ int abc_hip_mul_relin(abc_hip_ctx *c, const uint64_t *a, const uint64_t *b, uint
   int rc = (c->scheme == ABC_HIP_SCHEME_CKKS) ? launch_ckks_tensor(c, a, b, t3, nl, count) : bfv_multiply(c, r.mul, a, b, t3, count);
   if (!rc) rc = launch_keyswitch(c, r.ks, ks_of_ciphertexts(c, t3, 3, c->d_relin, out, nl, count));  // as in relinearize
   return rc;
+}
+int abc_hip_mul_relin(abc_hip_ctx *c, const uint64_t *a, const uint64_t *b, uint64_t *out, int nl, size_t count) {
+  CTX_GUARD(c);
+  if (check_level(c, nl)) return 1;
+  if (!c->d_relin) { set_error("mul_relin: no relinearisation key"); return 1; }
+  return mul_relin(c, a, b, out, nl, count);
 }
 // what both sum-of-products calls check before anything is written or enqueued; exact_ok: a term may BE d_out (mul_sum_relin)
 static int check_mul_sum(abc_hip_ctx *c, const char *op, const uint64_t *const *h_a, const uint64_t *const *h_b, int n_terms, const uint64_t *out,
@@ -1556,6 +1649,159 @@ int abc_hip_mod_switch(abc_hip_ctx *c, const uint64_t *in, uint64_t *out, int si
   if (check_level(c, nl)) return 1;
   if (in == out) { set_error("mod_switch: d_out must not alias d_in (the output has one limb less per polynomial)"); return 1; }
   return launch_drop_last(c, in, out, size, nl, count);
+}
+
+// ---- scalar constants and polynomial evaluation (CKKS) ----
+int abc_hip_ckks_const_words(abc_hip_ctx *c, double value, double scale, int nl, uint64_t *h_words) {
+  if (!c) { set_error("null context"); return 1; }
+  if (c->scheme != ABC_HIP_SCHEME_CKKS) { set_error("ckks_const_words is a CKKS operation"); return 1; }
+  if (nl < 1 || nl > c->L) { set_error("limb count out of range for this context"); return 1; }
+  if (!h_words) { set_error("ckks_const_words: null output"); return 1; }
+  u64 w[kMaxLimbs];
+  if (const_words(c, "ckks_const_words", value, scale, nl, w)) return 1;  // nothing written on failure
+  std::memcpy(h_words, w, (size_t)nl * 8);
+  return 0;
+}
+// what both scalar-weighted sums check before anything is written or enqueued; out_nl: nl, or nl - 1 for the rescaled form, where
+// d_out may not even BE d_addend (the shapes differ)
+static int check_const_sum(abc_hip_ctx *c, const std::string &op, const uint64_t *const *h_ct, const int *h_ct_nl, const uint64_t *h_weights, int n_terms,
+                           const uint64_t *h_const, const uint64_t *addend, const uint64_t *out, int size, int nl, int out_nl, size_t count) {
+  if (c->scheme != ABC_HIP_SCHEME_CKKS) { set_error(op + " is a CKKS operation"); return 1; }
+  if (check_level(c, nl)) return 1;
+  if (out_nl < 1) { set_error(op + ": no limb left to drop"); return 1; }
+  if (size != 2 && size != 3) { set_error(op + ": size must be 2 or 3"); return 1; }
+  if ((ptrdiff_t)count < 0) { set_error(op + ": negative count"); return 1; }
+  if (n_terms < 0 || (n_terms && (!h_ct || !h_weights))) { set_error(op + ": bad term list"); return 1; }
+  if (!out && count) { set_error(op + ": null output"); return 1; }
+  const size_t N = (size_t)c->n, out_bytes = count * size * (size_t)out_nl * N * 8;
+  for (int k = 0; k < n_terms; k++) {
+    if (!h_ct[k]) { set_error(op + ": null term pointer"); return 1; }
+    const int l = h_ct_nl ? h_ct_nl[k] : nl;
+    if (l < nl || l > c->L) { set_error(op + ": a term's limb count must be in nl .. L"); return 1; }
+    for (int j = 0; j < nl; j++)
+      if (h_weights[(size_t)k * nl + j] >= c->primes[j]) { set_error(op + ": a weight word is not below its prime"); return 1; }
+    if (out_bytes && ranges_overlap(h_ct[k], count * size * (size_t)l * N * 8, out, out_bytes)) { set_error(op + ": d_out must not overlap a ciphertext term"); return 1; }
+  }
+  for (int j = 0; h_const && j < nl; j++)
+    if (h_const[j] >= c->primes[j]) { set_error(op + ": a constant word is not below its prime"); return 1; }
+  if (addend && !(out_nl == nl && addend == out) && out_bytes && ranges_overlap(addend, count * size * (size_t)nl * N * 8, out, out_bytes)) {
+    set_error(op + (out_nl == nl ? ": d_out may be d_addend, but must not overlap it otherwise" : ": d_out must not overlap d_addend (the output has one limb less per polynomial)"));
+    return 1;
+  }
+  return 0;
+}
+static std::vector<int> term_levels(const int *h_ct_nl, int n_terms, int nl) {
+  std::vector<int> v((size_t)n_terms, nl);
+  for (int k = 0; h_ct_nl && k < n_terms; k++) v[k] = h_ct_nl[k];
+  return v;
+}
+int abc_hip_multiply_const_sum(abc_hip_ctx *c, const uint64_t *const *h_ct, const int *h_ct_nl, const uint64_t *h_weights, int n_terms,
+                               const uint64_t *h_const, const uint64_t *addend, uint64_t *out, int size, int nl, size_t count) {
+  CTX_GUARD(c);
+  if (check_const_sum(c, "multiply_const_sum", h_ct, h_ct_nl, h_weights, n_terms, h_const, addend, out, size, nl, nl, count)) return 1;
+  return guarded([&] {
+    return const_mac_sum(c, route_const_mac_sum(c->facts, nl), std::vector<const u64 *>(h_ct, h_ct + n_terms), term_levels(h_ct_nl, n_terms, nl), h_weights,
+                         h_const, addend, out, size, nl, count);
+  });
+}
+int abc_hip_multiply_const_sum_rescale(abc_hip_ctx *c, const uint64_t *const *h_ct, const int *h_ct_nl, const uint64_t *h_weights, int n_terms,
+                                       const uint64_t *h_const, const uint64_t *addend, uint64_t *out, int size, int nl, size_t count) {
+  CTX_GUARD(c);
+  if (check_const_sum(c, "multiply_const_sum_rescale", h_ct, h_ct_nl, h_weights, n_terms, h_const, addend, out, size, nl, nl - 1, count)) return 1;
+  return guarded([&] {
+    return const_sum_rescale(c, std::vector<const u64 *>(h_ct, h_ct + n_terms), term_levels(h_ct_nl, n_terms, nl), h_weights, h_const, addend, out, size,
+                             nl, count);
+  });
+}
+
+static int ceil_log2(int k) {  // k >= 1
+  int e = 0;
+  while ((1 << e) < k) e++;
+  return e;
+}
+int abc_hip_ckks_poly_eval_depth(int degree) {
+  if (degree < 1) { set_error("ckks_poly_eval_depth: degree must be at least 1"); return -1; }
+  return ceil_log2(degree) + 1;
+}
+// The fixed sequence of abc_hip.h.  Everything a refusal depends on -- the levels, the scales, every weight -- is worked out on
+// the host before the first launch.  Per group of ciphertexts (arena_group: the POWERS, arena 5, stay within 4 GiB; the lowered factor,
+// the product and the last step's sum -- arenas 3, 4 and 1 -- are one ciphertext of at most nl limbs per member of the group each): power k, ascending, is
+// mul_relin of x^h and x^l at nl - e + 1 limbs -- x^l lowered into arena 3 where it is held higher -- into arena 4, then the
+// rescale into the power's slab of arena 5; the last step is const_sum_rescale over x (in place in d_x) and the slabs, each read at
+// its own level (arenas 1, 2, 6).
+static int poly_eval(abc_hip_ctx *c, const u64 *x, double x_scale, const double *coeffs, int degree, double out_scale, u64 *out, int nl, size_t count) {
+  const int d = degree, E = ceil_log2(d), m = nl - E;
+  const size_t N = (size_t)c->n;
+  std::vector<int> level(d + 1, nl), hi(d + 1, 0), lo(d + 1, 0);
+  std::vector<double> scale(d + 1, x_scale);
+  std::vector<char> need(d + 1, 0);
+  for (int k = 2; k <= d; k++) {
+    const int e = ceil_log2(k);
+    hi[k] = 1 << (e - 1), lo[k] = k - hi[k], level[k] = nl - e;
+    scale[k] = scale[hi[k]] * scale[lo[k]] / (double)c->primes[nl - e];
+  }
+  for (int k = 1; k <= d; k++) need[k] = coeffs[k] != 0.0;
+  for (int k = d; k >= 2; k--)
+    if (need[k]) need[hi[k]] = need[lo[k]] = 1;
+  const double top = out_scale * (double)c->primes[m - 1];
+  std::vector<int> terms;  // the powers with a non-zero coefficient: a zero weight adds nothing to any word
+  for (int k = 1; k <= d; k++)
+    if (coeffs[k] != 0.0) terms.push_back(k);
+  std::vector<u64> w(terms.size() * (size_t)m + 1), w0(m);
+  for (size_t i = 0; i < terms.size(); i++)
+    if (const_words(c, "ckks_poly_eval", coeffs[terms[i]], top / scale[terms[i]], m, w.data() + i * m)) return 1;
+  if (const_words(c, "ckks_poly_eval", coeffs[0], top, m, w0.data())) return 1;
+  if (!count) return 0;
+  size_t slab_limbs = 0;  // limbs per ciphertext polynomial pair over the powers kept
+  std::vector<size_t> slab_at(d + 1, 0);
+  int kept = 0;
+  for (int k = 2; k <= d; k++)
+    if (need[k]) slab_at[k] = slab_limbs, slab_limbs += (size_t)level[k], kept++;
+  const size_t group = arena_group(c->facts, nl, count, 2 * (size_t)(kept ? kept : 1));
+  if (kept && (ensure_aux(c, 5, group * 2 * slab_limbs * N * 8) || ensure_aux(c, 3, group * 2 * (size_t)nl * N * 8) || ensure_aux(c, 4, group * 2 * (size_t)nl * N * 8))) return 1;
+  std::vector<const u64 *> ct(terms.size());
+  std::vector<int> ct_nl(terms.size());
+  for (size_t off = 0; off < count; off += group) {
+    const size_t cc = count - off < group ? count - off : group;
+    const u64 *gx = x + off * 2 * (size_t)nl * N;
+    auto power = [&](int k) -> u64 * { return k == 1 ? const_cast<u64 *>(gx) : (u64 *)c->aux[5] + group * 2 * slab_at[k] * N; };
+    for (int k = 2; k <= d; k++) {
+      if (!need[k]) continue;
+      const int lk = level[k] + 1;  // the product's level: that of x^h
+      const u64 *a = power(hi[k]), *b = power(lo[k]);
+      if (level[lo[k]] > lk) {
+        if (launch_drop_to(c, b, (u64 *)c->aux[3], level[lo[k]], lk, cc * 2)) return 1;
+        b = (const u64 *)c->aux[3];
+      }
+      if (mul_relin(c, a, b, (u64 *)c->aux[4], lk, cc)) return 1;
+      if (launch_rescale(c, (const u64 *)c->aux[4], power(k), 2, lk, cc)) return 1;
+    }
+    for (size_t i = 0; i < terms.size(); i++) ct[i] = power(terms[i]), ct_nl[i] = level[terms[i]];
+    if (const_sum_rescale(c, ct, ct_nl, w.data(), w0.data(), nullptr, out + off * 2 * (size_t)(m - 1) * N, 2, m, cc)) return 1;
+  }
+  return 0;
+}
+int abc_hip_ckks_poly_eval(abc_hip_ctx *c, const uint64_t *d_x, double x_scale, const double *h_coeffs, int degree, double out_scale, uint64_t *d_out,
+                           int nl, size_t count) {
+  CTX_GUARD(c);
+  if (c->scheme != ABC_HIP_SCHEME_CKKS) { set_error("ckks_poly_eval is a CKKS operation"); return 1; }
+  if (check_level(c, nl)) return 1;
+  if (degree < 1 || degree > 31) { set_error("ckks_poly_eval: degree must be in 1 .. 31"); return 1; }
+  const int depth = ceil_log2(degree) + 1;
+  if (nl < depth + 1) { set_error("ckks_poly_eval: the chain is too short (nl must be at least ceil(log2 degree) + 2)"); return 1; }
+  if ((ptrdiff_t)count < 0) { set_error("ckks_poly_eval: negative count"); return 1; }
+  if (!h_coeffs) { set_error("ckks_poly_eval: null coefficients"); return 1; }
+  if (!std::isfinite(x_scale) || !std::isfinite(out_scale) || x_scale <= 0 || out_scale <= 0) { set_error("ckks_poly_eval: scales must be finite and positive"); return 1; }
+  for (int k = 0; k <= degree; k++)
+    if (!std::isfinite(h_coeffs[k])) { set_error("ckks_poly_eval: a coefficient is not finite"); return 1; }
+  if (!c->d_relin) { set_error("ckks_poly_eval: no relinearisation key"); return 1; }
+  if (count && (!d_x || !d_out)) { set_error("ckks_poly_eval: null ciphertext pointer"); return 1; }
+  const size_t N = (size_t)c->n;
+  if (count && ranges_overlap(d_x, count * 2 * (size_t)nl * N * 8, d_out, count * 2 * (size_t)(nl - depth) * N * 8)) {
+    set_error("ckks_poly_eval: d_out must not overlap d_x");
+    return 1;
+  }
+  return guarded([&] { return poly_eval(c, d_x, x_scale, h_coeffs, degree, out_scale, d_out, nl, count); });
 }
 
 // ---- raw pieces ----

@@ -196,13 +196,14 @@ struct abc_hip_ctx {
   };
   std::unordered_map<const uint64_t *, KeyMirror> key_mirrors;
   std::vector<uint32_t> galois_order;
-  // workspace (kernel-sequence scratch) and five caller-level arenas (0: permuted input, 1 / 2: products (multiply_plain_rescale's separate route and multiply_plain_sum_rescale's leading sum among them) and rotation ping-pong, 3 / 4: rotate_sum's running sums);
+  // workspace (kernel-sequence scratch) and seven caller-level arenas (0: permuted input, 1 / 2: products (multiply_plain_rescale's separate route and multiply_plain_sum_rescale's leading sum among them) and rotation ping-pong, 3 / 4: rotate_sum's running sums
+  // and poly_eval's lowered factor and product, 5: poly_eval's powers, 6: the constant plaintext and lowered term of multiply_const_sum's composed route);
   // all grow on demand and are reused, so steady-state calls perform no hipMalloc / hipFree; one that grows while a graph owns
   // it is held back, not freed (ensure_arena in abc_buffers.hip)
   void *ws = nullptr;
   size_t ws_bytes = 0;
-  void *aux[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t aux_bytes[5] = {0, 0, 0, 0, 0};
+  void *aux[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  size_t aux_bytes[7] = {0, 0, 0, 0, 0, 0, 0};
   size_t limb_words() const { return (size_t)n; }
   size_t key_words() const { return (size_t)L * 2 * K * n; }
 };
@@ -315,6 +316,19 @@ int launch_ckks_tensor_sum(abc_hip_ctx *c, const u64 *const *a, const u64 *const
 constexpr int kPlainMacTerms = kTensorSumTerms;
 int launch_ckks_plain_mac_sum(abc_hip_ctx *c, const u64 *const *ct, const u64 *const *plain, size_t plain_stride, int n_terms, const u64 *addend,
                               u64 *out, int size, int nl, size_t count);
+// out [count][size][nl][N] = (addend or 0) + cst (component 0) + sum over k < n_terms of w[k] * ct[k] (CKKS; ct: HOST array of device
+// pointers, term k [count][size][ct_nl[k]][N], ct_nl[k] >= nl, its first nl limbs read in place; ct_nl null: every term at nl; w: HOST
+// [n_terms][nl] canonical words, cst: HOST [nl] or null; out may be addend): k_ckks_const_mac_sum, kConstMacTerms pointers and their
+// weights per launch by value in the kernel arguments; n_terms >= 0
+constexpr int kConstMacTerms = kPlainMacTerms;
+int launch_ckks_const_mac_sum(abc_hip_ctx *c, const u64 *const *ct, const int *ct_nl, const u64 *w, int n_terms, const u64 *cst, const u64 *addend,
+                              u64 *out, int size, int nl, size_t count);
+// the same sum with the rescale behind it, formed in the loads of the two LDS-resident rescale kernels (k_constsum_rescale_*): r a
+// route_rescale that is not generic, every term at nl limbs, 1 <= n_terms <= kConstSumRescaleTerms
+int launch_const_sum_rescale(abc_hip_ctx *c, const RescaleRoute &r, const u64 *const *ct, const u64 *w, int n_terms, const u64 *cst, const u64 *addend,
+                             u64 *out, int size, int nl, size_t count);
+int launch_const_plain_fill(abc_hip_ctx *c, const u64 *w, u64 *plain, int nl);  // plain [nl][N]: every word of limb j = w[j] (HOST words)
+int launch_drop_to(abc_hip_ctx *c, const u64 *in, u64 *out, int from_nl, int nl, size_t polys);  // the first nl of from_nl limbs per polynomial
 int keyswitch_generic(abc_hip_ctx *c, KsFront front, const KsOperands &o);
 int launch_ks_tmod(abc_hip_ctx *c, const u64 *prodS, u64 *tmod, int nl, size_t polys);
 int launch_ks_finish(abc_hip_ctx *c, const u64 *prodD, const u64 *tmod, u64 *out, const u64 *addend, size_t addend_stride,

@@ -887,6 +887,31 @@ int launch_drop_last(abc_hip_ctx *c, const u64 *in, u64 *out, int size, int nl, 
   return 0;
 }
 
+// ---- the pieces of multiply_const_sum's composed route (ABC_HIP_NO_CONST_MAC_SUM; the K-term kernel is further down) ----
+// the constant plaintext: plain [nl][N], every word of limb j = w[j] (by value)
+struct ConstWords {
+  u64 w[kMaxLimbs];
+};
+__global__ __launch_bounds__(256) void k_const_plain_fill(DevCtx c, ConstWords cw, u64 *plain) {
+  const u32 spans = (u32)c.n / kTensorSumSpan;  // one workgroup per span of one limb: the word is workgroup-uniform
+  const u64 v = cw.w[blockIdx.x / spans];
+  *reinterpret_cast<u64x2 *>(plain + (size_t)blockIdx.x * kTensorSumSpan + 2 * threadIdx.x) = u64x2{v, v};
+}
+int launch_const_plain_fill(abc_hip_ctx *c, const u64 *w, u64 *plain, int nl) {
+  ConstWords cw{};
+  for (int j = 0; j < nl; j++) cw.w[j] = w[j];
+  hipLaunchKernelGGL(k_const_plain_fill, dim3((unsigned)(nl * (c->n / kTensorSumSpan))), dim3(256), 0, c->stream, c->dc, cw, plain);
+  ABC_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+// in [polys][from_nl][N] -> out [polys][nl][N], the first nl limbs of each: launch_drop_last repeated from_nl - nl times, in one copy
+int launch_drop_to(abc_hip_ctx *c, const u64 *in, u64 *out, int from_nl, int nl, size_t polys) {
+  const size_t N = (size_t)c->n;
+  if (!polys) return 0;
+  ABC_HIP_CHECK(hipMemcpy2DAsync(out, nl * N * 8, in, from_nl * N * 8, nl * N * 8, polys, hipMemcpyDeviceToDevice, c->stream));
+  return 0;
+}
+
 // ---- CKKS plaintext ops (NTT-form plaintext [nl][N]) ----
 __global__ __launch_bounds__(256) void k_ckks_plain(DevCtx c, const u64 *ct, const u64 *plain, size_t plain_stride, u64 *out,
                                                     int size, int nl, size_t count, int op) {
@@ -1066,6 +1091,185 @@ int launch_ckks_plain_mac_sum(abc_hip_ctx *c, const u64 *const *ct, const u64 *c
     auto go = [&](auto has_fp, auto has_int, auto sz) {
       hipLaunchKernelGGL((k_ckks_plain_mac_sum<decltype(has_fp)::value, decltype(has_int)::value, decltype(sz)::value>), grid, dim3(256), 0,
                          c->stream, c->dc, t, nt, plain_stride, carry, out, nl, tiles, fpmask);
+    };
+    auto by_size = [&](auto has_fp, auto has_int) {
+      if (size == 3) go(has_fp, has_int, std::integral_constant<int, 3>{});
+      else go(has_fp, has_int, std::integral_constant<int, 2>{});
+    };
+    if (fpmask == full) by_size(std::true_type{}, std::false_type{});
+    else if (!fpmask) by_size(std::false_type{}, std::true_type{});
+    else by_size(std::true_type{}, std::true_type{});
+    ABC_HIP_CHECK(hipGetLastError());
+  }
+  return 0;
+}
+
+// ---- CKKS scalar-weighted sum: out = (carry or 0) + const (component 0) + sum over the launch's terms of w_k * ct_k ----
+// k_ckks_plain_mac_sum with the plaintext of every term a CONSTANT: in NTT form the constant c is the polynomial whose every word of
+// limb j is c mod q_j, so a term needs no plaintext load at all -- its weight is one word per limb, and the limb is workgroup-uniform.
+// The weights and the additive constant travel BY VALUE in the kernel arguments (kConstMacTerms x kMaxLimbs words and kMaxLimbs
+// more) and are indexed by the limb, which is workgroup-uniform: scalar loads from the kernel-argument segment, no private copy (the
+// resource table shows no scratch), no device-side table, and the call stays capturable with the weights in its record.  Every term has its own polynomial
+// stride: term k is laid out [count][SIZE][limbs[k]][N] with limbs[k] >= nl and its first nl limbs are read in place, which is
+// abc_hip_mod_switch down to nl without the copy.  Tiles, the 16-byte accesses, the next term's loads ahead of the arithmetic, the
+// carry by pointer (out == carry needs no copy) as in k_ckks_plain_mac_sum.  Results are exact modular sums in canonical form:
+// bit-identical to k_ckks_plain per term on the constant plaintext, k_addsub, and k_ckks_plain's add on component 0.
+struct ConstMacTerms {
+  const u64 *ct[kConstMacTerms];
+  u32 limbs[kConstMacTerms];           // polynomial stride of term k in limbs
+  u64 w[kConstMacTerms][kMaxLimbs];    // weight of term k modulo q_j, canonical
+  u64 cst[kMaxLimbs];                  // the additive constant modulo q_j (zeros where there is none, and on every launch after the first)
+};
+// The bounds of k_ckks_plain_mac_sum carry over: a weight is below q exactly as a plaintext word is.  Integer limbs: a launch sums at
+// most kConstMacTerms products, each at most (q - 1)^2, the carried word and the constant (both below q, together less than one
+// product): (T + 1) (q - 1)^2 < 2^128 for the widest prime a context accepts, 2^60.
+static_assert(kConstMacTerms + 1 <= (1 << (128 - 2 * kTensorSumPrimeBits)), "const mac sum: the 128-bit accumulator would overflow within one launch");
+// fp64 limbs (q < 2^50): the carried word and the constant are below q each, every product is |.| < q, integer-valued doubles are
+// exact up to 2^53 >= 8 q: the accumulators are re-centred after every kPlainMacFpTerms = 4 terms (carried + constant + 4 products
+// < 6 q, then q/2 + 4 products < 4.5 q), and fp_to_canon centres the last group.
+static_assert(kPlainMacFpTerms + 2 <= 8 && kConstMacTerms <= 2 * kPlainMacFpTerms, "const mac sum: the fp64 accumulator would pass 2^53 between two re-centrings");
+
+template <int SIZE>
+struct ConstMacLoad {
+  u64x2 c[SIZE];
+};
+template <int SIZE>
+__device__ __forceinline__ ConstMacLoad<SIZE> const_mac_load(const u64 *ct, size_t off, size_t pw) {
+  ConstMacLoad<SIZE> t;
+#pragma unroll
+  for (int s = 0; s < SIZE; s++) t.c[s] = *reinterpret_cast<const u64x2 *>(ct + off + s * pw);
+  return t;
+}
+// where this lane's words of term k start: ciphertext `ct`, word w inside a polynomial of term k's own stride
+template <int SIZE>
+__device__ __forceinline__ size_t const_mac_off(const ConstMacTerms &t, int k, size_t ct, size_t w, int n) {
+  return ct * SIZE * ((size_t)t.limbs[k] * n) + w;
+}
+
+// one tile on the integers; pc: this lane's words of the carried value, or null
+template <int SIZE>
+__device__ __forceinline__ void const_mac_int(const ConstMacTerms &t, int nt, int j, const Mod &m, size_t ct, size_t w, int n, size_t pw, const u64 *pc,
+                                              u64 *po) {
+  U128 ax[SIZE], ay[SIZE];
+#pragma unroll
+  for (int s = 0; s < SIZE; s++) ax[s] = U128{0, 0}, ay[s] = U128{0, 0};
+  if (pc) {  // workgroup-uniform
+#pragma unroll
+    for (int s = 0; s < SIZE; s++) {
+      const u64x2 r = *reinterpret_cast<const u64x2 *>(pc + s * pw);
+      ax[s].lo = r.x, ay[s].lo = r.y;
+    }
+  }
+  const u64 cst = t.cst[j];
+  add128(ax[0], U128{cst, 0}), add128(ay[0], U128{cst, 0});
+  u64 wk[kConstMacTerms];  // every weight of the launch ahead of the loop: the scalar loads are in flight together, not one per term
+#pragma unroll
+  for (int k = 0; k < kConstMacTerms; k++) wk[k] = t.w[k][j];
+  ConstMacLoad<SIZE> cur{}, nxt{};
+  if (nt > 0) cur = const_mac_load<SIZE>(t.ct[0], const_mac_off<SIZE>(t, 0, ct, w, n), (size_t)t.limbs[0] * n);
+#pragma unroll
+  for (int k = 0; k < kConstMacTerms; k++) {
+    if (k < nt) {  // workgroup-uniform
+      if (k + 1 < kConstMacTerms && k + 1 < nt) nxt = const_mac_load<SIZE>(t.ct[k + 1], const_mac_off<SIZE>(t, k + 1, ct, w, n), (size_t)t.limbs[k + 1] * n);
+#pragma unroll
+      for (int s = 0; s < SIZE; s++) mac128(ax[s], cur.c[s].x, wk[k]), mac128(ay[s], cur.c[s].y, wk[k]);
+      cur = nxt;
+    }
+  }
+  const u64 r64 = reduce64(0ull - m.q, m);  // 2^64 mod q
+#pragma unroll
+  for (int s = 0; s < SIZE; s++) *reinterpret_cast<u64x2 *>(po + s * pw) = u64x2{reduce128(ax[s], r64, m), reduce128(ay[s], r64, m)};
+}
+
+// one tile in fp64 (q < 2^50)
+template <int SIZE>
+__device__ __forceinline__ void const_mac_fp(const ConstMacTerms &t, int nt, int j, const Mod &m, size_t ct, size_t w, int n, size_t pw, const u64 *pc,
+                                             u64 *po) {
+  const double q = m.qd, qinv = m.qinv;
+  double ax[SIZE], ay[SIZE];
+#pragma unroll
+  for (int s = 0; s < SIZE; s++) ax[s] = 0, ay[s] = 0;
+  if (pc) {  // workgroup-uniform
+#pragma unroll
+    for (int s = 0; s < SIZE; s++) {
+      const u64x2 r = *reinterpret_cast<const u64x2 *>(pc + s * pw);
+      ax[s] = fp_from_u64(r.x), ay[s] = fp_from_u64(r.y);
+    }
+  }
+  const double cst = fp_from_u64(t.cst[j]);
+  ax[0] += cst, ay[0] += cst;
+  double wk[kConstMacTerms];  // every weight of the launch ahead of the loop, converted once
+#pragma unroll
+  for (int k = 0; k < kConstMacTerms; k++) wk[k] = fp_from_u64(t.w[k][j]);
+  ConstMacLoad<SIZE> cur{}, nxt{};
+  if (nt > 0) cur = const_mac_load<SIZE>(t.ct[0], const_mac_off<SIZE>(t, 0, ct, w, n), (size_t)t.limbs[0] * n);
+#pragma unroll
+  for (int k = 0; k < kConstMacTerms; k++) {
+    if (k < nt) {  // workgroup-uniform
+      if (k + 1 < kConstMacTerms && k + 1 < nt) nxt = const_mac_load<SIZE>(t.ct[k + 1], const_mac_off<SIZE>(t, k + 1, ct, w, n), (size_t)t.limbs[k + 1] * n);
+#pragma unroll
+      for (int s = 0; s < SIZE; s++) {
+        ax[s] += fp_mulmod(fp_from_u64(cur.c[s].x), wk[k], q, qinv);
+        ay[s] += fp_mulmod(fp_from_u64(cur.c[s].y), wk[k], q, qinv);
+      }
+      // carried value + constant + kPlainMacFpTerms products < 6 q < 2^53 up to here
+      if ((k + 1) % kPlainMacFpTerms == 0 && k + 1 < kConstMacTerms) {
+#pragma unroll
+        for (int s = 0; s < SIZE; s++) ax[s] = fp_centre(ax[s], q, qinv), ay[s] = fp_centre(ay[s], q, qinv);
+      }
+      cur = nxt;
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < SIZE; s++) *reinterpret_cast<u64x2 *>(po + s * pw) = u64x2{fp_to_canon(ax[s], q, qinv), fp_to_canon(ay[s], q, qinv)};
+}
+
+// tiles, fpmask, HAS_FP / HAS_INT as in k_ckks_plain_mac_sum; nt may be 0 (carry + constant); carry: [count][SIZE][nl][N] like out
+// (and possibly out itself), or null
+template <bool HAS_FP, bool HAS_INT, int SIZE>
+__global__ __launch_bounds__(256) void k_ckks_const_mac_sum(DevCtx c, ConstMacTerms t, int nt, const u64 *carry, u64 *out, int nl, size_t tiles,
+                                                            u32 fpmask) {
+  const u32 spans = (u32)c.n / kTensorSumSpan;
+  const size_t pw = (size_t)nl * c.n;
+  for (size_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const size_t limb = tile / spans;  // ct * nl + j
+    const u32 span = (u32)(tile - limb * spans);
+    const size_t ct = limb / (u32)nl;
+    const int j = (int)(limb - ct * (u32)nl);
+    const size_t w = (size_t)j * c.n + (size_t)span * kTensorSumSpan + 2 * threadIdx.x;  // word inside a polynomial, whatever its stride
+    const Mod m = mod_at(c, j);
+    const size_t out_off = ct * SIZE * pw + w;
+    const u64 *pc = carry ? carry + out_off : nullptr;
+    if (HAS_FP && (!HAS_INT || ((fpmask >> j) & 1u))) const_mac_fp<SIZE>(t, nt, j, m, ct, w, c.n, pw, pc, out + out_off);
+    else const_mac_int<SIZE>(t, nt, j, m, ct, w, c.n, pw, pc, out + out_off);
+  }
+}
+
+// out [count][size][nl][N] = (addend or 0) + cst (component 0) + sum over k < n_terms of w[k] * ct[k]; ct: HOST array of device
+// pointers, term k [count][size][ct_nl[k]][N] with ct_nl[k] >= nl (ct_nl null: all nl); w: [n_terms][nl] canonical words, cst: [nl]
+// or null; n_terms >= 0 (an empty sum is one launch that writes addend + cst), size 2 or 3, on stream c->stream
+int launch_ckks_const_mac_sum(abc_hip_ctx *c, const u64 *const *ct, const int *ct_nl, const u64 *w, int n_terms, const u64 *cst, const u64 *addend,
+                              u64 *out, int size, int nl, size_t count) {
+  const size_t tiles = count * nl * ((size_t)c->n / kTensorSumSpan);
+  if (!tiles || n_terms < 0) return 0;
+  const u32 full = (1u << nl) - 1u;
+  const u32 fpmask = (c->use_fp && (c->facts.data_fp(nl) || !c->sw.no_mixed)) ? c->facts.fp_data_mask(nl) : 0u;
+  const size_t cap = 256 * 8 * 16;  // workgroups: every CU several times over, the tile loop beyond
+  const dim3 grid((unsigned)(tiles < cap ? tiles : cap));
+  for (int k0 = 0; k0 == 0 || k0 < n_terms; k0 += kConstMacTerms) {
+    const int nt = n_terms - k0 < kConstMacTerms ? n_terms - k0 : kConstMacTerms;
+    ConstMacTerms t{};
+    for (int k = 0; k < kConstMacTerms; k++) {  // unused slots repeat a valid term (none is read)
+      const int src = k0 + (k < nt ? k : 0);
+      t.ct[k] = nt ? ct[src] : nullptr;
+      t.limbs[k] = (u32)(nt && ct_nl ? ct_nl[src] : nl);
+      for (int j = 0; j < nl; j++) t.w[k][j] = k < nt ? w[(size_t)src * nl + j] : 0;
+    }
+    for (int j = 0; j < nl; j++) t.cst[j] = (cst && !k0) ? cst[j] : 0;
+    const u64 *carry = k0 ? out : addend;
+    auto go = [&](auto has_fp, auto has_int, auto sz) {
+      hipLaunchKernelGGL((k_ckks_const_mac_sum<decltype(has_fp)::value, decltype(has_int)::value, decltype(sz)::value>), grid, dim3(256), 0,
+                         c->stream, c->dc, t, nt, carry, out, nl, tiles, fpmask);
     };
     auto by_size = [&](auto has_fp, auto has_int) {
       if (size == 3) go(has_fp, has_int, std::integral_constant<int, 3>{});
@@ -1285,6 +1489,219 @@ int launch_plain_sum_rescale(abc_hip_ctx *c, const RescaleRoute &r, const u64 *c
     });
   return dispatch_logn<10, 14>(c->logn, [&](auto LB) {
     return launch_plain_sum_rescale_lds<decltype(LB)::value, false>(c, t, n_terms, plain_stride, carry, out, size, nl, polys, 0u);
+  });
+}
+
+// ---- K-term SCALAR-weighted sum + rescale in one: carry + const + sum_k w_k * ct_k formed in the loads of R1 and R2 ----
+// k_plainsum_rescale_* with a functor whose weight is the workgroup-uniform scalar instead of a loaded plaintext word: a term costs
+// one load per coefficient, not two.  At most kConstSumRescaleTerms = 4 terms (beyond four the streaming kernel and the rescale are
+// as fast: profiles/const_sum_ab.log), every term at level nl -- a term held higher has another stride and stays with
+// k_ckks_const_mac_sum.  The record travels by value; the functor is built once per workgroup and holds this limb's weights and
+// constant as VALUES (scalar loads from the kernel-argument segment, the limb is workgroup-uniform).  The constant belongs to
+// component 0: polynomial p of the batch is component p % size.  Bounds: fp64, carried + constant + 4 products < 6 q < 2^53, one
+// centring at the end, |result| <= q/2; integers, (4 + 1) (q - 1)^2 < 2^128, one reduction, canonical.  Exact modular sums whatever
+// the representative: bit-identical to k_ckks_const_mac_sum followed by the rescale kernels.
+struct ConstSumRescaleTerms {
+  const u64 *ct[kConstSumRescaleTerms];
+  u64 w[kConstSumRescaleTerms][kMaxLimbs];
+  u64 cst[kMaxLimbs];  // zeros where there is no constant
+};
+static_assert(kConstSumRescaleTerms + 2 <= 8, "const sum rescale: the fp64 accumulator would pass 2^53 before its one centring");
+static_assert(kConstSumRescaleTerms + 1 <= (1 << (128 - 2 * kTensorSumPrimeBits)), "const sum rescale: the 128-bit accumulator would overflow");
+// CHUNK: coefficients R2 asks for at a time behind its transform (kChunk); the mixed R2 kernel at N = 2^14 -- 1024 threads, 128 VGPRs
+// at most -- takes half of what its twins take, which keeps it out of scratch
+template <int CHUNK>
+struct ConstSumLimbFpT {
+  static constexpr int kStage = 16, kChunk = CHUNK;
+  const u64 *ct[kConstSumRescaleTerms];  // this limb of every term
+  int nt;
+  const u64 *__restrict__ carry;  // this limb of the carried value, or null
+  u64 w[kConstSumRescaleTerms], cst;  // canonical words: uniform, so they stay in scalar registers across the transform; converted at each use
+  double q, qinv;
+  template <int C>
+  __device__ __forceinline__ void sums(const int (&i)[C], double (&out)[C]) const {
+    double acc[C];
+    const double c0 = fp_from_u64(cst);
+#pragma unroll
+    for (int e = 0; e < C; e++) acc[e] = c0;
+    if (carry) {  // workgroup-uniform
+#pragma unroll
+      for (int e = 0; e < C; e++) acc[e] += fp_from_u64(carry[i[e]]);
+    }
+#pragma unroll
+    for (int k = 0; k < kConstSumRescaleTerms; k++) {
+      if (k < nt) {  // workgroup-uniform
+        u64 cv[C];
+#pragma unroll
+        for (int e = 0; e < C; e++) cv[e] = ct[k][i[e]];
+        const double wk = fp_from_u64(w[k]);
+#pragma unroll
+        for (int e = 0; e < C; e++) acc[e] += fp_mulmod(fp_from_u64(cv[e]), wk, q, qinv);
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < C; e++) out[e] = fp_centre(acc[e], q, qinv);
+  }
+};
+template <int CHUNK>
+struct ConstSumLimbIntT {
+  static constexpr int kStage = 8, kChunk = CHUNK;
+  const u64 *ct[kConstSumRescaleTerms];
+  int nt;
+  const u64 *__restrict__ carry;
+  u64 w[kConstSumRescaleTerms], cst;
+  Mod m;
+  template <int C>
+  __device__ __forceinline__ void sums(const int (&i)[C], u64 (&out)[C]) const {
+    U128 acc[C];
+#pragma unroll
+    for (int e = 0; e < C; e++) acc[e] = U128{cst, 0};
+    if (carry) {  // workgroup-uniform
+#pragma unroll
+      for (int e = 0; e < C; e++) add128(acc[e], U128{carry[i[e]], 0});
+    }
+#pragma unroll
+    for (int k = 0; k < kConstSumRescaleTerms; k++) {
+      if (k < nt) {  // workgroup-uniform
+        u64 cv[C];
+#pragma unroll
+        for (int e = 0; e < C; e++) cv[e] = ct[k][i[e]];
+#pragma unroll
+        for (int e = 0; e < C; e++) mac128(acc[e], cv[e], w[k]);
+      }
+    }
+    const u64 r64 = reduce64(0ull - m.q, m);  // 2^64 mod q
+#pragma unroll
+    for (int e = 0; e < C; e++) out[e] = reduce128(acc[e], r64, m);
+  }
+};
+using ConstSumLimbFp = ConstSumLimbFpT<4>;
+using ConstSumLimbInt = ConstSumLimbIntT<2>;
+// limb j of polynomial p (component p % size): off = (p * nl + j) * N
+template <class F = ConstSumLimbFp>
+__device__ __forceinline__ F const_sum_limb_fp(const ConstSumRescaleTerms &t, int nt, const u64 *carry, size_t off, int j, bool comp0, const Mod &m) {
+  F f;
+#pragma unroll
+  for (int k = 0; k < kConstSumRescaleTerms; k++) f.ct[k] = t.ct[k] + off, f.w[k] = t.w[k][j];
+  f.nt = nt, f.carry = carry ? carry + off : nullptr, f.cst = comp0 ? t.cst[j] : 0, f.q = m.qd, f.qinv = m.qinv;
+  return f;
+}
+template <class F = ConstSumLimbInt>
+__device__ __forceinline__ F const_sum_limb_int(const ConstSumRescaleTerms &t, int nt, const u64 *carry, size_t off, int j, bool comp0, const Mod &m) {
+  F f;
+#pragma unroll
+  for (int k = 0; k < kConstSumRescaleTerms; k++) f.ct[k] = t.ct[k] + off, f.w[k] = t.w[k][j];
+  f.nt = nt, f.carry = carry ? carry + off : nullptr, f.cst = comp0 ? t.cst[j] : 0, f.m = m;
+  return f;
+}
+
+// LdsOperand under a name of its own: divround_to_coef<.., ScalarLdsOperand<E>> is then an instantiation of its own, and the ones the
+// k_plainsum_rescale_* kernels call keep the callers -- and with them the inlining and the device code -- they had
+template <class E>
+struct ScalarLdsOperand {
+  const E *lds;
+  __device__ __forceinline__ E operator()(int i) const { return lds[lds_pad(i)]; }
+};
+template <int LB>
+__global__ __launch_bounds__((1 << LB) / 16) void k_constsum_rescale_intt_fp(DevCtx c, ConstSumRescaleTerms t, int nt, const u64 *__restrict__ carry,
+                                                                             u64 *__restrict__ last, int size, int nl) {
+  __shared__ double lds[lds_words(LB)];
+  const size_t N = (size_t)1 << LB, p = blockIdx.x;
+  const Mod m = mod_at(c, nl - 1);
+  plain_sum_stage<LB>(lds, const_sum_limb_fp(t, nt, carry, (p * nl + (nl - 1)) * N, nl - 1, p % size == 0, m));
+  divround_to_coef<LB, FpArith, false, ScalarLdsOperand<double>>(lds, m, fp_table(c, nl - 1), nullptr, last + p * N, nullptr, ScalarLdsOperand<double>{lds});
+}
+template <int LB>
+__global__ __launch_bounds__((1 << LB) / 16) void k_constsum_rescale_intt_mixed(DevCtx c, ConstSumRescaleTerms t, int nt, const u64 *__restrict__ carry,
+                                                                                u64 *__restrict__ last, int size, int nl, int fp_last) {
+  __shared__ u64 lds_raw[lds_words(LB)];
+  const size_t N = (size_t)1 << LB, p = blockIdx.x;
+  const size_t off = (p * nl + (nl - 1)) * N;
+  const bool comp0 = p % size == 0;
+  u64 *__restrict__ dst = last + p * N;
+  if (fp_last) {
+    const Mod m = mod_at(c, nl - 1);
+    double *lds = reinterpret_cast<double *>(lds_raw);
+    plain_sum_stage<LB>(lds, const_sum_limb_fp(t, nt, carry, off, nl - 1, comp0, m));
+    divround_to_coef<LB, FpArith, false, ScalarLdsOperand<double>>(lds, m, fp_table(c, nl - 1), nullptr, dst, nullptr, ScalarLdsOperand<double>{lds});
+  } else {
+    const Mod m = c.mods[nl - 1];
+    plain_sum_stage<LB>(lds_raw, const_sum_limb_int(t, nt, carry, off, nl - 1, comp0, m));
+    divround_to_coef<LB, IntArith<true>, false, ScalarLdsOperand<u64>>(lds_raw, m, ntt_table(c, nl - 1), nullptr, dst, nullptr, ScalarLdsOperand<u64>{lds_raw});
+  }
+}
+template <int LB, bool MIXED>
+__global__ __launch_bounds__((1 << LB) / 16) void k_constsum_rescale_ntt(DevCtx c, ConstSumRescaleTerms t, int nt, const u64 *__restrict__ carry,
+                                                                         const u64 *__restrict__ last, u64 *__restrict__ out, int size, int nl, int npoly,
+                                                                         u32 fpmask) {
+  __shared__ u64 lds_raw[lds_words(LB)];
+  int j;
+  size_t p;
+  xcd_slot(blockIdx.x, nl - 1, npoly, j, p);
+  const size_t N = (size_t)1 << LB;
+  const Mod m = MIXED ? c.mods[j] : mod_at(c, j);
+  const auto fix = round_fix<std::conditional_t<MIXED, u64, double>>(c.mods[nl - 1].q >> 1, m);
+  const DropInv d = inv_qlast_at(c, nl - 1, j);
+  const u64 *__restrict__ src = last + p * N;
+  const size_t off = (p * nl + j) * N;
+  const bool comp0 = p % size == 0;
+  u64 *__restrict__ o = out + (p * (nl - 1) + j) * N;
+  if constexpr (!MIXED) {
+    divround_finish<LB, FpArith, false, false, false, ConstSumLimbFp>(reinterpret_cast<double *>(lds_raw), m, fp_table(c, j), fix, d, src, nullptr, nullptr, o,
+                                                                      nullptr, const_sum_limb_fp(t, nt, carry, off, j, comp0, m));
+  } else {
+    using Fp = std::conditional_t<LB == 14, ConstSumLimbFpT<2>, ConstSumLimbFp>;
+    using Int = std::conditional_t<LB == 14, ConstSumLimbIntT<1>, ConstSumLimbInt>;
+    if ((fpmask >> j) & 1u) {
+      const Mod mf = mod_at(c, j);
+      divround_finish<LB, FpArith, true, false, false, Fp>(reinterpret_cast<double *>(lds_raw), mf, fp_table(c, j), fix, d, src, nullptr, nullptr, o, nullptr,
+                                                           const_sum_limb_fp<Fp>(t, nt, carry, off, j, comp0, mf));
+    } else {
+      divround_finish<LB, IntArith<true>, false, false, false, Int>(lds_raw, m, ntt_table(c, j), fix, d, src, nullptr, nullptr, o, nullptr,
+                                                                    const_sum_limb_int<Int>(t, nt, carry, off, j, comp0, m));
+    }
+  }
+}
+template <int LB, bool MIXED>
+static int launch_const_sum_rescale_lds(abc_hip_ctx *c, const ConstSumRescaleTerms &t, int nt, const u64 *carry, u64 *out, int size, int nl, size_t polys,
+                                        u32 fpmask) {
+  const size_t N = (size_t)1 << LB;
+  if (ensure_workspace(c, polys * N * 8)) return 1;
+  u64 *last = (u64 *)c->ws;
+  const dim3 block((1 << LB) / 16);
+  if constexpr (MIXED)
+    hipLaunchKernelGGL(k_constsum_rescale_intt_mixed<LB>, dim3((unsigned)polys), block, 0, c->stream, c->dc, t, nt, carry, last, size, nl,
+                       (int)((fpmask >> (nl - 1)) & 1u));
+  else
+    hipLaunchKernelGGL(k_constsum_rescale_intt_fp<LB>, dim3((unsigned)polys), block, 0, c->stream, c->dc, t, nt, carry, last, size, nl);
+  hipLaunchKernelGGL((k_constsum_rescale_ntt<LB, MIXED>), dim3((unsigned)(polys * (nl - 1))), block, 0, c->stream, c->dc, t, nt, carry, last, out, size, nl,
+                     (int)polys, fpmask);
+  ABC_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// out [count][size][nl-1][N] = rescale((addend or 0) + cst (component 0) + sum over k < n_terms of w[k] * ct[k]) by the fused pair; every
+// term at nl limbs, 1 <= n_terms <= kConstSumRescaleTerms, r not generic, nl >= 2 (const_sum_rescale in abc_context.hip sees to it)
+int launch_const_sum_rescale(abc_hip_ctx *c, const RescaleRoute &r, const u64 *const *ct, const u64 *w, int n_terms, const u64 *cst, const u64 *addend,
+                             u64 *out, int size, int nl, size_t count) {
+  const size_t polys = count * size;
+  if (!polys) return 0;
+  if (r.kind == Rescale::generic || n_terms < 1 || n_terms > kConstSumRescaleTerms || nl < 2) {
+    set_error("const_sum_rescale: not a launch of the fused pair");
+    return 1;
+  }
+  ConstSumRescaleTerms t{};  // unused slots repeat a valid pointer (none is read)
+  for (int k = 0; k < kConstSumRescaleTerms; k++) {
+    t.ct[k] = ct[k < n_terms ? k : 0];
+    for (int j = 0; j < nl; j++) t.w[k][j] = k < n_terms ? w[(size_t)k * nl + j] : 0;
+  }
+  for (int j = 0; j < nl; j++) t.cst[j] = cst ? cst[j] : 0;
+  if (r.kind == Rescale::mixed)
+    return dispatch_logn<10, 14>(c->logn, [&](auto LB) {
+      return launch_const_sum_rescale_lds<decltype(LB)::value, true>(c, t, n_terms, addend, out, size, nl, polys, r.fpmask);
+    });
+  return dispatch_logn<10, 14>(c->logn, [&](auto LB) {
+    return launch_const_sum_rescale_lds<decltype(LB)::value, false>(c, t, n_terms, addend, out, size, nl, polys, 0u);
   });
 }
 

@@ -27,6 +27,8 @@ struct Switches {
   bool no_tensor_sum = false;  // ABC_HIP_NO_TENSOR_SUM: multiply_sum / mul_sum_relin form every product on its own (tensor into an arena, then the add kernel)
   bool no_plain_sum_rescale_fusion = false;  // ABC_HIP_NO_PLAIN_SUM_RESCALE_FUSION: multiply_plain_sum_rescale (and the inner sums of diag_matvec_bsgs_rescale) as multiply_plain_sum into an arena, then rescale
   bool no_plain_mac_sum = false;  // ABC_HIP_NO_PLAIN_MAC_SUM: multiply_plain_sum (and the inner sums of diag_matvec_bsgs) as multiply_plain into an arena, then the add kernel, per term
+  bool no_const_mac_sum = false;  // ABC_HIP_NO_CONST_MAC_SUM: multiply_const_sum (and the last step of ckks_poly_eval) as a filled constant plaintext, mod_switch copies, multiply_plain and the add kernel, per term
+  int const_sum_rescale_fused = -1;  // ABC_HIP_CONST_SUM_RESCALE_FUSED=1 / =0: multiply_const_sum_rescale on its fused pair wherever the pair can run / nowhere (tests, A/B); unset: the measured rule of route_const_sum_rescale
   bool main_two_per_cu = false;  // ABC_HIP_MAIN_TWO_PER_CU: k_split4_main_fp in its one-piece pair phase at nl <= 4 (same step, same route: a form of the kernel)
   bool host_sampling = false;  // ABC_HIP_HOST_SAMPLING: the keyed entries (the OS-keyed ones call them) draw with the host twin of the keyed spec (no route depends on it)
   size_t chunk = 0, few_limbs = 48, lean_limit = 96, bfv_scratch_mb = 0, pass0_target_limit = 128;
@@ -272,6 +274,8 @@ inline MulSumRoute route_mul_sum(const RouteFacts &f, int nl) {
 
 // (addend or 0) + sum of K plaintext products at level nl (CKKS): the K-term kernel at every ring, chain and level
 inline bool route_plain_mac_sum(const RouteFacts &f, int) { return f.scheme == 2 && !f.sw.no_plain_mac_sum; }
+// multiply_const_sum: the K-term scalar-weighted kernel (k_ckks_const_mac_sum), or the composed sequence per term
+inline bool route_const_mac_sum(const RouteFacts &f, int) { return f.scheme == 2 && !f.sw.no_const_mac_sum; }
 
 // rescale((addend or 0) + sum of K plaintext products) at level nl (CKKS), `polys` = count * size polynomials.  Fused: the K-term forms
 // of the LDS-resident rescale kernels form the sum of the last `fused_terms` terms (and the carried value) in their loads; the terms
@@ -297,6 +301,27 @@ inline PlainSumRescaleRoute route_plain_sum_rescale(const RouteFacts &f, int nl,
   if (f.sw.plain_sum_rescale_terms >= 0) return {r, true, f.sw.plain_sum_rescale_terms < 8 ? f.sw.plain_sum_rescale_terms : 8};
   const bool wins = n_terms <= kPlainSumRescaleTerms && polys >= kPlainSumRescaleMinPolys && (polys << f.logn) >= kPlainSumRescaleMinCoeffs;
   return {r, wins, kPlainSumRescaleTerms};
+}
+// multiply_const_sum_rescale (and the last step of ckks_poly_eval): the sum formed in the loads of the two LDS-resident rescale kernels
+// (k_constsum_rescale_*: fused), or multiply_const_sum into an arena and then the rescale (separate).  The pair CAN run where the
+// rescale is LDS-resident (rings up to 2^14; not ABC_HIP_NO_FUSED, nor ABC_HIP_NO_ISPLIT on a chain with a prime above 2^50), on 1 ..
+// kConstSumRescaleTerms terms that all sit at level nl (`raised`: some term is held higher -- another stride, which only the
+// streaming kernel reads), and not under ABC_HIP_NO_CONST_MAC_SUM.  Within that, ABC_HIP_CONST_SUM_RESCALE_FUSED=1 / =0 force it on
+// and off; unset, the measured rule (profiles/const_sum_ab.log).  It started from route_plain_sum_rescale's -- four terms, 256
+// polynomials, 2^20 coefficients -- and the measurement moved one bound: with one load per coefficient and term instead of two the
+// pair is faster than the two steps at EVERY shape measured up to four terms, down to 64 polynomials (N = 2^14, batch 32),
+// where the plaintext pair loses; all of those shapes have 2^20 coefficients or more, so that bound stays, unmeasured below.
+constexpr int kConstSumRescaleTerms = 4;
+constexpr size_t kConstSumRescaleMinPolys = 64, kConstSumRescaleMinCoeffs = (size_t)1 << 20;
+struct ConstSumRescaleRoute {
+  RescaleRoute rescale;  // the rescale, out of place
+  bool fused;
+};
+inline ConstSumRescaleRoute route_const_sum_rescale(const RouteFacts &f, int nl, size_t polys, int n_terms, bool raised) {
+  const RescaleRoute r = route_rescale(f, nl, false);
+  if (r.kind == Rescale::generic || f.sw.no_const_mac_sum || raised || n_terms < 1 || n_terms > kConstSumRescaleTerms) return {r, false};
+  if (f.sw.const_sum_rescale_fused >= 0) return {r, f.sw.const_sum_rescale_fused != 0};
+  return {r, polys >= kConstSumRescaleMinPolys && (polys << f.logn) >= kConstSumRescaleMinCoeffs};
 }
 // terms of a K-term sum that the streaming kernel sums into the arena first: whole launches of terms_per_launch, as few as leave the
 // fused pair at most fused_terms
@@ -538,6 +563,25 @@ inline int format_matvec_bsgs_rescale(char *buf, size_t cap, const RouteFacts &f
   format_ks(giant, sizeof giant, f, r.giant.rot.ks, nl - 1, group);
   const int n = snprintf(buf, cap, "%s %s sumrescale=%s %s %s add=%s", r.baby.fold ? "fold" : "permute", baby, r.sum.fused ? "fused" : "separate",
                          r.giant.rot.fold ? "fold" : "permute", giant, r.giant.fused ? "fused" : "separate");
+  return n < 0 ? -1 : (size_t)n < cap ? n : -1;
+}
+// ABC_HIP_ROUTE_CONST_SUM_RESCALE (18) and ABC_HIP_ROUTE_POLY_EVAL (19), formatters of their own like 13's.  18: the rescale's route at
+// nl, then constsum=fused|separate for a sum of ONE term over `count` size-2 ciphertexts, every term at nl (abc_hip_route has no
+// argument for the number of terms or their levels: more than kConstSumRescaleTerms terms, or a term above nl, is separate
+// whatever the string says).  19: the mul_relin route at nl, then constsum=separate: from degree 2 on the last step reads powers held
+// above its level (a degree-1 call follows string 18 at nl).
+constexpr int kRouteConstSumRescale = 18, kRoutePolyEval = 19;
+inline int format_const_sum_rescale(char *buf, size_t cap, const RouteFacts &f, int nl, size_t count) {
+  const ConstSumRescaleRoute r = route_const_sum_rescale(f, nl, count * 2, 1, false);
+  const char *how = r.fused ? "fused" : "separate";
+  const int n = r.rescale.kind == Rescale::mixed ? snprintf(buf, cap, "mixed fpmask=0x%x constsum=%s", (unsigned)r.rescale.fpmask, how)
+                                                 : snprintf(buf, cap, "%s constsum=%s", name(r.rescale.kind), how);
+  return n < 0 ? -1 : (size_t)n < cap ? n : -1;
+}
+inline int format_poly_eval(char *buf, size_t cap, const RouteFacts &f, int nl, size_t count) {
+  char mul[128];
+  if (format_op(mul, sizeof mul, f, kRouteMulRelin, nl, count, false) < 0) return -1;
+  const int n = snprintf(buf, cap, "%s constsum=separate", mul);
   return n < 0 ? -1 : (size_t)n < cap ? n : -1;
 }
 // ABC_HIP_ROUTE_BFV_PLAIN_SUM (14) and ABC_HIP_ROUTE_BFV_MATVEC_BSGS (15), formatters of their own for the same reason.  14:

@@ -30,6 +30,15 @@ std::vector<double> realCleartext(const ICleartext &operand, const char *op) {
   if (auto p = dynamic_cast<const Cleartext<float> *>(&operand)) return std::vector<double>(p->getData().begin(), p->getData().end());
   throw std::runtime_error(std::string(op) + "(Ciphertext,Cleartext) requires a Cleartext<int>, <float> or <double> under CKKS.");
 }
+// the one number a public value stands for: every entry equal (the factory pads a short vector with its last entry), and no more
+// entries than the encoded path accepts (expandVector throws beyond `slots`: that vector stays with it, and is refused there)
+bool oneNumber(const std::vector<double> &vals, size_t slots, double &c) {
+  if (vals.empty() || vals.size() > slots) return false;
+  for (double v : vals)
+    if (!(v == vals[0])) return false;
+  c = vals[0];
+  return true;
+}
 }  // namespace
 
 HipCiphertext::Buffer::~Buffer() {
@@ -383,8 +392,21 @@ std::unique_ptr<AbstractCiphertext> HipCiphertext::multiplyPlain(const ICleartex
   r->multiplyPlainInplace(operand);
   return r;
 }
+// HipSchemeConfig::constOperands: this value plus the constant c at this value's own scale, the K = 0 form of
+// abc_hip_multiply_const_sum (component 0 only); no plaintext, no cache entry
+void HipCiphertext::addConstInplace(double c) {
+  const auto &f = getFactory();
+  uint64_t w[16];
+  abcHipCheck(abc_hip_ckks_const_words(f.context(), c, sc, nl, w), "ckks_const_words");
+  auto t = target();
+  abcHipCheck(abc_hip_multiply_const_sum(f.context(), nullptr, nullptr, nullptr, 0, w, in(), t->p, 2, nl, f.batchSize()), "multiply_const_sum");
+  f.countConstOperand();
+  adopt(std::move(t));
+}
 void HipCiphertext::addPlainInplace(const ICleartext &operand) {
   if (getFactory().isCkks()) {  // encoded at this value's own level and scale: exact scale match
+    double c;
+    if (getFactory().takesConstOperands() && oneNumber(realCleartext(operand, "ADD"), getFactory().usableSlots(), c)) return addConstInplace(c);
     const uint64_t *pl = getFactory().cachedCkksPlaintext(realCleartext(operand, "ADD"), nl, sc);
     auto t = target();
     abcHipCheck(abc_hip_add_plain(getFactory().context(), in(), pl, 0, t->p, 2, nl, getFactory().batchSize()), "add_plain");
@@ -398,6 +420,8 @@ void HipCiphertext::addPlainInplace(const ICleartext &operand) {
 }
 void HipCiphertext::subtractPlainInplace(const ICleartext &operand) {
   if (getFactory().isCkks()) {
+    double c;
+    if (getFactory().takesConstOperands() && oneNumber(realCleartext(operand, "SUB"), getFactory().usableSlots(), c)) return addConstInplace(-c);  // const_words(-c)
     const uint64_t *pl = getFactory().cachedCkksPlaintext(realCleartext(operand, "SUB"), nl, sc);
     auto t = target();
     abcHipCheck(abc_hip_sub_plain(getFactory().context(), in(), pl, 0, t->p, 2, nl, getFactory().batchSize()), "sub_plain");
@@ -421,6 +445,30 @@ void HipCiphertext::multiplyPlainInplace(const ICleartext &operand) {
       return;
     }
     const double ps = getFactory().defaultScale();
+    double c;
+    if (getFactory().takesConstOperands() && oneNumber(vals, getFactory().usableSlots(), c)) {
+      // the scalar as per-limb words, at the scale the encoded path would have used: one abc_hip_multiply_const_sum_rescale where a
+      // limb is left to drop (bookkeeping as below), the product alone at one limb; the checks throw before anything is enqueued
+      const auto &f = getFactory();
+      uint64_t w[16];
+      abcHipCheck(abc_hip_ckks_const_words(f.context(), c, ps, nl, w), "ckks_const_words");
+      checkScaleFits(sc * ps, nl);
+      const uint64_t *term = in();
+      if (nl >= 2) {
+        auto r = allocate(f, nl - 1);
+        abcHipCheck(abc_hip_multiply_const_sum_rescale(f.context(), &term, nullptr, w, 1, nullptr, nullptr, r->p, 2, nl, f.batchSize()), "multiply_const_sum_rescale");
+        sc = sc * ps / (double)f.prime(nl - 1);
+        buf = std::move(r);
+        --nl;
+      } else {
+        auto t = allocate(f, nl);  // never in place: the sum's output may not be one of its terms
+        abcHipCheck(abc_hip_multiply_const_sum(f.context(), &term, nullptr, w, 1, nullptr, nullptr, t->p, 2, nl, f.batchSize()), "multiply_const_sum");
+        adopt(std::move(t));
+        sc *= ps;
+      }
+      f.countConstOperand();
+      return;
+    }
     const uint64_t *pl = getFactory().cachedCkksPlaintext(vals, nl, ps);
     if (nl >= 2 && getFactory().fusesMultiplyPlainRescale()) {
       // product and rescale as one call: the words of the two calls below, bookkeeping as rescaleIfPossible does it; the check

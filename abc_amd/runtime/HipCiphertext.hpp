@@ -88,6 +88,7 @@ class HipCiphertext : public AbstractCiphertext, public RotateAddCapable, public
   void subtractInplace(const AbstractCiphertext &operand) override;
   std::unique_ptr<AbstractCiphertext> subtractPlain(const ICleartext &operand) const override;
   void subtractPlainInplace(const ICleartext &operand) override;
+  void addConstInplace(double c);  // HipSchemeConfig::constOperands: + c at this value's scale, by abc_hip_multiply_const_sum
   std::unique_ptr<AbstractCiphertext> rotateRows(int steps) const override;
   void rotateRowsInplace(int steps) override;
   // RotateAddCapable: *this += rotate(src, steps) as one abc_hip_rotate_add into a fresh buffer (so that the key switch can take

@@ -20,7 +20,7 @@ HipCiphertextFactory::HipCiphertextFactory(const HipSchemeConfig &cfg)
     : ciphertextSlotSize(cfg.ringDegree), keySeed(cfg.seed), batch(cfg.batch), ckksMode(cfg.ckks), ckksScale(cfg.ckksScale),
       ckksBits(cfg.ckksBits), hostCkksCodec(cfg.hostCkksCodec), fuseRotateAdd(cfg.fuseRotateAdd),
       fuseMultiplyPlainRescale(cfg.fuseMultiplyPlainRescale), lazyRelin(cfg.lazyRelinearize), fusePlainSums(cfg.fusePlainSum),
-      lazyRescale(cfg.lazyRescale) {
+      lazyRescale(cfg.lazyRescale), constOperands(cfg.constOperands) {
   if (!batch) throw std::runtime_error("HipCiphertextFactory: batch size must be at least 1");
   if (ckksMode && ckksBits.size() < 2) throw std::runtime_error("HipCiphertextFactory: a CKKS chain needs a data limb and the special prime");
   setupContext(cfg.device);

@@ -54,6 +54,12 @@ struct HipSchemeConfig {
   // sum of the products is rescaled once.  OFF by default, like lazyRelinearize: the result decrypts to the same values, with one
   // rescale rounding instead of one per product, but its words are not those of multiplyPlain per product and addInplace
   bool lazyRescale = false;
+  // CKKS plain operations whose public value is ONE number (every entry equal: `x *** 0.5`, `x +++ 3`, `x --- 0.25`) take the scalar as
+  // per-limb words in the kernel arguments (abc_hip_ckks_const_words, abc_hip_multiply_const_sum_rescale / abc_hip_multiply_const_sum):
+  // no vector is expanded, nothing is encoded, no plaintext is cached.  OFF by default, like lazyRescale: the device encoder's fp64
+  // transform may round coefficient 0 of a non-dyadic constant one unit away from const_words, so the ciphertext words are not
+  // guaranteed to be those of the encoded path (they are for dyadic values); the decoded values agree within the CKKS tolerance
+  bool constOperands = false;
 };
 
 class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapable {
@@ -114,6 +120,8 @@ class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapab
   mutable size_t plainSums = 0;  // abc_hip_bfv_multiply_plain_sum calls issued by HipCiphertext::plainSum
   bool lazyRescale = false;
   mutable size_t plainSumRescales = 0;  // abc_hip_multiply_plain_sum_rescale calls issued by HipCiphertext::plainSum
+  bool constOperands = false;
+  mutable size_t constOperandOps = 0;  // abc_hip_multiply_const_sum(_rescale) calls issued by the three plain operations of HipCiphertext
   // oldest first; the block is shared with a caller that holds it (cachedCkksPlaintextBlock), as in plainNttCache
   struct CachedCkksPlain {
     std::vector<double> values;
@@ -166,6 +174,10 @@ class HipCiphertextFactory : public AbstractCiphertextFactory, public GraphCapab
   void setLazyRescale(bool on) { lazyRescale = on; }
   [[nodiscard]] size_t plainSumRescaleCalls() const { return plainSumRescales; }
   void countPlainSumRescale() const { ++plainSumRescales; }
+  [[nodiscard]] bool takesConstOperands() const { return constOperands; }
+  void setConstOperands(bool on) { constOperands = on; }
+  [[nodiscard]] size_t constOperandCalls() const { return constOperandOps; }
+  void countConstOperand() const { ++constOperandOps; }
   [[nodiscard]] static constexpr size_t plainCacheEntries() { return kPlainCacheEntries; }
   // BFV: device plaintext [L][N], lifted and in NTT form, of public values, from the factory's cache (least recently used out
   // first).  The block lives as long as the cache or the caller holds it: hold it until the call that reads it has been enqueued

@@ -81,6 +81,8 @@ int abc_hip_ctx_reload_env(abc_hip_ctx *ctx);
 #define ABC_HIP_ROUTE_BFV_PLAIN_SUM 14 /* BFV: plainsum=fused / plainsum=ntt_domain for abc_hip_bfv_multiply_plain_sum of `count` ciphertexts */
 #define ABC_HIP_ROUTE_BFV_MATVEC_BSGS 15 /* BFV: the baby rotation's route (as ABC_HIP_ROUTE_ROTATE, out of place), the plainsum= of an inner sum, then the giant step's add=fused / add=separate; per-chunk fields and the group: those of a one-step baby list */
 #define ABC_HIP_ROUTE_PLAIN_SUM_RESCALE 16 /* CKKS, nl >= 2: the rescale's route plus sumrescale=fused / sumrescale=separate, for a sum of up to four terms over `count` size-2 ciphertexts (a longer sum is separate unless ABC_HIP_PLAIN_SUM_RESCALE_TERMS is set) */
+#define ABC_HIP_ROUTE_CONST_SUM_RESCALE 18 /* CKKS, nl >= 2: the rescale's route plus constsum=fused / constsum=separate, for a one-term sum over `count` size-2 ciphertexts at nl (more than four terms or a term above nl: separate) */
+#define ABC_HIP_ROUTE_POLY_EVAL 19 /* CKKS, nl >= 2: the mul_relin route at nl, then constsum=separate: the string answers for degree 2 and above, whose last step reads powers above its level; a degree-1 call has one term, at nl, and its last step takes what ABC_HIP_ROUTE_CONST_SUM_RESCALE says at nl (abc_hip_route has no argument for the degree) */
 #define ABC_HIP_ROUTE_DIAG_MATVEC_BSGS_RESCALE 17 /* CKKS, nl >= 2: the baby rotation's route at nl, sumrescale=, then the giant step's route at nl - 1 with add=fused / add=separate; per-chunk fields: the first group's.  Two key-switch routes in one string: 160 bytes hold any */
 int abc_hip_route(abc_hip_ctx *ctx, int op, int nl, size_t count, int in_place, char *buf, size_t cap);
 
@@ -423,6 +425,69 @@ int abc_hip_mod_switch(abc_hip_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, 
  * nothing.  Capturable, under the "run once eagerly first" rule of abc_hip_graph_begin. */
 int abc_hip_multiply_plain_rescale(abc_hip_ctx *ctx, const uint64_t *d_ct, const uint64_t *d_plain, size_t plain_stride,
                                    uint64_t *d_out, int size, int nl, size_t count);
+
+/* ---- CKKS: scalar constants and polynomial evaluation (an activation behind a linear layer) ----
+ * In NTT form the constant c at scale s is the plaintext whose every word of limb j is round(c * s) mod q_j: a scalar operand is one
+ * word per limb, and needs neither an encode (an N/2-point transform and nl NTTs) nor a plaintext of nl * N equal-per-limb words
+ * in memory.  The words: r = value * scale rounded to the nearest integer, ties away from zero; h_words[j] = r mod q_j in [0, q_j)
+ * (a negative r maps to q_j - (|r| mod q_j), 0 stays 0).  Fails, with h_words untouched, for a BFV context, a bad nl, a non-finite
+ * product or |r| >= 2^62 (the encoder's own limit).  No GPU work.  For a dyadic value * scale these are the words of
+ * abc_hip_ckks_encode on N/2 copies of the value; the encoder's fp64 transform may round coefficient 0 of another constant one
+ * unit away. */
+int abc_hip_ckks_const_words(abc_hip_ctx *ctx, double value, double scale, int nl, uint64_t *h_words);
+/* A scalar-weighted sum of ciphertexts, each term read at ITS OWN level:
+ *   d_out [count][size][nl][N] = (d_addend or 0) + const (component 0 only) + w_0 * ct_0 + ... + w_{K-1} * ct_{K-1},  size = 2 or 3.
+ * h_ct: HOST array of n_terms device pointers; ct_k is [count][size][h_ct_nl[k]][N] with h_ct_nl[k] >= nl (h_ct_nl == NULL: every
+ * term at nl) and its first nl limbs are read in place -- abc_hip_mod_switch down to nl without the copy.  h_weights [n_terms][nl]
+ * and h_const [nl] (or NULL) are HOST words as abc_hip_ckks_const_words makes them, each below its prime; everything is read
+ * during the call only, and the words travel by value in the kernel arguments, eight terms per launch, the running sum carried by
+ * pointer from launch to launch.  One pointer may appear in several terms; d_out may be exactly d_addend.  Bit-identical to, in
+ * order: abc_hip_mod_switch repeated down to nl, abc_hip_multiply_plain per term with the constant plaintext, abc_hip_add,
+ * abc_hip_add_plain for the constant.  ABC_HIP_NO_CONST_MAC_SUM=1 runs that sequence on plaintexts filled in an arena instead of
+ * the K-term kernel.  n_terms == 0 writes the addend plus the constant, or the constant over zeros; count == 0 succeeds and
+ * enqueues nothing.  Fails with nothing written or enqueued for: a BFV context, a bad level or size, h_ct_nl[k] < nl or > L,
+ * n_terms < 0, a null term pointer, a weight or constant word >= q_j, d_out overlapping any term, d_out overlapping d_addend
+ * without being equal to it.  Capturable, under the "run once eagerly first" rule of abc_hip_graph_begin. */
+int abc_hip_multiply_const_sum(abc_hip_ctx *ctx, const uint64_t *const *h_ct, const int *h_ct_nl, const uint64_t *h_weights, int n_terms,
+                               const uint64_t *h_const, const uint64_t *d_addend, uint64_t *d_out, int size, int nl, size_t count);
+/* nl >= 2: the same sum with ONE rescale behind it, d_out [count][size][nl-1][N].  Bit-identical to abc_hip_multiply_const_sum into
+ * a temporary followed by abc_hip_rescale; n_terms == 1 without addend and constant gives the words of
+ * abc_hip_multiply_plain_rescale with the constant plaintext.  Route (abc_hip_route, ABC_HIP_ROUTE_CONST_SUM_RESCALE): the
+ * rescale's route, then constsum=fused -- K-term forms of the two LDS-resident rescale kernels with the scalar weight in place of a
+ * loaded plaintext word form the sum in their loads, so it never reaches memory -- or constsum=separate -- the sum into a context
+ * arena, then the rescale.  The fused pair takes 1 .. 4 terms that all sit at level nl, on rings 2^10 .. 2^14; never N >= 2^15,
+ * ABC_HIP_NO_FUSED=1, ABC_HIP_NO_ISPLIT=1 on a chain with a prime above 2^50, ABC_HIP_NO_CONST_MAC_SUM=1, more than four terms, or a
+ * term above nl.  Within that it is the default where the measurement has it faster (at least 64 polynomials, count * size, and
+ * 2^20 coefficients among them); ABC_HIP_CONST_SUM_RESCALE_FUSED=1 / =0 force it on and off.  Refusals as above, and nl < 2, and
+ * d_out overlapping d_addend at all (the shapes differ). */
+int abc_hip_multiply_const_sum_rescale(abc_hip_ctx *ctx, const uint64_t *const *h_ct, const int *h_ct_nl, const uint64_t *h_weights,
+                                       int n_terms, const uint64_t *h_const, const uint64_t *d_addend, uint64_t *d_out, int size, int nl,
+                                       size_t count);
+/* Levels p(x) of degree `degree` consumes: ceil(log2 degree) + 1; -1 for degree < 1. */
+int abc_hip_ckks_poly_eval_depth(int degree);
+/* p(x) = c_0 + c_1 x + ... + c_d x^d on d_x [count][2][nl][N] at scale x_scale; h_coeffs [degree + 1], c_0 first;
+ * d_out [count][2][nl - depth][N] at scale out_scale.  The sequence is FIXED (tests/poly_eval_spec.py restates it on the oracle):
+ *   x^1 = x: level(1) = nl, scale(1) = x_scale.  For k = 2 .. d: e = ceil(log2 k), h = 2^(e-1), l = k - h,
+ *   x^k = rescale( mul_relin( x^h, mod_switch(x^l down to nl - e + 1 limbs) ) ), level(k) = nl - e,
+ *   scale(k) = scale(h) * scale(l) / q_{nl-e}, tracked in doubles on the host (a power of two is a square).
+ *   A power that no non-zero coefficient and no later power needs is skipped, and a term with a zero coefficient is left out of
+ *   the sum: no output word changes.
+ *   E = ceil(log2 d) (0 for d = 1), m = nl - E;  W_k = const_words(c_k, out_scale * q_{m-1} / scale(k), m),
+ *   W_0 = const_words(c_0, out_scale * q_{m-1}, m);  the output is ONE abc_hip_multiply_const_sum_rescale at level m over
+ *   k = 1 .. d with h_ct_nl[k] = level(k): every term lands at out_scale after the one rescale, at level m - 1.
+ * abc_hip_ckks_const_words holds every weight below 2^62; the constant term enters at out_scale * q_{m-1}, so
+ * |c_0| * out_scale * q_{m-1} < 2^62 is required: 30-bit rescaling primes at scale 2^30, or a smaller out_scale on wider ones.
+ * The powers live in a context arena; the batch is walked in groups of ciphertexts that keep THAT arena within 4 GiB (the rule of
+ * abc_hip_mul_sum_relin; with ABC_HIP_CHUNK=c exactly c * lanes); three more arenas hold one ciphertext per member of the group
+ * each: the lowered factor, the product before its rescale, and the last step's sum.  count == 0 succeeds and enqueues nothing.  Fails with nothing
+ * written for: a BFV context, degree < 1 or > 31, nl < E + 2, a non-finite or non-positive scale, a non-finite coefficient, a
+ * weight past 2^62, no relinearisation key, d_out overlapping d_x.  Route (ABC_HIP_ROUTE_POLY_EVAL): the abc_hip_mul_relin route at
+ * nl, then constsum=separate -- for degree 2 and above, whose last step reads powers held above its level; at degree 1 the one term
+ * sits at nl and the last step follows ABC_HIP_ROUTE_CONST_SUM_RESCALE at nl (fused from 64 polynomials on).  Capturable under the run-once rule; the recorded kernels hold the weights by value.
+ * NOT in it: Paterson-Stockmeyer; folding the coefficients into the last multiplication to save the extra level; Chebyshev
+ * bases; products batched across powers or through abc_hip_mul_sum_relin. */
+int abc_hip_ckks_poly_eval(abc_hip_ctx *ctx, const uint64_t *d_x, double x_scale, const double *h_coeffs, int degree, double out_scale,
+                           uint64_t *d_out, int nl, size_t count);
 
 /* ---- HIP-graph capture of an operation sequence (a recorded circuit in place of the
  * eager per-call dispatch of SpecialRuntimeVisitor, src/runtime/RuntimeVisitor.cpp:40-159).

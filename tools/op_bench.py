@@ -756,6 +756,163 @@ def single_ops(res, only, rng):
         g.close()
 
 
+def const_sum_ab(res, only, rng):
+    """sum over K terms of c_k * ct_k for scalar constants c_k, alternating in one process, five runs each:
+    (a) `composed`: K x abc_hip_multiply_plain and K - 1 x abc_hip_add on pre-filled constant plaintexts ([nl][N], every word of a limb equal);
+    (b) `plain_sum`: abc_hip_multiply_plain_sum on the same plaintexts;
+    (c) `const_sum`: abc_hip_multiply_const_sum, the weights in the kernel arguments;
+    and with one rescale behind the sum: (d) `plain_sum_rescale`: abc_hip_multiply_plain_sum_rescale on the plaintexts, as its route sends
+    it; then abc_hip_multiply_const_sum_rescale three ways: (e) `csr_separate` under ABC_HIP_CONST_SUM_RESCALE_FUSED=0, (f) `csr_fused`
+    under =1 (separate all the same beyond four terms and at N = 2^15), (g) `csr_default`, as route_const_sum_rescale sends it (the rule
+    these numbers gave).
+    The K ciphertext operands are distinct buffers (device copies of one random batch: the kernels have no data-dependent path)."""
+    shapes = [  # tag, context, levels, batches
+        ("ckks14", lambda: capi.Context(capi.CKKS, 16384, capi.create_primes(16384, [50, 40, 40, 40, 50])), (4, 3), (512, 128, 64, 32)),
+        ("ckks15", lambda: capi.Context(capi.CKKS, 32768, capi.create_primes(32768, [50, 40, 40, 50])), (3,), (256,)),
+        ("ckks12", lambda: capi.Context(capi.CKKS, 4096, capi.create_primes(4096, [50, 40, 40, 50])), (3,), (1024, 128)),
+    ]
+    kinds = ("composed", "plain_sum", "const_sum", "plain_sum_rescale", "csr_separate", "csr_fused", "csr_default")
+    u64p = C.POINTER(C.c_uint64)
+    for tag, make, levels, batches in shapes:
+        if only and only not in "%s_const_sum" % tag and "const_sum" not in only:
+            continue
+        g = make()
+        for nl in levels:
+            for B in batches:
+                cb, zero = C.c_size_t(B), C.c_size_t(0)
+                first, nb = rand_ct(g, rng, B, 2, nl)
+                pool = [first]
+                for _ in range(15):
+                    pool.append(g.alloc(nb))
+                    g.op("memcpy_d2d", pool[-1].ptr, first.ptr, C.c_size_t(nb))
+                w = np.stack([g.const_words(v, 2.0 ** 40, nl) for v in rng.uniform(-1, 1, 16)])
+                plains = [g.upload(np.ascontiguousarray(np.repeat(w[k][:, None], g.n, axis=1))) for k in range(16)]
+                tmp, out = g.alloc(nb), g.alloc(nb)
+                for K in (1, 2, 4, 8, 16):
+                    names = ["%s_L%d_b%d_const_sum_K%d_%s" % (tag, nl, B, K, kind) for kind in kinds]
+                    if not any(only in k for k in names):
+                        continue
+                    pc, pp = g.term_pointers([x.ptr for x in pool[:K]]), g.term_pointers([x.ptr for x in plains[:K]])
+                    wk = np.ascontiguousarray(w[:K])
+                    wp = wk.ctypes.data_as(u64p)
+
+                    def composed():
+                        g.op("multiply_plain", pool[0].ptr, plains[0].ptr, zero, out.ptr, 2, nl, cb)
+                        for k in range(1, K):
+                            g.op("multiply_plain", pool[k].ptr, plains[k].ptr, zero, tmp.ptr, 2, nl, cb)
+                            g.op("add", out.ptr, tmp.ptr, out.ptr, 2, nl, cb)
+
+                    def plain_sum():
+                        g.op("multiply_plain_sum", pc, pp, zero, K, None, out.ptr, 2, nl, cb)
+
+                    def const_sum():
+                        g.op("multiply_const_sum", pc, None, wp, K, None, None, out.ptr, 2, nl, cb)
+
+                    def plain_sum_rescale():
+                        g.op("multiply_plain_sum_rescale", pc, pp, zero, K, None, out.ptr, 2, nl, cb)
+
+                    def const_sum_rescale():
+                        g.op("multiply_const_sum_rescale", pc, None, wp, K, None, None, out.ptr, 2, nl, cb)
+                    routes = ("composed", "macsum=kernel", "constmac=kernel", g.route("plain_sum_rescale", nl, B) + (" (more than four terms: separate)" if K > 4 else ""))
+                    reps = 10 if B * K >= 256 else 50
+                    _rounds(g, res, names[:4], (composed, plain_sum, const_sum, plain_sum_rescale), routes, B, reps)
+                    key = "ABC_HIP_CONST_SUM_RESCALE_FUSED"
+                    _env_rounds(g, res, names[4:], (const_sum_rescale,) * 3, ({key: "0"}, {key: "1"}, {}), "const_sum_rescale", nl, B, reps)
+                    med = lambda i: res[names[i]]["ms_median"]  # noqa: E731
+                    print("    plain_sum / const_sum: %.2f;  csr_separate / csr_fused: %.2f;  csr_separate / csr_default: %.2f;  plain_sum_rescale / csr_default: %.2f%s" % (
+                        med(1) / med(2), med(4) / med(5), med(4) / med(6), med(3) / med(6), "  (K > 4: every csr row is separate)" if K > 4 else ""), flush=True)
+                del pool, first, plains, tmp, out
+        g.close()
+
+
+def poly_eval_ab(res, only, rng):
+    """c_0 + c_1 x + ... + c_d x^d at N = 2^14 on {50,40,40,40,40,40 | 50}, degree 3 and 7, alternating in one process, five runs each:
+    (a) `composed`: the calls a caller writes today on pre-encoded constant plaintexts -- abc_hip_mul_relin, abc_hip_rescale and
+        abc_hip_mod_switch per power; abc_hip_multiply_plain, abc_hip_rescale, abc_hip_mod_switch and abc_hip_add per term; abc_hip_add_plain;
+    (b) `composed_encode`: the same with the d + 1 abc_hip_ckks_encode calls of the constant vectors in the timed region;
+    (c) `poly_eval`: abc_hip_ckks_poly_eval.
+    x at 2^40, the result at 2^20 (the constant term enters at out_scale * q_{m-1} < 2^62); the timings do not depend on the values."""
+    if only and "poly_eval" not in only:
+        return
+    n, bits, B = 16384, [50, 40, 40, 40, 40, 40, 50], 128
+    g = capi.Context(capi.CKKS, n, capi.create_primes(n, bits))
+    g.keygen(5)
+    L, N, cb, zero = g.L, g.n, C.c_size_t(B), C.c_size_t(0)
+    xs, outs = 2.0 ** 40, 2.0 ** 20
+    x, nb = rand_ct(g, rng, B, 2, L)
+
+    def ceil_log2(k):
+        e = 0
+        while (1 << e) < k:
+            e += 1
+        return e
+    for d in (3, 7):
+        names = ["ckks14_L%d_b%d_poly_eval_d%d_%s" % (L, B, d, kind) for kind in ("composed", "composed_encode", "poly_eval")]
+        if not any(only in k for k in names):
+            continue
+        coeffs = [float(v) for v in rng.uniform(-1, 1, d + 1)]
+        level, scale, hi, lo = [L] * (d + 1), [xs] * (d + 1), [0] * (d + 1), [0] * (d + 1)
+        for k in range(2, d + 1):
+            e = ceil_log2(k)
+            hi[k], lo[k], level[k] = 1 << (e - 1), k - (1 << (e - 1)), L - e
+            scale[k] = scale[hi[k]] * scale[lo[k]] / g.primes[L - e]
+        m = L - ceil_log2(d)
+        pw = {1: x}
+        for k in range(2, d + 1):
+            pw[k] = g.alloc(nb)
+        sa, sb, acc = g.alloc(nb), g.alloc(nb), g.alloc(nb)
+        slots = g.upload(np.stack([np.full(N // 2, c) for c in coeffs]))  # the expanded constant vectors, [d + 1][N / 2] doubles
+        plain = [g.alloc(L * N * 8) for _ in range(d + 1)]
+        pscale = [outs] + [outs * g.primes[level[k] - 1] / scale[k] for k in range(1, d + 1)]
+        plevel = [m - 1] + [level[k] for k in range(1, d + 1)]
+
+        def encode():
+            for k in range(d + 1):
+                g.op("ckks_encode", C.c_void_p(slots.ptr.value + k * (N // 2) * 8), None, C.c_size_t(N // 2), C.c_double(pscale[k]), plevel[k],
+                     plain[k].ptr, C.c_size_t(1))
+
+        def lower(src, frm, to):
+            """mod_switch src from `frm` limbs down to `to` through sa / sb; the buffer that holds the result"""
+            dst = sa
+            while frm > to:
+                g.op("mod_switch", src.ptr, dst.ptr, 2, frm, cb)
+                src, dst, frm = dst, (sb if dst is sa else sa), frm - 1
+            return src
+
+        def composed():
+            for k in range(2, d + 1):
+                lk = level[k] + 1
+                b = lower(pw[lo[k]], level[lo[k]], lk)
+                g.op("mul_relin", pw[hi[k]].ptr, b.ptr, acc.ptr, lk, cb)
+                g.op("rescale", acc.ptr, pw[k].ptr, 2, lk, cb)
+            for k in range(1, d + 1):
+                g.op("multiply_plain", pw[k].ptr, plain[k].ptr, zero, sa.ptr, 2, level[k], cb)
+                g.op("rescale", sa.ptr, sb.ptr, 2, level[k], cb)
+                t = sb
+                for frm in range(level[k] - 1, m - 1, -1):
+                    u = sa if t is sb else sb
+                    g.op("mod_switch", t.ptr, u.ptr, 2, frm, cb)
+                    t = u
+                if k == 1:
+                    g.op("memcpy_d2d", acc.ptr, t.ptr, C.c_size_t(B * 2 * (m - 1) * N * 8))
+                else:
+                    g.op("add", acc.ptr, t.ptr, acc.ptr, 2, m - 1, cb)
+            g.op("add_plain", acc.ptr, plain[0].ptr, zero, acc.ptr, 2, m - 1, cb)
+
+        def composed_encode():
+            encode()
+            composed()
+        co = (C.c_double * (d + 1))(*coeffs)
+        out = g.alloc(nb)
+
+        def poly_eval():
+            g.op("ckks_poly_eval", x.ptr, C.c_double(xs), co, d, C.c_double(outs), out.ptr, L, cb)
+        encode()
+        route = g.route("poly_eval", L, B)
+        _rounds(g, res, names, (composed, composed_encode, poly_eval), ("composed", "composed", route), B, 5)
+    g.close()
+
+
 def main():
     # --only SUBSTRING: the entries whose name contains it (the contexts of single_ops are still created)
     only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else ""
@@ -765,7 +922,7 @@ def main():
     # runs nothing else (and sets up no other context), and a filter that does not say "bfv_" -- `--only matvec_bsgs` -- leaves them out
     bfv_sums = any(x in only for x in ("bfv_plain_sum", "bfv_matvec_bsgs"))
     if not bfv_sums:
-        if not (only and any(x in only for x in ("mul_sum", "plain_mac_sum", "matvec_bsgs", "plain_sum_rescale"))):  # those A/Bs have their own contexts and operand batches: nothing else is set up
+        if not (only and any(x in only for x in ("mul_sum", "plain_mac_sum", "matvec_bsgs", "plain_sum_rescale", "const_sum", "poly_eval"))):  # those A/Bs have their own contexts and operand batches: nothing else is set up
             single_ops(res, only, rng)
         rotate_add_ab(res, only, rng)
         rotate_mac_ab(res, only, rng)
@@ -777,6 +934,8 @@ def main():
             matvec_bsgs_ab(res, only, rng)
         matvec_bsgs_rescale_ab(res, only, rng)
         keyswitch_batch1(res, only, rng)
+        const_sum_ab(res, only, rng)
+        poly_eval_ab(res, only, rng)
     if not only or "bfv_" in only:
         bfv_plain_sum_ab(res, only, rng)
         bfv_matvec_bsgs_ab(res, only, rng)
