@@ -4,7 +4,8 @@ The reference has no CKKS code at all (ref:src/runtime/Seal
 this follows the published CKKS encoding with SEAL's slot order: slot i <-> evaluation at zeta^(3^i), zeta = exp(i*pi/N),
 conjugates at zeta^(-3^i).  It produces / consumes COEFFICIENT-form residues [nl][N]; the device turns them into the NTT form
 ciphertexts and plaintexts travel in (abc_hip_ntt_limbs).  Floating point: values agree with any other CKKS encoder to
-rounding error, not bit-for-bit.
+rounding error, not bit-for-bit.  Coefficients are rounded to the nearest integer, ties away from zero (SEAL's rule and the
+device encoder's, include/abc_hip.h at abc_hip_ckks_encode).
 """
 import numpy as np
 
@@ -32,7 +33,8 @@ def encode(values, scale, n, primes):
     coef = (np.fft.fft(w) * np.exp(-1j * np.pi * k / n)).real / n * scale
     if np.abs(coef).max() >= 2.0 ** 62:
         raise ValueError("scale too large for 64-bit coefficient rounding")
-    r = np.rint(coef).astype(np.int64)
+    r = np.trunc(coef)  # nearest, ties away from zero; not floor(coef + 0.5), which takes 0.49999999999999994 to 1
+    r = (r + np.sign(coef) * (np.abs(coef - r) >= 0.5)).astype(np.int64)
     out = np.empty((len(primes), n), dtype=np.uint64)
     for j, q in enumerate(primes):
         out[j] = np.mod(r, q).astype(np.uint64)  # python-style mod: result in [0, q)

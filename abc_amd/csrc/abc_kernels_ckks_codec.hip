@@ -25,7 +25,7 @@
 // built on the host in long double and uploaded once per context, on first use.
 //
 // Encode fusions: the first load gathers the slots (zero beyond values_per_row); the last store applies twist x scale / M,
-// rint, the |c| < 2^62 range flag (one word, read back once per call) and the reduction into every limb, writing coefficient
+// rounding (ties away from zero), the |c| < 2^62 range flag (one word, read back once per call) and the reduction into every limb, writing coefficient
 // form; the existing forward NTT launcher then brings the plaintext into NTT form.
 // Decode fusions: the existing inverse NTT runs into scratch; the first load does the Garner digits (per-limb constants), a
 // multi-word Horner, the compare with Q/2 of the level (exact centred lift of any residue vector), the conversion to double,
@@ -179,7 +179,7 @@ struct SrcSlots {
   }
 };
 
-// encode, last store: twist, scale / M, rint, range flag, reduction into every limb (coefficient form, [count][nl][N])
+// encode, last store: twist, scale / M, round (ties away from zero), range flag, reduction into every limb (coefficient form, [count][nl][N])
 struct DstCoef {
   DevCtx c;
   u64 *plain;
@@ -189,7 +189,7 @@ struct DstCoef {
   const cplx *zeta;
   int *flag;
   __device__ void put(u64 *o, double x) const {
-    const double r = __builtin_rint(x);
+    const double r = __builtin_round(x);  // nearest, ties away from zero (abc_hip.h; abc_hip_ckks_const_words' rule)
     u64 mag = 0;
     bool neg = false;
     if (__builtin_fabs(r) < 0x1p62) {  // also false for NaN

@@ -5,7 +5,8 @@
 // HAVE_SEAL_CKKS hook), so this follows the published encoding with SEAL's slot order: slot i <-> evaluation at
 // zeta^(3^i), zeta = exp(i pi / N), conjugates at zeta^(-3^i).  It produces / consumes COEFFICIENT-form residues [nl][N];
 // the device turns them into the NTT form ciphertexts and plaintexts travel in (abc_hip_ntt_limbs).  Floating point: off
-// the hot path, agrees with any other CKKS encoder to rounding error, not bit for bit.
+// the hot path, agrees with any other CKKS encoder to rounding error, not bit for bit.  Coefficients are rounded to the nearest
+// integer, ties away from zero (SEAL's rule and the device encoder's, include/abc_hip.h at abc_hip_ckks_encode).
 #pragma once
 
 #include <cmath>
@@ -91,7 +92,7 @@ class CkksEncoder {
     for (size_t k = 0; k < n; k++) {
       const double c = (w[k] * twist[k]).real() / (double)n * scale;
       if (!(std::fabs(c) < 4.6e18)) throw std::runtime_error("CKKS encode: scale too large for 64-bit coefficient rounding");
-      const int64_t r = (int64_t)std::llrint(c);
+      const int64_t r = (int64_t)std::llround(c);  // ties away from zero, as abc_hip_ckks_encode and abc_hip_ckks_const_words
       for (int j = 0; j < nl; j++) {
         const int64_t q = (int64_t)primes[j];
         int64_t v = r % q;

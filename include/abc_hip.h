@@ -142,7 +142,9 @@ int abc_hip_batch_decode(abc_hip_ctx *ctx, const uint64_t *d_plain, int64_t *d_v
  * ABC_HIP_SCHEME_CKKS): d_re / d_im (d_im may be NULL = real slots) [count][values_per_row] doubles, values_per_row <= N/2,
  * the rest of the N/2 slots zero -> d_plain [count][nl][N], NTT form (ready for abc_hip_encrypt / *_plain), limb j modulo q_j.
  * Slot i is the evaluation at zeta^(3^i), zeta = exp(i pi / N) (the order of runtime/CkksEncoder.hpp).  Coefficients are rounded to the
- * nearest integer; one reaching 2^62 in magnitude fails the call (non-zero status).  Reads one word back: not capturable. */
+ * nearest integer, ties away from zero (SEAL's rule, the one of abc_hip_ckks_const_words and of both host encoders: 0.5 -> 1,
+ * -0.5 -> -1, 2.5 -> 3); one reaching 2^62 in magnitude after rounding, or a value that is not finite, fails the call with status 2.
+ * Reads one word back: not capturable. */
 int abc_hip_ckks_encode(abc_hip_ctx *ctx, const double *d_re, const double *d_im, size_t values_per_row, double scale,
                         int nl, uint64_t *d_plain, size_t count);
 /* CKKS counterpart of seal::BatchEncoder::decode (SealCiphertextFactory.cpp:151; no reference CKKS implementation):

@@ -1,9 +1,18 @@
 """Product-side CKKS encoder (abc_amd/ckks_encoder.py, numpy) against the oracle's independent C encoder.
-Floating point: coefficients may differ by a rounding unit, decoded values agree to ~1e-9 (tolerance stated here)."""
+Floating point: coefficients may differ by a rounding unit, decoded values agree to ~1e-9 (tolerance stated here).
+Against the exact reference of tests/ckks_codec_spec.py the encoder is held word for word wherever that reference is farther from a
+tie than fp64 can blur, and both host encoders (this one and runtime/CkksEncoder.hpp) to the tie rule: away from zero."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
 from abc_amd import ckks_encoder as ce
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import ckks_codec_spec as spec  # noqa: E402
 
 
 def test_encode_decode_agree_with_oracle(oracle_mod):
@@ -29,6 +38,61 @@ def test_short_and_real_inputs():
     back = ce.decode(ce.encode(v, 2.0 ** 30, n, primes), 2.0 ** 30, n, primes)
     assert np.abs(back[:3] - np.array(v)).max() < 1e-6
     assert np.abs(back[3:]).max() < 1e-6
+
+
+def test_encoder_equals_the_exact_reference():
+    """against tests/ckks_codec_spec.py (long double, ties away from zero) at N = 2^12: every coefficient at scale 2^20, where the
+    reference has none within the margin of a tie; at scale 2^40 every one farther from a tie than the margin (8 x the fp64 error
+    the spec measures on itself), the rest within one unit"""
+    logn, n = 12, 4096
+    primes = [1125899906826241, 1099511480321, 1099511590913]  # residues only: any primes do
+    for cplx in (False, True):
+        for short in (False, True):
+            v, want, dist = spec.encode_case_reference(logn, cplx, short, 20)
+            assert dist.min() > spec.encode_margin(logn, 20)
+            _, res, _ = spec.encode_exact(v, 2.0 ** 20, n, primes)
+            assert np.array_equal(ce.encode(v, 2.0 ** 20, n, primes), res)
+            v, want, dist = spec.encode_case_reference(logn, cplx, short, 40)
+            got, Q = spec.crt_centred(ce.encode(v, 2.0 ** 40, n, primes), primes)
+            d = np.array([abs(int(a) - int(b)) for a, b in zip(got, want)])
+            near = dist <= spec.encode_margin(logn, 40)
+            assert near.mean() < 5e-3
+            assert not d[~near].any()
+            assert d.max() <= 1
+
+
+TIES = [(0.5, 1.0, 1), (-0.5, 1.0, -1), (1.5, 1.0, 2), (2.5, 1.0, 3), (-2.5, 1.0, -3), (2.0 ** 40 + 0.5, 1.0, 2 ** 40 + 1),
+        (0.5 * 2.0 ** -40, 2.0 ** 40, 1)]
+
+
+@pytest.mark.parametrize("value,scale,want", TIES)
+@pytest.mark.parametrize("n", [1024, 32768])
+def test_ties_round_away_from_zero(n, value, scale, want):
+    """a constant slot vector c makes coefficient 0 exactly c * scale, and the slots +-i c (+ for even i) are those of
+    c X^(N/2): ties the encoder takes away from zero, as abc_hip_ckks_encode and abc_hip_ckks_const_words do"""
+    primes = [1152921504606830593, 1099511480321]
+    sign = np.where(np.arange(n // 2) % 2 == 0, 1.0, -1.0)
+    for pos, slots in ((0, np.full(n // 2, value, complex)), (n // 2, 1j * value * sign)):
+        got, _ = spec.crt_centred(ce.encode(slots, scale, n, primes), primes)
+        expect = np.zeros(n, dtype=object)
+        expect[pos] = want
+        assert list(got) == list(expect)
+
+
+def test_just_below_a_tie_rounds_down():
+    """0.49999999999999994 is not a tie: floor(x + 0.5) would take it to 1"""
+    n = 1024
+    got, _ = spec.crt_centred(ce.encode(np.full(n // 2, 0.49999999999999994), 1.0, n, [1099511480321]), [1099511480321])
+    assert not any(got)
+
+
+def test_cpp_encoder_ties():
+    """the same constants through runtime/CkksEncoder.hpp (tests/cpp/test_ckks_encoder_ties.cpp, host only)"""
+    rt = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "abc_amd", "runtime")
+    subprocess.check_call(["make", "-C", rt, "test_ckks_encoder_ties"], stdout=subprocess.DEVNULL)
+    p = subprocess.run([os.path.join(rt, "test_ckks_encoder_ties")], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stdout + p.stderr
+    assert " 0 failed" in p.stdout
 
 
 @pytest.mark.gpu

@@ -33,7 +33,7 @@ def contexts(oracle_mod, capi):
 
 
 def _grid():
-    for logn in (12, 13, 14, 15, 16):
+    for logn in (10, 11, 12, 13, 14, 15, 16):
         for name, bits in CHAINS.items():
             yield pytest.param(1 << logn, bits, id="N%d-%s" % (1 << logn, name))
     yield pytest.param(1 << 16, [60, 50, 50, 50, 50, 50, 50, 50, 60], id="N65536-8limbs")
