@@ -1,7 +1,8 @@
 // abc_buffers.hip -- the driver side of the buffer table (abc_buffers.hpp): the caching allocator behind abc_hip_malloc /
 // abc_hip_free, the lifetime of recorded circuits (abc_hip_graph_*), the scratch arenas and the mirrors of key-switching keys.
 // Every device buffer a recorded circuit may have baked into its kernel arguments is entered here and leaves here; the table
-// decides who owns what, this file calls hipMalloc / hipFree.  Table calls are made under alloc_mu.
+// decides who owns what, this file calls hipMalloc / hipFree.  Table calls are made under alloc_mu.  Under ABC_HIP_POISON=1 (debug)
+// it also fills what it hands out -- caller blocks and scratch arenas, never keys or their mirrors -- with 0xFF bytes (poison_fill).
 #include "../../include/abc_hip.h"
 
 #include "abc_context.hpp"
@@ -27,6 +28,20 @@ static void free_all(const std::vector<void *> &ptrs) {
 // abc_hip_trim, when the cap is reached, and whenever a hipMalloc of this context fails.
 // (hipMallocAsync / hipFreeAsync were tried first and returned wrong results on some boxes of this pool when two contexts
 // alternated -- analysis in DESIGN.md section 4b; ABC_HIP_SYNC_ALLOC=1 turns the cache off.)
+// ABC_HIP_POISON=1 (debug): every block handed out -- a cache hit and a fresh hipMalloc alike -- and the scratch arenas, when they
+// grow and when an outermost C-ABI operation begins, are filled with 0xFF bytes on the context's stream, so that a kernel which
+// leaves output unwritten or reads scratch it never wrote cannot find a previous call's words there.  Nothing is filled while a
+// capture is open (a recording gains no memset node), and keys and key mirrors are never filled.
+
+static int poison_fill(abc_hip_ctx *c, void *p, size_t bytes) {
+  if (!c->poison || !p || !bytes || c->buffers.capturing || capturing(c)) return 0;
+  ABC_HIP_CHECK(hipMemsetAsync(p, 0xFF, bytes, c->stream));
+  return 0;
+}
+void poison_arenas(abc_hip_ctx *c) {
+  (void)poison_fill(c, c->ws, c->ws_bytes);
+  for (int i = 0; i < 7; i++) (void)poison_fill(c, c->aux[i], c->aux_bytes[i]);
+}
 
 // Give every cached block back to the driver.  The stream is drained first: a cached block may still be read by work that was
 // enqueued before it was freed.
@@ -51,7 +66,7 @@ int buffer_malloc(abc_hip_ctx *c, void **d_ptr, size_t bytes) {
   if (c->cache_alloc) {
     std::lock_guard<std::mutex> lock(c->alloc_mu);
     const BufferTable::Take t = c->buffers.take(bytes, d_ptr);
-    if (t == BufferTable::Take::hit) return 0;
+    if (t == BufferTable::Take::hit) return poison_fill(c, *d_ptr, bytes);
     if (t == BufferTable::Take::refused) {
       set_error("allocation during graph capture found no cached buffer: run the sequence once eagerly first");
       return 1;
@@ -62,7 +77,7 @@ int buffer_malloc(abc_hip_ctx *c, void **d_ptr, size_t bytes) {
     std::lock_guard<std::mutex> lock(c->alloc_mu);
     c->buffers.add_block(*d_ptr, bytes);
   }
-  return 0;
+  return poison_fill(c, *d_ptr, bytes);
 }
 int buffer_free(abc_hip_ctx *c, void *d_ptr) {
   if (!d_ptr) return 0;
@@ -118,7 +133,7 @@ static int ensure_arena(abc_hip_ctx *c, void **buf, size_t *have, size_t bytes, 
   }
   ABC_HIP_CHECK(alloc_context_buffer(c, buf, bytes + headroom, true));
   *have = bytes + headroom;
-  return 0;
+  return poison_fill(c, *buf, *have);
 }
 int ensure_workspace(abc_hip_ctx *c, size_t bytes) { return ensure_arena(c, &c->ws, &c->ws_bytes, bytes, bytes / 8); }
 int ensure_aux(abc_hip_ctx *c, int which, size_t bytes) { return ensure_arena(c, &c->aux[which], &c->aux_bytes[which], bytes, 0); }

@@ -917,10 +917,22 @@ struct OpRange {
     if (on) roctx().pop();
   }
 };
+// the one place every C-ABI entry passes: the outermost one of a call poisons the scratch arenas (ABC_HIP_POISON=1); a composite
+// call that re-enters the C ABI is deeper and keeps what it has built there
+struct OpDepth {
+  abc_hip_ctx *c;
+  explicit OpDepth(abc_hip_ctx *c_) : c(c_ && c_->poison ? c_ : nullptr) {
+    if (c && c->op_depth++ == 0 && hipSetDevice(c->device) == hipSuccess) poison_arenas(c);
+  }
+  ~OpDepth() {
+    if (c) c->op_depth--;
+  }
+};
 }  // namespace abc
 
 #define CTX_GUARD(c)                                   \
   abc::OpRange abc_op_range_(__func__);                \
+  abc::OpDepth abc_op_depth_(c);                       \
   do {                                                 \
     if (!(c)) { set_error("null context"); return 1; } \
     if (hipSetDevice((c)->device) != hipSuccess) { set_error("hipSetDevice failed"); return 1; } \
@@ -1059,6 +1071,7 @@ int abc_hip_ctx_create(int scheme, int logn, const uint64_t *primes, int nprimes
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) c->buffers.cache_cap = total_b / 4;  // at most a quarter of the device
   }
+  if (!rc) c->poison = env_on("ABC_HIP_POISON");
   if (rc) { abc_hip_ctx_destroy(c); return 1; }
   *out = c;
   return 0;

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <map>
 #include <mutex>
 #include <unordered_map>
@@ -168,6 +169,11 @@ struct abc_hip_ctx {
   // workspace, arenas, keys, key mirrors -- and the graphs that own it: one table, one rule (abc_buffers.hpp), driven by
   // abc_buffers.hip.  cache_alloc: abc_hip_free recycles blocks through the table's cache (off: ABC_HIP_SYNC_ALLOC=1).
   bool cache_alloc = false;
+  // ABC_HIP_POISON=1 (debug, read when the context is created): every block abc_hip_malloc hands out, and the scratch arenas when
+  // they grow and when an outermost C-ABI operation begins (op_depth: a composite call that re-enters the C ABI keeps its
+  // intermediate state), are filled with 0xFF bytes -- no residue as a u64, a NaN as a double (abc_buffers.hip)
+  bool poison = false;
+  std::atomic<int> op_depth{0};
   mutable std::mutex alloc_mu;  // guards `buffers`
   abc::BufferTable buffers;
   bool behz_fp = false;  // BFV: 50-bit BEHZ auxiliary base and fp64 base-conversion kernels
@@ -286,6 +292,9 @@ void free_buffers(abc_hip_ctx *c);       // abc_hip_ctx_destroy: everything the 
 // workspace / arena `which`: grow on demand (never inside a timed region after warm-up, never inside a capture)
 int ensure_workspace(abc_hip_ctx *c, size_t bytes);
 int ensure_aux(abc_hip_ctx *c, int which, size_t bytes);
+// ABC_HIP_POISON=1: 0xFF over the workspace and every arena on c->stream (nothing while a capture is open); OpDepth calls it when
+// an outermost C-ABI operation begins
+void poison_arenas(abc_hip_ctx *c);
 // hipMalloc of a context buffer (a key, a mirror, an arena), entered into the table; retry: flush the cache once on failure
 hipError_t alloc_context_buffer(abc_hip_ctx *c, void **p, size_t bytes, bool retry);
 // free context buffer p, or hold it back while a live graph owns it; the caller has drained c->stream

@@ -654,6 +654,23 @@ def fused_cases(seed, max_logn, max_cases=0):
             yield case
 
 
+def prefill_outputs(capi):
+    """The GPU side of every case allocates its outputs through Context.alloc (inputs go through upload): from here on each such
+    buffer starts as tests/footprint.py's sentinel -- no residue of any prime, different in every word -- instead of whatever the
+    block held, so an output word the call leaves unwritten cannot equal the oracle's by being the previous case's.  Host side only:
+    no draw and no recorded case changes."""
+    import ctypes as C
+    import footprint
+    plain_alloc = capi.Context.alloc
+
+    def alloc(self, nbytes):
+        buf = plain_alloc(self, nbytes)
+        fill = footprint.sentinel_words(0, (buf.nbytes + 7) // 8)
+        capi._chk(capi.lib().abc_hip_memcpy_h2d(self.h, buf.ptr, fill.ctypes.data_as(C.c_void_p), C.c_size_t(buf.nbytes)))
+        return buf
+    capi.Context.alloc = alloc
+
+
 def dry_run(a, om):
     """draw and validate, no library and no GPU: the summary a test reads to see what a campaign covers"""
     out = {"family": a.family, "cases": 0, "skipped": 0, "contexts": 0, "referenced": 0}
@@ -724,6 +741,7 @@ def main(argv=None):
         return dry_run(a, om)
     import oracle_py as om
     from abc_amd import capi
+    prefill_outputs(capi)
     if a.case:
         case = json.loads(a.case)
         for kv in filter(None, a.also.split(",")):
